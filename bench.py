@@ -8,7 +8,8 @@ ONT-profile reads, seed_len 20, thres 300 (reference defaults), GACT T=320 O=120
 
   python bench.py --gpus N --steps K --warmup W        (N>1: launched under torch.distributed.run)
 
-Rank 0 prints ONE JSON line:
+Rank 0 prints ONE JSON line on stdout, short enough for a log tail (compact_record(): the figures below without the
+per-kernel tables, the per-leg details and the notes); --record FILE writes the full record:
   value / value_hbm_resident   HBM-resident rate of the timed steps (the contract's `value`)
   value_pcie_inclusive         SURVEY 8(d)'s metric: the same batches through the drop-in boundary on CALLER buffers --
                                H2D of the reads and D2H of every result inside the timed region; details in
@@ -27,6 +28,9 @@ Rank 0 prints ONE JSON line:
   grch38           the same measurement on the north-star configuration (GRCh38-sized text, 3.1 Gbp, 100 k x 10 kbp ONT
                    reads per step, one GPU) from a fresh child process, when the host has the memory for the index build
   kernels / isolated.kernels   per-kernel tables of the timed (overlapped) region and of the replay
+
+--dump-outputs DIR writes what the last timed step handed its caller as DIR/<name>.npy (dump_outputs()): the workload is
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import gc
@@ -35,6 +39,7 @@ import os
 import resource
 import subprocess
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -123,6 +128,81 @@ def load_pmc_summary(args, n, Lr):
         return None, None
 
 
+DUMP_BYTES = 64_000_000      # --dump-outputs writes at most this much
+
+
+def dump_plan(n, stride, store_stride):
+    """The reads --dump-outputs keeps: (those whose per-read fields are written, those whose op bytes and read rows are).
+    Every read where the budget allows it, else a fixed seeded sample in ascending order."""
+    rng = np.random.default_rng(0)
+
+    def pick(k):
+        return np.arange(n) if k >= n else np.sort(rng.choice(n, size=k, replace=False))
+    return pick(DUMP_BYTES // 5 // (12 * 8)), pick(DUMP_BYTES * 3 // 4 // (4 * (stride + store_stride)))
+
+
+def write_outputs(path, arrays):
+    """DIR/<name>.npy: one-byte fields as float32, wider integers as float64; every value must survive that format."""
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        f = a.astype(np.float32 if a.dtype.itemsize == 1 else np.float64)
+        assert np.array_equal(f.astype(a.dtype), a), "%s does not fit %s" % (name, f.dtype)
+        np.save(os.path.join(path, name + ".npy"), f)
+        total += f.nbytes
+    assert total <= DUMP_BYTES
+    return total
+
+
+def dump_outputs(path, slot, n):
+    """What the step that just ran on `slot` handed its caller (lrm_seed_batch_dev + lrm_extend_batch_dev): best[], score,
+    n_ops, meta_r and meta (loc, off, seq_id, strand) of the reads in read_index; the op bytes (zero past n_ops: those bytes
+    are not part of the result) and the batch rows as extend left them (reverse-strand reads reverse-complemented) of the
+    reads in row_index."""
+    import torch
+    from longreadmapper_amd import mapper
+    dm, reads = slot["dm"], slot["reads"]
+    sel, rows = dump_plan(n, reads.shape[1], dm.store_stride)
+
+    def take(t, idx):
+        return t.index_select(0, torch.from_numpy(idx).to(t.device)).cpu().numpy()
+    meta = take(dm.meta, sel).reshape(-1).view(mapper.META_DT)
+    ops = take(dm.store, rows)
+    ops[np.arange(ops.shape[1])[None, :] >= take(dm.n_ops, rows)[:, None]] = 0
+    return write_outputs(path, dict(
+        read_index=sel, row_index=rows, best=take(dm.best, sel), score=take(dm.score, sel), n_ops=take(dm.n_ops, sel),
+        meta_r=take(dm.meta_r, sel), ops=ops, reads=take(reads, rows),
+        meta=np.stack([meta["loc"].astype(np.int64), meta["off"].astype(np.int64), meta["seq_id"].astype(np.int64),
+                       meta["strand"].astype(np.int64)], axis=1)))
+
+
+def compact_record(out):
+    """The stdout line: the figures of the full record without per-kernel tables, per-leg details and notes, so that the
+    whole line fits a log tail (tests/test_bench_record.py holds it under 6 KB)."""
+    def pick(d, *keys):
+        return {k: d[k] for k in keys if k in d} if d else None
+    c = pick(out, "metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+             "vs_baseline", "dtype", "data", "value_hbm_resident", "value_pcie_inclusive", "config", "streams",
+             "speedup_vs_cpu", "speedup_pcie_inclusive_vs_cpu", "child_wall_s")
+    c["roofline"] = pick(out.get("roofline"), "kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_frac",
+                         "avg_launch_ms", "gcups")
+    cpu = out.get("cpu_baseline")
+    c["cpu_baseline"] = pick(cpu, "value", "unit", "cores", "kind")
+    if cpu and "one_thread" in cpu:
+        c["cpu_baseline"]["one_thread"] = cpu["one_thread"]["value"]
+    pc = out.get("pcie_inclusive")
+    if pc:
+        c["pcie_inclusive"] = dict(steps=pc["steps"], **{k: v["value"] for k, v in pc.items() if isinstance(v, dict) and "value" in v})
+    if out.get("kernels"):
+        c["kernel_avg_ms"] = {k: v["avg_ms"] for k, v in out["kernels"].items()}
+    c["isolated"] = pick(out.get("isolated"), "ms_per_step", "value", "kernel_ms_per_step")
+    c["index"] = pick(out.get("index"), "rows", "image_bytes", "build_s", "host_cpus", "peak_rss_gb")
+    g = out.get("grch38")
+    if g:
+        c["grch38"] = compact_record(g) if "value" in g else {k: str(v)[-400:] for k, v in g.items()}
+    return c
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -147,6 +227,9 @@ def main():
     ap.add_argument("--no-grch38", action="store_true",
                     help="do not run the GRCh38-sized leg in a child process after the default workload")
     ap.add_argument("--grch38-timeout", type=float, default=400.0)
+    ap.add_argument("--record", metavar="FILE", help="write the full record (per-kernel tables, every PCIe leg, notes) as JSON to FILE")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB; see dump_outputs)")
     ap.add_argument("--sa-sampled", type=int, default=0, help="lrm_index_options.sa_sampled (0: full suffix array)")
     args = ap.parse_args()
 
@@ -247,6 +330,9 @@ def main():
         step()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, slots[(step_no[0] - 1) % nstreams], n)
+        log("outputs of the last timed step: %.1f MB under %s" % (dumped / 1e6, args.dump_outputs))
     ktimes = {}
     if not args.no_kernel_timing:
         for sl in slots:
@@ -644,17 +730,19 @@ def main():
             del slots, dm, di, blob, pristine, d_lens, d_reads, hi, oi, full, r, rs, ref
             gc.collect()
             torch.cuda.empty_cache()
+            tmp = tempfile.TemporaryDirectory()
+            child_record = os.path.join(tmp.name, "grch38.json")
             cmd = [sys.executable, os.path.abspath(__file__), "--no-grch38", "--ref-len", str(GRCH38_N), "--steps", "10", "--warmup", "3",
                    "--pcie-steps", "6", "--cpu-seconds", "6", "--reads", str(args.reads), "--read-len", str(args.read_len),
-                   "--seed-len", str(args.seed_len), "--thres", str(args.thres), "--gact", args.gact]
+                   "--seed-len", str(args.seed_len), "--thres", str(args.thres), "--gact", args.gact, "--record", child_record]
             tg = time.time()
             pr = None
             try:
                 pr = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=args.grch38_timeout)
-                line = [l for l in pr.stdout.splitlines() if l.startswith("{")]
-                if pr.returncode == 0 and line:
-                    g = json.loads(line[-1])
-                    for k in ("kernels", "isolated", "algorithmic_bytes_per_base"):       # the per-kernel tables stay in the child's own line
+                if pr.returncode == 0 and os.path.exists(child_record):
+                    with open(child_record) as f:
+                        g = json.load(f)
+                    for k in ("kernels", "isolated", "algorithmic_bytes_per_base"):       # the per-kernel tables stay in the child's own record
                         if k == "isolated" and g.get(k):
                             g[k] = dict(ms_per_step=g[k]["ms_per_step"], value=g[k]["value"], kernel_ms_per_step=g[k]["kernel_ms_per_step"],
                                         kernel_avg_ms={kn: kv["avg_ms"] for kn, kv in g[k]["kernels"].items()})
@@ -669,7 +757,12 @@ def main():
             for l in (pr.stderr.splitlines()[-12:] if pr is not None else []):
                 if l.startswith("[bench]"):
                     log("grch38 child:", l[8:])
-    print(json.dumps(out), flush=True)
+            tmp.cleanup()
+    if args.record:
+        os.makedirs(os.path.dirname(os.path.abspath(args.record)), exist_ok=True)
+        with open(args.record, "w") as f:
+            json.dump(out, f)
+    print(json.dumps(compact_record(out)), flush=True)
     if world > 1:
         tdist.barrier()
 

@@ -2,6 +2,8 @@
 # Runs on the GPU box (via gpurun) from the repo root: bench lines, rocprofv3 kernel-trace stats of the
 # same commands, and the PMC passes (own runs, counters only -- never combined with trace domains).
 # Outputs land in gpurun_out/$TAG/ ; profiles/summarize_pmc.py turns them into profiles/<round>/.
+# bench_default, bench_streams1 and the other-config *.json are bench.py's full records (--record): the summaries read
+# the per-kernel tables from them; the profiled runs keep the short stdout line.
 #   default command  = steps alternate over 3 HIP streams (kernels of different steps overlap), then a serialized
 #                      replay on one stream (what `roofline` is taken from) and the PCIe-inclusive leg
 #   --streams 1      = one stream: every kernel has the chip to itself (isolated per-kernel durations)
@@ -14,9 +16,9 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
 if [ "$PART" = "A" ]; then
-    timeout -k 10 700 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || exit 1
+    timeout -k 10 700 python bench.py --record $OUT/bench_default.json > /dev/null 2> $OUT/bench_default.err || exit 1
     grep -v "lrm build" $OUT/bench_default.err | tail -4
-    timeout -k 10 300 python bench.py --streams 1 --cpu-seconds 5 --no-pcie --no-grch38 > $OUT/bench_streams1.json 2> $OUT/bench_streams1.err || exit 1
+    timeout -k 10 300 python bench.py --streams 1 --cpu-seconds 5 --no-pcie --no-grch38 --record $OUT/bench_streams1.json > /dev/null 2> $OUT/bench_streams1.err || exit 1
     cd /tmp && export TMPDIR=/tmp
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- \
         python3 $GRAFT_REPO_ROOT/bench.py --cpu-seconds 0 --no-pcie --no-grch38 > $OUT/bench_trace.json 2> $OUT/bench_trace.err || exit 1
@@ -45,9 +47,9 @@ elif [ "$PART" = "D" ]; then
     done
 else
     timeout -k 10 400 python bench.py --no-grch38 --ref-len 248956422 --reads 50000 --read-len 15000 --profile pacbio --steps 6 --warmup 2 \
-        --cpu-seconds 5 > $OUT/bench_chr1_pacbio15k.json 2> $OUT/bench_chr1_pacbio15k.err || exit 1
+        --cpu-seconds 5 --record $OUT/bench_chr1_pacbio15k.json > /dev/null 2> $OUT/bench_chr1_pacbio15k.err || exit 1
     tail -1 $OUT/bench_chr1_pacbio15k.err
     timeout -k 10 400 python bench.py --no-grch38 --reads 20000 --read-len 100000 --steps 6 --warmup 2 --cpu-seconds 5 \
-        > $OUT/bench_ultralong_20k_x_100kbp.json 2> $OUT/bench_ultralong_20k_x_100kbp.err || exit 1
+        --record $OUT/bench_ultralong_20k_x_100kbp.json > /dev/null 2> $OUT/bench_ultralong_20k_x_100kbp.err || exit 1
     tail -1 $OUT/bench_ultralong_20k_x_100kbp.err
 fi

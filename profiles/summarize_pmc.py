@@ -115,7 +115,7 @@ if stats1:
     shutil.copy(stats1[0], os.path.join(dst, "kernel_stats_streams1.csv"))
 with open(os.path.join(dst, "README.md"), "w") as f:
     f.write("# Profiles %s -- default `bench.py` workload on one MI355X\n\n" % tag)
-    f.write("`bench_default.json`: the JSON line of `python bench.py` (%d steps, %d warm-up, steps alternating over %d HIP "
+    f.write("`bench_default.json`: the full record of `python bench.py --record` (%d steps, %d warm-up, steps alternating over %d HIP "
             "streams so that kernels of different steps overlap).\n\n" % (bench["steps"], bench["warmup"], bench.get("streams", 1)))
     f.write("value = **%.2f Gbp/s**, %.1f ms per 1-Gbp step; CPU oracle on %d host cores: %.4f Gbp/s (x%.0f).\n\n"
             % (bench["value"], bench["ms_per_step"], bench["cpu_baseline"]["cores"], bench["cpu_baseline"]["value"],
