@@ -238,9 +238,14 @@ def index_options(**kw):
     o = IndexOptions()
     lib.lrm_index_options_init(C.byref(o))
     for k, v in kw.items():
+        if k not in _INDEX_OPTION_NAMES:      # (a ctypes structure takes any attribute: a misspelt option would be dropped)
+            raise AttributeError("lrm_index_options has no field %r" % k)
         if v is not None:
-            setattr(o, k, v)          # AttributeError for a field the struct does not have
+            setattr(o, k, v)
     return o
+
+
+_INDEX_OPTION_NAMES = frozenset(n for n, _ in IndexOptions._fields_) - {"struct_size", "reserved"}
 
 
 def map_options(**kw):
