@@ -274,9 +274,18 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(const uint8_t *__restric
 // WRITE = false: only the text length (tlen[row]); WRITE = true: the text at dense + off[row], NUL-terminated.
 // Reads without an alignment (no ops, locus outside every sequence, score -1) print "*".
 __device__ __forceinline__ uint32_t op_class(uint32_t b) { return (b == '=' || b == 'X') ? (uint32_t) 'M' : b; }
-__device__ __forceinline__ uint32_t dec_digits(uint32_t v) {
-    return v < 10 ? 1u : v < 100 ? 2u : v < 1000 ? 3u : v < 10000 ? 4u : v < 100000 ? 5u : v < 1000000 ? 6u : v < 10000000 ? 7u : 10u;
+__host__ __device__ constexpr uint32_t dec_digits(uint32_t v) {
+    return v < 10 ? 1u : v < 100 ? 2u : v < 1000 ? 3u : v < 10000 ? 4u : v < 100000 ? 5u : v < 1000000 ? 6u : v < 10000000 ? 7u :
+           v < 100000000 ? 8u : v < 1000000000 ? 9u : 10u;
 }
+// no read the tests can afford has a run of 10^7 ops: the ladder is pinned here, at every power of ten a uint32_t holds
+constexpr bool dec_digits_ok() {
+    uint64_t p = 10;
+    for (uint32_t k = 1; k <= 9; ++k, p *= 10)
+        if (dec_digits((uint32_t) (p - 1)) != k || dec_digits((uint32_t) p) != k + 1) return false;
+    return dec_digits(0) == 1 && dec_digits(0xFFFFFFFFu) == 10;
+}
+static_assert(dec_digits_ok(), "dec_digits: one digit per power of ten");
 template <bool IS_MAX>
 __device__ __forceinline__ int block_excl_scan(int v, int *s_w, int *total) {       // exclusive scan over 256 threads (max with -1 / sum with 0)
     const int lane = (int) (threadIdx.x & 63u), wave = (int) (threadIdx.x >> 6);
