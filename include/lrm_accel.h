@@ -163,7 +163,13 @@ typedef struct lrm_map_options {
                                   prints such a read (SAM SEQ) applies meta_out[i].strand itself: the read was reverse-complemented
                                   iff meta_r[i] != 0 && meta_out[i].strand == 1 (lrm_accaln's formatter does).  Host-buffer
                                   batch calls only. */
-    uint32_t reserved[7];
+    uint32_t anchored;         /* 1: ANCHORED extension (docs/GACT_SPEC.md, "Anchored extension"): the longest exact match of the
+                                  read within LRM_ANCHOR_DIAGS diagonals of the voted locus becomes the anchor, the read is extended
+                                  to the right and to the left of it, and meta_out[i].loc / .off move to the alignment's first text
+                                  base (SAM POS).  Needs store_stride >= 2*max_len + max_len/8 + 2.  0: every read is aligned
+                                  against the window at the voted locus (alnmain.c:440-446) */
+    uint32_t anchor_min_len;   /* shortest exact match that anchors a read: 0 = 20 (the default seed length), else 12..64 */
+    uint32_t reserved[5];
 } lrm_map_options;
 void lrm_map_options_init(lrm_map_options *o);
 
@@ -341,6 +347,30 @@ int lrm_extend_batch_dev(lrm_index *idx, lrm_workspace *ws, char *d_reads, uint6
                          uint64_t store_stride, int32_t *d_n_ops, int32_t *d_score,
                          lrm_seq_meta *d_meta, int32_t *d_meta_r, void *stream);
 
+/* ANCHORED extension (lrm_map_options.anchored; docs/GACT_SPEC.md): the arguments of lrm_extend_batch_dev plus the anchor
+ * records (d_anchor: n entries in device memory, may be NULL) and the shortest anchor (min_len: 0 = 20, else 12..64).
+ * The precondition on the store becomes store_stride >= 2*max_len + max_len/8 + 2 (checked).  The first call on a
+ * workspace allocates the scratch of the mode (job table, job rows, their op bytes); lrm_workspace_bytes grows by it. */
+#define LRM_ANCHOR_DIAGS 64            /* diagonals L + delta, delta in [-32, 32), searched around the voted locus L */
+#define LRM_ANCHOR_ANCHORED 1u         /* lrm_anchor.flags: an anchor was found, the read was extended both ways from it */
+#define LRM_ANCHOR_FALLBACK 2u         /*   no exact match of min_len bases: extended from the voted locus as without the mode */
+#define LRM_ANCHOR_NO_LEFT 4u          /*   the anchor starts at the read's first base: no left job */
+#define LRM_ANCHOR_LEFT_CLIPPED 8u     /*   the left job's target window ends at the start of the sequence */
+#define LRM_ANCHOR_RIGHT_CLIPPED 16u   /*   the right job's target window ends at the end of the sequence */
+typedef struct lrm_anchor {
+    uint64_t text_pos;                 /* text position of read[read_pos] (forward half of the sequence) */
+    uint32_t read_pos, len;            /* the exact match read[read_pos .. read_pos + len) */
+    int32_t delta;                     /* its diagonal relative to the voted locus */
+    uint32_t left_ops;                 /* alignment columns of the left job (the first left_ops op bytes of the read) */
+    uint32_t flags;                    /* LRM_ANCHOR_*; 0 for a read without a locus (meta_r == 0) */
+} lrm_anchor;
+int lrm_extend_batch_anchored_dev(lrm_index *idx, lrm_workspace *ws, char *d_reads, uint64_t stride,
+                                  const uint32_t *d_lens, uint64_t n, uint32_t max_len,
+                                  const lrm_entry *d_best, lrm_gact_params gp, uint8_t *d_store,
+                                  uint64_t store_stride, int32_t *d_n_ops, int32_t *d_score,
+                                  lrm_seq_meta *d_meta, int32_t *d_meta_r, lrm_anchor *d_anchor, uint32_t min_len,
+                                  void *stream);
+
 /* Counters of the last *_dev call on this workspace (device->host copy, syncs
  * the stream): vote items per table tier, reads decided in
  * phase 0, GACT tiles.  For tests / bench bookkeeping only. */
@@ -361,7 +391,8 @@ int lrm_workspace_stats(lrm_workspace *ws, lrm_stats *out, void *stream);
 
 /* Per-kernel timing with HIP events recorded on the launch stream (bench bookkeeping).
  * Kernel order: pack2bit, seed_search, vote, decide, locus_resolve, revcomp, gact (byte kernels),
- * bs_pack_reads, gact_bs (bit-sliced kernel + expansion).
+ * bs_pack_reads, gact_bs (bit-sliced kernel + expansion).  The anchored mode adds its anchor scan to the
+ * locus_resolve slot, its job builder to the revcomp slot and its stitch to the slot of the extension kernel.
  * lrm_workspace_timing synchronises the stream, ADDS the elapsed milliseconds and launch counts
  * of everything recorded since the last call into ms[LRM_N_KERNELS] / launches[LRM_N_KERNELS], and
  * resets the record. */
@@ -387,6 +418,10 @@ int lrm_debug_reload_env(lrm_index *idx);
 /* RCCL self-test (tests only): dlopen + ncclCommInitAll + a 1-rank grouped ncclBroadcast of `bytes` bytes on
  * `device`.  0 ok, 1 librccl not loadable (lrm_index_upload_multi then uses hipMemcpyPeer), <0 error. */
 int lrm_debug_rccl_selftest(int device, uint64_t bytes);
+
+/* Anchor tap (tests only): the anchor of ONE read (oriented like the forward strand) at ONE voted locus `loc`, a text
+ * position on the forward half of a sequence; out->left_ops is 0 (nothing is extended). */
+int lrm_debug_anchor(lrm_index *idx, const char *read, uint32_t len, uint64_t loc, uint32_t min_len, lrm_anchor *out);
 
 /* Direct kernel tap (tests only): simple_gact on one (q, d) pair. */
 int lrm_debug_gact(const char *q, int n, const char *d, int m, lrm_gact_params gp,

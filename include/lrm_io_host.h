@@ -68,6 +68,11 @@ void lrm_free(void *p);
  * reference's "Sensitivity: valid/total" counters (alnmain.c:541). */
 int lrm_accaln(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
                lrm_gact_params gp, int device, long rg_id, uint64_t *total, uint64_t *valid);
+/* ... with options (NULL: lrm_accaln).  Taken from opt: anchored, anchor_min_len -- SAM POS is then the alignment's first
+ * text base (meta.off + 1 of the moved meta); the other fields are this flow's own choice. */
+int lrm_accaln_opt(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
+                   lrm_gact_params gp, int device, long rg_id, uint64_t *total, uint64_t *valid,
+                   const lrm_map_options *opt);
 
 #ifdef __cplusplus
 }

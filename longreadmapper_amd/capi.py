@@ -77,7 +77,17 @@ class MapOptions(C.Structure):         # lrm_map_options
     _fields_ = [("struct_size", C.c_uint32), ("dense_results", C.c_int32), ("gact_impl", C.c_int32),
                 ("seed_rounds", C.c_int32), ("vote_exact_only", C.c_int32), ("slice_reads", C.c_uint32),
                 ("sub_batches", C.c_uint32), ("group_subs", C.c_uint32), ("bs_waves", C.c_uint32),
-                ("cigar_text", C.c_uint32), ("copy_threads", C.c_uint32), ("keep_reads", C.c_uint32), ("reserved", C.c_uint32 * 7)]
+                ("cigar_text", C.c_uint32), ("copy_threads", C.c_uint32), ("keep_reads", C.c_uint32), ("anchored", C.c_uint32),
+                ("anchor_min_len", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
+class Anchor(C.Structure):             # lrm_anchor
+    _fields_ = [("text_pos", C.c_uint64), ("read_pos", C.c_uint32), ("len", C.c_uint32), ("delta", C.c_int32),
+                ("left_ops", C.c_uint32), ("flags", C.c_uint32)]
+
+
+ANCHOR_ANCHORED, ANCHOR_FALLBACK, ANCHOR_NO_LEFT, ANCHOR_LEFT_CLIPPED, ANCHOR_RIGHT_CLIPPED = 1, 2, 4, 8, 16
+ANCHOR_DIAGS = 64                      # LRM_ANCHOR_DIAGS
 
 
 class Stats(C.Structure):
@@ -98,6 +108,7 @@ class HostIndex(C.Structure):          # lrm_index_host.h
 
 
 assert C.sizeof(Ui40) == 8 and C.sizeof(Entry) == 24 and C.sizeof(SeqMeta) == 24
+assert C.sizeof(MapOptions) == 76 and C.sizeof(Anchor) == 32
 
 # every symbol include/*.h declares: (restype, argtypes)
 SYMBOLS = {
@@ -166,6 +177,10 @@ SYMBOLS = {
     "lrm_extend_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                        C.c_uint32, C.c_void_p, GactParams, C.c_void_p, C.c_uint64, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lrm_extend_batch_anchored_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                                C.c_uint32, C.c_void_p, GactParams, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "lrm_debug_anchor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(Anchor)]),
     "lrm_workspace_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats), C.c_void_p]),
     "lrm_workspace_set_counting": (C.c_int, [C.c_void_p, C.c_int]),
     "lrm_workspace_set_timing": (C.c_int, [C.c_void_p, C.c_int]),
@@ -207,6 +222,8 @@ SYMBOLS = {
                                     C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
     "lrm_free": (None, [C.c_void_p]),
     "lrm_accaln": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, Params, GactParams, C.c_int, C.c_long, u64p, u64p]),
+    "lrm_accaln_opt": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, Params, GactParams, C.c_int, C.c_long, u64p, u64p,
+                                 C.POINTER(MapOptions)]),
 }
 
 

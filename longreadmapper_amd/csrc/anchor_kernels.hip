@@ -1,0 +1,537 @@
+// anchor_kernels.hip -- gfx950 kernels of the ANCHORED extension mode (docs/GACT_SPEC.md, "Anchored extension")
+//
+//   anchor_scan     the longest exact match of a read on the LRM_ANCHOR_DIAGS diagonals around its voted locus
+//   anchor_jobs     the job table (2 rows per read: right job, left job) and the job read rows
+//   (extension)     ONE launch of the unchanged extension kernels over the job table (lrm_gact_launch_jobs)
+//   anchor_stitch   reverse(left ops) ++ right ops into the caller's store, sums, moved meta, lrm_anchor records
+//
+// Scan: a wavefront takes one SEGMENT of one read and its 64 lanes take the 64 diagonals.  Per 32 read bases a lane
+// builds one 32-bit mismatch word -- from the bit-planar images the bit-sliced extension already keeps (reads:
+// bs_pack_reads, text: the index's planar copy), two 64-bit words of text funnel-shifted to the lane's diagonal and
+// XORed with the read's word -- and carries the length of the run of equal bases that is open at the word's end.
+// A run is counted by the segment it STARTS in: a lane first looks at the base before its segment (a run already open
+// there belongs to the segment before), and after its last word it goes on, word by word, until the run still open
+// has ended.  Runs that lie inside one word (no longer than 30 bases) are only looked for when a shift-and-AND test
+// says the word holds 12 equal bases in a row (12 is the shortest anchor the option allows).  Reads or texts with a
+// byte other than ACGT build the same mismatch words from bytes.  The best (length, |delta|, delta, j) of the lanes
+// is reduced as one 64-bit key and merged into the read's key with one atomicMax per segment.
+#include <hip/hip_runtime.h>
+#include <cstdlib>
+#include "lrm_internal.h"
+#include "seq_bytes.h"
+
+#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
+    lrm_set_error("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); return -1; } } while (0)
+
+#define AN_SEG_WORDS 64                       // words (of 32 bases) per scan segment: 2048 bases
+#define AN_HALF (LRM_ANCHOR_DIAGS / 2)
+#define AN_CHUNK 4096                         // bytes of a row one workgroup of the job / stitch kernels moves
+static_assert(LRM_ANCHOR_DIAGS == 64, "one lane per diagonal");
+
+struct LrmAnchorScratch {
+    uint64_t n_max;
+    uint32_t max_len;
+    uint64_t *keys;                           // per read: best (length, |delta|, delta, j) as one word, 0 = none
+    char *job_reads; uint64_t job_stride;     // 2 rows per read
+    uint32_t *job_lens, *job_tlens;
+    lrm_seq_meta *job_meta;
+    int32_t *job_meta_r, *job_nops, *job_score;
+    uint8_t *job_store; uint64_t job_store_stride;
+    lrm_anchor *anchors;                      // used when the caller passes none
+    // bit-sliced extension over the job table
+    uint64_t *qpl; uint32_t *rflags; uint32_t *ckpt; uint64_t *codes; uint64_t cw; int32_t *ncodes;
+};
+
+struct __attribute__((packed, aligned(1))) An16 { uint32_t x, y, z, w; };     // 16 bytes at any address
+
+// ---- the key: larger is better -----------------------------------------------------------------------------------
+// bits 40..63 length | 33..38 32 - |delta| | 32 delta < 0 | 0..31 ~j : longest run, then smallest |delta|, then
+// smallest delta, then smallest j
+__host__ __device__ static inline uint64_t an_key(uint32_t len, int delta, uint32_t j) {
+    const uint32_t ad = (uint32_t) (delta < 0 ? -delta : delta);
+    return ((uint64_t) len << 40) | ((uint64_t) (AN_HALF - ad) << 33) | ((uint64_t) (delta < 0) << 32) | (uint64_t) (0xFFFFFFFFu - j);
+}
+
+struct AnPlan {                               // what the key of a read means for its two jobs
+    uint32_t flags, j, len;
+    int32_t delta;
+    uint64_t p;                               // text position of read[j]
+    uint64_t left_loc;                        // start of the left job's target on the reverse-complement half
+    uint32_t right_tlen, left_tlen;
+};
+__host__ __device__ static inline AnPlan an_plan(uint64_t key, uint64_t L, uint32_t n, uint64_t S, uint64_t len_s) {
+    AnPlan a = {};
+    if (key == 0) { a.flags = LRM_ANCHOR_FALLBACK; a.p = L; return a; }
+    a.len = (uint32_t) (key >> 40);
+    const int ad = AN_HALF - (int) ((key >> 33) & 63u);
+    a.delta = ((key >> 32) & 1u) ? -ad : ad;
+    a.j = 0xFFFFFFFFu - (uint32_t) key;
+    a.p = (uint64_t) ((int64_t) L + a.delta + (int64_t) a.j);
+    a.flags = LRM_ANCHOR_ANCHORED;
+    const uint64_t nr = n - a.j, wr = nr + (nr + 7) / 8, room_r = S + len_s - a.p;
+    a.right_tlen = (uint32_t) (wr < room_r ? wr : room_r);
+    if (wr > room_r) a.flags |= LRM_ANCHOR_RIGHT_CLIPPED;
+    if (a.j == 0) { a.flags |= LRM_ANCHOR_NO_LEFT; return a; }
+    const uint64_t nl = a.j, wl = nl + (nl + 7) / 8, room_l = a.p - S;
+    a.left_tlen = (uint32_t) (wl < room_l ? wl : room_l);
+    if (wl > room_l) a.flags |= LRM_ANCHOR_LEFT_CLIPPED;
+    a.left_loc = 2 * S + 2 * len_s - a.p;     // mirror of p - 1: y = 2S + 2 len_s - 1 - x
+    return a;
+}
+
+// ---- scan ------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t an_bits(int lo, int hi) {        // bits lo .. hi-1, 0 <= lo < hi <= 32
+    return (hi >= 32 ? 0xFFFFFFFFu : ((1u << hi) - 1u)) & ~((1u << lo) - 1u);
+}
+__device__ __forceinline__ bool an_is_acgt(uint32_t c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; }
+
+struct AnScan {
+    const uint64_t *qw;          // planar read words (null: bytes)
+    const uint64_t *cpl;         // planar text, word 0 = bases 0..31
+    const uint8_t *q, *text;     // bytes
+    int64_t P0;                  // text position of read base 0 on this lane's diagonal
+    int64_t S, E;                // the sequence [S, E)
+    int n;
+
+    // bit k set <=> read base 32w + k does NOT match the text on this diagonal (or lies outside the read / the sequence)
+    __device__ __forceinline__ uint32_t mismatch(int w) const {
+        const int b0 = 32 * w;
+        const int64_t P = P0 + b0;
+        const int64_t lo64 = S - P, hi64 = E - P;
+        const int lo = lo64 > 0 ? (lo64 < 32 ? (int) lo64 : 32) : 0;
+        int hi = hi64 < 32 ? (hi64 > 0 ? (int) hi64 : 0) : 32;
+        hi = min(hi, n - b0);
+        if (hi <= lo) return 0xFFFFFFFFu;
+        uint32_t x;
+        if (qw) {
+            const uint64_t qv = qw[w];
+            const int64_t wi = P >> 5;                 // >= -1 here: the planar text has padding words in front
+            const uint32_t sh = (uint32_t) P & 31u;
+            const uint64_t t0 = cpl[wi], t1 = cpl[wi + 1];
+            const uint32_t tlo = __builtin_amdgcn_alignbit((uint32_t) t1, (uint32_t) t0, sh);
+            const uint32_t thi = __builtin_amdgcn_alignbit((uint32_t) (t1 >> 32), (uint32_t) (t0 >> 32), sh);
+            x = ((uint32_t) qv ^ tlo) | ((uint32_t) (qv >> 32) ^ thi);
+        } else {
+            x = 0;
+            for (int k = lo; k < hi; ++k) {
+                const uint32_t a = q[b0 + k], b = text[P + k];
+                x |= (uint32_t) !(a == b && an_is_acgt(a)) << k;
+            }
+        }
+        return x | ~an_bits(lo, hi);
+    }
+};
+
+__global__ __launch_bounds__(256) void anchor_scan_kernel(const char *__restrict__ reads, uint64_t stride,
+                                                          const uint32_t *__restrict__ lens,
+                                                          const lrm_seq_meta *__restrict__ meta,
+                                                          const int32_t *__restrict__ meta_r, uint64_t n_reads,
+                                                          const LrmMtaDev *__restrict__ mta, const char *__restrict__ content,
+                                                          const uint64_t *__restrict__ qpl, uint64_t wpr,
+                                                          const uint32_t *__restrict__ rflags,
+                                                          const uint64_t *__restrict__ cpl, uint32_t min_len,
+                                                          uint32_t segs_per_read, unsigned long long *__restrict__ keys) {
+    const uint64_t wave_id = (uint64_t) blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const uint64_t r = wave_id / segs_per_read;
+    if (r >= n_reads || !meta_r[r]) return;
+    const int n = (int) lens[r];
+    const int nw = (n + 31) >> 5;
+    const int w0 = (int) (wave_id % segs_per_read) * AN_SEG_WORDS;
+    if (w0 >= nw) return;
+    const int w1 = min(w0 + AN_SEG_WORDS, nw);
+    const lrm_seq_meta m = meta[r];
+    const int delta = lane - AN_HALF;
+    AnScan sc;
+    const bool planar = qpl && cpl && !rflags[r];
+    sc.qw = planar ? qpl + r * wpr + LRM_BS_PADW : nullptr;
+    sc.cpl = cpl;
+    sc.q = reinterpret_cast<const uint8_t *>(reads) + r * stride;
+    sc.text = reinterpret_cast<const uint8_t *>(content);
+    sc.P0 = (int64_t) m.loc + delta;
+    sc.S = (int64_t) mta[m.seq_id].offset;
+    sc.E = sc.S + (int64_t) mta[m.seq_id].seq_len;
+    sc.n = n;
+
+    uint32_t run = 0, best_len = 0, best_j = 0;
+    bool own = true;                                 // the open run started in this segment
+    if (w0 > 0 && !(sc.mismatch(w0 - 1) >> 31)) { run = 1; own = false; }
+    int w = w0;
+    for (;; ++w) {
+        const bool in_seg = w < w1;
+        const bool live = in_seg || (own && run > 0);    // past the segment only a run that is still open goes on
+        if (!in_seg && (w >= nw || !__any(live))) break;
+        if (live) {
+            const uint32_t x = sc.mismatch(w);
+            if (x == 0) {
+                run += 32;
+            } else {
+                const uint32_t f = (uint32_t) __builtin_ctz(x), len = run + f;
+                if (own && len >= min_len && len > best_len) { best_len = len; best_j = (uint32_t) (32 * w) + f - len; }
+                run = 0;
+                own = true;
+                if (in_seg) {
+                    const uint32_t h = (uint32_t) __builtin_clz(x);
+                    // runs between the first and the last mismatch of the word
+                    uint32_t z = ~x & ~((2u << f) - 1u) & (0x7FFFFFFFu >> h);
+                    const uint32_t r2 = z & (z >> 1), r4 = r2 & (r2 >> 2), r8 = r4 & (r4 >> 4);
+                    if (r8 & (r4 >> 8)) {
+                        while (z) {
+                            const uint32_t s = (uint32_t) __builtin_ctz(z);
+                            const uint32_t l = (uint32_t) __builtin_ctz(~(z >> s));
+                            if (l >= min_len && l > best_len) { best_len = l; best_j = (uint32_t) (32 * w) + s; }
+                            z &= ~(((1u << l) - 1u) << s);
+                        }
+                    }
+                    run = h;
+                }
+            }
+        }
+    }
+    if (own && run >= min_len && run > best_len) { best_len = run; best_j = (uint32_t) (32 * w) - run; }
+
+    uint64_t key = best_len ? an_key(best_len, delta, best_j) : 0;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const uint32_t lo = (uint32_t) __shfl_xor((int) (uint32_t) key, o), hi = (uint32_t) __shfl_xor((int) (uint32_t) (key >> 32), o);
+        const uint64_t other = ((uint64_t) hi << 32) | lo;
+        key = other > key ? other : key;
+    }
+    if (lane == 0 && key) atomicMax(keys + r, (unsigned long long) key);
+}
+
+// ---- jobs ------------------------------------------------------------------------------------------------------------
+// dst[k] = src[k] (right job) or comp(src[cnt - 1 - k]) (left job), k in [c0, c1): 16 bytes per thread, aligned stores
+// (job rows are 16-byte aligned), loads at any address inside the source span
+template <bool REV>
+__device__ __forceinline__ void an_fill_row(char *__restrict__ dst, const char *__restrict__ src, uint32_t cnt, uint32_t c0,
+                                            uint32_t c1, uint32_t tid) {
+    for (uint32_t k = c0 + 16 * tid; k < c1; k += 16 * 256) {
+        if (k + 16 <= cnt) {
+            const An16 v = *reinterpret_cast<const An16 *>(REV ? src + (cnt - 16 - k) : src + k);
+            *reinterpret_cast<uint4 *>(dst + k) = REV ? make_uint4(revcomp4(v.w), revcomp4(v.z), revcomp4(v.y), revcomp4(v.x))
+                                                      : make_uint4(v.x, v.y, v.z, v.w);
+        } else {
+            for (uint32_t e = k; e < cnt; ++e) dst[e] = REV ? comp_base(src[cnt - 1 - e]) : src[e];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void anchor_jobs_kernel(const char *__restrict__ reads, uint64_t stride,
+                                                          const uint32_t *__restrict__ lens,
+                                                          const lrm_seq_meta *__restrict__ meta,
+                                                          const int32_t *__restrict__ meta_r, uint64_t n_reads,
+                                                          const LrmMtaDev *__restrict__ mta, uint64_t con_len,
+                                                          unsigned long long *__restrict__ keys, uint32_t chunks_per_read,
+                                                          char *__restrict__ job_reads, uint64_t job_stride,
+                                                          uint32_t *__restrict__ job_lens, uint32_t *__restrict__ job_tlens,
+                                                          lrm_seq_meta *__restrict__ job_meta, int32_t *__restrict__ job_meta_r) {
+    const uint64_t r = blockIdx.x / chunks_per_read;
+    const uint32_t chunk = blockIdx.x % chunks_per_read, tid = threadIdx.x;
+    if (r >= n_reads) return;
+    const bool mapped = meta_r[r] != 0;
+    const uint32_t n = mapped ? lens[r] : 0;
+    const lrm_seq_meta m = meta[r];
+    AnPlan a = {};
+    if (mapped) {
+        const uint64_t S = mta[m.seq_id].offset, len_s = mta[m.seq_id].seq_len;
+        // (a text that does not hold the reverse-complement half of the sequence cannot serve a left job)
+        const uint64_t key = S + 2 * len_s <= con_len ? keys[r] : 0;
+        a = an_plan(key, m.loc, n, S, len_s);
+    }
+    const bool anchored = a.flags & LRM_ANCHOR_ANCHORED;
+    if (chunk == 0 && tid == 0) {
+        lrm_seq_meta mr = m, ml = m;
+        mr.loc = a.p;
+        ml.loc = a.left_loc;
+        job_meta[2 * r] = mr; job_meta[2 * r + 1] = ml;
+        job_lens[2 * r] = anchored ? n - a.j : n;
+        job_tlens[2 * r] = anchored ? a.right_tlen : n;
+        job_meta_r[2 * r] = mapped;
+        job_lens[2 * r + 1] = anchored ? a.j : 0;
+        job_tlens[2 * r + 1] = a.left_tlen;
+        job_meta_r[2 * r + 1] = anchored && a.j > 0;
+        if (mapped && !anchored) keys[r] = 0;      // (only differs for the text without a reverse half)
+    }
+    if (!mapped) return;
+    const char *src = reads + r * stride;
+    const uint32_t j = anchored ? a.j : 0;
+    const uint32_t c0 = chunk * AN_CHUNK;
+    char *right = job_reads + 2 * r * job_stride, *left = right + job_stride;
+    if (c0 < n - j) an_fill_row<false>(right, src + j, n - j, c0, min(c0 + AN_CHUNK, n - j), tid);
+    if (c0 < j) an_fill_row<true>(left, src, j, c0, min(c0 + AN_CHUNK, j), tid);
+}
+
+// ---- stitch ----------------------------------------------------------------------------------------------------------
+// the whole 24-byte record, padding included: the mode's meta is the same bytes whatever the buffer held before
+__device__ __forceinline__ void an_store_meta(lrm_seq_meta *dst, uint64_t loc, uint64_t off, int32_t seq_id, uint8_t strand) {
+    static_assert(sizeof(lrm_seq_meta) == 24, "three words");
+    uint64_t *w = reinterpret_cast<uint64_t *>(dst);
+    w[0] = loc; w[1] = off; w[2] = (uint64_t) (uint32_t) seq_id | ((uint64_t) strand << 32);
+}
+__global__ __launch_bounds__(256) void anchor_stitch_kernel(const uint32_t *__restrict__ lens,
+                                                            lrm_seq_meta *__restrict__ meta,
+                                                            const int32_t *__restrict__ meta_r, uint64_t n_reads,
+                                                            const LrmMtaDev *__restrict__ mta,
+                                                            const unsigned long long *__restrict__ keys,
+                                                            uint32_t chunks_per_read,
+                                                            const uint8_t *__restrict__ job_store, uint64_t job_store_stride,
+                                                            const int32_t *__restrict__ job_nops,
+                                                            const int32_t *__restrict__ job_score,
+                                                            uint8_t *__restrict__ store, uint64_t store_stride,
+                                                            int32_t *__restrict__ n_ops, int32_t *__restrict__ score,
+                                                            lrm_anchor *__restrict__ anchors) {
+    __shared__ uint32_t s_cnt[4];
+    const uint64_t r = blockIdx.x / chunks_per_read;
+    const uint32_t chunk = blockIdx.x % chunks_per_read, tid = threadIdx.x;
+    if (r >= n_reads) return;
+    if (!meta_r[r]) {
+        if (chunk == 0 && tid == 0) {
+            n_ops[r] = 0; score[r] = -1;
+            an_store_meta(meta + r, 0, 0, -1, 0);
+            lrm_anchor z = {};
+            anchors[r] = z;
+        }
+        return;
+    }
+    const lrm_seq_meta m = meta[r];
+    const uint64_t S = mta[m.seq_id].offset, len_s = mta[m.seq_id].seq_len;
+    const AnPlan a = an_plan(keys[r], m.loc, lens[r], S, len_s);
+    const bool left = (a.flags & LRM_ANCHOR_ANCHORED) && a.j > 0;
+    const uint32_t nr = (uint32_t) job_nops[2 * r], nl = left ? (uint32_t) job_nops[2 * r + 1] : 0, total = nl + nr;
+    const uint8_t *rrow = job_store + 2 * r * job_store_stride, *lrow = rrow + job_store_stride;
+    uint8_t *out = store + r * store_stride;
+    const uint32_t c1 = min((chunk + 1) * AN_CHUNK, total);
+    for (uint32_t o = chunk * AN_CHUNK + 16 * tid; o < c1; o += 16 * 256) {
+        An16 v;
+        if (o + 16 <= nl) {                        // reversed left ops
+            const An16 s = *reinterpret_cast<const An16 *>(lrow + (nl - 16 - o));
+            v.x = __builtin_bswap32(s.w); v.y = __builtin_bswap32(s.z); v.z = __builtin_bswap32(s.y); v.w = __builtin_bswap32(s.x);
+            *reinterpret_cast<An16 *>(out + o) = v;
+        } else if (o >= nl && o + 16 <= total) {   // right ops
+            *reinterpret_cast<An16 *>(out + o) = *reinterpret_cast<const An16 *>(rrow + (o - nl));
+        } else {
+            for (uint32_t e = o; e < o + 16 && e < total; ++e) out[e] = e < nl ? lrow[nl - 1 - e] : rrow[e - nl];
+        }
+    }
+    if (chunk != 0) return;
+    // target bases the left job consumed: its columns other than 'I'
+    uint32_t cnt = 0;
+    for (uint32_t o = tid; o < nl; o += 256) cnt += lrow[o] != (uint8_t) 'I';
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) cnt += (uint32_t) __shfl_xor((int) cnt, o);
+    if ((tid & 63) == 0) s_cnt[tid >> 6] = cnt;
+    __syncthreads();
+    if (tid != 0) return;
+    const uint32_t consumed = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    n_ops[r] = (int32_t) total;
+    score[r] = job_score[2 * r] + (left ? job_score[2 * r + 1] : 0);
+    lrm_anchor an;
+    an.text_pos = a.p; an.read_pos = a.j; an.len = a.len; an.delta = a.delta; an.left_ops = nl; an.flags = a.flags;
+    anchors[r] = an;
+    if (a.flags & LRM_ANCHOR_ANCHORED) {           // meta moves to the alignment's first text base
+        an_store_meta(meta + r, a.p - consumed, a.p - consumed - S, m.seq_id, m.strand);
+    } else {
+        an_store_meta(meta + r, m.loc, m.off, m.seq_id, m.strand);
+    }
+}
+
+// debug tap: the record of one read straight from its key
+__global__ void anchor_record_kernel(const uint32_t *lens, const lrm_seq_meta *meta, const LrmMtaDev *mta,
+                                     const unsigned long long *keys, lrm_anchor *out) {
+    const lrm_seq_meta m = meta[0];
+    const AnPlan a = an_plan(keys[0], m.loc, lens[0], mta[m.seq_id].offset, mta[m.seq_id].seq_len);
+    lrm_anchor an;
+    an.text_pos = a.p; an.read_pos = a.j; an.len = a.len; an.delta = a.delta; an.left_ops = 0; an.flags = a.flags;
+    out[0] = an;
+}
+
+// ----------------------------------------------------------------------------------------
+// host side
+// ----------------------------------------------------------------------------------------
+void lrm_anchor_scratch_free(lrm_workspace *ws) {
+    LrmAnchorScratch *s = ws ? ws->an : nullptr;
+    if (!s) return;
+    void *bufs[] = {s->keys, s->job_reads, s->job_lens, s->job_tlens, s->job_meta, s->job_meta_r, s->job_nops, s->job_score,
+                    s->job_store, s->anchors, s->qpl, s->rflags, s->ckpt, s->codes, s->ncodes};
+    for (void *b : bufs) if (b) (void) hipFree(b);
+    delete s;
+    ws->an = nullptr;
+}
+
+// Scratch of the mode, sized once from the workspace's batch shape: 2 n_max jobs, job reads of up to max_len bases,
+// targets of up to len + ceil(len / 8) bases (so up to lrm_anchored_store_stride(max_len) op bytes and 2-bit codes per job).
+static int anchor_scratch(lrm_workspace *ws, bool planar) {
+    if (ws->an) return 0;
+    LrmAnchorScratch *s = new (std::nothrow) LrmAnchorScratch();
+    if (!s) { lrm_set_error("out of memory"); return -1; }
+    ws->an = s;
+    const uint64_t n = ws->n_max, jobs = 2 * n;
+    s->n_max = n; s->max_len = ws->max_len;
+    s->job_stride = ((uint64_t) ws->max_len + 31) & ~15ull;
+    s->job_store_stride = (lrm_anchored_store_stride(ws->max_len) + 15) & ~15ull;
+    s->cw = lrm_bs_code_words(ws->max_len + ws->max_len / 16 + 2);
+    struct { void **p; uint64_t bytes; bool on; } allocs[] = {
+        {(void **) &s->keys, n * 8, true},
+        {(void **) &s->job_reads, jobs * s->job_stride, true},
+        {(void **) &s->job_lens, jobs * 4, true},
+        {(void **) &s->job_tlens, jobs * 4, true},
+        {(void **) &s->job_meta, jobs * sizeof(lrm_seq_meta), true},
+        {(void **) &s->job_meta_r, jobs * 4, true},
+        {(void **) &s->job_nops, jobs * 4, true},
+        {(void **) &s->job_score, jobs * 4, true},
+        {(void **) &s->job_store, jobs * s->job_store_stride, true},
+        {(void **) &s->anchors, n * sizeof(lrm_anchor), true},
+        {(void **) &s->qpl, jobs * ws->qpl_wpr * 8 + 16, planar},
+        {(void **) &s->rflags, jobs * 4, planar},
+        {(void **) &s->ckpt, lrm_bs_ckpt_words(jobs) * 4, planar},
+        {(void **) &s->codes, jobs * s->cw * 8, planar},
+        {(void **) &s->ncodes, jobs * 4, planar},
+    };
+    for (auto &a : allocs) {
+        if (!a.on) continue;
+        if (hipMalloc(a.p, a.bytes) != hipSuccess) {
+            lrm_set_error("hipMalloc of %llu bytes of anchored-mode scratch failed", (unsigned long long) a.bytes);
+            lrm_anchor_scratch_free(ws);
+            return -1;
+        }
+        ws->bytes += a.bytes;
+    }
+    return 0;
+}
+
+static int anchor_min_len(uint32_t min_len, uint32_t *out) {
+    if (min_len == 0) min_len = LRM_ANCHOR_MIN_DEFAULT;
+    if (min_len < 12 || min_len > 64) { lrm_set_error("anchor_min_len %u outside [12, 64]", min_len); return -1; }
+    *out = min_len;
+    return 0;
+}
+
+static int launch_scan(const char *d_reads, uint64_t stride, const uint32_t *d_lens, const lrm_seq_meta *d_meta,
+                       const int32_t *d_meta_r, uint64_t n, uint32_t max_len, const LrmIndexView &ix, const uint64_t *qpl,
+                       uint64_t wpr, const uint32_t *rflags, const uint64_t *cpl, uint32_t min_len, uint64_t *keys,
+                       hipStream_t stream) {
+    const uint32_t nw = (max_len + 31) / 32;
+    const uint32_t segs = nw ? (nw + AN_SEG_WORDS - 1) / AN_SEG_WORDS : 1;
+    const uint64_t blocks = (n * segs + 3) / 4;
+    if (blocks > 0x7fffffffull) { lrm_set_error("anchor scan grid too large: split the batch"); return -1; }
+    HIPCHK(hipMemsetAsync(keys, 0, n * 8, stream));
+    hipLaunchKernelGGL(anchor_scan_kernel, dim3((uint32_t) blocks), dim3(256), 0, stream, d_reads, stride, d_lens, d_meta,
+                       d_meta_r, n, ix.mta, ix.content, qpl, wpr, rflags, cpl ? cpl + LRM_BS_PADW : nullptr, min_len, segs,
+                       (unsigned long long *) keys);
+    return 0;
+}
+
+int lrm_launch_extend_anchored(lrm_index *idx, lrm_workspace *ws, char *d_reads, uint64_t stride,
+                               const uint32_t *d_lens, uint64_t n, uint32_t max_len,
+                               const lrm_entry *d_best, lrm_gact_params gp, uint8_t *d_store,
+                               uint64_t store_stride, int32_t *d_n_ops, int32_t *d_score,
+                               lrm_seq_meta *d_meta, int32_t *d_meta_r, lrm_anchor *d_anchor, uint32_t min_len,
+                               const LrmMapTune &mt, void *stream_) {
+    hipStream_t stream = (hipStream_t) stream_;
+    if (n == 0) return 0;
+    if (lrm_gact_resolve_params(&gp) || anchor_min_len(min_len, &min_len)) return -1;
+    if (store_stride < lrm_anchored_store_stride(max_len)) {
+        lrm_set_error("anchored extension: store_stride %llu < 2*max_len + max_len/8 + 2 = %llu",
+                      (unsigned long long) store_stride, (unsigned long long) lrm_anchored_store_stride(max_len));
+        return -1;
+    }
+    if (!(ws->parts & LRM_WS_EXTEND) || n > ws->n_max || max_len > ws->max_len) {
+        lrm_set_error("anchored extension: workspace too small (have n=%llu len=%u with%s extension scratch, need n=%llu len=%u)",
+                      (unsigned long long) ws->n_max, ws->max_len, (ws->parts & LRM_WS_EXTEND) ? "" : "out",
+                      (unsigned long long) n, max_len);
+        return -1;
+    }
+    const bool planar = idx->d_cpl && idx->cpl_ok && ws->d_qpl;
+    if (anchor_scratch(ws, planar)) return -1;
+    LrmAnchorScratch &s = *ws->an;
+    if (lrm_launch_locus_revcomp(idx, ws, d_reads, stride, d_lens, n, max_len, d_best, d_meta, d_meta_r, stream_)) return -1;
+
+    // anchor: planar image of the oriented reads, then the scan
+    lrm_time_begin(ws, LRM_K_LOCUS, stream);
+    if (planar && lrm_bs_pack_reads(d_reads, stride, d_lens, n, max_len, ws->d_qpl, ws->qpl_wpr, ws->d_rflags, stream)) return -1;
+    if (launch_scan(d_reads, stride, d_lens, d_meta, d_meta_r, n, max_len, idx->view, planar ? ws->d_qpl : nullptr,
+                    ws->qpl_wpr, ws->d_rflags, planar ? idx->d_cpl : nullptr, min_len, s.keys, stream)) return -1;
+    lrm_time_end(ws, stream);
+
+    // jobs
+    const uint32_t chunks_rd = max_len ? (max_len + AN_CHUNK - 1) / AN_CHUNK : 1;
+    if (n * chunks_rd > 0x7fffffffull) { lrm_set_error("anchor jobs grid too large: split the batch"); return -1; }
+    lrm_time_begin(ws, LRM_K_REVCOMP, stream);
+    hipLaunchKernelGGL(anchor_jobs_kernel, dim3((uint32_t) (n * chunks_rd)), dim3(256), 0, stream, d_reads, stride, d_lens,
+                       d_meta, d_meta_r, n, idx->view.mta, idx->view.con_len, (unsigned long long *) s.keys, chunks_rd,
+                       s.job_reads, s.job_stride, s.job_lens, s.job_tlens, s.job_meta, s.job_meta_r);
+    lrm_time_end(ws, stream);
+
+    // one extension launch over the job table
+    const uint64_t jobs = 2 * n;
+    LrmBsArgs bs = {};
+    const bool want_bs = planar && lrm_bs_wanted(gp, jobs, mt.gact_impl);
+    if (want_bs) {
+        lrm_time_begin(ws, LRM_K_PACK_PLANAR, stream);
+        if (lrm_bs_pack_reads(s.job_reads, s.job_stride, s.job_lens, jobs, max_len, s.qpl, ws->qpl_wpr, s.rflags, stream)) return -1;
+        lrm_time_end(ws, stream);
+        bs.qpl = s.qpl; bs.wpr = ws->qpl_wpr; bs.flags = s.rflags; bs.cpl = idx->d_cpl;
+        bs.ckpt = s.ckpt; bs.codes = s.codes; bs.cw = s.cw; bs.ncodes = s.ncodes;
+    }
+    const int slot = want_bs ? LRM_K_GACT_BS : LRM_K_GACT;
+    lrm_time_begin(ws, slot, stream);
+    if (lrm_gact_launch_jobs(gp, jobs, stream_, s.job_reads, s.job_stride, s.job_lens, s.job_meta, s.job_meta_r,
+                             idx->view.content, s.job_tlens, s.job_store, s.job_store_stride, s.job_nops, s.job_score,
+                             ws->d_counters, want_bs ? &bs : nullptr, mt.gact_impl, mt.bs_waves)) return -1;
+    lrm_time_end(ws, stream);
+
+    // stitch
+    const uint64_t ops_max = lrm_anchored_store_stride(max_len);
+    const uint32_t chunks_op = (uint32_t) ((ops_max + AN_CHUNK - 1) / AN_CHUNK);
+    if (n * chunks_op > 0x7fffffffull) { lrm_set_error("anchor stitch grid too large: split the batch"); return -1; }
+    lrm_time_begin(ws, slot, stream);
+    hipLaunchKernelGGL(anchor_stitch_kernel, dim3((uint32_t) (n * chunks_op)), dim3(256), 0, stream, d_lens, d_meta, d_meta_r,
+                       n, idx->view.mta, (const unsigned long long *) s.keys, chunks_op, s.job_store, s.job_store_stride,
+                       s.job_nops, s.job_score, d_store, store_stride, d_n_ops, d_score, d_anchor ? d_anchor : s.anchors);
+    lrm_time_end(ws, stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int lrm_debug_anchor(lrm_index *idx, const char *read, uint32_t len, uint64_t loc, uint32_t min_len,
+                                lrm_anchor *out) {
+    if (!idx || !read || !out || len == 0) { lrm_set_error("bad argument"); return -1; }
+    if (lrm_require_device(idx->device) || anchor_min_len(min_len, &min_len)) return -1;
+    const int nm = idx->view.mta_len;
+    LrmMtaDev *hm = (LrmMtaDev *) malloc(sizeof(LrmMtaDev) * (size_t) (nm > 0 ? nm : 1));
+    if (!hm) { lrm_set_error("out of memory"); return -1; }
+    lrm_seq_meta m = {};
+    m.seq_id = -1;
+    if (hipMemcpy(hm, idx->view.mta, sizeof(LrmMtaDev) * (size_t) nm, hipMemcpyDeviceToHost) == hipSuccess)
+        for (int i = 0; i < nm && m.seq_id < 0; ++i)
+            if (loc >= hm[i].offset && loc < hm[i].offset + hm[i].seq_len) { m.seq_id = i; m.loc = loc; m.off = loc - hm[i].offset; }
+    free(hm);
+    if (m.seq_id < 0) { lrm_set_error("locus %llu is not on the forward half of a sequence", (unsigned long long) loc); return -1; }
+    struct Buf {
+        void *p = nullptr;
+        ~Buf() { if (p) (void) hipFree(p); }
+        int alloc(size_t bytes) { return hipMalloc(&p, bytes) == hipSuccess ? 0 : -1; }
+    };
+    const bool planar = idx->d_cpl && idx->cpl_ok;
+    const uint64_t wpr = lrm_bs_planar_words(len);
+    Buf br, bl, bm, bmr, bk, ba, bq, bf;
+    if (br.alloc((size_t) len + 32) || bl.alloc(16) || bm.alloc(sizeof(m)) || bmr.alloc(16) || bk.alloc(16) ||
+        ba.alloc(sizeof(lrm_anchor)) || bq.alloc(wpr * 8 + 16) || bf.alloc(16)) { lrm_set_error("device allocation failed"); return -1; }
+    const int32_t one = 1;
+    HIPCHK(hipMemcpy(br.p, read, len, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(bl.p, &len, 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(bm.p, &m, sizeof(m), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(bmr.p, &one, 4, hipMemcpyHostToDevice));
+    if (planar && lrm_bs_pack_reads((const char *) br.p, 0, (const uint32_t *) bl.p, 1, len, (uint64_t *) bq.p, wpr,
+                                    (uint32_t *) bf.p, nullptr)) return -1;
+    if (launch_scan((const char *) br.p, 0, (const uint32_t *) bl.p, (const lrm_seq_meta *) bm.p, (const int32_t *) bmr.p, 1,
+                    len, idx->view, planar ? (const uint64_t *) bq.p : nullptr, wpr, (const uint32_t *) bf.p,
+                    planar ? idx->d_cpl : nullptr, min_len, (uint64_t *) bk.p, nullptr)) return -1;
+    hipLaunchKernelGGL(anchor_record_kernel, dim3(1), dim3(1), 0, nullptr, (const uint32_t *) bl.p, (const lrm_seq_meta *) bm.p,
+                       idx->view.mta, (const unsigned long long *) bk.p, (lrm_anchor *) ba.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, ba.p, sizeof(lrm_anchor), hipMemcpyDeviceToHost));
+    return 0;
+}

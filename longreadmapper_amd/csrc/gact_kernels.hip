@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include "lrm_internal.h"
+#include "seq_bytes.h"
 
 #define GACT_NEG (-(1 << 28))
 #define DPP_WAVE_SHL1 0x130  // lane L <- lane L+1
@@ -58,33 +59,6 @@ __global__ __launch_bounds__(256) void locus_resolve_kernel(LrmIndexView ix, con
     if (!mr) { m.loc = 0; m.off = 0; m.seq_id = -1; m.strand = 0; }
     meta[read] = m;
     meta_r[read] = mr;
-}
-
-// alnmain.c:31-52: A/a -> T, C/c -> G, G/g -> C, T/t -> A, anything else -> N.  Branch-free on purpose: a `switch`
-// compiles to a cascade of divergent branches per byte (the first revcomp kernel spent 1.5 ms per Gbp in them).
-__device__ __forceinline__ char comp_base(char c) {
-    const uint32_t u = (uint32_t) (uint8_t) c & 0xDFu;            // fold case
-    uint32_t r = 'N';
-    r = u == 'A' ? 'T' : r;
-    r = u == 'C' ? 'G' : r;
-    r = u == 'G' ? 'C' : r;
-    r = u == 'T' ? 'A' : r;
-    return (char) r;
-}
-
-__device__ __forceinline__ uint32_t bytes_equal(uint32_t x, uint32_t c4) {     // 0xFF in every byte of x equal to c4's
-    const uint32_t z = x ^ c4;
-    const uint32_t t = ~(((z & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | z | 0x7F7F7F7Fu);  // 0x80 where the byte of z is zero
-    return (t >> 7) * 0xFFu;
-}
-
-__device__ __forceinline__ uint32_t revcomp4(uint32_t w) {       // 4 bases: reversed and complemented
-    const uint32_t x = w & 0xDFDFDFDFu;
-    const uint32_t a = bytes_equal(x, 0x41414141u), c = bytes_equal(x, 0x43434343u);
-    const uint32_t g = bytes_equal(x, 0x47474747u), t = bytes_equal(x, 0x54545454u);
-    const uint32_t o = (a & 0x54545454u) | (c & 0x47474747u) | (g & 0x43434343u) | (t & 0x41414141u) |
-                       (~(a | c | g | t) & 0x4E4E4E4Eu);
-    return __builtin_bswap32(o);
 }
 
 // In place, with ALIGNED 16-byte accesses only (rows start at any byte: stride = max_read_len + 1).  A workgroup owns
@@ -727,6 +701,49 @@ static int gact_launch(lrm_gact_params gp, uint64_t n, hipStream_t stream, const
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
     lrm_set_error("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); return -1; } } while (0)
 
+// {0,0,0} selects the defaults; the limits are those of the kernels
+int lrm_gact_resolve_params(lrm_gact_params *gp) {
+    if (gp->T == 0 && gp->O == 0 && gp->W == 0) {
+        gp->T = LRM_GACT_T_DEFAULT; gp->O = LRM_GACT_O_DEFAULT; gp->W = LRM_GACT_W_DEFAULT;
+    }
+    if (gp->T < 16 || gp->T > 512 || gp->O < 0 || gp->O >= gp->T || gp->W < 2 || (gp->W & 1) || gp->W > 1024) {
+        lrm_set_error("unsupported GACT parameters T=%d O=%d W=%d (need 16<=T<=512, 0<=O<T, even 2<=W<=1024)",
+                      gp->T, gp->O, gp->W);
+        return -1;
+    }
+    return 0;
+}
+
+// locus_resolve + in-place reverse complement: what both extension modes start with
+int lrm_launch_locus_revcomp(lrm_index *idx, lrm_workspace *ws, char *d_reads, uint64_t stride, const uint32_t *d_lens,
+                             uint64_t n, uint32_t max_len, const lrm_entry *d_best, lrm_seq_meta *d_meta,
+                             int32_t *d_meta_r, void *stream_) {
+    hipStream_t stream = (hipStream_t) stream_;
+    lrm_time_begin(ws, LRM_K_LOCUS, stream);
+    hipLaunchKernelGGL(locus_resolve_kernel, dim3((uint32_t) ((n + 255) / 256)), dim3(256), 0, stream,
+                       idx->view, d_best, d_lens, n, d_meta, d_meta_r);
+    lrm_time_end(ws, stream);
+    const uint32_t half = max_len / 2 + 1;
+    const uint32_t cpr = (half + RC_SEG - 1) / RC_SEG;                                  // workgroups per read
+    const uint32_t seg = ((half + cpr - 1) / cpr + 15) & ~15u;                           // <= RC_SEG bases each
+    uint64_t blocks = n * cpr;
+    if (blocks > 0x7fffffffull) { lrm_set_error("revcomp grid too large: split the batch"); return -1; }
+    lrm_time_begin(ws, LRM_K_REVCOMP, stream);
+    hipLaunchKernelGGL(revcomp_kernel, dim3((uint32_t) blocks), dim3(256), 0, stream, d_reads, stride,
+                       d_lens, d_meta, d_meta_r, n, cpr, seg);
+    lrm_time_end(ws, stream);
+    return 0;
+}
+
+// the extension proper over a table of jobs (anchor_kernels.hip builds one; the classic mode's table is the batch itself)
+int lrm_gact_launch_jobs(lrm_gact_params gp, uint64_t n, void *stream, const char *reads, uint64_t stride,
+                         const uint32_t *lens, const lrm_seq_meta *meta, const int32_t *meta_r, const char *content,
+                         const uint32_t *tlens, uint8_t *store, uint64_t store_stride, int32_t *n_ops, int32_t *score,
+                         LrmDevCounters *counters, const LrmBsArgs *bs, int impl, uint32_t bs_waves) {
+    return gact_launch(gp, n, (hipStream_t) stream, reads, stride, lens, meta, meta_r, content, tlens, store, store_stride,
+                       n_ops, score, counters, bs, impl, bs_waves);
+}
+
 int lrm_launch_extend(lrm_index *idx, lrm_workspace *ws, char *d_reads, uint64_t stride,
                       const uint32_t *d_lens, uint64_t n, uint32_t max_len,
                       const lrm_entry *d_best, lrm_gact_params gp, uint8_t *d_store,
@@ -734,33 +751,15 @@ int lrm_launch_extend(lrm_index *idx, lrm_workspace *ws, char *d_reads, uint64_t
                       lrm_seq_meta *d_meta, int32_t *d_meta_r, const LrmMapTune &mt, void *stream_) {
     hipStream_t stream = (hipStream_t) stream_;
     if (n == 0) return 0;
-    if (gp.T == 0 && gp.O == 0 && gp.W == 0) {
-        gp.T = LRM_GACT_T_DEFAULT; gp.O = LRM_GACT_O_DEFAULT; gp.W = LRM_GACT_W_DEFAULT;
-    }
-    if (gp.T < 16 || gp.T > 512 || gp.O < 0 || gp.O >= gp.T || gp.W < 2 || (gp.W & 1) || gp.W > 1024) {
-        lrm_set_error("unsupported GACT parameters T=%d O=%d W=%d (need 16<=T<=512, 0<=O<T, even 2<=W<=1024)",
-                      gp.T, gp.O, gp.W);
-        return -1;
-    }
+    if (mt.anchored)                                       // anchor_kernels.hip; nothing below is reached
+        return lrm_launch_extend_anchored(idx, ws, d_reads, stride, d_lens, n, max_len, d_best, gp, d_store, store_stride,
+                                          d_n_ops, d_score, d_meta, d_meta_r, nullptr, mt.anchor_min_len, mt, stream_);
+    if (lrm_gact_resolve_params(&gp)) return -1;
     if (store_stride < 2ull * max_len) {
         lrm_set_error("store_stride %llu < 2*max_len %u", (unsigned long long) store_stride, max_len);
         return -1;
     }
-    lrm_time_begin(ws, LRM_K_LOCUS, stream);
-    hipLaunchKernelGGL(locus_resolve_kernel, dim3((uint32_t) ((n + 255) / 256)), dim3(256), 0, stream,
-                       idx->view, d_best, d_lens, n, d_meta, d_meta_r);
-    lrm_time_end(ws, stream);
-    {
-        const uint32_t half = max_len / 2 + 1;
-        const uint32_t cpr = (half + RC_SEG - 1) / RC_SEG;                                  // workgroups per read
-        const uint32_t seg = ((half + cpr - 1) / cpr + 15) & ~15u;                           // <= RC_SEG bases each
-        uint64_t blocks = n * cpr;
-        if (blocks > 0x7fffffffull) { lrm_set_error("revcomp grid too large: split the batch"); return -1; }
-        lrm_time_begin(ws, LRM_K_REVCOMP, stream);
-        hipLaunchKernelGGL(revcomp_kernel, dim3((uint32_t) blocks), dim3(256), 0, stream, d_reads, stride,
-                           d_lens, d_meta, d_meta_r, n, cpr, seg);
-        lrm_time_end(ws, stream);
-    }
+    if (lrm_launch_locus_revcomp(idx, ws, d_reads, stride, d_lens, n, max_len, d_best, d_meta, d_meta_r, stream_)) return -1;
     LrmBsArgs bs = {};
     const bool want_bs = lrm_bs_wanted(gp, n, mt.gact_impl) && idx->d_cpl && idx->cpl_ok && ws->d_qpl && n <= ws->n_max &&
                          max_len <= ws->max_len;

@@ -696,6 +696,20 @@ struct StageError {                                      // lrm_last_error() is 
 // AND be parallel.  Output is identical: batches are written in input order.
 extern "C" int lrm_accaln(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
                           lrm_gact_params gp, int device, long rg_id, uint64_t *total_out, uint64_t *valid_out) {
+    return lrm_accaln_opt(genome, reads_path, sam_path, p, gp, device, rg_id, total_out, valid_out, nullptr);
+}
+
+// user: only the fields that change WHAT is computed are taken (anchored, anchor_min_len); the shape of the pipeline is this
+// function's own choice
+extern "C" int lrm_accaln_opt(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
+                              lrm_gact_params gp, int device, long rg_id, uint64_t *total_out, uint64_t *valid_out,
+                              const lrm_map_options *user) {
+    const bool anchored = user && user->struct_size >= offsetof(lrm_map_options, anchor_min_len) + sizeof(uint32_t) && user->anchored;
+    // op bytes per read: alnmain.c:316-320, a multiple of 16; the anchored mode's targets are an eighth longer than the reads
+    auto store_stride_of = [anchored](uint64_t max_len) {
+        const uint64_t s = ((anchored ? 2 * max_len + max_len / 8 + 2 : 2 * max_len) + 15) & ~15ull;
+        return s > 0 ? s : (uint64_t) 16;
+    };
     const bool verbose = getenv("LRM_HOST_VERBOSE") != nullptr;            // stage times on stderr (tuning aid)
     auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t_load = 0, t_map = 0, t_fmt = 0, t_write = 0;
@@ -740,6 +754,7 @@ extern "C" int lrm_accaln(const char *genome, const char *reads_path, const char
         mopt.cigar_text = 1;                        // parse_cigar (alnmain.c:497-498) runs on the device: the SAM CIGAR text comes back
         mopt.copy_threads = 2;                      // the parser and the formatter need the cores
         mopt.keep_reads = 1;                        // reverse-strand reads are reverse-complemented by the formatter as it copies them
+        if (anchored) { mopt.anchored = 1; mopt.anchor_min_len = user->anchor_min_len; }
         // Pinning the batch buffers (0.2 s per GB to pin and to release, and the device stalls while the runtime pins)
         // pays from a few tens of Gbp on: reads files below 16 GiB run through pageable buffers.
         bool want_pinned = false;
@@ -782,7 +797,7 @@ extern "C" int lrm_accaln(const char *genome, const char *reads_path, const char
                 if (n == 0) { BatchSet *q = s; free_sets.push(std::move(q)); break; }
                 if (!dims_known) {
                     std::lock_guard<std::mutex> lk(dims_m);
-                    const uint64_t rb = s->b.n * s->b.stride, sb = s->b.n * ((((uint64_t) s->b.max_len * 2 + 15) & ~15ull) + 16);
+                    const uint64_t rb = s->b.n * s->b.stride, sb = s->b.n * (store_stride_of(s->b.max_len) + 16);
                     dim_reads = rb + rb / 8 + 4096; dim_store = sb + sb / 8 + 4096;
                     dims_known = true;
                     dims_cv.notify_all();
@@ -861,7 +876,7 @@ extern "C" int lrm_accaln(const char *genome, const char *reads_path, const char
             if (err.get()) { lrm_read_batch_free(&s->b); BatchSet *q = s; free_sets.push(std::move(q)); continue; }   // drain what the loader already parsed
             const size_t n = (size_t) s->b.n;
             s->best.resize(n); s->cig.resize(n); s->score.resize(n); s->meta_r.resize(n); s->meta.resize(n);
-            s->sstride = (((uint64_t) s->b.max_len * 2 + 15) & ~15ull) > 0 ? (((uint64_t) s->b.max_len * 2 + 15) & ~15ull) : 16;   // alnmain.c:316-320, a multiple of 16
+            s->sstride = store_stride_of(s->b.max_len);
             if (s->pin_ready.load(std::memory_order_acquire) && n * s->sstride <= s->store_cap) {
                 s->store = s->store_pin;
             } else {

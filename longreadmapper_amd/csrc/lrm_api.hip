@@ -146,6 +146,8 @@ void lrm_resolve_map_tune(const lrm_map_options *opt, const LrmEnv &env, LrmMapT
     t->slice_reads = o.slice_reads; t->sub_batches = o.sub_batches; t->group_subs = o.group_subs; t->bs_waves = o.bs_waves;
     t->copy_threads = o.copy_threads <= 16 ? o.copy_threads : 16;
     t->keep_reads = o.keep_reads != 0;
+    t->anchored = o.anchored != 0;
+    t->anchor_min_len = o.anchor_min_len;
     // measured defaults of the kernel knobs (tools/seed_probe.py sweeps them through the environment)
     t->ss_items = 2048; t->vote_vg = 16; t->vote_t1 = LRM_VOTE_T1_LIMIT; t->vote_u = 2; t->vote_load = 50; t->vote_fast = o.vote_exact_only ? 0 : 1;
     t->ext_streams = 2; t->seed_streams = 2;
@@ -856,6 +858,7 @@ extern "C" void lrm_workspace_free(lrm_workspace *ws) {
     (void) hipFree(ws->d_hcount); (void) hipFree(ws->d_counters); (void) hipFree(ws->d_recq); (void) hipFree(ws->d_cnt); (void) hipFree(ws->d_kc_key); (void) hipFree(ws->d_kc_ord); (void) hipFree(ws->d_redo); (void) hipFree(ws->d_big); (void) hipFree(ws->d_gtab); (void) hipFree(ws->d_glock);
     (void) hipFree(ws->d_qpl); (void) hipFree(ws->d_rflags);
     (void) hipFree(ws->d_ckpt); (void) hipFree(ws->d_codes); (void) hipFree(ws->d_ncodes);
+    lrm_anchor_scratch_free(ws);
     if (ws->h_err) (void) hipHostFree((void *) ws->h_err);
     for (int i = 0; i < LRM_MAX_TIMED; ++i) {
         if (ws->ev_start[i]) (void) hipEventDestroy((hipEvent_t) ws->ev_start[i]);
@@ -1024,6 +1027,22 @@ extern "C" int lrm_workspace_stats(lrm_workspace *ws, lrm_stats *out, void *stre
     out->seed_table_lookups = c.reserved[4];
     out->seed_rank_requests = c.reserved[5];
     return lrm_ws_take_error(ws);
+}
+extern "C" int lrm_extend_batch_anchored_dev(lrm_index *idx, lrm_workspace *ws, char *d_reads, uint64_t stride,
+                                             const uint32_t *d_lens, uint64_t n, uint32_t max_len, const lrm_entry *d_best,
+                                             lrm_gact_params gp, uint8_t *d_store, uint64_t store_stride, int32_t *d_n_ops,
+                                             int32_t *d_score, lrm_seq_meta *d_meta, int32_t *d_meta_r, lrm_anchor *d_anchor,
+                                             uint32_t min_len, void *stream) {
+    if (!idx || !ws || !d_reads || !d_lens || !d_best || !d_store || !d_n_ops || !d_score || !d_meta || !d_meta_r) {
+        lrm_set_error("null argument");
+        return -1;
+    }
+    if (ws->idx != idx) { lrm_set_error("workspace does not belong to this index"); return -1; }
+    if (lrm_ws_take_error(ws)) return -2;
+    HIPCHK(hipSetDevice(idx->device));
+    if (n == 0) return 0;
+    return lrm_launch_extend_anchored(idx, ws, d_reads, stride, d_lens, n, max_len, d_best, gp, d_store, store_stride,
+                                      d_n_ops, d_score, d_meta, d_meta_r, d_anchor, min_len, idx->mtune, stream);
 }
 
 // ------------------------------------------------------------------------------------------

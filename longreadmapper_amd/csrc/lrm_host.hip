@@ -939,6 +939,11 @@ int submit_impl(lrm_index *idx, const MapJob &j, const lrm_map_options *opt, lrm
     const uint32_t max_len = max_of(j.lens, j.n);
     if (j.stride < max_len) { lrm_set_error("stride < longest read"); return -1; }
     if ((j.mode & DO_EXTEND) && j.store_stride < 2ull * max_len) { lrm_set_error("store_stride < 2 * longest read (alnmain.c:316-320)"); return -1; }
+    if ((j.mode & DO_EXTEND) && mt.anchored && j.store_stride < lrm_anchored_store_stride(max_len)) {
+        lrm_set_error("anchored extension: store_stride %llu < 2 * longest read + longest read / 8 + 2 = %llu",
+                      (unsigned long long) j.store_stride, (unsigned long long) lrm_anchored_store_stride(max_len));
+        return -1;
+    }
     if ((j.mode & DO_EXTEND) && mt.dense && (j.store_stride & 15u)) { lrm_set_error("dense results need store_stride to be a multiple of 16"); return -1; }
     std::unique_ptr<lrm_ticket> t(new lrm_ticket);
     if (j.n) {

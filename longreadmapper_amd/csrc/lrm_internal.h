@@ -112,7 +112,8 @@ struct LrmIndexTune {
     uint64_t lcx_threshold;
 };
 struct LrmMapTune {
-    int dense, gact_impl, seed_rounds, cigar_text, keep_reads;
+    int dense, gact_impl, seed_rounds, cigar_text, keep_reads, anchored;
+    uint32_t anchor_min_len;        // 0: LRM_ANCHOR_MIN_DEFAULT
     uint32_t slice_reads, sub_batches, group_subs, bs_waves, copy_threads;
     uint32_t ss_items, ss_lds_pad, vote_vg, vote_t1, vote_u, vote_load, vote_fast;      // kernel tuning (environment only; measured defaults)
     uint32_t t3_limit, t3_slots;                                 // lrm_debug_set_vote_limits (tests)
@@ -231,6 +232,7 @@ struct lrm_workspace {
     uint64_t *d_codes;       // 2-bit CIGAR codes (expanded to bytes by bs_expand_kernel)
     uint64_t codes_cw;
     int32_t *d_ncodes;
+    struct LrmAnchorScratch *an;   // anchored mode (anchor_kernels.hip): allocated by its first call on this workspace
 };
 
 #define LRM_BS_PADW 24       // planar words of padding on either side of a packed sequence
@@ -279,6 +281,24 @@ int lrm_launch_extend(lrm_index *idx, lrm_workspace *ws, char *d_reads, uint64_t
                       const lrm_entry *d_best, lrm_gact_params gp, uint8_t *d_store,
                       uint64_t store_stride, int32_t *d_n_ops, int32_t *d_score,
                       lrm_seq_meta *d_meta, int32_t *d_meta_r, const LrmMapTune &mt, void *stream);
+// anchored extension (anchor_kernels.hip); the helpers it shares with the classic mode live in gact_kernels.hip
+#define LRM_ANCHOR_MIN_DEFAULT 20
+int lrm_gact_resolve_params(lrm_gact_params *gp);
+int lrm_launch_locus_revcomp(lrm_index *idx, lrm_workspace *ws, char *d_reads, uint64_t stride, const uint32_t *d_lens,
+                             uint64_t n, uint32_t max_len, const lrm_entry *d_best, lrm_seq_meta *d_meta,
+                             int32_t *d_meta_r, void *stream);
+int lrm_gact_launch_jobs(lrm_gact_params gp, uint64_t n, void *stream, const char *reads, uint64_t stride,
+                         const uint32_t *lens, const lrm_seq_meta *meta, const int32_t *meta_r, const char *content,
+                         const uint32_t *tlens, uint8_t *store, uint64_t store_stride, int32_t *n_ops, int32_t *score,
+                         LrmDevCounters *counters, const LrmBsArgs *bs, int impl, uint32_t bs_waves);
+int lrm_launch_extend_anchored(lrm_index *idx, lrm_workspace *ws, char *d_reads, uint64_t stride,
+                               const uint32_t *d_lens, uint64_t n, uint32_t max_len,
+                               const lrm_entry *d_best, lrm_gact_params gp, uint8_t *d_store,
+                               uint64_t store_stride, int32_t *d_n_ops, int32_t *d_score,
+                               lrm_seq_meta *d_meta, int32_t *d_meta_r, lrm_anchor *d_anchor, uint32_t min_len,
+                               const LrmMapTune &mt, void *stream);
+void lrm_anchor_scratch_free(lrm_workspace *ws);
+static inline uint64_t lrm_anchored_store_stride(uint32_t max_len) { return 2ull * max_len + max_len / 8 + 2; }
 int lrm_launch_debug_seed(lrm_index *idx, const char *d_read, uint32_t len, uint32_t seed_len,
                           uint64_t *d_reads2, uint64_t words, int32_t *d_j, uint64_t *d_rr,
                           uint64_t *d_k, uint64_t *d_l, uint64_t cap, void *stream);

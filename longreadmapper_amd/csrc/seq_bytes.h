@@ -1,0 +1,31 @@
+// seq_bytes.h -- byte-level base helpers shared by the extension-stage kernels (device code only)
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+// alnmain.c:31-52: A/a -> T, C/c -> G, G/g -> C, T/t -> A, anything else -> N.  Branch-free on purpose: a `switch`
+// compiles to a cascade of divergent branches per byte (the first revcomp kernel spent 1.5 ms per Gbp in them).
+__device__ __forceinline__ char comp_base(char c) {
+    const uint32_t u = (uint32_t) (uint8_t) c & 0xDFu;            // fold case
+    uint32_t r = 'N';
+    r = u == 'A' ? 'T' : r;
+    r = u == 'C' ? 'G' : r;
+    r = u == 'G' ? 'C' : r;
+    r = u == 'T' ? 'A' : r;
+    return (char) r;
+}
+
+__device__ __forceinline__ uint32_t bytes_equal(uint32_t x, uint32_t c4) {     // 0xFF in every byte of x equal to c4's
+    const uint32_t z = x ^ c4;
+    const uint32_t t = ~(((z & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | z | 0x7F7F7F7Fu);  // 0x80 where the byte of z is zero
+    return (t >> 7) * 0xFFu;
+}
+
+__device__ __forceinline__ uint32_t revcomp4(uint32_t w) {       // 4 bases: reversed and complemented
+    const uint32_t x = w & 0xDFDFDFDFu;
+    const uint32_t a = bytes_equal(x, 0x41414141u), c = bytes_equal(x, 0x43434343u);
+    const uint32_t g = bytes_equal(x, 0x47474747u), t = bytes_equal(x, 0x54545454u);
+    const uint32_t o = (a & 0x54545454u) | (c & 0x47474747u) | (g & 0x43434343u) | (t & 0x41414141u) |
+                       (~(a | c | g | t) & 0x4E4E4E4Eu);
+    return __builtin_bswap32(o);
+}

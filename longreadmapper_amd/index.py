@@ -3,6 +3,7 @@
 Mirrors the reference's index life cycle: `accidx` (asindex.c) builds the five files,
 `init()` (alnmain.c:179-256) loads them; here `HostIndex.build()/read()` produce the same
 in-memory structs and `DeviceIndex` holds their MI355X image."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -165,6 +166,18 @@ class DeviceIndex:
     def set_map_options(self, **opts):
         """Default lrm_map_options of the batch calls on this handle (no arguments: the automatic choices)."""
         check(lib.lrm_index_set_map_options(self.handle, C.byref(capi.map_options(**opts))), "lrm_index_set_map_options")
+        self._map_opts = dict(opts)
+
+    @contextlib.contextmanager
+    def map_options_plus(self, **extra):
+        """The handle's default lrm_map_options with `extra` on top for the duration of a `with` block."""
+        saved = dict(getattr(self, "_map_opts", {}))
+        self.set_map_options(**{**saved, **extra})
+        try:
+            yield self
+        finally:
+            if self.handle:
+                self.set_map_options(**saved)
 
     def tables(self):
         """The derived seed tables this handle ended up with (lrm_index_get_tables) as a dict."""

@@ -18,6 +18,28 @@ DEFAULT_SEED_LEN = 20      # alnmain.c:577-580
 DEFAULT_THRES = 300
 DEFAULT_GACT = (320, 120, 128)
 N_KERNELS = 9              # LRM_N_KERNELS in include/lrm_accel.h
+ANCHOR_DT = np.dtype([("text_pos", "<u8"), ("read_pos", "<u4"), ("len", "<u4"), ("delta", "<i4"), ("left_ops", "<u4"),
+                      ("flags", "<u4"), ("_pad", "V4")])      # lrm_anchor
+assert ANCHOR_DT.itemsize == 32
+
+
+def anchored_store_stride(max_len):
+    """Op bytes per read the anchored mode needs: both jobs' targets are an eighth longer than their queries."""
+    return 2 * max_len + max_len // 8 + 2
+
+
+def _anchor_options(options, anchored, anchor_min_len):
+    if not anchored:
+        return options
+    return {**(options or {}), "anchored": 1, "anchor_min_len": anchor_min_len}
+
+
+def debug_anchor(index, read, loc, min_len=0):
+    """lrm_debug_anchor: the anchor of one forward-oriented read at one voted locus -> dict of the lrm_anchor fields."""
+    read = np.ascontiguousarray(read, dtype=np.uint8)
+    a = capi.Anchor()
+    check(lib.lrm_debug_anchor(index.handle, read.ctypes.data, len(read), loc, min_len, C.byref(a)), "lrm_debug_anchor")
+    return {f: int(getattr(a, f)) for f, _ in a._fields_}
 
 
 def seed_batch(index, reads, lens, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES):
@@ -32,16 +54,24 @@ def seed_batch(index, reads, lens, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRE
     return best
 
 
-def extend_batch(index, reads, lens, best, gact=DEFAULT_GACT):
+def extend_batch(index, reads, lens, best, gact=DEFAULT_GACT, anchored=False, anchor_min_len=0):
     """Host buffers; `reads` is modified in place (reverse-strand reads are rev-comped).
+    anchored: the anchored extension mode (lrm_map_options.anchored) for this call, on top of the handle's options.
 
     Returns dict(ops=(n, store_stride) uint8, n_ops, score, meta, meta_r)."""
+    if anchored:
+        with index.map_options_plus(anchored=1, anchor_min_len=anchor_min_len):
+            return _extend_batch(index, reads, lens, best, gact, True)
+    return _extend_batch(index, reads, lens, best, gact, False)
+
+
+def _extend_batch(index, reads, lens, best, gact, anchored):
     assert reads.dtype == np.uint8 and reads.flags.c_contiguous and reads.flags.writeable
     lens = np.ascontiguousarray(lens, dtype=np.uint32)
     best = np.ascontiguousarray(best, dtype=ENTRY_DT)
     n, stride = reads.shape
     max_len = int(lens.max()) if n else 0
-    store_stride = max(2 * max_len, 1)                    # alnmain.c:316-320
+    store_stride = anchored_store_stride(max_len) if anchored else max(2 * max_len, 1)     # alnmain.c:316-320
     store = np.zeros((n, store_stride), dtype=np.uint8)
     cig = (capi.Cigar * max(n, 1))()
     score = np.zeros(n, dtype=np.int32)
@@ -116,16 +146,20 @@ def ops_of(res, i):
 
 
 def map_batch_submit(index, reads, lens, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT, store=None,
-                     options=None):
+                     options=None, anchored=False, anchor_min_len=0):
     """lrm_map_batch_submit: queues the batch and returns a PendingBatch.  `reads` is modified in place like
-    extend_batch once the batch runs; `store` may be a caller-provided (n, >= 2*max_len) uint8 array (e.g. pinned);
-    `options`: dict of lrm_map_options fields (None: the handle's defaults)."""
+    extend_batch once the batch runs; `store` may be a caller-provided (n, >= 2*max_len) uint8 array (e.g. pinned;
+    anchored: >= anchored_store_stride(max_len)); `options`: dict of lrm_map_options fields (None: the handle's
+    defaults); anchored=True adds the anchored extension mode to them."""
     assert reads.dtype == np.uint8 and reads.flags.c_contiguous and reads.flags.writeable
+    options = _anchor_options(options, anchored, anchor_min_len)
+    anchored = bool(options and options.get("anchored"))
     lens = np.ascontiguousarray(lens, dtype=np.uint32)
     n, stride = reads.shape
     max_len = int(lens.max()) if n else 0
     if store is None:
-        store = np.zeros((n, max((2 * max_len + 15) // 16 * 16, 16)), dtype=np.uint8)
+        need = anchored_store_stride(max_len) if anchored else 2 * max_len
+        store = np.zeros((n, max((need + 15) // 16 * 16, 16)), dtype=np.uint8)
     store_stride = store.shape[1]
     best = np.zeros(n, dtype=ENTRY_DT)
     cig = (capi.Cigar * max(n, 1))()
@@ -145,9 +179,11 @@ def map_batch_submit(index, reads, lens, seed_len=DEFAULT_SEED_LEN, thres=DEFAUL
 
 
 def map_batch(index, reads, lens, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT, store=None,
-              options=None):
+              options=None, anchored=False, anchor_min_len=0):
     """PART 1 + PART 2 in one device pass; `reads` is modified in place like extend_batch.
-    Without `options` this is lrm_map_batch (the handle's default options), with them submit + wait."""
+    Without `options` this is lrm_map_batch (the handle's default options), with them (or with anchored=True, which
+    is one of them) submit + wait."""
+    options = _anchor_options(options, anchored, anchor_min_len)
     if options is not None:
         return map_batch_submit(index, reads, lens, seed_len, thres, gact, store, options).wait()
     assert reads.dtype == np.uint8 and reads.flags.c_contiguous and reads.flags.writeable
@@ -188,7 +224,7 @@ class DeviceMapper:
     current stream (so torch.cuda.Event brackets them)."""
 
     def __init__(self, index, n_max, max_len, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT,
-                 device=0):
+                 device=0, anchored=False, anchor_min_len=0):
         import torch
         self.torch = torch
         self.index = index
@@ -199,13 +235,16 @@ class DeviceMapper:
         check(lib.lrm_workspace_create(C.byref(ws), index.handle, n_max, max_len, seed_len, thres),
               "lrm_workspace_create")
         self.ws = ws
-        self.store_stride = 2 * max_len
+        self.anchored, self.anchor_min_len = bool(anchored), anchor_min_len
+        # anchored: lrm_extend_batch_anchored_dev, results() also returns the lrm_anchor records
+        self.store_stride = (anchored_store_stride(max_len) + 15) // 16 * 16 if anchored else 2 * max_len
         self.best = torch.zeros((n_max, 3), dtype=torch.int64, device=self.dev)       # lrm_entry
         self.store = torch.zeros((n_max, self.store_stride), dtype=torch.uint8, device=self.dev)
         self.n_ops = torch.zeros(n_max, dtype=torch.int32, device=self.dev)
         self.score = torch.zeros(n_max, dtype=torch.int32, device=self.dev)
         self.meta = torch.zeros((n_max, 24), dtype=torch.uint8, device=self.dev)      # lrm_seq_meta
         self.meta_r = torch.zeros(n_max, dtype=torch.int32, device=self.dev)
+        self.anchor = torch.zeros((n_max, 32), dtype=torch.uint8, device=self.dev) if anchored else None     # lrm_anchor
 
     def workspace_bytes(self):
         return int(lib.lrm_workspace_bytes(self.ws))
@@ -223,6 +262,14 @@ class DeviceMapper:
     def extend(self, d_reads, d_lens, n=None):
         n = d_reads.shape[0] if n is None else n
         gp = capi.GactParams(*self.gact)
+        if self.anchored:
+            check(lib.lrm_extend_batch_anchored_dev(self.index.handle, self.ws, d_reads.data_ptr(), d_reads.stride(0),
+                                                    d_lens.data_ptr(), n, self.max_len, self.best.data_ptr(), gp,
+                                                    self.store.data_ptr(), self.store_stride, self.n_ops.data_ptr(),
+                                                    self.score.data_ptr(), self.meta.data_ptr(), self.meta_r.data_ptr(),
+                                                    self.anchor.data_ptr(), self.anchor_min_len, self._stream()),
+                  "lrm_extend_batch_anchored_dev")
+            return
         check(lib.lrm_extend_batch_dev(self.index.handle, self.ws, d_reads.data_ptr(), d_reads.stride(0),
                                        d_lens.data_ptr(), n, self.max_len, self.best.data_ptr(), gp,
                                        self.store.data_ptr(), self.store_stride, self.n_ops.data_ptr(),
@@ -258,8 +305,11 @@ class DeviceMapper:
         out = np.zeros(n, dtype=ENTRY_DT)
         out["key"], out["val"], out["bucket"] = best[:, 0], best[:, 1], best[:, 2]
         meta = self.meta[:n].cpu().numpy().reshape(-1).view(META_DT)
-        return dict(best=out, ops=self.store[:n].cpu().numpy(), n_ops=self.n_ops[:n].cpu().numpy(),
-                    score=self.score[:n].cpu().numpy(), meta=meta, meta_r=self.meta_r[:n].cpu().numpy())
+        res = dict(best=out, ops=self.store[:n].cpu().numpy(), n_ops=self.n_ops[:n].cpu().numpy(),
+                   score=self.score[:n].cpu().numpy(), meta=meta, meta_r=self.meta_r[:n].cpu().numpy())
+        if self.anchored:
+            res["anchor"] = self.anchor[:n].cpu().numpy().reshape(-1).view(ANCHOR_DT)
+        return res
 
     def close(self):
         if self.ws:

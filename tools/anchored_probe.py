@@ -1,0 +1,49 @@
+"""Probe (run on the GPU box): what the anchored extension mode costs.  The bench workload (ONT reads on an E. coli-sized
+text) and a PacBio-CLR workload, HBM-resident through DeviceMapper with launch timing: classic vs anchored, a warm-up and
+three timed repeats each, ms per kernel slot (mean, and the spread of the per-repeat totals), and the median ED / len.
+    python tools/anchored_probe.py          PROBE_READS / PROBE_LEN / PROBE_REF scale it down"""
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from longreadmapper_amd import index, mapper, synth
+
+REPEATS = 3
+n = int(os.environ.get("PROBE_READS", "100000"))
+ref_len = int(os.environ.get("PROBE_REF", "4641652"))
+ref = synth.reference(ref_len, seed=1, repeat_frac=0.05, rep_len=300, rep_copies=1000, rep_div=0.05)
+hi = index.HostIndex.build([ref], hlen=12)
+di = index.DeviceIndex.upload(hi, 0)
+for name, profile, length, count in (("bench workload (ONT 10 kbp)", synth.ONT, int(os.environ.get("PROBE_LEN", "10000")), n),
+                                     ("PacBio CLR 15 kbp", synth.PACBIO_CLR, 15000, max(n // 5, 1))):
+    r = synth.reads([ref], count, length, profile, seed=11)
+    d_lens = torch.from_numpy(r["lens"].astype(np.int32)).cuda()
+    print("%s: %d reads, %.2f Gbp" % (name, count, float(r["lens"].sum()) / 1e9), flush=True)
+    for anchored in (False, True):
+        dm = mapper.DeviceMapper(di, count, length, anchored=anchored)
+        per_slot, totals = {}, []
+        for rep in range(REPEATS + 1):                      # the first one warms up (and allocates the mode's scratch)
+            d_reads = torch.from_numpy(r["reads"]).cuda()   # the extension reverse-complements in place: a fresh copy
+            dm.seed(d_reads, d_lens)
+            torch.cuda.synchronize()
+            dm.set_timing(rep > 0)
+            dm.extend(d_reads, d_lens)
+            torch.cuda.synchronize()
+            if rep > 0:
+                t = dm.timing()
+                totals.append(sum(ms for ms, _ in t.values()))
+                for k, (ms, launches) in t.items():
+                    if launches:
+                        per_slot[k] = per_slot.get(k, 0.0) + ms / REPEATS
+        res = dm.results(count)
+        ok = res["score"] >= 0
+        print("  %-8s extension %.2f ms (min %.2f, max %.2f)  median ED/len %.4f  workspace %.2f GiB" %
+              ("anchored" if anchored else "classic", np.mean(totals), min(totals), max(totals),
+               float(np.median(res["score"][ok] / r["lens"][ok])), dm.workspace_bytes() / 2.0**30))
+        print("           " + "  ".join("%s %.2f" % (k.replace("_kernel", ""), v) for k, v in per_slot.items()), flush=True)
+        dm.close()
+        del dm
+di.close()
