@@ -17,11 +17,8 @@
 // is reduced as one 64-bit key and merged into the read's key with one atomicMax per segment.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
-#include "lrm_internal.h"
+#include "lrm_hip_util.h"
 #include "seq_bytes.h"
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-    lrm_set_error("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); return -1; } } while (0)
 
 #define AN_SEG_WORDS 64                       // words (of 32 bases) per scan segment: 2048 bases
 #define AN_HALF (LRM_ANCHOR_DIAGS / 2)
@@ -38,8 +35,7 @@ struct LrmAnchorScratch {
     int32_t *job_meta_r, *job_nops, *job_score;
     uint8_t *job_store; uint64_t job_store_stride;
     lrm_anchor *anchors;                      // used when the caller passes none
-    // bit-sliced extension over the job table
-    uint64_t *qpl; uint32_t *rflags; uint32_t *ckpt; uint64_t *codes; uint64_t cw; int32_t *ncodes;
+    LrmBsScratch bs;                          // bit-sliced extension over the job table
 };
 
 struct __attribute__((packed, aligned(1))) An16 { uint32_t x, y, z, w; };     // 16 bytes at any address
@@ -353,8 +349,9 @@ void lrm_anchor_scratch_free(lrm_workspace *ws) {
     LrmAnchorScratch *s = ws ? ws->an : nullptr;
     if (!s) return;
     void *bufs[] = {s->keys, s->job_reads, s->job_lens, s->job_tlens, s->job_meta, s->job_meta_r, s->job_nops, s->job_score,
-                    s->job_store, s->anchors, s->qpl, s->rflags, s->ckpt, s->codes, s->ncodes};
+                    s->job_store, s->anchors};
     for (void *b : bufs) if (b) (void) hipFree(b);
+    lrm_bs_scratch_free(&s->bs);
     delete s;
     ws->an = nullptr;
 }
@@ -370,32 +367,29 @@ static int anchor_scratch(lrm_workspace *ws, bool planar) {
     s->n_max = n; s->max_len = ws->max_len;
     s->job_stride = ((uint64_t) ws->max_len + 31) & ~15ull;
     s->job_store_stride = (lrm_anchored_store_stride(ws->max_len) + 15) & ~15ull;
-    s->cw = lrm_bs_code_words(ws->max_len + ws->max_len / 16 + 2);
-    struct { void **p; uint64_t bytes; bool on; } allocs[] = {
-        {(void **) &s->keys, n * 8, true},
-        {(void **) &s->job_reads, jobs * s->job_stride, true},
-        {(void **) &s->job_lens, jobs * 4, true},
-        {(void **) &s->job_tlens, jobs * 4, true},
-        {(void **) &s->job_meta, jobs * sizeof(lrm_seq_meta), true},
-        {(void **) &s->job_meta_r, jobs * 4, true},
-        {(void **) &s->job_nops, jobs * 4, true},
-        {(void **) &s->job_score, jobs * 4, true},
-        {(void **) &s->job_store, jobs * s->job_store_stride, true},
-        {(void **) &s->anchors, n * sizeof(lrm_anchor), true},
-        {(void **) &s->qpl, jobs * ws->qpl_wpr * 8 + 16, planar},
-        {(void **) &s->rflags, jobs * 4, planar},
-        {(void **) &s->ckpt, lrm_bs_ckpt_words(jobs) * 4, planar},
-        {(void **) &s->codes, jobs * s->cw * 8, planar},
-        {(void **) &s->ncodes, jobs * 4, planar},
+    struct { void **p; uint64_t bytes; } allocs[] = {
+        {(void **) &s->keys, n * 8},
+        {(void **) &s->job_reads, jobs * s->job_stride},
+        {(void **) &s->job_lens, jobs * 4},
+        {(void **) &s->job_tlens, jobs * 4},
+        {(void **) &s->job_meta, jobs * sizeof(lrm_seq_meta)},
+        {(void **) &s->job_meta_r, jobs * 4},
+        {(void **) &s->job_nops, jobs * 4},
+        {(void **) &s->job_score, jobs * 4},
+        {(void **) &s->job_store, jobs * s->job_store_stride},
+        {(void **) &s->anchors, n * sizeof(lrm_anchor)},
     };
     for (auto &a : allocs) {
-        if (!a.on) continue;
         if (hipMalloc(a.p, a.bytes) != hipSuccess) {
             lrm_set_error("hipMalloc of %llu bytes of anchored-mode scratch failed", (unsigned long long) a.bytes);
             lrm_anchor_scratch_free(ws);
             return -1;
         }
         ws->bytes += a.bytes;
+    }
+    if (planar && lrm_bs_scratch_alloc(&s->bs, jobs, ws->max_len, ws->max_len + ws->max_len / 16 + 2, &ws->bytes)) {
+        lrm_anchor_scratch_free(ws);
+        return -1;
     }
     return 0;
 }
@@ -407,88 +401,80 @@ static int anchor_min_len(uint32_t min_len, uint32_t *out) {
     return 0;
 }
 
-static int launch_scan(const char *d_reads, uint64_t stride, const uint32_t *d_lens, const lrm_seq_meta *d_meta,
-                       const int32_t *d_meta_r, uint64_t n, uint32_t max_len, const LrmIndexView &ix, const uint64_t *qpl,
-                       uint64_t wpr, const uint32_t *rflags, const uint64_t *cpl, uint32_t min_len, uint64_t *keys,
-                       hipStream_t stream) {
-    const uint32_t nw = (max_len + 31) / 32;
+// the scan over the reads at their loci; cpl: the text's planar image and pl the reads' (pack_reads), null: from bytes
+static int launch_scan(const LrmExtendBatch &b, const LrmIndexView &ix, const LrmBsScratch &pl, const uint64_t *cpl,
+                       uint32_t min_len, uint64_t *keys, hipStream_t stream) {
+    const uint32_t nw = (b.max_len + 31) / 32;
     const uint32_t segs = nw ? (nw + AN_SEG_WORDS - 1) / AN_SEG_WORDS : 1;
-    const uint64_t blocks = (n * segs + 3) / 4;
-    if (blocks > 0x7fffffffull) { lrm_set_error("anchor scan grid too large: split the batch"); return -1; }
-    HIPCHK(hipMemsetAsync(keys, 0, n * 8, stream));
-    hipLaunchKernelGGL(anchor_scan_kernel, dim3((uint32_t) blocks), dim3(256), 0, stream, d_reads, stride, d_lens, d_meta,
-                       d_meta_r, n, ix.mta, ix.content, qpl, wpr, rflags, cpl ? cpl + LRM_BS_PADW : nullptr, min_len, segs,
-                       (unsigned long long *) keys);
+    uint32_t grid;
+    if (lrm_grid_1d((b.n * segs + 3) / 4, "anchor scan", &grid)) return -1;
+    HIPCHK(hipMemsetAsync(keys, 0, b.n * 8, stream));
+    hipLaunchKernelGGL(anchor_scan_kernel, dim3(grid), dim3(256), 0, stream, b.reads, b.stride, b.lens, b.meta, b.meta_r, b.n,
+                       ix.mta, ix.content, cpl ? pl.qpl : nullptr, pl.wpr, pl.rflags, cpl ? cpl + LRM_BS_PADW : nullptr,
+                       min_len, segs, (unsigned long long *) keys);
     return 0;
 }
 
-int lrm_launch_extend_anchored(lrm_index *idx, lrm_workspace *ws, char *d_reads, uint64_t stride,
-                               const uint32_t *d_lens, uint64_t n, uint32_t max_len,
-                               const lrm_entry *d_best, lrm_gact_params gp, uint8_t *d_store,
-                               uint64_t store_stride, int32_t *d_n_ops, int32_t *d_score,
-                               lrm_seq_meta *d_meta, int32_t *d_meta_r, lrm_anchor *d_anchor, uint32_t min_len,
-                               const LrmMapTune &mt, void *stream_) {
+int lrm_launch_extend_anchored(lrm_index *idx, lrm_workspace *ws, const LrmExtendBatch &b, lrm_gact_params gp,
+                               lrm_anchor *d_anchor, uint32_t min_len, const LrmMapTune &mt, void *stream_) {
     hipStream_t stream = (hipStream_t) stream_;
+    const uint64_t n = b.n;
     if (n == 0) return 0;
     if (lrm_gact_resolve_params(&gp) || anchor_min_len(min_len, &min_len)) return -1;
-    if (store_stride < lrm_anchored_store_stride(max_len)) {
+    if (b.store_stride < lrm_anchored_store_stride(b.max_len)) {
         lrm_set_error("anchored extension: store_stride %llu < 2*max_len + max_len/8 + 2 = %llu",
-                      (unsigned long long) store_stride, (unsigned long long) lrm_anchored_store_stride(max_len));
+                      (unsigned long long) b.store_stride, (unsigned long long) lrm_anchored_store_stride(b.max_len));
         return -1;
     }
-    if (!(ws->parts & LRM_WS_EXTEND) || n > ws->n_max || max_len > ws->max_len) {
+    if (!(ws->parts & LRM_WS_EXTEND) || n > ws->n_max || b.max_len > ws->max_len) {
         lrm_set_error("anchored extension: workspace too small (have n=%llu len=%u with%s extension scratch, need n=%llu len=%u)",
                       (unsigned long long) ws->n_max, ws->max_len, (ws->parts & LRM_WS_EXTEND) ? "" : "out",
-                      (unsigned long long) n, max_len);
+                      (unsigned long long) n, b.max_len);
         return -1;
     }
-    const bool planar = idx->d_cpl && idx->cpl_ok && ws->d_qpl;
+    const bool planar = idx->d_cpl && idx->cpl_ok && ws->bs.qpl;
     if (anchor_scratch(ws, planar)) return -1;
     LrmAnchorScratch &s = *ws->an;
-    if (lrm_launch_locus_revcomp(idx, ws, d_reads, stride, d_lens, n, max_len, d_best, d_meta, d_meta_r, stream_)) return -1;
+    const LrmGactJobs jobs = {s.job_reads, s.job_stride, s.job_lens, s.job_tlens, s.job_meta, s.job_meta_r, idx->view.content,
+                              idx->d_cpl, 2 * n, s.job_store, s.job_store_stride, s.job_nops, s.job_score};
+    LrmGactPlan plan;
+    if (lrm_gact_plan(jobs, gp, mt.gact_impl, planar, &plan)) return -1;
+    if (lrm_launch_locus_revcomp(idx, ws, b, stream_)) return -1;
 
     // anchor: planar image of the oriented reads, then the scan
     lrm_time_begin(ws, LRM_K_LOCUS, stream);
-    if (planar && lrm_bs_pack_reads(d_reads, stride, d_lens, n, max_len, ws->d_qpl, ws->qpl_wpr, ws->d_rflags, stream)) return -1;
-    if (launch_scan(d_reads, stride, d_lens, d_meta, d_meta_r, n, max_len, idx->view, planar ? ws->d_qpl : nullptr,
-                    ws->qpl_wpr, ws->d_rflags, planar ? idx->d_cpl : nullptr, min_len, s.keys, stream)) return -1;
+    if (planar && lrm_bs_pack_reads(b.reads, b.stride, b.lens, n, b.max_len, ws->bs, stream)) return -1;
+    if (launch_scan(b, idx->view, ws->bs, planar ? idx->d_cpl : nullptr, min_len, s.keys, stream)) return -1;
     lrm_time_end(ws, stream);
 
     // jobs
-    const uint32_t chunks_rd = max_len ? (max_len + AN_CHUNK - 1) / AN_CHUNK : 1;
-    if (n * chunks_rd > 0x7fffffffull) { lrm_set_error("anchor jobs grid too large: split the batch"); return -1; }
+    const uint32_t chunks_rd = b.max_len ? (b.max_len + AN_CHUNK - 1) / AN_CHUNK : 1;
+    uint32_t grid;
+    if (lrm_grid_1d(n * chunks_rd, "anchor jobs", &grid)) return -1;
     lrm_time_begin(ws, LRM_K_REVCOMP, stream);
-    hipLaunchKernelGGL(anchor_jobs_kernel, dim3((uint32_t) (n * chunks_rd)), dim3(256), 0, stream, d_reads, stride, d_lens,
-                       d_meta, d_meta_r, n, idx->view.mta, idx->view.con_len, (unsigned long long *) s.keys, chunks_rd,
-                       s.job_reads, s.job_stride, s.job_lens, s.job_tlens, s.job_meta, s.job_meta_r);
+    hipLaunchKernelGGL(anchor_jobs_kernel, dim3(grid), dim3(256), 0, stream, b.reads, b.stride, b.lens, b.meta, b.meta_r, n,
+                       idx->view.mta, idx->view.con_len, (unsigned long long *) s.keys, chunks_rd, s.job_reads, s.job_stride,
+                       s.job_lens, s.job_tlens, s.job_meta, s.job_meta_r);
     lrm_time_end(ws, stream);
 
     // one extension launch over the job table
-    const uint64_t jobs = 2 * n;
-    LrmBsArgs bs = {};
-    const bool want_bs = planar && lrm_bs_wanted(gp, jobs, mt.gact_impl);
-    if (want_bs) {
+    if (plan.kernel == LRM_GACT_BS) {
         lrm_time_begin(ws, LRM_K_PACK_PLANAR, stream);
-        if (lrm_bs_pack_reads(s.job_reads, s.job_stride, s.job_lens, jobs, max_len, s.qpl, ws->qpl_wpr, s.rflags, stream)) return -1;
+        if (lrm_bs_pack_reads(jobs.reads, jobs.stride, jobs.lens, jobs.n, b.max_len, s.bs, stream)) return -1;
         lrm_time_end(ws, stream);
-        bs.qpl = s.qpl; bs.wpr = ws->qpl_wpr; bs.flags = s.rflags; bs.cpl = idx->d_cpl;
-        bs.ckpt = s.ckpt; bs.codes = s.codes; bs.cw = s.cw; bs.ncodes = s.ncodes;
     }
-    const int slot = want_bs ? LRM_K_GACT_BS : LRM_K_GACT;
-    lrm_time_begin(ws, slot, stream);
-    if (lrm_gact_launch_jobs(gp, jobs, stream_, s.job_reads, s.job_stride, s.job_lens, s.job_meta, s.job_meta_r,
-                             idx->view.content, s.job_tlens, s.job_store, s.job_store_stride, s.job_nops, s.job_score,
-                             ws->d_counters, want_bs ? &bs : nullptr, mt.gact_impl, mt.bs_waves)) return -1;
+    lrm_time_begin(ws, plan.slot, stream);
+    if (lrm_gact_launch_jobs(jobs, gp, plan, &s.bs, ws->d_counters, mt.bs_waves, stream)) return -1;
     lrm_time_end(ws, stream);
 
     // stitch
-    const uint64_t ops_max = lrm_anchored_store_stride(max_len);
+    const uint64_t ops_max = lrm_anchored_store_stride(b.max_len);
     const uint32_t chunks_op = (uint32_t) ((ops_max + AN_CHUNK - 1) / AN_CHUNK);
-    if (n * chunks_op > 0x7fffffffull) { lrm_set_error("anchor stitch grid too large: split the batch"); return -1; }
-    lrm_time_begin(ws, slot, stream);
-    hipLaunchKernelGGL(anchor_stitch_kernel, dim3((uint32_t) (n * chunks_op)), dim3(256), 0, stream, d_lens, d_meta, d_meta_r,
-                       n, idx->view.mta, (const unsigned long long *) s.keys, chunks_op, s.job_store, s.job_store_stride,
-                       s.job_nops, s.job_score, d_store, store_stride, d_n_ops, d_score, d_anchor ? d_anchor : s.anchors);
+    if (lrm_grid_1d(n * chunks_op, "anchor stitch", &grid)) return -1;
+    lrm_time_begin(ws, plan.slot, stream);
+    hipLaunchKernelGGL(anchor_stitch_kernel, dim3(grid), dim3(256), 0, stream, b.lens, b.meta, b.meta_r, n, idx->view.mta,
+                       (const unsigned long long *) s.keys, chunks_op, s.job_store, s.job_store_stride, s.job_nops,
+                       s.job_score, b.store, b.store_stride, b.n_ops, b.score, d_anchor ? d_anchor : s.anchors);
     lrm_time_end(ws, stream);
     HIPCHK(hipGetLastError());
     return 0;
@@ -508,28 +494,25 @@ extern "C" int lrm_debug_anchor(lrm_index *idx, const char *read, uint32_t len, 
             if (loc >= hm[i].offset && loc < hm[i].offset + hm[i].seq_len) { m.seq_id = i; m.loc = loc; m.off = loc - hm[i].offset; }
     free(hm);
     if (m.seq_id < 0) { lrm_set_error("locus %llu is not on the forward half of a sequence", (unsigned long long) loc); return -1; }
-    struct Buf {
-        void *p = nullptr;
-        ~Buf() { if (p) (void) hipFree(p); }
-        int alloc(size_t bytes) { return hipMalloc(&p, bytes) == hipSuccess ? 0 : -1; }
-    };
     const bool planar = idx->d_cpl && idx->cpl_ok;
-    const uint64_t wpr = lrm_bs_planar_words(len);
-    Buf br, bl, bm, bmr, bk, ba, bq, bf;
+    LrmBsScratch pl = {};
+    pl.wpr = lrm_bs_planar_words(len);
+    DevBuf br, bl, bm, bmr, bk, ba, bq, bf;
     if (br.alloc((size_t) len + 32) || bl.alloc(16) || bm.alloc(sizeof(m)) || bmr.alloc(16) || bk.alloc(16) ||
-        ba.alloc(sizeof(lrm_anchor)) || bq.alloc(wpr * 8 + 16) || bf.alloc(16)) { lrm_set_error("device allocation failed"); return -1; }
+        ba.alloc(sizeof(lrm_anchor)) || bq.alloc(pl.wpr * 8 + 16) || bf.alloc(16)) { lrm_set_error("device allocation failed"); return -1; }
+    pl.qpl = (uint64_t *) bq.p; pl.rflags = (uint32_t *) bf.p;
     const int32_t one = 1;
     HIPCHK(hipMemcpy(br.p, read, len, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(bl.p, &len, 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(bm.p, &m, sizeof(m), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(bmr.p, &one, 4, hipMemcpyHostToDevice));
-    if (planar && lrm_bs_pack_reads((const char *) br.p, 0, (const uint32_t *) bl.p, 1, len, (uint64_t *) bq.p, wpr,
-                                    (uint32_t *) bf.p, nullptr)) return -1;
-    if (launch_scan((const char *) br.p, 0, (const uint32_t *) bl.p, (const lrm_seq_meta *) bm.p, (const int32_t *) bmr.p, 1,
-                    len, idx->view, planar ? (const uint64_t *) bq.p : nullptr, wpr, (const uint32_t *) bf.p,
-                    planar ? idx->d_cpl : nullptr, min_len, (uint64_t *) bk.p, nullptr)) return -1;
-    hipLaunchKernelGGL(anchor_record_kernel, dim3(1), dim3(1), 0, nullptr, (const uint32_t *) bl.p, (const lrm_seq_meta *) bm.p,
-                       idx->view.mta, (const unsigned long long *) bk.p, (lrm_anchor *) ba.p);
+    LrmExtendBatch b = {};
+    b.reads = (char *) br.p; b.lens = (const uint32_t *) bl.p; b.n = 1; b.max_len = len;
+    b.meta = (lrm_seq_meta *) bm.p; b.meta_r = (int32_t *) bmr.p;
+    if (planar && lrm_bs_pack_reads(b.reads, 0, b.lens, 1, len, pl, nullptr)) return -1;
+    if (launch_scan(b, idx->view, pl, planar ? idx->d_cpl : nullptr, min_len, (uint64_t *) bk.p, nullptr)) return -1;
+    hipLaunchKernelGGL(anchor_record_kernel, dim3(1), dim3(1), 0, nullptr, b.lens, b.meta, idx->view.mta,
+                       (const unsigned long long *) bk.p, (lrm_anchor *) ba.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, ba.p, sizeof(lrm_anchor), hipMemcpyDeviceToHost));

@@ -32,7 +32,7 @@
 // follows its own path with the steps predicated on "my path is on this anti-diagonal".
 #include <hip/hip_runtime.h>
 #include <cstdlib>
-#include "lrm_internal.h"
+#include "lrm_hip_util.h"
 
 #ifndef BS_K
 #define BS_K 32                 // anti-diagonals per traceback block (even, <= 32)
@@ -584,14 +584,7 @@ __global__ __launch_bounds__(256) void bs_expand_kernel(const uint64_t *__restri
 // ----------------------------------------------------------------------------------------
 // host side
 // ----------------------------------------------------------------------------------------
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-    lrm_set_error("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); return -1; } } while (0)
-
 uint64_t lrm_bs_planar_words(uint64_t len) { return 2 * ((len + 63) / 64) + 2 * (uint64_t) BS_PADW; }
-
-bool lrm_bs_wanted(lrm_gact_params gp, uint64_t n, int impl) {
-    return gp.W <= 128 && (impl == 4 || (impl == 0 && n >= LRM_BS_MIN_READS));
-}
 
 // planar text into a caller-provided buffer of lrm_bs_planar_words(len) words (+ a flag word)
 int lrm_bs_pack_text(const char *d_text, uint64_t len, uint64_t *d_out, uint32_t *d_flag, void *stream_) {
@@ -638,18 +631,18 @@ void lrm_bs_free_index(lrm_index *idx) {
     idx->d_cpl = nullptr;
 }
 
-// planar reads + per-read "has a byte other than ACGT" flags into caller-provided buffers
+// planar reads + per-read "has a byte other than ACGT" flags into the scratch
 int lrm_bs_pack_reads(const char *d_reads, uint64_t stride, const uint32_t *d_lens, uint64_t n, uint32_t max_len,
-                      uint64_t *d_qpl, uint64_t wpr, uint32_t *d_flags, void *stream_) {
+                      const LrmBsScratch &bs, void *stream_) {
     hipStream_t stream = (hipStream_t) stream_;
     const uint32_t gpr = (max_len + 63) / 64;
     uint32_t wv = (gpr + BS_PACK_G - 1) / BS_PACK_G;   // 16 groups (1 KiB of read) per wavefront
     if (wv == 0) wv = 1;
-    const uint64_t waves = n * wv;
-    if ((waves + 3) / 4 > 0x7fffffffull) { lrm_set_error("planar pack grid too large: split the batch"); return -1; }
-    HIPCHK(hipMemsetAsync(d_flags, 0, n * sizeof(uint32_t), stream));
-    hipLaunchKernelGGL(bs_pack_reads_kernel, dim3((uint32_t) ((waves + 3) / 4)), dim3(256), 0, stream, d_reads, stride,
-                       d_lens, d_qpl, wpr, d_flags, n, gpr, wv);
+    uint32_t grid;
+    if (lrm_grid_1d((n * wv + 3) / 4, "planar pack", &grid)) return -1;
+    HIPCHK(hipMemsetAsync(bs.rflags, 0, n * sizeof(uint32_t), stream));
+    hipLaunchKernelGGL(bs_pack_reads_kernel, dim3(grid), dim3(256), 0, stream, d_reads, stride, d_lens, bs.qpl, bs.wpr,
+                       bs.rflags, n, gpr, wv);
     return 0;
 }
 
@@ -660,20 +653,46 @@ uint64_t lrm_bs_ckpt_words(uint64_t n) {                     // T - O <= 512: at
     return waves * (uint64_t) (1024 / BS_K) * 512ull;
 }
 
-int lrm_bs_launch(const LrmBsArgs *bs, const uint32_t *d_lens, const lrm_seq_meta *d_meta, const int32_t *d_meta_r,
-                  const uint32_t *d_tlens, uint64_t n, int T, int O, int W, uint8_t *d_store, uint64_t store_stride,
-                  int32_t *d_n_ops, int32_t *d_score, LrmDevCounters *counters, uint32_t max_waves, void *stream_) {
+int lrm_bs_scratch_alloc(LrmBsScratch *s, uint64_t jobs, uint32_t max_len, uint32_t ops_len, uint64_t *bytes) {
+    s->wpr = lrm_bs_planar_words(max_len);
+    s->cw = lrm_bs_code_words(ops_len);
+    struct { void **p; uint64_t bytes; } allocs[] = {
+        {(void **) &s->qpl, jobs * s->wpr * 8 + 16},
+        {(void **) &s->rflags, jobs * 4},
+        {(void **) &s->ckpt, lrm_bs_ckpt_words(jobs) * 4},
+        {(void **) &s->codes, jobs * s->cw * 8},
+        {(void **) &s->ncodes, jobs * 4},
+    };
+    for (auto &a : allocs) {
+        if (hipMalloc(a.p, a.bytes) != hipSuccess) {
+            lrm_set_error("hipMalloc of %llu bytes of bit-sliced extension scratch failed", (unsigned long long) a.bytes);
+            lrm_bs_scratch_free(s);
+            return -1;
+        }
+        *bytes += a.bytes;
+    }
+    return 0;
+}
+
+void lrm_bs_scratch_free(LrmBsScratch *s) {
+    (void) hipFree(s->qpl); (void) hipFree(s->rflags); (void) hipFree(s->ckpt); (void) hipFree(s->codes); (void) hipFree(s->ncodes);
+    *s = LrmBsScratch{};
+}
+
+int lrm_bs_launch(const LrmGactJobs &j, lrm_gact_params gp, const LrmBsScratch &bs, LrmDevCounters *counters,
+                  uint32_t max_waves, void *stream_) {
     hipStream_t stream = (hipStream_t) stream_;
-    uint64_t blocks = (n + 63) / 64;
+    uint64_t blocks = (j.n + 63) / 64;
     if (blocks > LRM_BS_MAX_WAVES) blocks = LRM_BS_MAX_WAVES;              // resident wavefronts; lanes refill from the queue
     if (max_waves >= 1 && max_waves < blocks) blocks = max_waves;          // (tests: a small grid forces refills)
     HIPCHK(hipMemsetAsync(&counters->reserved[0], 0, sizeof(unsigned long long), stream));
-    hipLaunchKernelGGL(gact_bs_kernel, dim3((uint32_t) blocks), dim3(64), 0, stream, bs->qpl, bs->wpr, d_lens, d_meta,
-                       d_meta_r, bs->cpl + BS_PADW, d_tlens, bs->flags, n, T, O, W, bs->ckpt, bs->codes, bs->cw,
-                       bs->ncodes, d_n_ops, d_score, counters);
-    const uint32_t bpr = (uint32_t) ((bs->cw * 32 + 4095) / 4096);          // 256 threads x 16 columns per block
-    if (n * bpr > 0x7fffffffull) { lrm_set_error("expand grid too large: split the batch"); return -1; }
-    hipLaunchKernelGGL(bs_expand_kernel, dim3((uint32_t) (n * bpr)), dim3(256), 0, stream, bs->codes, bs->cw, bs->ncodes,
-                       d_n_ops, bs->flags, d_meta_r, n, bpr, d_store, store_stride);
+    hipLaunchKernelGGL(gact_bs_kernel, dim3((uint32_t) blocks), dim3(64), 0, stream, bs.qpl, bs.wpr, j.lens, j.meta,
+                       j.meta_r, j.cpl + BS_PADW, j.tlens, bs.rflags, j.n, gp.T, gp.O, gp.W, bs.ckpt, bs.codes, bs.cw,
+                       bs.ncodes, j.n_ops, j.score, counters);
+    const uint32_t bpr = (uint32_t) ((bs.cw * 32 + 4095) / 4096);           // 256 threads x 16 columns per block
+    uint32_t grid;
+    if (lrm_grid_1d(j.n * bpr, "expand", &grid)) return -1;
+    hipLaunchKernelGGL(bs_expand_kernel, dim3(grid), dim3(256), 0, stream, bs.codes, bs.cw, bs.ncodes, j.n_ops, bs.rflags,
+                       j.meta_r, j.n, bpr, j.store, j.store_stride);
     return 0;
 }

@@ -4,11 +4,14 @@
 //
 //   locus_resolve  one lane per read: seq_lookup with the reference's u64 arithmetic
 //   revcomp        reverse-complement reads that resolved to the reverse strand, in place
-//   gact3          TWO READS PER WAVEFRONT (packed 16-bit scores, traceback planes in registers): small batches
+//   gact3          TWO READS PER WAVEFRONT (packed 16-bit scores, traceback planes in registers): small batches.
+//                  The compiler reports 103 VGPRs (NB = 26) / 121 (NB = 32), no scratch, 4 wavefronts per SIMD
 //   gact_wide      ONE READ PER WAVEFRONT (32-bit scores, traceback in LDS): bands wider than 128 diagonals, and the
-//                  general fallback (reads with bytes other than ACGT, T - O > 256)
+//                  general fallback (reads with bytes other than ACGT, T - O > 256).  78 / 78 / 88 / 122 VGPRs and
+//                  6 / 6 / 5 / 4 wavefronts per SIMD at 1 / 2 / 4 / 8 diagonal pairs per lane, no scratch
 //                  Tiles of a read are walked in sequence (tile i+1 starts where tile i's traceback stopped),
 //                  docs/GACT_SPEC.md.  Large batches run on the bit-sliced lane-per-read kernel (gact_bs_kernels.hip).
+//   host side      lrm_gact_plan picks the kernel of a job table, lrm_gact_launch_jobs launches it
 //
 // GACT tile on a 64-lane wavefront: the band (<=128 diagonals) is laid across the lanes and
 // the wavefront sweeps anti-diagonals s = a+b from the far corner down to the anchor.  On an
@@ -20,7 +23,7 @@
 // recurrences: nothing here is a contraction, MFMA does not apply.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
-#include "lrm_internal.h"
+#include "lrm_hip_util.h"
 #include "seq_bytes.h"
 
 #define GACT_NEG (-(1 << 28))
@@ -252,8 +255,8 @@ __device__ __forceinline__ uint32_t gact2_cell(uint32_t v_diag, uint32_t v_ins, 
 // statically named register (switch on the block number, one v_mov per plane), and the
 // wave-uniform walk fetches the word of the lane it needs with v_readlane from the register the
 // same switch names.  LDS then holds only the staged sequences (3.1 KiB per wavefront) and
-// occupancy is set by registers (~5 wavefronts = 10 reads per SIMD).  The walk looks two blocks
-// ahead, so a DIAG run only ends at an indel or after >= 16 moves.
+// occupancy is set by registers (103 / 121 VGPRs: 4 wavefronts = 8 reads per SIMD).  The walk looks
+// two blocks ahead, so a DIAG run only ends at an indel or after >= 16 moves.
 // ----------------------------------------------------------------------------------------
 // (block, next block) pairs; the planes are plain local variables tbnK / tbgK (K = 0..32) of the kernel --
 // not an array or struct: LLVM sinks the stores of a switch over a[K] / s.mK into one dynamically
@@ -631,76 +634,73 @@ __global__ __launch_bounds__(64) void gact_wide_kernel(const char *__restrict__ 
     }
 }
 
-typedef void (*gact1_fn_t)(const char *, uint64_t, const uint32_t *, const lrm_seq_meta *, const int32_t *,
-                           const char *, const uint32_t *, uint64_t, int, int, int, uint8_t *, uint64_t, int32_t *,
-                           int32_t *, LrmDevCounters *, const uint32_t *);
-typedef void (*gact2_fn_t)(const char *, uint64_t, const uint32_t *, const lrm_seq_meta *, const int32_t *,
-                           const char *, const uint32_t *, uint64_t, int, int, int, uint8_t *, uint64_t, int32_t *,
-                           int32_t *, LrmDevCounters *);
-
-// one read per wavefront (gact_wide_kernel): DPL diagonal pairs per lane for the band W; flags != null: flagged reads only
-static int launch_one_per_wave(lrm_gact_params gp, uint64_t n, hipStream_t stream, const char *reads, uint64_t stride,
-                               const uint32_t *lens, const lrm_seq_meta *meta, const int32_t *meta_r, const char *content,
-                               const uint32_t *tlens, uint8_t *store, uint64_t store_stride, int32_t *n_ops, int32_t *score,
-                               LrmDevCounters *counters, const uint32_t *flags) {
-    const int dpl = gp.W <= 128 ? 1 : gp.W <= 256 ? 2 : gp.W <= 512 ? 4 : 8;
-    const int nx = 64 * dpl, padw = nx / 2 + 40;
-    const int tbw = ((2 * (gp.T - gp.O) - 1) >> 4) + 1;
-    const int seqb = (gp.T + 2 * padw + 15) & ~15;
-    size_t shw = (size_t) tbw * nx * 4 + 2 * (size_t) seqb + (((size_t) 2 * (gp.T - gp.O) + 15) & ~(size_t) 15);
-    if (shw > 160 * 1024) { lrm_set_error("GACT T=%d O=%d W=%d needs %zu B of LDS (> 160 KiB)", gp.T, gp.O, gp.W, shw); return -1; }
-    gact1_fn_t fw = dpl == 1 ? gact_wide_kernel<1> : dpl == 2 ? gact_wide_kernel<2> : dpl == 4 ? gact_wide_kernel<4> : gact_wide_kernel<8>;
-    if (shw > 64 * 1024) {
+// one read per wavefront (gact_wide_kernel<plan.dpl>); flags != null: flagged reads only
+static int launch_one_per_wave(const LrmGactJobs &j, lrm_gact_params gp, const LrmGactPlan &plan, LrmDevCounters *counters,
+                               const uint32_t *flags, hipStream_t stream) {
+    auto fw = plan.dpl == 1 ? gact_wide_kernel<1> : plan.dpl == 2 ? gact_wide_kernel<2>
+            : plan.dpl == 4 ? gact_wide_kernel<4> : gact_wide_kernel<8>;
+    if (plan.lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fw),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int) shw);
-        if (e != hipSuccess) { lrm_set_error("hipFuncSetAttribute(%zu B LDS) failed: %s", shw, hipGetErrorString(e)); return -1; }
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int) plan.lds);
+        if (e != hipSuccess) { lrm_set_error("hipFuncSetAttribute(%zu B LDS) failed: %s", plan.lds, hipGetErrorString(e)); return -1; }
     }
-    if (n > 0x7fffffffull) { lrm_set_error("gact grid too large: split the batch"); return -1; }
-    hipLaunchKernelGGL(fw, dim3((uint32_t) n), dim3(64), shw, stream, reads, stride, lens, meta, meta_r, content,
-                       tlens, n, gp.T, gp.O, gp.W, store, store_stride, n_ops, score, counters, flags);
+    uint32_t grid;
+    if (lrm_grid_1d(j.n, "gact", &grid)) return -1;
+    hipLaunchKernelGGL(fw, dim3(grid), dim3(64), plan.lds, stream, j.reads, j.stride, j.lens, j.meta, j.meta_r, j.content,
+                       j.tlens, j.n, gp.T, gp.O, gp.W, j.store, j.store_stride, j.n_ops, j.score, counters, flags);
     return 0;
 }
 
-static int gact_launch(lrm_gact_params gp, uint64_t n, hipStream_t stream, const char *reads, uint64_t stride,
-                       const uint32_t *lens, const lrm_seq_meta *meta, const int32_t *meta_r, const char *content,
-                       const uint32_t *tlens, uint8_t *store, uint64_t store_stride, int32_t *n_ops, int32_t *score,
-                       LrmDevCounters *counters, const LrmBsArgs *bs, int impl, uint32_t bs_waves) {
-    if (gp.W > 128)
-        return launch_one_per_wave(gp, n, stream, reads, stride, lens, meta, meta_r, content, tlens, store, store_stride,
-                                   n_ops, score, counters, nullptr);
-    // impl (lrm_map_options.gact_impl): 0 = automatic, 1 = one read per wavefront, 3 = packed two reads per wavefront,
-    // 4 = bit-sliced lane per read whenever it applies (W <= 128, pure ACGT text, 4-byte aligned CIGAR store;
-    // otherwise as 0)
-    const int nblk = ((2 * (gp.T - gp.O) - 1) >> 4) + 1;
-    // Bit-sliced kernel: a wavefront carries 64 reads, so it needs a large batch to fill the chip
-    // (below ~16 k reads the two-reads-per-wavefront kernel finishes first).
-    const bool bs_ok = bs && bs->cpl && gp.W <= 128 && (((uintptr_t) store | (uintptr_t) store_stride) & 3u) == 0;
-    if (bs_ok && (impl == 4 || (impl == 0 && n >= LRM_BS_MIN_READS))) {
-        if (lrm_bs_launch(bs, lens, meta, meta_r, tlens, n, gp.T, gp.O, gp.W, store, store_stride, n_ops, score, counters,
-                          bs_waves, stream)) return -1;
-        // reads holding a byte other than ACGT (rare): one read per wavefront, flagged reads only
-        return launch_one_per_wave(gp, n, stream, reads, stride, lens, meta, meta_r, content, tlens, store, store_stride,
-                                   n_ops, score, counters, bs->flags);
+// THE choice of the extension kernel (gact_impl: lrm_map_options in lrm_accel.h; the rule as a table: INTEGRATION.md)
+int lrm_gact_plan(const LrmGactJobs &j, lrm_gact_params gp, int impl, bool planar, LrmGactPlan *out) {
+    LrmGactPlan p = {};
+    const int nblk = ((2 * (gp.T - gp.O) - 1) >> 4) + 1;              // traceback blocks of a tile
+    // Bit-sliced kernel: a wavefront carries 64 reads, so it needs a large batch to fill the chip (below ~16 k reads
+    // the two-reads-per-wavefront kernel finishes first); it stores CIGAR bytes four at a time.
+    if (gp.W <= 128 && planar && (((uintptr_t) j.store | (uintptr_t) j.store_stride) & 3u) == 0 &&
+        (impl == 4 || (impl == 0 && j.n >= LRM_BS_MIN_READS)))
+        p.kernel = LRM_GACT_BS;
+    else if (gp.W <= 128 && impl != 1 && nblk <= 32)
+        p.kernel = LRM_GACT_PACKED;
+    else                                  // W > 128, T - O > 256 (more traceback planes than the packed kernel keeps in registers), impl 1
+        p.kernel = LRM_GACT_WIDE;
+    p.slot = p.kernel == LRM_GACT_BS ? LRM_K_GACT_BS : LRM_K_GACT;
+    if (p.kernel == LRM_GACT_PACKED) {
+        p.nb = nblk <= 26 ? 26 : 32;
+        p.fullband = gp.W >= 128;
+        p.lds = (size_t) 4 * 2 * ((size_t) gp.T + 2 * G2_PAD) * 4;
+    } else {                              // DPL diagonal pairs per lane for the band W
+        p.dpl = gp.W <= 128 ? 1 : gp.W <= 256 ? 2 : gp.W <= 512 ? 4 : 8;
+        const int nx = 64 * p.dpl, padw = nx / 2 + 40;
+        const int seqb = (gp.T + 2 * padw + 15) & ~15;
+        p.lds = (size_t) nblk * nx * 4 + 2 * (size_t) seqb + (((size_t) 2 * (gp.T - gp.O) + 15) & ~(size_t) 15);
+        if (p.lds > 160 * 1024) { lrm_set_error("GACT T=%d O=%d W=%d needs %zu B of LDS (> 160 KiB)", gp.T, gp.O, gp.W, p.lds); return -1; }
     }
-    if (impl != 1 && nblk <= 32) {
-        size_t shmem3 = (size_t) 4 * 2 * ((size_t) gp.T + 2 * G2_PAD) * 4;
-        gact2_fn_t fn3;
-        if (nblk <= 26) fn3 = gp.W >= 128 ? gact3_kernel<true, 26> : gact3_kernel<false, 26>;
-        else fn3 = gp.W >= 128 ? gact3_kernel<true, 32> : gact3_kernel<false, 32>;
-        uint64_t blocks3 = (n + 7) / 8;
-        hipLaunchKernelGGL(fn3, dim3((uint32_t) blocks3), dim3(256), shmem3, stream, reads, stride, lens, meta, meta_r,
-                           content, tlens, n, gp.T, gp.O, gp.W, store, store_stride, n_ops, score, counters);
+    *out = p;
+    return 0;
+}
+
+// the extension proper over a table of jobs (anchor_kernels.hip builds one; the classic mode's table is the batch itself)
+int lrm_gact_launch_jobs(const LrmGactJobs &j, lrm_gact_params gp, const LrmGactPlan &plan, const LrmBsScratch *bs,
+                         LrmDevCounters *counters, uint32_t bs_waves, void *stream_) {
+    hipStream_t stream = (hipStream_t) stream_;
+    if (plan.kernel == LRM_GACT_BS) {
+        if (lrm_bs_launch(j, gp, *bs, counters, bs_waves, stream)) return -1;
+        // reads holding a byte other than ACGT (rare): one read per wavefront, flagged reads only
+        return launch_one_per_wave(j, gp, plan, counters, bs->rflags, stream);
+    }
+    if (plan.kernel == LRM_GACT_PACKED) {
+        auto fn3 = plan.nb == 26 ? (plan.fullband ? gact3_kernel<true, 26> : gact3_kernel<false, 26>)
+                                 : (plan.fullband ? gact3_kernel<true, 32> : gact3_kernel<false, 32>);
+        hipLaunchKernelGGL(fn3, dim3((uint32_t) ((j.n + 7) / 8)), dim3(256), plan.lds, stream, j.reads, j.stride, j.lens,
+                           j.meta, j.meta_r, j.content, j.tlens, j.n, gp.T, gp.O, gp.W, j.store, j.store_stride, j.n_ops,
+                           j.score, counters);
         return 0;
     }
-    // T - O > 256 (more traceback planes than the packed kernel keeps in registers) or LRM_GACT_IMPL=1
-    return launch_one_per_wave(gp, n, stream, reads, stride, lens, meta, meta_r, content, tlens, store, store_stride,
-                               n_ops, score, counters, nullptr);
+    return launch_one_per_wave(j, gp, plan, counters, nullptr, stream);
 }
 
 // ----------------------------------------------------------------------------------------
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-    lrm_set_error("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); return -1; } } while (0)
-
 // {0,0,0} selects the defaults; the limits are those of the kernels
 int lrm_gact_resolve_params(lrm_gact_params *gp) {
     if (gp->T == 0 && gp->O == 0 && gp->W == 0) {
@@ -715,66 +715,48 @@ int lrm_gact_resolve_params(lrm_gact_params *gp) {
 }
 
 // locus_resolve + in-place reverse complement: what both extension modes start with
-int lrm_launch_locus_revcomp(lrm_index *idx, lrm_workspace *ws, char *d_reads, uint64_t stride, const uint32_t *d_lens,
-                             uint64_t n, uint32_t max_len, const lrm_entry *d_best, lrm_seq_meta *d_meta,
-                             int32_t *d_meta_r, void *stream_) {
+int lrm_launch_locus_revcomp(lrm_index *idx, lrm_workspace *ws, const LrmExtendBatch &b, void *stream_) {
     hipStream_t stream = (hipStream_t) stream_;
     lrm_time_begin(ws, LRM_K_LOCUS, stream);
-    hipLaunchKernelGGL(locus_resolve_kernel, dim3((uint32_t) ((n + 255) / 256)), dim3(256), 0, stream,
-                       idx->view, d_best, d_lens, n, d_meta, d_meta_r);
+    hipLaunchKernelGGL(locus_resolve_kernel, dim3((uint32_t) ((b.n + 255) / 256)), dim3(256), 0, stream,
+                       idx->view, b.best, b.lens, b.n, b.meta, b.meta_r);
     lrm_time_end(ws, stream);
-    const uint32_t half = max_len / 2 + 1;
+    const uint32_t half = b.max_len / 2 + 1;
     const uint32_t cpr = (half + RC_SEG - 1) / RC_SEG;                                  // workgroups per read
     const uint32_t seg = ((half + cpr - 1) / cpr + 15) & ~15u;                           // <= RC_SEG bases each
-    uint64_t blocks = n * cpr;
-    if (blocks > 0x7fffffffull) { lrm_set_error("revcomp grid too large: split the batch"); return -1; }
+    uint32_t grid;
+    if (lrm_grid_1d(b.n * cpr, "revcomp", &grid)) return -1;
     lrm_time_begin(ws, LRM_K_REVCOMP, stream);
-    hipLaunchKernelGGL(revcomp_kernel, dim3((uint32_t) blocks), dim3(256), 0, stream, d_reads, stride,
-                       d_lens, d_meta, d_meta_r, n, cpr, seg);
+    hipLaunchKernelGGL(revcomp_kernel, dim3(grid), dim3(256), 0, stream, b.reads, b.stride, b.lens, b.meta, b.meta_r, b.n,
+                       cpr, seg);
     lrm_time_end(ws, stream);
     return 0;
 }
 
-// the extension proper over a table of jobs (anchor_kernels.hip builds one; the classic mode's table is the batch itself)
-int lrm_gact_launch_jobs(lrm_gact_params gp, uint64_t n, void *stream, const char *reads, uint64_t stride,
-                         const uint32_t *lens, const lrm_seq_meta *meta, const int32_t *meta_r, const char *content,
-                         const uint32_t *tlens, uint8_t *store, uint64_t store_stride, int32_t *n_ops, int32_t *score,
-                         LrmDevCounters *counters, const LrmBsArgs *bs, int impl, uint32_t bs_waves) {
-    return gact_launch(gp, n, (hipStream_t) stream, reads, stride, lens, meta, meta_r, content, tlens, store, store_stride,
-                       n_ops, score, counters, bs, impl, bs_waves);
-}
-
-int lrm_launch_extend(lrm_index *idx, lrm_workspace *ws, char *d_reads, uint64_t stride,
-                      const uint32_t *d_lens, uint64_t n, uint32_t max_len,
-                      const lrm_entry *d_best, lrm_gact_params gp, uint8_t *d_store,
-                      uint64_t store_stride, int32_t *d_n_ops, int32_t *d_score,
-                      lrm_seq_meta *d_meta, int32_t *d_meta_r, const LrmMapTune &mt, void *stream_) {
+int lrm_launch_extend(lrm_index *idx, lrm_workspace *ws, const LrmExtendBatch &b, lrm_gact_params gp, const LrmMapTune &mt,
+                      void *stream_) {
     hipStream_t stream = (hipStream_t) stream_;
-    if (n == 0) return 0;
+    if (b.n == 0) return 0;
     if (mt.anchored)                                       // anchor_kernels.hip; nothing below is reached
-        return lrm_launch_extend_anchored(idx, ws, d_reads, stride, d_lens, n, max_len, d_best, gp, d_store, store_stride,
-                                          d_n_ops, d_score, d_meta, d_meta_r, nullptr, mt.anchor_min_len, mt, stream_);
+        return lrm_launch_extend_anchored(idx, ws, b, gp, nullptr, mt.anchor_min_len, mt, stream_);
     if (lrm_gact_resolve_params(&gp)) return -1;
-    if (store_stride < 2ull * max_len) {
-        lrm_set_error("store_stride %llu < 2*max_len %u", (unsigned long long) store_stride, max_len);
+    if (b.store_stride < 2ull * b.max_len) {
+        lrm_set_error("store_stride %llu < 2*max_len %u", (unsigned long long) b.store_stride, b.max_len);
         return -1;
     }
-    if (lrm_launch_locus_revcomp(idx, ws, d_reads, stride, d_lens, n, max_len, d_best, d_meta, d_meta_r, stream_)) return -1;
-    LrmBsArgs bs = {};
-    const bool want_bs = lrm_bs_wanted(gp, n, mt.gact_impl) && idx->d_cpl && idx->cpl_ok && ws->d_qpl && n <= ws->n_max &&
-                         max_len <= ws->max_len;
-    if (want_bs) {
+    const bool planar = idx->d_cpl && idx->cpl_ok && ws->bs.qpl && b.n <= ws->n_max && b.max_len <= ws->max_len;
+    const LrmGactJobs jobs = {b.reads, b.stride, b.lens, nullptr, b.meta, b.meta_r, idx->view.content, idx->d_cpl, b.n,
+                              b.store, b.store_stride, b.n_ops, b.score};
+    LrmGactPlan plan;
+    if (lrm_gact_plan(jobs, gp, mt.gact_impl, planar, &plan)) return -1;
+    if (lrm_launch_locus_revcomp(idx, ws, b, stream_)) return -1;
+    if (plan.kernel == LRM_GACT_BS) {
         lrm_time_begin(ws, LRM_K_PACK_PLANAR, stream);
-        if (lrm_bs_pack_reads(d_reads, stride, d_lens, n, max_len, ws->d_qpl, ws->qpl_wpr, ws->d_rflags, stream)) return -1;
+        if (lrm_bs_pack_reads(b.reads, b.stride, b.lens, b.n, b.max_len, ws->bs, stream)) return -1;
         lrm_time_end(ws, stream);
-        bs.qpl = ws->d_qpl; bs.wpr = ws->qpl_wpr; bs.flags = ws->d_rflags; bs.cpl = idx->d_cpl;
-        bs.ckpt = ws->d_ckpt; bs.codes = ws->d_codes; bs.cw = ws->codes_cw; bs.ncodes = ws->d_ncodes;
     }
-    const bool runs_bs = want_bs && (((uintptr_t) d_store | (uintptr_t) store_stride) & 3u) == 0;
-    lrm_time_begin(ws, runs_bs ? LRM_K_GACT_BS : LRM_K_GACT, stream);
-    if (gact_launch(gp, n, stream, d_reads, stride, d_lens, d_meta, d_meta_r, idx->view.content,
-                    (const uint32_t *) nullptr, d_store, store_stride, d_n_ops, d_score, ws->d_counters,
-                    want_bs ? &bs : nullptr, mt.gact_impl, mt.bs_waves)) return -1;
+    lrm_time_begin(ws, plan.slot, stream);
+    if (lrm_gact_launch_jobs(jobs, gp, plan, &ws->bs, ws->d_counters, mt.bs_waves, stream)) return -1;
     lrm_time_end(ws, stream);
     HIPCHK(hipGetLastError());
     return 0;
@@ -793,33 +775,14 @@ extern "C" int lrm_debug_gact(const char *q, int n, const char *d, int m, lrm_ga
 extern "C" int lrm_debug_gact_impl(const char *q, int n, const char *d, int m, lrm_gact_params gp, int impl, uint8_t *ops,
                                    int *n_ops, int *score, int device) {
     if (!q || !d || !ops || !n_ops || !score || n < 0 || m < 0) { lrm_set_error("bad argument"); return -1; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        lrm_set_error("no HIP device available: liblrm_accel has no CPU fallback");
-        return -1;
-    }
-    HIPCHK(hipSetDevice(device));
-    if (gp.T == 0 && gp.O == 0 && gp.W == 0) {
-        gp.T = LRM_GACT_T_DEFAULT; gp.O = LRM_GACT_O_DEFAULT; gp.W = LRM_GACT_W_DEFAULT;
-    }
-    if (gp.T < 16 || gp.T > 512 || gp.O < 0 || gp.O >= gp.T || gp.W < 2 || (gp.W & 1) || gp.W > 1024) {
-        lrm_set_error("unsupported GACT parameters T=%d O=%d W=%d", gp.T, gp.O, gp.W);
-        return -1;
-    }
-    // every device buffer is owned by a guard: an early HIPCHK return frees them all
-    struct Buf {
-        void *p = nullptr;
-        ~Buf() { if (p) (void) hipFree(p); }
-        int alloc(size_t bytes) { return hipMalloc(&p, bytes) == hipSuccess ? 0 : -1; }
-    };
-    Buf bq, bd, bops, bl, bm, br, bc, bqpl, bcpl, bfl, bcodes, bck;
+    if (lrm_require_device(device) || lrm_gact_resolve_params(&gp)) return -1;
+    DevBuf bq, bd, bops, bl, bm, br, bc, bcpl, btf;
     if (bq.alloc((size_t) n + 16) || bd.alloc((size_t) m + 16) || bops.alloc((size_t) n + m + 16) || bl.alloc(16) ||
         bm.alloc(sizeof(lrm_seq_meta)) || br.alloc(16) || bc.alloc(sizeof(LrmDevCounters))) { lrm_set_error("device allocation failed"); return -1; }
     char *dq = (char *) bq.p, *dd = (char *) bd.p;
-    uint8_t *dops = (uint8_t *) bops.p;
-    uint32_t *dl = (uint32_t *) bl.p;
+    uint32_t *dl = (uint32_t *) bl.p;                       // {read length, target length}
     lrm_seq_meta *dm = (lrm_seq_meta *) bm.p;
-    int32_t *dr = (int32_t *) br.p;
+    int32_t *dr = (int32_t *) br.p;                         // {meta_r, n_ops, score}
     LrmDevCounters *dc = (LrmDevCounters *) bc.p;
     HIPCHK(hipMemset(dc, 0, sizeof(LrmDevCounters)));
     uint32_t hl[2] = {(uint32_t) n, (uint32_t) m};
@@ -830,26 +793,27 @@ extern "C" int lrm_debug_gact_impl(const char *q, int n, const char *d, int m, l
     HIPCHK(hipMemcpy(dl, hl, 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dm, &hm, sizeof(hm), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dr, hr, 12, hipMemcpyHostToDevice));
-    LrmBsArgs bs = {};
-    if (lrm_bs_wanted(gp, 1, impl)) {
-        const uint64_t wq = lrm_bs_planar_words((uint64_t) n), wd = lrm_bs_planar_words((uint64_t) m);
-        bs.cw = lrm_bs_code_words((uint32_t) (n > m ? n : m));
-        if (bqpl.alloc(wq * 8 + 16) || bcpl.alloc(wd * 8 + 16) || bfl.alloc(16) || bcodes.alloc(bs.cw * 8 + 16) ||
-            bck.alloc(lrm_bs_ckpt_words(1) * 4)) { lrm_set_error("device allocation failed"); return -1; }
-        uint32_t *dfl = (uint32_t *) bfl.p;
-        if (lrm_bs_pack_text(dd, (uint64_t) m, (uint64_t *) bcpl.p, dfl + 1, nullptr)) return -1;
-        if (lrm_bs_pack_reads(dq, 0, dl, 1, (uint32_t) n, (uint64_t *) bqpl.p, wq, dfl, nullptr)) return -1;
+    LrmGactJobs jobs = {dq, 0, dl, dl + 1, dm, dr, dd, nullptr, 1, (uint8_t *) bops.p, 0, dr + 1, dr + 2};
+    struct BsGuard { LrmBsScratch s = {}; ~BsGuard() { lrm_bs_scratch_free(&s); } } bs;
+    LrmGactPlan plan;
+    if (lrm_gact_plan(jobs, gp, impl, true, &plan)) return -1;
+    if (plan.kernel == LRM_GACT_BS) {                       // planar images of the pair; a text that is not pure ACGT plans again
+        uint64_t bytes = 0;
+        if (lrm_bs_scratch_alloc(&bs.s, 1, (uint32_t) n, (uint32_t) (n > m ? n : m), &bytes)) return -1;
+        if (bcpl.alloc(lrm_bs_planar_words((uint64_t) m) * 8 + 16) || btf.alloc(4)) { lrm_set_error("device allocation failed"); return -1; }
+        if (lrm_bs_pack_text(dd, (uint64_t) m, (uint64_t *) bcpl.p, (uint32_t *) btf.p, nullptr)) return -1;
+        if (lrm_bs_pack_reads(dq, 0, dl, 1, (uint32_t) n, bs.s, nullptr)) return -1;
         uint32_t tf = 0;
-        HIPCHK(hipMemcpy(&tf, dfl + 1, 4, hipMemcpyDeviceToHost));
-        bs.qpl = (uint64_t *) bqpl.p; bs.wpr = wq; bs.flags = dfl; bs.cpl = tf ? nullptr : (uint64_t *) bcpl.p;
-        bs.codes = (uint64_t *) bcodes.p; bs.ckpt = (uint32_t *) bck.p; bs.ncodes = (int32_t *) (dfl + 2);
+        HIPCHK(hipMemcpy(&tf, btf.p, 4, hipMemcpyDeviceToHost));
+        if (!tf) jobs.cpl = (const uint64_t *) bcpl.p;
+        else if (lrm_gact_plan(jobs, gp, impl, false, &plan)) return -1;
     }
-    if (gact_launch(gp, 1, 0, dq, 0, dl, dm, dr, dd, dl + 1, dops, 0, dr + 1, dr + 2, dc, bs.qpl ? &bs : nullptr, impl, 0)) return -1;
+    if (lrm_gact_launch_jobs(jobs, gp, plan, &bs.s, dc, 0, nullptr)) return -1;
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(hr, dr, 12, hipMemcpyDeviceToHost));
     *n_ops = hr[1];
     *score = hr[2];
-    if (hr[1] > 0) HIPCHK(hipMemcpy(ops, dops, (size_t) hr[1], hipMemcpyDeviceToHost));
+    if (hr[1] > 0) HIPCHK(hipMemcpy(ops, jobs.store, (size_t) hr[1], hipMemcpyDeviceToHost));
     return 0;
 }

@@ -12,7 +12,7 @@
 #include <dlfcn.h>
 #include <sched.h>
 #include <omp.h>
-#include "lrm_internal.h"
+#include "lrm_hip_util.h"
 
 static thread_local char g_err[512] = "";
 
@@ -22,9 +22,6 @@ void lrm_set_error(const char *fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-    lrm_set_error("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); return -1; } } while (0)
 
 extern "C" const char *lrm_last_error(void) { return g_err; }
 int lrm_host_threads(void) {
@@ -856,8 +853,7 @@ extern "C" void lrm_workspace_free(lrm_workspace *ws) {
     (void) hipSetDevice(ws->device);
     (void) hipFree(ws->d_reads2); (void) hipFree(ws->d_rec); (void) hipFree(ws->d_phase); (void) hipFree(ws->d_decided);
     (void) hipFree(ws->d_hcount); (void) hipFree(ws->d_counters); (void) hipFree(ws->d_recq); (void) hipFree(ws->d_cnt); (void) hipFree(ws->d_kc_key); (void) hipFree(ws->d_kc_ord); (void) hipFree(ws->d_redo); (void) hipFree(ws->d_big); (void) hipFree(ws->d_gtab); (void) hipFree(ws->d_glock);
-    (void) hipFree(ws->d_qpl); (void) hipFree(ws->d_rflags);
-    (void) hipFree(ws->d_ckpt); (void) hipFree(ws->d_codes); (void) hipFree(ws->d_ncodes);
+    lrm_bs_scratch_free(&ws->bs);
     lrm_anchor_scratch_free(ws);
     if (ws->h_err) (void) hipHostFree((void *) ws->h_err);
     for (int i = 0; i < LRM_MAX_TIMED; ++i) {
@@ -893,8 +889,6 @@ int lrm_workspace_create_parts(lrm_workspace **out, lrm_index *idx, uint64_t n_m
     ws->cap_q = (jl + ws->P - 1) / ws->P;
     if (ws->cap_q == 0) ws->cap_q = 1;
     ws->words_per_read = (uint64_t) max_len / 32 + 2;
-    ws->qpl_wpr = lrm_bs_planar_words(max_len);
-    ws->codes_cw = lrm_bs_code_words(max_len);
     ws->parts = parts;
     {   // pool of global vote tables: a slice holds 2^k >= 2 x the most hits one (read, phase) item can have
         const uint64_t hmax = (uint64_t) ws->cap_q * (thres > 1 ? thres - 1 : 1);
@@ -920,11 +914,6 @@ int lrm_workspace_create_parts(lrm_workspace **out, lrm_index *idx, uint64_t n_m
         {(void **) &ws->d_decided, n_max, LRM_WS_SEED},
         {(void **) &ws->d_hcount, n_max * (uint64_t) ws->P * 4, LRM_WS_SEED},
         {(void **) &ws->d_counters, sizeof(LrmDevCounters), LRM_WS_SEED | LRM_WS_EXTEND},
-        {(void **) &ws->d_qpl, n_max * ws->qpl_wpr * 8 + 16, LRM_WS_EXTEND},
-        {(void **) &ws->d_rflags, n_max * 4, LRM_WS_EXTEND},
-        {(void **) &ws->d_ckpt, lrm_bs_ckpt_words(n_max) * 4, LRM_WS_EXTEND},
-        {(void **) &ws->d_codes, n_max * ws->codes_cw * 8, LRM_WS_EXTEND},
-        {(void **) &ws->d_ncodes, n_max * 4, LRM_WS_EXTEND},
     };
     for (auto &a : allocs) {
         if (!(a.part & parts)) continue;
@@ -935,6 +924,7 @@ int lrm_workspace_create_parts(lrm_workspace **out, lrm_index *idx, uint64_t n_m
         }
         ws->bytes += a.bytes;
     }
+    if ((parts & LRM_WS_EXTEND) && lrm_bs_scratch_alloc(&ws->bs, n_max, max_len, max_len, &ws->bytes)) { lrm_workspace_free(ws); return -1; }
     if (hipMemset(ws->d_counters, 0, sizeof(LrmDevCounters)) != hipSuccess) { lrm_workspace_free(ws); lrm_set_error("memset failed"); return -1; }
     if (ws->d_glock && hipMemset(ws->d_glock, 0, 64 * 4) != hipSuccess) { lrm_workspace_free(ws); lrm_set_error("memset failed"); return -1; }
     {   // error word: host-coherent pinned memory the kernels store to (never reset by a launch)
@@ -990,19 +980,25 @@ extern "C" int lrm_seed_batch_dev(lrm_index *idx, lrm_workspace *ws, const char 
     return lrm_launch_seed(idx, ws, d_reads, stride, d_lens, n, max_len, p.seed_len, p.thres, d_best, idx->mtune, stream);
 }
 
-extern "C" int lrm_extend_batch_dev(lrm_index *idx, lrm_workspace *ws, char *d_reads, uint64_t stride,
-                                    const uint32_t *d_lens, uint64_t n, uint32_t max_len, const lrm_entry *d_best,
-                                    lrm_gact_params gp, uint8_t *d_store, uint64_t store_stride, int32_t *d_n_ops,
-                                    int32_t *d_score, lrm_seq_meta *d_meta, int32_t *d_meta_r, void *stream) {
-    if (!idx || !ws || !d_reads || !d_lens || !d_best || !d_store || !d_n_ops || !d_score || !d_meta || !d_meta_r) {
+// what the device-buffer extension entry points check before they launch
+static int extend_dev_ready(lrm_index *idx, lrm_workspace *ws, const LrmExtendBatch &b) {
+    if (!idx || !ws || !b.reads || !b.lens || !b.best || !b.store || !b.n_ops || !b.score || !b.meta || !b.meta_r) {
         lrm_set_error("null argument");
         return -1;
     }
     if (ws->idx != idx) { lrm_set_error("workspace does not belong to this index"); return -1; }
     if (lrm_ws_take_error(ws)) return -2;
     HIPCHK(hipSetDevice(idx->device));
-    return lrm_launch_extend(idx, ws, d_reads, stride, d_lens, n, max_len, d_best, gp, d_store, store_stride,
-                             d_n_ops, d_score, d_meta, d_meta_r, idx->mtune, stream);
+    return 0;
+}
+
+extern "C" int lrm_extend_batch_dev(lrm_index *idx, lrm_workspace *ws, char *d_reads, uint64_t stride,
+                                    const uint32_t *d_lens, uint64_t n, uint32_t max_len, const lrm_entry *d_best,
+                                    lrm_gact_params gp, uint8_t *d_store, uint64_t store_stride, int32_t *d_n_ops,
+                                    int32_t *d_score, lrm_seq_meta *d_meta, int32_t *d_meta_r, void *stream) {
+    const LrmExtendBatch b = {d_reads, stride, d_lens, n, max_len, d_best, d_store, store_stride, d_n_ops, d_score, d_meta, d_meta_r};
+    if (int rc = extend_dev_ready(idx, ws, b)) return rc;
+    return lrm_launch_extend(idx, ws, b, gp, idx->mtune, stream);
 }
 
 extern "C" int lrm_workspace_stats(lrm_workspace *ws, lrm_stats *out, void *stream) {
@@ -1033,16 +1029,9 @@ extern "C" int lrm_extend_batch_anchored_dev(lrm_index *idx, lrm_workspace *ws, 
                                              lrm_gact_params gp, uint8_t *d_store, uint64_t store_stride, int32_t *d_n_ops,
                                              int32_t *d_score, lrm_seq_meta *d_meta, int32_t *d_meta_r, lrm_anchor *d_anchor,
                                              uint32_t min_len, void *stream) {
-    if (!idx || !ws || !d_reads || !d_lens || !d_best || !d_store || !d_n_ops || !d_score || !d_meta || !d_meta_r) {
-        lrm_set_error("null argument");
-        return -1;
-    }
-    if (ws->idx != idx) { lrm_set_error("workspace does not belong to this index"); return -1; }
-    if (lrm_ws_take_error(ws)) return -2;
-    HIPCHK(hipSetDevice(idx->device));
-    if (n == 0) return 0;
-    return lrm_launch_extend_anchored(idx, ws, d_reads, stride, d_lens, n, max_len, d_best, gp, d_store, store_stride,
-                                      d_n_ops, d_score, d_meta, d_meta_r, d_anchor, min_len, idx->mtune, stream);
+    const LrmExtendBatch b = {d_reads, stride, d_lens, n, max_len, d_best, d_store, store_stride, d_n_ops, d_score, d_meta, d_meta_r};
+    if (int rc = extend_dev_ready(idx, ws, b)) return rc;
+    return lrm_launch_extend_anchored(idx, ws, b, gp, d_anchor, min_len, idx->mtune, stream);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1113,12 +1102,6 @@ extern "C" void lrm_result_flags(const int *score, const int *meta_r, const lrm_
 // ------------------------------------------------------------------------------------------
 // debug taps (tests only)
 // ------------------------------------------------------------------------------------------
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void) hipFree(p); }
-    int alloc(uint64_t bytes) { return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess ? 0 : -1; }
-};
-
 extern "C" int lrm_debug_seed_search(lrm_index *idx, const char *read, uint32_t len, uint32_t seed_len, uint32_t thres,
                                      int32_t *j_out, uint64_t *rr_out, uint64_t *k_out, uint64_t *l_out, uint64_t cap,
                                      uint64_t *n_out) {

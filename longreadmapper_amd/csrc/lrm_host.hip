@@ -48,10 +48,7 @@
 #include <string>
 #include <thread>
 #include <vector>
-#include "lrm_internal.h"
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-    lrm_set_error("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); return -1; } } while (0)
+#include "lrm_hip_util.h"
 
 // completion of one submitted batch: `pending` slices (over all replicas) still to be collected
 struct lrm_ticket {
@@ -598,10 +595,11 @@ int plan_and_issue(LrmHostCtx &c, SliceJob &sj) {
             const int xs = (int) (g % (uint64_t) n_ext_streams);
             for (uint64_t x = g ? ends[g - 1] : 0; x <= k; ++x) HIPCHK(hipStreamWaitEvent(c.ext[xs], (j.mode & DO_SEED) ? S.ev_seed[x] : S.ev_up[x], 0));
             const Range &u = units[g];
-            if (lrm_launch_extend(idx, S.ws_ext[xs], (char *) d.reads.p + u.off * j.stride, j.stride, (const uint32_t *) d.lens.p + u.off, u.m,
-                                  sj.max_len, (const lrm_entry *) d.best.p + u.off, j.gp, (uint8_t *) d.store.p + u.off * dstride, dstride,
-                                  (int32_t *) d.nops.p + u.off, (int32_t *) d.score.p + u.off, (lrm_seq_meta *) d.meta.p + u.off,
-                                  (int32_t *) d.mr.p + u.off, mt, c.ext[xs])) return -1;
+            const LrmExtendBatch b = {(char *) d.reads.p + u.off * j.stride, j.stride, (const uint32_t *) d.lens.p + u.off, u.m, sj.max_len,
+                                      (const lrm_entry *) d.best.p + u.off, (uint8_t *) d.store.p + u.off * dstride, dstride,
+                                      (int32_t *) d.nops.p + u.off, (int32_t *) d.score.p + u.off, (lrm_seq_meta *) d.meta.p + u.off,
+                                      (int32_t *) d.mr.p + u.off};
+            if (lrm_launch_extend(idx, S.ws_ext[xs], b, j.gp, mt, c.ext[xs])) return -1;
             if (mt.cigar_text) {                                               // length of every read's run-length CIGAR text
                 hipLaunchKernelGGL(cigar_text_kernel<false>, dim3((uint32_t) u.m), dim3(256), 0, c.ext[xs], (const uint8_t *) d.store.p + u.off * dstride, dstride,
                                    (const int32_t *) d.nops.p + u.off, (const int32_t *) d.score.p + u.off, (const int32_t *) d.mr.p + u.off,

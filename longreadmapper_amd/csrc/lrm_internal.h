@@ -25,6 +25,7 @@
 //
 // All sections are 256-byte aligned.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include "../../include/lrm_accel.h"
 
@@ -186,6 +187,14 @@ enum LrmKernelId { LRM_K_PACK2BIT = 0, LRM_K_SEED_SEARCH, LRM_K_VOTE, LRM_K_DECI
                    LRM_K_COUNT };
 #define LRM_MAX_TIMED 4096
 
+struct LrmBsScratch {                      // device scratch of the bit-sliced kernel for a number of jobs
+    uint64_t *qpl; uint64_t wpr;           // planar reads, wpr words per read
+    uint32_t *rflags;                      // per read: holds a byte other than ACGT
+    uint32_t *ckpt;                        // checkpoint scratch, lrm_bs_ckpt_words(jobs) words
+    uint64_t *codes; uint64_t cw;          // 2-bit CIGAR codes, cw words per read (expanded to bytes by bs_expand_kernel)
+    int32_t *ncodes;                       // codes per read (the rest of n_ops is the 'I' tail)
+};
+
 #define LRM_WS_SEED 1
 #define LRM_WS_EXTEND 2
 struct lrm_workspace {
@@ -224,37 +233,52 @@ struct lrm_workspace {
     uint64_t hist_n;         // reads of the last seed launch (with the phase-0 decision count at h_err + 2: round policy)
     volatile uint32_t *h_err;   // error word (pinned host memory, 64 B block) and its device alias
     uint32_t *d_err;
-    // bit-sliced GACT: planar reads (wpr words per read) and per-read "byte other than ACGT" flags
-    uint64_t *d_qpl;
-    uint64_t qpl_wpr;
-    uint32_t *d_rflags;
-    uint32_t *d_ckpt;        // checkpoint scratch of the bit-sliced kernel
-    uint64_t *d_codes;       // 2-bit CIGAR codes (expanded to bytes by bs_expand_kernel)
-    uint64_t codes_cw;
-    int32_t *d_ncodes;
+    LrmBsScratch bs;         // bit-sliced GACT over up to n_max reads of up to max_len bases (LRM_WS_EXTEND)
     struct LrmAnchorScratch *an;   // anchored mode (anchor_kernels.hip): allocated by its first call on this workspace
 };
 
+// ---- extension stage: a table of jobs, the kernel that runs it, the bit-sliced kernel's scratch (all host only) ----------
 #define LRM_BS_PADW 24       // planar words of padding on either side of a packed sequence
 #define LRM_BS_MIN_READS 16384
-struct LrmBsArgs {
-    const uint64_t *qpl; uint64_t wpr;     // planar reads
-    const uint32_t *flags;                 // per read: holds a byte other than ACGT
-    const uint64_t *cpl;                   // planar text
-    uint32_t *ckpt;                        // checkpoint scratch, lrm_bs_ckpt_words(n) words
-    uint64_t *codes; uint64_t cw;          // 2-bit CIGAR codes, cw words per read
-    int32_t *ncodes;                       // codes per read (the rest of n_ops is the 'I' tail)
+// buffers for `jobs` reads of up to max_len bases whose alignments have up to 2 * ops_len ops; adds what it allocated to *bytes
+int lrm_bs_scratch_alloc(LrmBsScratch *s, uint64_t jobs, uint32_t max_len, uint32_t ops_len, uint64_t *bytes);
+void lrm_bs_scratch_free(LrmBsScratch *s);
+
+struct LrmGactJobs {                       // n extension jobs: read i against the text at meta[i].loc
+    const char *reads; uint64_t stride; const uint32_t *lens;
+    const uint32_t *tlens;                 // null: target length = read length
+    const lrm_seq_meta *meta; const int32_t *meta_r;
+    const char *content;                   // the text, one byte per base
+    const uint64_t *cpl;                   // its planar copy (lrm_bs_pack_text); null: none, or the text is not pure ACGT
+    uint64_t n;
+    uint8_t *store; uint64_t store_stride; int32_t *n_ops, *score;
 };
+enum LrmGactKernel {
+    LRM_GACT_WIDE,                         // gact_wide_kernel, one read per wavefront
+    LRM_GACT_PACKED,                       // gact3_kernel, two reads per wavefront
+    LRM_GACT_BS                            // gact_bs_kernel, then gact_wide_kernel on the reads holding a byte other than ACGT
+};
+struct LrmGactPlan {                       // lrm_gact_plan: which kernel runs a job table
+    int kernel;                            // LrmGactKernel
+    int dpl;                               // gact_wide_kernel<DPL> (also the flagged reads of LRM_GACT_BS)
+    int nb; bool fullband;                 // gact3_kernel<FULLBAND, NB>
+    size_t lds;                            // dynamic LDS bytes of gact3_kernel (LRM_GACT_PACKED) or gact_wide_kernel
+    int slot;                              // timing slot: LRM_K_GACT / LRM_K_GACT_BS
+};
+// THE choice of the extension kernel for a job table.  planar: the text has a pure-ACGT planar copy and there is scratch
+// to pack the reads into (the caller packs them when the plan says LRM_GACT_BS)
+int lrm_gact_plan(const LrmGactJobs &j, lrm_gact_params gp, int gact_impl, bool planar, LrmGactPlan *out);
+// the launch the plan names (bs: packed reads and scratch, used by LRM_GACT_BS only; bs_waves: 0 or a smaller grid, tests)
+int lrm_gact_launch_jobs(const LrmGactJobs &j, lrm_gact_params gp, const LrmGactPlan &plan, const LrmBsScratch *bs,
+                         LrmDevCounters *counters, uint32_t bs_waves, void *stream);
 uint64_t lrm_bs_planar_words(uint64_t len);
 uint64_t lrm_bs_code_words(uint32_t max_len);
 uint64_t lrm_bs_ckpt_words(uint64_t n);
-bool lrm_bs_wanted(lrm_gact_params gp, uint64_t n, int gact_impl);      // W <= 128 and (impl 4, or automatic with a large batch)
 int lrm_bs_pack_reads(const char *d_reads, uint64_t stride, const uint32_t *d_lens, uint64_t n, uint32_t max_len,
-                      uint64_t *d_qpl, uint64_t wpr, uint32_t *d_flags, void *stream);
+                      const LrmBsScratch &bs, void *stream);
 int lrm_bs_pack_text(const char *d_text, uint64_t len, uint64_t *d_out, uint32_t *d_flag, void *stream);
-int lrm_bs_launch(const LrmBsArgs *bs, const uint32_t *d_lens, const lrm_seq_meta *d_meta, const int32_t *d_meta_r,
-                  const uint32_t *d_tlens, uint64_t n, int T, int O, int W, uint8_t *d_store, uint64_t store_stride,
-                  int32_t *d_n_ops, int32_t *d_score, LrmDevCounters *counters, uint32_t max_waves, void *stream);
+int lrm_bs_launch(const LrmGactJobs &j, lrm_gact_params gp, const LrmBsScratch &bs, LrmDevCounters *counters,
+                  uint32_t max_waves, void *stream);
 int lrm_bs_prepare_index(lrm_index *idx);
 int lrm_lcl_prepare_index(lrm_index *idx);       // seed_kernels.hip: the long seed table
 void lrm_bs_free_index(lrm_index *idx);
@@ -276,27 +300,21 @@ void lrm_time_end(lrm_workspace *ws, void *stream);
 int lrm_launch_seed(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint64_t stride,
                     const uint32_t *d_lens, uint64_t n, uint32_t max_len, uint32_t seed_len,
                     uint32_t thres, lrm_entry *d_best, const LrmMapTune &mt, void *stream);
-int lrm_launch_extend(lrm_index *idx, lrm_workspace *ws, char *d_reads, uint64_t stride,
-                      const uint32_t *d_lens, uint64_t n, uint32_t max_len,
-                      const lrm_entry *d_best, lrm_gact_params gp, uint8_t *d_store,
-                      uint64_t store_stride, int32_t *d_n_ops, int32_t *d_score,
-                      lrm_seq_meta *d_meta, int32_t *d_meta_r, const LrmMapTune &mt, void *stream);
+// a batch as the extension entry points receive it (device pointers; field order of the extern "C" parameter lists)
+struct LrmExtendBatch {
+    char *reads; uint64_t stride; const uint32_t *lens; uint64_t n; uint32_t max_len;
+    const lrm_entry *best;
+    uint8_t *store; uint64_t store_stride; int32_t *n_ops, *score;
+    lrm_seq_meta *meta; int32_t *meta_r;
+};
+int lrm_launch_extend(lrm_index *idx, lrm_workspace *ws, const LrmExtendBatch &b, lrm_gact_params gp, const LrmMapTune &mt,
+                      void *stream);
 // anchored extension (anchor_kernels.hip); the helpers it shares with the classic mode live in gact_kernels.hip
 #define LRM_ANCHOR_MIN_DEFAULT 20
 int lrm_gact_resolve_params(lrm_gact_params *gp);
-int lrm_launch_locus_revcomp(lrm_index *idx, lrm_workspace *ws, char *d_reads, uint64_t stride, const uint32_t *d_lens,
-                             uint64_t n, uint32_t max_len, const lrm_entry *d_best, lrm_seq_meta *d_meta,
-                             int32_t *d_meta_r, void *stream);
-int lrm_gact_launch_jobs(lrm_gact_params gp, uint64_t n, void *stream, const char *reads, uint64_t stride,
-                         const uint32_t *lens, const lrm_seq_meta *meta, const int32_t *meta_r, const char *content,
-                         const uint32_t *tlens, uint8_t *store, uint64_t store_stride, int32_t *n_ops, int32_t *score,
-                         LrmDevCounters *counters, const LrmBsArgs *bs, int impl, uint32_t bs_waves);
-int lrm_launch_extend_anchored(lrm_index *idx, lrm_workspace *ws, char *d_reads, uint64_t stride,
-                               const uint32_t *d_lens, uint64_t n, uint32_t max_len,
-                               const lrm_entry *d_best, lrm_gact_params gp, uint8_t *d_store,
-                               uint64_t store_stride, int32_t *d_n_ops, int32_t *d_score,
-                               lrm_seq_meta *d_meta, int32_t *d_meta_r, lrm_anchor *d_anchor, uint32_t min_len,
-                               const LrmMapTune &mt, void *stream);
+int lrm_launch_locus_revcomp(lrm_index *idx, lrm_workspace *ws, const LrmExtendBatch &b, void *stream);
+int lrm_launch_extend_anchored(lrm_index *idx, lrm_workspace *ws, const LrmExtendBatch &b, lrm_gact_params gp,
+                               lrm_anchor *d_anchor, uint32_t min_len, const LrmMapTune &mt, void *stream);
 void lrm_anchor_scratch_free(lrm_workspace *ws);
 static inline uint64_t lrm_anchored_store_stride(uint32_t max_len) { return 2ull * max_len + max_len / 8 + 2; }
 int lrm_launch_debug_seed(lrm_index *idx, const char *d_read, uint32_t len, uint32_t seed_len,

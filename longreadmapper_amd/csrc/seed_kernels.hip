@@ -16,7 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <cstdio>
-#include "lrm_internal.h"
+#include "lrm_hip_util.h"
 
 
 // A/a=0 C/c=1 G/g=2 T/t=3 ; other bytes are fenced (UB in the reference, lchash.c:38-44)
@@ -1942,8 +1942,6 @@ __global__ __launch_bounds__(256) void decide_kernel(const LrmPhaseRes *__restri
 // ----------------------------------------------------------------------------------------
 // host launchers
 // ----------------------------------------------------------------------------------------
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-    lrm_set_error("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); return -1; } } while (0)
 
 int lrm_launch_seed(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint64_t stride,
                     const uint32_t *d_lens, uint64_t n, uint32_t max_len, uint32_t seed_len,
@@ -1962,10 +1960,10 @@ int lrm_launch_seed(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint
     {
         uint64_t bpr = wpr * 8;
         uint32_t cpr = (uint32_t) ((bpr / 4 + 255) / 256);
-        uint64_t blocks = n * cpr;
-        if (blocks > 0x7fffffffull) { lrm_set_error("pack2bit grid too large"); return -1; }
+        uint32_t grid;
+        if (lrm_grid_1d(n * cpr, "pack2bit", &grid)) return -1;
         lrm_time_begin(ws, LRM_K_PACK2BIT, stream);
-        hipLaunchKernelGGL(pack2bit_kernel, dim3((uint32_t) blocks), dim3(256), 0, stream, d_reads, stride,
+        hipLaunchKernelGGL(pack2bit_kernel, dim3(grid), dim3(256), 0, stream, d_reads, stride,
                            d_lens, (uint8_t *) ws->d_reads2, bpr, cpr, n);
         lrm_time_end(ws, stream);
     }
@@ -2006,15 +2004,15 @@ int lrm_launch_seed(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint
         const uint8_t *dec = round == 0 || single ? nullptr : ws->d_decided;
         const uint32_t ss_items = mt.ss_items;
         uint32_t bpr = (uint32_t) (((uint64_t) np * cap_q + ss_items - 1) / ss_items);
-        uint64_t blocks = n * bpr;
-        if (blocks > 0x7fffffffull) { lrm_set_error("seed_search grid too large: split the batch"); return -1; }
+        uint32_t grid;
+        if (lrm_grid_1d(n * bpr, "seed_search", &grid)) return -1;
         lrm_time_begin(ws, LRM_K_SEED_SEARCH, stream);
         auto sk = ws->counting ? seed_search_kernel<2048, true>
                                : ss_items == 1024u ? seed_search_kernel<1024, false> : ss_items == 4096u ? seed_search_kernel<4096, false> : seed_search_kernel<2048, false>;
         if (ws->counting) bpr = (uint32_t) (((uint64_t) np * cap_q + 2047) / 2048);
-        if (ws->counting) blocks = n * bpr;
+        if (ws->counting) grid = (uint32_t) (n * bpr);
         // (mt.ss_lds_pad: extra dynamic LDS per workgroup, i.e. fewer resident workgroups per CU -- see DESIGN 5)
-        hipLaunchKernelGGL(sk, dim3((uint32_t) blocks), dim3(256), mt.ss_lds_pad, stream, idx->view,
+        hipLaunchKernelGGL(sk, dim3(grid), dim3(256), mt.ss_lds_pad, stream, idx->view,
                            ws->d_reads2, wpr, d_lens, dec, n, (int) seed_len, thres, lo, hi, cap_q, bpr,
                            ws->d_rec, ws->d_recq, ws->d_cnt, ws->d_hcount, ws->d_counters);
         lrm_time_end(ws, stream);
