@@ -11,8 +11,9 @@
 //     u = H(a+1,b), w = V(a,b+1), s = +-1:   X = max(s, u-1, w-1),  V = X - u,  H = X - w
 //     DIAG iff s >= u-1 and s >= w-1, else INS iff u >= w, else DEL          (the spec's tie order)
 // so a whole anti-diagonal of the band -- 64 lattice points of one parity -- is four 64-bit bit-planes and
-// one step is ~25 boolean operations on them, independent of the neighbouring lanes.  A wavefront
-// advances 64 reads x 64 lattice points per step.
+// one step is 2 x 12 boolean operations on them (gact_bs_circuit.h: ten truth tables and the two instructions of
+// the base comparison per 32-bit half; two more for the decision planes), independent of the neighbouring
+// lanes.  A wavefront advances 64 reads x 64 lattice points per step.
 //
 //   anti-diagonal s, bit t: diagonal d = 2t - 64 (+1 when s is odd), a = A0 - t, b = B0 + t,
 //   A0 = (s + 64 - (s&1)) >> 1, B0 = s - A0.  even s: u = H_prev << 1, w = V_prev; odd s: u = H_prev,
@@ -29,14 +30,13 @@
 // to the anchor and keeps the four difference planes at every 32nd anti-diagonal below 2(T-O) in LDS
 // (32 B per lane and checkpoint).  Pass 2 takes the 32-step blocks in walk order: recompute the block
 // from its checkpoint with the decision planes kept in registers, then walk through it -- every lane
-// follows its own path with the steps predicated on "my path is on this anti-diagonal".
+// follows its own path with the steps predicated on "my path is on this anti-diagonal" (the walk's bookkeeping:
+// gact_bs_circuit.h, bs_walk_block).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include "lrm_hip_util.h"
+#include "gact_bs_circuit.h"    // BS_K, the difference circuit, the walk's bookkeeping
 
-#ifndef BS_K
-#define BS_K 32                 // anti-diagonals per traceback block (even, <= 32)
-#endif
 #define BS_H (BS_K / 2)
 #define LRM_BS_MAX_WAVES 2048ull  // 2 per SIMD on 256 CUs
 #define BS_PADW LRM_BS_PADW
@@ -193,8 +193,6 @@ __device__ __forceinline__ BsWord bs_d_conv(const BsTile &t, int b_lo, const BsP
 }
 __device__ __forceinline__ BsWord bs_d_word(const BsTile &t, int b_lo) { return bs_d_conv(t, b_lo, bs_d_raw(t, b_lo)); }
 
-struct BsPl { uint32_t lo, hi; };                    // one bit-plane of an anti-diagonal: 64 lattice points
-
 struct BsStream {
     BsWord q0, q1, q2, d0, d1, d2;     // three consecutive stream words each
     BsPl Qlo, Qhi, Qs, Dlo, Dhi, Ds;
@@ -237,40 +235,14 @@ __device__ __forceinline__ bool bs_any_sentinel(const BsStream &st) {
 
 struct BsState { BsPl V1, V0, H1, H0; };
 
-// gfx950 v_bitop3_b32: any boolean function of three words in one instruction; the table is the
-// function evaluated on A = 0xF0, B = 0xCC, C = 0xAA
-enum : uint32_t { TA = 0xF0u, TB = 0xCCu, TC = 0xAAu };
-#define BS_LOP3(a, b, c, EXPR) __builtin_amdgcn_bitop3_b32((a), (b), (c), (uint32_t) (EXPR) & 0xFFu)
-
-// one 32-bit half of an anti-diagonal: u = H of the lower neighbour, w = V of the upper one
+// one 32-bit half of an anti-diagonal: u = H of the lower neighbour, w = V of the upper one (gact_bs_circuit.h)
 template <bool BOUND, bool TRACK>
 __device__ __forceinline__ void bs_half(uint32_t u1, uint32_t u0, uint32_t w1, uint32_t w0, uint32_t ql, uint32_t qh,
                                         uint32_t dl, uint32_t dh, uint32_t bm, uint32_t band, uint32_t &V1, uint32_t &V0,
                                         uint32_t &H1, uint32_t &H0, uint32_t &N, uint32_t &G) {
-    const uint32_t e1 = ql ^ dl;
-    const uint32_t m = BS_LOP3(e1, qh, dh, ~TA & ~(TB ^ TC));              // bases equal
-    const uint32_t b0 = BS_LOP3(u0, w0, w0, ~TA & TB);                     // borrow of the low code bit
-    const uint32_t lt = BS_LOP3(u1, w1, b0, ((TA ^ TB) & TB) | (~(TA ^ TB) & TC));   // u < w
-    const uint32_t nd = BS_LOP3(m, u1, w1, ~TA & (TB | TC));               // a gap beats the mismatch diagonal
-    const uint32_t d0 = u0 ^ w0;
-    const uint32_t d1 = BS_LOP3(u1, w1, b0, TA ^ TB ^ TC);                 // (u - w) mod 4 = d1 d0
-    // high bit of w - u for u < w: w - u >= 2 needs w >= 1 (code >= 2), i.e. w1 set, so the lattice point is a gap point
-    // (nd) unless the bases match -- `nd & lt` need not be formed: the match bit gates it in the next instruction
-    const uint32_t a = BS_LOP3(lt, d1, d0, TA & (TB ^ TC));
-    uint32_t v1 = BS_LOP3(a, m, u1, (TA & ~TB) | (TB & ~TC));               // match ? ~u1 : a
-    const uint32_t hh = BS_LOP3(nd, lt, d1, TA & ~TB & TC);
-    uint32_t h1 = BS_LOP3(hh, m, w1, TA | (TB & ~TC));
-    const uint32_t x = BS_LOP3(nd, lt, d0, TA & TB & TC);
-    uint32_t v0 = BS_LOP3(x, nd, u0, TA | (~(TB | TC) & 0xFFu));
-    const uint32_t xx = BS_LOP3(nd, lt, d0, TA & ~TB & TC);
-    uint32_t h0 = BS_LOP3(xx, nd, w0, TA | (~(TB | TC) & 0xFFu));
-    if (BOUND) {                 // free-exit points: V = H = 0 (code 1); lattice points outside a band narrower
-                                 // than the 128 diagonals of the planes: code 0 (-1), the value that never wins
-        v1 = BS_LOP3(v1, bm, band, TA & ~TB & TC);  v0 = BS_LOP3(v0, bm, band, (TA | TB) & TC);
-        h1 = BS_LOP3(h1, bm, band, TA & ~TB & TC);  h0 = BS_LOP3(h0, bm, band, (TA | TB) & TC);
-    }
-    V1 = v1; V0 = v0; H1 = h1; H0 = h0;
-    if (TRACK) { N = nd; G = BS_LOP3(nd, lt, m, (TA & TB) | (~TA & TC)); }   // G: deletion if N, else MATCH
+    const BsHalf o = bs_half_circuit(BOUND, TRACK, u1, u0, w1, w0, ql, qh, dl, dh, bm, band);
+    V1 = o.V1; V0 = o.V0; H1 = o.H1; H0 = o.H0;
+    if (TRACK) { N = o.N; G = o.G; }
 }
 
 // one anti-diagonal.  TRACK: also produce the decision planes
@@ -459,16 +431,14 @@ __global__ __launch_bounds__(64) void gact_bs_kernel(const uint64_t *__restrict_
             if (hb) bs_extract_d<true>(st, shd); else bs_extract_d<false>(st, shd);
         }
         // ---- pass 2: per block recompute with decision planes, then walk through the block ----
-        int a = 0, b = 0;
-        bool running = act;
         // the walk keeps at most T-O bases of either sequence; in the read's last tile it may run on to the edge
         // but not past anti-diagonal 2(T-O) (docs/GACT_SPEC.md)
         const int amax = last ? t.tq : min(t.tq, cap), bmax = last ? t.tt : min(t.tt, cap);
-        const int smax = last ? lim2 : 0x7fffffff;
+        BsWalk wk = {act ? -amax : 0, act ? -bmax : 0, act ? -lim2 : 0, score};
         BsBlockRaw raw;
         bs_block_prefetch(raw, t, 0, ckw, lane);
         for (int c = 0; c < nb; ++c) {
-            if (__ballot(running) == 0) break;
+            if (__ballot(bs_walk_running(&wk)) == 0) break;
             {
                 const int A0 = BS_H * (c + 1) + 31, b_lo = BS_H * c - 32;
                 st.q0 = bs_q_conv(t, A0, raw.q0); st.q1 = bs_q_conv(t, A0 - 32, raw.q1); st.q2 = bs_q_conv(t, A0 - 64, raw.q2);
@@ -502,25 +472,9 @@ __global__ __launch_bounds__(64) void gact_bs_kernel(const uint64_t *__restrict_
                 }
             }
             // walk: the lane's path crosses each anti-diagonal at most once; codes 0 X, 1 =, 2 I, 3 D.
-            // Branch-free: every step runs in all lanes, `on` (0/1) gates its effects.
-            const int sbase = BS_K * c;
-            uint64_t bw = 0;
-            uint32_t e2 = 0;
-#pragma unroll
-            for (int k = 0; k < BS_K; ++k) {
-                const uint32_t on = (running && a + b == sbase + k) ? 1u : 0u;
-                const uint32_t dd = (uint32_t) (b - a + 64);
-                const bool up = dd >= 64u;
-                const uint32_t nbit = __builtin_amdgcn_ubfe(up ? N[k].hi : N[k].lo, dd >> 1, 1u);   // v_bfe takes the offset mod 32
-                const uint32_t gbit = __builtin_amdgcn_ubfe(up ? G[k].hi : G[k].lo, dd >> 1, 1u);
-                const uint32_t code = (nbit << 1) | gbit;
-                bw |= (uint64_t) (on ? code : 0u) << e2;
-                e2 += on << 1;
-                score += (int) BS_LOP3(on, nbit, gbit, TA & ~(~TB & TC));          // every column but '='
-                a += (int) BS_LOP3(on, nbit, gbit, TA & ~(TB & TC));               // every column but 'D'
-                b += (int) BS_LOP3(on, nbit, gbit, TA & ~(TB & ~TC));              // every column but 'I'
-                running = running && a < amax && b < bmax && a + b < smax;
-            }
+            // Branch-free: every step runs in all lanes, gated by "my path is on this anti-diagonal".
+            uint32_t e2;
+            const uint64_t bw = bs_walk_block(&wk, N, G, BS_K * c, lim2, bmax - BS_H * c + 32, &e2);
             // append the block's codes (at most 32) to the lane's code stream
             sb |= bw << fill;
             cnt += (int) (e2 >> 1);
@@ -532,6 +486,8 @@ __global__ __launch_bounds__(64) void gact_bs_kernel(const uint64_t *__restrict_
             fill += (int) e2;
         }
         if (act) {
+            const int a = wk.na + amax, b = wk.nb + bmax;
+            score = wk.score;
             i += a;
             j += b;
             if (a + b == 0) score = -1;                           // cannot happen (every walk moves); never spin
