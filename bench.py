@@ -8,9 +8,12 @@ ONT-profile reads, seed_len 20, thres 300 (reference defaults), GACT T=320 O=120
 
   python bench.py --gpus N --steps K --warmup W        (N>1: launched under torch.distributed.run)
 
-Rank 0 prints ONE JSON line on stdout, short enough for a log tail (compact_record(): the figures below without the
-per-kernel tables, the per-leg details and the notes); --record FILE writes the full record:
-  value / value_hbm_resident   HBM-resident rate of the timed steps (the contract's `value`)
+A plain run does what the headline figure needs and nothing else: index and reads, W warm-up steps, K timed steps, then
+rank 0 prints ONE JSON line on stdout (metric, value, unit, ms_per_step, higher_is_better, dtype, the workload in `config`,
+the index build and the average time of every kernel inside the timed steps).  --full runs every other leg after the timed
+steps and adds its figures to the same line, short enough for a log tail (compact_record(): the figures below without the
+per-kernel tables, the per-leg details and the notes); --record FILE writes the whole record of either kind of run:
+  value / value_hbm_resident   HBM-resident rate of the timed steps (the contract's `value`; every run)
   value_pcie_inclusive         SURVEY 8(d)'s metric: the same batches through the drop-in boundary on CALLER buffers --
                                H2D of the reads and D2H of every result inside the timed region; details in
                                `pcie_inclusive`: batches in flight (lrm_map_batch_submit / _wait), one call at a time
@@ -24,7 +27,8 @@ per-kernel tables, the per-leg details and the notes); --record FILE writes the 
                    reference layout's algorithmic bytes per second -- a rate of reference work, not a
                    fraction of anything
   cpu_baseline     the CPU oracle on a bounded sample of the same reads: all host cores and 1 thread
-                   (the reference's own configuration: both pragmas are commented out, alnmain.c:327-328)
+                   (the reference's own configuration: both pragmas are commented out, alnmain.c:327-328); the GPU's
+                   results on that sample, and those of every PCIe-inclusive leg, are asserted equal to the oracle's
   grch38           the same measurement on the north-star configuration (GRCh38-sized text, 3.1 Gbp, 100 k x 10 kbp ONT
                    reads per step, one GPU) from a fresh child process, when the host has the memory for the index build
   kernels / isolated.kernels   per-kernel tables of the timed (overlapped) region and of the replay
@@ -203,11 +207,15 @@ def compact_record(out):
     return c
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run every other leg: serialized replay and roofline, request counts, "
+                         "PCIe-inclusive legs, CPU baseline with its comparison against the GPU's results, GRCh38-sized "
+                         "child run (minutes; the options marked --full choose among them)")
     ap.add_argument("--ref-len", type=int, default=ECOLI_N)
     ap.add_argument("--reads", type=int, default=100_000)
     ap.add_argument("--read-len", type=int, default=10_000)
@@ -216,22 +224,27 @@ def main():
     ap.add_argument("--thres", type=int, default=300)
     ap.add_argument("--gact", default="320,120,128")
     ap.add_argument("--no-isolated-replay", action="store_true",
-                    help="skip the serialized replay of the steps on one stream that `roofline` is taken from")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the PCIe-inclusive legs through the host-buffer boundary")
-    ap.add_argument("--pcie-steps", type=int, default=0, help="batches of every PCIe-inclusive leg (default: min(steps, 10))")
+                    help="--full: skip the serialized replay of the steps on one stream that `roofline` is taken from")
+    ap.add_argument("--no-pcie", action="store_true", help="--full: skip the PCIe-inclusive legs through the host-buffer boundary")
+    ap.add_argument("--pcie-steps", type=int, default=0, help="--full: batches of every PCIe-inclusive leg (default: min(steps, 10))")
     ap.add_argument("--streams", type=int, default=int(os.environ.get("LRM_BENCH_STREAMS", "3")),
                     help="HIP streams the steps alternate over (each with its own workspace); >1 overlaps the "
                          "HBM-latency-bound seed kernels of one step with the VALU-bound extension of another")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline time (0: skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: target CPU-baseline time (0: only the sample the results are checked on)")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-grch38", action="store_true",
-                    help="do not run the GRCh38-sized leg in a child process after the default workload")
-    ap.add_argument("--grch38-timeout", type=float, default=400.0)
-    ap.add_argument("--record", metavar="FILE", help="write the full record (per-kernel tables, every PCIe leg, notes) as JSON to FILE")
+                    help="--full: do not run the GRCh38-sized leg in a child process after the default workload")
+    ap.add_argument("--grch38-timeout", type=float, default=400.0, help="--full: seconds after which that child is killed")
+    ap.add_argument("--record", metavar="FILE",
+                    help="write the whole record (with --full: per-kernel tables, every PCIe leg, notes) as JSON to FILE")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB; see dump_outputs)")
     ap.add_argument("--sa-sampled", type=int, default=0, help="lrm_index_options.sa_sampled (0: full suffix array)")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
 
     # OpenMP (index builder, staging copies, the CPU oracle) must not spawn one thread per hardware thread of the
     # host when the job only owns a share of it (cgroup quota): oversubscribed threads are throttled
@@ -281,6 +294,11 @@ def main():
     di_tables["derive_s"] = round(time.time() - t1, 2)
     if rank == 0:
         log("derived tables: %s" % di_tables)
+
+    def index_record():
+        return dict(rows=hi.length, image_bytes=int(blob.numel()), reference_s=round(t_synth, 1), build_s=round(t_build, 1),
+                    pack_upload_s=round(t_pack, 1), broadcast_s=round(t_bcast, 3),
+                    host_cpus=usable_cpus(), peak_rss_gb=round(peak_rss_gb(), 1), tables=di_tables)
 
     # ---- reads: every rank maps its own batch (weak scaling), resident in HBM ----------------------
     n, Lr = args.reads, args.read_len
@@ -341,6 +359,42 @@ def main():
                     a = ktimes.get(name, (0.0, 0))
                     ktimes[name] = (a[0] + ms, a[1] + launches)
             sl["dm"].set_timing(False)
+    elapsed = max_over_ranks(elapsed)
+    total_bases = bases * world * args.steps
+    workload = "%s synthetic reference (%d bp, 5%% planted repeats), %d x %d bp %s-profile reads per GPU" \
+               % ({ECOLI_N: "E. coli K-12 sized", CHR1_N: "human chr1 sized", GRCH38_N: "GRCh38 sized"}.get(args.ref_len, "custom"),
+                  args.ref_len, n, Lr, args.profile)
+    value = total_bases / elapsed / 1e9
+    out = dict(metric="aligned Gbp/sec", value=value, unit="Gbp/s", n_gpus=world,
+               steps=args.steps, warmup=args.warmup, ms_per_step=elapsed / args.steps * 1e3,
+               higher_is_better=True, scaling="weak", vs_baseline=None, dtype="u8/u64 integer", data="synthetic",
+               value_hbm_resident=value,
+               config=dict(workload=workload,
+                           seed_len=args.seed_len, thres=args.thres, gact_T=gact[0], gact_O=gact[1], gact_W=gact[2],
+                           reads_per_gpu=n, read_len=Lr, streams=nstreams, sa_sampled=args.sa_sampled or 1,
+                           parallelism="reads sharded, index replicated (1 RCCL bcast)"),
+               streams=nstreams)
+
+    def emit():
+        if args.record:
+            os.makedirs(os.path.dirname(os.path.abspath(args.record)), exist_ok=True)
+            with open(args.record, "w") as f:
+                json.dump(out, f)
+        print(json.dumps(compact_record(out)), flush=True)
+        if world > 1:
+            tdist.barrier()
+
+    if not args.full:
+        # a plain run ends here: the headline figure and what the timed steps themselves left behind
+        if rank != 0:
+            tdist.barrier()
+            return
+        out.update(kernels={name: dict(ms_total=round(ms, 3), launches=launches, avg_ms=round(ms / launches, 4))
+                            for name, (ms, launches) in ktimes.items() if launches},
+                   index=index_record())
+        emit()
+        return
+
     # serialized replay of the same steps on ONE stream: per-kernel durations without the other streams' kernels
     # sharing the chip (the timed region above is what `value` comes from, the replay what `roofline` comes from)
     ktimes_iso = {}
@@ -371,7 +425,6 @@ def main():
             slots[0]["dm"].seed(slots[0]["reads"], d_lens)         # leaves best[] of the product kernel for the checks below
             slots[0]["dm"].extend(slots[0]["reads"], d_lens)
         torch.cuda.synchronize()
-    elapsed = max_over_ranks(elapsed)
     stats = dm.stats()
     full = dm.results(n) if rank == 0 else None
 
@@ -690,28 +743,14 @@ def main():
         if roofline and nstreams > 1:
             roofline["source"] = ("timed region, steps alternating over %d HIP streams: durations include the time a kernel "
                                   "shared the chip with kernels of other steps" % nstreams)
-    total_bases = bases * world * args.steps
-    workload = "%s synthetic reference (%d bp, 5%% planted repeats), %d x %d bp %s-profile reads per GPU" \
-               % ({ECOLI_N: "E. coli K-12 sized", CHR1_N: "human chr1 sized", GRCH38_N: "GRCh38 sized"}.get(args.ref_len, "custom"),
-                  args.ref_len, n, Lr, args.profile)
-    value = total_bases / elapsed / 1e9
-    out = dict(metric="aligned Gbp/sec", value=value, unit="Gbp/s", n_gpus=world,
-               steps=args.steps, warmup=args.warmup, ms_per_step=elapsed / args.steps * 1e3,
-               higher_is_better=True, scaling="weak", vs_baseline=None, dtype="u8/u64 integer", data="synthetic",
-               value_hbm_resident=value, value_pcie_inclusive=pcie["value"] if pcie else None,
-               config=dict(workload=workload,
-                           seed_len=args.seed_len, thres=args.thres, gact_T=gact[0], gact_O=gact[1], gact_W=gact[2],
-                           reads_per_gpu=n, read_len=Lr, streams=nstreams, sa_sampled=args.sa_sampled or 1,
-                           parallelism="reads sharded, index replicated (1 RCCL bcast)"),
+    out.update(value_pcie_inclusive=pcie["value"] if pcie else None,
                roofline=roofline, roofline_hbm_kernel=roofline_hbm, cpu_baseline=cpu, pcie_inclusive=pcie,
                value_note="`value` = `value_hbm_resident`: the batch is in device memory when the timed region starts (the contract's "
                           "definition); SURVEY 8(d)'s metric with H2D of reads and D2H of results timed is `value_pcie_inclusive` "
                           "(details in `pcie_inclusive`)",
-               kernels=kernels, isolated=isolated, streams=nstreams,
+               kernels=kernels, isolated=isolated,
                algorithmic_bytes_per_base=dict(reference_layout=per_base, device_layout=dev_per_base), stats=stats,
-               index=dict(rows=hi.length, image_bytes=int(blob.numel()), reference_s=round(t_synth, 1), build_s=round(t_build, 1),
-                          pack_upload_s=round(t_pack, 1), broadcast_s=round(t_bcast, 3),
-                          host_cpus=usable_cpus(), peak_rss_gb=round(peak_rss_gb(), 1), tables=di_tables),
+               index=index_record(),
                speedup_vs_cpu=value / cpu["value"],
                speedup_pcie_inclusive_vs_cpu=(pcie["value"] / cpu["value"]) if pcie else None)
 
@@ -732,7 +771,7 @@ def main():
             torch.cuda.empty_cache()
             tmp = tempfile.TemporaryDirectory()
             child_record = os.path.join(tmp.name, "grch38.json")
-            cmd = [sys.executable, os.path.abspath(__file__), "--no-grch38", "--ref-len", str(GRCH38_N), "--steps", "10", "--warmup", "3",
+            cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-grch38", "--ref-len", str(GRCH38_N), "--steps", "10", "--warmup", "3",
                    "--pcie-steps", "6", "--cpu-seconds", "6", "--reads", str(args.reads), "--read-len", str(args.read_len),
                    "--seed-len", str(args.seed_len), "--thres", str(args.thres), "--gact", args.gact, "--record", child_record]
             tg = time.time()
@@ -758,13 +797,7 @@ def main():
                 if l.startswith("[bench]"):
                     log("grch38 child:", l[8:])
             tmp.cleanup()
-    if args.record:
-        os.makedirs(os.path.dirname(os.path.abspath(args.record)), exist_ok=True)
-        with open(args.record, "w") as f:
-            json.dump(out, f)
-    print(json.dumps(compact_record(out)), flush=True)
-    if world > 1:
-        tdist.barrier()
+    emit()
 
 
 if __name__ == "__main__":

@@ -11,7 +11,7 @@ dst = os.path.join(os.path.dirname(os.path.abspath(__file__)), tag)
 d = json.loads(open(os.path.join(dst, "bench_grch38_100k_x_10kbp.json")).read().strip().splitlines()[-1])
 ix, iso, pc, rf, cpu = d["index"], d["isolated"], d["pcie_inclusive"], d["roofline"], d["cpu_baseline"]
 out = ["", "## GRCh38-sized text on one GPU (`bench_grch38_100k_x_10kbp.json`, `.log`)", "",
-       "`python bench.py --ref-len 3099750718 --steps %d --warmup %d --cpu-seconds 8`: synthetic 3,099,750,718 bp reference "
+       "`python bench.py --full --ref-len 3099750718 --steps %d --warmup %d --cpu-seconds 8`: synthetic 3,099,750,718 bp reference "
        "(no FASTA on the box), L = %d rows; index built on the box's %d-CPU share in %.1f s (peak RSS %.1f GB), %.1f GiB "
        "image packed + uploaded in %.1f s, 64 GiB long seed table (pair-line 16-mers) derived on the device."
        % (d["steps"], d["warmup"], ix["rows"], ix["host_cpus"], ix["build_s"], ix["peak_rss_gb"], ix["image_bytes"] / 2**30,

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Turns gpurun_out/<tag>/ (written by profiles/collect.sh) into the committed summaries:
+"""Turns OUTDIR/<tag>/ (written by profiles/collect.sh TAG PART [OUTDIR]; default bench_out/profiles) into the committed summaries:
 profiles/<tag>/kernel_stats.csv (rocprofv3 --kernel-trace --stats), bench_default.json,
 pmc_summary.json (per kernel, per timed step of the default workload) and README.md."""
 import collections
@@ -12,7 +12,7 @@ import sys
 
 tag = sys.argv[1] if len(sys.argv) > 1 else "r3"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = os.path.join(ROOT, "gpurun_out", tag)
+src = os.path.join(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "bench_out", "profiles"), tag)
 dst = os.path.join(ROOT, "profiles", tag)
 os.makedirs(dst, exist_ok=True)
 
@@ -115,13 +115,13 @@ if stats1:
     shutil.copy(stats1[0], os.path.join(dst, "kernel_stats_streams1.csv"))
 with open(os.path.join(dst, "README.md"), "w") as f:
     f.write("# Profiles %s -- default `bench.py` workload on one MI355X\n\n" % tag)
-    f.write("`bench_default.json`: the full record of `python bench.py --record` (%d steps, %d warm-up, steps alternating over %d HIP "
+    f.write("`bench_default.json`: the full record of `python bench.py --full --record` (%d steps, %d warm-up, steps alternating over %d HIP "
             "streams so that kernels of different steps overlap).\n\n" % (bench["steps"], bench["warmup"], bench.get("streams", 1)))
     f.write("value = **%.2f Gbp/s**, %.1f ms per 1-Gbp step; CPU oracle on %d host cores: %.4f Gbp/s (x%.0f).\n\n"
             % (bench["value"], bench["ms_per_step"], bench["cpu_baseline"]["cores"], bench["cpu_baseline"]["value"],
                bench["speedup_vs_cpu"]))
     if b1:
-        f.write("`bench_streams1.json`: `python bench.py --streams 1` (every kernel alone on the chip): **%.2f Gbp/s**, "
+        f.write("`bench_streams1.json`: `python bench.py --full --streams 1` (every kernel alone on the chip): **%.2f Gbp/s**, "
                 "%.1f ms per step.\n\n" % (b1["value"], b1["ms_per_step"]))
     if bc:
         f.write("`bench_chr1_pacbio15k.json`: human-chr1-sized text, 50 k x 15 kbp PacBio-CLR-profile reads: **%.2f Gbp/s**, "

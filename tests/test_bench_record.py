@@ -1,6 +1,6 @@
 """bench.py's host side: the stdout line stays short enough for a log tail, and --dump-outputs keeps a fixed sample of
 the outputs inside its byte budget in float formats that hold every value.  tests/golden/bench_record.json is a full
-record (--record) of the default workload, GRCh38-sized child leg included."""
+record (--full --record) of the default workload, GRCh38-sized child leg included."""
 import json
 import os
 
@@ -38,6 +38,33 @@ def test_stdout_line_of_a_record_without_optional_legs():
     back = json.loads(json.dumps(bench.compact_record(full)))
     assert back["value"] == full["value"] and back["roofline"] is None and "pcie_inclusive" not in back
     assert back["grch38"]["failed"] == "child exit code 1" and len(back["grch38"]["stderr_tail"]) == 400
+
+
+def test_full_is_an_option_that_is_off_by_default():
+    assert bench.parse_args([]).full is False
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.gpus, a.steps, a.warmup, a.full, a.dump_outputs) == (1, 7, 2, False, None)
+    assert bench.parse_args(["--steps", "7", "--full"]).full is True
+
+
+def test_stdout_line_of_a_plain_run():
+    """A run without --full has the headline figure, the workload, the index build and the kernel times of the timed
+    steps: the line carries those and none of the legs that --full adds."""
+    with open(GOLD) as f:
+        full = json.load(f)
+    headline = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                "vs_baseline", "dtype", "data", "value_hbm_resident", "config", "streams")
+    plain = {k: full[k] for k in headline + ("index",)}
+    plain["kernels"] = {k: dict(ms_total=v["ms_total"], launches=v["launches"], avg_ms=v["avg_ms"]) for k, v in full["kernels"].items()}
+    back = json.loads(json.dumps(bench.compact_record(plain)))
+    for k in headline:
+        assert back[k] == full[k], k
+    assert back["kernel_avg_ms"]["gact_bs_kernel"] == full["kernels"]["gact_bs_kernel"]["avg_ms"]
+    assert back["index"]["build_s"] == full["index"]["build_s"]
+    for k in ("roofline", "cpu_baseline", "isolated"):
+        assert back[k] is None, k
+    for k in ("value_pcie_inclusive", "pcie_inclusive", "speedup_vs_cpu", "grch38"):
+        assert k not in back, k
 
 
 def test_dump_plan_is_fixed_and_within_budget(tmp_path):

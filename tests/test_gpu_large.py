@@ -2,7 +2,7 @@
 reference (4.4 G rows: more than 2^32, so `k`, `l`, SA values and loci all need their high bits), built by the
 product's parallel suffix sorter.  Needs ~75 GB of host RAM and about one minute on the GPU box's 16 CPUs
 (`profiles/r2/large_test.log`); it is skipped when the host has less than 110 GB available or with
-LRM_TEST_LARGE=0.  bench.py --ref-len 3099750718 asserts the same equality on the GRCh38-sized text in every run."""
+LRM_TEST_LARGE=0.  bench.py --full --ref-len 3099750718 asserts the same equality on the GRCh38-sized text in every run."""
 import os
 
 import numpy as np

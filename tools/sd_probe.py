@@ -12,7 +12,7 @@ for tag, env in variants:
     e = dict(os.environ)
     e.update(env)
     rec = tempfile.NamedTemporaryFile(suffix=".json")      # the per-kernel tables are in the full record, not in the stdout line
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "3", "--no-pcie", "--no-grch38",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "10", "--warmup", "3", "--no-pcie", "--no-grch38",
                         "--record", rec.name] + sys.argv[1:], env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     print(tag, "rc", r.returncode, flush=True)
     try:
