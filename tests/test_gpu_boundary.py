@@ -441,3 +441,57 @@ def test_map_batch_degenerate_and_ragged_batches(gpu):
         assert np.array_equal(gz["best"], bz) and np.array_equal(gz["score"], ez["score"]) and np.array_equal(gz["meta_r"], ez["meta_r"])
     finally:
         di.close()
+
+
+def test_cigar_text_that_outgrows_its_rows_is_refused(gpu, map_options):
+    """The text layout writes a unit's run-length texts into the unit's own rows of store_mem, and a run of one column
+    prints as two bytes: 8-base reads whose alignments alternate (1D1M1D1M...) have texts of 16 bytes and more, which with
+    their NUL take two 16-byte slots of a 16-byte row.  lrm_extend_batch with store_stride = 16 = 2 * max_len on a handle
+    whose default options ask for the text must fail as a whole (collect(), rc -3) -- never write beyond the unit's rows --
+    and the handle must map the next batch."""
+    import ctypes as C
+    import gact_cases
+    import sam_ref
+    rng = np.random.default_rng(12)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    pairs = [(b"GGCATCAA", b"AGAGGCTA")] + [(bytes(acgt[rng.integers(0, 4, 8)]), bytes(acgt[rng.integers(0, 4, 8)])) for _ in range(255)]
+    want = [orc.gact(q, d)[:2] for q, d in pairs]
+    texts = [sam_ref.rle(ops) for _, ops in want]
+    assert texts[0] == "1D1M1D1M1D1M1I1M1I1M1I" and sum(len(t) >= 16 for t in texts) >= 4
+    assert sum((len(t) + 1 + 15) // 16 * 16 for t in texts) > 16 * len(pairs)
+    b = gact_cases.batch_of(pairs)
+    hi = index.HostIndex.build(b["seqs"], hlen=8)
+    di = index.DeviceIndex.upload(hi, gpu)
+    try:
+        map_options(di, cigar_text=1)
+        reads, lens = gact_cases.read_matrix(b["reads"])
+        n = len(lens)
+        best = np.zeros(n, dtype=mapper.ENTRY_DT)
+        best["key"] = np.array(b["keys"], dtype=np.uint64)
+
+        def extend(store_stride):
+            store = np.full((n + 1, store_stride), 0xA5, dtype=np.uint8)       # one row of slack: must stay untouched
+            cig = (capi.Cigar * n)()
+            score, meta, meta_r = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=mapper.META_DT), np.zeros(n, dtype=np.int32)
+            rd = reads.copy()
+            rc = capi.lib.lrm_extend_batch(di.handle, rd.ctypes.data, rd.shape[1], lens.ctypes.data, n, best.ctypes.data,
+                                           capi.GactParams(*mapper.DEFAULT_GACT), C.cast(cig, C.c_void_p), store.ctypes.data, store_stride,
+                                           score.ctypes.data, meta.ctypes.data, meta_r.ctypes.data)
+            assert (store[n] == 0xA5).all()
+            return rc, store, cig, score, meta_r
+
+        rc, store, _, _, _ = extend(16)
+        assert rc < 0
+        msg = capi.lib.lrm_last_error().decode()
+        assert "run-length CIGAR text of a group" in msg and "does not fit" in msg, msg
+        rc, store, cig, score, meta_r = extend(48)                               # 33 bytes at most: three slots per row
+        assert rc == 0, capi.lib.lrm_last_error()
+        flat, base = store.reshape(-1), store.ctypes.data
+        for i in range(n):
+            o = C.cast(cig[i].cigar, C.c_void_p).value - base
+            assert 0 <= o < n * 48 and o % 16 == 0
+            t = texts[i].encode() + b"\0"
+            assert meta_r[i] == 1 and score[i] == want[i][0] and cig[i].n_cigar_op == len(want[i][1])
+            assert bytes(flat[o:o + len(t)]) == t, (i, pairs[i])
+    finally:
+        di.close()

@@ -314,6 +314,12 @@ def test_device_resident_pipeline_equals_host_path(dev_indexes, gpu):
     r = sc["reads"].copy()
     ext = mapper.extend_batch(di, r, sc["lens"], best)
     assert np.array_equal(res["score"], ext["score"]) and np.array_equal(res["n_ops"], ext["n_ops"])
+    assert np.array_equal(res["meta_r"], ext["meta_r"])
+    for f in ("loc", "off", "seq_id", "strand"):
+        assert np.array_equal(res["meta"][f], ext["meta"][f]), f
+    for i in range(n):
+        k = max(int(ext["n_ops"][i]), 0)
+        assert bytes(res["ops"][i, :k]) == bytes(ext["ops"][i, :k]), i
     assert np.array_equal(d_reads.cpu().numpy(), r)
     st = dm.stats()
     assert st["gact_tiles"] > 0
