@@ -1,8 +1,10 @@
 // SPDX-License-Identifier: MIT
 // The lane-local arithmetic of the bit-sliced GACT kernel (gact_bs_kernels.hip): the difference circuit of one
-// 32-bit half of an anti-diagonal, and the bookkeeping of one traceback block's walk.  The file compiles for the
-// device (hipcc: v_bitop3_b32, v_bfe_u32) and as plain C for the host (the same truth tables evaluated bit by bit),
-// so tests/test_gact_bs_circuit.py checks on the CPU the very source the kernel runs.
+// 32-bit half of an anti-diagonal, the bookkeeping of one traceback block's walk, and the recompute and walk of a
+// block on the 32 lattice points per anti-diagonal that one lane's walk can reach.  The file compiles for the
+// device (hipcc: v_bitop3_b32, v_bfe_u32, v_alignbit_b32) and as plain C for the host (the same truth tables
+// evaluated bit by bit), so tests/test_gact_bs_circuit.py and tests/test_gact_bs_window.py check on the CPU the
+// very source the kernel runs.
 #ifndef LRM_GACT_BS_CIRCUIT_H
 #define LRM_GACT_BS_CIRCUIT_H
 #include <stdint.h>
@@ -15,6 +17,7 @@ enum { TA = 0xF0, TB = 0xCC, TC = 0xAA };
 // gfx950 v_bitop3_b32: any boolean function of three words in one instruction
 #define BS_LOP3(a, b, c, EXPR) __builtin_amdgcn_bitop3_b32((a), (b), (c), (uint32_t) (EXPR) & 0xFFu)
 #define BS_BFE(x, off, width) __builtin_amdgcn_ubfe((x), (off), (width))          // offset and width mod 32
+#define BS_ALIGNBIT(hi, lo, sh) __builtin_amdgcn_alignbit((hi), (lo), (sh))      // bits sh .. sh+31 of hi:lo, sh mod 32
 // keeps the compiler from rewriting a value's arithmetic (it would track sums a second time, or turn a 0/1 into selects)
 #define BS_OPAQUE(x) asm("" : "+v"(x))
 #else
@@ -31,6 +34,7 @@ static inline uint32_t bs_bfe_eval(uint32_t x, uint32_t off, uint32_t width) {
     return width ? (x >> (off & 31u)) & ((1u << width) - 1u) : 0u;
 }
 #define BS_BFE(x, off, width) bs_bfe_eval((x), (off), (width))
+#define BS_ALIGNBIT(hi, lo, sh) ((uint32_t) ((((uint64_t) (hi) << 32) | (uint64_t) (lo)) >> ((sh) & 31u)))
 #define BS_OPAQUE(x) (void) (x)
 #endif
 
@@ -106,6 +110,19 @@ BS_FN int bs_walk_running(const struct BsWalk *w) {
 // One anti-diagonal.  k: its number inside the block; sk: that anti-diagonal minus 2(T-O), or BS_WALK_NO_STEP;
 // boff: bmax - (anti-diagonal of the block's first plane) / 2 + 32, so that the lane's lattice point is bit
 // nb + boff - ceil(k/2) of the 64-bit plane.  The codes (0 X, 1 =, 2 I, 3 D) are appended to *bw at bit *e2.
+// the lane's decision (n, g; both 0 where `on` is 0) taken: code appended, place advanced, stop rule applied
+BS_FN void bs_walk_take(struct BsWalk *w, uint32_t on, uint32_t n, uint32_t g, uint32_t *bw, uint32_t *e2) {
+    *bw |= ((n << 1) | g) << *e2;
+    *e2 += on << 1;
+    const uint32_t ia = BS_LOP3(on, n, g, TA & ~(TB & TC));                  // every column but 'D'
+    const uint32_t ib = BS_LOP3(on, n, g, TA & ~(TB & ~TC));                 // every column but 'I'
+    w->na += (int32_t) ia;
+    w->nb += (int32_t) ib;
+    w->ns += (int32_t) (ia + ib);
+    const uint32_t in = BS_LOP3((uint32_t) w->na, (uint32_t) w->nb, (uint32_t) w->ns, TA & TB & TC);
+    w->ns = (int32_t) BS_LOP3((uint32_t) w->ns, in, BS_WALK_STOPPED_BIT, TA & (TB | ~TC));
+}
+
 BS_FN void bs_walk_step(struct BsWalk *w, int k, int sk, int32_t boff, struct BsPl N, struct BsPl G, uint32_t *bw,
                         uint32_t *e2) {
     uint32_t on = w->ns == sk ? 1u : 0u;
@@ -116,15 +133,21 @@ BS_FN void bs_walk_step(struct BsWalk *w, int k, int sk, int32_t boff, struct Bs
     const uint32_t t = (uint32_t) (w->nb + boff - ((k + 1) >> 1));
     const int up = t > 31u;
     const uint32_t n = BS_BFE(up ? N.hi : N.lo, t, on), g = BS_BFE(up ? G.hi : G.lo, t, on);   // width 0: not on this one
-    *bw |= ((n << 1) | g) << *e2;
-    *e2 += on << 1;
-    const uint32_t ia = BS_LOP3(on, n, g, TA & ~(TB & TC));                  // every column but 'D'
-    const uint32_t ib = BS_LOP3(on, n, g, TA & ~(TB & ~TC));                 // every column but 'I'
-    w->na += (int32_t) ia;
-    w->nb += (int32_t) ib;
-    w->ns += (int32_t) (ia + ib);
-    const uint32_t in = BS_LOP3((uint32_t) w->na, (uint32_t) w->nb, (uint32_t) w->ns, TA & TB & TC);
-    w->ns = (int32_t) BS_LOP3((uint32_t) w->ns, in, BS_WALK_STOPPED_BIT, TA & (TB | ~TC));
+    bs_walk_take(w, on, n, g, bw, e2);
+}
+
+// The same on the block's 32-point window (below): N, G hold plane bits o .. o+31 and boffw = boff - o, so the
+// lane's lattice point is bit nb + boffw - ceil(k/2), always inside the word while the lane steps in this block.
+BS_FN void bs_walk_step_win(struct BsWalk *w, int k, int sk, int32_t boffw, uint32_t N, uint32_t G, uint32_t *bw,
+                            uint32_t *e2) {
+    uint32_t on = w->ns == sk ? 1u : 0u;
+    BS_OPAQUE(on);
+    BS_OPAQUE(w->nb);
+    BS_OPAQUE(*e2);
+    BS_OPAQUE(*bw);
+    const uint32_t t = (uint32_t) (w->nb + boffw - ((k + 1) >> 1));
+    const uint32_t n = BS_BFE(N, t, on), g = BS_BFE(G, t, on);
+    bs_walk_take(w, on, n, g, bw, e2);
 }
 
 BS_FN uint32_t bs_popcount32(uint32_t x) {
@@ -138,21 +161,108 @@ BS_FN uint32_t bs_popcount32(uint32_t x) {
 // The whole block: anti-diagonals sbase .. sbase + BS_K - 1 (sbase a multiple of BS_K), lim2 = 2(T-O),
 // boff = bmax - sbase/2 + 32.  Returns the block's codes, *e2 = twice their number.  The score (one per column
 // that is not '=') is counted from the code words afterwards instead of step by step.
-BS_FN uint64_t bs_walk_block(struct BsWalk *w, const struct BsPl *N, const struct BsPl *G, int sbase, int lim2, int32_t boff,
-                             uint32_t *e2) {
-    uint32_t bw[2] = {0u, 0u}, e[2] = {0u, 0u};
-    BS_OPAQUE(boff);
-#pragma unroll
-    for (int k = 0; k < BS_K; ++k) {
-        const uint32_t sk = (uint32_t) (sbase - lim2 + k);                    // negative, or past the last anti-diagonal
-
-        bs_walk_step(w, k, (int32_t) (sk > BS_WALK_NO_STEP ? sk : BS_WALK_NO_STEP), boff, N[k], G[k], &bw[k >= BS_K / 2], &e[k >= BS_K / 2]);
-    }
+BS_FN int32_t bs_walk_sk(int sbase, int lim2, int k) {
+    const uint32_t sk = (uint32_t) (sbase - lim2 + k);                        // negative, or past the last anti-diagonal
+    return (int32_t) (sk > BS_WALK_NO_STEP ? sk : BS_WALK_NO_STEP);
+}
+BS_FN uint64_t bs_walk_join(struct BsWalk *w, const uint32_t *bw, const uint32_t *e, uint32_t *e2) {
     const uint32_t eq = bs_popcount32(BS_LOP3(bw[0], bw[0] >> 1, 0x55555555u, TA & ~TB & TC)) +
                         bs_popcount32(BS_LOP3(bw[1], bw[1] >> 1, 0x55555555u, TA & ~TB & TC));
     *e2 = e[0] + e[1];
     w->score += (int32_t) ((*e2 >> 1) - eq);
     return (uint64_t) bw[0] | ((uint64_t) bw[1] << e[0]);                   // e[0] <= 32
+}
+
+BS_FN uint64_t bs_walk_block(struct BsWalk *w, const struct BsPl *N, const struct BsPl *G, int sbase, int lim2, int32_t boff,
+                             uint32_t *e2) {
+    uint32_t bw[2] = {0u, 0u}, e[2] = {0u, 0u};
+    BS_OPAQUE(boff);
+#pragma unroll
+    for (int k = 0; k < BS_K; ++k)
+        bs_walk_step(w, k, bs_walk_sk(sbase, lim2, k), boff, N[k], G[k], &bw[k >= BS_K / 2], &e[k >= BS_K / 2]);
+    return bs_walk_join(w, bw, e, e2);
+}
+
+// on the window planes of bs_win_block, o the window's origin
+BS_FN uint64_t bs_walk_block_win(struct BsWalk *w, const uint32_t *N, const uint32_t *G, int sbase, int lim2, int32_t boff,
+                                 uint32_t o, uint32_t *e2) {
+    uint32_t bw[2] = {0u, 0u}, e[2] = {0u, 0u};
+    int32_t boffw = boff - (int32_t) o;
+    BS_OPAQUE(boffw);
+#pragma unroll
+    for (int k = 0; k < BS_K; ++k)
+        bs_walk_step_win(w, k, bs_walk_sk(sbase, lim2, k), boffw, N[k], G[k], &bw[k >= BS_K / 2], &e[k >= BS_K / 2]);
+    return bs_walk_join(w, bw, e, e2);
+}
+
+// ----------------------------------------------------------------------------------------
+// a traceback block recomputed on a 32-point window
+// ----------------------------------------------------------------------------------------
+// The only reader of a block's decision planes is the lane's own walk, and where it enters is known before the
+// recompute: plane bit t0 = nb + boff of anti-diagonal k = 0 of the block (a walk that enters on k = 1 is on bit
+// t0 - 1 of that plane, which is what a step from bit t0 of k = 0 can reach).  Crossing k anti-diagonals moves a
+// walk by at most k diagonals, and in plane bits (even k: diagonal 2t - 64, odd k: 2t - 63) that is
+//     even k:  t0 - k/2 <= t <= t0 + k/2          odd k:  t0 - (k+1)/2 <= t <= t0 + (k-1)/2
+// so every point the walk can be on has t0 - 16 <= t <= t0 + 15 on every anti-diagonal of the block (k <= 31):
+// ONE 32-bit word per plane with a fixed origin o, the same bit numbering on all anti-diagonals.  The set is closed
+// under the recurrence: a point of it on anti-diagonal k reads its neighbours' bits t-1, t (even k) or t, t+1
+// (odd k) of anti-diagonal k+1, which satisfy the bound of k+1.  So the step is the full-width step on one word
+// (u = H << 1 on even, w = V >> 1 on odd anti-diagonals), and the zeros the shifts bring in at an inner edge of the
+// window spoil one more bit every second step, exactly as fast as the reachable set draws back from that edge.
+// The origin is clamped to the plane (o = min(max(t0 - 16, 0), 32)): the window then never holds a point outside
+// the 64 of the plane, an edge it shares with the plane gets the zeros the full-width step gets there, and what
+// the clamp cuts off is out of the band anyway.  The 33 reachable points of the checkpoint (k = BS_K) enter only
+// as the inputs of the first step: u = H bits o .. o+31, w = V bits o+1 .. o+32.
+// Valid for a band of all 128 diagonals and no free-exit point near it (the unmasked step).
+BS_FN uint32_t bs_win_origin(int32_t t0) {
+    const int32_t o = t0 - 16;
+    return (uint32_t) (o < 0 ? 0 : o > 32 ? 32 : o);
+}
+// bits o .. o+31 of hi:lo, 0 <= o <= 33
+BS_FN uint32_t bs_win32(uint32_t lo, uint32_t hi, uint32_t o) {
+    return (uint32_t) ((((uint64_t) hi << 32) | (uint64_t) lo) >> o);
+}
+
+// What the block reads, cut to the window.  ck: the checkpoint as stored (V1, V0, H1, H0, each lo then hi);
+// q, d: the block's three stream words of one sequence bit-plane, bit 0 of q[0] / d[0] being plane bit 0 at window
+// shift 0; kept are stream bits o .. o+63, from which a step takes its word with one funnel shift by its own
+// (compile-time) window shift.
+struct BsWinIn {
+    uint32_t u1, u0, w1, w0;                 // neighbour inputs of step BS_K - 1
+    uint32_t ql[2], qh[2], dl[2], dh[2];
+};
+BS_FN void bs_win_cut_ck(struct BsWinIn *in, const uint32_t *ck, uint32_t o) {
+    in->w1 = bs_win32(ck[0], ck[1], o + 1u); in->w0 = bs_win32(ck[2], ck[3], o + 1u);
+    in->u1 = bs_win32(ck[4], ck[5], o);      in->u0 = bs_win32(ck[6], ck[7], o);
+}
+BS_FN void bs_win_cut_seq(uint32_t *out, uint32_t s0, uint32_t s1, uint32_t s2, uint32_t o) {
+    out[0] = bs_win32(s0, s1, o);
+    out[1] = bs_win32(s1, s2, o);
+}
+
+// The block's BS_K steps, BS_K - 1 down to 0: N[k], G[k] = decision bits of plane bits o .. o+31 of anti-diagonal k.
+// The query window starts at shift 0 and moves up by one after every even anti-diagonal, the text window starts
+// at BS_K/2 and moves down by one after every odd one (the order of the full-width recompute).
+BS_FN void bs_win_block(const struct BsWinIn *in, uint32_t *N, uint32_t *G) {
+    uint32_t V1 = 0u, V0 = 0u, H1 = 0u, H0 = 0u;
+    uint32_t ql = in->ql[0], qh = in->qh[0];
+    uint32_t dl = BS_ALIGNBIT(in->dl[1], in->dl[0], BS_K / 2), dh = BS_ALIGNBIT(in->dh[1], in->dh[0], BS_K / 2);
+#pragma unroll
+    for (int k = BS_K - 1; k >= 1; k -= 2) {
+        const int first = k == BS_K - 1;
+        struct BsHalf x = bs_half_circuit(0, 1, first ? in->u1 : H1, first ? in->u0 : H0, first ? in->w1 : V1 >> 1,
+                                          first ? in->w0 : V0 >> 1, ql, qh, dl, dh, 0u, 0u);
+        N[k] = x.N; G[k] = x.G;
+        const uint32_t shd = (uint32_t) ((k - 1) >> 1);                          // K/2-1 .. 0
+        dl = BS_ALIGNBIT(in->dl[1], in->dl[0], shd); dh = BS_ALIGNBIT(in->dh[1], in->dh[0], shd);
+        x = bs_half_circuit(0, 1, x.H1 << 1, x.H0 << 1, x.V1, x.V0, ql, qh, dl, dh, 0u, 0u);
+        N[k - 1] = x.N; G[k - 1] = x.G;
+        V1 = x.V1; V0 = x.V0; H1 = x.H1; H0 = x.H0;
+        if (k > 1) {
+            const uint32_t shq = (uint32_t) (BS_K / 2 - ((k - 1) >> 1));         // 1 .. K/2-1
+            ql = BS_ALIGNBIT(in->ql[1], in->ql[0], shq); qh = BS_ALIGNBIT(in->qh[1], in->qh[0], shq);
+        }
+    }
 }
 
 #endif

@@ -31,7 +31,11 @@
 // (32 B per lane and checkpoint).  Pass 2 takes the 32-step blocks in walk order: recompute the block
 // from its checkpoint with the decision planes kept in registers, then walk through it -- every lane
 // follows its own path with the steps predicated on "my path is on this anti-diagonal" (the walk's bookkeeping:
-// gact_bs_circuit.h, bs_walk_block).
+// gact_bs_circuit.h, bs_walk_block).  The only reader of a block's decisions is the lane's own walk, which stays
+// within k diagonals of where it entered after k anti-diagonals: 32 lattice points per anti-diagonal, closed under
+// the recurrence.  So a block with no free-exit point near the band (and the full band, W = 128) is recomputed
+// and walked on ONE 32-bit word per plane, cut out of the checkpoint and the sequence windows around the lane's
+// entry point (gact_bs_circuit.h, bs_win_block / bs_walk_block_win); the other blocks keep the full-width masked step.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include "lrm_hip_util.h"
@@ -439,22 +443,37 @@ __global__ __launch_bounds__(64) void gact_bs_kernel(const uint64_t *__restrict_
         bs_block_prefetch(raw, t, 0, ckw, lane);
         for (int c = 0; c < nb; ++c) {
             if (__ballot(bs_walk_running(&wk)) == 0) break;
-            {
-                const int A0 = BS_H * (c + 1) + 31, b_lo = BS_H * c - 32;
-                st.q0 = bs_q_conv(t, A0, raw.q0); st.q1 = bs_q_conv(t, A0 - 32, raw.q1); st.q2 = bs_q_conv(t, A0 - 64, raw.q2);
-                st.d0 = bs_d_conv(t, b_lo, raw.d0); st.d1 = bs_d_conv(t, b_lo + 32, raw.d1); st.d2 = bs_d_conv(t, b_lo + 64, raw.d2);
+            const int A0 = BS_H * (c + 1) + 31, b_lo = BS_H * c - 32;
+            st.q0 = bs_q_conv(t, A0, raw.q0); st.q1 = bs_q_conv(t, A0 - 32, raw.q1); st.q2 = bs_q_conv(t, A0 - 64, raw.q2);
+            st.d0 = bs_d_conv(t, b_lo, raw.d0); st.d1 = bs_d_conv(t, b_lo + 32, raw.d1); st.d2 = bs_d_conv(t, b_lo + 64, raw.d2);
+            // A free-exit point near the band, or a band narrower than the planes (wave-uniform): the block in full width
+            // with the masked step.  Every other block on the 32 points per anti-diagonal that the lane's walk can reach
+            // from where it stands (gact_bs_circuit.h); lanes that do not walk compute something nobody reads.
+            const bool full = bs_any_sentinel(st);
+            const int32_t boff = bmax - BS_H * c + 32;
+            const uint32_t o = bs_win_origin(wk.nb + boff);
+            BsWinIn win;
+            if (full) {
                 x.V1.lo = raw.ck[0]; x.V1.hi = raw.ck[1]; x.V0.lo = raw.ck[2]; x.V0.hi = raw.ck[3];
                 x.H1.lo = raw.ck[4]; x.H1.hi = raw.ck[5]; x.H0.lo = raw.ck[6]; x.H0.hi = raw.ck[7];
                 bs_extract_q<true>(st, 0);
                 bs_extract_d<true>(st, BS_H);
+            } else {
+                bs_win_cut_ck(&win, raw.ck, o);
+                bs_win_cut_seq(win.ql, st.q0.lo, st.q1.lo, st.q2.lo, o); bs_win_cut_seq(win.qh, st.q0.hi, st.q1.hi, st.q2.hi, o);
+                bs_win_cut_seq(win.dl, st.d0.lo, st.d1.lo, st.d2.lo, o); bs_win_cut_seq(win.dh, st.d0.hi, st.d1.hi, st.d2.hi, o);
             }
             // the next block's words and checkpoint are fetched a whole block ahead (248 VGPRs: still two wavefronts per SIMD;
             // behind the recompute, with only the walk in between: 11.72 against 11.57 ms)
             if (c + 1 < nb) bs_block_prefetch(raw, t, c + 1, ckw, lane);
             // the previous block's full code word goes out here, behind the loads it must not delay
             if (has_pend) { cout[widx++] = pend; has_pend = false; }
-            BsPl N[BS_K], G[BS_K];
-            if (bs_any_sentinel(st)) {
+            // walk: the lane's path crosses each anti-diagonal at most once; codes 0 X, 1 =, 2 I, 3 D.
+            // Branch-free: every step runs in all lanes, gated by "my path is on this anti-diagonal".
+            uint32_t e2;
+            uint64_t bw;
+            if (full) {
+                BsPl N[BS_K], G[BS_K];
 #pragma unroll
                 for (int k = BS_K - 1; k >= 1; k -= 2) {
                     bs_step<true, true, true>(x, st, N[k], G[k]);
@@ -462,19 +481,12 @@ __global__ __launch_bounds__(64) void gact_bs_kernel(const uint64_t *__restrict_
                     bs_step<false, true, true>(x, st, N[k - 1], G[k - 1]);
                     if (k > 1) bs_extract_q<true>(st, (uint32_t) (BS_H - ((k - 1) >> 1)));   // 1 .. K/2-1
                 }
+                bw = bs_walk_block(&wk, N, G, BS_K * c, lim2, boff, &e2);
             } else {
-#pragma unroll
-                for (int k = BS_K - 1; k >= 1; k -= 2) {
-                    bs_step<true, false, true>(x, st, N[k], G[k]);
-                    bs_extract_d<false>(st, (uint32_t) ((k - 1) >> 1));
-                    bs_step<false, false, true>(x, st, N[k - 1], G[k - 1]);
-                    if (k > 1) bs_extract_q<false>(st, (uint32_t) (BS_H - ((k - 1) >> 1)));
-                }
+                uint32_t N[BS_K], G[BS_K];
+                bs_win_block(&win, N, G);
+                bw = bs_walk_block_win(&wk, N, G, BS_K * c, lim2, boff, o, &e2);
             }
-            // walk: the lane's path crosses each anti-diagonal at most once; codes 0 X, 1 =, 2 I, 3 D.
-            // Branch-free: every step runs in all lanes, gated by "my path is on this anti-diagonal".
-            uint32_t e2;
-            const uint64_t bw = bs_walk_block(&wk, N, G, BS_K * c, lim2, bmax - BS_H * c + 32, &e2);
             // append the block's codes (at most 32) to the lane's code stream
             sb |= bw << fill;
             cnt += (int) (e2 >> 1);
