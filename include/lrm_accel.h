@@ -79,7 +79,7 @@ typedef struct lrm_mta_entry {
 typedef struct lrm_seq_meta { uint64_t loc, off; int32_t seq_id; uint8_t strand; } lrm_seq_meta;
 
 /* gact `cigar` as used at mutils.c:97-103 / alnmain.c:314-325: one op byte per
- * alignment column ('=' 'X' 'I' 'D') in a caller-owned buffer */
+ * alignment column ('=' 'X' 'I' 'D'; 'S' at the two ends only with lrm_map_options.clip) in a caller-owned buffer */
 typedef struct lrm_cigar { uint8_t *cigar; int n_cigar_op; int score; } lrm_cigar;
 
 /* GACT tile / overlap / band (docs/GACT_SPEC.md); {0,0,0} selects the defaults */
@@ -169,7 +169,16 @@ typedef struct lrm_map_options {
                                   base (SAM POS).  Needs store_stride >= 2*max_len + max_len/8 + 2.  0: every read is aligned
                                   against the window at the voted locus (alnmain.c:440-446) */
     uint32_t anchor_min_len;   /* shortest exact match that anchors a read: 0 = 20 (the default seed length), else 12..64 */
-    uint32_t reserved[5];
+    uint32_t clip;             /* 1 (needs anchored): END CLIPPING (docs/GACT_SPEC.md, "End clipping"): each of the two jobs of an
+                                  anchored read keeps the best-scoring prefix of its columns, counted outward from the anchor
+                                  ('=' +1, 'X' / 'I' / 'D' -clip_penalty; the smallest such prefix), when that gains more than
+                                  clip_end_bonus over keeping the whole job; the query bases of the columns that go become 'S'
+                                  columns at the ends of the ops, score counts the aligned columns only and meta_out[i].loc / .off
+                                  is the first ALIGNED text base.  Unanchored reads are left as the anchored mode leaves them.
+                                  0: both jobs are global in the read */
+    uint32_t clip_penalty;     /* P: 0 = 2, else 1..15 */
+    uint32_t clip_end_bonus;   /* B: 0 = 6, else 1..255 */
+    uint32_t reserved[2];
 } lrm_map_options;
 void lrm_map_options_init(lrm_map_options *o);
 
@@ -357,11 +366,14 @@ int lrm_extend_batch_dev(lrm_index *idx, lrm_workspace *ws, char *d_reads, uint6
 #define LRM_ANCHOR_NO_LEFT 4u          /*   the anchor starts at the read's first base: no left job */
 #define LRM_ANCHOR_LEFT_CLIPPED 8u     /*   the left job's target window ends at the start of the sequence */
 #define LRM_ANCHOR_RIGHT_CLIPPED 16u   /*   the right job's target window ends at the end of the sequence */
+#define LRM_ANCHOR_SOFT_LEFT 32u       /*   end clipping: the ops begin with 'S' columns */
+#define LRM_ANCHOR_SOFT_RIGHT 64u      /*   end clipping: the ops end with 'S' columns */
 typedef struct lrm_anchor {
     uint64_t text_pos;                 /* text position of read[read_pos] (forward half of the sequence) */
     uint32_t read_pos, len;            /* the exact match read[read_pos .. read_pos + len) */
     int32_t delta;                     /* its diagonal relative to the voted locus */
-    uint32_t left_ops;                 /* alignment columns of the left job (the first left_ops op bytes of the read) */
+    uint32_t left_ops;                 /* alignment columns of the left job (the first left_ops op bytes of the read; with end
+                                          clipping: its 'S' columns and the columns it kept) */
     uint32_t flags;                    /* LRM_ANCHOR_*; 0 for a read without a locus (meta_r == 0) */
 } lrm_anchor;
 int lrm_extend_batch_anchored_dev(lrm_index *idx, lrm_workspace *ws, char *d_reads, uint64_t stride,
@@ -370,6 +382,19 @@ int lrm_extend_batch_anchored_dev(lrm_index *idx, lrm_workspace *ws, char *d_rea
                                   uint64_t store_stride, int32_t *d_n_ops, int32_t *d_score,
                                   lrm_seq_meta *d_meta, int32_t *d_meta_r, lrm_anchor *d_anchor, uint32_t min_len,
                                   void *stream);
+
+/* The anchored extension with END CLIPPING (lrm_map_options.clip; docs/GACT_SPEC.md, "End clipping"): the arguments of
+ * lrm_extend_batch_anchored_dev (which never clips, whatever the handle's options say), the penalty P (clip_penalty: 0 = 2,
+ * else 1..15), the end bonus B (clip_end_bonus: 0 = 6, else 1..255) and the soft-clipped bases per read (d_clip: n entries
+ * in device memory, may be NULL; zeros for a read the step leaves alone: unanchored or without a locus).  The first
+ * clipping call on a workspace allocates 16 bytes per job on top of the mode's scratch. */
+typedef struct lrm_clip { uint32_t left, right; } lrm_clip;     /* 'S' columns at the start / at the end of the ops */
+int lrm_extend_batch_clipped_dev(lrm_index *idx, lrm_workspace *ws, char *d_reads, uint64_t stride,
+                                 const uint32_t *d_lens, uint64_t n, uint32_t max_len,
+                                 const lrm_entry *d_best, lrm_gact_params gp, uint8_t *d_store,
+                                 uint64_t store_stride, int32_t *d_n_ops, int32_t *d_score,
+                                 lrm_seq_meta *d_meta, int32_t *d_meta_r, lrm_anchor *d_anchor, uint32_t min_len,
+                                 uint32_t clip_penalty, uint32_t clip_end_bonus, lrm_clip *d_clip, void *stream);
 
 /* Counters of the last *_dev call on this workspace (device->host copy, syncs
  * the stream): vote items per table tier, reads decided in
@@ -392,7 +417,8 @@ int lrm_workspace_stats(lrm_workspace *ws, lrm_stats *out, void *stream);
 /* Per-kernel timing with HIP events recorded on the launch stream (bench bookkeeping).
  * Kernel order: pack2bit, seed_search, vote, decide, locus_resolve, revcomp, gact (byte kernels),
  * bs_pack_reads, gact_bs (bit-sliced kernel + expansion).  The anchored mode adds its anchor scan to the
- * locus_resolve slot, its job builder to the revcomp slot and its stitch to the slot of the extension kernel.
+ * locus_resolve slot, its job builder to the revcomp slot, its end clipping and its stitch to the slot of the extension
+ * kernel.
  * lrm_workspace_timing synchronises the stream, ADDS the elapsed milliseconds and launch counts
  * of everything recorded since the last call into ms[LRM_N_KERNELS] / launches[LRM_N_KERNELS], and
  * resets the record. */

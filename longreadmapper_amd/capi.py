@@ -78,7 +78,8 @@ class MapOptions(C.Structure):         # lrm_map_options
                 ("seed_rounds", C.c_int32), ("vote_exact_only", C.c_int32), ("slice_reads", C.c_uint32),
                 ("sub_batches", C.c_uint32), ("group_subs", C.c_uint32), ("bs_waves", C.c_uint32),
                 ("cigar_text", C.c_uint32), ("copy_threads", C.c_uint32), ("keep_reads", C.c_uint32), ("anchored", C.c_uint32),
-                ("anchor_min_len", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+                ("anchor_min_len", C.c_uint32), ("clip", C.c_uint32), ("clip_penalty", C.c_uint32),
+                ("clip_end_bonus", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
 class Anchor(C.Structure):             # lrm_anchor
@@ -86,7 +87,14 @@ class Anchor(C.Structure):             # lrm_anchor
                 ("left_ops", C.c_uint32), ("flags", C.c_uint32)]
 
 
+
+
+class Clip(C.Structure):               # lrm_clip
+    _fields_ = [("left", C.c_uint32), ("right", C.c_uint32)]
+
+
 ANCHOR_ANCHORED, ANCHOR_FALLBACK, ANCHOR_NO_LEFT, ANCHOR_LEFT_CLIPPED, ANCHOR_RIGHT_CLIPPED = 1, 2, 4, 8, 16
+ANCHOR_SOFT_LEFT, ANCHOR_SOFT_RIGHT = 32, 64      # end clipping (lrm_map_options.clip)
 ANCHOR_DIAGS = 64                      # LRM_ANCHOR_DIAGS
 
 
@@ -108,7 +116,7 @@ class HostIndex(C.Structure):          # lrm_index_host.h
 
 
 assert C.sizeof(Ui40) == 8 and C.sizeof(Entry) == 24 and C.sizeof(SeqMeta) == 24
-assert C.sizeof(MapOptions) == 76 and C.sizeof(Anchor) == 32
+assert C.sizeof(MapOptions) == 76 and C.sizeof(Anchor) == 32 and C.sizeof(Clip) == 8
 
 # every symbol include/*.h declares: (restype, argtypes)
 SYMBOLS = {
@@ -180,6 +188,10 @@ SYMBOLS = {
     "lrm_extend_batch_anchored_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                                 C.c_uint32, C.c_void_p, GactParams, C.c_void_p, C.c_uint64, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "lrm_extend_batch_clipped_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                               C.c_uint32, C.c_void_p, GactParams, C.c_void_p, C.c_uint64, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                               C.c_uint32, C.c_void_p, C.c_void_p]),
     "lrm_debug_anchor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(Anchor)]),
     "lrm_workspace_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats), C.c_void_p]),
     "lrm_workspace_set_counting": (C.c_int, [C.c_void_p, C.c_int]),

@@ -3,7 +3,9 @@
 //   anchor_scan     the longest exact match of a read on the LRM_ANCHOR_DIAGS diagonals around its voted locus
 //   anchor_jobs     the job table (2 rows per read: right job, left job) and the job read rows
 //   (extension)     ONE launch of the unchanged extension kernels over the job table (lrm_gact_launch_jobs)
-//   anchor_stitch   reverse(left ops) ++ right ops into the caller's store, sums, moved meta, lrm_anchor records
+//   anchor_clip     (lrm_map_options.clip) per job: the best-scoring prefix of its op bytes and what that prefix holds
+//   anchor_stitch   reverse(left ops) ++ right ops into the caller's store, sums, moved meta, lrm_anchor records; with
+//                   the clip records: the kept prefixes between runs of 'S'
 //
 // Scan: a wavefront takes one SEGMENT of one read and its 64 lanes take the 64 diagonals.  Per 32 read bases a lane
 // builds one 32-bit mismatch word -- from the bit-planar images the bit-sliced extension already keeps (reads:
@@ -19,6 +21,7 @@
 #include <cstdlib>
 #include "lrm_hip_util.h"
 #include "seq_bytes.h"
+#include "anchor_clip.h"
 
 #define AN_SEG_WORDS 64                       // words (of 32 bases) per scan segment: 2048 bases
 #define AN_HALF (LRM_ANCHOR_DIAGS / 2)
@@ -35,6 +38,7 @@ struct LrmAnchorScratch {
     int32_t *job_meta_r, *job_nops, *job_score;
     uint8_t *job_store; uint64_t job_store_stride;
     lrm_anchor *anchors;                      // used when the caller passes none
+    uint4 *clip_recs;                         // end clipping, per job {keep, non_eq, non_I, non_D}: allocated by its first call
     LrmBsScratch bs;                          // bit-sliced extension over the job table
 };
 
@@ -258,6 +262,59 @@ __global__ __launch_bounds__(256) void anchor_jobs_kernel(const char *__restrict
     if (c0 < j) an_fill_row<true>(left, src, j, c0, min(c0 + AN_CHUNK, j), tid);
 }
 
+// ---- clip ------------------------------------------------------------------------------------------------------------
+// One wavefront per job.  Per step the wavefront takes 1024 op bytes of the job's row, 16 per lane with one aligned load
+// (job rows are 16-byte aligned); a lane folds its columns into (sum, key) (anchor_clip.h), an inclusive scan of the sums
+// places the lanes' keys in the step, their maximum is merged into the carried summary of the row.  With `keep` known, a
+// second sweep over the kept prefix counts its columns other than '=', other than 'I' and other than 'D'.
+__device__ __forceinline__ void an_clip_load(const uint8_t *row, uint32_t off, uint32_t m, uint32_t w[4]) {
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (off < m) v = *reinterpret_cast<const uint4 *>(row + off);
+    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+}
+__global__ __launch_bounds__(256) void anchor_clip_kernel(uint64_t n_jobs, const int32_t *__restrict__ job_meta_r,
+                                                          const unsigned long long *__restrict__ keys,
+                                                          const uint8_t *__restrict__ job_store, uint64_t job_store_stride,
+                                                          const int32_t *__restrict__ job_nops, uint32_t P, uint32_t B,
+                                                          uint4 *__restrict__ recs) {
+    const uint64_t job = (uint64_t) blockIdx.x * 4 + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63;
+    if (job >= n_jobs) return;
+    const bool live = job_meta_r[job] != 0;
+    const uint32_t m = live ? min((uint32_t) job_nops[job], (uint32_t) job_store_stride) : 0;
+    if (!live || keys[job >> 1] == 0) {               // no job, or the single job of an unanchored read: kept whole
+        if (lane == 0) recs[job] = make_uint4(m, 0, 0, 0);
+        return;
+    }
+    const uint8_t *row = job_store + job * job_store_stride;
+    AcSeg acc = ac_empty();
+    for (uint32_t base = 0; base < m; base += 64 * AC_LANE_COLS) {
+        const uint32_t off = base + AC_LANE_COLS * lane;
+        uint32_t w[4];
+        an_clip_load(row, off, m, w);
+        const AcSeg l = ac_fold16(w, off < m ? m - off : 0, P);
+        const uint32_t incl = wave_incl_scan((uint32_t) l.sum);
+        const uint64_t placed = ac_key_move(l.key, (int32_t) (incl - (uint32_t) l.sum), AC_LANE_COLS * lane);
+        AcSeg step;
+        step.key = wave_max_u64(placed);
+        step.sum = __builtin_amdgcn_readlane((int) incl, 63);
+        acc = ac_merge(acc, base, step);
+    }
+    const uint32_t keep = ac_keep(acc, m, B);
+    uint32_t non_eq = 0, non_i = 0, non_d = 0;
+    for (uint32_t base = 0; base < keep; base += 64 * AC_LANE_COLS) {
+        const uint32_t off = base + AC_LANE_COLS * lane;
+        uint32_t w[4];
+        an_clip_load(row, off, keep, w);
+        const uint32_t nv = off < keep ? keep - off : 0;
+        non_eq += ac_count_not(w, nv, '=');
+        non_i += ac_count_not(w, nv, 'I');
+        non_d += ac_count_not(w, nv, 'D');
+    }
+    non_eq = wave_incl_scan(non_eq); non_i = wave_incl_scan(non_i); non_d = wave_incl_scan(non_d);
+    if (lane == 63) recs[job] = make_uint4(keep, non_eq, non_i, non_d);       // the last lane holds the totals
+}
+
 // ---- stitch ----------------------------------------------------------------------------------------------------------
 // the whole 24-byte record, padding included: the mode's meta is the same bytes whatever the buffer held before
 __device__ __forceinline__ void an_store_meta(lrm_seq_meta *dst, uint64_t loc, uint64_t off, int32_t seq_id, uint8_t strand) {
@@ -276,7 +333,8 @@ __global__ __launch_bounds__(256) void anchor_stitch_kernel(const uint32_t *__re
                                                             const int32_t *__restrict__ job_score,
                                                             uint8_t *__restrict__ store, uint64_t store_stride,
                                                             int32_t *__restrict__ n_ops, int32_t *__restrict__ score,
-                                                            lrm_anchor *__restrict__ anchors) {
+                                                            lrm_anchor *__restrict__ anchors,
+                                                            const uint4 *__restrict__ clip_recs, lrm_clip *__restrict__ clip_out) {
     __shared__ uint32_t s_cnt[4];
     const uint64_t r = blockIdx.x / chunks_per_read;
     const uint32_t chunk = blockIdx.x % chunks_per_read, tid = threadIdx.x;
@@ -287,6 +345,7 @@ __global__ __launch_bounds__(256) void anchor_stitch_kernel(const uint32_t *__re
             an_store_meta(meta + r, 0, 0, -1, 0);
             lrm_anchor z = {};
             anchors[r] = z;
+            if (clip_out) clip_out[r] = lrm_clip{0, 0};
         }
         return;
     }
@@ -294,37 +353,50 @@ __global__ __launch_bounds__(256) void anchor_stitch_kernel(const uint32_t *__re
     const uint64_t S = mta[m.seq_id].offset, len_s = mta[m.seq_id].seq_len;
     const AnPlan a = an_plan(keys[r], m.loc, lens[r], S, len_s);
     const bool left = (a.flags & LRM_ANCHOR_ANCHORED) && a.j > 0;
-    const uint32_t nr = (uint32_t) job_nops[2 * r], nl = left ? (uint32_t) job_nops[2 * r + 1] : 0, total = nl + nr;
+    // end clipping (anchored reads only): the jobs' kept prefixes stand for the jobs, cl / cr query bases become 'S'
+    const bool clip = clip_recs && (a.flags & LRM_ANCHOR_ANCHORED);
+    const uint4 rec_r = clip ? clip_recs[2 * r] : make_uint4(0, 0, 0, 0);
+    const uint4 rec_l = clip && left ? clip_recs[2 * r + 1] : make_uint4(0, 0, 0, 0);
+    const uint32_t nr = clip ? rec_r.x : (uint32_t) job_nops[2 * r];
+    const uint32_t nl = clip ? rec_l.x : left ? (uint32_t) job_nops[2 * r + 1] : 0;
+    const uint32_t cl = clip ? a.j - rec_l.w : 0, cr = clip ? (lens[r] - a.j) - rec_r.w : 0;
+    const uint32_t b0 = cl, b1 = cl + nl, b2 = b1 + nr, total = b2 + cr;      // 'S' | reversed left | right | 'S'
     const uint8_t *rrow = job_store + 2 * r * job_store_stride, *lrow = rrow + job_store_stride;
     uint8_t *out = store + r * store_stride;
     const uint32_t c1 = min((chunk + 1) * AN_CHUNK, total);
     for (uint32_t o = chunk * AN_CHUNK + 16 * tid; o < c1; o += 16 * 256) {
         An16 v;
-        if (o + 16 <= nl) {                        // reversed left ops
-            const An16 s = *reinterpret_cast<const An16 *>(lrow + (nl - 16 - o));
+        if (o >= b0 && o + 16 <= b1) {             // reversed left ops
+            const An16 s = *reinterpret_cast<const An16 *>(lrow + (b1 - 16 - o));
             v.x = __builtin_bswap32(s.w); v.y = __builtin_bswap32(s.z); v.z = __builtin_bswap32(s.y); v.w = __builtin_bswap32(s.x);
             *reinterpret_cast<An16 *>(out + o) = v;
-        } else if (o >= nl && o + 16 <= total) {   // right ops
-            *reinterpret_cast<An16 *>(out + o) = *reinterpret_cast<const An16 *>(rrow + (o - nl));
-        } else {
-            for (uint32_t e = o; e < o + 16 && e < total; ++e) out[e] = e < nl ? lrow[nl - 1 - e] : rrow[e - nl];
+        } else if (o >= b1 && o + 16 <= b2) {      // right ops
+            *reinterpret_cast<An16 *>(out + o) = *reinterpret_cast<const An16 *>(rrow + (o - b1));
+        } else if (o + 16 <= b0 || (o >= b2 && o + 16 <= total)) {
+            v.x = v.y = v.z = v.w = 0x53535353u;   // 'S'
+            *reinterpret_cast<An16 *>(out + o) = v;
+        } else {                                   // a group that straddles a seam, or the tail
+            for (uint32_t e = o; e < o + 16 && e < total; ++e)
+                out[e] = e < b0 || e >= b2 ? (uint8_t) 'S' : e < b1 ? lrow[b1 - 1 - e] : rrow[e - b1];
         }
     }
     if (chunk != 0) return;
-    // target bases the left job consumed: its columns other than 'I'
+    // target bases the left job consumed: its columns other than 'I' (with the clip records: counted there)
     uint32_t cnt = 0;
-    for (uint32_t o = tid; o < nl; o += 256) cnt += lrow[o] != (uint8_t) 'I';
+    for (uint32_t o = tid; o < (clip ? 0u : nl); o += 256) cnt += lrow[o] != (uint8_t) 'I';
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) cnt += (uint32_t) __shfl_xor((int) cnt, o);
     if ((tid & 63) == 0) s_cnt[tid >> 6] = cnt;
     __syncthreads();
     if (tid != 0) return;
-    const uint32_t consumed = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    const uint32_t consumed = clip ? rec_l.z : s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
     n_ops[r] = (int32_t) total;
-    score[r] = job_score[2 * r] + (left ? job_score[2 * r + 1] : 0);
+    score[r] = clip ? (int32_t) (rec_l.y + rec_r.y) : job_score[2 * r] + (left ? job_score[2 * r + 1] : 0);
     lrm_anchor an;
-    an.text_pos = a.p; an.read_pos = a.j; an.len = a.len; an.delta = a.delta; an.left_ops = nl; an.flags = a.flags;
+    an.text_pos = a.p; an.read_pos = a.j; an.len = a.len; an.delta = a.delta; an.left_ops = b1;
+    an.flags = a.flags | (cl ? LRM_ANCHOR_SOFT_LEFT : 0u) | (cr ? LRM_ANCHOR_SOFT_RIGHT : 0u);
     anchors[r] = an;
+    if (clip_out) clip_out[r] = lrm_clip{cl, cr};
     if (a.flags & LRM_ANCHOR_ANCHORED) {           // meta moves to the alignment's first text base
         an_store_meta(meta + r, a.p - consumed, a.p - consumed - S, m.seq_id, m.strand);
     } else {
@@ -349,7 +421,7 @@ void lrm_anchor_scratch_free(lrm_workspace *ws) {
     LrmAnchorScratch *s = ws ? ws->an : nullptr;
     if (!s) return;
     void *bufs[] = {s->keys, s->job_reads, s->job_lens, s->job_tlens, s->job_meta, s->job_meta_r, s->job_nops, s->job_score,
-                    s->job_store, s->anchors};
+                    s->job_store, s->anchors, s->clip_recs};
     for (void *b : bufs) if (b) (void) hipFree(b);
     lrm_bs_scratch_free(&s->bs);
     delete s;
@@ -394,6 +466,30 @@ static int anchor_scratch(lrm_workspace *ws, bool planar) {
     return 0;
 }
 
+// the records of the clip step: with the first call that has the step on
+static int anchor_clip_scratch(lrm_workspace *ws) {
+    LrmAnchorScratch *s = ws->an;
+    if (s->clip_recs) return 0;
+    const uint64_t bytes = 2 * s->n_max * sizeof(uint4);
+    if (hipMalloc((void **) &s->clip_recs, bytes) != hipSuccess) {
+        s->clip_recs = nullptr;
+        lrm_set_error("hipMalloc of %llu bytes of end-clipping scratch failed", (unsigned long long) bytes);
+        return -1;
+    }
+    ws->bytes += bytes;
+    return 0;
+}
+
+// P and B of the clip step: 0 selects the default
+static int anchor_clip_params(LrmClipOpt *c) {
+    if (!c->on) return 0;
+    if (c->penalty == 0) c->penalty = LRM_CLIP_PENALTY_DEFAULT;
+    if (c->end_bonus == 0) c->end_bonus = LRM_CLIP_END_BONUS_DEFAULT;
+    if (c->penalty > 15) { lrm_set_error("clip_penalty %u outside [1, 15]", c->penalty); return -1; }
+    if (c->end_bonus > 255) { lrm_set_error("clip_end_bonus %u outside [1, 255]", c->end_bonus); return -1; }
+    return 0;
+}
+
 static int anchor_min_len(uint32_t min_len, uint32_t *out) {
     if (min_len == 0) min_len = LRM_ANCHOR_MIN_DEFAULT;
     if (min_len < 12 || min_len > 64) { lrm_set_error("anchor_min_len %u outside [12, 64]", min_len); return -1; }
@@ -416,11 +512,13 @@ static int launch_scan(const LrmExtendBatch &b, const LrmIndexView &ix, const Lr
 }
 
 int lrm_launch_extend_anchored(lrm_index *idx, lrm_workspace *ws, const LrmExtendBatch &b, lrm_gact_params gp,
-                               lrm_anchor *d_anchor, uint32_t min_len, const LrmMapTune &mt, void *stream_) {
+                               lrm_anchor *d_anchor, uint32_t min_len, const LrmClipOpt &clip_, const LrmMapTune &mt,
+                               void *stream_) {
     hipStream_t stream = (hipStream_t) stream_;
     const uint64_t n = b.n;
     if (n == 0) return 0;
-    if (lrm_gact_resolve_params(&gp) || anchor_min_len(min_len, &min_len)) return -1;
+    LrmClipOpt clip = clip_;
+    if (lrm_gact_resolve_params(&gp) || anchor_min_len(min_len, &min_len) || anchor_clip_params(&clip)) return -1;
     if (b.store_stride < lrm_anchored_store_stride(b.max_len)) {
         lrm_set_error("anchored extension: store_stride %llu < 2*max_len + max_len/8 + 2 = %llu",
                       (unsigned long long) b.store_stride, (unsigned long long) lrm_anchored_store_stride(b.max_len));
@@ -433,7 +531,7 @@ int lrm_launch_extend_anchored(lrm_index *idx, lrm_workspace *ws, const LrmExten
         return -1;
     }
     const bool planar = idx->d_cpl && idx->cpl_ok && ws->bs.qpl;
-    if (anchor_scratch(ws, planar)) return -1;
+    if (anchor_scratch(ws, planar) || (clip.on && anchor_clip_scratch(ws))) return -1;
     LrmAnchorScratch &s = *ws->an;
     const LrmGactJobs jobs = {s.job_reads, s.job_stride, s.job_lens, s.job_tlens, s.job_meta, s.job_meta_r, idx->view.content,
                               idx->d_cpl, 2 * n, s.job_store, s.job_store_stride, s.job_nops, s.job_score};
@@ -467,6 +565,16 @@ int lrm_launch_extend_anchored(lrm_index *idx, lrm_workspace *ws, const LrmExten
     if (lrm_gact_launch_jobs(jobs, gp, plan, &s.bs, ws->d_counters, mt.bs_waves, stream)) return -1;
     lrm_time_end(ws, stream);
 
+    // clip: one wavefront per job
+    if (clip.on) {
+        if (lrm_grid_1d((2 * n + 3) / 4, "anchor clip", &grid)) return -1;
+        lrm_time_begin(ws, plan.slot, stream);
+        hipLaunchKernelGGL(anchor_clip_kernel, dim3(grid), dim3(256), 0, stream, 2 * n, s.job_meta_r,
+                           (const unsigned long long *) s.keys, s.job_store, s.job_store_stride, s.job_nops, clip.penalty,
+                           clip.end_bonus, s.clip_recs);
+        lrm_time_end(ws, stream);
+    }
+
     // stitch
     const uint64_t ops_max = lrm_anchored_store_stride(b.max_len);
     const uint32_t chunks_op = (uint32_t) ((ops_max + AN_CHUNK - 1) / AN_CHUNK);
@@ -474,7 +582,8 @@ int lrm_launch_extend_anchored(lrm_index *idx, lrm_workspace *ws, const LrmExten
     lrm_time_begin(ws, plan.slot, stream);
     hipLaunchKernelGGL(anchor_stitch_kernel, dim3(grid), dim3(256), 0, stream, b.lens, b.meta, b.meta_r, n, idx->view.mta,
                        (const unsigned long long *) s.keys, chunks_op, s.job_store, s.job_store_stride, s.job_nops,
-                       s.job_score, b.store, b.store_stride, b.n_ops, b.score, d_anchor ? d_anchor : s.anchors);
+                       s.job_score, b.store, b.store_stride, b.n_ops, b.score, d_anchor ? d_anchor : s.anchors,
+                       clip.on ? s.clip_recs : nullptr, clip.on ? clip.d_clip : nullptr);
     lrm_time_end(ws, stream);
     HIPCHK(hipGetLastError());
     return 0;

@@ -738,7 +738,8 @@ int lrm_launch_extend(lrm_index *idx, lrm_workspace *ws, const LrmExtendBatch &b
     hipStream_t stream = (hipStream_t) stream_;
     if (b.n == 0) return 0;
     if (mt.anchored)                                       // anchor_kernels.hip; nothing below is reached
-        return lrm_launch_extend_anchored(idx, ws, b, gp, nullptr, mt.anchor_min_len, mt, stream_);
+        return lrm_launch_extend_anchored(idx, ws, b, gp, nullptr, mt.anchor_min_len, lrm_clip_of(mt), mt, stream_);
+    if (mt.clip) { lrm_set_error("lrm_map_options.clip needs lrm_map_options.anchored"); return -1; }
     if (lrm_gact_resolve_params(&gp)) return -1;
     if (b.store_stride < 2ull * b.max_len) {
         lrm_set_error("store_stride %llu < 2*max_len %u", (unsigned long long) b.store_stride, b.max_len);

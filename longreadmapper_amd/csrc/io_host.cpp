@@ -699,12 +699,14 @@ extern "C" int lrm_accaln(const char *genome, const char *reads_path, const char
     return lrm_accaln_opt(genome, reads_path, sam_path, p, gp, device, rg_id, total_out, valid_out, nullptr);
 }
 
-// user: only the fields that change WHAT is computed are taken (anchored, anchor_min_len); the shape of the pipeline is this
-// function's own choice
+// user: only the fields that change WHAT is computed are taken (anchored, anchor_min_len, clip, clip_penalty, clip_end_bonus);
+// the shape of the pipeline is this function's own choice
 extern "C" int lrm_accaln_opt(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
                               lrm_gact_params gp, int device, long rg_id, uint64_t *total_out, uint64_t *valid_out,
                               const lrm_map_options *user) {
     const bool anchored = user && user->struct_size >= offsetof(lrm_map_options, anchor_min_len) + sizeof(uint32_t) && user->anchored;
+    // (a caller built before the clip fields existed has them inside its zeroed reserved words or not at all)
+    const bool clip = user && user->struct_size >= offsetof(lrm_map_options, clip_end_bonus) + sizeof(uint32_t) && user->clip;
     // op bytes per read: alnmain.c:316-320, a multiple of 16; the anchored mode's targets are an eighth longer than the reads
     auto store_stride_of = [anchored](uint64_t max_len) {
         const uint64_t s = ((anchored ? 2 * max_len + max_len / 8 + 2 : 2 * max_len) + 15) & ~15ull;
@@ -755,6 +757,7 @@ extern "C" int lrm_accaln_opt(const char *genome, const char *reads_path, const 
         mopt.copy_threads = 2;                      // the parser and the formatter need the cores
         mopt.keep_reads = 1;                        // reverse-strand reads are reverse-complemented by the formatter as it copies them
         if (anchored) { mopt.anchored = 1; mopt.anchor_min_len = user->anchor_min_len; }
+        if (clip) { mopt.clip = 1; mopt.clip_penalty = user->clip_penalty; mopt.clip_end_bonus = user->clip_end_bonus; }
         // Pinning the batch buffers (0.2 s per GB to pin and to release, and the device stalls while the runtime pins)
         // pays from a few tens of Gbp on: reads files below 16 GiB run through pageable buffers.
         bool want_pinned = false;

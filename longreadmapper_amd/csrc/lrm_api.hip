@@ -145,6 +145,7 @@ void lrm_resolve_map_tune(const lrm_map_options *opt, const LrmEnv &env, LrmMapT
     t->keep_reads = o.keep_reads != 0;
     t->anchored = o.anchored != 0;
     t->anchor_min_len = o.anchor_min_len;
+    t->clip = o.clip != 0; t->clip_penalty = o.clip_penalty; t->clip_end_bonus = o.clip_end_bonus;
     // measured defaults of the kernel knobs (tools/seed_probe.py sweeps them through the environment)
     t->ss_items = 2048; t->vote_vg = 16; t->vote_t1 = LRM_VOTE_T1_LIMIT; t->vote_u = 2; t->vote_load = 50; t->vote_fast = o.vote_exact_only ? 0 : 1;
     t->ext_streams = 2; t->seed_streams = 2;
@@ -1031,7 +1032,18 @@ extern "C" int lrm_extend_batch_anchored_dev(lrm_index *idx, lrm_workspace *ws, 
                                              uint32_t min_len, void *stream) {
     const LrmExtendBatch b = {d_reads, stride, d_lens, n, max_len, d_best, d_store, store_stride, d_n_ops, d_score, d_meta, d_meta_r};
     if (int rc = extend_dev_ready(idx, ws, b)) return rc;
-    return lrm_launch_extend_anchored(idx, ws, b, gp, d_anchor, min_len, idx->mtune, stream);
+    return lrm_launch_extend_anchored(idx, ws, b, gp, d_anchor, min_len, LrmClipOpt{}, idx->mtune, stream);
+}
+extern "C" int lrm_extend_batch_clipped_dev(lrm_index *idx, lrm_workspace *ws, char *d_reads, uint64_t stride,
+                                            const uint32_t *d_lens, uint64_t n, uint32_t max_len, const lrm_entry *d_best,
+                                            lrm_gact_params gp, uint8_t *d_store, uint64_t store_stride, int32_t *d_n_ops,
+                                            int32_t *d_score, lrm_seq_meta *d_meta, int32_t *d_meta_r, lrm_anchor *d_anchor,
+                                            uint32_t min_len, uint32_t clip_penalty, uint32_t clip_end_bonus, lrm_clip *d_clip,
+                                            void *stream) {
+    const LrmExtendBatch b = {d_reads, stride, d_lens, n, max_len, d_best, d_store, store_stride, d_n_ops, d_score, d_meta, d_meta_r};
+    if (int rc = extend_dev_ready(idx, ws, b)) return rc;
+    return lrm_launch_extend_anchored(idx, ws, b, gp, d_anchor, min_len, LrmClipOpt{1, clip_penalty, clip_end_bonus, d_clip},
+                                      idx->mtune, stream);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -937,6 +937,7 @@ int submit_impl(lrm_index *idx, const MapJob &j, const lrm_map_options *opt, lrm
     const uint32_t max_len = max_of(j.lens, j.n);
     if (j.stride < max_len) { lrm_set_error("stride < longest read"); return -1; }
     if ((j.mode & DO_EXTEND) && j.store_stride < 2ull * max_len) { lrm_set_error("store_stride < 2 * longest read (alnmain.c:316-320)"); return -1; }
+    if ((j.mode & DO_EXTEND) && mt.clip && !mt.anchored) { lrm_set_error("lrm_map_options.clip needs lrm_map_options.anchored"); return -1; }
     if ((j.mode & DO_EXTEND) && mt.anchored && j.store_stride < lrm_anchored_store_stride(max_len)) {
         lrm_set_error("anchored extension: store_stride %llu < 2 * longest read + longest read / 8 + 2 = %llu",
                       (unsigned long long) j.store_stride, (unsigned long long) lrm_anchored_store_stride(max_len));

@@ -115,6 +115,7 @@ struct LrmIndexTune {
 struct LrmMapTune {
     int dense, gact_impl, seed_rounds, cigar_text, keep_reads, anchored;
     uint32_t anchor_min_len;        // 0: LRM_ANCHOR_MIN_DEFAULT
+    uint32_t clip, clip_penalty, clip_end_bonus;     // end clipping of the anchored mode; 0: LRM_CLIP_*_DEFAULT
     uint32_t slice_reads, sub_batches, group_subs, bs_waves, copy_threads;
     uint32_t ss_items, ss_lds_pad, vote_vg, vote_t1, vote_u, vote_load, vote_fast;      // kernel tuning (environment only; measured defaults)
     uint32_t t3_limit, t3_slots;                                 // lrm_debug_set_vote_limits (tests)
@@ -313,8 +314,13 @@ int lrm_launch_extend(lrm_index *idx, lrm_workspace *ws, const LrmExtendBatch &b
 #define LRM_ANCHOR_MIN_DEFAULT 20
 int lrm_gact_resolve_params(lrm_gact_params *gp);
 int lrm_launch_locus_revcomp(lrm_index *idx, lrm_workspace *ws, const LrmExtendBatch &b, void *stream);
+#define LRM_CLIP_PENALTY_DEFAULT 2
+#define LRM_CLIP_END_BONUS_DEFAULT 6
+// end clipping (docs/GACT_SPEC.md, "End clipping"): on = 0 is the mode as it is without the step
+struct LrmClipOpt { uint32_t on, penalty, end_bonus; lrm_clip *d_clip; };
+static inline LrmClipOpt lrm_clip_of(const LrmMapTune &mt) { return LrmClipOpt{mt.clip, mt.clip_penalty, mt.clip_end_bonus, nullptr}; }
 int lrm_launch_extend_anchored(lrm_index *idx, lrm_workspace *ws, const LrmExtendBatch &b, lrm_gact_params gp,
-                               lrm_anchor *d_anchor, uint32_t min_len, const LrmMapTune &mt, void *stream);
+                               lrm_anchor *d_anchor, uint32_t min_len, const LrmClipOpt &clip, const LrmMapTune &mt, void *stream);
 void lrm_anchor_scratch_free(lrm_workspace *ws);
 static inline uint64_t lrm_anchored_store_stride(uint32_t max_len) { return 2ull * max_len + max_len / 8 + 2; }
 int lrm_launch_debug_seed(lrm_index *idx, const char *d_read, uint32_t len, uint32_t seed_len,

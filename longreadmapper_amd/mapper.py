@@ -21,6 +21,7 @@ N_KERNELS = 9              # LRM_N_KERNELS in include/lrm_accel.h
 ANCHOR_DT = np.dtype([("text_pos", "<u8"), ("read_pos", "<u4"), ("len", "<u4"), ("delta", "<i4"), ("left_ops", "<u4"),
                       ("flags", "<u4"), ("_pad", "V4")])      # lrm_anchor
 assert ANCHOR_DT.itemsize == 32
+CLIP_DT = np.dtype([("left", "<u4"), ("right", "<u4")])          # lrm_clip
 
 
 def anchored_store_stride(max_len):
@@ -28,10 +29,16 @@ def anchored_store_stride(max_len):
     return 2 * max_len + max_len // 8 + 2
 
 
-def _anchor_options(options, anchored, anchor_min_len):
-    if not anchored:
+def _anchor_options(options, anchored, anchor_min_len, clip=False, clip_penalty=0, clip_end_bonus=0):
+    """clip (docs/GACT_SPEC.md, "End clipping": each job of an anchored read keeps its best-scoring prefix, '=' +1, any
+    other column -clip_penalty (0 = 2), when that gains more than clip_end_bonus (0 = 6); the rest becomes 'S') implies
+    anchored."""
+    if not anchored and not clip:
         return options
-    return {**(options or {}), "anchored": 1, "anchor_min_len": anchor_min_len}
+    extra = {"anchored": 1, "anchor_min_len": anchor_min_len}
+    if clip:
+        extra.update(clip=1, clip_penalty=clip_penalty, clip_end_bonus=clip_end_bonus)
+    return {**(options or {}), **extra}
 
 
 def debug_anchor(index, read, loc, min_len=0):
@@ -54,13 +61,17 @@ def seed_batch(index, reads, lens, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRE
     return best
 
 
-def extend_batch(index, reads, lens, best, gact=DEFAULT_GACT, anchored=False, anchor_min_len=0):
+def extend_batch(index, reads, lens, best, gact=DEFAULT_GACT, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0,
+                 clip_end_bonus=0):
     """Host buffers; `reads` is modified in place (reverse-strand reads are rev-comped).
     anchored: the anchored extension mode (lrm_map_options.anchored) for this call, on top of the handle's options.
+    clip: its end clipping (lrm_map_options.clip; implies anchored): the read ends that do not align come out as 'S'
+    columns; clip_penalty / clip_end_bonus: P and B of the rule, 0 = the defaults 2 and 6.
 
     Returns dict(ops=(n, store_stride) uint8, n_ops, score, meta, meta_r)."""
-    if anchored:
-        with index.map_options_plus(anchored=1, anchor_min_len=anchor_min_len):
+    extra = _anchor_options(None, anchored, anchor_min_len, clip, clip_penalty, clip_end_bonus)
+    if extra:
+        with index.map_options_plus(**extra):
             return _extend_batch(index, reads, lens, best, gact, True)
     return _extend_batch(index, reads, lens, best, gact, False)
 
@@ -146,13 +157,14 @@ def ops_of(res, i):
 
 
 def map_batch_submit(index, reads, lens, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT, store=None,
-                     options=None, anchored=False, anchor_min_len=0):
+                     options=None, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0):
     """lrm_map_batch_submit: queues the batch and returns a PendingBatch.  `reads` is modified in place like
     extend_batch once the batch runs; `store` may be a caller-provided (n, >= 2*max_len) uint8 array (e.g. pinned;
     anchored: >= anchored_store_stride(max_len)); `options`: dict of lrm_map_options fields (None: the handle's
-    defaults); anchored=True adds the anchored extension mode to them."""
+    defaults); anchored=True adds the anchored extension mode to them, clip=True that mode with its end clipping
+    (see extend_batch)."""
     assert reads.dtype == np.uint8 and reads.flags.c_contiguous and reads.flags.writeable
-    options = _anchor_options(options, anchored, anchor_min_len)
+    options = _anchor_options(options, anchored, anchor_min_len, clip, clip_penalty, clip_end_bonus)
     anchored = bool(options and options.get("anchored"))
     lens = np.ascontiguousarray(lens, dtype=np.uint32)
     n, stride = reads.shape
@@ -179,11 +191,11 @@ def map_batch_submit(index, reads, lens, seed_len=DEFAULT_SEED_LEN, thres=DEFAUL
 
 
 def map_batch(index, reads, lens, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT, store=None,
-              options=None, anchored=False, anchor_min_len=0):
+              options=None, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0):
     """PART 1 + PART 2 in one device pass; `reads` is modified in place like extend_batch.
-    Without `options` this is lrm_map_batch (the handle's default options), with them (or with anchored=True, which
-    is one of them) submit + wait."""
-    options = _anchor_options(options, anchored, anchor_min_len)
+    Without `options` this is lrm_map_batch (the handle's default options), with them (or with anchored=True or
+    clip=True, which are among them) submit + wait."""
+    options = _anchor_options(options, anchored, anchor_min_len, clip, clip_penalty, clip_end_bonus)
     if options is not None:
         return map_batch_submit(index, reads, lens, seed_len, thres, gact, store, options).wait()
     assert reads.dtype == np.uint8 and reads.flags.c_contiguous and reads.flags.writeable
@@ -224,7 +236,7 @@ class DeviceMapper:
     current stream (so torch.cuda.Event brackets them)."""
 
     def __init__(self, index, n_max, max_len, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT,
-                 device=0, anchored=False, anchor_min_len=0):
+                 device=0, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0):
         import torch
         self.torch = torch
         self.index = index
@@ -235,8 +247,11 @@ class DeviceMapper:
         check(lib.lrm_workspace_create(C.byref(ws), index.handle, n_max, max_len, seed_len, thres),
               "lrm_workspace_create")
         self.ws = ws
-        self.anchored, self.anchor_min_len = bool(anchored), anchor_min_len
-        # anchored: lrm_extend_batch_anchored_dev, results() also returns the lrm_anchor records
+        anchored = bool(anchored or clip)
+        self.anchored, self.anchor_min_len = anchored, anchor_min_len
+        self.clip_on, self.clip_penalty, self.clip_end_bonus = bool(clip), clip_penalty, clip_end_bonus
+        # anchored: lrm_extend_batch_anchored_dev, results() also returns the lrm_anchor records; clip (implies anchored):
+        # lrm_extend_batch_clipped_dev, results() also returns the lrm_clip records (soft-clipped bases per read)
         self.store_stride = (anchored_store_stride(max_len) + 15) // 16 * 16 if anchored else 2 * max_len
         self.best = torch.zeros((n_max, 3), dtype=torch.int64, device=self.dev)       # lrm_entry
         self.store = torch.zeros((n_max, self.store_stride), dtype=torch.uint8, device=self.dev)
@@ -245,6 +260,7 @@ class DeviceMapper:
         self.meta = torch.zeros((n_max, 24), dtype=torch.uint8, device=self.dev)      # lrm_seq_meta
         self.meta_r = torch.zeros(n_max, dtype=torch.int32, device=self.dev)
         self.anchor = torch.zeros((n_max, 32), dtype=torch.uint8, device=self.dev) if anchored else None     # lrm_anchor
+        self.clip = torch.zeros((n_max, 2), dtype=torch.int32, device=self.dev) if clip else None           # lrm_clip
 
     def workspace_bytes(self):
         return int(lib.lrm_workspace_bytes(self.ws))
@@ -262,6 +278,15 @@ class DeviceMapper:
     def extend(self, d_reads, d_lens, n=None):
         n = d_reads.shape[0] if n is None else n
         gp = capi.GactParams(*self.gact)
+        if self.clip_on:
+            check(lib.lrm_extend_batch_clipped_dev(self.index.handle, self.ws, d_reads.data_ptr(), d_reads.stride(0),
+                                                   d_lens.data_ptr(), n, self.max_len, self.best.data_ptr(), gp,
+                                                   self.store.data_ptr(), self.store_stride, self.n_ops.data_ptr(),
+                                                   self.score.data_ptr(), self.meta.data_ptr(), self.meta_r.data_ptr(),
+                                                   self.anchor.data_ptr(), self.anchor_min_len, self.clip_penalty,
+                                                   self.clip_end_bonus, self.clip.data_ptr(), self._stream()),
+                  "lrm_extend_batch_clipped_dev")
+            return
         if self.anchored:
             check(lib.lrm_extend_batch_anchored_dev(self.index.handle, self.ws, d_reads.data_ptr(), d_reads.stride(0),
                                                     d_lens.data_ptr(), n, self.max_len, self.best.data_ptr(), gp,
@@ -309,6 +334,8 @@ class DeviceMapper:
                    score=self.score[:n].cpu().numpy(), meta=meta, meta_r=self.meta_r[:n].cpu().numpy())
         if self.anchored:
             res["anchor"] = self.anchor[:n].cpu().numpy().reshape(-1).view(ANCHOR_DT)
+        if self.clip_on:
+            res["clip"] = self.clip[:n].cpu().numpy().reshape(-1).view(CLIP_DT)
         return res
 
     def close(self):

@@ -1,6 +1,7 @@
 """Probe (run on the GPU box): what the anchored extension mode costs.  The bench workload (ONT reads on an E. coli-sized
-text) and a PacBio-CLR workload, HBM-resident through DeviceMapper with launch timing: classic vs anchored, a warm-up and
-three timed repeats each, ms per kernel slot (mean, and the spread of the per-repeat totals), and the median ED / len.
+text) and a PacBio-CLR workload, HBM-resident through DeviceMapper with launch timing: classic vs anchored vs anchored with
+end clipping (its kernel is recorded in the extension kernel's slot, next to the stitch), a warm-up and three timed
+repeats each, ms per kernel slot (mean, and the spread of the per-repeat totals), and the median ED / len.
     python tools/anchored_probe.py          PROBE_READS / PROBE_LEN / PROBE_REF scale it down"""
 import os
 import sys
@@ -22,8 +23,8 @@ for name, profile, length, count in (("bench workload (ONT 10 kbp)", synth.ONT, 
     r = synth.reads([ref], count, length, profile, seed=11)
     d_lens = torch.from_numpy(r["lens"].astype(np.int32)).cuda()
     print("%s: %d reads, %.2f Gbp" % (name, count, float(r["lens"].sum()) / 1e9), flush=True)
-    for anchored in (False, True):
-        dm = mapper.DeviceMapper(di, count, length, anchored=anchored)
+    for label, anchored, clip in (("classic", False, False), ("anchored", True, False), ("anch+clip", True, True)):
+        dm = mapper.DeviceMapper(di, count, length, anchored=anchored, clip=clip)
         per_slot, totals = {}, []
         for rep in range(REPEATS + 1):                      # the first one warms up (and allocates the mode's scratch)
             d_reads = torch.from_numpy(r["reads"]).cuda()   # the extension reverse-complements in place: a fresh copy
@@ -40,8 +41,8 @@ for name, profile, length, count in (("bench workload (ONT 10 kbp)", synth.ONT, 
                         per_slot[k] = per_slot.get(k, 0.0) + ms / REPEATS
         res = dm.results(count)
         ok = res["score"] >= 0
-        print("  %-8s extension %.2f ms (min %.2f, max %.2f)  median ED/len %.4f  workspace %.2f GiB" %
-              ("anchored" if anchored else "classic", np.mean(totals), min(totals), max(totals),
+        print("  %-9s extension %.2f ms (min %.2f, max %.2f)  median ED/len %.4f  workspace %.2f GiB" %
+              (label, np.mean(totals), min(totals), max(totals),
                float(np.median(res["score"][ok] / r["lens"][ok])), dm.workspace_bytes() / 2.0**30))
         print("           " + "  ".join("%s %.2f" % (k.replace("_kernel", ""), v) for k, v in per_slot.items()), flush=True)
         dm.close()
