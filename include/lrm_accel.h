@@ -178,7 +178,11 @@ typedef struct lrm_map_options {
                                   0: both jobs are global in the read */
     uint32_t clip_penalty;     /* P: 0 = 2, else 1..15 */
     uint32_t clip_end_bonus;   /* B: 0 = 6, else 1..255 */
-    uint32_t reserved[2];
+    uint32_t split;            /* 1 (needs clip): SPLIT READS (docs/GACT_SPEC.md, "Split reads"): a soft-clipped end of at least
+                                  split_min_len bases is mapped as a read of its own -- lrm_split_batch / lrm_split_batch_dev are the
+                                  second pass, lrm_accaln_opt prints its results as supplementary records with SA:Z.  The batch
+                                  calls themselves ignore the field: with it or without it they return the same bytes */
+    uint32_t split_min_len;    /* M: 0 = 200, else 50..2^20 */
 } lrm_map_options;
 void lrm_map_options_init(lrm_map_options *o);
 
@@ -396,6 +400,82 @@ int lrm_extend_batch_clipped_dev(lrm_index *idx, lrm_workspace *ws, char *d_read
                                  lrm_seq_meta *d_meta, int32_t *d_meta_r, lrm_anchor *d_anchor, uint32_t min_len,
                                  uint32_t clip_penalty, uint32_t clip_end_bonus, lrm_clip *d_clip, void *stream);
 
+/* SPLIT READS (lrm_map_options.split; docs/GACT_SPEC.md, "Split reads"): the soft-clipped ends of a batch that went through
+ * the anchored extension with end clipping, mapped as reads of their own.  For read i with n = lens[i] bases, R the read as
+ * the extension left it and (cl, cr) its lrm_clip: the left segment R[0 .. cl) if cl >= M, then the right segment
+ * R[n - cr .. n) if cr >= M; reads ascending, left before right, M = split_min_len (0 = 200, else 50..2^20). */
+#define LRM_SPLIT_MIN_DEFAULT 200
+#define LRM_SEG_RIGHT 1u               /* lrm_segment.flags: the segment is the read's right end */
+#define LRM_SEG_ALIGNED 2u             /*   REPORTED: it has a locus (meta_r != 0) and was extended from an anchor of its own */
+typedef struct lrm_segment { uint32_t read, start, len, flags; } lrm_segment;   /* start: in R's coordinates */
+
+/* The segment table from clip counts: pure host arithmetic, usable without a GPU.  seg_out holds up to cap records (may be
+ * NULL when cap == 0); *n_seg is the number of segments in any case.  0 ok, -3 more than cap segments (nothing written),
+ * -1 bad argument (split_min_len outside its range). */
+int lrm_split_plan(const uint32_t *lens, const lrm_clip *clip, uint64_t n, uint32_t split_min_len, lrm_segment *seg_out,
+                   uint64_t cap, uint64_t *n_seg);
+/* The 'S' run at either end of one alignment: of its op bytes (is_text == 0) or of its run-length text (is_text != 0:
+ * cig->cigar is NUL-terminated, lrm_map_options.cigar_text).  The host-buffer batch calls return no lrm_clip records;
+ * this recovers them.  No alignment (n_cigar_op <= 0, "*"): 0, 0. */
+int lrm_clip_of_cigar(const lrm_cigar *cig, int is_text, uint32_t *left, uint32_t *right);
+
+/* Device buffers of the second pass, owned by the caller, for up to cap segments: the segment table, the segment batch
+ * (row s at rows + s*row_stride, 16-byte aligned, row_stride a multiple of 16 and > the longest segment) and, per segment,
+ * everything lrm_seed_batch_dev + lrm_extend_batch_clipped_dev return for a batch made of those rows (store_stride >=
+ * 2*L + L/8 + 2 for the longest segment L, a multiple of 4; checked). */
+typedef struct lrm_split_dev {
+    uint64_t cap;
+    lrm_segment *seg;
+    char *rows; uint64_t row_stride;
+    uint32_t *lens;
+    lrm_entry *best;
+    uint8_t *store; uint64_t store_stride;
+    int32_t *n_ops, *score;
+    lrm_seq_meta *meta; int32_t *meta_r;
+    lrm_anchor *anchor;
+    lrm_clip *clip;
+} lrm_split_dev;
+/* Call after lrm_extend_batch_clipped_dev on the same stream: d_reads, d_lens, d_clip are that call's.  p, gp, anchor_min_len,
+ * clip_penalty, clip_end_bonus: as the primary pass had them.  The stage marks and counts the segments on the device, and
+ * THE COUNT CROSSES TO THE HOST (8 bytes into pinned memory; the call sleeps on an event until they are there): this is the
+ * one place a *_dev call waits for the device, everything before it on the stream included.  Then it gathers the segment
+ * rows and runs the seed stage and the clipped anchored extension over them on ws_seg, in chunks of ws_seg's n_max rows
+ * when there are more segments than that; these launches are asynchronous like those of the other *_dev calls.
+ * *n_seg = the number of segments.  More than out->cap: -3, *n_seg says how many, no result array is written.
+ * ws_seg: a workspace from lrm_workspace_create for (rows per chunk, longest segment, p.seed_len, p.thres).  The workspace
+ * of the primary pass MAY be passed: its scratch is idle once the primary's extension has been issued on the same stream,
+ * it holds reads at least as long as any segment, and a batch with more segments than its n_max goes through it in chunks
+ * (its counters and its timing record then describe the two passes together). */
+int lrm_split_batch_dev(lrm_index *idx, lrm_workspace *ws_seg, const char *d_reads, uint64_t stride, const uint32_t *d_lens,
+                        uint64_t n, const lrm_clip *d_clip, lrm_params p, lrm_gact_params gp, uint32_t anchor_min_len,
+                        uint32_t clip_penalty, uint32_t clip_end_bonus, uint32_t split_min_len, const lrm_split_dev *out,
+                        uint64_t *n_seg, void *stream);
+
+/* The second pass with HOST buffers, over a batch the caller has just got back from lrm_map_batch / lrm_map_batch_wait with
+ * lrm_map_options.clip: reads_buf, lens, cig, meta, meta_r as returned.  It takes the clip counts from cig (rows, dense or
+ * cigar_text layout, as opt says), plans the segments, gathers their bases on the host (with opt->keep_reads the caller's
+ * copy of a reverse-strand read was not reverse-complemented: meta_r != 0 && strand == 1 -- the gather does it) and sends
+ * that batch through lrm_map_batch_submit / _wait with opt (split and keep_reads themselves ignored: the segment rows come
+ * back as the extension left them).  Only the clipped bases cross the link a second time.  Same segment table and same
+ * per-segment bytes as lrm_split_batch_dev; group handles work.  out->cig[s] is in opt's layout inside out->store.
+ * opt == NULL: the handle's default options.  -3: more than out->cap segments (out->n_seg says how many). */
+typedef struct lrm_split_out {
+    uint64_t cap, n_seg;               /* n_seg: set by the call */
+    lrm_segment *seg;
+    char *rows; uint64_t row_stride;   /* may be pinned (lrm_host_alloc); row_stride a multiple of 16 and > the longest segment */
+    uint32_t *lens;
+    lrm_entry *best;
+    lrm_cigar *cig;
+    uint8_t *store; uint64_t store_stride;
+    int *score;
+    lrm_seq_meta *meta; int *meta_r;
+    lrm_anchor *anchor;
+    lrm_clip *clip;
+} lrm_split_out;
+int lrm_split_batch(lrm_index *idx, const char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
+                    const lrm_cigar *cig, const lrm_seq_meta *meta, const int *meta_r, lrm_params p, lrm_gact_params gp,
+                    const lrm_map_options *opt, lrm_split_out *out);
+
 /* Counters of the last *_dev call on this workspace (device->host copy, syncs
  * the stream): vote items per table tier, reads decided in
  * phase 0, GACT tiles.  For tests / bench bookkeeping only. */
@@ -418,7 +498,8 @@ int lrm_workspace_stats(lrm_workspace *ws, lrm_stats *out, void *stream);
  * Kernel order: pack2bit, seed_search, vote, decide, locus_resolve, revcomp, gact (byte kernels),
  * bs_pack_reads, gact_bs (bit-sliced kernel + expansion).  The anchored mode adds its anchor scan to the
  * locus_resolve slot, its job builder to the revcomp slot, its end clipping and its stitch to the slot of the extension
- * kernel.
+ * kernel.  The split stage (lrm_split_batch_dev) books its own kernels -- split_count / split_scan / split_mark,
+ * split_gather, split_flag -- into the revcomp slot of ws_seg, next to the seed and extension kernels of the segment batch.
  * lrm_workspace_timing synchronises the stream, ADDS the elapsed milliseconds and launch counts
  * of everything recorded since the last call into ms[LRM_N_KERNELS] / launches[LRM_N_KERNELS], and
  * resets the record. */

@@ -61,6 +61,16 @@ char *lrm_sam_header(const lrm_mta_entry *mta, int mta_len, long rg_id, uint64_t
 char *lrm_sam_format(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len,
                      const lrm_cigar *cig, const int *score, const lrm_seq_meta *meta,
                      const int *meta_r, uint64_t n, uint64_t *len_out);
+/* The same with SPLIT READS (docs/GACT_SPEC.md, "Split reads"): `split` is what lrm_split_batch returned for this batch
+ * (NULL or no segment: exactly the lines of lrm_sam_format).  Right behind a read's primary line comes one supplementary line
+ * (FLAG 2048, + 16 when its strand relative to the read as sequenced is reverse) per REPORTED segment: SEQ the segment row,
+ * QUAL the matching slice of the read's qualities, CIGAR <hl>H + the segment's own run-length CIGAR + <hr>H.  The primary and
+ * its supplementary lines name each other in SA:Z (rname,pos,strand,<c5>S<q>M<d>D|I<c3>S,255,ED;).
+ * cigar_is_text: cig[i].cigar and split->cig[s].cigar are run-length text (lrm_map_options.cigar_text), not op bytes;
+ * revcomp_here: the batch ran with keep_reads -- reverse-strand reads are reverse-complemented while they are printed. */
+char *lrm_sam_format_split(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig,
+                           const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t n, int cigar_is_text,
+                           int revcomp_here, const lrm_split_out *split, uint64_t *len_out);
 void lrm_free(void *p);
 
 /* `accaln genome reads [batch seed_len thres]` on the GPU path: loads the index files next to
@@ -69,7 +79,9 @@ void lrm_free(void *p);
 int lrm_accaln(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
                lrm_gact_params gp, int device, long rg_id, uint64_t *total, uint64_t *valid);
 /* ... with options (NULL: lrm_accaln).  Taken from opt: anchored, anchor_min_len -- SAM POS is then the alignment's first
- * text base (meta.off + 1 of the moved meta); the other fields are this flow's own choice. */
+ * text base (meta.off + 1 of the moved meta) --, clip and its two parameters, split and split_min_len (needs clip: after a
+ * batch's wait its clipped ends go through lrm_split_batch and come out as supplementary records, lrm_sam_format_split;
+ * total / valid keep counting reads); the other fields are this flow's own choice. */
 int lrm_accaln_opt(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
                    lrm_gact_params gp, int device, long rg_id, uint64_t *total, uint64_t *valid,
                    const lrm_map_options *opt);

@@ -73,13 +73,23 @@ class IndexTables(C.Structure):        # lrm_index_tables
                 ("seed_table_side_entries", C.c_uint64), ("derived_bytes", C.c_uint64), ("reserved", C.c_uint64 * 4)]
 
 
+class _SplitWords(C.Structure):        # the last two words of lrm_map_options
+    _fields_ = [("split", C.c_uint32), ("split_min_len", C.c_uint32)]
+
+
+class _MapTail(C.Union):               # ... which were `reserved` until the split fields took them: both names reach them
+    _anonymous_ = ("_split",)
+    _fields_ = [("_split", _SplitWords), ("reserved", C.c_uint32 * 2)]
+
+
 class MapOptions(C.Structure):         # lrm_map_options
+    _anonymous_ = ("_tail",)
     _fields_ = [("struct_size", C.c_uint32), ("dense_results", C.c_int32), ("gact_impl", C.c_int32),
                 ("seed_rounds", C.c_int32), ("vote_exact_only", C.c_int32), ("slice_reads", C.c_uint32),
                 ("sub_batches", C.c_uint32), ("group_subs", C.c_uint32), ("bs_waves", C.c_uint32),
                 ("cigar_text", C.c_uint32), ("copy_threads", C.c_uint32), ("keep_reads", C.c_uint32), ("anchored", C.c_uint32),
                 ("anchor_min_len", C.c_uint32), ("clip", C.c_uint32), ("clip_penalty", C.c_uint32),
-                ("clip_end_bonus", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+                ("clip_end_bonus", C.c_uint32), ("_tail", _MapTail)]
 
 
 class Anchor(C.Structure):             # lrm_anchor
@@ -93,6 +103,25 @@ class Clip(C.Structure):               # lrm_clip
     _fields_ = [("left", C.c_uint32), ("right", C.c_uint32)]
 
 
+class Segment(C.Structure):            # lrm_segment
+    _fields_ = [("read", C.c_uint32), ("start", C.c_uint32), ("len", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class SplitDev(C.Structure):           # lrm_split_dev (device pointers)
+    _fields_ = [("cap", C.c_uint64), ("seg", C.c_void_p), ("rows", C.c_void_p), ("row_stride", C.c_uint64), ("lens", C.c_void_p),
+                ("best", C.c_void_p), ("store", C.c_void_p), ("store_stride", C.c_uint64), ("n_ops", C.c_void_p),
+                ("score", C.c_void_p), ("meta", C.c_void_p), ("meta_r", C.c_void_p), ("anchor", C.c_void_p), ("clip", C.c_void_p)]
+
+
+class SplitOut(C.Structure):           # lrm_split_out (host pointers)
+    _fields_ = [("cap", C.c_uint64), ("n_seg", C.c_uint64), ("seg", C.c_void_p), ("rows", C.c_void_p), ("row_stride", C.c_uint64),
+                ("lens", C.c_void_p), ("best", C.c_void_p), ("cig", C.c_void_p), ("store", C.c_void_p),
+                ("store_stride", C.c_uint64), ("score", C.c_void_p), ("meta", C.c_void_p), ("meta_r", C.c_void_p),
+                ("anchor", C.c_void_p), ("clip", C.c_void_p)]
+
+
+SEG_RIGHT, SEG_ALIGNED = 1, 2          # lrm_segment.flags
+SPLIT_MIN_DEFAULT = 200                # LRM_SPLIT_MIN_DEFAULT
 ANCHOR_ANCHORED, ANCHOR_FALLBACK, ANCHOR_NO_LEFT, ANCHOR_LEFT_CLIPPED, ANCHOR_RIGHT_CLIPPED = 1, 2, 4, 8, 16
 ANCHOR_SOFT_LEFT, ANCHOR_SOFT_RIGHT = 32, 64      # end clipping (lrm_map_options.clip)
 ANCHOR_DIAGS = 64                      # LRM_ANCHOR_DIAGS
@@ -117,6 +146,7 @@ class HostIndex(C.Structure):          # lrm_index_host.h
 
 assert C.sizeof(Ui40) == 8 and C.sizeof(Entry) == 24 and C.sizeof(SeqMeta) == 24
 assert C.sizeof(MapOptions) == 76 and C.sizeof(Anchor) == 32 and C.sizeof(Clip) == 8
+assert MapOptions.split.offset == 68 and C.sizeof(Segment) == 16 and C.sizeof(SplitDev) == 112 and C.sizeof(SplitOut) == 120
 
 # every symbol include/*.h declares: (restype, argtypes)
 SYMBOLS = {
@@ -192,6 +222,13 @@ SYMBOLS = {
                                                C.c_uint32, C.c_void_p, GactParams, C.c_void_p, C.c_uint64, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                                C.c_uint32, C.c_void_p, C.c_void_p]),
+    "lrm_split_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, u64p]),
+    "lrm_clip_of_cigar": (C.c_int, [C.POINTER(Cigar), C.c_int, u32p, u32p]),
+    "lrm_split_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, Params,
+                                      GactParams, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SplitDev), u64p,
+                                      C.c_void_p]),
+    "lrm_split_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  Params, GactParams, C.POINTER(MapOptions), C.POINTER(SplitOut)]),
     "lrm_debug_anchor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(Anchor)]),
     "lrm_workspace_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats), C.c_void_p]),
     "lrm_workspace_set_counting": (C.c_int, [C.c_void_p, C.c_int]),
@@ -232,6 +269,8 @@ SYMBOLS = {
     "lrm_sam_header": (C.c_void_p, [C.POINTER(MtaEntry), C.c_int, C.c_long, u64p]),
     "lrm_sam_format": (C.c_void_p, [C.POINTER(ReadBatch), C.POINTER(MtaEntry), C.c_int, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
+    "lrm_sam_format_split": (C.c_void_p, [C.POINTER(ReadBatch), C.POINTER(MtaEntry), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(SplitOut), u64p]),
     "lrm_free": (None, [C.c_void_p]),
     "lrm_accaln": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, Params, GactParams, C.c_int, C.c_long, u64p, u64p]),
     "lrm_accaln_opt": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, Params, GactParams, C.c_int, C.c_long, u64p, u64p,

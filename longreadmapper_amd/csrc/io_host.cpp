@@ -537,12 +537,122 @@ extern "C" char *lrm_sam_header(const lrm_mta_entry *mta, int mta_len, long rg_i
 // _rev_comp_in_place's base map (alnmain.c:29-52): ACGT of either case -> upper-case complement, anything else -> 'N'
 static const struct CompTable { char t[256]; CompTable() { for (int c = 0; c < 256; ++c) t[c] = 'N'; t['A'] = t['a'] = 'T'; t['C'] = t['c'] = 'G'; t['G'] = t['g'] = 'C'; t['T'] = t['t'] = 'A'; } } k_comp;
 
+// ---- split reads: supplementary records and SA:Z (docs/GACT_SPEC.md, "Split reads") ----------------------------------------
+struct AlnShape { uint64_t q, t, sl, sr; };        // aligned query bases, target span, 'S' columns at the start / at the end
+static AlnShape aln_shape(const lrm_cigar &c, bool is_text) {
+    AlnShape a = {0, 0, 0, 0};
+    if (c.n_cigar_op <= 0 || !c.cigar) return a;
+    bool seen = false;                             // a column other than 'S' has been seen: an 'S' run from here on is the right one
+    auto add = [&](char op, uint64_t run) {
+        if (op == 'S') { (seen ? a.sr : a.sl) += run; return; }
+        seen = true;
+        if (op == 'M' || op == '=' || op == 'X') { a.q += run; a.t += run; }
+        else if (op == 'I') a.q += run;
+        else if (op == 'D') a.t += run;
+    };
+    if (is_text) {
+        uint64_t run = 0;
+        for (const char *p = (const char *) c.cigar; *p; ++p) {
+            if (*p >= '0' && *p <= '9') run = run * 10 + (uint64_t) (*p - '0');
+            else { add(*p, run); run = 0; }
+        }
+    } else {
+        for (int i = 0; i < c.n_cigar_op; ++i) add((char) c.cigar[i], 1);
+    }
+    return a;
+}
+static inline void put_num(std::string &s, uint64_t v) { char num[24]; s.append(num, (size_t) put_uint(num, v)); }
+static inline void put_int(std::string &s, int64_t v) { if (v < 0) { s += '-'; put_num(s, (uint64_t) -v); } else put_num(s, (uint64_t) v); }
+// one SA:Z entry: rname,pos,strand,<c5>S<q>M<d>D|I<c3>S,255,ED;
+static void sa_entry(std::string &s, const lrm_mta_entry *mta, int mta_len, const lrm_seq_meta &m, bool rev, uint64_t c5,
+                     const AlnShape &a, uint64_t c3, int ed) {
+    if (m.seq_id >= 0 && m.seq_id < mta_len) s.append(mta[m.seq_id].name, mta[m.seq_id].name_len); else s += '*';
+    s += ','; put_num(s, m.off + 1); s += ','; s += rev ? '-' : '+'; s += ',';
+    if (c5) { put_num(s, c5); s += 'S'; }
+    put_num(s, a.q); s += 'M';
+    if (a.t > a.q) { put_num(s, a.t - a.q); s += 'D'; }
+    if (a.q > a.t) { put_num(s, a.q - a.t); s += 'I'; }
+    if (c3) { put_num(s, c3); s += 'S'; }
+    s += ",255,"; put_int(s, ed); s += ';';
+}
+struct SplitCtx {                                  // a batch's segments, and where those of read i begin (first[i] .. first[i + 1])
+    const lrm_split_out *sp;
+    std::vector<uint64_t> first;
+    SplitCtx(const lrm_split_out *o, uint64_t n) : sp(o), first((size_t) n + 1, 0) {
+        const uint64_t k = o ? o->n_seg : 0;
+        for (uint64_t s = 0; s < k; ++s) if (o->seg[s].read < n) ++first[(size_t) o->seg[s].read + 1];
+        for (uint64_t i = 0; i < n; ++i) first[(size_t) i + 1] += first[(size_t) i];
+    }
+};
+// the hard-clipped bases either side of segment g of a read of n bases, in the orientation of the segment's record
+static inline void seg_hard(const lrm_segment &g, uint32_t n, bool ss, uint64_t *hl, uint64_t *hr) {
+    const uint64_t a = g.start, b = (uint64_t) n - g.start - g.len;
+    *hl = ss ? b : a; *hr = ss ? a : b;
+}
+// SA:Z of read i's primary (tail of its line) and its supplementary lines
+static void sam_split_lines(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig, const int *score,
+                            const lrm_seq_meta *meta, uint64_t i, const SplitCtx &sx, bool cigar_is_text, std::string &s) {
+    const lrm_split_out &o = *sx.sp;
+    uint64_t rep[2];
+    int nrep = 0;
+    for (uint64_t k = sx.first[(size_t) i]; k < sx.first[(size_t) i + 1] && nrep < 2; ++k) if (o.seg[k].flags & LRM_SEG_ALIGNED) rep[nrep++] = k;
+    if (!nrep) { s += '\n'; return; }
+    const uint32_t n = reads->lens[i];
+    const bool ps = meta[i].strand == 1;
+    const AlnShape pa = aln_shape(cig[i], cigar_is_text);
+    AlnShape sa[2];
+    uint64_t hl[2], hr[2];
+    bool ss[2];
+    for (int k = 0; k < nrep; ++k) {
+        sa[k] = aln_shape(o.cig[rep[k]], cigar_is_text);
+        ss[k] = o.meta[rep[k]].strand == 1;
+        seg_hard(o.seg[rep[k]], n, ss[k], &hl[k], &hr[k]);
+    }
+    auto seg_entry = [&](int k) { sa_entry(s, mta, mta_len, o.meta[rep[k]], ps != ss[k], hl[k] + sa[k].sl, sa[k], sa[k].sr + hr[k], o.score[rep[k]]); };
+    s += "\tSA:Z:";
+    for (int k = 0; k < nrep; ++k) seg_entry(k);
+    s += '\n';
+    for (int k = 0; k < nrep; ++k) {
+        const uint64_t x = rep[k];
+        const lrm_segment &g = o.seg[x];
+        const bool rev = ps != ss[k];
+        s += reads->names[i];
+        s += '\t'; put_num(s, 2048u + (rev ? 16u : 0u));
+        s += '\t';
+        if (o.meta[x].seq_id >= 0 && o.meta[x].seq_id < mta_len) s.append(mta[o.meta[x].seq_id].name, mta[o.meta[x].seq_id].name_len); else s += '*';
+        s += '\t'; put_num(s, o.meta[x].off + 1);
+        s += "\t255\t";
+        if (hl[k]) { put_num(s, hl[k]); s += 'H'; }
+        if (o.cig[x].n_cigar_op > 0 && cigar_is_text) s.append((const char *) o.cig[x].cigar);
+        else if (o.cig[x].n_cigar_op > 0) {
+            const size_t at = s.size();
+            s.resize(at + 2 * (size_t) o.cig[x].n_cigar_op + 16);
+            s.resize(at + rle_write(o.cig[x].cigar, o.cig[x].n_cigar_op, &s[at]));
+        } else s += '*';
+        if (hr[k]) { put_num(s, hr[k]); s += 'H'; }
+        s += "\t*\t0\t0\t";
+        s.append(o.rows + x * o.row_stride, g.len);                  // the segment row as the extension left it
+        s += '\t';
+        if (reads->quals[i]) {                                       // the read's qualities run as it was sequenced
+            const uint64_t q0 = ps ? (uint64_t) n - g.start - g.len : g.start;
+            const char *q = reads->quals[i] + q0;
+            if (rev) { const size_t at = s.size(); s.resize(at + g.len); for (uint32_t c = 0; c < g.len; ++c) s[at + c] = q[g.len - 1 - c]; }
+            else s.append(q, g.len);
+        } else s += '*';
+        s += "\tED:I:"; put_int(s, o.score[x]);
+        s += "\tSA:Z:";
+        sa_entry(s, mta, mta_len, meta[i], ps, pa.sl, pa, pa.sr, score[i]);
+        if (nrep == 2) seg_entry(1 - k);
+        s += '\n';
+    }
+}
+
 // SAM lines of reads [lo, hi) appended to s (alnmain.c:500-525 field for field).  No snprintf on the hot path: a 10 kbp
 // ONT read has ~2000 CIGAR runs.
 // cigar_is_text: cig[i].cigar is the NUL-terminated run-length text already (lrm_map_options.cigar_text), not op bytes.
 static void sam_format_range(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig,
                              const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t lo, uint64_t hi,
-                             std::string &s, bool cigar_is_text, bool revcomp_here) {
+                             std::string &s, bool cigar_is_text, bool revcomp_here, const SplitCtx *sx = nullptr) {
     uint64_t est = 0;
     for (uint64_t i = lo; i < hi; ++i) est += 2ull * reads->lens[i] + 2ull * (cig[i].n_cigar_op > 0 ? (uint64_t) cig[i].n_cigar_op : 0) + 160;
     s.clear();
@@ -591,21 +701,37 @@ static void sam_format_range(const lrm_read_batch *reads, const lrm_mta_entry *m
         s += "\tED:I:";
         if (score[i] < 0) { s += '-'; s.append(num, (size_t) put_uint(num, (uint64_t) (-(int64_t) score[i]))); }
         else s.append(num, (size_t) put_uint(num, (uint64_t) score[i]));
-        s += '\n';
+        if (sx && !unmapped) sam_split_lines(reads, mta, mta_len, cig, score, meta, i, *sx, cigar_is_text, s);
+        else s += '\n';
     }
 }
 
 // Every thread formats a contiguous range of reads into its own buffer.
 static void sam_format_parts(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig,
                              const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t n, int nt,
-                             std::vector<std::string> &parts, bool cigar_is_text = false, bool revcomp_here = false) {
+                             std::vector<std::string> &parts, bool cigar_is_text = false, bool revcomp_here = false,
+                             const SplitCtx *sx = nullptr) {
     if (nt < 1) nt = 1;
     if ((uint64_t) nt > n) nt = n ? (int) n : 1;
     parts.resize((size_t) nt);
 #pragma omp parallel for schedule(static, 1) num_threads(nt)
     for (int t = 0; t < nt; ++t)
         sam_format_range(reads, mta, mta_len, cig, score, meta, meta_r, n * (uint64_t) t / (uint64_t) nt, n * (uint64_t) (t + 1) / (uint64_t) nt,
-                         parts[(size_t) t], cigar_is_text, revcomp_here);
+                         parts[(size_t) t], cigar_is_text, revcomp_here, sx);
+}
+
+static char *sam_join(std::vector<std::string> &parts, uint64_t *len_out);
+extern "C" char *lrm_sam_format_split(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig,
+                                      const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t n, int cigar_is_text,
+                                      int revcomp_here, const lrm_split_out *split, uint64_t *len_out) {
+    std::vector<std::string> parts;
+    if (!split || split->n_seg == 0) {
+        sam_format_parts(reads, mta, mta_len, cig, score, meta, meta_r, n, lrm_host_threads(), parts, cigar_is_text != 0, revcomp_here != 0);
+    } else {
+        const SplitCtx sx(split, n);
+        sam_format_parts(reads, mta, mta_len, cig, score, meta, meta_r, n, lrm_host_threads(), parts, cigar_is_text != 0, revcomp_here != 0, &sx);
+    }
+    return sam_join(parts, len_out);
 }
 
 extern "C" char *lrm_sam_format(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len,
@@ -613,6 +739,9 @@ extern "C" char *lrm_sam_format(const lrm_read_batch *reads, const lrm_mta_entry
                                 const int *meta_r, uint64_t n, uint64_t *len_out) {
     std::vector<std::string> parts;
     sam_format_parts(reads, mta, mta_len, cig, score, meta, meta_r, n, lrm_host_threads(), parts);
+    return sam_join(parts, len_out);
+}
+static char *sam_join(std::vector<std::string> &parts, uint64_t *len_out) {
     uint64_t total = 0;
     std::vector<uint64_t> at(parts.size() + 1, 0);
     for (size_t k = 0; k < parts.size(); ++k) { at[k + 1] = at[k] + parts[k].size(); total = at[k + 1]; }
@@ -671,7 +800,19 @@ struct BatchSet {
     std::vector<lrm_seq_meta> meta;
     uint64_t sstride = 0;
     lrm_ticket *ticket = nullptr;
-    BatchSet() { memset(&b, 0, sizeof(b)); }
+    // split reads: the second pass over this batch's clipped ends (lrm_split_batch), pageable buffers grown on demand
+    lrm_split_out split;
+    std::vector<lrm_segment> sp_seg;
+    std::vector<char> sp_rows;
+    std::vector<uint8_t> sp_store;
+    std::vector<uint32_t> sp_lens;
+    std::vector<lrm_entry> sp_best;
+    std::vector<lrm_cigar> sp_cig;
+    std::vector<int> sp_score, sp_meta_r;
+    std::vector<lrm_seq_meta> sp_meta;
+    std::vector<lrm_anchor> sp_anchor;
+    std::vector<lrm_clip> sp_clip;
+    BatchSet() { memset(&b, 0, sizeof(b)); memset(&split, 0, sizeof(split)); }
     ~BatchSet() { lrm_host_free(reads_pin); lrm_host_free(store_pin); free(store_pg); }
 };
 
@@ -707,6 +848,12 @@ extern "C" int lrm_accaln_opt(const char *genome, const char *reads_path, const 
     const bool anchored = user && user->struct_size >= offsetof(lrm_map_options, anchor_min_len) + sizeof(uint32_t) && user->anchored;
     // (a caller built before the clip fields existed has them inside its zeroed reserved words or not at all)
     const bool clip = user && user->struct_size >= offsetof(lrm_map_options, clip_end_bonus) + sizeof(uint32_t) && user->clip;
+    // split reads: after a batch's wait its clipped ends go through lrm_split_batch, the formatter prints what that placed
+    const bool split = clip && user->struct_size >= offsetof(lrm_map_options, split_min_len) + sizeof(uint32_t) && user->split;
+    if (user && user->struct_size >= offsetof(lrm_map_options, split_min_len) + sizeof(uint32_t) && user->split && !clip) {
+        lrm_set_error("lrm_map_options.split needs lrm_map_options.clip");
+        return -1;
+    }
     // op bytes per read: alnmain.c:316-320, a multiple of 16; the anchored mode's targets are an eighth longer than the reads
     auto store_stride_of = [anchored](uint64_t max_len) {
         const uint64_t s = ((anchored ? 2 * max_len + max_len / 8 + 2 : 2 * max_len) + 15) & ~15ull;
@@ -758,6 +905,33 @@ extern "C" int lrm_accaln_opt(const char *genome, const char *reads_path, const 
         mopt.keep_reads = 1;                        // reverse-strand reads are reverse-complemented by the formatter as it copies them
         if (anchored) { mopt.anchored = 1; mopt.anchor_min_len = user->anchor_min_len; }
         if (clip) { mopt.clip = 1; mopt.clip_penalty = user->clip_penalty; mopt.clip_end_bonus = user->clip_end_bonus; }
+        if (split) { mopt.split = 1; mopt.split_min_len = user->split_min_len; }
+        // the second pass over a batch that has come back: size the segment buffers from the plan, then lrm_split_batch
+        auto split_pass = [&](BatchSet *s) -> int {
+            const uint64_t n = s->b.n;
+            std::vector<lrm_clip> cl((size_t) n);
+            for (uint64_t i = 0; i < n; ++i) {
+                cl[i].left = cl[i].right = 0;
+                if (s->meta_r[i] != 0 && s->score[i] != -1) (void) lrm_clip_of_cigar(&s->cig[i], 1, &cl[i].left, &cl[i].right);
+            }
+            uint64_t k = 0;
+            if (lrm_split_plan(s->b.lens, cl.data(), n, mopt.split_min_len, nullptr, 0, &k) == -1) return -1;
+            uint32_t longest = 0;
+            for (uint64_t i = 0; i < n; ++i) longest = std::max(longest, std::max(cl[i].left, cl[i].right));
+            lrm_split_out &o = s->split;
+            memset(&o, 0, sizeof(o));
+            if (k == 0) return 0;
+            o.cap = k;
+            o.row_stride = ((uint64_t) longest + 16) & ~15ull;
+            o.store_stride = store_stride_of(longest);
+            s->sp_seg.resize(k); s->sp_rows.resize(k * o.row_stride); s->sp_store.resize(k * o.store_stride); s->sp_lens.resize(k);
+            s->sp_best.resize(k); s->sp_cig.resize(k); s->sp_score.resize(k); s->sp_meta_r.resize(k); s->sp_meta.resize(k);
+            s->sp_anchor.resize(k); s->sp_clip.resize(k);
+            o.seg = s->sp_seg.data(); o.rows = s->sp_rows.data(); o.store = s->sp_store.data(); o.lens = s->sp_lens.data();
+            o.best = s->sp_best.data(); o.cig = s->sp_cig.data(); o.score = s->sp_score.data(); o.meta_r = s->sp_meta_r.data();
+            o.meta = s->sp_meta.data(); o.anchor = s->sp_anchor.data(); o.clip = s->sp_clip.data();
+            return lrm_split_batch(gpu, s->b.seqs, s->b.stride, s->b.lens, n, s->cig.data(), s->meta.data(), s->meta_r.data(), p, gp, &mopt, &o);
+        };
         // Pinning the batch buffers (0.2 s per GB to pin and to release, and the device stalls while the runtime pins)
         // pays from a few tens of Gbp on: reads files below 16 GiB run through pageable buffers.
         bool want_pinned = false;
@@ -821,6 +995,11 @@ extern "C" int lrm_accaln_opt(const char *genome, const char *reads_path, const 
                 if (!err.get() && free_texts.pop(tb)) {
                     const uint64_t n = s->b.n;
                     const double t0 = now();
+                    if (split && s->split.n_seg) {
+                        const SplitCtx sx(&s->split, n);
+                        sam_format_parts(&s->b, hi.mta, hi.mta_len, s->cig.data(), s->score.data(), s->meta.data(), s->meta_r.data(), n,
+                                         io_threads, tb->parts, /* cigar_is_text */ true, /* revcomp_here */ true, &sx);
+                    } else
                     sam_format_parts(&s->b, hi.mta, hi.mta_len, s->cig.data(), s->score.data(), s->meta.data(), s->meta_r.data(), n,
                                      io_threads, tb->parts, /* cigar_is_text */ true, /* revcomp_here */ true);
                     t_fmt += now() - t0;
@@ -867,7 +1046,8 @@ extern "C" int lrm_accaln_opt(const char *genome, const char *reads_path, const 
             BatchSet *s = inflight.front();
             inflight.pop_front();
             const double t0 = now();
-            const int mrc = lrm_map_batch_wait(s->ticket);
+            int mrc = lrm_map_batch_wait(s->ticket);
+            if (!mrc && split) mrc = split_pass(s);
             t_map += now() - t0;
             if (verbose) fprintf(stderr, "[lrm accaln] %.3f waited %.3f s for a batch of %llu\n", now() - t_upload, now() - t0, (unsigned long long) s->b.n);
             s->ticket = nullptr;

@@ -146,6 +146,7 @@ void lrm_resolve_map_tune(const lrm_map_options *opt, const LrmEnv &env, LrmMapT
     t->anchored = o.anchored != 0;
     t->anchor_min_len = o.anchor_min_len;
     t->clip = o.clip != 0; t->clip_penalty = o.clip_penalty; t->clip_end_bonus = o.clip_end_bonus;
+    t->split = o.split != 0; t->split_min_len = o.split_min_len;
     // measured defaults of the kernel knobs (tools/seed_probe.py sweeps them through the environment)
     t->ss_items = 2048; t->vote_vg = 16; t->vote_t1 = LRM_VOTE_T1_LIMIT; t->vote_u = 2; t->vote_load = 50; t->vote_fast = o.vote_exact_only ? 0 : 1;
     t->ext_streams = 2; t->seed_streams = 2;
@@ -856,6 +857,7 @@ extern "C" void lrm_workspace_free(lrm_workspace *ws) {
     (void) hipFree(ws->d_hcount); (void) hipFree(ws->d_counters); (void) hipFree(ws->d_recq); (void) hipFree(ws->d_cnt); (void) hipFree(ws->d_kc_key); (void) hipFree(ws->d_kc_ord); (void) hipFree(ws->d_redo); (void) hipFree(ws->d_big); (void) hipFree(ws->d_gtab); (void) hipFree(ws->d_glock);
     lrm_bs_scratch_free(&ws->bs);
     lrm_anchor_scratch_free(ws);
+    lrm_split_scratch_free(ws);
     if (ws->h_err) (void) hipHostFree((void *) ws->h_err);
     for (int i = 0; i < LRM_MAX_TIMED; ++i) {
         if (ws->ev_start[i]) (void) hipEventDestroy((hipEvent_t) ws->ev_start[i]);
@@ -1044,6 +1046,90 @@ extern "C" int lrm_extend_batch_clipped_dev(lrm_index *idx, lrm_workspace *ws, c
     if (int rc = extend_dev_ready(idx, ws, b)) return rc;
     return lrm_launch_extend_anchored(idx, ws, b, gp, d_anchor, min_len, LrmClipOpt{1, clip_penalty, clip_end_bonus, d_clip},
                                       idx->mtune, stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// split reads (docs/GACT_SPEC.md, "Split reads"): the rule on the host, and the device-buffer entry point
+// ------------------------------------------------------------------------------------------
+int lrm_split_min_len(uint32_t m, uint32_t *out) {
+    if (m == 0) m = LRM_SPLIT_MIN_DEFAULT;
+    if (m < 50 || m > (1u << 20)) { lrm_set_error("split_min_len %u outside [50, 2^20]", m); return -1; }
+    *out = m;
+    return 0;
+}
+
+extern "C" int lrm_split_plan(const uint32_t *lens, const lrm_clip *clip, uint64_t n, uint32_t split_min_len,
+                              lrm_segment *seg_out, uint64_t cap, uint64_t *n_seg) {
+    uint32_t M;
+    if (!n_seg || (n && (!lens || !clip)) || (cap && !seg_out)) { lrm_set_error("null argument"); return -1; }
+    if (n > 0xFFFFFFFFull) { lrm_set_error("batch too large"); return -1; }
+    if (lrm_split_min_len(split_min_len, &M)) return -1;
+    uint64_t total = 0;
+    lrm_segment two[2];
+    for (uint64_t i = 0; i < n; ++i) total += lrm_split_segments((uint32_t) i, lens[i], clip[i].left, clip[i].right, M, two);
+    *n_seg = total;
+    if (total > cap) {
+        lrm_set_error("%llu segments, room for %llu", (unsigned long long) total, (unsigned long long) cap);
+        return -3;
+    }
+    uint64_t at = 0;
+    for (uint64_t i = 0; i < n; ++i) at += lrm_split_segments((uint32_t) i, lens[i], clip[i].left, clip[i].right, M, seg_out + at);
+    return 0;
+}
+
+extern "C" int lrm_clip_of_cigar(const lrm_cigar *cig, int is_text, uint32_t *left, uint32_t *right) {
+    if (!cig || !left || !right) { lrm_set_error("null argument"); return -1; }
+    *left = *right = 0;
+    if (cig->n_cigar_op <= 0 || !cig->cigar) return 0;
+    if (!is_text) {
+        const uint8_t *o = cig->cigar;
+        const int k = cig->n_cigar_op;
+        int l = 0, r = 0;
+        while (l < k && o[l] == 'S') ++l;
+        while (r < k - l && o[k - 1 - r] == 'S') ++r;
+        *left = (uint32_t) l; *right = (uint32_t) r;
+        return 0;
+    }
+    // run-length text: <count><op>...; the first run and the last run
+    const char *t = (const char *) cig->cigar;
+    uint64_t run = 0, first = 0, last = 0;
+    int runs = 0;
+    char last_op = 0;
+    for (const char *c = t; *c; ++c) {
+        if (*c >= '0' && *c <= '9') { run = run * 10 + (uint64_t) (*c - '0'); continue; }
+        if (runs == 0 && *c == 'S') first = run;
+        last = run; last_op = *c;
+        ++runs;
+        run = 0;
+    }
+    *left = (uint32_t) first;
+    if (runs > 1 && last_op == 'S') *right = (uint32_t) last;
+    return 0;
+}
+
+extern "C" int lrm_split_batch_dev(lrm_index *idx, lrm_workspace *ws_seg, const char *d_reads, uint64_t stride,
+                                   const uint32_t *d_lens, uint64_t n, const lrm_clip *d_clip, lrm_params p, lrm_gact_params gp,
+                                   uint32_t anchor_min_len, uint32_t clip_penalty, uint32_t clip_end_bonus, uint32_t split_min_len,
+                                   const lrm_split_dev *out, uint64_t *n_seg, void *stream) {
+    if (!idx || !ws_seg || !out || !n_seg || (n && (!d_reads || !d_lens || !d_clip))) { lrm_set_error("null argument"); return -1; }
+    *n_seg = 0;
+    if (out->cap && (!out->seg || !out->rows || !out->lens || !out->best || !out->store || !out->n_ops || !out->score || !out->meta ||
+                     !out->meta_r || !out->anchor || !out->clip)) { lrm_set_error("null array in lrm_split_dev"); return -1; }
+    if (n > 0x7fffffffull) { lrm_set_error("batch too large"); return -1; }
+    if (ws_seg->idx != idx) { lrm_set_error("workspace does not belong to this index"); return -1; }
+    if ((ws_seg->parts & (LRM_WS_SEED | LRM_WS_EXTEND)) != (LRM_WS_SEED | LRM_WS_EXTEND)) { lrm_set_error("segment workspace needs seed and extension scratch"); return -1; }
+    if (p.seed_len != ws_seg->seed_len || p.thres > ws_seg->thres) {
+        lrm_set_error("segment workspace was made for seed=%u thres=%u, the batch has seed=%u thres=%u", ws_seg->seed_len, ws_seg->thres, p.seed_len, p.thres);
+        return -1;
+    }
+    if (out->cap && (((uintptr_t) out->rows | out->row_stride) & 15u)) { lrm_set_error("segment rows must be 16-byte aligned, row_stride a multiple of 16"); return -1; }
+    if (out->cap && (out->store_stride & 3u)) { lrm_set_error("segment store_stride must be a multiple of 4"); return -1; }
+    LrmSplitArgs a = {d_reads, stride, d_lens, n, d_clip, p.seed_len, p.thres, gp, anchor_min_len, clip_penalty, clip_end_bonus, 0};
+    if (lrm_split_min_len(split_min_len, &a.split_min_len)) return -1;
+    if (lrm_ws_take_error(ws_seg)) return -2;
+    HIPCHK(hipSetDevice(idx->device));
+    if (n == 0) return 0;
+    return lrm_launch_split(idx, ws_seg, a, *out, n_seg, stream);
 }
 
 // ------------------------------------------------------------------------------------------

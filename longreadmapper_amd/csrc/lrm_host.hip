@@ -104,7 +104,7 @@ constexpr int N_RING = 16;          // 256 MiB of pinned chunks per replica: a u
 constexpr int N_SEED_STREAMS = 3;
 constexpr int N_EXT_STREAMS = 4;
 constexpr int N_SLOTS = 3;            // upper bound on the batches (slices) in flight per replica; n_slots of them are used
-struct DevSet { DevSlot reads, lens, best, store, nops, score, meta, mr, tlen; };
+struct DevSet { DevSlot reads, lens, best, store, nops, score, meta, mr, tlen, anchor; };
 
 // device-side resources of one slice in flight
 struct Slot {
@@ -115,6 +115,7 @@ struct Slot {
     hipEvent_t ev_dense[2] = {nullptr, nullptr};   // the last transfer out of dense[b] has drained
     bool dense_used[2] = {false, false};
     PinSlot h_small;                               // pinned staging of the small result arrays and offset tables (per read)
+    PinSlot h_anchor;                              // ... of the anchor records, for the one caller that asks for them (lrm_split_batch)
     std::vector<hipEvent_t> ev_up, ev_seed, ev_ext;   // per sub-batch / per extension group, grown on demand
     bool busy = false;
 };
@@ -134,6 +135,8 @@ int wait_event(hipEvent_t ev) {
 }
 
 }  // namespace
+
+int lrm_wait_event(void *ev) { return wait_event((hipEvent_t) ev); }
 
 struct MapJob;
 struct SliceJob;
@@ -469,11 +472,13 @@ struct MapJob {
     lrm_params p; lrm_gact_params gp;
     const lrm_entry *best_in; lrm_entry *best_out;
     lrm_cigar *cig; uint8_t *store_mem; uint64_t store_stride; int *score; lrm_seq_meta *meta; int *meta_r;
+    lrm_anchor *anchor_out;           // anchored mode: the anchor records too (null: they stay in the workspace)
     MapJob slice(uint64_t o, uint64_t m) const {
         MapJob j = *this;
         j.reads = reads + o * stride; j.lens = lens + o; j.n = m;
         if (best_in) j.best_in = best_in + o;
         if (best_out) j.best_out = best_out + o;
+        if (anchor_out) j.anchor_out = anchor_out + o;
         if (cig) { j.cig = cig + o; j.store_mem = store_mem + o * store_stride; j.score = score + o; j.meta = meta + o; j.meta_r = meta_r + o; }
         return j;
     }
@@ -571,6 +576,8 @@ int plan_and_issue(LrmHostCtx &c, SliceJob &sj) {
         for (int b = 0; b < 2; ++b)
             if (S.dense[b].ensure(unit_max * (dstride + j.stride + 32)) || S.offs[b].ensure(unit_max * 2 * 12)) { lrm_set_error("device allocation failed"); return -1; }
     if (S.h_small.ensure(n * 96 + 4096)) { lrm_set_error("pinned staging allocation failed"); return -1; }
+    const bool want_anchor = j.anchor_out && (j.mode & DO_EXTEND) && mt.anchored;
+    if (want_anchor && (d.anchor.ensure(n * sizeof(lrm_anchor)) || S.h_anchor.ensure(n * sizeof(lrm_anchor)))) { lrm_set_error("allocation for the anchor records failed"); return -1; }
     S.dense_used[0] = S.dense_used[1] = false;
 
     for (uint64_t k = 0; k < subs.size(); ++k) {
@@ -599,7 +606,10 @@ int plan_and_issue(LrmHostCtx &c, SliceJob &sj) {
                                       (const lrm_entry *) d.best.p + u.off, (uint8_t *) d.store.p + u.off * dstride, dstride,
                                       (int32_t *) d.nops.p + u.off, (int32_t *) d.score.p + u.off, (lrm_seq_meta *) d.meta.p + u.off,
                                       (int32_t *) d.mr.p + u.off};
-            if (lrm_launch_extend(idx, S.ws_ext[xs], b, j.gp, mt, c.ext[xs])) return -1;
+            if (want_anchor) {                                                 // what lrm_launch_extend does in this mode, with the records kept
+                if (lrm_launch_extend_anchored(idx, S.ws_ext[xs], b, j.gp, (lrm_anchor *) d.anchor.p + u.off, mt.anchor_min_len, lrm_clip_of(mt),
+                                               mt, c.ext[xs])) return -1;
+            } else if (lrm_launch_extend(idx, S.ws_ext[xs], b, j.gp, mt, c.ext[xs])) return -1;
             if (mt.cigar_text) {                                               // length of every read's run-length CIGAR text
                 hipLaunchKernelGGL(cigar_text_kernel<false>, dim3((uint32_t) u.m), dim3(256), 0, c.ext[xs], (const uint8_t *) d.store.p + u.off * dstride, dstride,
                                    (const int32_t *) d.nops.p + u.off, (const int32_t *) d.score.p + u.off, (const int32_t *) d.mr.p + u.off,
@@ -651,6 +661,9 @@ int collect(LrmHostCtx &c, SliceJob &sj, size_t g) {
         HIPCHK(hipMemcpyAsync(h_mr, (const int32_t *) d.mr.p + o, m * 4, hipMemcpyDeviceToHost, c.down));
         if (text) HIPCHK(hipMemcpyAsync(h_tlen, (const uint32_t *) d.tlen.p + o, m * 4, hipMemcpyDeviceToHost, c.down));
     }
+    const bool want_anchor = j.anchor_out && (j.mode & DO_EXTEND) && sj.mt.anchored;
+    lrm_anchor *h_anchor = want_anchor ? (lrm_anchor *) S.h_anchor.p + o : nullptr;
+    if (want_anchor) HIPCHK(hipMemcpyAsync(h_anchor, (const lrm_anchor *) d.anchor.p + o, m * sizeof(lrm_anchor), hipMemcpyDeviceToHost, c.down));
     HIPCHK(hipEventRecord(c.ev_small, c.down));
     if (wait_event(c.ev_small)) return -1;
     if (j.mode & DO_SEED) memcpy(j.best_out + o, h_best, m * sizeof(lrm_entry));
@@ -658,6 +671,7 @@ int collect(LrmHostCtx &c, SliceJob &sj, size_t g) {
     memcpy(j.score + o, h_score, m * 4);
     memcpy(j.meta + o, h_meta, m * sizeof(lrm_seq_meta));
     memcpy(j.meta_r + o, h_mr, m * 4);
+    if (want_anchor) memcpy(j.anchor_out + o, h_anchor, m * sizeof(lrm_anchor));
 
     // Dense image of the unit on the device: the used part of every CIGAR row, then the reads that were
     // reverse-complemented in place (alnmain.c:437; the other rows of reads_buf did not change).  Everything crosses
@@ -1039,9 +1053,10 @@ void lrm_host_ctx_free(lrm_index *idx) {
         for (int s = 0; s < N_EXT_STREAMS; ++s) if (S.ws_ext[s]) lrm_workspace_free(S.ws_ext[s]);
         DevSet &d = S.dev;
         d.reads.release(); d.lens.release(); d.best.release(); d.store.release();
-        d.nops.release(); d.score.release(); d.meta.release(); d.mr.release(); d.tlen.release();
+        d.nops.release(); d.score.release(); d.meta.release(); d.mr.release(); d.tlen.release(); d.anchor.release();
         for (int b = 0; b < 2; ++b) { S.dense[b].release(); S.offs[b].release(); if (S.ev_dense[b]) (void) hipEventDestroy(S.ev_dense[b]); }
         S.h_small.release();
+        S.h_anchor.release();
     }
     delete c;
 }
@@ -1098,6 +1113,86 @@ extern "C" int lrm_map_batch_submit(lrm_index *idx, char *reads_buf, uint64_t st
     MapJob j;
     if (map_job_of(j, idx, reads_buf, stride, lens, n, p, gp, best_out, cig_out, store_mem, store_stride, score_out, meta_out, meta_r_out)) return -1;
     return run_job(idx, j, opt, ticket_out);
+}
+
+// ---- split reads: the second pass over a batch that came back with end clipping (docs/GACT_SPEC.md, "Split reads") ----------
+// alnmain.c:31-52 on the host, as the device's comp_base has it
+static inline char split_comp(char ch) {
+    switch (ch & 0xDF) { case 'A': return 'T'; case 'C': return 'G'; case 'G': return 'C'; case 'T': return 'A'; default: return 'N'; }
+}
+static int split_batch_impl(lrm_index *idx, const char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
+                            const lrm_cigar *cig, const lrm_seq_meta *meta, const int *meta_r, lrm_params p, lrm_gact_params gp,
+                            const lrm_map_options *opt, lrm_split_out *out) {
+    LrmMapTune mt = idx->mtune;
+    if (opt) lrm_resolve_map_tune(opt, idx->env, &mt);
+    if (!mt.clip || !mt.anchored) { lrm_set_error("lrm_split_batch needs lrm_map_options.clip (and with it .anchored)"); return -1; }
+    uint32_t M;
+    if (lrm_split_min_len(mt.split_min_len, &M)) return -1;
+    if (n > 0x7fffffffull) { lrm_set_error("batch too large"); return -1; }
+    // the clip counts, as the op bytes or the text of every read have them
+    std::vector<lrm_clip> clip((size_t) n);
+    for (uint64_t i = 0; i < n; ++i) {
+        clip[i].left = clip[i].right = 0;
+        if (meta_r[i] != 0 && cig[i].score != -1) (void) lrm_clip_of_cigar(&cig[i], mt.cigar_text, &clip[i].left, &clip[i].right);
+    }
+    uint64_t n_seg = 0;
+    const int prc = lrm_split_plan(lens, clip.data(), n, M, out->seg, out->cap, &n_seg);
+    out->n_seg = n_seg;
+    if (prc) return prc;
+    if (n_seg == 0) return 0;
+    uint32_t longest = 0;
+    for (uint64_t s = 0; s < n_seg; ++s) longest = out->seg[s].len > longest ? out->seg[s].len : longest;
+    if ((out->row_stride & 15u) || out->row_stride <= longest) {
+        lrm_set_error("split: row_stride %llu must be a multiple of 16 above the longest segment (%u)", (unsigned long long) out->row_stride, longest);
+        return -1;
+    }
+    // gather on the host: R is the caller's row, or its reverse complement when the caller kept its reads as they were
+    const int nt = lrm_host_threads();
+#pragma omp parallel for schedule(dynamic, 64) num_threads(nt)
+    for (uint64_t s = 0; s < n_seg; ++s) {
+        const lrm_segment &g = out->seg[s];
+        const char *src = reads_buf + (uint64_t) g.read * stride;
+        char *dst = out->rows + s * out->row_stride;
+        const uint32_t len_r = lens[g.read];
+        if (mt.keep_reads && meta_r[g.read] != 0 && meta[g.read].strand == 1)
+            for (uint32_t k = 0; k < g.len; ++k) dst[k] = split_comp(src[len_r - 1 - (g.start + k)]);
+        else memcpy(dst, src + g.start, g.len);
+        memset(dst + g.len, 0, (size_t) (((uint64_t) g.len + 16) & ~15ull) - g.len);
+        out->lens[s] = g.len;
+    }
+    // the segment batch through the pipeline, in the caller's result layout
+    lrm_map_options o2;
+    lrm_map_options_init(&o2);
+    if (opt) memcpy(&o2, opt, opt->struct_size && opt->struct_size < sizeof(o2) ? opt->struct_size : sizeof(o2));
+    else {
+        o2.dense_results = mt.dense; o2.cigar_text = (uint32_t) mt.cigar_text; o2.gact_impl = mt.gact_impl; o2.seed_rounds = mt.seed_rounds;
+        o2.anchor_min_len = mt.anchor_min_len; o2.clip_penalty = mt.clip_penalty; o2.clip_end_bonus = mt.clip_end_bonus;
+        o2.copy_threads = mt.copy_threads;
+    }
+    o2.struct_size = (uint32_t) sizeof(o2);
+    o2.anchored = 1; o2.clip = 1; o2.keep_reads = 0; o2.split = 0;
+    MapJob j = {};
+    j.mode = DO_SEED | DO_EXTEND; j.reads = out->rows; j.stride = out->row_stride; j.lens = out->lens; j.n = n_seg; j.p = p; j.gp = gp;
+    j.best_out = out->best; j.cig = out->cig; j.store_mem = out->store; j.store_stride = out->store_stride; j.score = out->score;
+    j.meta = out->meta; j.meta_r = out->meta_r; j.anchor_out = out->anchor;
+    if (int rc = run_job(idx, j, &o2, nullptr)) return rc;
+    for (uint64_t s = 0; s < n_seg; ++s) {
+        out->clip[s].left = out->clip[s].right = 0;
+        if (out->meta_r[s] != 0 && out->score[s] != -1) (void) lrm_clip_of_cigar(&out->cig[s], mt.cigar_text, &out->clip[s].left, &out->clip[s].right);
+        if (out->meta_r[s] != 0 && (out->anchor[s].flags & LRM_ANCHOR_ANCHORED)) out->seg[s].flags |= LRM_SEG_ALIGNED;
+    }
+    return 0;
+}
+
+extern "C" int lrm_split_batch(lrm_index *idx, const char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
+                               const lrm_cigar *cig, const lrm_seq_meta *meta, const int *meta_r, lrm_params p, lrm_gact_params gp,
+                               const lrm_map_options *opt, lrm_split_out *out) {
+    if (!idx || !out || (n && (!reads_buf || !lens || !cig || !meta || !meta_r))) { lrm_set_error("null argument"); return -1; }
+    out->n_seg = 0;
+    if (out->cap && (!out->seg || !out->rows || !out->lens || !out->best || !out->cig || !out->store || !out->score || !out->meta ||
+                     !out->meta_r || !out->anchor || !out->clip)) { lrm_set_error("null array in lrm_split_out"); return -1; }
+    try { return split_batch_impl(idx, reads_buf, stride, lens, n, cig, meta, meta_r, p, gp, opt, out); }
+    catch (const std::exception &e) { lrm_set_error("host-side failure: %s", e.what()); return -1; }
 }
 
 extern "C" int lrm_map_batch_wait(lrm_ticket *ticket) {

@@ -116,6 +116,7 @@ struct LrmMapTune {
     int dense, gact_impl, seed_rounds, cigar_text, keep_reads, anchored;
     uint32_t anchor_min_len;        // 0: LRM_ANCHOR_MIN_DEFAULT
     uint32_t clip, clip_penalty, clip_end_bonus;     // end clipping of the anchored mode; 0: LRM_CLIP_*_DEFAULT
+    uint32_t split, split_min_len;                   // split reads (second pass over the clipped ends); 0: LRM_SPLIT_MIN_DEFAULT
     uint32_t slice_reads, sub_batches, group_subs, bs_waves, copy_threads;
     uint32_t ss_items, ss_lds_pad, vote_vg, vote_t1, vote_u, vote_load, vote_fast;      // kernel tuning (environment only; measured defaults)
     uint32_t t3_limit, t3_slots;                                 // lrm_debug_set_vote_limits (tests)
@@ -236,6 +237,7 @@ struct lrm_workspace {
     uint32_t *d_err;
     LrmBsScratch bs;         // bit-sliced GACT over up to n_max reads of up to max_len bases (LRM_WS_EXTEND)
     struct LrmAnchorScratch *an;   // anchored mode (anchor_kernels.hip): allocated by its first call on this workspace
+    struct LrmSplitScratch *sp;    // split stage (split_kernels.hip): allocated by its first call with this workspace as ws_seg
 };
 
 // ---- extension stage: a table of jobs, the kernel that runs it, the bit-sliced kernel's scratch (all host only) ----------
@@ -323,6 +325,30 @@ int lrm_launch_extend_anchored(lrm_index *idx, lrm_workspace *ws, const LrmExten
                                lrm_anchor *d_anchor, uint32_t min_len, const LrmClipOpt &clip, const LrmMapTune &mt, void *stream);
 void lrm_anchor_scratch_free(lrm_workspace *ws);
 static inline uint64_t lrm_anchored_store_stride(uint32_t max_len) { return 2ull * max_len + max_len / 8 + 2; }
+// split reads (split_kernels.hip; docs/GACT_SPEC.md, "Split reads")
+int lrm_split_min_len(uint32_t m, uint32_t *out);          // 0 -> the default; -1 + message outside 50..2^20
+// the segments of read i from its length and clip counts, appended at out (room for two); returns how many.  THE rule:
+// the device kernels, lrm_split_plan and the host gather all go through it
+#if defined(__HIPCC__) && defined(__device__)
+__host__ __device__
+#endif
+static inline uint32_t lrm_split_segments(uint32_t read, uint32_t n, uint32_t cl, uint32_t cr, uint32_t M, lrm_segment *out) {
+    uint32_t k = 0;
+    if (cl > n) cl = n;                                    // (clip counts never exceed the read: keeps a bad input inside its row)
+    if (cr > n) cr = n;
+    if (cl >= M) { out[k].read = read; out[k].start = 0; out[k].len = cl; out[k].flags = 0; ++k; }
+    if (cr >= M) { out[k].read = read; out[k].start = n - cr; out[k].len = cr; out[k].flags = LRM_SEG_RIGHT; ++k; }
+    return k;
+}
+struct LrmSplitArgs {                                      // lrm_split_batch_dev after its checks
+    const char *reads; uint64_t stride; const uint32_t *lens; uint64_t n; const lrm_clip *clip;
+    uint32_t seed_len, thres; lrm_gact_params gp;
+    uint32_t anchor_min_len, clip_penalty, clip_end_bonus, split_min_len;
+};
+int lrm_launch_split(lrm_index *idx, lrm_workspace *ws_seg, const LrmSplitArgs &a, const lrm_split_dev &out, uint64_t *n_seg,
+                     void *stream);
+void lrm_split_scratch_free(lrm_workspace *ws);
+int lrm_wait_event(void *ev);                              // lrm_host.hip: the sleep-poll every host wait of this library uses
 int lrm_launch_debug_seed(lrm_index *idx, const char *d_read, uint32_t len, uint32_t seed_len,
                           uint64_t *d_reads2, uint64_t words, int32_t *d_j, uint64_t *d_rr,
                           uint64_t *d_k, uint64_t *d_l, uint64_t cap, void *stream);

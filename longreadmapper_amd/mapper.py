@@ -22,6 +22,8 @@ ANCHOR_DT = np.dtype([("text_pos", "<u8"), ("read_pos", "<u4"), ("len", "<u4"), 
                       ("flags", "<u4"), ("_pad", "V4")])      # lrm_anchor
 assert ANCHOR_DT.itemsize == 32
 CLIP_DT = np.dtype([("left", "<u4"), ("right", "<u4")])          # lrm_clip
+SEGMENT_DT = np.dtype([("read", "<u4"), ("start", "<u4"), ("len", "<u4"), ("flags", "<u4")])      # lrm_segment
+SEG_RIGHT, SEG_ALIGNED = capi.SEG_RIGHT, capi.SEG_ALIGNED
 
 
 def anchored_store_stride(max_len):
@@ -218,6 +220,112 @@ def map_batch(index, reads, lens, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES
     return dict(best=best, ops=store, n_ops=n_ops, score=score, meta=meta, meta_r=meta_r)
 
 
+def split_plan(lens, clip, split_min_len=0, cap=None):
+    """lrm_split_plan: the segment table (SEGMENT_DT) of a batch from its read lengths and lrm_clip records; pure host.
+    cap=None: room for every segment; otherwise -> (rc, n_seg, table) without raising on rc == -3."""
+    lens = np.ascontiguousarray(lens, dtype=np.uint32)
+    clip = np.ascontiguousarray(clip, dtype=CLIP_DT)
+    n = len(lens)
+    room = 2 * n if cap is None else cap
+    seg = np.zeros(max(room, 1), dtype=SEGMENT_DT)
+    k = C.c_uint64()
+    rc = lib.lrm_split_plan(lens.ctypes.data, clip.ctypes.data, n, split_min_len, seg.ctypes.data if room else None, room,
+                            C.byref(k))
+    if cap is None:
+        check(rc, "lrm_split_plan")
+        return seg[:k.value].copy()
+    return rc, int(k.value), seg[:min(k.value, room)].copy()
+
+
+def clip_of_cigar(ops_or_text, is_text=False):
+    """lrm_clip_of_cigar of one alignment: op bytes, or (is_text) its run-length text -> (left, right)."""
+    data = bytes(ops_or_text)
+    buf = C.create_string_buffer(data, len(data) + 1)
+    n_ops = len(data) if not is_text else (0 if data == b"*" else 1)
+    cg = capi.Cigar(C.cast(buf, capi.u8p), n_ops, 0)
+    left, right = C.c_uint32(), C.c_uint32()
+    check(lib.lrm_clip_of_cigar(C.byref(cg), int(is_text), C.byref(left), C.byref(right)), "lrm_clip_of_cigar")
+    return int(left.value), int(right.value)
+
+
+class SplitBuffers:
+    """Host arrays of an lrm_split_out for up to cap segments of up to max_seg bases."""
+
+    def __init__(self, cap, max_seg):
+        self.cap = cap
+        self.row_stride = (max_seg + 16) // 16 * 16
+        self.store_stride = (anchored_store_stride(max_seg) + 15) // 16 * 16
+        k = max(cap, 1)
+        self.seg = np.zeros(k, dtype=SEGMENT_DT)
+        self.rows = np.zeros((k, self.row_stride), dtype=np.uint8)
+        self.lens = np.zeros(k, dtype=np.uint32)
+        self.best = np.zeros(k, dtype=ENTRY_DT)
+        self.cig = (capi.Cigar * k)()
+        self.store = np.zeros((k, self.store_stride), dtype=np.uint8)
+        self.score = np.zeros(k, dtype=np.int32)
+        self.meta = np.zeros(k, dtype=META_DT)
+        self.meta_r = np.zeros(k, dtype=np.int32)
+        self.anchor = np.zeros(k, dtype=ANCHOR_DT)
+        self.clip = np.zeros(k, dtype=CLIP_DT)
+        self.out = capi.SplitOut(cap, 0, self.seg.ctypes.data, self.rows.ctypes.data, self.row_stride, self.lens.ctypes.data,
+                                 self.best.ctypes.data, C.cast(self.cig, C.c_void_p), self.store.ctypes.data, self.store_stride,
+                                 self.score.ctypes.data, self.meta.ctypes.data, self.meta_r.ctypes.data, self.anchor.ctypes.data,
+                                 self.clip.ctypes.data)
+
+    def result(self, dense, text):
+        k = int(self.out.n_seg)
+        cv = np.ctypeslib.as_array(C.cast(self.cig, C.POINTER(C.c_int32)), shape=(max(self.cap, 1), 4))[:k]
+        res = dict(seg=self.seg[:k], rows=self.rows[:k], lens=self.lens[:k], best=self.best[:k], ops=self.store, n_ops=cv[:, 2].copy(),
+                   score=self.score[:k], meta=self.meta[:k], meta_r=self.meta_r[:k], anchor=self.anchor[:k], clip=self.clip[:k],
+                   is_text=text, buffers=self)
+        if dense:
+            ptr = np.ctypeslib.as_array(C.cast(self.cig, C.POINTER(C.c_uint64)), shape=(max(self.cap, 1), 2))[:k, 0]
+            res["ops_off"] = (ptr - np.uint64(self.store.ctypes.data)).astype(np.int64)
+        return res
+
+
+def _cigars_of(res, n):
+    """lrm_cigar array that points into a map_batch result, as the C caller would still hold it."""
+    cig = (capi.Cigar * max(n, 1))()
+    base = res["ops"].ctypes.data
+    stride = res["ops"].shape[1] if res["ops"].ndim == 2 else 0
+    for i in range(n):
+        off = int(res["ops_off"][i]) if "ops_off" in res else i * stride
+        cig[i].cigar = C.cast(C.c_void_p(base + off), capi.u8p)
+        cig[i].n_cigar_op = int(res["n_ops"][i])
+        cig[i].score = int(res["score"][i])
+    return cig
+
+
+def split_batch(index, reads, lens, res, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT, options=None,
+                anchor_min_len=0, clip_penalty=0, clip_end_bonus=0, split_min_len=0, cap=None, buffers=None):
+    """lrm_split_batch: the second pass over `res`, what map_batch(index, reads, lens, clip=True, ...) returned for `reads`
+    (as that call left them), with the same options.  -> dict(seg=SEGMENT_DT table, rows, lens, best, ops, n_ops, score, meta,
+    meta_r, anchor, clip [, ops_off]); ops_of / text_of read a segment's alignment like a read's.  cap: room for that many
+    segments (None: for every possible one); more raise LrmError, the count is in .n_seg of the exception."""
+    reads = np.ascontiguousarray(reads, dtype=np.uint8)
+    lens = np.ascontiguousarray(lens, dtype=np.uint32)
+    n, stride = reads.shape
+    options = _anchor_options(options, True, anchor_min_len, True, clip_penalty, clip_end_bonus)
+    options = {**options, "split": 1, "split_min_len": split_min_len}
+    opt = capi.map_options(**options)
+    text = bool(opt.cigar_text)
+    dense = bool(opt.dense_results) or text
+    if buffers is None:
+        buffers = SplitBuffers(2 * n if cap is None else cap, int(lens.max()) if n else 0)
+    cig = _cigars_of(res, n)
+    meta = np.ascontiguousarray(res["meta"], dtype=META_DT)
+    meta_r = np.ascontiguousarray(res["meta_r"], dtype=np.int32)
+    rc = lib.lrm_split_batch(index.handle, reads.ctypes.data, stride, lens.ctypes.data, n, C.cast(cig, C.c_void_p), meta.ctypes.data,
+                             meta_r.ctypes.data, capi.Params(n, seed_len, thres), capi.GactParams(*gact), C.byref(opt),
+                             C.byref(buffers.out))
+    if rc < 0:
+        e = capi.LrmError("lrm_split_batch: " + lib.lrm_last_error().decode(errors="replace"))
+        e.rc, e.n_seg = rc, int(buffers.out.n_seg)
+        raise e
+    return buffers.result(dense, text)
+
+
 def result_flags(score, meta_r, meta):
     n = len(score)
     flag = np.zeros(n, dtype=np.int32)
@@ -236,7 +344,12 @@ class DeviceMapper:
     current stream (so torch.cuda.Event brackets them)."""
 
     def __init__(self, index, n_max, max_len, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT,
-                 device=0, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0):
+                 device=0, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0, split=False,
+                 split_min_len=0, seg_cap=None, seg_rows=None):
+        """split (needs clip): split() after extend() maps the soft-clipped ends of at least split_min_len bases (0 = 200) as
+        reads of their own (lrm_split_batch_dev), results() returns them as res["split"].  seg_cap: room for that many
+        segments (None: 2 * n_max, every possible one); seg_rows: rows of the segment workspace (None: min(seg_cap, n_max);
+        0: no workspace of its own -- the primary's is used a second time); more segments than rows run in chunks."""
         import torch
         self.torch = torch
         self.index = index
@@ -261,6 +374,28 @@ class DeviceMapper:
         self.meta_r = torch.zeros(n_max, dtype=torch.int32, device=self.dev)
         self.anchor = torch.zeros((n_max, 32), dtype=torch.uint8, device=self.dev) if anchored else None     # lrm_anchor
         self.clip = torch.zeros((n_max, 2), dtype=torch.int32, device=self.dev) if clip else None           # lrm_clip
+        self.split_on, self.split_min_len, self.ws_seg, self.n_seg = bool(split), split_min_len, None, 0
+        if split:
+            if not clip:
+                raise capi.LrmError("DeviceMapper: split needs clip")
+            cap = self.seg_cap = 2 * n_max if seg_cap is None else seg_cap
+            rows = min(cap, n_max) if seg_rows is None else seg_rows
+            if rows:
+                wseg = C.c_void_p()
+                check(lib.lrm_workspace_create(C.byref(wseg), index.handle, rows, max_len, seed_len, thres), "lrm_workspace_create")
+                self.ws_seg = wseg
+            k = max(cap, 1)
+            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.dev)
+            self.seg_row_stride = (max_len + 16) // 16 * 16
+            self.seg = dict(seg=z((k, 4), torch.int32), rows=z((k, self.seg_row_stride), torch.uint8), lens=z(k, torch.int32),
+                            best=z((k, 3), torch.int64), store=z((k, self.store_stride), torch.uint8), n_ops=z(k, torch.int32),
+                            score=z(k, torch.int32), meta=z((k, 24), torch.uint8), meta_r=z(k, torch.int32),
+                            anchor=z((k, 32), torch.uint8), clip=z((k, 2), torch.int32))
+            g = self.seg
+            self.split_dev = capi.SplitDev(cap, g["seg"].data_ptr(), g["rows"].data_ptr(), self.seg_row_stride, g["lens"].data_ptr(),
+                                           g["best"].data_ptr(), g["store"].data_ptr(), self.store_stride, g["n_ops"].data_ptr(),
+                                           g["score"].data_ptr(), g["meta"].data_ptr(), g["meta_r"].data_ptr(),
+                                           g["anchor"].data_ptr(), g["clip"].data_ptr())
 
     def workspace_bytes(self):
         return int(lib.lrm_workspace_bytes(self.ws))
@@ -301,6 +436,43 @@ class DeviceMapper:
                                        self.score.data_ptr(), self.meta.data_ptr(), self.meta_r.data_ptr(),
                                        self._stream()), "lrm_extend_batch_dev")
 
+    def split(self, d_reads, d_lens, n=None):
+        """lrm_split_batch_dev after extend() on the same stream -> number of segments (the call waits for that count).
+        More than seg_cap raise LrmError with .rc == -3 and .n_seg."""
+        assert self.split_on
+        n = d_reads.shape[0] if n is None else n
+        k = C.c_uint64()
+        rc = lib.lrm_split_batch_dev(self.index.handle, self.ws_seg or self.ws, d_reads.data_ptr(), d_reads.stride(0), d_lens.data_ptr(),
+                                     n, self.clip.data_ptr(), capi.Params(n, self.seed_len, self.thres), capi.GactParams(*self.gact),
+                                     self.anchor_min_len, self.clip_penalty, self.clip_end_bonus, self.split_min_len,
+                                     C.byref(self.split_dev), C.byref(k), self._stream())
+        self.n_seg = int(k.value) if rc >= 0 else 0
+        if rc < 0:
+            e = capi.LrmError("lrm_split_batch_dev: " + lib.lrm_last_error().decode(errors="replace"))
+            e.rc, e.n_seg = rc, int(k.value)
+            raise e
+        return self.n_seg
+
+    def seg_timing(self):
+        """timing() of the segment workspace (the split stage's own kernels are in the revcomp_kernel slot)."""
+        ms = np.zeros(N_KERNELS, dtype=np.float64)
+        launches = np.zeros(N_KERNELS, dtype=np.uint64)
+        check(lib.lrm_workspace_timing(self.ws_seg or self.ws, ms.ctypes.data, launches.ctypes.data, self._stream()),
+              "lrm_workspace_timing")
+        return {lib.lrm_kernel_name(i).decode(): (float(ms[i]), int(launches[i])) for i in range(N_KERNELS)}
+
+    def split_results(self):
+        """The outputs of the last split() as numpy arrays (same keys as split_batch, `ops` in rows)."""
+        k, g = self.n_seg, self.seg
+        h = {name: t[:k].cpu().numpy() for name, t in g.items()}
+        best = np.zeros(k, dtype=ENTRY_DT)
+        b = h["best"].view(np.uint64).reshape(k, 3)
+        best["key"], best["val"], best["bucket"] = b[:, 0], b[:, 1], b[:, 2]
+        return dict(seg=h["seg"].reshape(-1).view(SEGMENT_DT), rows=h["rows"], lens=h["lens"].view(np.uint32), best=best,
+                    ops=h["store"], n_ops=h["n_ops"], score=h["score"], meta=h["meta"].reshape(-1).view(META_DT),
+                    meta_r=h["meta_r"], anchor=h["anchor"].reshape(-1).view(ANCHOR_DT), clip=h["clip"].reshape(-1).view(CLIP_DT),
+                    is_text=False)
+
     def stats(self):
         st = capi.Stats()
         check(lib.lrm_workspace_stats(self.ws, C.byref(st), self._stream()), "lrm_workspace_stats")
@@ -336,9 +508,14 @@ class DeviceMapper:
             res["anchor"] = self.anchor[:n].cpu().numpy().reshape(-1).view(ANCHOR_DT)
         if self.clip_on:
             res["clip"] = self.clip[:n].cpu().numpy().reshape(-1).view(CLIP_DT)
+        if self.split_on:
+            res["split"] = self.split_results()
         return res
 
     def close(self):
+        if getattr(self, "ws_seg", None):
+            lib.lrm_workspace_free(self.ws_seg)
+            self.ws_seg = None
         if self.ws:
             lib.lrm_workspace_free(self.ws)
             self.ws = None
