@@ -20,7 +20,7 @@
  *     alnmain.c:302-330, 420-424 (batches overlap on the device)
  *   params (run-time options), alnmain.h:10-13,                  lrm_index_options / lrm_map_options
  *     alnmain.c:574-588
- *   PART 3 result flags, alnmain.c:458-477                      lrm_result_flags
+ *   PART 3 result flags, alnmain.c:458-477                      lrm_result_flags (lrm_result_flags_mapq: a real MAPQ)
  *   context_destroy(), accaln.c:7-43                            lrm_index_free
  *   host batch loop over devices, alnmain.c:302-330             lrm_index_upload_multi (+ the same batch calls)
  *   pair_end(), alnmain.c:554-557 (unimplemented, returns -1)   lrm_pair_end
@@ -334,6 +334,26 @@ int lrm_pair_end(int argc, const char *argv[]);
 void lrm_result_flags(const int *score, const int *meta_r, const lrm_seq_meta *meta,
                       uint64_t n, int *flag_out, int *mapq_out, int *valid_out);
 
+/* MAPPING QUALITY (docs/GACT_SPEC.md, "Mapping quality").  The reference prints MAPQ 255 for every mapped read
+ * (alnmain.c:460-474); this is a choice of THIS implementation, and it is asked for per CALL -- the entry points that take an
+ * lrm_mapq array compute the records when they are given one, every other output is the same with it or without it --
+ * not through lrm_map_options: that struct has no spare words left and keeps its 76 bytes.  Per read: n1 = the seed hits (phases up to the
+ * deciding one) within `radius` diagonals of the chosen locus, n2 = the most hits any other place of width <= radius
+ * collected, mapq = 60 * (n1 - min(n2, n1)) * min(n1, 10) / (10 * n1).  A read without a locus (best.val == 0): all zeros. */
+#define LRM_MAPQ_SLOTS 4096            /* distinct (histogram, bucket) pairs of rival hits one read can hold */
+#define LRM_MAPQ_OVERFLOW 1u           /* lrm_mapq.flags: more distinct rival places than slots -- a repeat read: n2 = n1, mapq 0 */
+typedef struct lrm_mapq { uint32_t n1, n2, radius; uint8_t mapq, phase, flags, pad; } lrm_mapq;   /* 16 bytes; phase: the deciding one */
+/* lrm_result_flags with the records: mapq_out[i] = mq[i].mapq for a mapped read, 0 for an unmapped one.  mq == NULL:
+ * lrm_result_flags. */
+void lrm_result_flags_mapq(const int *score, const int *meta_r, const lrm_seq_meta *meta, const lrm_mapq *mq, uint64_t n,
+                           int *flag_out, int *mapq_out, int *valid_out);
+/* lrm_map_batch_submit plus the records of the batch (mapq_out: n entries, filled when the wait returns; group handles write
+ * every share in place).  mapq_out == NULL: lrm_map_batch_submit. */
+int lrm_map_batch_submit_mapq(lrm_index *idx, char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
+                              lrm_params p, lrm_gact_params gp, lrm_entry *best_out, lrm_cigar *cig_out,
+                              uint8_t *store_mem, uint64_t store_stride, int *score_out, lrm_seq_meta *meta_out,
+                              int *meta_r_out, const lrm_map_options *opt, lrm_mapq *mapq_out, lrm_ticket **ticket_out);
+
 /* ---------------------------------------------------------------------------
  * Batch entry points with DEVICE buffers (inputs/outputs resident in HBM;
  * asynchronous on `stream`, a hipStream_t passed as void*, may be NULL).
@@ -353,6 +373,13 @@ uint64_t lrm_workspace_bytes(const lrm_workspace *ws);
 int lrm_seed_batch_dev(lrm_index *idx, lrm_workspace *ws, const char *d_reads,
                        uint64_t stride, const uint32_t *d_lens, uint64_t n,
                        uint32_t max_len, lrm_params p, lrm_entry *d_best, void *stream);
+
+/* lrm_seed_batch_dev plus the mapping-quality records (d_mapq: n entries in device memory; NULL: lrm_seed_batch_dev).  The
+ * stage runs right behind the seed stage on the same stream, over the survivor lists that stage left in the workspace.  The
+ * first such call on a workspace allocates one byte per read (the deciding phase); lrm_workspace_bytes grows by it. */
+int lrm_seed_batch_mapq_dev(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint64_t stride,
+                            const uint32_t *d_lens, uint64_t n, uint32_t max_len, lrm_params p,
+                            lrm_entry *d_best, lrm_mapq *d_mapq, void *stream);
 
 int lrm_extend_batch_dev(lrm_index *idx, lrm_workspace *ws, char *d_reads, uint64_t stride,
                          const uint32_t *d_lens, uint64_t n, uint32_t max_len,
@@ -517,6 +544,10 @@ int lrm_debug_seed_search(lrm_index *idx, const char *read, uint32_t len, uint32
 /* Test-only: force the multi-pass vote tier of this handle's batches into overflow (a pass limit above the table size
  * and a small table); 0, 0 restores the defaults. */
 int lrm_debug_set_vote_limits(lrm_index *idx, uint32_t t3_limit, uint32_t t3_slots);
+
+/* Test-only: the mapping-quality stage of this handle's batches (every replica) uses a rival table of `slots` slots: 0 =
+ * LRM_MAPQ_SLOTS, else a power of two 16..LRM_MAPQ_SLOTS -- a small table forces LRM_MAPQ_OVERFLOW. */
+int lrm_debug_set_mapq_slots(lrm_index *idx, uint32_t slots);
 
 /* Tuning sessions only (tools/): re-read the LRM_* overrides for the batch calls of this handle (normally they are
  * read once, when the handle is created). */

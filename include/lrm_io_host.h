@@ -5,7 +5,7 @@
  *
  *   reads_load + refactor_reads_seq   accaln.c:45-58, alnmain.c:87-103   -> lrm_reader_*
  *   gen_sam_header                    alnmain.c:62-75                    -> lrm_sam_header
- *   SAM record printing               alnmain.c:485-527                  -> lrm_sam_format
+ *   SAM record printing               alnmain.c:485-527                  -> lrm_sam_format (_split, _mapq)
  *   parse_cigar (gact submodule, source absent; PARITY UNPINNED)         -> lrm_parse_cigar
  *   single_end                        alnmain.c:277-551                  -> lrm_accaln
  */
@@ -71,6 +71,13 @@ char *lrm_sam_format(const lrm_read_batch *reads, const lrm_mta_entry *mta, int 
 char *lrm_sam_format_split(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig,
                            const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t n, int cigar_is_text,
                            int revcomp_here, const lrm_split_out *split, uint64_t *len_out);
+/* The same with MAPPING QUALITY (docs/GACT_SPEC.md, "Mapping quality"): mq is what lrm_map_batch_submit_mapq returned for this
+ * batch (NULL: exactly the lines of lrm_sam_format_split).  Column 5 of a mapped read is mq[i].mapq instead of 255, every
+ * read's line gains v1:i:<n1>\tv2:i:<n2> behind ED:I, and the primary's entry inside the SA:Z of its supplementary lines
+ * carries the primary's MAPQ.  The split segments have no records: their lines and their own SA:Z entries keep 255. */
+char *lrm_sam_format_mapq(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig,
+                          const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t n, int cigar_is_text,
+                          int revcomp_here, const lrm_split_out *split, const lrm_mapq *mq, uint64_t *len_out);
 void lrm_free(void *p);
 
 /* `accaln genome reads [batch seed_len thres]` on the GPU path: loads the index files next to
@@ -85,6 +92,12 @@ int lrm_accaln(const char *genome, const char *reads_path, const char *sam_path,
 int lrm_accaln_opt(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
                    lrm_gact_params gp, int device, long rg_id, uint64_t *total, uint64_t *valid,
                    const lrm_map_options *opt);
+/* ... with MAPPING QUALITY (docs/GACT_SPEC.md, "Mapping quality"; mapq == 0: lrm_accaln_opt): every batch goes through
+ * lrm_map_batch_submit_mapq and is printed by lrm_sam_format_mapq -- column 5 is the record's MAPQ instead of 255, v1:i / v2:i
+ * follow ED:I.  The flag travels next to the options, not inside them: lrm_map_options keeps its size. */
+int lrm_accaln_mapq(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
+                    lrm_gact_params gp, int device, long rg_id, uint64_t *total, uint64_t *valid,
+                    const lrm_map_options *opt, int mapq);
 
 #ifdef __cplusplus
 }

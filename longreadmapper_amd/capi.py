@@ -120,6 +120,12 @@ class SplitOut(C.Structure):           # lrm_split_out (host pointers)
                 ("anchor", C.c_void_p), ("clip", C.c_void_p)]
 
 
+class Mapq(C.Structure):               # lrm_mapq
+    _fields_ = [("n1", C.c_uint32), ("n2", C.c_uint32), ("radius", C.c_uint32), ("mapq", C.c_uint8), ("phase", C.c_uint8),
+                ("flags", C.c_uint8), ("pad", C.c_uint8)]
+
+
+MAPQ_SLOTS, MAPQ_OVERFLOW = 4096, 1    # LRM_MAPQ_SLOTS, LRM_MAPQ_OVERFLOW (lrm_mapq.flags)
 SEG_RIGHT, SEG_ALIGNED = 1, 2          # lrm_segment.flags
 SPLIT_MIN_DEFAULT = 200                # LRM_SPLIT_MIN_DEFAULT
 ANCHOR_ANCHORED, ANCHOR_FALLBACK, ANCHOR_NO_LEFT, ANCHOR_LEFT_CLIPPED, ANCHOR_RIGHT_CLIPPED = 1, 2, 4, 8, 16
@@ -146,6 +152,7 @@ class HostIndex(C.Structure):          # lrm_index_host.h
 
 assert C.sizeof(Ui40) == 8 and C.sizeof(Entry) == 24 and C.sizeof(SeqMeta) == 24
 assert C.sizeof(MapOptions) == 76 and C.sizeof(Anchor) == 32 and C.sizeof(Clip) == 8
+assert C.sizeof(Mapq) == 16
 assert MapOptions.split.offset == 68 and C.sizeof(Segment) == 16 and C.sizeof(SplitDev) == 112 and C.sizeof(SplitOut) == 120
 
 # every symbol include/*.h declares: (restype, argtypes)
@@ -181,9 +188,13 @@ SYMBOLS = {
     "lrm_map_batch_submit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, Params, GactParams,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.POINTER(MapOptions), C.POINTER(C.c_void_p)]),
+    "lrm_map_batch_submit_mapq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, Params, GactParams,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(MapOptions), C.c_void_p, C.POINTER(C.c_void_p)]),
     "lrm_map_batch_wait": (C.c_int, [C.c_void_p]),
     "lrm_debug_reload_env": (C.c_int, [C.c_void_p]),
     "lrm_debug_set_vote_limits": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "lrm_debug_set_mapq_slots": (C.c_int, [C.c_void_p, C.c_uint32]),
     "lrm_debug_gact_impl": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, GactParams, C.c_int, C.c_void_p,
                                       C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
     "lrm_index_adopt_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_uint64, C.c_int]),
@@ -206,12 +217,16 @@ SYMBOLS = {
     "lrm_index_replicas": (C.c_int, [C.c_void_p]),
     "lrm_index_replica": (C.c_void_p, [C.c_void_p, C.c_int]),
     "lrm_result_flags": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lrm_result_flags_mapq": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
     "lrm_workspace_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                        C.c_uint32]),
     "lrm_workspace_free": (None, [C.c_void_p]),
     "lrm_workspace_bytes": (C.c_uint64, [C.c_void_p]),
     "lrm_seed_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                      C.c_uint32, Params, C.c_void_p, C.c_void_p]),
+    "lrm_seed_batch_mapq_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                          C.c_uint32, Params, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lrm_extend_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                        C.c_uint32, C.c_void_p, GactParams, C.c_void_p, C.c_uint64, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -271,10 +286,14 @@ SYMBOLS = {
                                     C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
     "lrm_sam_format_split": (C.c_void_p, [C.POINTER(ReadBatch), C.POINTER(MtaEntry), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(SplitOut), u64p]),
+    "lrm_sam_format_mapq": (C.c_void_p, [C.POINTER(ReadBatch), C.POINTER(MtaEntry), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(SplitOut), C.c_void_p, u64p]),
     "lrm_free": (None, [C.c_void_p]),
     "lrm_accaln": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, Params, GactParams, C.c_int, C.c_long, u64p, u64p]),
     "lrm_accaln_opt": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, Params, GactParams, C.c_int, C.c_long, u64p, u64p,
                                  C.POINTER(MapOptions)]),
+    "lrm_accaln_mapq": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, Params, GactParams, C.c_int, C.c_long, u64p, u64p,
+                                  C.POINTER(MapOptions), C.c_int]),
 }
 
 

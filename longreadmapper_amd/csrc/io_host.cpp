@@ -563,9 +563,9 @@ static AlnShape aln_shape(const lrm_cigar &c, bool is_text) {
 }
 static inline void put_num(std::string &s, uint64_t v) { char num[24]; s.append(num, (size_t) put_uint(num, v)); }
 static inline void put_int(std::string &s, int64_t v) { if (v < 0) { s += '-'; put_num(s, (uint64_t) -v); } else put_num(s, (uint64_t) v); }
-// one SA:Z entry: rname,pos,strand,<c5>S<q>M<d>D|I<c3>S,255,ED;
+// one SA:Z entry: rname,pos,strand,<c5>S<q>M<d>D|I<c3>S,<mapq>,ED;  (mapq: 255 without a record -- the split segments have none)
 static void sa_entry(std::string &s, const lrm_mta_entry *mta, int mta_len, const lrm_seq_meta &m, bool rev, uint64_t c5,
-                     const AlnShape &a, uint64_t c3, int ed) {
+                     const AlnShape &a, uint64_t c3, int ed, unsigned mapq = 255) {
     if (m.seq_id >= 0 && m.seq_id < mta_len) s.append(mta[m.seq_id].name, mta[m.seq_id].name_len); else s += '*';
     s += ','; put_num(s, m.off + 1); s += ','; s += rev ? '-' : '+'; s += ',';
     if (c5) { put_num(s, c5); s += 'S'; }
@@ -573,7 +573,7 @@ static void sa_entry(std::string &s, const lrm_mta_entry *mta, int mta_len, cons
     if (a.t > a.q) { put_num(s, a.t - a.q); s += 'D'; }
     if (a.q > a.t) { put_num(s, a.q - a.t); s += 'I'; }
     if (c3) { put_num(s, c3); s += 'S'; }
-    s += ",255,"; put_int(s, ed); s += ';';
+    s += ','; put_num(s, mapq); s += ','; put_int(s, ed); s += ';';
 }
 struct SplitCtx {                                  // a batch's segments, and where those of read i begin (first[i] .. first[i + 1])
     const lrm_split_out *sp;
@@ -591,7 +591,8 @@ static inline void seg_hard(const lrm_segment &g, uint32_t n, bool ss, uint64_t 
 }
 // SA:Z of read i's primary (tail of its line) and its supplementary lines
 static void sam_split_lines(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig, const int *score,
-                            const lrm_seq_meta *meta, uint64_t i, const SplitCtx &sx, bool cigar_is_text, std::string &s) {
+                            const lrm_seq_meta *meta, uint64_t i, const SplitCtx &sx, bool cigar_is_text, std::string &s,
+                            const lrm_mapq *mq) {
     const lrm_split_out &o = *sx.sp;
     uint64_t rep[2];
     int nrep = 0;
@@ -641,7 +642,7 @@ static void sam_split_lines(const lrm_read_batch *reads, const lrm_mta_entry *mt
         } else s += '*';
         s += "\tED:I:"; put_int(s, o.score[x]);
         s += "\tSA:Z:";
-        sa_entry(s, mta, mta_len, meta[i], ps, pa.sl, pa, pa.sr, score[i]);
+        sa_entry(s, mta, mta_len, meta[i], ps, pa.sl, pa, pa.sr, score[i], mq ? mq[i].mapq : 255u);
         if (nrep == 2) seg_entry(1 - k);
         s += '\n';
     }
@@ -652,7 +653,8 @@ static void sam_split_lines(const lrm_read_batch *reads, const lrm_mta_entry *mt
 // cigar_is_text: cig[i].cigar is the NUL-terminated run-length text already (lrm_map_options.cigar_text), not op bytes.
 static void sam_format_range(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig,
                              const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t lo, uint64_t hi,
-                             std::string &s, bool cigar_is_text, bool revcomp_here, const SplitCtx *sx = nullptr) {
+                             std::string &s, bool cigar_is_text, bool revcomp_here, const SplitCtx *sx = nullptr,
+                             const lrm_mapq *mq = nullptr) {
     uint64_t est = 0;
     for (uint64_t i = lo; i < hi; ++i) est += 2ull * reads->lens[i] + 2ull * (cig[i].n_cigar_op > 0 ? (uint64_t) cig[i].n_cigar_op : 0) + 160;
     s.clear();
@@ -664,6 +666,7 @@ static void sam_format_range(const lrm_read_batch *reads, const lrm_mta_entry *m
         int flag = 0, mapq = 255;
         if (unmapped) { flag += 0x4; mapq = 0; }
         else if (meta[i].strand == 1) flag += 16;
+        if (mq && !unmapped) mapq = mq[i].mapq;                      // mapping quality: the record's value instead of 255
         s += reads->names[i];
         s += '\t';
         s.append(num, (size_t) put_uint(num, (uint64_t) flag));
@@ -701,7 +704,11 @@ static void sam_format_range(const lrm_read_batch *reads, const lrm_mta_entry *m
         s += "\tED:I:";
         if (score[i] < 0) { s += '-'; s.append(num, (size_t) put_uint(num, (uint64_t) (-(int64_t) score[i]))); }
         else s.append(num, (size_t) put_uint(num, (uint64_t) score[i]));
-        if (sx && !unmapped) sam_split_lines(reads, mta, mta_len, cig, score, meta, i, *sx, cigar_is_text, s);
+        if (mq) {                                                      // the two vote counts behind the MAPQ
+            s += "\tv1:i:"; s.append(num, (size_t) put_uint(num, mq[i].n1));
+            s += "\tv2:i:"; s.append(num, (size_t) put_uint(num, mq[i].n2));
+        }
+        if (sx && !unmapped) sam_split_lines(reads, mta, mta_len, cig, score, meta, i, *sx, cigar_is_text, s, mq);
         else s += '\n';
     }
 }
@@ -710,28 +717,34 @@ static void sam_format_range(const lrm_read_batch *reads, const lrm_mta_entry *m
 static void sam_format_parts(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig,
                              const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t n, int nt,
                              std::vector<std::string> &parts, bool cigar_is_text = false, bool revcomp_here = false,
-                             const SplitCtx *sx = nullptr) {
+                             const SplitCtx *sx = nullptr, const lrm_mapq *mq = nullptr) {
     if (nt < 1) nt = 1;
     if ((uint64_t) nt > n) nt = n ? (int) n : 1;
     parts.resize((size_t) nt);
 #pragma omp parallel for schedule(static, 1) num_threads(nt)
     for (int t = 0; t < nt; ++t)
         sam_format_range(reads, mta, mta_len, cig, score, meta, meta_r, n * (uint64_t) t / (uint64_t) nt, n * (uint64_t) (t + 1) / (uint64_t) nt,
-                         parts[(size_t) t], cigar_is_text, revcomp_here, sx);
+                         parts[(size_t) t], cigar_is_text, revcomp_here, sx, mq);
 }
 
 static char *sam_join(std::vector<std::string> &parts, uint64_t *len_out);
+extern "C" char *lrm_sam_format_mapq(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig,
+                                     const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t n, int cigar_is_text,
+                                     int revcomp_here, const lrm_split_out *split, const lrm_mapq *mq, uint64_t *len_out) {
+    std::vector<std::string> parts;
+    if (!split || split->n_seg == 0) {
+        sam_format_parts(reads, mta, mta_len, cig, score, meta, meta_r, n, lrm_host_threads(), parts, cigar_is_text != 0, revcomp_here != 0,
+                         nullptr, mq);
+    } else {
+        const SplitCtx sx(split, n);
+        sam_format_parts(reads, mta, mta_len, cig, score, meta, meta_r, n, lrm_host_threads(), parts, cigar_is_text != 0, revcomp_here != 0, &sx, mq);
+    }
+    return sam_join(parts, len_out);
+}
 extern "C" char *lrm_sam_format_split(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig,
                                       const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t n, int cigar_is_text,
                                       int revcomp_here, const lrm_split_out *split, uint64_t *len_out) {
-    std::vector<std::string> parts;
-    if (!split || split->n_seg == 0) {
-        sam_format_parts(reads, mta, mta_len, cig, score, meta, meta_r, n, lrm_host_threads(), parts, cigar_is_text != 0, revcomp_here != 0);
-    } else {
-        const SplitCtx sx(split, n);
-        sam_format_parts(reads, mta, mta_len, cig, score, meta, meta_r, n, lrm_host_threads(), parts, cigar_is_text != 0, revcomp_here != 0, &sx);
-    }
-    return sam_join(parts, len_out);
+    return lrm_sam_format_mapq(reads, mta, mta_len, cig, score, meta, meta_r, n, cigar_is_text, revcomp_here, split, nullptr, len_out);
 }
 
 extern "C" char *lrm_sam_format(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len,
@@ -812,6 +825,7 @@ struct BatchSet {
     std::vector<lrm_seq_meta> sp_meta;
     std::vector<lrm_anchor> sp_anchor;
     std::vector<lrm_clip> sp_clip;
+    std::vector<lrm_mapq> mq;                    // lrm_accaln_mapq: the records of the batch
     BatchSet() { memset(&b, 0, sizeof(b)); memset(&split, 0, sizeof(split)); }
     ~BatchSet() { lrm_host_free(reads_pin); lrm_host_free(store_pin); free(store_pg); }
 };
@@ -842,9 +856,23 @@ extern "C" int lrm_accaln(const char *genome, const char *reads_path, const char
 
 // user: only the fields that change WHAT is computed are taken (anchored, anchor_min_len, clip, clip_penalty, clip_end_bonus);
 // the shape of the pipeline is this function's own choice
+static int accaln_impl(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
+                       lrm_gact_params gp, int device, long rg_id, uint64_t *total_out, uint64_t *valid_out,
+                       const lrm_map_options *user, bool mapq);
 extern "C" int lrm_accaln_opt(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
                               lrm_gact_params gp, int device, long rg_id, uint64_t *total_out, uint64_t *valid_out,
                               const lrm_map_options *user) {
+    return accaln_impl(genome, reads_path, sam_path, p, gp, device, rg_id, total_out, valid_out, user, false);
+}
+// mapq: the mapping-quality records come back with every batch, column 5 and v1:i / v2:i print them (lrm_sam_format_mapq)
+extern "C" int lrm_accaln_mapq(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
+                               lrm_gact_params gp, int device, long rg_id, uint64_t *total_out, uint64_t *valid_out,
+                               const lrm_map_options *user, int mapq) {
+    return accaln_impl(genome, reads_path, sam_path, p, gp, device, rg_id, total_out, valid_out, user, mapq != 0);
+}
+static int accaln_impl(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
+                       lrm_gact_params gp, int device, long rg_id, uint64_t *total_out, uint64_t *valid_out,
+                       const lrm_map_options *user, bool mapq) {
     const bool anchored = user && user->struct_size >= offsetof(lrm_map_options, anchor_min_len) + sizeof(uint32_t) && user->anchored;
     // (a caller built before the clip fields existed has them inside its zeroed reserved words or not at all)
     const bool clip = user && user->struct_size >= offsetof(lrm_map_options, clip_end_bonus) + sizeof(uint32_t) && user->clip;
@@ -998,10 +1026,10 @@ extern "C" int lrm_accaln_opt(const char *genome, const char *reads_path, const 
                     if (split && s->split.n_seg) {
                         const SplitCtx sx(&s->split, n);
                         sam_format_parts(&s->b, hi.mta, hi.mta_len, s->cig.data(), s->score.data(), s->meta.data(), s->meta_r.data(), n,
-                                         io_threads, tb->parts, /* cigar_is_text */ true, /* revcomp_here */ true, &sx);
+                                         io_threads, tb->parts, /* cigar_is_text */ true, /* revcomp_here */ true, &sx, mapq ? s->mq.data() : nullptr);
                     } else
                     sam_format_parts(&s->b, hi.mta, hi.mta_len, s->cig.data(), s->score.data(), s->meta.data(), s->meta_r.data(), n,
-                                     io_threads, tb->parts, /* cigar_is_text */ true, /* revcomp_here */ true);
+                                     io_threads, tb->parts, /* cigar_is_text */ true, /* revcomp_here */ true, nullptr, mapq ? s->mq.data() : nullptr);
                     t_fmt += now() - t0;
                     if (verbose) fprintf(stderr, "[lrm accaln] %.3f formatted %llu reads in %.3f s\n", now() - t_upload, (unsigned long long) n, now() - t0);
                     total += n;
@@ -1059,6 +1087,7 @@ extern "C" int lrm_accaln_opt(const char *genome, const char *reads_path, const 
             if (err.get()) { lrm_read_batch_free(&s->b); BatchSet *q = s; free_sets.push(std::move(q)); continue; }   // drain what the loader already parsed
             const size_t n = (size_t) s->b.n;
             s->best.resize(n); s->cig.resize(n); s->score.resize(n); s->meta_r.resize(n); s->meta.resize(n);
+            if (mapq) s->mq.resize(n);
             s->sstride = store_stride_of(s->b.max_len);
             if (s->pin_ready.load(std::memory_order_acquire) && n * s->sstride <= s->store_cap) {
                 s->store = s->store_pin;
@@ -1073,8 +1102,9 @@ extern "C" int lrm_accaln_opt(const char *genome, const char *reads_path, const 
             }
             // PART 1 + PART 2 in one device pass, asynchronously: up to two batches on the device
             const double t0 = now();
-            const int src = lrm_map_batch_submit(gpu, s->b.seqs, s->b.stride, s->b.lens, (uint64_t) n, p, gp, s->best.data(), s->cig.data(),
-                                                 s->store, s->sstride, s->score.data(), s->meta.data(), s->meta_r.data(), &mopt, &s->ticket);
+            const int src = lrm_map_batch_submit_mapq(gpu, s->b.seqs, s->b.stride, s->b.lens, (uint64_t) n, p, gp, s->best.data(), s->cig.data(),
+                                                      s->store, s->sstride, s->score.data(), s->meta.data(), s->meta_r.data(), &mopt,
+                                                      mapq ? s->mq.data() : nullptr, &s->ticket);
             t_map += now() - t0;
             if (verbose) fprintf(stderr, "[lrm accaln] %.3f submitted %zu reads (%s store) in %.3f s\n", now() - t_upload, n, s->store == s->store_pin ? "pinned" : "pageable", now() - t0);
             if (!first_submitted) { { std::lock_guard<std::mutex> lk(dims_m); first_submitted = true; } dims_cv.notify_all(); }

@@ -801,6 +801,16 @@ extern "C" int lrm_debug_set_vote_limits(lrm_index *idx, uint32_t t3_limit, uint
     return 0;
 }
 
+extern "C" int lrm_debug_set_mapq_slots(lrm_index *idx, uint32_t slots) {
+    if (!idx) { lrm_set_error("null argument"); return -1; }
+    if (slots && (slots < 16 || slots > LRM_MAPQ_SLOTS || (slots & (slots - 1u)))) {
+        lrm_set_error("mapq slots %u: not a power of two in [16, %d]", slots, LRM_MAPQ_SLOTS);
+        return -1;
+    }
+    for (int r = 0; r < idx->n_peers; ++r) (idx->peers ? idx->peers[r] : idx)->dbg_mapq_slots = slots;
+    return 0;
+}
+
 extern "C" int lrm_index_get_tables(const lrm_index *idx, lrm_index_tables *out) {
     if (!idx || !out) { lrm_set_error("lrm_index_get_tables: null argument"); return -1; }
     memset(out, 0, sizeof(*out));
@@ -858,6 +868,7 @@ extern "C" void lrm_workspace_free(lrm_workspace *ws) {
     lrm_bs_scratch_free(&ws->bs);
     lrm_anchor_scratch_free(ws);
     lrm_split_scratch_free(ws);
+    (void) hipFree(ws->d_mq_phase);
     if (ws->h_err) (void) hipHostFree((void *) ws->h_err);
     for (int i = 0; i < LRM_MAX_TIMED; ++i) {
         if (ws->ev_start[i]) (void) hipEventDestroy((hipEvent_t) ws->ev_start[i]);
@@ -971,16 +982,26 @@ static int check_ws(lrm_workspace *ws, lrm_index *idx, uint64_t n, uint32_t max_
     return 0;
 }
 
-extern "C" int lrm_seed_batch_dev(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint64_t stride,
-                                  const uint32_t *d_lens, uint64_t n, uint32_t max_len, lrm_params p,
-                                  lrm_entry *d_best, void *stream) {
+// d_mapq != null: the mapping-quality stage right behind the seed stage, over the lists that stage leaves in the workspace
+extern "C" int lrm_seed_batch_mapq_dev(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint64_t stride,
+                                       const uint32_t *d_lens, uint64_t n, uint32_t max_len, lrm_params p,
+                                       lrm_entry *d_best, lrm_mapq *d_mapq, void *stream) {
     if (!idx || !d_reads || !d_lens || !d_best) { lrm_set_error("null argument"); return -1; }
     if (check_ws(ws, idx, n, max_len, p.seed_len, p.thres)) return -1;
     if (!(ws->parts & LRM_WS_SEED)) { lrm_set_error("workspace has no seed-stage scratch"); return -1; }
     if (stride < max_len) { lrm_set_error("stride %llu < max_len %u", (unsigned long long) stride, max_len); return -1; }
     if (lrm_ws_take_error(ws)) return -2;
     HIPCHK(hipSetDevice(idx->device));
-    return lrm_launch_seed(idx, ws, d_reads, stride, d_lens, n, max_len, p.seed_len, p.thres, d_best, idx->mtune, stream);
+    uint8_t *d_phase = nullptr;
+    if (d_mapq && !(d_phase = lrm_mapq_phase_buf(ws))) return -1;
+    if (int rc = lrm_launch_seed(idx, ws, d_reads, stride, d_lens, n, max_len, p.seed_len, p.thres, d_best, idx->mtune, stream, d_phase)) return rc;
+    if (!d_mapq) return 0;
+    return lrm_launch_mapq(idx, ws, d_lens, n, p.seed_len, p.thres, d_best, d_mapq, stream);
+}
+extern "C" int lrm_seed_batch_dev(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint64_t stride,
+                                  const uint32_t *d_lens, uint64_t n, uint32_t max_len, lrm_params p,
+                                  lrm_entry *d_best, void *stream) {
+    return lrm_seed_batch_mapq_dev(idx, ws, d_reads, stride, d_lens, n, max_len, p, d_best, nullptr, stream);
 }
 
 // what the device-buffer extension entry points check before they launch
@@ -1195,6 +1216,13 @@ extern "C" void lrm_result_flags(const int *score, const int *meta_r, const lrm_
         else if (meta[i].strand == 1) flag += 16;
         flag_out[i] = flag; mapq_out[i] = mapq; valid_out[i] = valid;
     }
+}
+extern "C" void lrm_result_flags_mapq(const int *score, const int *meta_r, const lrm_seq_meta *meta, const lrm_mapq *mq, uint64_t n,
+                                      int *flag_out, int *mapq_out, int *valid_out) {
+    lrm_result_flags(score, meta_r, meta, n, flag_out, mapq_out, valid_out);
+    if (!mq) return;
+    for (uint64_t i = 0; i < n; ++i)
+        if (mapq_out[i] != 0) mapq_out[i] = mq[i].mapq;        // mapped reads: the record's value instead of 255
 }
 
 // ------------------------------------------------------------------------------------------

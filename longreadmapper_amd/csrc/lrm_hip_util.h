@@ -56,4 +56,72 @@ __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
     const uint32_t hi = (uint32_t) __builtin_amdgcn_readlane((int) (uint32_t) (v >> 32), 63);
     return ((uint64_t) hi << 32) | lo;
 }
+
+// ---- index gathers and hit expansion shared by the vote kernels (seed_kernels.hip) and the mapping-quality vote (mapq_kernels.hip) ----
+// ----------------------------------------------------------------------------------------
+// FM LF-mapping: lf(c, loc) = C[c] + rank(c, loc), rank = # of c in bwt[0..loc] == _occ_access (fmidx.c:277-293)
+// and C[] as fmi_aln adds it (fmidx.c:305-311).  One 16-byte gather {C[c] + prefix, mask}, one shift and one
+// popcount.  The seed kernel is bound by the number of per-lane memory requests, then by its 64-bit index arithmetic,
+// so the layout is built to make an LF step ONE request and the packer folds C[c] into the stored prefix (the
+// first version selected C[c] from four scalar pairs in every step: 14 of its ~63 vector instructions).
+// ----------------------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t occ_lf_of(const ulonglong2 e, uint64_t loc) {
+    return e.x + (uint64_t) __popcll(e.y << (63u - ((uint32_t) loc & 63u)));          // bits 0 .. loc % 64 of the mask
+}
+
+// SA[row].  Full SA: one 8-byte gather (sa_access, fmidx.c:18-33).  Sampled SA (LRM_SA_SAMPLED=r): only rows
+// i*r are stored -- the reference's csa table (fmidx.c:153-163) -- and the other rows walk LF steps until
+// they reach a stored row or the '$' row: SA[row] = SA[LF^t(row)] + t (csa_access, fmidx.c:315-331).  The
+// bwt symbol of a row is the symbol whose occurrence mask holds the row's bit; the masks of the four symbols
+// of a block share one 64-byte line.  The reference's own LF step there subtracts one row too many
+// (fmidx.c:323, `- 1` on top of the inclusive rank: its walk leaves the text order and gives up after 5*ratio
+// steps); this is the textbook LF, so that the locate equals sa_access on every row -- the two modes of this
+// library give identical results, and csa_access itself is never called on the reference's hot path.
+__device__ __forceinline__ uint64_t sa_locate(const LrmIndexView &ix, uint64_t row) {
+    if (ix.sa_shift == 0) return ix.sa[row];
+    const uint64_t rmask = (1ull << ix.sa_shift) - 1ull;
+    uint64_t t = 0;
+    while (row & rmask) {
+        if (row == ix.dollar_row) return t;                             // SA[row] == 0
+        const LrmOccBlock *b = &ix.occ[row >> 6];
+        const uint32_t r = (uint32_t) row & 63u;
+        const ulonglong2 e0 = *reinterpret_cast<const ulonglong2 *>(&b->sym[0]);
+        const ulonglong2 e1 = *reinterpret_cast<const ulonglong2 *>(&b->sym[1]);
+        const ulonglong2 e2 = *reinterpret_cast<const ulonglong2 *>(&b->sym[2]);
+        const ulonglong2 e3 = *reinterpret_cast<const ulonglong2 *>(&b->sym[3]);
+        const uint32_t c = (uint32_t) ((e1.y >> r) & 1ull) | ((uint32_t) ((e2.y >> r) & 1ull) << 1) | ((uint32_t) ((e3.y >> r) & 1ull) * 3u);
+        const ulonglong2 e = c == 0 ? e0 : c == 1 ? e1 : c == 2 ? e2 : e3;
+        row = occ_lf_of(e, row);                                        // LF(row) = C[c] + rank(c, row)
+        ++t;
+    }
+    return ix.sa[row >> ix.sa_shift] + t;
+}
+
+// A survivor record's row field (40 bits) with bit 39 set holds the TEXT POSITION of a unique seed instead of its row: the
+// seed table stores SA[k] next to such a seed (count code 0), so the vote stage has nothing to gather for it.  (Rows and
+// positions stay below 2^39: 288 GB of HBM hold no longer text.)
+#define LRM_LOCATED_BIT (1ull << 39)
+__device__ __forceinline__ uint64_t sa_of_unique(const LrmIndexView &ix, uint64_t rec) {
+    const uint64_t kk = rec & ((1ull << 40) - 1ull);
+    return (kk & LRM_LOCATED_BIT) ? (kk & (LRM_LOCATED_BIT - 1ull)) : sa_locate(ix, kk);
+}
+
+// # of set bits of a wave mask below this lane
+__device__ __forceinline__ uint32_t mask_rank(unsigned long long m) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t) (m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m, 0u));
+}
+
+// survivor s of the hit h: off[s] <= h < off[s + 1]  (off: exclusive prefix of the staged survivors' hit counts,
+// strictly increasing because every survivor has at least one hit; cnt >= 1)
+// (Measured alternative for the wavefront tier [r2]: a marker byte where the hits of each staged seed begin + a DPP
+//  prefix maximum over the 64 consecutive hits of the lanes, i.e. one LDS read instead of seven dependent ones:
+//  9.80 vs 9.76 ms per Gbp -- the search is not what the tier waits for.)
+__device__ __forceinline__ uint32_t find_seed(const uint32_t *off, uint32_t cnt, uint32_t h) {
+    uint32_t lo = 0, hi = cnt;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (off[mid] <= h) lo = mid; else hi = mid;
+    }
+    return lo;
+}
 #endif

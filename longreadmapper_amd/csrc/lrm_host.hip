@@ -104,7 +104,7 @@ constexpr int N_RING = 16;          // 256 MiB of pinned chunks per replica: a u
 constexpr int N_SEED_STREAMS = 3;
 constexpr int N_EXT_STREAMS = 4;
 constexpr int N_SLOTS = 3;            // upper bound on the batches (slices) in flight per replica; n_slots of them are used
-struct DevSet { DevSlot reads, lens, best, store, nops, score, meta, mr, tlen, anchor; };
+struct DevSet { DevSlot reads, lens, best, store, nops, score, meta, mr, tlen, anchor, mapq; };
 
 // device-side resources of one slice in flight
 struct Slot {
@@ -116,6 +116,7 @@ struct Slot {
     bool dense_used[2] = {false, false};
     PinSlot h_small;                               // pinned staging of the small result arrays and offset tables (per read)
     PinSlot h_anchor;                              // ... of the anchor records, for the one caller that asks for them (lrm_split_batch)
+    PinSlot h_mapq;                                // ... of the mapping-quality records (lrm_map_batch_submit_mapq)
     std::vector<hipEvent_t> ev_up, ev_seed, ev_ext;   // per sub-batch / per extension group, grown on demand
     bool busy = false;
 };
@@ -473,12 +474,14 @@ struct MapJob {
     const lrm_entry *best_in; lrm_entry *best_out;
     lrm_cigar *cig; uint8_t *store_mem; uint64_t store_stride; int *score; lrm_seq_meta *meta; int *meta_r;
     lrm_anchor *anchor_out;           // anchored mode: the anchor records too (null: they stay in the workspace)
+    lrm_mapq *mapq_out;               // mapping quality: the stage runs behind every seed sub-batch, the records come down with the small arrays (null: no stage)
     MapJob slice(uint64_t o, uint64_t m) const {
         MapJob j = *this;
         j.reads = reads + o * stride; j.lens = lens + o; j.n = m;
         if (best_in) j.best_in = best_in + o;
         if (best_out) j.best_out = best_out + o;
         if (anchor_out) j.anchor_out = anchor_out + o;
+        if (mapq_out) j.mapq_out = mapq_out + o;
         if (cig) { j.cig = cig + o; j.store_mem = store_mem + o * store_stride; j.score = score + o; j.meta = meta + o; j.meta_r = meta_r + o; }
         return j;
     }
@@ -558,9 +561,11 @@ int plan_and_issue(LrmHostCtx &c, SliceJob &sj) {
     uint64_t unit_max = 0;
     for (auto &u : units) unit_max = u.m > unit_max ? u.m : unit_max;
     if (n > 0x7fffffffull) { lrm_set_error("batch too large"); return -1; }
+    const bool want_mapq = j.mapq_out && (j.mode & DO_SEED);
     if (j.mode & DO_SEED)
         for (int s = 0; s < n_seed_streams && (size_t) s < subs.size(); ++s)
-            if (get_ws(S.ws_seed[s], idx, sub, sj.max_len, j.p.seed_len, j.p.thres, LRM_WS_SEED)) return -1;
+            if (get_ws(S.ws_seed[s], idx, sub, sj.max_len, j.p.seed_len, j.p.thres, LRM_WS_SEED) ||
+                (want_mapq && !lrm_mapq_phase_buf(S.ws_seed[s]))) return -1;
     if (j.mode & DO_EXTEND)
         for (int s = 0; s < n_ext_streams && (size_t) s < units.size(); ++s)
             if (get_ws(S.ws_ext[s], idx, unit_max, sj.max_len, 20, 300, LRM_WS_EXTEND)) return -1;
@@ -578,6 +583,7 @@ int plan_and_issue(LrmHostCtx &c, SliceJob &sj) {
     if (S.h_small.ensure(n * 96 + 4096)) { lrm_set_error("pinned staging allocation failed"); return -1; }
     const bool want_anchor = j.anchor_out && (j.mode & DO_EXTEND) && mt.anchored;
     if (want_anchor && (d.anchor.ensure(n * sizeof(lrm_anchor)) || S.h_anchor.ensure(n * sizeof(lrm_anchor)))) { lrm_set_error("allocation for the anchor records failed"); return -1; }
+    if (want_mapq && (d.mapq.ensure(n * sizeof(lrm_mapq)) || S.h_mapq.ensure(n * sizeof(lrm_mapq)))) { lrm_set_error("allocation for the mapping-quality records failed"); return -1; }
     S.dense_used[0] = S.dense_used[1] = false;
 
     for (uint64_t k = 0; k < subs.size(); ++k) {
@@ -593,7 +599,10 @@ int plan_and_issue(LrmHostCtx &c, SliceJob &sj) {
         if (j.mode & DO_SEED) {
             HIPCHK(hipStreamWaitEvent(c.seed[s], S.ev_up[k], 0));
             if (lrm_launch_seed(idx, S.ws_seed[s], dr, j.stride, (const uint32_t *) d.lens.p + off, m, sj.max_len, j.p.seed_len, j.p.thres,
-                                (lrm_entry *) d.best.p + off, mt, c.seed[s])) return -1;
+                                (lrm_entry *) d.best.p + off, mt, c.seed[s], want_mapq ? lrm_mapq_phase_buf(S.ws_seed[s]) : nullptr)) return -1;
+            // (the next sub-batch on this workspace overwrites the survivor lists: the records are made right here)
+            if (want_mapq && lrm_launch_mapq(idx, S.ws_seed[s], (const uint32_t *) d.lens.p + off, m, j.p.seed_len, j.p.thres,
+                                             (const lrm_entry *) d.best.p + off, (lrm_mapq *) d.mapq.p + off, c.seed[s])) return -1;
             HIPCHK(hipEventRecord(S.ev_seed[k], c.seed[s]));
         }
         const uint64_t g = unit_of[k];
@@ -664,9 +673,13 @@ int collect(LrmHostCtx &c, SliceJob &sj, size_t g) {
     const bool want_anchor = j.anchor_out && (j.mode & DO_EXTEND) && sj.mt.anchored;
     lrm_anchor *h_anchor = want_anchor ? (lrm_anchor *) S.h_anchor.p + o : nullptr;
     if (want_anchor) HIPCHK(hipMemcpyAsync(h_anchor, (const lrm_anchor *) d.anchor.p + o, m * sizeof(lrm_anchor), hipMemcpyDeviceToHost, c.down));
+    const bool want_mapq = j.mapq_out && (j.mode & DO_SEED);
+    lrm_mapq *h_mapq = want_mapq ? (lrm_mapq *) S.h_mapq.p + o : nullptr;
+    if (want_mapq) HIPCHK(hipMemcpyAsync(h_mapq, (const lrm_mapq *) d.mapq.p + o, m * sizeof(lrm_mapq), hipMemcpyDeviceToHost, c.down));
     HIPCHK(hipEventRecord(c.ev_small, c.down));
     if (wait_event(c.ev_small)) return -1;
     if (j.mode & DO_SEED) memcpy(j.best_out + o, h_best, m * sizeof(lrm_entry));
+    if (want_mapq) memcpy(j.mapq_out + o, h_mapq, m * sizeof(lrm_mapq));
     if (!(j.mode & DO_EXTEND)) return 0;
     memcpy(j.score + o, h_score, m * 4);
     memcpy(j.meta + o, h_meta, m * sizeof(lrm_seq_meta));
@@ -1053,10 +1066,11 @@ void lrm_host_ctx_free(lrm_index *idx) {
         for (int s = 0; s < N_EXT_STREAMS; ++s) if (S.ws_ext[s]) lrm_workspace_free(S.ws_ext[s]);
         DevSet &d = S.dev;
         d.reads.release(); d.lens.release(); d.best.release(); d.store.release();
-        d.nops.release(); d.score.release(); d.meta.release(); d.mr.release(); d.tlen.release(); d.anchor.release();
+        d.nops.release(); d.score.release(); d.meta.release(); d.mr.release(); d.tlen.release(); d.anchor.release(); d.mapq.release();
         for (int b = 0; b < 2; ++b) { S.dense[b].release(); S.offs[b].release(); if (S.ev_dense[b]) (void) hipEventDestroy(S.ev_dense[b]); }
         S.h_small.release();
         S.h_anchor.release();
+        S.h_mapq.release();
     }
     delete c;
 }
@@ -1105,14 +1119,23 @@ extern "C" int lrm_map_batch(lrm_index *idx, char *reads_buf, uint64_t stride, c
     return run_job(idx, j, nullptr, nullptr);
 }
 
+// mapq_out != null: the mapping-quality stage behind every seed sub-batch (docs/GACT_SPEC.md, "Mapping quality")
+extern "C" int lrm_map_batch_submit_mapq(lrm_index *idx, char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
+                                         lrm_params p, lrm_gact_params gp, lrm_entry *best_out, lrm_cigar *cig_out,
+                                         uint8_t *store_mem, uint64_t store_stride, int *score_out, lrm_seq_meta *meta_out,
+                                         int *meta_r_out, const lrm_map_options *opt, lrm_mapq *mapq_out, lrm_ticket **ticket_out) {
+    if (!ticket_out) { lrm_set_error("null argument"); return -1; }
+    MapJob j;
+    if (map_job_of(j, idx, reads_buf, stride, lens, n, p, gp, best_out, cig_out, store_mem, store_stride, score_out, meta_out, meta_r_out)) return -1;
+    j.mapq_out = mapq_out;
+    return run_job(idx, j, opt, ticket_out);
+}
 extern "C" int lrm_map_batch_submit(lrm_index *idx, char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
                                     lrm_params p, lrm_gact_params gp, lrm_entry *best_out, lrm_cigar *cig_out,
                                     uint8_t *store_mem, uint64_t store_stride, int *score_out, lrm_seq_meta *meta_out,
                                     int *meta_r_out, const lrm_map_options *opt, lrm_ticket **ticket_out) {
-    if (!ticket_out) { lrm_set_error("null argument"); return -1; }
-    MapJob j;
-    if (map_job_of(j, idx, reads_buf, stride, lens, n, p, gp, best_out, cig_out, store_mem, store_stride, score_out, meta_out, meta_r_out)) return -1;
-    return run_job(idx, j, opt, ticket_out);
+    return lrm_map_batch_submit_mapq(idx, reads_buf, stride, lens, n, p, gp, best_out, cig_out, store_mem, store_stride, score_out,
+                                     meta_out, meta_r_out, opt, nullptr, ticket_out);
 }
 
 // ---- split reads: the second pass over a batch that came back with end clipping (docs/GACT_SPEC.md, "Split reads") ----------

@@ -150,6 +150,7 @@ struct lrm_index {
     LrmIndexTune itune;
     LrmMapTune mtune;         // default options of the batch calls on this handle (lrm_index_set_map_options)
     uint32_t dbg_t3_limit, dbg_t3_slots;   // lrm_debug_set_vote_limits (0 = default)
+    uint32_t dbg_mapq_slots;               // lrm_debug_set_mapq_slots (0 = LRM_MAPQ_SLOTS)
 };
 
 // Per-(read,phase) vote result written by the vote kernels.
@@ -238,6 +239,7 @@ struct lrm_workspace {
     LrmBsScratch bs;         // bit-sliced GACT over up to n_max reads of up to max_len bases (LRM_WS_EXTEND)
     struct LrmAnchorScratch *an;   // anchored mode (anchor_kernels.hip): allocated by its first call on this workspace
     struct LrmSplitScratch *sp;    // split stage (split_kernels.hip): allocated by its first call with this workspace as ws_seg
+    uint8_t *d_mq_phase;           // mapping quality (mapq_kernels.hip): deciding phase per read, allocated by the first mapq call
 };
 
 // ---- extension stage: a table of jobs, the kernel that runs it, the bit-sliced kernel's scratch (all host only) ----------
@@ -302,7 +304,13 @@ void lrm_time_end(lrm_workspace *ws, void *stream);
 // launchers implemented in the .hip files (all asynchronous on `stream`)
 int lrm_launch_seed(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint64_t stride,
                     const uint32_t *d_lens, uint64_t n, uint32_t max_len, uint32_t seed_len,
-                    uint32_t thres, lrm_entry *d_best, const LrmMapTune &mt, void *stream);
+                    uint32_t thres, lrm_entry *d_best, const LrmMapTune &mt, void *stream, uint8_t *d_phase_out = nullptr);
+// mapping quality (mapq_kernels.hip; docs/GACT_SPEC.md, "Mapping quality"): lrm_mapq_phase_buf before lrm_launch_seed (the
+// deciding phase per read is that call's d_phase_out; the first call on a workspace allocates the n_max bytes),
+// lrm_launch_mapq right behind it on the same stream -- the survivor lists of the workspace are still those of the batch
+uint8_t *lrm_mapq_phase_buf(lrm_workspace *ws);
+int lrm_launch_mapq(lrm_index *idx, lrm_workspace *ws, const uint32_t *d_lens, uint64_t n, uint32_t seed_len, uint32_t thres,
+                    const lrm_entry *d_best, lrm_mapq *d_mapq, void *stream);
 // a batch as the extension entry points receive it (device pointers; field order of the extern "C" parameter lists)
 struct LrmExtendBatch {
     char *reads; uint64_t stride; const uint32_t *lens; uint64_t n; uint32_t max_len;

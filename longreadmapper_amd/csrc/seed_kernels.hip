@@ -53,17 +53,7 @@ __global__ __launch_bounds__(256) void pack2bit_kernel(const char *__restrict__ 
     *reinterpret_cast<uint32_t *>(out + read * bytes_per_read + ow * 4) = v;
 }
 
-// ----------------------------------------------------------------------------------------
-// FM LF-mapping: lf(c, loc) = C[c] + rank(c, loc), rank = # of c in bwt[0..loc] == _occ_access (fmidx.c:277-293)
-// and C[] as fmi_aln adds it (fmidx.c:305-311).  One 16-byte gather {C[c] + prefix, mask}, one shift and one
-// popcount.  The kernel is bound by the number of per-lane memory requests, then by its 64-bit index arithmetic,
-// so the layout is built to make an LF step ONE request and the packer folds C[c] into the stored prefix (the
-// first version selected C[c] from four scalar pairs in every step: 14 of its ~63 vector instructions).
-// ----------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t occ_lf_of(const ulonglong2 e, uint64_t loc) {
-    return e.x + (uint64_t) __popcll(e.y << (63u - ((uint32_t) loc & 63u)));          // bits 0 .. loc % 64 of the mask
-}
-
+// (the LF step occ_lf_of, sa_locate and sa_of_unique live in lrm_hip_util.h: the mapping-quality vote gathers the same rows)
 // the two LF values of one backward step; after the table lookup most intervals are a handful of rows,
 // so k-1 and l usually fall into the same 64-row block and ONE 16-byte request serves both
 // (returns the number of 16-byte requests it made: 1 or 2 -- only the counting build of seed_search looks at it)
@@ -76,43 +66,6 @@ __device__ __forceinline__ uint32_t occ_lf2(const LrmIndexView &ix, uint32_t c, 
     ra = occ_lf_of(ea, loc_a);
     rb = occ_lf_of(eb, loc_b);
     return two ? 2u : 1u;
-}
-
-// SA[row].  Full SA: one 8-byte gather (sa_access, fmidx.c:18-33).  Sampled SA (LRM_SA_SAMPLED=r): only rows
-// i*r are stored -- the reference's csa table (fmidx.c:153-163) -- and the other rows walk LF steps until
-// they reach a stored row or the '$' row: SA[row] = SA[LF^t(row)] + t (csa_access, fmidx.c:315-331).  The
-// bwt symbol of a row is the symbol whose occurrence mask holds the row's bit; the masks of the four symbols
-// of a block share one 64-byte line.  The reference's own LF step there subtracts one row too many
-// (fmidx.c:323, `- 1` on top of the inclusive rank: its walk leaves the text order and gives up after 5*ratio
-// steps); this is the textbook LF, so that the locate equals sa_access on every row -- the two modes of this
-// library give identical results, and csa_access itself is never called on the reference's hot path.
-__device__ __forceinline__ uint64_t sa_locate(const LrmIndexView &ix, uint64_t row) {
-    if (ix.sa_shift == 0) return ix.sa[row];
-    const uint64_t rmask = (1ull << ix.sa_shift) - 1ull;
-    uint64_t t = 0;
-    while (row & rmask) {
-        if (row == ix.dollar_row) return t;                             // SA[row] == 0
-        const LrmOccBlock *b = &ix.occ[row >> 6];
-        const uint32_t r = (uint32_t) row & 63u;
-        const ulonglong2 e0 = *reinterpret_cast<const ulonglong2 *>(&b->sym[0]);
-        const ulonglong2 e1 = *reinterpret_cast<const ulonglong2 *>(&b->sym[1]);
-        const ulonglong2 e2 = *reinterpret_cast<const ulonglong2 *>(&b->sym[2]);
-        const ulonglong2 e3 = *reinterpret_cast<const ulonglong2 *>(&b->sym[3]);
-        const uint32_t c = (uint32_t) ((e1.y >> r) & 1ull) | ((uint32_t) ((e2.y >> r) & 1ull) << 1) | ((uint32_t) ((e3.y >> r) & 1ull) * 3u);
-        const ulonglong2 e = c == 0 ? e0 : c == 1 ? e1 : c == 2 ? e2 : e3;
-        row = occ_lf_of(e, row);                                        // LF(row) = C[c] + rank(c, row)
-        ++t;
-    }
-    return ix.sa[row >> ix.sa_shift] + t;
-}
-
-// A survivor record's row field (40 bits) with bit 39 set holds the TEXT POSITION of a unique seed instead of its row: the
-// seed table stores SA[k] next to such a seed (count code 0), so the vote stage has nothing to gather for it.  (Rows and
-// positions stay below 2^39: 288 GB of HBM hold no longer text.)
-#define LRM_LOCATED_BIT (1ull << 39)
-__device__ __forceinline__ uint64_t sa_of_unique(const LrmIndexView &ix, uint64_t rec) {
-    const uint64_t kk = rec & ((1ull << 40) - 1ull);
-    return (kk & LRM_LOCATED_BIT) ? (kk & (LRM_LOCATED_BIT - 1ull)) : sa_locate(ix, kk);
 }
 
 // lc_access (lchash.c:12-16) on the 8-byte device entries
@@ -1086,11 +1039,6 @@ __device__ __forceinline__ void write_phase(LrmPhaseRes *out, const PhaseTop &p)
     *out = res;
 }
 
-// # of set bits of a wave mask below this lane
-__device__ __forceinline__ uint32_t mask_rank(unsigned long long m) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t) (m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m, 0u));
-}
-
 // Top-2 of a vote table, "count descending, first-seen ascending" (histo.c:84-96 with the insertion order carried
 // by the order key): one u64 per slot, count << 32 | ~first, is unique among the filled slots (every hit has its own
 // order key), so the stable top-2 is the two largest keys.  Every lane scans its slots, then two max-reductions.
@@ -1150,20 +1098,6 @@ __device__ __forceinline__ Top2 table_top2_global(const VoteTable &t, uint32_t t
         r.s2 = (uint32_t) __builtin_amdgcn_readlane((int) (win ? s2 : s1), src);
     }
     return r;
-}
-
-// survivor s of the hit h: off[s] <= h < off[s + 1]  (off: exclusive prefix of the staged survivors' hit counts,
-// strictly increasing because every survivor has at least one hit; cnt >= 1)
-// (Measured alternative for the wavefront tier [r2]: a marker byte where the hits of each staged seed begin + a DPP
-//  prefix maximum over the 64 consecutive hits of the lanes, i.e. one LDS read instead of seven dependent ones:
-//  9.80 vs 9.76 ms per Gbp -- the search is not what the tier waits for.)
-__device__ __forceinline__ uint32_t find_seed(const uint32_t *off, uint32_t cnt, uint32_t h) {
-    uint32_t lo = 0, hi = cnt;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (off[mid] <= h) lo = mid; else hi = mid;
-    }
-    return lo;
 }
 
 // Survivors come in two kinds.  UNIQUE seeds (rr == 1: the read's true locus, ~3/4 of the survivors of a noisy
@@ -1840,13 +1774,16 @@ void vote_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec,
 //   mode 0 : phase 0 only -- mark reads whose phase-0 vote passes (they are final)
 //   mode 1 : all phases, for reads not marked in mode 0
 //   mode 2 : all phases for every read (single-round launches); counts the reads mode 0 would have marked
+// phase_out (optional, every mode): the phase at which the loop broke, P - 1 when it ran out -- the evidence phases of
+// the mapping-quality vote (mapq_kernels.hip).
 // (double)v/num_seeds > 0.6  <=>  5v > 3*num_seeds for every feasible size.
 // ----------------------------------------------------------------------------------------
 #define MAX_PHASES 40
 __global__ __launch_bounds__(256) void decide_kernel(const LrmPhaseRes *__restrict__ phase_res,
                                                      const uint32_t *__restrict__ lens, uint64_t n,
                                                      int seed_len, int mode, uint8_t *__restrict__ decided,
-                                                     lrm_entry *__restrict__ best, LrmDevCounters *counters) {
+                                                     lrm_entry *__restrict__ best, LrmDevCounters *counters,
+                                                     uint8_t *__restrict__ phase_out) {
     uint64_t read = (uint64_t) blockIdx.x * 256 + threadIdx.x;
     if (read >= n) return;
     const int P = seed_len + 1;
@@ -1861,6 +1798,7 @@ __global__ __launch_bounds__(256) void decide_kernel(const LrmPhaseRes *__restri
                 d = 1;
                 lrm_entry e = {r0.key1, r0.val1, r0.bucket1};
                 best[read] = e;
+                if (phase_out) phase_out[read] = 0;
                 atomicAdd(&counters->decided_phase0, 1ull);
             }
         }
@@ -1902,6 +1840,7 @@ __global__ __launch_bounds__(256) void decide_kernel(const LrmPhaseRes *__restri
         out = t1;
     }
     best[read] = out;
+    if (phase_out) phase_out[read] = (uint8_t) (iter < P ? iter : P - 1);      // the deciding phase (docs/GACT_SPEC.md, "Mapping quality")
 }
 
 // ----------------------------------------------------------------------------------------
@@ -1910,7 +1849,7 @@ __global__ __launch_bounds__(256) void decide_kernel(const LrmPhaseRes *__restri
 
 int lrm_launch_seed(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint64_t stride,
                     const uint32_t *d_lens, uint64_t n, uint32_t max_len, uint32_t seed_len,
-                    uint32_t thres, lrm_entry *d_best, const LrmMapTune &mt, void *stream_) {
+                    uint32_t thres, lrm_entry *d_best, const LrmMapTune &mt, void *stream_, uint8_t *d_phase_out) {
     hipStream_t stream = (hipStream_t) stream_;
     if (n == 0) return 0;
     const int P = (int) seed_len + 1;
@@ -2017,7 +1956,7 @@ int lrm_launch_seed(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint
         lrm_time_end(ws, stream);
         lrm_time_begin(ws, LRM_K_DECIDE, stream);
         hipLaunchKernelGGL(decide_kernel, dim3((uint32_t) ((n + 255) / 256)), dim3(256), 0, stream, ws->d_phase,
-                           d_lens, n, (int) seed_len, single ? 2 : round, ws->d_decided, d_best, ws->d_counters);
+                           d_lens, n, (int) seed_len, single ? 2 : round, ws->d_decided, d_best, ws->d_counters, d_phase_out);
         lrm_time_end(ws, stream);
     }
     HIPCHK(hipMemcpyAsync((void *) (ws->h_err + 2), &ws->d_counters->decided_phase0, 8, hipMemcpyDeviceToHost, stream));

@@ -188,6 +188,10 @@ class DeviceIndex:
     def debug_set_vote_limits(self, t3_limit=0, t3_slots=0):
         check(lib.lrm_debug_set_vote_limits(self.handle, t3_limit, t3_slots), "lrm_debug_set_vote_limits")
 
+    def debug_set_mapq_slots(self, slots=0):
+        """Test-only: slots of the mapping-quality stage's rival table (0: LRM_MAPQ_SLOTS); a small table forces overflows."""
+        check(lib.lrm_debug_set_mapq_slots(self.handle, slots), "lrm_debug_set_mapq_slots")
+
     @property
     def replicas(self):
         return int(lib.lrm_index_replicas(self.handle))

@@ -24,6 +24,10 @@ assert ANCHOR_DT.itemsize == 32
 CLIP_DT = np.dtype([("left", "<u4"), ("right", "<u4")])          # lrm_clip
 SEGMENT_DT = np.dtype([("read", "<u4"), ("start", "<u4"), ("len", "<u4"), ("flags", "<u4")])      # lrm_segment
 SEG_RIGHT, SEG_ALIGNED = capi.SEG_RIGHT, capi.SEG_ALIGNED
+MAPQ_DT = np.dtype([("n1", "<u4"), ("n2", "<u4"), ("radius", "<u4"), ("mapq", "u1"), ("phase", "u1"), ("flags", "u1"),
+                    ("_pad", "u1")])                              # lrm_mapq (docs/GACT_SPEC.md, "Mapping quality")
+assert MAPQ_DT.itemsize == 16
+MAPQ_OVERFLOW = capi.MAPQ_OVERFLOW
 
 
 def anchored_store_stride(max_len):
@@ -128,6 +132,8 @@ class PendingBatch:
         n = self.n
         cv = np.ctypeslib.as_array(C.cast(cig, C.POINTER(C.c_int32)), shape=(max(n, 1), 4))[:n]
         out = dict(best=best, ops=store, n_ops=cv[:, 2].copy(), score=score, meta=meta, meta_r=meta_r)
+        if len(self._keep) > 8:
+            out["mapq"] = self._keep[8]
         if self.dense:          # cig[i].cigar = store_mem + off[i]
             ptr = np.ctypeslib.as_array(C.cast(cig, C.POINTER(C.c_uint64)), shape=(max(n, 1), 2))[:n, 0]
             out["ops_off"] = (ptr - np.uint64(store.ctypes.data)).astype(np.int64)
@@ -159,8 +165,9 @@ def ops_of(res, i):
 
 
 def map_batch_submit(index, reads, lens, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT, store=None,
-                     options=None, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0):
-    """lrm_map_batch_submit: queues the batch and returns a PendingBatch.  `reads` is modified in place like
+                     options=None, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0, mapq=False):
+    """lrm_map_batch_submit (mapq=True: lrm_map_batch_submit_mapq -- the result gains "mapq", the MAPQ_DT records of the
+    batch): queues the batch and returns a PendingBatch.  `reads` is modified in place like
     extend_batch once the batch runs; `store` may be a caller-provided (n, >= 2*max_len) uint8 array (e.g. pinned;
     anchored: >= anchored_store_stride(max_len)); `options`: dict of lrm_map_options fields (None: the handle's
     defaults); anchored=True adds the anchored extension mode to them, clip=True that mode with its end clipping
@@ -182,24 +189,27 @@ def map_batch_submit(index, reads, lens, seed_len=DEFAULT_SEED_LEN, thres=DEFAUL
     meta_r = np.zeros(n, dtype=np.int32)
     opt = capi.map_options(**options) if options is not None else None
     ticket = C.c_void_p()
-    check(lib.lrm_map_batch_submit(index.handle, reads.ctypes.data, stride, lens.ctypes.data, n,
-                                   capi.Params(n, seed_len, thres), capi.GactParams(*gact), best.ctypes.data,
-                                   C.cast(cig, C.c_void_p), store.ctypes.data, store_stride, score.ctypes.data,
-                                   meta.ctypes.data, meta_r.ctypes.data, C.byref(opt) if opt is not None else None,
-                                   C.byref(ticket)), "lrm_map_batch_submit")
+    mq = np.zeros(n, dtype=MAPQ_DT) if mapq else None
+    check(lib.lrm_map_batch_submit_mapq(index.handle, reads.ctypes.data, stride, lens.ctypes.data, n,
+                                        capi.Params(n, seed_len, thres), capi.GactParams(*gact), best.ctypes.data,
+                                        C.cast(cig, C.c_void_p), store.ctypes.data, store_stride, score.ctypes.data,
+                                        meta.ctypes.data, meta_r.ctypes.data, C.byref(opt) if opt is not None else None,
+                                        mq.ctypes.data if mapq else None, C.byref(ticket)), "lrm_map_batch_submit_mapq")
     text = bool(opt.cigar_text) if opt is not None else False
     dense = (bool(opt.dense_results) or text) if opt is not None else False
-    return PendingBatch(ticket, (best, store, cig, score, meta, meta_r, reads, lens), n, dense, text)
+    keep = (best, store, cig, score, meta, meta_r, reads, lens)
+    return PendingBatch(ticket, keep + (mq,) if mapq else keep, n, dense, text)
 
 
 def map_batch(index, reads, lens, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT, store=None,
-              options=None, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0):
+              options=None, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0, mapq=False):
     """PART 1 + PART 2 in one device pass; `reads` is modified in place like extend_batch.
     Without `options` this is lrm_map_batch (the handle's default options), with them (or with anchored=True or
-    clip=True, which are among them) submit + wait."""
+    clip=True, which are among them) submit + wait.  mapq=True: the mapping-quality records (MAPQ_DT) come back as
+    res["mapq"] next to the other results, which do not change (submit + wait through lrm_map_batch_submit_mapq)."""
     options = _anchor_options(options, anchored, anchor_min_len, clip, clip_penalty, clip_end_bonus)
-    if options is not None:
-        return map_batch_submit(index, reads, lens, seed_len, thres, gact, store, options).wait()
+    if options is not None or mapq:
+        return map_batch_submit(index, reads, lens, seed_len, thres, gact, store, options, mapq=mapq).wait()
     assert reads.dtype == np.uint8 and reads.flags.c_contiguous and reads.flags.writeable
     lens = np.ascontiguousarray(lens, dtype=np.uint32)
     n, stride = reads.shape
@@ -326,17 +336,24 @@ def split_batch(index, reads, lens, res, seed_len=DEFAULT_SEED_LEN, thres=DEFAUL
     return buffers.result(dense, text)
 
 
-def result_flags(score, meta_r, meta):
+def result_flags(score, meta_r, meta, mapq=None):
+    """lrm_result_flags; mapq: the MAPQ_DT records of the batch (lrm_result_flags_mapq: a mapped read's MAPQ is its record's)."""
     n = len(score)
     flag = np.zeros(n, dtype=np.int32)
-    mapq = np.zeros(n, dtype=np.int32)
+    out = np.zeros(n, dtype=np.int32)
     valid = np.zeros(n, dtype=np.int32)
     score = np.ascontiguousarray(score, dtype=np.int32)
     meta_r = np.ascontiguousarray(meta_r, dtype=np.int32)
     meta = np.ascontiguousarray(meta, dtype=META_DT)
-    lib.lrm_result_flags(score.ctypes.data, meta_r.ctypes.data, meta.ctypes.data, n, flag.ctypes.data,
-                         mapq.ctypes.data, valid.ctypes.data)
-    return flag, mapq, valid
+    if mapq is not None:
+        mq = np.ascontiguousarray(mapq, dtype=MAPQ_DT)
+        assert len(mq) == n
+        lib.lrm_result_flags_mapq(score.ctypes.data, meta_r.ctypes.data, meta.ctypes.data, mq.ctypes.data, n, flag.ctypes.data,
+                                  out.ctypes.data, valid.ctypes.data)
+    else:
+        lib.lrm_result_flags(score.ctypes.data, meta_r.ctypes.data, meta.ctypes.data, n, flag.ctypes.data,
+                             out.ctypes.data, valid.ctypes.data)
+    return flag, out, valid
 
 
 class DeviceMapper:
@@ -345,8 +362,10 @@ class DeviceMapper:
 
     def __init__(self, index, n_max, max_len, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT,
                  device=0, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0, split=False,
-                 split_min_len=0, seg_cap=None, seg_rows=None):
-        """split (needs clip): split() after extend() maps the soft-clipped ends of at least split_min_len bases (0 = 200) as
+                 split_min_len=0, seg_cap=None, seg_rows=None, mapq=False):
+        """mapq: seed() runs the mapping-quality stage behind the seed stage (lrm_seed_batch_mapq_dev); mapq_records(n) and
+        results(n)["mapq"] are the MAPQ_DT records of the last seed call.
+        split (needs clip): split() after extend() maps the soft-clipped ends of at least split_min_len bases (0 = 200) as
         reads of their own (lrm_split_batch_dev), results() returns them as res["split"].  seg_cap: room for that many
         segments (None: 2 * n_max, every possible one); seg_rows: rows of the segment workspace (None: min(seg_cap, n_max);
         0: no workspace of its own -- the primary's is used a second time); more segments than rows run in chunks."""
@@ -374,6 +393,7 @@ class DeviceMapper:
         self.meta_r = torch.zeros(n_max, dtype=torch.int32, device=self.dev)
         self.anchor = torch.zeros((n_max, 32), dtype=torch.uint8, device=self.dev) if anchored else None     # lrm_anchor
         self.clip = torch.zeros((n_max, 2), dtype=torch.int32, device=self.dev) if clip else None           # lrm_clip
+        self.mapq = torch.zeros((n_max, 16), dtype=torch.uint8, device=self.dev) if mapq else None           # lrm_mapq
         self.split_on, self.split_min_len, self.ws_seg, self.n_seg = bool(split), split_min_len, None, 0
         if split:
             if not clip:
@@ -406,9 +426,19 @@ class DeviceMapper:
     def seed(self, d_reads, d_lens, n=None):
         n = d_reads.shape[0] if n is None else n
         p = capi.Params(n, self.seed_len, self.thres)
+        if self.mapq is not None:
+            check(lib.lrm_seed_batch_mapq_dev(self.index.handle, self.ws, d_reads.data_ptr(), d_reads.stride(0),
+                                              d_lens.data_ptr(), n, self.max_len, p, self.best.data_ptr(),
+                                              self.mapq.data_ptr(), self._stream()), "lrm_seed_batch_mapq_dev")
+            return
         check(lib.lrm_seed_batch_dev(self.index.handle, self.ws, d_reads.data_ptr(), d_reads.stride(0),
                                      d_lens.data_ptr(), n, self.max_len, p, self.best.data_ptr(), self._stream()),
               "lrm_seed_batch_dev")
+
+    def mapq_records(self, n):
+        """The lrm_mapq records (MAPQ_DT) of the last seed() -- DeviceMapper(..., mapq=True)."""
+        assert self.mapq is not None
+        return self.mapq[:n].cpu().numpy().reshape(-1).view(MAPQ_DT)
 
     def extend(self, d_reads, d_lens, n=None):
         n = d_reads.shape[0] if n is None else n
@@ -510,6 +540,8 @@ class DeviceMapper:
             res["clip"] = self.clip[:n].cpu().numpy().reshape(-1).view(CLIP_DT)
         if self.split_on:
             res["split"] = self.split_results()
+        if self.mapq is not None:
+            res["mapq"] = self.mapq_records(n)
         return res
 
     def close(self):
