@@ -311,7 +311,7 @@ __global__ __launch_bounds__(64) void gact_bs_kernel(const uint64_t *__restrict_
     // Lanes take reads from a queue (one atomic per wavefront and refill): reads of very different
     // lengths share a wavefront without the short ones idling behind the longest, and a grid of a few
     // resident wavefronts per SIMD serves any batch size.
-    unsigned long long *queue = &counters->reserved[0];
+    unsigned long long *queue = &counters->bs_queue;
     uint64_t r = 0;
     bool alive = false, exhausted = false;
     int n = 0, m = 0;
@@ -653,7 +653,7 @@ int lrm_bs_launch(const LrmGactJobs &j, lrm_gact_params gp, const LrmBsScratch &
     uint64_t blocks = (j.n + 63) / 64;
     if (blocks > LRM_BS_MAX_WAVES) blocks = LRM_BS_MAX_WAVES;              // resident wavefronts; lanes refill from the queue
     if (max_waves >= 1 && max_waves < blocks) blocks = max_waves;          // (tests: a small grid forces refills)
-    HIPCHK(hipMemsetAsync(&counters->reserved[0], 0, sizeof(unsigned long long), stream));
+    HIPCHK(hipMemsetAsync(&counters->bs_queue, 0, sizeof(unsigned long long), stream));
     hipLaunchKernelGGL(gact_bs_kernel, dim3((uint32_t) blocks), dim3(64), 0, stream, bs.qpl, bs.wpr, j.lens, j.meta,
                        j.meta_r, j.cpl + BS_PADW, j.tlens, bs.rflags, j.n, gp.T, gp.O, gp.W, bs.ckpt, bs.codes, bs.cw,
                        bs.ncodes, j.n_ops, j.score, counters);

@@ -994,7 +994,7 @@ extern "C" int lrm_seed_batch_mapq_dev(lrm_index *idx, lrm_workspace *ws, const 
     HIPCHK(hipSetDevice(idx->device));
     uint8_t *d_phase = nullptr;
     if (d_mapq && !(d_phase = lrm_mapq_phase_buf(ws))) return -1;
-    if (int rc = lrm_launch_seed(idx, ws, d_reads, stride, d_lens, n, max_len, p.seed_len, p.thres, d_best, idx->mtune, stream, d_phase)) return rc;
+    if (int rc = lrm_launch_seed(idx, ws, d_reads, stride, d_lens, n, p.seed_len, p.thres, d_best, idx->mtune, stream, d_phase)) return rc;
     if (!d_mapq) return 0;
     return lrm_launch_mapq(idx, ws, d_lens, n, p.seed_len, p.thres, d_best, d_mapq, stream);
 }
@@ -1043,9 +1043,9 @@ extern "C" int lrm_workspace_stats(lrm_workspace *ws, lrm_stats *out, void *stre
     out->reads_decided_phase0 = c.decided_phase0;
     out->gact_tiles = c.gact_tiles;
     out->vote_redo_items = c.vote_redo_n[0] + c.vote_redo_n[1];
-    out->seeds_evaluated = c.reserved[3];
-    out->seed_table_lookups = c.reserved[4];
-    out->seed_rank_requests = c.reserved[5];
+    out->seeds_evaluated = c.seed_traffic[0];
+    out->seed_table_lookups = c.seed_traffic[1];
+    out->seed_rank_requests = c.seed_traffic[2];
     return lrm_ws_take_error(ws);
 }
 extern "C" int lrm_extend_batch_anchored_dev(lrm_index *idx, lrm_workspace *ws, char *d_reads, uint64_t stride,

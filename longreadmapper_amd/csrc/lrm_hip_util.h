@@ -21,7 +21,7 @@ static inline int lrm_grid_1d(uint64_t blocks, const char *what, uint32_t *out) 
 }
 
 #if defined(__HIPCC__)
-// ---- wavefront primitives on the DPP network (seed_kernels.hip, anchor_kernels.hip) ----
+// ---- wavefront primitives on the DPP network (seed_kernels.hip, vote_kernels.hip, anchor_kernels.hip) ----
 // inclusive prefix sum over the 64 lanes on the DPP network: four row shifts inside the rows of 16, then the
 // row totals are broadcast to the following rows (row_bcast:15 / row_bcast:31) -- six v_add_u32_dpp, no LDS
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
@@ -57,7 +57,7 @@ __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
     return ((uint64_t) hi << 32) | lo;
 }
 
-// ---- index gathers and hit expansion shared by the vote kernels (seed_kernels.hip) and the mapping-quality vote (mapq_kernels.hip) ----
+// ---- index gathers and hit expansion shared by the vote kernels (vote_kernels.hip), the seed-table build (index_tables.hip) and the mapping-quality vote (mapq_kernels.hip) ----
 // ----------------------------------------------------------------------------------------
 // FM LF-mapping: lf(c, loc) = C[c] + rank(c, loc), rank = # of c in bwt[0..loc] == _occ_access (fmidx.c:277-293)
 // and C[] as fmi_aln adds it (fmidx.c:305-311).  One 16-byte gather {C[c] + prefix, mask}, one shift and one

@@ -598,7 +598,7 @@ int plan_and_issue(LrmHostCtx &c, SliceJob &sj) {
         HIPCHK(hipEventRecord(S.ev_up[k], c.up));
         if (j.mode & DO_SEED) {
             HIPCHK(hipStreamWaitEvent(c.seed[s], S.ev_up[k], 0));
-            if (lrm_launch_seed(idx, S.ws_seed[s], dr, j.stride, (const uint32_t *) d.lens.p + off, m, sj.max_len, j.p.seed_len, j.p.thres,
+            if (lrm_launch_seed(idx, S.ws_seed[s], dr, j.stride, (const uint32_t *) d.lens.p + off, m, j.p.seed_len, j.p.thres,
                                 (lrm_entry *) d.best.p + off, mt, c.seed[s], want_mapq ? lrm_mapq_phase_buf(S.ws_seed[s]) : nullptr)) return -1;
             // (the next sub-batch on this workspace overwrites the survivor lists: the records are made right here)
             if (want_mapq && lrm_launch_mapq(idx, S.ws_seed[s], (const uint32_t *) d.lens.p + off, m, j.p.seed_len, j.p.thres,

@@ -75,14 +75,14 @@ struct LrmIndexView {
     const uint64_t *lcl;      // optional LONG table (hl-mers, hl > hlen), built on the device from lc + FM steps; null = unused
     int32_t hl;
     int32_t sa_shift;         // log2 of the SA sampling ratio (0: every row is stored)
-    int32_t lcl_pair;         // long table in PAIR-LINE layout (seed_kernels.hip): the lookups of two neighbouring seeds share a 64-byte line
+    int32_t lcl_pair;         // long table in PAIR-LINE layout (seed_index_dev.h): the lookups of two neighbouring seeds share a 64-byte line
     int32_t lcl_kbits;        // 0: 8-byte entries (k | count << 40).  > 0: 5-BYTE entries, k in the low lcl_kbits bits, count above
                               // (all ones = look the hl-mer up in the side hash table lclx)
-    const uint64_t *core;     // optional CORE table of small texts (seed_kernels.hip): one 64-byte line per 13-mer holds the entries of
+    const uint64_t *core;     // optional CORE table of small texts (seed_index_dev.h): one 64-byte line per 13-mer holds the entries of
                               // the 16-mers around it, so that the lookups of FOUR neighbouring read positions share a line; null = unused
     const uint64_t *lclx;     // side hash table of the 5-byte layout: {hl-mer code + 1, k | count << 40} pairs, open addressing
     uint64_t lclx_mask;       // slots - 1 (a power of two)
-    // optional SEED table (seed_kernels.hip): (first row, count) of every distinct sd_len-mer of the text in 64-byte lines shared
+    // optional SEED table (seed_index_dev.h): (first row, count) of every distinct sd_len-mer of the text in 64-byte lines shared
     // by the seeds of sd_f neighbouring read positions; null = unused
     const uint64_t *sd;
     const uint64_t *sdx;      // its side hash table {code + 1, k | count << 40}: entries of crowded lines, counts beyond the slot's bits
@@ -161,7 +161,10 @@ struct LrmPhaseRes {
 
 // Device counters block (one per workspace).
 struct LrmDevCounters {
-    unsigned long long reserved[8];
+    unsigned long long bs_queue;              // work queue of the bit-sliced GACT kernel
+    unsigned long long vote_ticket[2];        // per seeding round: ticket of the exact vote kernel
+    unsigned long long seed_traffic[3];       // counting build of seed_search: seeds evaluated, table lookups, rank requests
+    unsigned long long reserved[2];
     unsigned long long decided_phase0;
     unsigned long long gact_tiles;
     unsigned long long pad[2];
@@ -170,12 +173,13 @@ struct LrmDevCounters {
     unsigned long long vote_big_n[2];         //   items it left to its workgroup form, and that kernel's ticket
     unsigned long long vote_big_ticket[2];
 };
+static_assert(offsetof(LrmDevCounters, decided_phase0) == 64 && sizeof(LrmDevCounters) == 160, "counters are addressed by the device as laid out here");
 // Error word of a workspace: ONE dword of host-coherent pinned memory that kernels set with a plain store (bit 0:
 // vote table overflow in the multi-pass tier).  It is never cleared by a launch, so an error raised by any
 // sub-batch survives until the host reads it: lrm_workspace_stats and every *_dev entry point check it (the
 // next call after the faulty batch fails), the host-buffer entry points check it per sub-batch.
 #define LRM_ERR_VOTE_OVERFLOW 1u
-// vote tiers (seed_kernels.hip): hits per (read, phase) item up to which one wavefront / one workgroup pass suffices
+// vote tiers (vote_kernels.hip): hits per (read, phase) item up to which one wavefront / one workgroup pass suffices
 #define LRM_VOTE_T1_LIMIT 192
 #ifndef LRM_VOTE_T3_SLOTS
 #define LRM_VOTE_T3_SLOTS 1024
@@ -285,7 +289,7 @@ int lrm_bs_pack_text(const char *d_text, uint64_t len, uint64_t *d_out, uint32_t
 int lrm_bs_launch(const LrmGactJobs &j, lrm_gact_params gp, const LrmBsScratch &bs, LrmDevCounters *counters,
                   uint32_t max_waves, void *stream);
 int lrm_bs_prepare_index(lrm_index *idx);
-int lrm_lcl_prepare_index(lrm_index *idx);       // seed_kernels.hip: the long seed table
+int lrm_lcl_prepare_index(lrm_index *idx);       // index_tables.hip: the long lc table, the core table, the seed table
 void lrm_bs_free_index(lrm_index *idx);
 
 void lrm_set_error(const char *fmt, ...);
@@ -303,8 +307,18 @@ void lrm_time_end(lrm_workspace *ws, void *stream);
 
 // launchers implemented in the .hip files (all asynchronous on `stream`)
 int lrm_launch_seed(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint64_t stride,
-                    const uint32_t *d_lens, uint64_t n, uint32_t max_len, uint32_t seed_len,
+                    const uint32_t *d_lens, uint64_t n, uint32_t seed_len,
                     uint32_t thres, lrm_entry *d_best, const LrmMapTune &mt, void *stream, uint8_t *d_phase_out = nullptr);
+// the vote of one seeding round over the survivor lists of the workspace (vote_kernels.hip): the fast pair plus the exact
+// kernel, or the exact kernel alone
+struct LrmVoteLaunch {
+    const uint8_t *decided;                // reads to skip (round 1 of two); null: none
+    uint64_t n; uint32_t seed_len; int phase_lo, phase_hi;
+    uint32_t tbits;                        // bits of the SA offset in the order key (q << tbits) | t
+    int round;                             // which ticket / list counters of LrmDevCounters
+    const LrmMapTune *mt;
+};
+int lrm_launch_vote(lrm_index *idx, lrm_workspace *ws, const LrmVoteLaunch &v, void *stream);
 // mapping quality (mapq_kernels.hip; docs/GACT_SPEC.md, "Mapping quality"): lrm_mapq_phase_buf before lrm_launch_seed (the
 // deciding phase per read is that call's d_phase_out; the first call on a workspace allocates the n_max bytes),
 // lrm_launch_mapq right behind it on the same stream -- the survivor lists of the workspace are still those of the batch

@@ -2,7 +2,7 @@
 // hits of a read.  The reference prints MAPQ 255 for every mapped read (alnmain.c:460-474); this stage is a choice of
 // THIS implementation and runs only when a caller asks for the records.
 //
-// The vote kernels of seed_kernels.hip keep the two largest 16-diagonal buckets of a phase, which on a noisy read are
+// The vote kernels of vote_kernels.hip keep the two largest 16-diagonal buckets of a phase, which on a noisy read are
 // neighbours of the same locus and say nothing about a RIVAL locus.  The survivor lists the seed kernel wrote (rec =
 // k | rr << 40, recq = seed ordinal, cnt, per (read, phase)) are still in the workspace when decide_kernel has run, so
 // this kernel goes over them once more: every hit of the phases 0 .. d (d: the deciding phase) is either within R

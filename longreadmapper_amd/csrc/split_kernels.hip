@@ -243,7 +243,7 @@ int lrm_launch_split(lrm_index *idx, lrm_workspace *ws, const LrmSplitArgs &a, c
     for (uint64_t o = 0; o < n_seg; o += ws->n_max) {
         const uint64_t m = n_seg - o < ws->n_max ? n_seg - o : ws->n_max;
         char *rows = out.rows + o * out.row_stride;
-        if (lrm_launch_seed(idx, ws, rows, out.row_stride, out.lens + o, m, longest, a.seed_len, a.thres, out.best + o, mt, stream_)) return -1;
+        if (lrm_launch_seed(idx, ws, rows, out.row_stride, out.lens + o, m, a.seed_len, a.thres, out.best + o, mt, stream_)) return -1;
         const LrmExtendBatch b = {rows, out.row_stride, out.lens + o, m, longest, out.best + o, out.store + o * out.store_stride,
                                   out.store_stride, out.n_ops + o, out.score + o, out.meta + o, out.meta_r + o};
         if (lrm_launch_extend_anchored(idx, ws, b, a.gp, out.anchor + o, a.anchor_min_len,

@@ -296,7 +296,7 @@ def test_multi_gpu_group_handle_equals_one_gpu(ont, gpu, ngpus):
 @pytest.mark.parametrize("ratio", [4, 32])
 def test_sampled_sa_locate_mode(gpu, name, ratio):
     """lrm_index_options.sa_sampled = r keeps SA rows i*r only (the reference's csa table, fmidx.c:153-163) and locates the
-    rest by LF steps on the device (csa_access, fmidx.c:315-331, with the textbook LF -- see seed_kernels.hip):
+    rest by LF steps on the device (csa_access, fmidx.c:315-331, with the textbook LF -- see sa_locate in lrm_hip_util.h):
     identical best[] to the full-SA mode and to the oracle, with 1/r of the SA bytes in HBM."""
     sc = workloads.scenario(name)
     oi = orc.OracleIndex.from_host_index(sc["hi"])
