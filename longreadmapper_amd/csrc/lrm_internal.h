@@ -27,6 +27,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 #include "../../include/lrm_accel.h"
 
 #define LRM_BLOB_MAGIC 0x4c524d424c4f4232ull   // "LRMBLOB2" (2: C[] folded into the occ prefixes)
@@ -124,8 +125,17 @@ struct LrmMapTune {
 };
 void lrm_resolve_index_tune(const lrm_index_options *opt, const LrmEnv &env, LrmIndexTune *out);
 void lrm_resolve_map_tune(const lrm_map_options *opt, const LrmEnv &env, LrmMapTune *out);
+// a caller's options struct over the defaults in *o: as many bytes as the caller's struct_size says it has (0: all)
+template <typename T>
+static inline void lrm_options_over_defaults(T *o, const T *opt) {
+    if (opt) memcpy(o, opt, opt->struct_size && opt->struct_size < sizeof(T) ? opt->struct_size : sizeof(T));
+}
 
-struct LrmHostCtx;            // lrm_host.hip: per-handle state of the host-buffer entry points
+struct LrmHostCtx;            // host_pipeline.h: per-handle state of the host-buffer entry points
+struct lrm_index;
+// the LrmMapTune of a call on a handle: the caller's options (null: the built-in defaults) under the handle's LRM_*
+// overrides, then the debug vote limits (lrm_debug_set_vote_limits)
+void lrm_call_map_tune(const lrm_index *ix, const lrm_map_options *opt, LrmMapTune *out);
 struct lrm_index {
     void *d_blob;
     uint64_t blob_bytes;
@@ -297,15 +307,29 @@ void lrm_set_error(const char *fmt, ...);
 // (affinity mask, cgroup CPU quota) -- a GPU box hands a job 16 of its 256 hardware threads, and a team of 256 on a
 // quota of 16 is throttled to a crawl.  OMP_NUM_THREADS still lowers it.
 int lrm_host_threads(void);
-int lrm_require_device(int device);
+int lrm_require_device(int device);                 // hipSetDevice + "no CPU fallback" error
 int lrm_workspace_create_parts(lrm_workspace **out, lrm_index *idx, uint64_t n_max, uint32_t max_len, uint32_t seed_len,
                                uint32_t thres, int parts);
 int lrm_ws_take_error(lrm_workspace *ws);        // -2 + message if a kernel raised the workspace's sticky error word
-void lrm_host_ctx_free(lrm_index *idx);          // lrm_host.hip            // hipSetDevice + "no CPU fallback" error
+void lrm_host_ctx_free(lrm_index *idx);          // host_pipeline.hip
 void lrm_time_begin(lrm_workspace *ws, int kernel, void *stream);
 void lrm_time_end(lrm_workspace *ws, void *stream);
 
+// index_image.hip: a handle over an image in device memory (owns: the handle frees it); the replicas of a group are made
+// with it too (index_group.hip)
+int lrm_index_make_handle(lrm_index **out, void *d_blob, uint64_t bytes, int device, int owns, const LrmBlobHeader &h,
+                          const lrm_index_options *opt);
+// ... and pack + streamed upload of the reference's arrays to one device
+int lrm_index_upload_one(lrm_index **out, const lrm_dna_fmi *fmi, const lrm_lc_hash *lch, const lrm_sa_mem *sa, const char *content,
+                         uint64_t con_len, const lrm_mta_entry *mta, int mta_len, int device, const lrm_index_options *opt);
+
 // launchers implemented in the .hip files (all asynchronous on `stream`)
+// the dense result image of a unit of the host pipeline (result_pack_kernels.hip): rows of d_len[i] bytes (up to row_cap)
+// to d_dense + d_off[i]; the run-length CIGAR text of every row (d_dense null: only its length, into d_tlen)
+int lrm_launch_pack_rows(const uint8_t *d_src, uint64_t pitch, uint64_t row_cap, const uint32_t *d_len, const uint64_t *d_off,
+                         uint8_t *d_dense, uint64_t rows, void *stream);
+int lrm_launch_cigar_text(const uint8_t *d_store, uint64_t pitch, const int32_t *d_n_ops, const int32_t *d_score, const int32_t *d_meta_r,
+                          uint32_t *d_tlen, const uint64_t *d_off, uint8_t *d_dense, uint64_t rows, void *stream);
 int lrm_launch_seed(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint64_t stride,
                     const uint32_t *d_lens, uint64_t n, uint32_t seed_len,
                     uint32_t thres, lrm_entry *d_best, const LrmMapTune &mt, void *stream, uint8_t *d_phase_out = nullptr);
@@ -370,7 +394,7 @@ struct LrmSplitArgs {                                      // lrm_split_batch_de
 int lrm_launch_split(lrm_index *idx, lrm_workspace *ws_seg, const LrmSplitArgs &a, const lrm_split_dev &out, uint64_t *n_seg,
                      void *stream);
 void lrm_split_scratch_free(lrm_workspace *ws);
-int lrm_wait_event(void *ev);                              // lrm_host.hip: the sleep-poll every host wait of this library uses
+int lrm_wait_event(void *ev);                              // host_pipeline.hip: the sleep-poll every host wait of this library uses
 int lrm_launch_debug_seed(lrm_index *idx, const char *d_read, uint32_t len, uint32_t seed_len,
                           uint64_t *d_reads2, uint64_t words, int32_t *d_j, uint64_t *d_rr,
                           uint64_t *d_k, uint64_t *d_l, uint64_t cap, void *stream);

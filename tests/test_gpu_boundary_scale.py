@@ -25,7 +25,7 @@ from longreadmapper_amd.capi import lib
 
 pytestmark = pytest.mark.gpu
 
-# lrm_host.hip: RING_CHUNK (bytes of one pinned piece of the download ring) and N_RING (pieces of the ring).  A download
+# host_pipeline.h: RING_CHUNK (bytes of one pinned piece of the download ring) and N_RING (pieces of the ring).  A download
 # of more than N_RING pieces re-uses the first chunk: the ring has lapped.
 RING_CHUNK, N_RING = 16 << 20, 16
 N_READS, L_MIN, L_MAX = 38_000, 2_000, 18_000
