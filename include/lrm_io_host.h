@@ -27,8 +27,8 @@ typedef struct lrm_read_batch {
     uint32_t *lens;
     char **names;
     char **quals;
-    /* storage behind names[] / quals[] when the batch came from the parallel parser (NULL: one allocation per entry),
-     * and whether seqs is the caller's buffer (lrm_reader_next_into); lrm_read_batch_free looks at them */
+    /* storage behind names[] / quals[] (one block each), and whether seqs is the caller's buffer
+     * (lrm_reader_next_into); lrm_read_batch_free looks at them */
     char *name_arena, *qual_arena;
     int seqs_borrowed;
 } lrm_read_batch;

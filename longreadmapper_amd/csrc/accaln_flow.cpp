@@ -1,0 +1,451 @@
+// accaln_flow.cpp -- `accaln genome reads` on the GPU path (lrm_accaln, lrm_accaln_opt, lrm_accaln_mapq,
+// include/lrm_io_host.h): single_end() (alnmain.c:277-551) as a pipeline of threads around the asynchronous batch calls.
+// Host-side C++; the kernels are reached only through the C-ABI.
+//
+// A loader thread parses batch k+2 (parallel FASTQ parser, sequences straight into a pinned buffer), the calling thread
+// keeps two batches in flight on the device (lrm_map_batch_submit / _wait, dense results DMA'd into pinned memory), a
+// formatter thread turns batch k-1 into SAM text in parallel and a flusher thread writes the parts of the text before
+// it with parallel pwrites.  Four sets of buffers go round.  The reference does the stages one after the other; at
+// device mapping rates the text stages are the whole run time, so they have to overlap AND be parallel.  Output is
+// identical: batches are written in input order.
+#include <hip/hip_runtime_api.h>
+#include <sys/stat.h>
+#include <fcntl.h>
+#include <unistd.h>
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <condition_variable>
+#include <cstddef>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <deque>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+#include "../../include/lrm_index_host.h"
+#include "sam_text.h"
+#include "lrm_internal.h"
+
+namespace {
+
+// bounded hand-off between two stages of the pipeline
+template <typename T>
+struct StageQueue {
+    std::mutex m;
+    std::condition_variable cv;
+    std::deque<T> q;
+    size_t cap;
+    bool closed = false;
+    explicit StageQueue(size_t c) : cap(c) {}
+    bool push(T v) {                                     // false: the queue was closed by the consumer (an error downstream)
+        std::unique_lock<std::mutex> lk(m);
+        cv.wait(lk, [&] { return q.size() < cap || closed; });
+        if (closed) return false;
+        q.push_back(std::move(v));
+        cv.notify_all();
+        return true;
+    }
+    bool pop(T &v) {                                     // false: closed and drained
+        std::unique_lock<std::mutex> lk(m);
+        cv.wait(lk, [&] { return !q.empty() || closed; });
+        if (q.empty()) return false;
+        v = std::move(q.front());
+        q.pop_front();
+        cv.notify_all();
+        return true;
+    }
+    void close() { std::lock_guard<std::mutex> lk(m); closed = true; cv.notify_all(); }
+};
+
+// what lrm_split_batch writes for one batch: pageable buffers grown on demand, and the table that points at them
+struct SplitBufs {
+    lrm_split_out out;
+    std::vector<lrm_segment> seg;
+    std::vector<char> rows;
+    std::vector<uint8_t> store;
+    std::vector<uint32_t> lens;
+    std::vector<lrm_entry> best;
+    std::vector<lrm_cigar> cig;
+    std::vector<int> score, meta_r;
+    std::vector<lrm_seq_meta> meta;
+    std::vector<lrm_anchor> anchor;
+    std::vector<lrm_clip> clip;
+    SplitBufs() { memset(&out, 0, sizeof(out)); }
+    // an empty table for k == 0, else room for k segments with rows and op bytes at these strides
+    lrm_split_out *fit(uint64_t k, uint64_t row_stride, uint64_t store_stride) {
+        memset(&out, 0, sizeof(out));
+        if (k == 0) return &out;
+        auto room = [](auto &v, uint64_t n) { v.resize((size_t) n); return v.data(); };
+        out.cap = k; out.row_stride = row_stride; out.store_stride = store_stride;
+        out.seg = room(seg, k); out.rows = room(rows, k * row_stride); out.store = room(store, k * store_stride);
+        out.lens = room(lens, k); out.best = room(best, k); out.cig = room(cig, k); out.score = room(score, k);
+        out.meta_r = room(meta_r, k); out.meta = room(meta, k); out.anchor = room(anchor, k); out.clip = room(clip, k);
+        return &out;
+    }
+};
+
+// one batch on its way through the pipeline, with the caller-side buffers of the hot path (pinned: the DMA engines
+// read the reads and write the dense op bytes straight from / into them); recycled.  A set belongs to the thread that
+// popped it from a queue, until that thread pushes it on.
+struct BatchSet {
+    lrm_read_batch b;
+    char *reads_pin = nullptr; uint64_t reads_cap = 0;           // written by the pinner, read by the others once pin_ready is set
+    uint8_t *store_pin = nullptr; uint64_t store_cap = 0;
+    std::atomic<bool> pin_ready{false};          // the pinner thread has given this set its pinned buffers
+    uint8_t *store_pg = nullptr; uint64_t store_pg_cap = 0;      // pageable stand-in until then (or when a batch outgrows the pinned one)
+    uint8_t *store = nullptr;
+    std::vector<lrm_entry> best;
+    std::vector<lrm_cigar> cig;
+    std::vector<int> score, meta_r;
+    std::vector<lrm_seq_meta> meta;
+    uint64_t sstride = 0;
+    lrm_ticket *ticket = nullptr;
+    SplitBufs sp;                                // split reads: the second pass over this batch's clipped ends (lrm_split_batch)
+    std::vector<lrm_mapq> mq;                    // lrm_accaln_mapq: the records of the batch
+    BatchSet() { memset(&b, 0, sizeof(b)); }
+    ~BatchSet() { lrm_host_free(reads_pin); lrm_host_free(store_pin); free(store_pg); }
+};
+
+struct TextBatch { std::vector<std::string> parts; };   // the SAM text of one batch, one part per formatting thread
+
+struct StageError {                                      // lrm_last_error() is thread-local: stages report through this
+    std::mutex m;
+    int rc = 0;
+    std::string msg;
+    void set(int code) {
+        std::lock_guard<std::mutex> lk(m);
+        if (!rc) { rc = code; msg = lrm_last_error(); }
+    }
+    int get() { std::lock_guard<std::mutex> lk(m); return rc; }
+};
+
+double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// One run of the flow.  The fields are what the threads share; next to each: which thread writes it while they run
+// ("main" is the caller's thread, which submits and waits).  The member functions are the stages.
+struct AccalnRun {
+    static constexpr int NSETS = 4;                      // loading, two on the device, formatting
+    // ---- written by main before the threads start, only read from then on ----
+    const lrm_params p;
+    const lrm_gact_params gp;
+    int device;
+    const bool mapq;                                     // the mapping-quality records come back with every batch and are printed
+    const bool verbose = getenv("LRM_HOST_VERBOSE") != nullptr;            // stage times on stderr (tuning aid)
+    lrm_map_options mopt;
+    bool split = false;                                  // after a batch's wait its clipped ends go through lrm_split_batch
+    bool want_pinned = false;
+    lrm_host_index hi;
+    lrm_index *gpu = nullptr;
+    lrm_reader *rd = nullptr;                            // (the loader is its only user)
+    int out_fd = -1;
+    const char *sam_path = nullptr;
+    const uint64_t bs;
+    const int io_threads = lrm_host_threads() > 2 ? lrm_host_threads() / 2 : 1;     // loader and formatter share the host
+    double t_begin = now(), t_read_idx = 0, t_upload = 0;
+    std::vector<std::unique_ptr<BatchSet>> sets;
+    // ---- the hand-offs (their own locks) ----
+    StageQueue<BatchSet *> free_sets{NSETS}, loaded{NSETS}, mapped{NSETS};  // to the loader, loader -> main, main -> formatter
+    StageQueue<std::unique_ptr<TextBatch>> texts{2}, free_texts{3};         // formatter -> flusher, and back
+    StageError err;                                      // any stage; the first error stays
+    // ---- the size of the pinned buffers, under dims_m ----
+    std::mutex dims_m;
+    std::condition_variable dims_cv;
+    uint64_t dim_reads = 0, dim_store = 0;               // loader (once, from the first batch); the pinner reads them
+    bool dims_known = false;                             // loader
+    bool first_submitted = false, dims_stop = false;     // main
+    // ---- each stage's own ----
+    double t_load = 0;                                   // loader
+    double t_map = 0;                                    // main
+    std::deque<BatchSet *> inflight;                     // main: submitted and not yet waited for, oldest first
+    double t_fmt = 0;                                    // formatter
+    uint64_t total = 0, valid = 0;                       // formatter
+    double t_write = 0;                                  // flusher
+    uint64_t out_off = 0;                                // flusher (main sets it behind the header before the threads start)
+
+    AccalnRun(lrm_params p_, lrm_gact_params gp_, int device_, bool mapq_)
+        : p(p_), gp(gp_), device(device_), mapq(mapq_), bs(p_.batch_size ? p_.batch_size : 1000) {}
+
+    // op bytes per read: alnmain.c:316-320, a multiple of 16; the anchored mode's targets are an eighth longer than the reads
+    uint64_t store_stride_of(uint64_t max_len) const {
+        const uint64_t s = ((mopt.anchored ? 2 * max_len + max_len / 8 + 2 : 2 * max_len) + 15) & ~15ull;
+        return s > 0 ? s : (uint64_t) 16;
+    }
+    void recycle(BatchSet *s) { lrm_read_batch_free(&s->b); free_sets.push(s); }
+
+    // user: only the fields that change WHAT is computed are taken (anchored, anchor_min_len, clip, clip_penalty,
+    // clip_end_bonus, split, split_min_len); the shape of the pipeline is this flow's own choice
+    int take_options(const lrm_map_options *user) {
+        // The fields came in three groups, and a group counts only if the caller's struct holds all of it (a caller built
+        // before the clip fields existed has them inside its zeroed reserved words or not at all).  struct_size == 0
+        // means "take nothing" here -- not "take everything" as in lrm_options_over_defaults.
+        lrm_map_options u;
+        memset(&u, 0, sizeof(u));
+        lrm_options_take_fields(&u, user, offsetof(lrm_map_options, anchored), offsetof(lrm_map_options, clip));
+        lrm_options_take_fields(&u, user, offsetof(lrm_map_options, clip), offsetof(lrm_map_options, split));
+        lrm_options_take_fields(&u, user, offsetof(lrm_map_options, split), offsetof(lrm_map_options, split_min_len) + sizeof(uint32_t));
+        if (u.split && !u.clip) { lrm_set_error("lrm_map_options.split needs lrm_map_options.clip"); return -1; }
+        lrm_map_options_init(&mopt);
+        mopt.cigar_text = 1;                        // parse_cigar (alnmain.c:497-498) runs on the device: the SAM CIGAR text comes back
+        mopt.copy_threads = 2;                      // the parser and the formatter need the cores
+        mopt.keep_reads = 1;                        // reverse-strand reads are reverse-complemented by the formatter as it copies them
+        if (u.anchored) { mopt.anchored = 1; mopt.anchor_min_len = u.anchor_min_len; }
+        if (u.clip) { mopt.clip = 1; mopt.clip_penalty = u.clip_penalty; mopt.clip_end_bonus = u.clip_end_bonus; }
+        split = u.clip && u.split;
+        if (split) { mopt.split = 1; mopt.split_min_len = u.split_min_len; }
+        return 0;
+    }
+
+    // init() (alnmain.c:179-256) behind the index files: the device image, the SAM file with its header, the reader
+    int begin(const char *reads_path, const char *sam, long rg_id) {
+        t_read_idx = now();
+        sam_path = sam;
+        struct stat st;
+        const bool sized = stat(reads_path, &st) == 0;            // (a file that cannot be sized is under neither rule)
+        lrm_index_options iopt;
+        lrm_index_options_init(&iopt);
+        // a reads file below 64 GiB (some tens of Gbp) does not repay the 0.7-2 s the 64 GiB seed table costs at upload
+        if (sized && (uint64_t) st.st_size < (64ull << 30)) iopt.lc_long_max = 15;
+        // Pinning the batch buffers (0.2 s per GB to pin and to release, and the device stalls while the runtime pins)
+        // pays from a few tens of Gbp on: reads files below 16 GiB run through pageable buffers.
+        want_pinned = sized && (uint64_t) st.st_size >= (16ull << 30);
+        int rc = lrm_index_upload_opt(&gpu, &hi.fmi, &hi.lch, &hi.sa, hi.content, hi.con_len, hi.mta, hi.mta_len, &device, 1, &iopt);
+        t_upload = now();
+        if (rc) return rc;
+        out_fd = open(sam_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (out_fd < 0) { lrm_set_error("cannot create: %s", sam_path); return -1; }
+        uint64_t hl = 0;
+        char *h = lrm_sam_header(hi.mta, hi.mta_len, rg_id, &hl);
+        if (pwrite(out_fd, h, hl, 0) != (ssize_t) hl) { lrm_set_error("cannot write: %s", sam_path); rc = -1; }
+        out_off = hl;
+        free(h);
+        return rc ? rc : lrm_reader_open(&rd, reads_path);
+    }
+
+    // Pinning memory costs ~0.2 s per GB: a thread of its own sizes the sets' pinned buffers from the first batch
+    // (+ 1/8) while the first batches already run through pageable memory (staged upload, staged dense download).
+    void pinner() {
+        if (hipSetDevice(device) != hipSuccess) { (void) hipGetLastError(); }
+        {
+            std::unique_lock<std::mutex> lk(dims_m);
+            // (after the first submit: that call builds the handle's host context -- streams, staging, mirrors -- and
+            //  would queue behind the runtime's lock while gigabytes are being pinned here)
+            dims_cv.wait(lk, [&] { return (dims_known && first_submitted) || dims_stop; });
+            if (!dims_known || dims_stop || !want_pinned) return;
+        }
+        for (auto &sp : sets) {
+            { std::lock_guard<std::mutex> lk(dims_m); if (dims_stop) return; }
+            BatchSet *s = sp.get();
+            s->reads_pin = (char *) lrm_host_alloc(dim_reads);
+            s->store_pin = (uint8_t *) lrm_host_alloc(dim_store);
+            if (!s->reads_pin || !s->store_pin) { lrm_host_free(s->reads_pin); lrm_host_free(s->store_pin); s->reads_pin = nullptr; s->store_pin = nullptr; return; }
+            s->reads_cap = dim_reads; s->store_cap = dim_store;
+            s->pin_ready.store(true, std::memory_order_release);
+            if (verbose) fprintf(stderr, "[lrm accaln] %.3f pinned a set (%.2f + %.2f GB)\n", now() - t_upload, dim_reads / 1e9, dim_store / 1e9);
+        }
+    }
+
+    void loader() {                                                           // alnmain.c:302
+        BatchSet *s = nullptr;
+        while (!err.get() && free_sets.pop(s)) {
+            const double t0 = now();
+            const bool pinned = s->pin_ready.load(std::memory_order_acquire);
+            int64_t n = lrm_reader_next_into(rd, bs, &s->b, pinned ? s->reads_pin : nullptr, pinned ? s->reads_cap : 0);
+            t_load += now() - t0;
+            if (verbose) fprintf(stderr, "[lrm accaln] %.3f loaded %lld reads in %.3f s (%s)\n", now() - t_upload, (long long) n, now() - t0, pinned ? "pinned" : "pageable");
+            if (n < 0) { err.set(-1); break; }
+            if (n == 0) { recycle(s); break; }
+            if (!dims_known) {
+                std::lock_guard<std::mutex> lk(dims_m);
+                const uint64_t rb = s->b.n * s->b.stride, sb = s->b.n * (store_stride_of(s->b.max_len) + 16);
+                dim_reads = rb + rb / 8 + 4096; dim_store = sb + sb / 8 + 4096;
+                dims_known = true;
+                dims_cv.notify_all();
+            }
+            if (!loaded.push(s)) break;
+        }
+        loaded.close();
+    }
+
+    // PART 3, alnmain.c:458-527, in two stages: the formatter turns a mapped batch into SAM text (one part per thread)
+    // and gives the set back; the flusher writes the parts of the previous batch with parallel pwrites meanwhile.
+    void formatter() {
+        BatchSet *s = nullptr;
+        while (mapped.pop(s)) {
+            std::unique_ptr<TextBatch> tb;
+            if (!err.get() && free_texts.pop(tb)) {
+                const uint64_t n = s->b.n;
+                const double t0 = now();
+                const SamBatch sb = {&s->b, hi.mta, hi.mta_len, s->cig.data(), s->score.data(), s->meta.data(), s->meta_r.data(), n,
+                                     /* cigar_is_text */ true, /* revcomp_here */ true, split ? &s->sp.out : nullptr, mapq ? s->mq.data() : nullptr};
+                sam_format_parts(sb, io_threads, tb->parts);
+                t_fmt += now() - t0;
+                if (verbose) fprintf(stderr, "[lrm accaln] %.3f formatted %llu reads in %.3f s\n", now() - t_upload, (unsigned long long) n, now() - t0);
+                total += n;
+                for (uint64_t i = 0; i < n; ++i) valid += (s->score[i] >= 0 && s->meta_r[i] != 0) ? 1 : 0;   // alnmain.c:464-469,489-491
+                if (!texts.push(std::move(tb))) err.set(-1);
+            }
+            recycle(s);
+        }
+        texts.close();
+    }
+
+    void flusher() {
+        std::unique_ptr<TextBatch> tb;
+        while (texts.pop(tb)) {
+            if (!err.get()) {
+                const double t1 = now();
+                const std::vector<std::string> &parts = tb->parts;
+                const std::vector<uint64_t> at = sam_part_offsets(parts, out_off);
+                bool ok = true;
+#pragma omp parallel for schedule(static, 1) num_threads((int) parts.size()) reduction(&& : ok)
+                for (size_t k = 0; k < parts.size(); ++k) {
+                    size_t done = 0;
+                    while (done < parts[k].size()) {
+                        const ssize_t w = pwrite(out_fd, parts[k].data() + done, parts[k].size() - done, (off_t) (at[k] + done));
+                        if (w <= 0) { ok = false; break; }
+                        done += (size_t) w;
+                    }
+                }
+                out_off = at[parts.size()];
+                if (!ok) { lrm_set_error("cannot write: %s", sam_path); err.set(-1); }
+                t_write += now() - t1;
+                if (verbose) fprintf(stderr, "[lrm accaln] %.3f wrote %.2f GB in %.3f s\n", now() - t_upload, (at[parts.size()] - at[0]) / 1e9, now() - t1);
+            }
+            if (!free_texts.push(std::move(tb))) break;
+        }
+        free_texts.close();
+    }
+
+    // the second pass over a batch that has come back: size the segment buffers from the plan, then lrm_split_batch
+    int split_pass(BatchSet *s) {
+        const uint64_t n = s->b.n;
+        std::vector<lrm_clip> cl((size_t) n);
+        uint32_t longest = 0;
+        for (uint64_t i = 0; i < n; ++i) {
+            cl[i].left = cl[i].right = 0;
+            if (s->meta_r[i] != 0 && s->score[i] != -1) (void) lrm_clip_of_cigar(&s->cig[i], 1, &cl[i].left, &cl[i].right);
+            longest = std::max(longest, std::max(cl[i].left, cl[i].right));
+        }
+        uint64_t k = 0;
+        if (lrm_split_plan(s->b.lens, cl.data(), n, mopt.split_min_len, nullptr, 0, &k) == -1) return -1;
+        lrm_split_out *o = s->sp.fit(k, ((uint64_t) longest + 16) & ~15ull, store_stride_of(longest));
+        if (k == 0) return 0;
+        return lrm_split_batch(gpu, s->b.seqs, s->b.stride, s->b.lens, n, s->cig.data(), s->meta.data(), s->meta_r.data(), p, gp, &mopt, o);
+    }
+
+    void finish_oldest() {
+        BatchSet *s = inflight.front();
+        inflight.pop_front();
+        const double t0 = now();
+        int mrc = lrm_map_batch_wait(s->ticket);
+        if (!mrc && split) mrc = split_pass(s);
+        t_map += now() - t0;
+        if (verbose) fprintf(stderr, "[lrm accaln] %.3f waited %.3f s for a batch of %llu\n", now() - t_upload, now() - t0, (unsigned long long) s->b.n);
+        s->ticket = nullptr;
+        if (mrc) { err.set(-1); recycle(s); return; }
+        (void) mapped.push(s);                                                // (only this thread closes `mapped`, behind the last batch)
+    }
+
+    // the result buffers of the batch in s: the pinned store if it is there and large enough, else a pageable one
+    bool fit_results(BatchSet *s) {
+        const size_t n = (size_t) s->b.n;
+        s->best.resize(n); s->cig.resize(n); s->score.resize(n); s->meta_r.resize(n); s->meta.resize(n);
+        if (mapq) s->mq.resize(n);
+        s->sstride = store_stride_of(s->b.max_len);
+        if (s->pin_ready.load(std::memory_order_acquire) && n * s->sstride <= s->store_cap) { s->store = s->store_pin; return true; }
+        if (n * s->sstride > s->store_pg_cap) {
+            free(s->store_pg);
+            s->store_pg_cap = n * s->sstride;
+            s->store_pg = (uint8_t *) malloc(s->store_pg_cap ? s->store_pg_cap : 1);
+            if (!s->store_pg) { s->store_pg_cap = 0; lrm_set_error("out of memory"); return false; }
+        }
+        s->store = s->store_pg;
+        return true;
+    }
+
+    // PART 1 + PART 2 in one device pass, asynchronously: two batches on the device, one queued behind them
+    void submit_loop() {
+        BatchSet *s = nullptr;
+        while (loaded.pop(s)) {
+            if (err.get()) { recycle(s); continue; }                          // drain what the loader already parsed
+            if (!fit_results(s)) { err.set(-1); recycle(s); continue; }
+            const double t0 = now();
+            const int src = lrm_map_batch_submit_mapq(gpu, s->b.seqs, s->b.stride, s->b.lens, s->b.n, p, gp, s->best.data(), s->cig.data(),
+                                                      s->store, s->sstride, s->score.data(), s->meta.data(), s->meta_r.data(), &mopt,
+                                                      mapq ? s->mq.data() : nullptr, &s->ticket);
+            t_map += now() - t0;
+            if (verbose) fprintf(stderr, "[lrm accaln] %.3f submitted %llu reads (%s store) in %.3f s\n", now() - t_upload, (unsigned long long) s->b.n, s->store == s->store_pin ? "pinned" : "pageable", now() - t0);
+            if (!first_submitted) { { std::lock_guard<std::mutex> lk(dims_m); first_submitted = true; } dims_cv.notify_all(); }
+            if (src) { err.set(-1); recycle(s); continue; }
+            inflight.push_back(s);
+            if (inflight.size() >= 3) finish_oldest();
+        }
+        while (!inflight.empty()) finish_oldest();
+    }
+
+    // all batches: starts the stages, submits on this thread, and takes everything down again in the order that matters
+    int run() {
+        for (int k = 0; k < NSETS; ++k) { sets.emplace_back(new BatchSet); free_sets.push(sets.back().get()); }
+        for (int k = 0; k < 3; ++k) free_texts.push(std::unique_ptr<TextBatch>(new TextBatch));
+        std::thread pin(&AccalnRun::pinner, this), load(&AccalnRun::loader, this), fmt(&AccalnRun::formatter, this), flush(&AccalnRun::flusher, this);
+        submit_loop();
+        mapped.close();
+        free_sets.close();
+        load.join();
+        fmt.join();
+        flush.join();
+        { std::lock_guard<std::mutex> lk(dims_m); dims_stop = true; }
+        dims_cv.notify_all();
+        pin.join();
+        const int rc = err.get();
+        if (rc) lrm_set_error("%s", err.msg.c_str());
+        const double t_done = now();
+        if (gpu) { lrm_index_free(gpu); gpu = nullptr; }                      // before the pinned buffers of the sets go
+        sets.clear();
+        if (verbose) fprintf(stderr, "[lrm accaln] last batch written %.2f s after the upload; freeing the device image and the pinned sets %.2f s\n",
+                             t_done - t_upload, now() - t_done);
+        return rc;
+    }
+
+    void end() {
+        if (rd) lrm_reader_close(rd);
+        if (out_fd >= 0) close(out_fd);
+        if (verbose)
+            fprintf(stderr, "[lrm accaln] index files %.2f s, upload %.2f s, batches %.2f s wall (busy: loader %.2f, device waits %.2f, "
+                            "formatter %.2f, write %.2f)\n", t_read_idx - t_begin, t_upload - t_read_idx, now() - t_upload, t_load, t_map,
+                    t_fmt, t_write);
+        if (gpu) lrm_index_free(gpu);
+        lrm_host_index_free(&hi);
+    }
+};
+
+}  // namespace
+
+// mapq: the mapping-quality records come back with every batch, column 5 and v1:i / v2:i print them (lrm_sam_format_mapq)
+extern "C" int lrm_accaln_mapq(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
+                               lrm_gact_params gp, int device, long rg_id, uint64_t *total_out, uint64_t *valid_out,
+                               const lrm_map_options *user, int mapq) {
+    AccalnRun r(p, gp, device, mapq != 0);
+    if (r.take_options(user)) return -1;
+    if (lrm_host_index_read(genome, &r.hi)) return -1;
+    int rc = r.begin(reads_path, sam_path, rg_id);
+    if (rc == 0) rc = r.run();
+    r.end();
+    if (total_out) *total_out = r.total;
+    if (valid_out) *valid_out = r.valid;
+    return rc;
+}
+extern "C" int lrm_accaln_opt(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
+                              lrm_gact_params gp, int device, long rg_id, uint64_t *total_out, uint64_t *valid_out,
+                              const lrm_map_options *user) {
+    return lrm_accaln_mapq(genome, reads_path, sam_path, p, gp, device, rg_id, total_out, valid_out, user, 0);
+}
+extern "C" int lrm_accaln(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
+                          lrm_gact_params gp, int device, long rg_id, uint64_t *total_out, uint64_t *valid_out) {
+    return lrm_accaln_mapq(genome, reads_path, sam_path, p, gp, device, rg_id, total_out, valid_out, nullptr, 0);
+}

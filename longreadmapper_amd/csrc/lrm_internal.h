@@ -130,6 +130,12 @@ template <typename T>
 static inline void lrm_options_over_defaults(T *o, const T *opt) {
     if (opt) memcpy(o, opt, opt->struct_size && opt->struct_size < sizeof(T) ? opt->struct_size : sizeof(T));
 }
+// the bytes [from, to) of a caller's options struct into *o, if the caller's struct_size says it holds all of them
+// (here 0 means: it holds nothing -- the rule of lrm_accaln_opt, which takes a few fields and leaves the rest)
+template <typename T>
+static inline void lrm_options_take_fields(T *o, const T *opt, size_t from, size_t to) {
+    if (opt && opt->struct_size >= to) memcpy((char *) o + from, (const char *) opt + from, to - from);
+}
 
 struct LrmHostCtx;            // host_pipeline.h: per-handle state of the host-buffer entry points
 struct lrm_index;
