@@ -30,6 +30,7 @@
 #include "../../include/lrm_index_host.h"
 #include "sam_text.h"
 #include "lrm_internal.h"
+#include "extend_stage.h"
 
 namespace {
 

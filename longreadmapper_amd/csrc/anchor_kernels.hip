@@ -2,7 +2,7 @@
 //
 //   anchor_scan     the longest exact match of a read on the LRM_ANCHOR_DIAGS diagonals around its voted locus
 //   anchor_jobs     the job table (2 rows per read: right job, left job) and the job read rows
-//   (extension)     ONE launch of the unchanged extension kernels over the job table (lrm_gact_launch_jobs)
+//   (extension)     ONE launch of the unchanged extension kernels over the job table (lrm_gact_run_jobs, extend_launch.hip)
 //   anchor_clip     (lrm_map_options.clip) per job: the best-scoring prefix of its op bytes and what that prefix holds
 //   anchor_stitch   reverse(left ops) ++ right ops into the caller's store, sums, moved meta, lrm_anchor records; with
 //                   the clip records: the kept prefixes between runs of 'S'
@@ -20,11 +20,12 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include "lrm_hip_util.h"
+#include "extend_stage.h"
 #include "seq_bytes.h"
 #include "anchor_clip.h"
+#include "anchor_plan.h"                      // the key, AnPlan, the lrm_anchor record
 
 #define AN_SEG_WORDS 64                       // words (of 32 bases) per scan segment: 2048 bases
-#define AN_HALF (LRM_ANCHOR_DIAGS / 2)
 #define AN_CHUNK 4096                         // bytes of a row one workgroup of the job / stitch kernels moves
 static_assert(LRM_ANCHOR_DIAGS == 64, "one lane per diagonal");
 
@@ -44,45 +45,7 @@ struct LrmAnchorScratch {
 
 struct __attribute__((packed, aligned(1))) An16 { uint32_t x, y, z, w; };     // 16 bytes at any address
 
-// ---- the key: larger is better -----------------------------------------------------------------------------------
-// bits 40..63 length | 33..38 32 - |delta| | 32 delta < 0 | 0..31 ~j : longest run, then smallest |delta|, then
-// smallest delta, then smallest j
-__host__ __device__ static inline uint64_t an_key(uint32_t len, int delta, uint32_t j) {
-    const uint32_t ad = (uint32_t) (delta < 0 ? -delta : delta);
-    return ((uint64_t) len << 40) | ((uint64_t) (AN_HALF - ad) << 33) | ((uint64_t) (delta < 0) << 32) | (uint64_t) (0xFFFFFFFFu - j);
-}
-
-struct AnPlan {                               // what the key of a read means for its two jobs
-    uint32_t flags, j, len;
-    int32_t delta;
-    uint64_t p;                               // text position of read[j]
-    uint64_t left_loc;                        // start of the left job's target on the reverse-complement half
-    uint32_t right_tlen, left_tlen;
-};
-__host__ __device__ static inline AnPlan an_plan(uint64_t key, uint64_t L, uint32_t n, uint64_t S, uint64_t len_s) {
-    AnPlan a = {};
-    if (key == 0) { a.flags = LRM_ANCHOR_FALLBACK; a.p = L; return a; }
-    a.len = (uint32_t) (key >> 40);
-    const int ad = AN_HALF - (int) ((key >> 33) & 63u);
-    a.delta = ((key >> 32) & 1u) ? -ad : ad;
-    a.j = 0xFFFFFFFFu - (uint32_t) key;
-    a.p = (uint64_t) ((int64_t) L + a.delta + (int64_t) a.j);
-    a.flags = LRM_ANCHOR_ANCHORED;
-    const uint64_t nr = n - a.j, wr = nr + (nr + 7) / 8, room_r = S + len_s - a.p;
-    a.right_tlen = (uint32_t) (wr < room_r ? wr : room_r);
-    if (wr > room_r) a.flags |= LRM_ANCHOR_RIGHT_CLIPPED;
-    if (a.j == 0) { a.flags |= LRM_ANCHOR_NO_LEFT; return a; }
-    const uint64_t nl = a.j, wl = nl + (nl + 7) / 8, room_l = a.p - S;
-    a.left_tlen = (uint32_t) (wl < room_l ? wl : room_l);
-    if (wl > room_l) a.flags |= LRM_ANCHOR_LEFT_CLIPPED;
-    a.left_loc = 2 * S + 2 * len_s - a.p;     // mirror of p - 1: y = 2S + 2 len_s - 1 - x
-    return a;
-}
-
 // ---- scan ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t an_bits(int lo, int hi) {        // bits lo .. hi-1, 0 <= lo < hi <= 32
-    return (hi >= 32 ? 0xFFFFFFFFu : ((1u << hi) - 1u)) & ~((1u << lo) - 1u);
-}
 __device__ __forceinline__ bool an_is_acgt(uint32_t c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; }
 
 struct AnScan {
@@ -118,7 +81,7 @@ struct AnScan {
                 x |= (uint32_t) !(a == b && an_is_acgt(a)) << k;
             }
         }
-        return x | ~an_bits(lo, hi);
+        return x | ~bit_range<uint32_t>(lo, hi);
     }
 };
 
@@ -190,13 +153,7 @@ __global__ __launch_bounds__(256) void anchor_scan_kernel(const char *__restrict
     }
     if (own && run >= min_len && run > best_len) { best_len = run; best_j = (uint32_t) (32 * w) - run; }
 
-    uint64_t key = best_len ? an_key(best_len, delta, best_j) : 0;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const uint32_t lo = (uint32_t) __shfl_xor((int) (uint32_t) key, o), hi = (uint32_t) __shfl_xor((int) (uint32_t) (key >> 32), o);
-        const uint64_t other = ((uint64_t) hi << 32) | lo;
-        key = other > key ? other : key;
-    }
+    const uint64_t key = wave_max_u64(best_len ? an_key(best_len, delta, best_j) : 0);     // 0 = none: the identity of the maximum
     if (lane == 0 && key) atomicMax(keys + r, (unsigned long long) key);
 }
 
@@ -209,8 +166,8 @@ __device__ __forceinline__ void an_fill_row(char *__restrict__ dst, const char *
     for (uint32_t k = c0 + 16 * tid; k < c1; k += 16 * 256) {
         if (k + 16 <= cnt) {
             const An16 v = *reinterpret_cast<const An16 *>(REV ? src + (cnt - 16 - k) : src + k);
-            *reinterpret_cast<uint4 *>(dst + k) = REV ? make_uint4(revcomp4(v.w), revcomp4(v.z), revcomp4(v.y), revcomp4(v.x))
-                                                      : make_uint4(v.x, v.y, v.z, v.w);
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+            *reinterpret_cast<uint4 *>(dst + k) = REV ? revcomp16([&](int e) { return w[e]; }) : make_uint4(w[0], w[1], w[2], w[3]);
         } else {
             for (uint32_t e = k; e < cnt; ++e) dst[e] = REV ? comp_base(src[cnt - 1 - e]) : src[e];
         }
@@ -384,18 +341,14 @@ __global__ __launch_bounds__(256) void anchor_stitch_kernel(const uint32_t *__re
     // target bases the left job consumed: its columns other than 'I' (with the clip records: counted there)
     uint32_t cnt = 0;
     for (uint32_t o = tid; o < (clip ? 0u : nl); o += 256) cnt += lrow[o] != (uint8_t) 'I';
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) cnt += (uint32_t) __shfl_xor((int) cnt, o);
-    if ((tid & 63) == 0) s_cnt[tid >> 6] = cnt;
+    cnt = wave_incl_scan(cnt);
+    if ((tid & 63) == 63) s_cnt[tid >> 6] = cnt;               // the last lane holds the wavefront's total
     __syncthreads();
     if (tid != 0) return;
     const uint32_t consumed = clip ? rec_l.z : s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
     n_ops[r] = (int32_t) total;
     score[r] = clip ? (int32_t) (rec_l.y + rec_r.y) : job_score[2 * r] + (left ? job_score[2 * r + 1] : 0);
-    lrm_anchor an;
-    an.text_pos = a.p; an.read_pos = a.j; an.len = a.len; an.delta = a.delta; an.left_ops = b1;
-    an.flags = a.flags | (cl ? LRM_ANCHOR_SOFT_LEFT : 0u) | (cr ? LRM_ANCHOR_SOFT_RIGHT : 0u);
-    anchors[r] = an;
+    anchors[r] = an_record(a, b1, (cl ? LRM_ANCHOR_SOFT_LEFT : 0u) | (cr ? LRM_ANCHOR_SOFT_RIGHT : 0u));
     if (clip_out) clip_out[r] = lrm_clip{cl, cr};
     if (a.flags & LRM_ANCHOR_ANCHORED) {           // meta moves to the alignment's first text base
         an_store_meta(meta + r, a.p - consumed, a.p - consumed - S, m.seq_id, m.strand);
@@ -404,25 +357,14 @@ __global__ __launch_bounds__(256) void anchor_stitch_kernel(const uint32_t *__re
     }
 }
 
-// debug tap: the record of one read straight from its key
-__global__ void anchor_record_kernel(const uint32_t *lens, const lrm_seq_meta *meta, const LrmMtaDev *mta,
-                                     const unsigned long long *keys, lrm_anchor *out) {
-    const lrm_seq_meta m = meta[0];
-    const AnPlan a = an_plan(keys[0], m.loc, lens[0], mta[m.seq_id].offset, mta[m.seq_id].seq_len);
-    lrm_anchor an;
-    an.text_pos = a.p; an.read_pos = a.j; an.len = a.len; an.delta = a.delta; an.left_ops = 0; an.flags = a.flags;
-    out[0] = an;
-}
-
 // ----------------------------------------------------------------------------------------
 // host side
 // ----------------------------------------------------------------------------------------
 void lrm_anchor_scratch_free(lrm_workspace *ws) {
     LrmAnchorScratch *s = ws ? ws->an : nullptr;
     if (!s) return;
-    void *bufs[] = {s->keys, s->job_reads, s->job_lens, s->job_tlens, s->job_meta, s->job_meta_r, s->job_nops, s->job_score,
-                    s->job_store, s->anchors, s->clip_recs};
-    for (void *b : bufs) if (b) (void) hipFree(b);
+    lrm_dev_free({s->keys, s->job_reads, s->job_lens, s->job_tlens, s->job_meta, s->job_meta_r, s->job_nops, s->job_score,
+                  s->job_store, s->anchors, s->clip_recs});
     lrm_bs_scratch_free(&s->bs);
     delete s;
     ws->an = nullptr;
@@ -439,7 +381,7 @@ static int anchor_scratch(lrm_workspace *ws, bool planar) {
     s->n_max = n; s->max_len = ws->max_len;
     s->job_stride = ((uint64_t) ws->max_len + 31) & ~15ull;
     s->job_store_stride = (lrm_anchored_store_stride(ws->max_len) + 15) & ~15ull;
-    struct { void **p; uint64_t bytes; } allocs[] = {
+    const LrmDevAlloc allocs[] = {
         {(void **) &s->keys, n * 8},
         {(void **) &s->job_reads, jobs * s->job_stride},
         {(void **) &s->job_lens, jobs * 4},
@@ -451,15 +393,8 @@ static int anchor_scratch(lrm_workspace *ws, bool planar) {
         {(void **) &s->job_store, jobs * s->job_store_stride},
         {(void **) &s->anchors, n * sizeof(lrm_anchor)},
     };
-    for (auto &a : allocs) {
-        if (hipMalloc(a.p, a.bytes) != hipSuccess) {
-            lrm_set_error("hipMalloc of %llu bytes of anchored-mode scratch failed", (unsigned long long) a.bytes);
-            lrm_anchor_scratch_free(ws);
-            return -1;
-        }
-        ws->bytes += a.bytes;
-    }
-    if (planar && lrm_bs_scratch_alloc(&s->bs, jobs, ws->max_len, ws->max_len + ws->max_len / 16 + 2, &ws->bytes)) {
+    if (lrm_dev_alloc_table(allocs, "bytes of anchored-mode scratch", &ws->bytes) ||
+        (planar && lrm_bs_scratch_alloc(&s->bs, jobs, ws->max_len, ws->max_len + ws->max_len / 16 + 2, &ws->bytes))) {
         lrm_anchor_scratch_free(ws);
         return -1;
     }
@@ -490,16 +425,16 @@ static int anchor_clip_params(LrmClipOpt *c) {
     return 0;
 }
 
-static int anchor_min_len(uint32_t min_len, uint32_t *out) {
+int lrm_anchor_min_len(uint32_t min_len, uint32_t *out) {
     if (min_len == 0) min_len = LRM_ANCHOR_MIN_DEFAULT;
     if (min_len < 12 || min_len > 64) { lrm_set_error("anchor_min_len %u outside [12, 64]", min_len); return -1; }
     *out = min_len;
     return 0;
 }
 
-// the scan over the reads at their loci; cpl: the text's planar image and pl the reads' (pack_reads), null: from bytes
-static int launch_scan(const LrmExtendBatch &b, const LrmIndexView &ix, const LrmBsScratch &pl, const uint64_t *cpl,
-                       uint32_t min_len, uint64_t *keys, hipStream_t stream) {
+int lrm_anchor_scan(const LrmExtendBatch &b, const LrmIndexView &ix, const LrmBsScratch &pl, const uint64_t *cpl,
+                    uint32_t min_len, uint64_t *keys, void *stream_) {
+    hipStream_t stream = (hipStream_t) stream_;
     const uint32_t nw = (b.max_len + 31) / 32;
     const uint32_t segs = nw ? (nw + AN_SEG_WORDS - 1) / AN_SEG_WORDS : 1;
     uint32_t grid;
@@ -518,7 +453,7 @@ int lrm_launch_extend_anchored(lrm_index *idx, lrm_workspace *ws, const LrmExten
     const uint64_t n = b.n;
     if (n == 0) return 0;
     LrmClipOpt clip = clip_;
-    if (lrm_gact_resolve_params(&gp) || anchor_min_len(min_len, &min_len) || anchor_clip_params(&clip)) return -1;
+    if (lrm_gact_resolve_params(&gp) || lrm_anchor_min_len(min_len, &min_len) || anchor_clip_params(&clip)) return -1;
     if (b.store_stride < lrm_anchored_store_stride(b.max_len)) {
         lrm_set_error("anchored extension: store_stride %llu < 2*max_len + max_len/8 + 2 = %llu",
                       (unsigned long long) b.store_stride, (unsigned long long) lrm_anchored_store_stride(b.max_len));
@@ -530,7 +465,7 @@ int lrm_launch_extend_anchored(lrm_index *idx, lrm_workspace *ws, const LrmExten
                       (unsigned long long) n, b.max_len);
         return -1;
     }
-    const bool planar = idx->d_cpl && idx->cpl_ok && ws->bs.qpl;
+    const bool planar = lrm_planar_ready(idx, ws);
     if (anchor_scratch(ws, planar) || (clip.on && anchor_clip_scratch(ws))) return -1;
     LrmAnchorScratch &s = *ws->an;
     const LrmGactJobs jobs = {s.job_reads, s.job_stride, s.job_lens, s.job_tlens, s.job_meta, s.job_meta_r, idx->view.content,
@@ -542,7 +477,7 @@ int lrm_launch_extend_anchored(lrm_index *idx, lrm_workspace *ws, const LrmExten
     // anchor: planar image of the oriented reads, then the scan
     lrm_time_begin(ws, LRM_K_LOCUS, stream);
     if (planar && lrm_bs_pack_reads(b.reads, b.stride, b.lens, n, b.max_len, ws->bs, stream)) return -1;
-    if (launch_scan(b, idx->view, ws->bs, planar ? idx->d_cpl : nullptr, min_len, s.keys, stream)) return -1;
+    if (lrm_anchor_scan(b, idx->view, ws->bs, planar ? idx->d_cpl : nullptr, min_len, s.keys, stream)) return -1;
     lrm_time_end(ws, stream);
 
     // jobs
@@ -556,14 +491,7 @@ int lrm_launch_extend_anchored(lrm_index *idx, lrm_workspace *ws, const LrmExten
     lrm_time_end(ws, stream);
 
     // one extension launch over the job table
-    if (plan.kernel == LRM_GACT_BS) {
-        lrm_time_begin(ws, LRM_K_PACK_PLANAR, stream);
-        if (lrm_bs_pack_reads(jobs.reads, jobs.stride, jobs.lens, jobs.n, b.max_len, s.bs, stream)) return -1;
-        lrm_time_end(ws, stream);
-    }
-    lrm_time_begin(ws, plan.slot, stream);
-    if (lrm_gact_launch_jobs(jobs, gp, plan, &s.bs, ws->d_counters, mt.bs_waves, stream)) return -1;
-    lrm_time_end(ws, stream);
+    if (lrm_gact_run_jobs(ws, jobs, b.max_len, gp, plan, s.bs, ws->d_counters, mt.bs_waves, stream)) return -1;
 
     // clip: one wavefront per job
     if (clip.on) {
@@ -586,44 +514,5 @@ int lrm_launch_extend_anchored(lrm_index *idx, lrm_workspace *ws, const LrmExten
                        clip.on ? s.clip_recs : nullptr, clip.on ? clip.d_clip : nullptr);
     lrm_time_end(ws, stream);
     HIPCHK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int lrm_debug_anchor(lrm_index *idx, const char *read, uint32_t len, uint64_t loc, uint32_t min_len,
-                                lrm_anchor *out) {
-    if (!idx || !read || !out || len == 0) { lrm_set_error("bad argument"); return -1; }
-    if (lrm_require_device(idx->device) || anchor_min_len(min_len, &min_len)) return -1;
-    const int nm = idx->view.mta_len;
-    LrmMtaDev *hm = (LrmMtaDev *) malloc(sizeof(LrmMtaDev) * (size_t) (nm > 0 ? nm : 1));
-    if (!hm) { lrm_set_error("out of memory"); return -1; }
-    lrm_seq_meta m = {};
-    m.seq_id = -1;
-    if (hipMemcpy(hm, idx->view.mta, sizeof(LrmMtaDev) * (size_t) nm, hipMemcpyDeviceToHost) == hipSuccess)
-        for (int i = 0; i < nm && m.seq_id < 0; ++i)
-            if (loc >= hm[i].offset && loc < hm[i].offset + hm[i].seq_len) { m.seq_id = i; m.loc = loc; m.off = loc - hm[i].offset; }
-    free(hm);
-    if (m.seq_id < 0) { lrm_set_error("locus %llu is not on the forward half of a sequence", (unsigned long long) loc); return -1; }
-    const bool planar = idx->d_cpl && idx->cpl_ok;
-    LrmBsScratch pl = {};
-    pl.wpr = lrm_bs_planar_words(len);
-    DevBuf br, bl, bm, bmr, bk, ba, bq, bf;
-    if (br.alloc((size_t) len + 32) || bl.alloc(16) || bm.alloc(sizeof(m)) || bmr.alloc(16) || bk.alloc(16) ||
-        ba.alloc(sizeof(lrm_anchor)) || bq.alloc(pl.wpr * 8 + 16) || bf.alloc(16)) { lrm_set_error("device allocation failed"); return -1; }
-    pl.qpl = (uint64_t *) bq.p; pl.rflags = (uint32_t *) bf.p;
-    const int32_t one = 1;
-    HIPCHK(hipMemcpy(br.p, read, len, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(bl.p, &len, 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(bm.p, &m, sizeof(m), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(bmr.p, &one, 4, hipMemcpyHostToDevice));
-    LrmExtendBatch b = {};
-    b.reads = (char *) br.p; b.lens = (const uint32_t *) bl.p; b.n = 1; b.max_len = len;
-    b.meta = (lrm_seq_meta *) bm.p; b.meta_r = (int32_t *) bmr.p;
-    if (planar && lrm_bs_pack_reads(b.reads, 0, b.lens, 1, len, pl, nullptr)) return -1;
-    if (launch_scan(b, idx->view, pl, planar ? idx->d_cpl : nullptr, min_len, (uint64_t *) bk.p, nullptr)) return -1;
-    hipLaunchKernelGGL(anchor_record_kernel, dim3(1), dim3(1), 0, nullptr, b.lens, b.meta, idx->view.mta,
-                       (const unsigned long long *) bk.p, (lrm_anchor *) ba.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, ba.p, sizeof(lrm_anchor), hipMemcpyDeviceToHost));
     return 0;
 }

@@ -1,9 +1,6 @@
-// gact_kernels.hip -- gfx950 kernels for PART 2 of the accaln hot path
-// (reference: alnmain.c:408-451 -- seq_lookup :151-176, _rev_comp_in_place :27-60,
-//  cigar_align mutils.c:94-105 -> simple_gact [gact submodule, source absent]).
+// gact_kernels.hip -- the byte kernels of the extension stage (reference: cigar_align mutils.c:94-105 -> simple_gact
+// [gact submodule, source absent]; docs/GACT_SPEC.md) and the launch of each
 //
-//   locus_resolve  one lane per read: seq_lookup with the reference's u64 arithmetic
-//   revcomp        reverse-complement reads that resolved to the reverse strand, in place
 //   gact3          TWO READS PER WAVEFRONT (packed 16-bit scores, traceback planes in registers): small batches.
 //                  The compiler reports 103 VGPRs (NB = 26) / 121 (NB = 32), no scratch, 4 wavefronts per SIMD
 //   gact_wide      ONE READ PER WAVEFRONT (32-bit scores, traceback in LDS): bands wider than 128 diagonals, and the
@@ -11,7 +8,8 @@
 //                  6 / 6 / 5 / 4 wavefronts per SIMD at 1 / 2 / 4 / 8 diagonal pairs per lane, no scratch
 //                  Tiles of a read are walked in sequence (tile i+1 starts where tile i's traceback stopped),
 //                  docs/GACT_SPEC.md.  Large batches run on the bit-sliced lane-per-read kernel (gact_bs_kernels.hip).
-//   host side      lrm_gact_plan picks the kernel of a job table, lrm_gact_launch_jobs launches it
+//   Which kernel runs a job table is decided in extend_launch.hip (lrm_gact_plan); tile geometry, the walk bound and
+//   the LDS layouts are in extend_stage.h, shared with that plan.
 //
 // GACT tile on a 64-lane wavefront: the band (<=128 diagonals) is laid across the lanes and
 // the wavefront sweeps anti-diagonals s = a+b from the far corner down to the anchor.  On an
@@ -22,110 +20,12 @@
 // 16 steps per dword and parked in LDS; the traceback walk reads them back.  Integer max/add
 // recurrences: nothing here is a contraction, MFMA does not apply.
 #include <hip/hip_runtime.h>
-#include <cstdlib>
 #include "lrm_hip_util.h"
-#include "seq_bytes.h"
+#include "extend_stage.h"
 
 #define GACT_NEG (-(1 << 28))
 #define DPP_WAVE_SHL1 0x130  // lane L <- lane L+1
 #define DPP_WAVE_SHR1 0x138  // lane L <- lane L-1
-
-// ----------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void locus_resolve_kernel(LrmIndexView ix, const lrm_entry *__restrict__ best,
-                                                            const uint32_t *__restrict__ lens, uint64_t n,
-                                                            lrm_seq_meta *__restrict__ meta,
-                                                            int32_t *__restrict__ meta_r) {
-    uint64_t read = (uint64_t) blockIdx.x * 256 + threadIdx.x;
-    if (read >= n) return;
-    const uint64_t loc = best[read].key;                       // alnmain.c:427
-    const uint32_t qlen = lens[read];
-    lrm_seq_meta m;
-    m.loc = 0; m.off = 0; m.seq_id = -1; m.strand = 0;
-    int mr = 0;
-    for (int i = 0; i < ix.mta_len; ++i) {                     // alnmain.c:155-174
-        uint64_t sl = ix.mta[i].seq_len;
-        uint64_t start = ix.mta[i].offset;
-        uint64_t end = start + sl * 2;
-        if (loc >= start && loc + qlen <= start + sl) {
-            m.strand = 0; m.seq_id = i; m.loc = loc; m.off = loc - start;
-            mr = 1;
-            break;
-        } else if (loc >= start + sl && loc + qlen <= end) {
-            m.strand = 1; m.seq_id = i; m.off = end - loc - qlen; m.loc = m.off + start;
-            mr = 1;
-            break;
-        }
-    }
-    // Fences: the reference consumes an uninitialised struct when the lookup fails,
-    // and a wrapped u64 locus can pass the test while pointing outside the text.
-    if (mr && (qlen == 0 || m.loc >= ix.con_len || (uint64_t) qlen > ix.con_len - m.loc)) mr = 0;
-    if (!mr) { m.loc = 0; m.off = 0; m.seq_id = -1; m.strand = 0; }
-    meta[read] = m;
-    meta_r[read] = mr;
-}
-
-// In place, with ALIGNED 16-byte accesses only (rows start at any byte: stride = max_read_len + 1).  A workgroup owns
-// `seg` bases of the front half of a read and their mirror bases; it copies both spans into LDS with aligned
-// 16-byte loads (the first and last chunk reach a few bytes outside the span: loaded, never used), and after the
-// barrier every thread builds whole aligned 16-byte chunks of each span from the other one (five LDS dwords,
-// v_alignbyte, byte swap + complement).  Chunks that straddle a span's ends are written bytewise.  Measured [r2]:
-// one unaligned dword per thread 1.5 ms per Gbp, one unaligned 16-byte access per thread 2.2 ms, this version
-// see profiles/r2.
-#define RC_SEG 4096
-__device__ __forceinline__ void revcomp_span(const uint8_t *__restrict__ src, uint32_t src_off, char *gdst,
-                                             uint32_t dst_off, uint32_t cnt, uint32_t tid) {
-    // destination bytes i in [0, cnt) live at gdst_aligned + dst_off + i; byte i = comp(src[src_off + cnt-1-i])
-    const uint32_t nchunk = (dst_off + cnt + 15) / 16;
-    const uint32_t *src32 = reinterpret_cast<const uint32_t *>(src);
-    for (uint32_t c = tid; c < nchunk; c += 256) {
-        const int32_t i0 = (int32_t) (16 * c) - (int32_t) dst_off;           // first destination byte of the chunk
-        if (i0 >= 0 && (uint32_t) i0 + 16 <= cnt) {
-            const uint32_t lo = src_off + cnt - 16 - (uint32_t) i0;          // source bytes [lo, lo + 16)
-            const uint32_t q = lo >> 2, sh = lo & 3;
-            uint32_t d[5], o[4];
-#pragma unroll
-            for (int e = 0; e < 5; ++e) d[e] = src32[q + e];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[3 - e] = revcomp4(__builtin_amdgcn_alignbyte(d[e + 1], d[e], sh));
-            *reinterpret_cast<uint4 *>(gdst + 16 * c) = make_uint4(o[0], o[1], o[2], o[3]);
-        } else {
-            for (int k = 0; k < 16; ++k) {
-                const int32_t i = i0 + k;
-                if (i >= 0 && (uint32_t) i < cnt) gdst[16 * c + k] = comp_base((char) src[src_off + cnt - 1 - (uint32_t) i]);
-            }
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void revcomp_kernel(char *__restrict__ reads, uint64_t stride,
-                                                      const uint32_t *__restrict__ lens,
-                                                      const lrm_seq_meta *__restrict__ meta,
-                                                      const int32_t *__restrict__ meta_r, uint64_t n,
-                                                      uint32_t chunks_per_read, uint32_t seg) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_a[RC_SEG + 48], s_b[RC_SEG + 48];
-    const uint64_t read = blockIdx.x / chunks_per_read;
-    const uint32_t chunk = blockIdx.x % chunks_per_read;
-    if (read >= n) return;
-    if (!meta_r[read] || meta[read].strand != 1) return;       // alnmain.c:433
-    const uint32_t len = lens[read], half = len / 2;
-    char *r = reads + read * stride;
-    const uint32_t tid = threadIdx.x;
-    if (chunk == 0 && tid == 0 && (len & 1)) r[half] = comp_base(r[half]);
-    const uint32_t s = chunk * seg;
-    if (s >= half) return;
-    const uint32_t e = s + seg < half ? s + seg : half, cnt = e - s;          // front [s, e), mirror [len-e, len-s)
-    char *ga = r + s, *gb = r + (len - e);
-    const uint32_t off_a = (uint32_t) ((uintptr_t) ga & 15), off_b = (uint32_t) ((uintptr_t) gb & 15);
-    ga -= off_a;
-    gb -= off_b;
-    for (uint32_t c = tid; 16 * c < off_a + cnt; c += 256)
-        *reinterpret_cast<uint4 *>(s_a + 16 * c) = *reinterpret_cast<const uint4 *>(ga + 16 * c);
-    for (uint32_t c = tid; 16 * c < off_b + cnt; c += 256)
-        *reinterpret_cast<uint4 *>(s_b + 16 * c) = *reinterpret_cast<const uint4 *>(gb + 16 * c);
-    __syncthreads();
-    revcomp_span(s_b, off_b, ga, off_a, cnt, tid);
-    revcomp_span(s_a, off_a, gb, off_b, cnt, tid);
-}
 
 // ----------------------------------------------------------------------------------------
 // GACT
@@ -157,6 +57,25 @@ __device__ __forceinline__ int gact_cell(int r_diag, int r_ins, int r_del, uint3
     return best;
 }
 
+// ---- the end of a read, the same in both kernels ----
+// a fenced read (no locus): no ops, score -1
+__device__ __forceinline__ void gact_write_fenced(int32_t *n_ops_out, int32_t *score_out, uint64_t r) {
+    n_ops_out[r] = 0; score_out[r] = -1;
+}
+// the text ran out before the read did: the rest of the read is inserted
+__device__ __forceinline__ void gact_i_tail(uint8_t *ops_out, int &nops, int &score, int i, int n, int lane) {
+    if (score >= 0 && i < n) {
+        int rest = n - i;
+        for (int x = lane; x < rest; x += 64) ops_out[nops + x] = 'I';
+        nops += rest;
+        score += rest;
+    }
+}
+__device__ __forceinline__ void gact_write_result(int32_t *n_ops_out, int32_t *score_out, uint64_t r, int nops, int score) {
+    n_ops_out[r] = score >= 0 ? nops : 0;
+    score_out[r] = score;
+}
+
 // ----------------------------------------------------------------------------------------
 // GACT v2: TWO reads per wavefront, packed 16-bit.
 //
@@ -174,7 +93,6 @@ __device__ __forceinline__ int gact_cell(int r_diag, int r_ins, int r_del, uint3
 //     recovered during the walk from the staged sequences, a whole DIAG run per instruction.
 // ----------------------------------------------------------------------------------------
 #define G2_BIAS 2560
-#define G2_PAD 40            // guard positions on both sides of the staged sequences (>= 33)
 
 typedef short v2s __attribute__((ext_vector_type(2)));
 typedef unsigned short v2u __attribute__((ext_vector_type(2)));
@@ -293,20 +211,19 @@ __global__ __launch_bounds__(256) void gact3_kernel(const char *__restrict__ rea
         q[h] = reinterpret_cast<const uint8_t *>(reads) + rs * stride;
         d[h] = reinterpret_cast<const uint8_t *>(content) + (ok[h] ? meta[rs].loc : 0);
         ops_out[h] = store + rs * store_stride;
-        if (r < n_reads && !ok[h] && lane == 0) { n_ops_out[r] = 0; score_out[r] = -1; }   // fenced
+        if (r < n_reads && !ok[h] && lane == 0) gact_write_fenced(n_ops_out, score_out, r);
     }
     if (!ok[0] && !ok[1]) return;
 
-    const uint32_t seq_words = (uint32_t) T + 2 * G2_PAD;
-    uint32_t *qbuf = reinterpret_cast<uint32_t *>(smem) + (size_t) wave * 2 * seq_words + G2_PAD;
-    uint32_t *dbuf = qbuf + seq_words;
+    const LrmPackedLds lds(T);
+    uint32_t *qbuf = reinterpret_cast<uint32_t *>(smem) + lds.q_word(wave);
+    uint32_t *dbuf = qbuf + lds.seq_words;
 
     const int hw = W / 2;
     const int dE = 2 * lane - 64, dO = 2 * lane - 63;
     const bool inE = dE >= -hw && dE < hw, inO = dO >= -hw && dO < hw;
     const int cap = T - O, lim2 = 2 * cap;
-    const int nblk = ((lim2 - 1) >> 4) + 1;
-    const int s_hi = nblk * 16 - 1;
+    const int s_hi = lrm_gact_tb_blocks(T, O) * 16 - 1;
     unsigned tiles = 0;
 #define X(K, K1) uint32_t tbn##K = 0, tbg##K = 0;
     G3_CASES(X)
@@ -325,13 +242,14 @@ __global__ __launch_bounds__(256) void gact3_kernel(const char *__restrict__ rea
 
     while ((i[0] < n[0] && j[0] < m[0]) || (i[1] < n[1] && j[1] < m[1])) {
         int tq[2], tt[2];
-        bool act[2], last[2];
+        bool act[2];
+        LrmGactTile tile[2];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             act[h] = i[h] < n[h] && j[h] < m[h];
-            tq[h] = act[h] ? min(T, n[h] - i[h]) : 0;
-            tt[h] = act[h] ? min(T, m[h] - j[h]) : 0;
-            last[h] = i[h] + tq[h] == n[h];
+            tile[h] = lrm_gact_tile(T, i[h], n[h], j[h], m[h], act[h]);
+            tq[h] = tile[h].tq;
+            tt[h] = tile[h].tt;
             tiles += act[h] ? 1u : 0u;
         }
         for (int x = lane; x < T; x += 64) {
@@ -429,7 +347,7 @@ __global__ __launch_bounds__(256) void gact3_kernel(const char *__restrict__ rea
             const int sh = 16 * h;
             int a = 0, b = 0, cnt = 0, sc = 0;
             uint8_t *out = ops_out[h] + nops[h];
-            while (a < tq[h] && b < tt[h] && (last[h] ? (a + b < lim2) : (a < cap && b < cap))) {
+            while (lrm_gact_walk_more(tile[h], a, b, cap)) {
                 const int sw = a + b, dd = b - a, e0 = sw & 15;
                 uint32_t n0 = 0, g0 = 0, n1 = 0, g1 = 0;
                 {
@@ -446,7 +364,7 @@ __global__ __launch_bounds__(256) void gact3_kernel(const char *__restrict__ rea
                 const int egap = gm ? __builtin_ctz(gm) : 32 + (e0 & 1);
                 const int r = (egap - e0) >> 1;
                 int rmax = min(tq[h] - a, tt[h] - b);
-                rmax = last[h] ? min(rmax, (lim2 - sw + 1) >> 1) : min(rmax, min(cap - a, cap - b));
+                rmax = tile[h].last ? min(rmax, (lim2 - sw + 1) >> 1) : min(rmax, min(cap - a, cap - b));
                 const int rr = min(r, rmax);
                 bool neq = false;
                 if (lane < rr) {
@@ -455,7 +373,7 @@ __global__ __launch_bounds__(256) void gact3_kernel(const char *__restrict__ rea
                 }
                 const int mism = __builtin_popcountll(__ballot(neq));
                 const int a2 = a + rr, b2 = b + rr;
-                const bool more = a2 < tq[h] && b2 < tt[h] && (last[h] ? (a2 + b2 < lim2) : (a2 < cap && b2 < cap));
+                const bool more = lrm_gact_walk_more(tile[h], a2, b2, cap);
                 const bool do_gap = gm != 0u && rr == r && more;
                 const bool is_del = ((wG >> (egap & 31)) & 1u) != 0u;
                 if (do_gap && lane == 0) out[cnt + rr] = is_del ? 'D' : 'I';
@@ -476,17 +394,8 @@ __global__ __launch_bounds__(256) void gact3_kernel(const char *__restrict__ rea
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         if (!ok[h]) continue;
-        const uint64_t r = r0 + (uint64_t) h;
-        if (score[h] >= 0 && i[h] < n[h]) {
-            int rest = n[h] - i[h];
-            for (int x = lane; x < rest; x += 64) ops_out[h][nops[h] + x] = 'I';
-            nops[h] += rest;
-            score[h] += rest;
-        }
-        if (lane == 0) {
-            n_ops_out[r] = score[h] >= 0 ? nops[h] : 0;
-            score_out[r] = score[h];
-        }
+        gact_i_tail(ops_out[h], nops[h], score[h], i[h], n[h], lane);
+        if (lane == 0) gact_write_result(n_ops_out, score_out, r0 + (uint64_t) h, nops[h], score[h]);
     }
     if (lane == 0) atomicAdd(&counters->gact_tiles, (unsigned long long) tiles);
 }
@@ -513,24 +422,22 @@ __global__ __launch_bounds__(64) void gact_wide_kernel(const char *__restrict__ 
                                                        int32_t *__restrict__ score_out, LrmDevCounters *counters,
                                                        const uint32_t *__restrict__ flags) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    constexpr int NX = 64 * DPL;                   // diagonal indices per parity
+    constexpr int NX = 64 * DPL;                   // diagonal indices per parity (LrmWideLds::nx)
     constexpr int HWX = NX;                        // d = 2x - HWX (+1)
-    constexpr int PADW = NX / 2 + 40;              // guard bytes on both sides of the staged sequences
     const int lane = threadIdx.x & 63;
     const uint64_t read = blockIdx.x;
     if (read >= n_reads) return;
     if (flags && !flags[read]) return;             // second launch behind the bit-sliced kernel: flagged reads only
     if (!meta_r[read]) {
-        if (lane == 0) { n_ops_out[read] = 0; score_out[read] = -1; }
+        if (lane == 0) gact_write_fenced(n_ops_out, score_out, read);
         return;
     }
-    const int cap = T - O, lim2 = 2 * cap;
-    const int tb_words = ((lim2 - 1) >> 4) + 1;
-    const int seq_bytes = (T + 2 * PADW + 15) & ~15;
+    const int cap = T - O;
+    const LrmWideLds lds(DPL, T, O);
     uint32_t *tb = reinterpret_cast<uint32_t *>(smem);
-    uint8_t *qbuf = smem + (size_t) tb_words * NX * 4 + PADW;
-    uint8_t *dbuf = qbuf + seq_bytes;
-    uint8_t *opsbuf = smem + (size_t) tb_words * NX * 4 + 2 * (size_t) seq_bytes;
+    uint8_t *qbuf = smem + lds.q_off();
+    uint8_t *dbuf = smem + lds.d_off();
+    uint8_t *opsbuf = smem + lds.ops_off();
 
     const int n = __builtin_amdgcn_readfirstlane((int) lens[read]);
     const int m = tlens ? __builtin_amdgcn_readfirstlane((int) tlens[read]) : n;
@@ -538,14 +445,13 @@ __global__ __launch_bounds__(64) void gact_wide_kernel(const char *__restrict__ 
     const uint8_t *d = reinterpret_cast<const uint8_t *>(content) + meta[read].loc;
     uint8_t *ops_out = store + read * store_stride;
     const int hw = W / 2;
-    const int s_hi = tb_words * 16 - 1;
+    const int s_hi = lds.tb_words * 16 - 1;
 
     int i = 0, j = 0, nops = 0, score = 0;
     unsigned tiles = 0;
     while (i < n && j < m) {
-        const int tq = (n - i) < T ? (n - i) : T;
-        const int tt = (m - j) < T ? (m - j) : T;
-        const bool last = (i + tq == n);
+        const LrmGactTile tile = lrm_gact_tile(T, i, n, j, m);
+        const int tq = tile.tq, tt = tile.tt;
         tiles++;
         for (int x = lane; x < tq; x += 64) qbuf[x] = q[i + x];
         for (int x = lane; x < tt; x += 64) dbuf[x] = d[j + x];
@@ -600,7 +506,7 @@ __global__ __launch_bounds__(64) void gact_wide_kernel(const char *__restrict__ 
         __builtin_amdgcn_wave_barrier();
 
         int a = 0, b = 0, cnt = 0;
-        while (a < tq && b < tt && (last ? (a + b < lim2) : (a < cap && b < cap))) {
+        while (lrm_gact_walk_more(tile, a, b, cap)) {
             const int sw = a + b, dd = b - a;
             const uint32_t word = __builtin_amdgcn_readfirstlane(tb[(sw >> 4) * NX + ((dd + HWX) >> 1)]);
             const uint32_t p = (word >> (2 * (sw & 15))) & 3u;
@@ -621,22 +527,28 @@ __global__ __launch_bounds__(64) void gact_wide_kernel(const char *__restrict__ 
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
-    if (score >= 0 && i < n) {
-        int rest = n - i;
-        for (int x = lane; x < rest; x += 64) ops_out[nops + x] = 'I';
-        nops += rest;
-        score += rest;
-    }
+    gact_i_tail(ops_out, nops, score, i, n, lane);
     if (lane == 0) {
-        n_ops_out[read] = score >= 0 ? nops : 0;
-        score_out[read] = score;
+        gact_write_result(n_ops_out, score_out, read, nops, score);
         atomicAdd(&counters->gact_tiles, (unsigned long long) tiles);
     }
 }
 
-// one read per wavefront (gact_wide_kernel<plan.dpl>); flags != null: flagged reads only
-static int launch_one_per_wave(const LrmGactJobs &j, lrm_gact_params gp, const LrmGactPlan &plan, LrmDevCounters *counters,
-                               const uint32_t *flags, hipStream_t stream) {
+// ----------------------------------------------------------------------------------------
+// host side: the launch of each kernel as lrm_gact_plan chose it
+// ----------------------------------------------------------------------------------------
+int lrm_gact_launch_packed(const LrmGactJobs &j, lrm_gact_params gp, const LrmGactPlan &plan, LrmDevCounters *counters,
+                           void *stream) {
+    auto fn3 = plan.nb == 26 ? (plan.fullband ? gact3_kernel<true, 26> : gact3_kernel<false, 26>)
+                             : (plan.fullband ? gact3_kernel<true, 32> : gact3_kernel<false, 32>);
+    hipLaunchKernelGGL(fn3, dim3((uint32_t) ((j.n + 7) / 8)), dim3(256), plan.lds, (hipStream_t) stream, j.reads, j.stride,
+                       j.lens, j.meta, j.meta_r, j.content, j.tlens, j.n, gp.T, gp.O, gp.W, j.store, j.store_stride, j.n_ops,
+                       j.score, counters);
+    return 0;
+}
+
+int lrm_gact_launch_wide(const LrmGactJobs &j, lrm_gact_params gp, const LrmGactPlan &plan, LrmDevCounters *counters,
+                         const uint32_t *flags, void *stream) {
     auto fw = plan.dpl == 1 ? gact_wide_kernel<1> : plan.dpl == 2 ? gact_wide_kernel<2>
             : plan.dpl == 4 ? gact_wide_kernel<4> : gact_wide_kernel<8>;
     if (plan.lds > 64 * 1024) {
@@ -646,175 +558,7 @@ static int launch_one_per_wave(const LrmGactJobs &j, lrm_gact_params gp, const L
     }
     uint32_t grid;
     if (lrm_grid_1d(j.n, "gact", &grid)) return -1;
-    hipLaunchKernelGGL(fw, dim3(grid), dim3(64), plan.lds, stream, j.reads, j.stride, j.lens, j.meta, j.meta_r, j.content,
-                       j.tlens, j.n, gp.T, gp.O, gp.W, j.store, j.store_stride, j.n_ops, j.score, counters, flags);
-    return 0;
-}
-
-// THE choice of the extension kernel (gact_impl: lrm_map_options in lrm_accel.h; the rule as a table: INTEGRATION.md)
-int lrm_gact_plan(const LrmGactJobs &j, lrm_gact_params gp, int impl, bool planar, LrmGactPlan *out) {
-    LrmGactPlan p = {};
-    const int nblk = ((2 * (gp.T - gp.O) - 1) >> 4) + 1;              // traceback blocks of a tile
-    // Bit-sliced kernel: a wavefront carries 64 reads, so it needs a large batch to fill the chip (below ~16 k reads
-    // the two-reads-per-wavefront kernel finishes first); it stores CIGAR bytes four at a time.
-    if (gp.W <= 128 && planar && (((uintptr_t) j.store | (uintptr_t) j.store_stride) & 3u) == 0 &&
-        (impl == 4 || (impl == 0 && j.n >= LRM_BS_MIN_READS)))
-        p.kernel = LRM_GACT_BS;
-    else if (gp.W <= 128 && impl != 1 && nblk <= 32)
-        p.kernel = LRM_GACT_PACKED;
-    else                                  // W > 128, T - O > 256 (more traceback planes than the packed kernel keeps in registers), impl 1
-        p.kernel = LRM_GACT_WIDE;
-    p.slot = p.kernel == LRM_GACT_BS ? LRM_K_GACT_BS : LRM_K_GACT;
-    if (p.kernel == LRM_GACT_PACKED) {
-        p.nb = nblk <= 26 ? 26 : 32;
-        p.fullband = gp.W >= 128;
-        p.lds = (size_t) 4 * 2 * ((size_t) gp.T + 2 * G2_PAD) * 4;
-    } else {                              // DPL diagonal pairs per lane for the band W
-        p.dpl = gp.W <= 128 ? 1 : gp.W <= 256 ? 2 : gp.W <= 512 ? 4 : 8;
-        const int nx = 64 * p.dpl, padw = nx / 2 + 40;
-        const int seqb = (gp.T + 2 * padw + 15) & ~15;
-        p.lds = (size_t) nblk * nx * 4 + 2 * (size_t) seqb + (((size_t) 2 * (gp.T - gp.O) + 15) & ~(size_t) 15);
-        if (p.lds > 160 * 1024) { lrm_set_error("GACT T=%d O=%d W=%d needs %zu B of LDS (> 160 KiB)", gp.T, gp.O, gp.W, p.lds); return -1; }
-    }
-    *out = p;
-    return 0;
-}
-
-// the extension proper over a table of jobs (anchor_kernels.hip builds one; the classic mode's table is the batch itself)
-int lrm_gact_launch_jobs(const LrmGactJobs &j, lrm_gact_params gp, const LrmGactPlan &plan, const LrmBsScratch *bs,
-                         LrmDevCounters *counters, uint32_t bs_waves, void *stream_) {
-    hipStream_t stream = (hipStream_t) stream_;
-    if (plan.kernel == LRM_GACT_BS) {
-        if (lrm_bs_launch(j, gp, *bs, counters, bs_waves, stream)) return -1;
-        // reads holding a byte other than ACGT (rare): one read per wavefront, flagged reads only
-        return launch_one_per_wave(j, gp, plan, counters, bs->rflags, stream);
-    }
-    if (plan.kernel == LRM_GACT_PACKED) {
-        auto fn3 = plan.nb == 26 ? (plan.fullband ? gact3_kernel<true, 26> : gact3_kernel<false, 26>)
-                                 : (plan.fullband ? gact3_kernel<true, 32> : gact3_kernel<false, 32>);
-        hipLaunchKernelGGL(fn3, dim3((uint32_t) ((j.n + 7) / 8)), dim3(256), plan.lds, stream, j.reads, j.stride, j.lens,
-                           j.meta, j.meta_r, j.content, j.tlens, j.n, gp.T, gp.O, gp.W, j.store, j.store_stride, j.n_ops,
-                           j.score, counters);
-        return 0;
-    }
-    return launch_one_per_wave(j, gp, plan, counters, nullptr, stream);
-}
-
-// ----------------------------------------------------------------------------------------
-// {0,0,0} selects the defaults; the limits are those of the kernels
-int lrm_gact_resolve_params(lrm_gact_params *gp) {
-    if (gp->T == 0 && gp->O == 0 && gp->W == 0) {
-        gp->T = LRM_GACT_T_DEFAULT; gp->O = LRM_GACT_O_DEFAULT; gp->W = LRM_GACT_W_DEFAULT;
-    }
-    if (gp->T < 16 || gp->T > 512 || gp->O < 0 || gp->O >= gp->T || gp->W < 2 || (gp->W & 1) || gp->W > 1024) {
-        lrm_set_error("unsupported GACT parameters T=%d O=%d W=%d (need 16<=T<=512, 0<=O<T, even 2<=W<=1024)",
-                      gp->T, gp->O, gp->W);
-        return -1;
-    }
-    return 0;
-}
-
-// locus_resolve + in-place reverse complement: what both extension modes start with
-int lrm_launch_locus_revcomp(lrm_index *idx, lrm_workspace *ws, const LrmExtendBatch &b, void *stream_) {
-    hipStream_t stream = (hipStream_t) stream_;
-    lrm_time_begin(ws, LRM_K_LOCUS, stream);
-    hipLaunchKernelGGL(locus_resolve_kernel, dim3((uint32_t) ((b.n + 255) / 256)), dim3(256), 0, stream,
-                       idx->view, b.best, b.lens, b.n, b.meta, b.meta_r);
-    lrm_time_end(ws, stream);
-    const uint32_t half = b.max_len / 2 + 1;
-    const uint32_t cpr = (half + RC_SEG - 1) / RC_SEG;                                  // workgroups per read
-    const uint32_t seg = ((half + cpr - 1) / cpr + 15) & ~15u;                           // <= RC_SEG bases each
-    uint32_t grid;
-    if (lrm_grid_1d(b.n * cpr, "revcomp", &grid)) return -1;
-    lrm_time_begin(ws, LRM_K_REVCOMP, stream);
-    hipLaunchKernelGGL(revcomp_kernel, dim3(grid), dim3(256), 0, stream, b.reads, b.stride, b.lens, b.meta, b.meta_r, b.n,
-                       cpr, seg);
-    lrm_time_end(ws, stream);
-    return 0;
-}
-
-int lrm_launch_extend(lrm_index *idx, lrm_workspace *ws, const LrmExtendBatch &b, lrm_gact_params gp, const LrmMapTune &mt,
-                      void *stream_) {
-    hipStream_t stream = (hipStream_t) stream_;
-    if (b.n == 0) return 0;
-    if (mt.anchored)                                       // anchor_kernels.hip; nothing below is reached
-        return lrm_launch_extend_anchored(idx, ws, b, gp, nullptr, mt.anchor_min_len, lrm_clip_of(mt), mt, stream_);
-    if (mt.clip) { lrm_set_error("lrm_map_options.clip needs lrm_map_options.anchored"); return -1; }
-    if (lrm_gact_resolve_params(&gp)) return -1;
-    if (b.store_stride < 2ull * b.max_len) {
-        lrm_set_error("store_stride %llu < 2*max_len %u", (unsigned long long) b.store_stride, b.max_len);
-        return -1;
-    }
-    const bool planar = idx->d_cpl && idx->cpl_ok && ws->bs.qpl && b.n <= ws->n_max && b.max_len <= ws->max_len;
-    const LrmGactJobs jobs = {b.reads, b.stride, b.lens, nullptr, b.meta, b.meta_r, idx->view.content, idx->d_cpl, b.n,
-                              b.store, b.store_stride, b.n_ops, b.score};
-    LrmGactPlan plan;
-    if (lrm_gact_plan(jobs, gp, mt.gact_impl, planar, &plan)) return -1;
-    if (lrm_launch_locus_revcomp(idx, ws, b, stream_)) return -1;
-    if (plan.kernel == LRM_GACT_BS) {
-        lrm_time_begin(ws, LRM_K_PACK_PLANAR, stream);
-        if (lrm_bs_pack_reads(b.reads, b.stride, b.lens, b.n, b.max_len, ws->bs, stream)) return -1;
-        lrm_time_end(ws, stream);
-    }
-    lrm_time_begin(ws, plan.slot, stream);
-    if (lrm_gact_launch_jobs(jobs, gp, plan, &ws->bs, ws->d_counters, mt.bs_waves, stream)) return -1;
-    lrm_time_end(ws, stream);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// direct kernel tap (tests only): simple_gact on one (q, d) pair, m may differ from n
-extern "C" int lrm_debug_gact(const char *q, int n, const char *d, int m, lrm_gact_params gp, uint8_t *ops,
-                              int *n_ops, int *score, int device) {
-    LrmEnv env;                                  // a tap without a handle: LRM_GACT_IMPL as it stands now
-    lrm_env_snapshot(&env);
-    long long impl = 0;
-    (void) env.get("LRM_GACT_IMPL", &impl);
-    return lrm_debug_gact_impl(q, n, d, m, gp, (int) impl, ops, n_ops, score, device);
-}
-
-extern "C" int lrm_debug_gact_impl(const char *q, int n, const char *d, int m, lrm_gact_params gp, int impl, uint8_t *ops,
-                                   int *n_ops, int *score, int device) {
-    if (!q || !d || !ops || !n_ops || !score || n < 0 || m < 0) { lrm_set_error("bad argument"); return -1; }
-    if (lrm_require_device(device) || lrm_gact_resolve_params(&gp)) return -1;
-    DevBuf bq, bd, bops, bl, bm, br, bc, bcpl, btf;
-    if (bq.alloc((size_t) n + 16) || bd.alloc((size_t) m + 16) || bops.alloc((size_t) n + m + 16) || bl.alloc(16) ||
-        bm.alloc(sizeof(lrm_seq_meta)) || br.alloc(16) || bc.alloc(sizeof(LrmDevCounters))) { lrm_set_error("device allocation failed"); return -1; }
-    char *dq = (char *) bq.p, *dd = (char *) bd.p;
-    uint32_t *dl = (uint32_t *) bl.p;                       // {read length, target length}
-    lrm_seq_meta *dm = (lrm_seq_meta *) bm.p;
-    int32_t *dr = (int32_t *) br.p;                         // {meta_r, n_ops, score}
-    LrmDevCounters *dc = (LrmDevCounters *) bc.p;
-    HIPCHK(hipMemset(dc, 0, sizeof(LrmDevCounters)));
-    uint32_t hl[2] = {(uint32_t) n, (uint32_t) m};
-    lrm_seq_meta hm; hm.loc = 0; hm.off = 0; hm.seq_id = 0; hm.strand = 0;
-    int32_t hr[3] = {1, 0, 0};
-    HIPCHK(hipMemcpy(dq, q, (size_t) n, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dd, d, (size_t) m, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dl, hl, 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dm, &hm, sizeof(hm), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dr, hr, 12, hipMemcpyHostToDevice));
-    LrmGactJobs jobs = {dq, 0, dl, dl + 1, dm, dr, dd, nullptr, 1, (uint8_t *) bops.p, 0, dr + 1, dr + 2};
-    struct BsGuard { LrmBsScratch s = {}; ~BsGuard() { lrm_bs_scratch_free(&s); } } bs;
-    LrmGactPlan plan;
-    if (lrm_gact_plan(jobs, gp, impl, true, &plan)) return -1;
-    if (plan.kernel == LRM_GACT_BS) {                       // planar images of the pair; a text that is not pure ACGT plans again
-        uint64_t bytes = 0;
-        if (lrm_bs_scratch_alloc(&bs.s, 1, (uint32_t) n, (uint32_t) (n > m ? n : m), &bytes)) return -1;
-        if (bcpl.alloc(lrm_bs_planar_words((uint64_t) m) * 8 + 16) || btf.alloc(4)) { lrm_set_error("device allocation failed"); return -1; }
-        if (lrm_bs_pack_text(dd, (uint64_t) m, (uint64_t *) bcpl.p, (uint32_t *) btf.p, nullptr)) return -1;
-        if (lrm_bs_pack_reads(dq, 0, dl, 1, (uint32_t) n, bs.s, nullptr)) return -1;
-        uint32_t tf = 0;
-        HIPCHK(hipMemcpy(&tf, btf.p, 4, hipMemcpyDeviceToHost));
-        if (!tf) jobs.cpl = (const uint64_t *) bcpl.p;
-        else if (lrm_gact_plan(jobs, gp, impl, false, &plan)) return -1;
-    }
-    if (lrm_gact_launch_jobs(jobs, gp, plan, &bs.s, dc, 0, nullptr)) return -1;
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(hr, dr, 12, hipMemcpyDeviceToHost));
-    *n_ops = hr[1];
-    *score = hr[2];
-    if (hr[1] > 0) HIPCHK(hipMemcpy(ops, jobs.store, (size_t) hr[1], hipMemcpyDeviceToHost));
+    hipLaunchKernelGGL(fw, dim3(grid), dim3(64), plan.lds, (hipStream_t) stream, j.reads, j.stride, j.lens, j.meta, j.meta_r,
+                       j.content, j.tlens, j.n, gp.T, gp.O, gp.W, j.store, j.store_stride, j.n_ops, j.score, counters, flags);
     return 0;
 }

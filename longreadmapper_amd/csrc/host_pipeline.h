@@ -12,6 +12,7 @@
 #include <thread>
 #include <vector>
 #include "lrm_hip_util.h"
+#include "extend_stage.h"
 
 // completion of one submitted batch: `pending` slices (over all replicas) still to be collected
 struct lrm_ticket {

@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <omp.h>
 #include "lrm_hip_util.h"
+#include "extend_stage.h"
 
 static inline uint64_t align256(uint64_t x) { return (x + 255ull) & ~255ull; }
 #define LRM_LCX_MAX 4096    // capacity of the long-interval side table

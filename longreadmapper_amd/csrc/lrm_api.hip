@@ -11,6 +11,7 @@
 #include <sched.h>
 #include <omp.h>
 #include "lrm_hip_util.h"
+#include "extend_stage.h"
 
 static thread_local char g_err[512] = "";
 

@@ -1,6 +1,7 @@
-// lrm_hip_util.h -- host helpers and wavefront primitives shared by the .hip files of liblrm_accel.so (lrm_internal.h is also read by plain C++)
+// lrm_hip_util.h -- host helpers and wavefront primitives shared by the .hip files of liblrm_accel.so (lrm_internal.h and extend_stage.h are also read by plain C++)
 #pragma once
 #include <hip/hip_runtime.h>
+#include <initializer_list>
 #include "lrm_internal.h"
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
@@ -13,6 +14,24 @@ struct DevBuf {
     int alloc(uint64_t bytes) { return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess ? 0 : -1; }
 };
 
+// a table of device buffers: hipMalloc of every entry, its bytes added to *total.  On a failure the message is
+// "hipMalloc of <bytes> <what> failed" and the caller releases its whole object (the entries not reached are still null)
+struct LrmDevAlloc { void **p; uint64_t bytes; };
+template <size_t N>
+static inline int lrm_dev_alloc_table(const LrmDevAlloc (&table)[N], const char *what, uint64_t *total) {
+    for (const LrmDevAlloc &a : table) {
+        if (hipMalloc(a.p, a.bytes) != hipSuccess) {
+            lrm_set_error("hipMalloc of %llu %s failed", (unsigned long long) a.bytes, what);
+            return -1;
+        }
+        *total += a.bytes;
+    }
+    return 0;
+}
+static inline void lrm_dev_free(std::initializer_list<void *> bufs) {
+    for (void *b : bufs) if (b) (void) hipFree(b);
+}
+
 // x extent of a one-dimensional grid of `blocks` workgroups
 static inline int lrm_grid_1d(uint64_t blocks, const char *what, uint32_t *out) {
     if (blocks > 0x7fffffffull) { lrm_set_error("%s grid too large: split the batch", what); return -1; }
@@ -21,6 +40,12 @@ static inline int lrm_grid_1d(uint64_t blocks, const char *what, uint32_t *out) 
 }
 
 #if defined(__HIPCC__)
+// bits lo .. hi-1 of a word of type T, 0 <= lo <= hi <= the width of T
+template <typename T>
+__host__ __device__ static inline T bit_range(int lo, int hi) {
+    return (hi >= (int) (8 * sizeof(T)) ? ~(T) 0 : (((T) 1 << hi) - (T) 1)) & ~(((T) 1 << lo) - (T) 1);
+}
+
 // ---- wavefront primitives on the DPP network (seed_kernels.hip, vote_kernels.hip, anchor_kernels.hip) ----
 // inclusive prefix sum over the 64 lanes on the DPP network: four row shifts inside the rows of 16, then the
 // row totals are broadcast to the following rows (row_bcast:15 / row_bcast:31) -- six v_add_u32_dpp, no LDS

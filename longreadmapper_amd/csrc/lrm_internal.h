@@ -1,4 +1,4 @@
-// lrm_internal.h -- device image layout + internal declarations of liblrm_accel.so
+// lrm_internal.h -- device image layout + internal declarations of liblrm_accel.so (the extension stage's: extend_stage.h)
 //
 // Device image ("blob"), designed for gfx950 gathers rather than copied from the
 // reference's in-memory arrays:
@@ -210,7 +210,8 @@ enum LrmKernelId { LRM_K_PACK2BIT = 0, LRM_K_SEED_SEARCH, LRM_K_VOTE, LRM_K_DECI
                    LRM_K_COUNT };
 #define LRM_MAX_TIMED 4096
 
-struct LrmBsScratch {                      // device scratch of the bit-sliced kernel for a number of jobs
+struct LrmBsScratch {                      // device scratch of the bit-sliced kernel for a number of jobs (extend_stage.h;
+                                           // here because a workspace holds one by value)
     uint64_t *qpl; uint64_t wpr;           // planar reads, wpr words per read
     uint32_t *rflags;                      // per read: holds a byte other than ACGT
     uint32_t *ckpt;                        // checkpoint scratch, lrm_bs_ckpt_words(jobs) words
@@ -262,51 +263,7 @@ struct lrm_workspace {
     uint8_t *d_mq_phase;           // mapping quality (mapq_kernels.hip): deciding phase per read, allocated by the first mapq call
 };
 
-// ---- extension stage: a table of jobs, the kernel that runs it, the bit-sliced kernel's scratch (all host only) ----------
-#define LRM_BS_PADW 24       // planar words of padding on either side of a packed sequence
-#define LRM_BS_MIN_READS 16384
-// buffers for `jobs` reads of up to max_len bases whose alignments have up to 2 * ops_len ops; adds what it allocated to *bytes
-int lrm_bs_scratch_alloc(LrmBsScratch *s, uint64_t jobs, uint32_t max_len, uint32_t ops_len, uint64_t *bytes);
-void lrm_bs_scratch_free(LrmBsScratch *s);
-
-struct LrmGactJobs {                       // n extension jobs: read i against the text at meta[i].loc
-    const char *reads; uint64_t stride; const uint32_t *lens;
-    const uint32_t *tlens;                 // null: target length = read length
-    const lrm_seq_meta *meta; const int32_t *meta_r;
-    const char *content;                   // the text, one byte per base
-    const uint64_t *cpl;                   // its planar copy (lrm_bs_pack_text); null: none, or the text is not pure ACGT
-    uint64_t n;
-    uint8_t *store; uint64_t store_stride; int32_t *n_ops, *score;
-};
-enum LrmGactKernel {
-    LRM_GACT_WIDE,                         // gact_wide_kernel, one read per wavefront
-    LRM_GACT_PACKED,                       // gact3_kernel, two reads per wavefront
-    LRM_GACT_BS                            // gact_bs_kernel, then gact_wide_kernel on the reads holding a byte other than ACGT
-};
-struct LrmGactPlan {                       // lrm_gact_plan: which kernel runs a job table
-    int kernel;                            // LrmGactKernel
-    int dpl;                               // gact_wide_kernel<DPL> (also the flagged reads of LRM_GACT_BS)
-    int nb; bool fullband;                 // gact3_kernel<FULLBAND, NB>
-    size_t lds;                            // dynamic LDS bytes of gact3_kernel (LRM_GACT_PACKED) or gact_wide_kernel
-    int slot;                              // timing slot: LRM_K_GACT / LRM_K_GACT_BS
-};
-// THE choice of the extension kernel for a job table.  planar: the text has a pure-ACGT planar copy and there is scratch
-// to pack the reads into (the caller packs them when the plan says LRM_GACT_BS)
-int lrm_gact_plan(const LrmGactJobs &j, lrm_gact_params gp, int gact_impl, bool planar, LrmGactPlan *out);
-// the launch the plan names (bs: packed reads and scratch, used by LRM_GACT_BS only; bs_waves: 0 or a smaller grid, tests)
-int lrm_gact_launch_jobs(const LrmGactJobs &j, lrm_gact_params gp, const LrmGactPlan &plan, const LrmBsScratch *bs,
-                         LrmDevCounters *counters, uint32_t bs_waves, void *stream);
-uint64_t lrm_bs_planar_words(uint64_t len);
-uint64_t lrm_bs_code_words(uint32_t max_len);
-uint64_t lrm_bs_ckpt_words(uint64_t n);
-int lrm_bs_pack_reads(const char *d_reads, uint64_t stride, const uint32_t *d_lens, uint64_t n, uint32_t max_len,
-                      const LrmBsScratch &bs, void *stream);
-int lrm_bs_pack_text(const char *d_text, uint64_t len, uint64_t *d_out, uint32_t *d_flag, void *stream);
-int lrm_bs_launch(const LrmGactJobs &j, lrm_gact_params gp, const LrmBsScratch &bs, LrmDevCounters *counters,
-                  uint32_t max_waves, void *stream);
-int lrm_bs_prepare_index(lrm_index *idx);
 int lrm_lcl_prepare_index(lrm_index *idx);       // index_tables.hip: the long lc table, the core table, the seed table
-void lrm_bs_free_index(lrm_index *idx);
 
 void lrm_set_error(const char *fmt, ...);
 // OpenMP team size for the library's host loops: omp_get_max_threads() capped by the CPUs this process may really use
@@ -355,51 +312,6 @@ int lrm_launch_vote(lrm_index *idx, lrm_workspace *ws, const LrmVoteLaunch &v, v
 uint8_t *lrm_mapq_phase_buf(lrm_workspace *ws);
 int lrm_launch_mapq(lrm_index *idx, lrm_workspace *ws, const uint32_t *d_lens, uint64_t n, uint32_t seed_len, uint32_t thres,
                     const lrm_entry *d_best, lrm_mapq *d_mapq, void *stream);
-// a batch as the extension entry points receive it (device pointers; field order of the extern "C" parameter lists)
-struct LrmExtendBatch {
-    char *reads; uint64_t stride; const uint32_t *lens; uint64_t n; uint32_t max_len;
-    const lrm_entry *best;
-    uint8_t *store; uint64_t store_stride; int32_t *n_ops, *score;
-    lrm_seq_meta *meta; int32_t *meta_r;
-};
-int lrm_launch_extend(lrm_index *idx, lrm_workspace *ws, const LrmExtendBatch &b, lrm_gact_params gp, const LrmMapTune &mt,
-                      void *stream);
-// anchored extension (anchor_kernels.hip); the helpers it shares with the classic mode live in gact_kernels.hip
-#define LRM_ANCHOR_MIN_DEFAULT 20
-int lrm_gact_resolve_params(lrm_gact_params *gp);
-int lrm_launch_locus_revcomp(lrm_index *idx, lrm_workspace *ws, const LrmExtendBatch &b, void *stream);
-#define LRM_CLIP_PENALTY_DEFAULT 2
-#define LRM_CLIP_END_BONUS_DEFAULT 6
-// end clipping (docs/GACT_SPEC.md, "End clipping"): on = 0 is the mode as it is without the step
-struct LrmClipOpt { uint32_t on, penalty, end_bonus; lrm_clip *d_clip; };
-static inline LrmClipOpt lrm_clip_of(const LrmMapTune &mt) { return LrmClipOpt{mt.clip, mt.clip_penalty, mt.clip_end_bonus, nullptr}; }
-int lrm_launch_extend_anchored(lrm_index *idx, lrm_workspace *ws, const LrmExtendBatch &b, lrm_gact_params gp,
-                               lrm_anchor *d_anchor, uint32_t min_len, const LrmClipOpt &clip, const LrmMapTune &mt, void *stream);
-void lrm_anchor_scratch_free(lrm_workspace *ws);
-static inline uint64_t lrm_anchored_store_stride(uint32_t max_len) { return 2ull * max_len + max_len / 8 + 2; }
-// split reads (split_kernels.hip; docs/GACT_SPEC.md, "Split reads")
-int lrm_split_min_len(uint32_t m, uint32_t *out);          // 0 -> the default; -1 + message outside 50..2^20
-// the segments of read i from its length and clip counts, appended at out (room for two); returns how many.  THE rule:
-// the device kernels, lrm_split_plan and the host gather all go through it
-#if defined(__HIPCC__) && defined(__device__)
-__host__ __device__
-#endif
-static inline uint32_t lrm_split_segments(uint32_t read, uint32_t n, uint32_t cl, uint32_t cr, uint32_t M, lrm_segment *out) {
-    uint32_t k = 0;
-    if (cl > n) cl = n;                                    // (clip counts never exceed the read: keeps a bad input inside its row)
-    if (cr > n) cr = n;
-    if (cl >= M) { out[k].read = read; out[k].start = 0; out[k].len = cl; out[k].flags = 0; ++k; }
-    if (cr >= M) { out[k].read = read; out[k].start = n - cr; out[k].len = cr; out[k].flags = LRM_SEG_RIGHT; ++k; }
-    return k;
-}
-struct LrmSplitArgs {                                      // lrm_split_batch_dev after its checks
-    const char *reads; uint64_t stride; const uint32_t *lens; uint64_t n; const lrm_clip *clip;
-    uint32_t seed_len, thres; lrm_gact_params gp;
-    uint32_t anchor_min_len, clip_penalty, clip_end_bonus, split_min_len;
-};
-int lrm_launch_split(lrm_index *idx, lrm_workspace *ws_seg, const LrmSplitArgs &a, const lrm_split_dev &out, uint64_t *n_seg,
-                     void *stream);
-void lrm_split_scratch_free(lrm_workspace *ws);
 int lrm_wait_event(void *ev);                              // host_pipeline.hip: the sleep-poll every host wait of this library uses
 int lrm_launch_debug_seed(lrm_index *idx, const char *d_read, uint32_t len, uint32_t seed_len,
                           uint64_t *d_reads2, uint64_t words, int32_t *d_j, uint64_t *d_rr,

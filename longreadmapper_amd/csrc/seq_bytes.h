@@ -29,3 +29,13 @@ __device__ __forceinline__ uint32_t revcomp4(uint32_t w) {       // 4 bases: rev
                        (~(a | c | g | t) & 0x4E4E4E4Eu);
     return __builtin_bswap32(o);
 }
+
+// 16 bases reversed and complemented; word(e), e = 0 .. 3: the four dwords in memory order (a callable, so that each
+// dword is formed right before its use, as the reverse-complement kernel's schedule wants it)
+template <typename F>
+__device__ __forceinline__ uint4 revcomp16(F word) {
+    uint32_t o[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[3 - e] = revcomp4(word(e));
+    return make_uint4(o[0], o[1], o[2], o[3]);
+}

@@ -20,6 +20,7 @@
 // the next multiple of 16 are written as 0.
 #include <hip/hip_runtime.h>
 #include "lrm_hip_util.h"
+#include "extend_stage.h"
 
 #define SP_BLOCK 256                          // reads per workgroup of split_count / split_mark
 #define SP_CHUNK 4096                         // bytes of a row one workgroup of split_gather moves
@@ -150,7 +151,7 @@ __global__ __launch_bounds__(256) void split_flag_kernel(lrm_segment *__restrict
 void lrm_split_scratch_free(lrm_workspace *ws) {
     LrmSplitScratch *s = ws ? ws->sp : nullptr;
     if (!s) return;
-    (void) hipFree(s->blk); (void) hipFree(s->d_tot);
+    lrm_dev_free({s->blk, s->d_tot});
     if (s->h_tot) (void) hipHostFree(s->h_tot);
     if (s->ev) (void) hipEventDestroy(s->ev);
     free(s);

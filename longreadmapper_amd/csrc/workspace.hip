@@ -4,6 +4,7 @@
 #include <new>
 #include <vector>
 #include "lrm_hip_util.h"
+#include "extend_stage.h"
 
 // ------------------------------------------------------------------------------------------
 // workspace
@@ -11,12 +12,11 @@
 extern "C" void lrm_workspace_free(lrm_workspace *ws) {
     if (!ws) return;
     (void) hipSetDevice(ws->device);
-    (void) hipFree(ws->d_reads2); (void) hipFree(ws->d_rec); (void) hipFree(ws->d_phase); (void) hipFree(ws->d_decided);
-    (void) hipFree(ws->d_hcount); (void) hipFree(ws->d_counters); (void) hipFree(ws->d_recq); (void) hipFree(ws->d_cnt); (void) hipFree(ws->d_kc_key); (void) hipFree(ws->d_kc_ord); (void) hipFree(ws->d_redo); (void) hipFree(ws->d_big); (void) hipFree(ws->d_gtab); (void) hipFree(ws->d_glock);
+    lrm_dev_free({ws->d_reads2, ws->d_rec, ws->d_phase, ws->d_decided, ws->d_hcount, ws->d_counters, ws->d_recq, ws->d_cnt, ws->d_kc_key,
+                  ws->d_kc_ord, ws->d_redo, ws->d_big, ws->d_gtab, ws->d_glock, ws->d_mq_phase});
     lrm_bs_scratch_free(&ws->bs);
     lrm_anchor_scratch_free(ws);
     lrm_split_scratch_free(ws);
-    (void) hipFree(ws->d_mq_phase);
     if (ws->h_err) (void) hipHostFree((void *) ws->h_err);
     for (int i = 0; i < LRM_MAX_TIMED; ++i) {
         if (ws->ev_start[i]) (void) hipEventDestroy((hipEvent_t) ws->ev_start[i]);
@@ -60,31 +60,26 @@ int lrm_workspace_create_parts(lrm_workspace **out, lrm_index *idx, uint64_t n_m
         ws->g_slots = (uint32_t) gs;
         ws->g_slices = (uint32_t) (nsl < 2 ? 2 : nsl > 32 ? 32 : nsl);
     }
-    struct { void **p; uint64_t bytes; int part; } allocs[] = {
-        {(void **) &ws->d_reads2, n_max * ws->words_per_read * 8 + 128, LRM_WS_SEED},   // + slack: seed_search's scalar window loads reach 6 words
-
-        {(void **) &ws->d_rec, n_max * (uint64_t) ws->P * ws->cap_q * 8, LRM_WS_SEED},
-        {(void **) &ws->d_recq, n_max * (uint64_t) ws->P * ws->cap_q * 4, LRM_WS_SEED},
-        {(void **) &ws->d_cnt, n_max * (uint64_t) ws->P * 4, LRM_WS_SEED},
-        {(void **) &ws->d_kc_key, (uint64_t) LRM_VOTE_GRID * LRM_VOTE_KC_CAP * 8, LRM_WS_SEED},
-        {(void **) &ws->d_kc_ord, (uint64_t) LRM_VOTE_GRID * LRM_VOTE_KC_CAP * 4, LRM_WS_SEED},
-        {(void **) &ws->d_redo, n_max * (uint64_t) ws->P * 8, LRM_WS_SEED},
-        {(void **) &ws->d_big, n_max * (uint64_t) ws->P * 8, LRM_WS_SEED},
-        {(void **) &ws->d_gtab, (uint64_t) ws->g_slices * ws->g_slots * 16, LRM_WS_SEED},
-        {(void **) &ws->d_glock, 64 * 4, LRM_WS_SEED},
-        {(void **) &ws->d_phase, n_max * (uint64_t) ws->P * sizeof(LrmPhaseRes), LRM_WS_SEED},
-        {(void **) &ws->d_decided, n_max, LRM_WS_SEED},
-        {(void **) &ws->d_hcount, n_max * (uint64_t) ws->P * 4, LRM_WS_SEED},
-        {(void **) &ws->d_counters, sizeof(LrmDevCounters), LRM_WS_SEED | LRM_WS_EXTEND},
+    const LrmDevAlloc seed[] = {
+        {(void **) &ws->d_reads2, n_max * ws->words_per_read * 8 + 128},   // + slack: seed_search's scalar window loads reach 6 words
+        {(void **) &ws->d_rec, n_max * (uint64_t) ws->P * ws->cap_q * 8},
+        {(void **) &ws->d_recq, n_max * (uint64_t) ws->P * ws->cap_q * 4},
+        {(void **) &ws->d_cnt, n_max * (uint64_t) ws->P * 4},
+        {(void **) &ws->d_kc_key, (uint64_t) LRM_VOTE_GRID * LRM_VOTE_KC_CAP * 8},
+        {(void **) &ws->d_kc_ord, (uint64_t) LRM_VOTE_GRID * LRM_VOTE_KC_CAP * 4},
+        {(void **) &ws->d_redo, n_max * (uint64_t) ws->P * 8},
+        {(void **) &ws->d_big, n_max * (uint64_t) ws->P * 8},
+        {(void **) &ws->d_gtab, (uint64_t) ws->g_slices * ws->g_slots * 16},
+        {(void **) &ws->d_glock, 64 * 4},
+        {(void **) &ws->d_phase, n_max * (uint64_t) ws->P * sizeof(LrmPhaseRes)},
+        {(void **) &ws->d_decided, n_max},
+        {(void **) &ws->d_hcount, n_max * (uint64_t) ws->P * 4},
     };
-    for (auto &a : allocs) {
-        if (!(a.part & parts)) continue;
-        if (hipMalloc(a.p, a.bytes) != hipSuccess) {
-            lrm_set_error("hipMalloc of %llu workspace bytes failed", (unsigned long long) a.bytes);
-            lrm_workspace_free(ws);
-            return -1;
-        }
-        ws->bytes += a.bytes;
+    const LrmDevAlloc both[] = {{(void **) &ws->d_counters, sizeof(LrmDevCounters)}};
+    if (((parts & LRM_WS_SEED) && lrm_dev_alloc_table(seed, "workspace bytes", &ws->bytes)) ||
+        ((parts & (LRM_WS_SEED | LRM_WS_EXTEND)) && lrm_dev_alloc_table(both, "workspace bytes", &ws->bytes))) {
+        lrm_workspace_free(ws);
+        return -1;
     }
     if ((parts & LRM_WS_EXTEND) && lrm_bs_scratch_alloc(&ws->bs, n_max, max_len, max_len, &ws->bytes)) { lrm_workspace_free(ws); return -1; }
     if (hipMemset(ws->d_counters, 0, sizeof(LrmDevCounters)) != hipSuccess) { lrm_workspace_free(ws); lrm_set_error("memset failed"); return -1; }
