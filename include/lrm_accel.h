@@ -187,6 +187,8 @@ typedef struct lrm_map_options {
 void lrm_map_options_init(lrm_map_options *o);
 
 const char *lrm_last_error(void);
+/* releases what an entry point documents as "free with lrm_free" (malloc'd text, the .cat of lrm_cat_from_seqs) */
+void lrm_free(void *p);
 int lrm_abi_version(void);
 /* number of visible HIP devices (<=0: none). Does not fail loudly: probing only. */
 int lrm_device_count(void);

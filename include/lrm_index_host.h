@@ -3,9 +3,10 @@
  * (part of liblrm_accel.so; index construction stays on the CPU by design).
  *
  * Replaces, with byte-identical outputs for N-free references:
- *   create_meta   asindex.c:78-116      -> lrm_cat_from_seqs / lrm_create_meta_fasta
- *   sa_build      psascan/sa_use.cc:8-18 -> lrm_sa_build   (own SA-IS; the SA of a text that ends
- *                                                          in a unique minimal '$' is unique)
+ *   create_meta   asindex.c:78-116      -> lrm_cat_from_seqs
+ *   sa_build      psascan/sa_use.cc:8-18 -> lrm_sa_build   (parallel bucket sorter with an SA-IS
+ *                                                          fallback; the SA of a text that ends in a
+ *                                                          unique minimal '$' is unique)
  *   fmi_build     fmidx.c:166-198       -> lrm_host_index_build  (C, BWT, O, CSA)
  *   lc_build      lchash.c:52-73        -> lrm_host_index_build  (one pass over the SA instead of
  *                                                          4^hlen backward searches; same table)
@@ -37,7 +38,8 @@ typedef struct lrm_host_index {
 
 /* .cat text + .mta table from in-memory sequences (names may be NULL).
  * Bases are upper-cased; N/n is replaced by a seeded pseudo-random base
- * (the reference uses srand48(time), asindex.c:37-60,125 -- not reproducible). */
+ * (the reference uses srand48(time), asindex.c:37-60,125 -- not reproducible).
+ * Release *cat_out with lrm_free (lrm_accel.h) and *mta_out with lrm_mta_free. */
 int lrm_cat_from_seqs(const char *const *names, const char *const *seqs, const uint64_t *lens,
                       int nseq, uint64_t n_seed, char **cat_out, uint64_t *cat_len,
                       lrm_mta_entry **mta_out);
@@ -57,6 +59,8 @@ int lrm_host_index_write(const lrm_host_index *idx, const char *genome);
 int lrm_host_index_read(const char *genome, lrm_host_index *out);
 
 int lrm_fmi_write(const lrm_dna_fmi *fmi, const char *prefix);      /* prefix + ".mfi" */
+/* lrm_fmi_read and lrm_lc_read allocate the arrays (free() releases them); after a failure the
+ * struct is all zero and nothing is left allocated. */
 int lrm_fmi_read(lrm_dna_fmi *fmi, const char *prefix);
 int lrm_lc_write(const char *path, const lrm_lc_hash *h);
 int lrm_lc_read(const char *path, lrm_lc_hash *h);

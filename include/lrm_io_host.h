@@ -78,7 +78,6 @@ char *lrm_sam_format_split(const lrm_read_batch *reads, const lrm_mta_entry *mta
 char *lrm_sam_format_mapq(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig,
                           const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t n, int cigar_is_text,
                           int revcomp_here, const lrm_split_out *split, const lrm_mapq *mq, uint64_t *len_out);
-void lrm_free(void *p);
 
 /* `accaln genome reads [batch seed_len thres]` on the GPU path: loads the index files next to
  * `genome`, maps `reads_path` batch by batch, writes SAM to `sam_path`.  total/valid are the

@@ -158,6 +158,7 @@ assert MapOptions.split.offset == 68 and C.sizeof(Segment) == 16 and C.sizeof(Sp
 # every symbol include/*.h declares: (restype, argtypes)
 SYMBOLS = {
     "lrm_last_error": (C.c_char_p, []),
+    "lrm_free": (None, [C.c_void_p]),
     "lrm_abi_version": (C.c_int, []),
     "lrm_device_count": (C.c_int, []),
     "lrm_index_blob_bytes": (C.c_uint64, [C.c_uint64, C.c_int, C.c_int]),
@@ -288,7 +289,6 @@ SYMBOLS = {
                                           C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(SplitOut), u64p]),
     "lrm_sam_format_mapq": (C.c_void_p, [C.POINTER(ReadBatch), C.POINTER(MtaEntry), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(SplitOut), C.c_void_p, u64p]),
-    "lrm_free": (None, [C.c_void_p]),
     "lrm_accaln": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, Params, GactParams, C.c_int, C.c_long, u64p, u64p]),
     "lrm_accaln_opt": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, Params, GactParams, C.c_int, C.c_long, u64p, u64p,
                                  C.POINTER(MapOptions)]),

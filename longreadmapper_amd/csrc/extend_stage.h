@@ -18,8 +18,6 @@
 #else
 #define LRM_HD
 #endif
-// internal functions that cross files without joining the library's exported symbols
-#define LRM_LOCAL __attribute__((visibility("hidden")))
 
 // ---- tile geometry and walk bound (docs/GACT_SPEC.md): ONE copy for the byte kernels and the plan -------------------------
 // 16-step traceback blocks of a tile: the walk never passes anti-diagonal 2(T-O)

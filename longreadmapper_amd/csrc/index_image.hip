@@ -63,10 +63,6 @@ extern "C" uint64_t lrm_index_blob_bytes(uint64_t length, int hlen, int mta_len)
     return lrm_index_blob_bytes_opt(length, hlen, mta_len, nullptr);
 }
 
-static inline int code_of(char c) {
-    switch (c) { case 'A': return 0; case 'C': return 1; case 'G': return 2; case 'T': return 3; default: return -1; }
-}
-
 // The image is produced SECTION BY SECTION in pieces of <= LRM_PACK_PIECE bytes, every piece by all host
 // threads, so that the same code fills a host blob (lrm_index_pack_blob) or a pair of pinned chunks whose DMA
 // overlaps the packing of the next piece (lrm_index_upload: no host copy of the image -- GRCh38 is a 63 GB
@@ -110,7 +106,7 @@ struct BlobPacker {
             uint64_t c[4] = {0, 0, 0, 0};
             for (uint64_t i = lo; i < hi; ++i) {
                 const char ch = fmi->bwt[i];
-                const int code = code_of(ch);
+                const int code = base_code(ch);
                 if (code >= 0) c[code]++;
                 else if (ch == '$') { n_dollar++; if (i < dollar) dollar = i; }
                 else if (i < bad_row) bad_row = i;
@@ -177,7 +173,7 @@ struct BlobPacker {
             for (int x = 0; x < 4; ++x) run[x] = seg_cnt[sgc * 4 + x];
             const uint64_t blo = sg * bps > b0 ? sg * bps : b0, bhi = (sg + 1) * bps < b0 + nb ? (sg + 1) * bps : b0 + nb;
             // rows of the segment before blo (a piece boundary inside a segment): count them
-            for (uint64_t i = sg * SEG; i < blo * LRM_OCC_ROWS && i < L; ++i) { const int c = code_of(fmi->bwt[i]); if (c >= 0) run[c]++; }
+            for (uint64_t i = sg * SEG; i < blo * LRM_OCC_ROWS && i < L; ++i) { const int c = base_code(fmi->bwt[i]); if (c >= 0) run[c]++; }
             for (uint64_t b = blo; b < bhi; ++b) {
                 LrmOccBlock blk;
                 for (int x = 0; x < 4; ++x) { blk.sym[x].cnt = h.c4[x] + run[x]; blk.sym[x].mask = 0; }
@@ -187,7 +183,7 @@ struct BlobPacker {
                         const uint64_t *o = fmi->o + 4 * (i / ratio);
                         if ((o[0] != run[0] || o[1] != run[1] || o[2] != run[2] || o[3] != run[3]) && i < bad) bad = i;
                     }
-                    const int c = code_of(fmi->bwt[i]);
+                    const int c = base_code(fmi->bwt[i]);
                     if (c >= 0) { run[c]++; blk.sym[c].mask |= 1ull << (i & 63); }
                 }
                 dst[b - b0] = blk;
@@ -218,10 +214,7 @@ struct BlobPacker {
     void fill_sa(uint64_t e0, uint64_t n, uint64_t *dst) const {
         const uint64_t r = h.sa_ratio;
 #pragma omp parallel for num_threads(lrm_host_threads()) schedule(static)
-        for (uint64_t i = 0; i < n; ++i) {
-            const lrm_ui40 &v = sa->mem[(e0 + i) * r];
-            dst[i] = ((uint64_t) v.high << 32) | (uint64_t) v.low;
-        }
+        for (uint64_t i = 0; i < n; ++i) dst[i] = ui40_get(sa->mem[(e0 + i) * r]);
     }
 
     // text bytes [o, o + n) and the NUL behind the text

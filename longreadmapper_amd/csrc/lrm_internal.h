@@ -27,6 +27,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 #include "../../include/lrm_accel.h"
 
@@ -266,6 +267,29 @@ struct lrm_workspace {
 int lrm_lcl_prepare_index(lrm_index *idx);       // index_tables.hip: the long lc table, the core table, the seed table
 
 void lrm_set_error(const char *fmt, ...);
+// internal functions that cross files without joining the library's exported symbols
+#define LRM_LOCAL __attribute__((visibility("hidden")))
+
+// THE code of a base: upper-case A, C, G, T -> 0..3, every other byte (lower case too) -> -1
+static inline int base_code(char c) {
+    switch (c) { case 'A': return 0; case 'C': return 1; case 'G': return 2; case 'T': return 3; default: return -1; }
+}
+
+// THE accessors of a suffix-array slot.  lrm_ui40 is {u32 low; u8 high} in 8 bytes (sa_use.h:17-20), 5 bytes low-first on
+// disk.  This library writes a slot as one little-endian u64: the value is < 2^40, so the three padding bytes are zero and
+// the slot read as a u64 is the value (HostIndex.sa() is such a view).
+static_assert(sizeof(lrm_ui40) == 8, "ui40 is 8 bytes in RAM (sa_use.h:17-20)");
+static inline uint64_t ui40_get(const lrm_ui40 &v) { return ((uint64_t) v.high << 32) | v.low; }
+static inline void ui40_put(lrm_ui40 *slot, uint64_t v) { *reinterpret_cast<uint64_t *>(slot) = v; }
+
+// malloc (zero: calloc) of n elements into p; false + "out of memory (what, bytes)" if there is none
+template <typename T>
+static inline bool lrm_alloc(T *&p, uint64_t n, const char *what, bool zero = false) {
+    const size_t bytes = (size_t) (n ? n : 1) * sizeof(T);
+    p = (T *) (zero ? calloc(1, bytes) : malloc(bytes));
+    if (!p) lrm_set_error("out of memory (%s, %llu bytes)", what, (unsigned long long) bytes);
+    return p != nullptr;
+}
 // OpenMP team size for the library's host loops: omp_get_max_threads() capped by the CPUs this process may really use
 // (affinity mask, cgroup CPU quota) -- a GPU box hands a job 16 of its 256 hardware threads, and a team of 256 on a
 // quota of 16 is throttled to a crawl.  OMP_NUM_THREADS still lowers it.

@@ -45,7 +45,7 @@ class HostIndex:
             check(lib.lrm_host_index_build(cat, cat_len.value, mta, n, o_ratio, hlen, C.byref(self.h)),
                   "lrm_host_index_build")
         finally:
-            C.CDLL(None).free(cat)
+            lib.lrm_free(cat)
             lib.lrm_mta_free(mta, n)
         self._owned = True
         return self

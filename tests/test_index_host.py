@@ -191,3 +191,144 @@ def test_suffix_sorter_falls_back_on_repetitive_text(monkeypatch):
     sa = out.astype(np.int64)
     sufs = [text[i:] for i in sa[:200]]
     assert sufs == sorted(sufs) and np.array_equal(np.sort(sa), np.arange(len(text)))
+
+
+# ---- files that end early, readers called directly, builds side by side, texts that are not upper-case ACGT ----
+
+_FILES = (".mta", ".cat", ".cat.mfi", ".cat.lch", ".cat.sa5")
+
+
+@pytest.fixture(scope="module")
+def small_index_files(tmp_path_factory):
+    """A 2000-base, two-sequence index (hlen 4) written once; every case below works on its own copy of the files."""
+    ref = synth.reference(2000, seed=17)
+    hi = index.HostIndex.build([ref[:1300], ref[1300:]], names=["one", "two"], hlen=4)
+    g = str(tmp_path_factory.mktemp("small_index") / "ref.fa")
+    hi.write(g)
+    return g, hi
+
+
+def _copy_index(g, tmp_path):
+    import shutil
+    dst = str(tmp_path / "ref.fa")
+    for ext in _FILES:
+        shutil.copy(g + ext, dst + ext)
+    return dst
+
+
+def _cut(path, size):
+    assert 0 <= size < os.path.getsize(path)
+    with open(path, "r+b") as f:
+        f.truncate(size)
+
+
+def _field_cuts(sizes):
+    """A byte offset inside every field of a file whose fields have these sizes."""
+    at, cuts = 0, []
+    for s in sizes:
+        cuts.append(at + s // 2)
+        at += s
+    return cuts
+
+
+_L_SMALL = 2 * 2000 + 1
+_MFI_FIELDS = ("c", "o_ratio", "o_len", "o", "length", "bwt", "csa_ratio", "csa_len", "csa")
+_MFI_SIZES = (2048, 4, 8, 8 * 4 * (_L_SMALL // 32 + 1), 8, _L_SMALL, 4, 8, 8 * (_L_SMALL // 4 + 1))
+_LCH_FIELDS = ("hlen", "len", "lc")
+_LCH_SIZES = (4, 8, 8 * 2 * 4 ** 4)
+_TRUNCATIONS = [(".cat.mfi", f, c) for f, c in zip(_MFI_FIELDS, _field_cuts(_MFI_SIZES))] + \
+               [(".cat.lch", f, c) for f, c in zip(_LCH_FIELDS, _field_cuts(_LCH_SIZES))]
+
+
+@pytest.mark.parametrize("ext,field,cut", _TRUNCATIONS, ids=["%s-%s" % (e[5:], f) for e, f, _ in _TRUNCATIONS])
+def test_read_of_truncated_table_file_fails_and_names_it(small_index_files, tmp_path, ext, field, cut):
+    g, hi = small_index_files
+    assert os.path.getsize(g + ".cat.mfi") == sum(_MFI_SIZES) and os.path.getsize(g + ".cat.lch") == sum(_LCH_SIZES)
+    d = _copy_index(g, tmp_path)
+    _cut(d + ext, cut)
+    with pytest.raises(capi.LrmError) as e:
+        index.HostIndex.read(d)
+    assert os.path.basename(d + ext) in str(e.value)
+
+
+def test_read_without_cat_fails_and_names_it(small_index_files, tmp_path):
+    d = _copy_index(small_index_files[0], tmp_path)
+    os.remove(d + ".cat")
+    with pytest.raises(capi.LrmError) as e:
+        index.HostIndex.read(d)
+    assert os.path.basename(d + ".cat") in str(e.value) and ".cat." not in str(e.value)
+
+
+def test_read_of_truncated_mta_and_sa5_keeps_what_is_whole(small_index_files, tmp_path):
+    g, hi = small_index_files
+    d = _copy_index(g, tmp_path)
+    rec = 8 + 3 + 8 + 8                                       # name length, "one", offset, seq_len
+    assert os.path.getsize(d + ".mta") == 2 * rec
+    _cut(d + ".mta", rec + rec // 2)                          # the middle of the second record (alnmain.c:125-140 stops there)
+    back = index.HostIndex.read(d)
+    assert back.mta() == hi.mta()[:1] == [("one", 0, 1300)]
+    k = 1234
+    _cut(d + ".cat.sa5", 5 * k)                               # ui40_fread semantics: the count it got (sa_use.h:31-46)
+    back = index.HostIndex.read(d)
+    assert int(back.h.sa.len) == k and np.array_equal(back.sa(), hi.sa()[:k])
+    assert back.length == hi.length and np.array_equal(back.bwt(), hi.bwt())
+
+
+def test_direct_readers_leave_a_zeroed_struct_on_failure(small_index_files, tmp_path):
+    d = _copy_index(small_index_files[0], tmp_path)
+    _cut(d + ".cat.mfi", _field_cuts(_MFI_SIZES)[5])          # inside bwt: c and o were allocated by then
+    _cut(d + ".cat.lch", _field_cuts(_LCH_SIZES)[2])          # inside lc
+    fmi = capi.DnaFmi()
+    C.memset(C.byref(fmi), 0xFF, C.sizeof(fmi))
+    assert capi.lib.lrm_fmi_read(C.byref(fmi), (d + ".cat").encode()) == -1
+    assert b".cat.mfi" in capi.lib.lrm_last_error()
+    assert not fmi.c and not fmi.o and not fmi.csa and not fmi.bwt
+    assert bytes(fmi) == bytes(C.sizeof(fmi))
+    lch = capi.LcHash()
+    C.memset(C.byref(lch), 0xFF, C.sizeof(lch))
+    assert capi.lib.lrm_lc_read((d + ".cat.lch").encode(), C.byref(lch)) == -1
+    assert b".cat.lch" in capi.lib.lrm_last_error()
+    assert not lch.lc
+    assert bytes(lch) == bytes(C.sizeof(lch))
+
+
+def test_concurrent_builds_equal_serial_builds():
+    """Two builds at once in one process (ctypes releases the GIL): no state is shared between them."""
+    import threading
+    texts = [synth.reference(50_000, seed=41), synth.reference(50_000, seed=42)]
+    want = []
+    for t in texts:
+        hi = index.HostIndex.build([t], hlen=6)
+        want.append((hi.sa().copy(), hi.bwt().copy(), hi.lc().copy()))
+    bad = []
+
+    def work(i):
+        for _ in range(4):
+            hi = index.HostIndex.build([texts[i]], hlen=6)
+            if not all(np.array_equal(a, b) for a, b in zip((hi.sa(), hi.bwt(), hi.lc()), want[i])):
+                bad.append(i)
+
+    th = [threading.Thread(target=work, args=(i,)) for i in range(2)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join()
+    assert not bad
+
+
+def test_lower_case_text_builds_the_recorded_tables():
+    """A text handed straight to lrm_host_index_build is not upper-cased: lower-case bases take the generic paths (SA-IS,
+    byte-wise C table, tolerant base codes in the O table and the lchash).  tests/golden/lower_case_index.npz holds the
+    text and the tables the library built from it before the builder was split into files."""
+    gold = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lower_case_index.npz"))
+    text = np.ascontiguousarray(gold["text"])
+    assert len(text) == 3000 and bytes(text[-1:]) == b"$" and bytes(text[:-1]).islower()
+    h = capi.HostIndex()
+    capi.check(capi.lib.lrm_host_index_build(text.ctypes.data, len(text), None, 0, 32, 4, C.byref(h)), "lrm_host_index_build")
+    try:
+        hi = index.HostIndex()
+        hi.h = h
+        for f in ("c", "o", "bwt", "lc", "sa"):
+            assert np.array_equal(getattr(hi, f)(), gold[f]), f
+    finally:
+        capi.lib.lrm_host_index_free(C.byref(h))
