@@ -543,6 +543,11 @@ int lrm_debug_seed_search(lrm_index *idx, const char *read, uint32_t len, uint32
                           uint32_t thres, int32_t *j_out, uint64_t *rr_out, uint64_t *k_out,
                           uint64_t *l_out, uint64_t cap, uint64_t *n_out);
 
+/* Debug/parity tap (tests only): what the vote kernels left for the first n reads of the last seed call on this
+ * workspace -- six words {key1, val1, bucket1, key2, val2, bucket2} per (read, phase), read-major, seed_len + 1 phases per
+ * read.  Only the phases the call evaluated are meaningful (phase 0 always is). */
+int lrm_debug_vote_results(lrm_workspace *ws, uint64_t n, uint64_t *out, void *stream);
+
 /* Test-only: force the multi-pass vote tier of this handle's batches into overflow (a pass limit above the table size
  * and a small table); 0, 0 restores the defaults. */
 int lrm_debug_set_vote_limits(lrm_index *idx, uint32_t t3_limit, uint32_t t3_slots);

@@ -247,6 +247,7 @@ SYMBOLS = {
                                   Params, GactParams, C.POINTER(MapOptions), C.POINTER(SplitOut)]),
     "lrm_debug_anchor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(Anchor)]),
     "lrm_workspace_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats), C.c_void_p]),
+    "lrm_debug_vote_results": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "lrm_workspace_set_counting": (C.c_int, [C.c_void_p, C.c_int]),
     "lrm_workspace_set_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "lrm_workspace_timing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

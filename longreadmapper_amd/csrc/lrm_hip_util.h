@@ -82,6 +82,32 @@ __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
     return ((uint64_t) hi << 32) | lo;
 }
 
+// the same for 32-bit values -- one DPP operand and one v_max_u32 / v_or_b32 per step instead of two moves, a 64-bit
+// compare and two selects: a third of the instructions of wave_max_u64
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint32_t dpp_src_u32(uint32_t v) {
+    return (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, CTRL, ROW_MASK, 0xf, false);   // 0 where the lane has no source
+}
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+    uint32_t o;
+    o = dpp_src_u32<0x111, 0xf>(v); v = o > v ? o : v;
+    o = dpp_src_u32<0x112, 0xf>(v); v = o > v ? o : v;
+    o = dpp_src_u32<0x114, 0xf>(v); v = o > v ? o : v;
+    o = dpp_src_u32<0x118, 0xf>(v); v = o > v ? o : v;
+    o = dpp_src_u32<0x142, 0xa>(v); v = o > v ? o : v;
+    o = dpp_src_u32<0x143, 0xc>(v); v = o > v ? o : v;
+    return (uint32_t) __builtin_amdgcn_readlane((int) v, 63);
+}
+__device__ __forceinline__ uint32_t wave_or_u32(uint32_t v) {
+    v |= dpp_src_u32<0x111, 0xf>(v);
+    v |= dpp_src_u32<0x112, 0xf>(v);
+    v |= dpp_src_u32<0x114, 0xf>(v);
+    v |= dpp_src_u32<0x118, 0xf>(v);
+    v |= dpp_src_u32<0x142, 0xa>(v);
+    v |= dpp_src_u32<0x143, 0xc>(v);
+    return (uint32_t) __builtin_amdgcn_readlane((int) v, 63);
+}
+
 // ---- index gathers and hit expansion shared by the vote kernels (vote_kernels.hip), the seed-table build (index_tables.hip) and the mapping-quality vote (mapq_kernels.hip) ----
 // ----------------------------------------------------------------------------------------
 // FM LF-mapping: lf(c, loc) = C[c] + rank(c, loc), rank = # of c in bwt[0..loc] == _occ_access (fmidx.c:277-293)

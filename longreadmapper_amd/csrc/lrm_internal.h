@@ -203,7 +203,9 @@ static_assert(offsetof(LrmDevCounters, decided_phase0) == 64 && sizeof(LrmDevCou
 #endif
 #define LRM_VOTE_T3_LIMIT (LRM_VOTE_T3_SLOTS * 3 / 4)
 #define LRM_VOTE_GRID 1536        // resident workgroups of the vote kernel (6 per CU)
-#define LRM_VOTE_FAST_GRID 1280   // ... of the fast vote kernel (5 per CU)
+#ifndef LRM_VOTE_FAST_GRID
+#define LRM_VOTE_FAST_GRID 1792   // ... of the fast vote kernel (7 per CU: its 22.6 KB of LDS per workgroup allow no more)
+#endif
 #define LRM_VOTE_KC_CAP 16384     // hits per workgroup whose keys the multi-pass items keep between passes (12 B each)
 
 enum LrmKernelId { LRM_K_PACK2BIT = 0, LRM_K_SEED_SEARCH, LRM_K_VOTE, LRM_K_DECIDE,

@@ -24,6 +24,11 @@
 // item, and all gathers of a step (up to 4 per lane) are in flight before the first vote is cast.  (The first
 // version walked repeat seeds two at a time, one memory latency per pair: an item with 24 repeat seeds took 12
 // dependent round trips, now 1-2.)
+// In front of that kernel run the FAST kernels (further down: "fast path"), which settle nearly every item of a real batch:
+// their table only counts -- a slot is {u32 identity of the bucket, u32 count}, an insert one 32-bit compare-and-swap and
+// one add -- and holds the unique seeds' buckets only; repeat seeds' hits are looked up in it and otherwise go to a sketch.
+// The top two, their minimum keys and their first-seen order are taken from the HITS once the table is final (the rank
+// step: 32-bit wave reductions, no table scan).  What they cannot settle goes to the exact kernel above by item number.
 // ----------------------------------------------------------------------------------------
 #define VG 16                // items per workgroup (default; LRM_VOTE_VG)
 #define VG_MAX 64
@@ -438,58 +443,208 @@ __device__ __forceinline__ void vote_item_block(const LrmIndexView &ix, const ui
 // item from the 256-slot wavefront table into the workgroup tier and its passes.  They cannot win.  The vote's output is
 // the top entry and the COUNT of the second (alnmain.c:374-388 reads cand[0] and cand[1].val only), so:
 //   A  the hits of the UNIQUE seeds (rr == 1; at most one per survivor) are inserted as before -- table T;
-//   B  a hit of a repeat seed is looked up in T with plain reads: present -> counted (count, min key, first-seen
-//      order: exactly what an insert would have done); absent -> it belongs to a bucket made of repeat hits only, and
+//   B  a hit of a repeat seed is looked up in T with plain reads: present -> counted, and noted on a short LDS list (it may
+//      hold its bucket's smallest key or earliest order); absent -> it belongs to a bucket made of repeat hits only, and
 //      only a 16-bit counter of a small SKETCH (indexed by a hash of the bucket) is incremented -- no compare-and-swap,
 //      no probe chain, no table space;
 //   C  with t2 = the second-highest count in T and M = the largest sketch counter (>= the count of every repeat-only
 //      bucket): if M < t2 no repeat-only bucket reaches the top two, and the top two of T are the item's result, bit for
-//      bit.  Otherwise (few true hits, or a read made of repeats) the item goes on a list for the exact kernel above.
+//      bit.  Otherwise (few true hits, a read made of repeats, more step-B entries than the list holds) the item goes
+//      on a list for the exact kernel above.
 // The table only ever holds buckets of unique seeds (<= survivors <= T1_LIMIT), so an item needs one pass whatever its
 // hit count, and a wavefront stages its repeat seeds 64 survivors at a time.  Items with more than T1_LIMIT survivors go
 // to the exact kernel as well.
 #define FAST_SK_WORDS 512                    // 1024 16-bit counters per wavefront
 #define FB_LIMIT 1536                        // survivors up to which the workgroup form takes an item (75 % of its 2048 slots)
+
+// The table of the fast kernels counts and nothing else: a slot is {u32 identity, u32 count} in two arrays.  A vote key is
+// SA - j (u64 wrap): on a text of fewer than 2^35 rows it lies in [0, 2^35) or in [2^64 - 2^32, 2^64), so the low 32 bits
+// of its bucket key >> 4 -- [0, 2^31) or [2^32 - 2^28, 2^32) -- name the bucket, and the bucket comes back from them
+// (bucket_of_ident).  The launcher takes the fast kernels only on such a text (every text the project handles; the exact
+// kernel has no such limit), and an item with a key outside the two ranges all the same (key_wide) is left to the exact
+// kernel: exactness does not rest on the row count.  An insert is one 32-bit compare-and-swap and one 32-bit add; the min key and the first-seen
+// order of a bucket are NOT kept current: only the top two buckets' are ever used, and they are properties of the HITS,
+// which the lanes still hold when the table is final (the rank step below).
+// (The exact kernel's slot is {u64 min key, u64 count << 32 | ~first}: a 64-bit compare-and-swap, sometimes a 64-bit min, an
+//  add and a max per hit, and twice the LDS.)
+#define EMPTY_ID 0x80000000u                 // in neither range
+#define FAST_NONE 0xFFFFFFFFu                // no slot / no hit
+struct FastTable { uint32_t *ident, *count; uint32_t slots; };
+
+// a key outside the two ranges (an index whose suffix-array values reach 2^35: the ui40 format holds 2^40): its bucket has
+// no 32-bit name, and the item it belongs to goes to the exact kernel
+__device__ __forceinline__ bool key_wide(uint64_t key) { return (uint32_t) (key >> 32) + 1u > 8u; }
+__device__ __forceinline__ uint64_t bucket_of_ident(uint32_t id) {
+    return id < 0x80000000u ? (uint64_t) id : (0x0FFFFFFF00000000ull | id);
+}
+
+// A: the slot of the bucket, claimed or found, with the hit counted; FAST_NONE if the table is full (never: both forms size
+// the table above their survivor limit) -- the probe loop is bounded so a wave can never spin
+__device__ __forceinline__ uint32_t fast_insert(const FastTable &t, uint32_t id, uint32_t hash) {
+    uint32_t slot = (uint32_t) (((uint64_t) hash * t.slots) >> 32);
+    for (uint32_t probe = 0; probe < t.slots; ++probe) {
+        const uint32_t prev = atomicCAS(&t.ident[slot], EMPTY_ID, id);
+        if (prev == EMPTY_ID || prev == id) { atomicAdd(&t.count[slot], 1u); return slot; }
+        slot = slot + 1 == t.slots ? 0 : slot + 1;
+    }
+    return FAST_NONE;
+}
+// B: the slot of the bucket if the table has it (plain reads; no deletions: an empty slot ends the chain)
+__device__ __forceinline__ uint32_t fast_find(const FastTable &t, uint32_t id, uint32_t hash) {
+    uint32_t slot = (uint32_t) (((uint64_t) hash * t.slots) >> 32);
+    for (uint32_t probe = 0; probe < t.slots; ++probe) {
+        const uint32_t prev = t.ident[slot];
+        if (prev == EMPTY_ID) return FAST_NONE;
+        if (prev == id) return slot;
+        slot = slot + 1 == t.slots ? 0 : slot + 1;
+    }
+    return FAST_NONE;
+}
+
+// A hit that counted in the table, as its lane keeps it: the word slot << 4 | (key & 15) -- the key is the bucket's
+// identity and these four bits -- and its order key.  A repeat seed's hit that lands in a table bucket (step B) can lower
+// that bucket's min key or its first-seen order, so it goes on a small LDS list as ~order << 32 | word and takes part in
+// the rank step like the unique seeds' hits.  An item with more of them than the list holds goes to the exact kernel:
+// exactness never depends on the capacity.
+// Capacity of the wavefront form, 64 entries: on the bench batch (100 k x 10 kbp ONT reads, E. coli sized text with 5 %
+// planted repeats, 2.1 M items) NO item has more than 32 -- a build with 32 entries and one with 64 leave the same 20 527
+// items to the exact kernel as the kernels before them, which had no list (profiles/r4/README.md) -- and vote takes the
+// same time with either (3.447 / 3.445 ms); 64 is one entry per lane of the rank step and 512 bytes.
+#ifndef LRM_VOTE_FAST_LIST
+#define LRM_VOTE_FAST_LIST 64
+#endif
+#define FAST_LIST LRM_VOTE_FAST_LIST
+#define FB_LIST 512                          // workgroup form: items of up to FB_LIMIT survivors
+__device__ __forceinline__ uint32_t hit_word(uint32_t slot, uint64_t key) { return (slot << 4) | ((uint32_t) key & 15u); }
+
+// B over the staged repeat seeds (for_each_hit's shape: all gathers of a step first).  n_list: entries so far, a wave-uniform
+// register in the wavefront form (NT == 64); the workgroup form counts in the LDS word list_n instead.
+template <int NT, int VOTE_U>
+__device__ __forceinline__ void fast_hits(const LrmIndexView &ix, const FastTable &t, const Staged &g, uint32_t *sketch, uint32_t sk_mask,
+                                          uint32_t tid, uint64_t *list, uint32_t cap, uint32_t &n_list, uint32_t *list_n, bool &wide) {
+    for (uint32_t hb = 0; hb < g.total; hb += NT * VOTE_U) {
+        uint64_t v[VOTE_U];
+        uint32_t ss[VOTE_U], tt[VOTE_U];
+#pragma unroll
+        for (int u = 0; u < VOTE_U; ++u) {
+            const uint32_t h = hb + (uint32_t) u * NT + tid;
+            v[u] = 0; ss[u] = 0; tt[u] = 0;
+            if (h < g.total) {
+                const uint32_t s = find_seed(g.off, g.cnt, h);
+                ss[u] = s;
+                tt[u] = h - g.off[s];
+                v[u] = sa_locate(ix, (g.srec[s] & ((1ull << 40) - 1ull)) + tt[u]);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < VOTE_U; ++u) {
+            const uint32_t h = hb + (uint32_t) u * NT + tid;
+            uint32_t hw = FAST_NONE, oinv = 0;
+            if (h < g.total) {
+                const uint32_t q = g.sq[ss[u]];
+                const uint64_t key = v[u] - (uint64_t) (g.iter + q * g.P);                    // alnmain.c:363-365 (u64 wrap kept); j < 2^32
+                const uint32_t hash = bucket_hash(key >> 4);
+                wide |= key_wide(key);
+                const uint32_t slot = fast_find(t, (uint32_t) (key >> 4), hash);
+                if (slot != FAST_NONE) {
+                    atomicAdd(&t.count[slot], 1u);
+                    hw = hit_word(slot, key);
+                    oinv = 0xFFFFFFFFu - ((q << g.tbits) | tt[u]);
+                } else {
+                    const uint32_t c = (hash >> 5) & sk_mask;
+                    atomicAdd(&sketch[c >> 1], 1u << (16 * (c & 1)));          // < 2^16 hits per bucket: 16 per seed at most
+                }
+            }
+            // (the loop bounds are uniform, so every lane of the wavefront is here)
+            const unsigned long long bm = __ballot(hw != FAST_NONE);
+            if (bm) {
+                uint32_t base;
+                if (NT == 64) { base = n_list; n_list += (uint32_t) __popcll(bm); }
+                else {
+                    uint32_t b0 = 0;
+                    if ((tid & 63u) == 0) b0 = atomicAdd(list_n, (uint32_t) __popcll(bm));
+                    base = (uint32_t) __builtin_amdgcn_readfirstlane((int) b0);
+                }
+                if (hw != FAST_NONE) {
+                    const uint32_t i = base + mask_rank(bm);
+                    if (i < cap) list[i] = ((uint64_t) oinv << 32) | hw;
+                }
+            }
+        }
+    }
+}
+
+// ---- the rank step: the stable top two from the hits ------------------------------------------------------------------
+// "count descending, first-seen ascending" is a property of the hits: with the table final, hit h in slot s has
+// r(h) = count[s] << 32 | ~order(h) (a plain LDS read), the winner is the slot of the hit with the largest r, the second the
+// slot of the largest r among the hits outside the winner's slot, and their keys are the smallest keys among their hits --
+// the bucket's identity and the smallest low four bits.  No table scan.  A 64-bit maximum is taken as two 32-bit ones (the
+// count, then ~order among the lanes that hold it); the two minima of four bits come out of ONE 32-bit OR reduction of
+// 0x8000 >> low4 (the winner's in the high half).
+struct RankTop { uint64_t r; uint32_t s; };              // r == 0: none
+__device__ __forceinline__ RankTop wave_top_rank(const RankTop &x) {
+    const uint32_t hi = (uint32_t) (x.r >> 32), lo = (uint32_t) x.r;
+    const uint32_t mh = wave_max_u32(hi);
+    const uint32_t ml = wave_max_u32(hi == mh ? lo : 0u);
+    RankTop w = {0, 0};
+    if (mh) {
+        const unsigned long long b = __ballot(hi == mh && lo == ml);       // order keys are unique per hit: one lane
+        w.r = ((uint64_t) mh << 32) | ml;
+        w.s = (uint32_t) __builtin_amdgcn_readlane((int) x.s, (int) __builtin_ctzll(b));
+    }
+    return w;
+}
+template <int N>
+__device__ __forceinline__ RankTop lane_top_rank(const uint64_t (&hr)[N], const uint32_t (&hw)[N], uint32_t skip) {
+    RankTop b = {0, 0};
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const uint32_t s = hw[k] >> 4;
+        if (hr[k] > b.r && s != skip) { b.r = hr[k]; b.s = s; }
+    }
+    return b;
+}
+template <int N>
+__device__ __forceinline__ uint32_t lane_low4_mask(const uint64_t (&hr)[N], const uint32_t (&hw)[N], const RankTop &a, const RankTop &b) {
+    uint32_t m = 0;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const uint32_t s = hw[k] >> 4, bit = 0x8000u >> (hw[k] & 15u);
+        if (hr[k] && s == a.s) m |= bit << 16;
+        else if (hr[k] && b.r && s == b.s) m |= bit;
+    }
+    return m;
+}
+__device__ __forceinline__ TopEntry fast_entry(const FastTable &t, const RankTop &w, uint32_t mask16) {
+    TopEntry e = {0, 0, 0, 0};
+    if (w.r) {
+        e.bucket = bucket_of_ident(t.ident[w.s]);
+        e.key = (e.bucket << 4) | (uint32_t) (__clz((int) mask16) - 16);
+        e.val = (uint32_t) (w.r >> 32); e.first = 0xFFFFFFFFu - (uint32_t) w.r;
+    }
+    return e;
+}
+
+// ---- fast path, wavefront form ------------------------------------------------------------------------------------------
 struct FastLds {
-    uint64_t key[T1_SLOTS];
-    uint64_t cf[T1_SLOTS];
+    uint32_t ident[T1_SLOTS];
+    uint32_t count[T1_SLOTS];
     uint64_t srec[64];
+    uint64_t list[FAST_LIST];
     uint32_t off[64 + 4];
     uint32_t sq[64];
     uint32_t sketch[FAST_SK_WORDS];
 };
 
-// B: returns true if the bucket is in the table (and has been counted)
-__device__ __forceinline__ bool vote_count_if_present(const VoteTable &t, uint64_t key, uint32_t order, uint32_t hash) {
-    const uint64_t bucket = key >> 4;
-    uint32_t slot = (uint32_t) (((uint64_t) hash * t.slots) >> 32);
-    for (uint32_t probe = 0; probe < t.slots; ++probe) {
-        const uint64_t prev = t.key[slot];
-        if (prev == EMPTY_KEY) return false;                              // (no deletions: an empty slot ends the chain)
-        if ((prev >> 4) == bucket) {
-            slot_count(t, slot, key < prev, key, order, 1u);
-            return true;
-        }
-        slot = slot + 1 == t.slots ? 0 : slot + 1;
-    }
-    return false;
-}
-
-template <int NT, int VOTE_U>
-__device__ __forceinline__ void fast_hits(const LrmIndexView &ix, const VoteTable &t, const Staged &g, uint32_t *sketch, uint32_t sk_mask,
-                                          uint32_t tid) {
-    for_each_hit<NT, VOTE_U>(ix, g, tid, [&](uint32_t, uint64_t key, uint32_t order) __attribute__((always_inline)) {
-        const uint32_t hash = bucket_hash(key >> 4);
-        if (!vote_count_if_present(t, key, order, hash)) {
-            const uint32_t c = (hash >> 5) & sk_mask;
-            atomicAdd(&sketch[c >> 1], 1u << (16 * (c & 1)));              // < 2^16 hits per bucket: 16 per seed at most
-        }
-    });
-}
-
+// 64 VGPRs and 22.6 KB of LDS per workgroup: seven workgroups per CU (the 16-byte slots' 28.7 KB allowed five).  vote per
+// 1-Gbp step, each kernel alone on the chip: 3.88 ms with five, 3.57 with six, 3.44 with seven [r4]
+// (builds without the per-hit key_wide test, which adds about 0.05 ms to each)
+#ifndef LRM_VOTE_FAST_WAVES
+#define LRM_VOTE_FAST_WAVES (LRM_VOTE_FAST_GRID / 256)      // workgroups per CU == waves per SIMD
+#endif
 #define FAST_CH 16                           // items per ticket of a wavefront
 template <int VOTE_U>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5)))
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LRM_VOTE_FAST_WAVES, LRM_VOTE_FAST_WAVES)))
 void vote_fast_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, const uint32_t *__restrict__ recq,
                       const uint32_t *__restrict__ gcnt, const uint32_t *__restrict__ ghits,
                       const uint8_t *__restrict__ decided, uint64_t n, int seed_len, int phase_lo, int phase_hi,
@@ -503,6 +658,7 @@ void vote_fast_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, const u
     const uint32_t np = (uint32_t) (phase_hi - phase_lo + 1);
     const uint64_t n_items = n * (uint64_t) np;
     constexpr int NU = (T1_LIMIT + 63) / 64;
+    constexpr int NL = (FAST_LIST + 63) / 64;
     for (;;) {
         unsigned long long base = 0;
         if (lane == 0) base = atomicAdd(ticket, (unsigned long long) FAST_CH);
@@ -528,7 +684,7 @@ void vote_fast_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, const u
                 }
                 continue;
             }
-            const VoteTable t = {L.key, L.cf, table_slots_for(cnt, load, T1_SLOTS)};
+            const FastTable t = {L.ident, L.count, table_slots_for(cnt, load, T1_SLOTS)};
             const uint64_t *irec = rec + id * cap_q;
             const uint32_t *iq = recq + id * cap_q;
             uint64_t e[NU], sv[NU];
@@ -539,9 +695,7 @@ void vote_fast_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, const u
                 e[u] = s < cnt ? irec[s] : 0ull;
                 qq[u] = s < cnt ? iq[s] : 0u;
             }
-            for (uint32_t s = lane; s < t.slots; s += 64) { t.key[s] = EMPTY_KEY; t.cf[s] = 0; }
-#pragma unroll
-            for (uint32_t s = 0; s < FAST_SK_WORDS / 64; ++s) L.sketch[s * 64 + lane] = 0;
+            for (uint32_t s = lane; s < t.slots; s += 64) { t.ident[s] = EMPTY_ID; t.count[s] = 0; }
             unsigned long long any_big = 0;
 #pragma unroll
             for (int u = 0; u < NU; ++u) {
@@ -549,15 +703,30 @@ void vote_fast_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, const u
                 sv[u] = rr == 1 ? sa_of_unique(ix, e[u]) : 0ull;       // unique seeds: gather at once (or nothing to gather)
                 any_big |= __ballot(rr > 1);
             }
+            if (any_big) {                                             // the sketch is cleared and scanned only for items with a repeat seed
+#pragma unroll
+                for (uint32_t s = 0; s < FAST_SK_WORDS / 64; ++s) L.sketch[s * 64 + lane] = 0;
+            }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
-            // A: the unique seeds' hits make the table
+            // A: the unique seeds' hits make the table; every lane keeps its hits (slot, low key bits; the order key is qq << tbits)
+            uint64_t hr[NU + NL];
+            uint32_t hw[NU + NL];
+            bool wide = false;                                         // a key without a 32-bit bucket name
 #pragma unroll
-            for (int u = 0; u < NU; ++u)
-                if ((uint32_t) (e[u] >> 40) == 1) vote_admit(t, sv[u] - (uint64_t) (iter + qq[u] * P), qq[u] << tbits, 1u, 0u);
+            for (int u = 0; u < NU; ++u) {
+                hw[u] = FAST_NONE;
+                if ((uint32_t) (e[u] >> 40) == 1) {
+                    const uint64_t key = sv[u] - (uint64_t) (iter + qq[u] * P);
+                    wide |= key_wide(key);
+                    const uint32_t slot = fast_insert(t, (uint32_t) (key >> 4), bucket_hash(key >> 4));
+                    if (slot != FAST_NONE) hw[u] = hit_word(slot, key);
+                }
+            }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
             // B: the repeat seeds' hits, 64 survivors at a time
+            uint32_t n_list = 0;
             if (any_big) {
 #pragma unroll
                 for (int u = 0; u < NU; ++u) {
@@ -575,25 +744,48 @@ void vote_fast_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, const u
                     if (lane == 0) L.off[nb] = run;
                     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                     __builtin_amdgcn_wave_barrier();
-                    fast_hits<64, VOTE_U>(ix, t, Staged{L.off, L.srec, L.sq, nb, run, iter, P, tbits}, L.sketch, 2 * FAST_SK_WORDS - 1, lane);
+                    fast_hits<64, VOTE_U>(ix, t, Staged{L.off, L.srec, L.sq, nb, run, iter, P, tbits}, L.sketch, 2 * FAST_SK_WORDS - 1, lane,
+                                          L.list, (uint32_t) FAST_LIST, n_list, nullptr, wide);
                     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                     __builtin_amdgcn_wave_barrier();
                 }
             }
-            // C
-            const Top2 w = table_top2<64>(t, lane);
-            uint32_t m = 0;
+            // rank: the top two from the hits (the table is final)
+            bool lost = wide;                                          // ... or a hit without a slot: never (see fast_insert)
 #pragma unroll
-            for (uint32_t s = 0; s < FAST_SK_WORDS / 64; ++s) {
-                const uint32_t x = L.sketch[s * 64 + lane];
-                const uint32_t a = x & 0xffffu, b = x >> 16;
-                m = a > m ? a : m;
-                m = b > m ? b : m;
+            for (int u = 0; u < NU; ++u) {
+                const bool uniq = (uint32_t) (e[u] >> 40) == 1;
+                lost |= uniq && hw[u] == FAST_NONE;
+                hr[u] = uniq && hw[u] != FAST_NONE ? ((uint64_t) t.count[hw[u] >> 4] << 32) | (0xFFFFFFFFu - (qq[u] << tbits)) : 0ull;
             }
-            const uint32_t M = (uint32_t) wave_max_u64((uint64_t) m);
-            const bool settled = any_big == 0 || M < (uint32_t) (w.k2 >> 32);
+#pragma unroll
+            for (int l = 0; l < NL; ++l) {
+                const uint32_t i = (uint32_t) l * 64 + lane;
+                hr[NU + l] = 0; hw[NU + l] = FAST_NONE;
+                if (i < n_list && i < (uint32_t) FAST_LIST) {
+                    const uint64_t x = L.list[i];
+                    hw[NU + l] = (uint32_t) x;
+                    hr[NU + l] = ((uint64_t) t.count[(uint32_t) x >> 4] << 32) | (x >> 32);
+                }
+            }
+            const RankTop a = wave_top_rank(lane_top_rank(hr, hw, FAST_NONE));
+            const RankTop b = wave_top_rank(lane_top_rank(hr, hw, a.r ? a.s : FAST_NONE));
+            const uint32_t lowm = wave_or_u32(lane_low4_mask(hr, hw, a, b));
+            // C
+            bool settled = n_list <= (uint32_t) FAST_LIST && __ballot(lost) == 0;
+            if (any_big) {
+                uint32_t m = 0;
+#pragma unroll
+                for (uint32_t s = 0; s < FAST_SK_WORDS / 64; ++s) {
+                    const uint32_t x = L.sketch[s * 64 + lane];
+                    const uint32_t lo = x & 0xffffu, hi = x >> 16;
+                    m = lo > m ? lo : m;
+                    m = hi > m ? hi : m;
+                }
+                settled = settled && wave_max_u32(m) < (uint32_t) (b.r >> 32);
+            }
             if (lane == 0) {
-                if (settled) write_phase(&phase_res[id], phase_of(t, w.k1, w.s1, w.k2, w.s2));
+                if (settled) write_phase(&phase_res[id], PhaseTop{fast_entry(t, a, lowm >> 16), fast_entry(t, b, lowm & 0xffffu)});
                 else redo[atomicAdd(redo_n, 1ull)] = item;
             }
             __builtin_amdgcn_wave_barrier();
@@ -604,17 +796,23 @@ void vote_fast_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, const u
 // The same for items with up to FB_LIMIT survivors (reads of 100 kbp: ~1200 per item), one WORKGROUP per item: a
 // 2048-slot table for the unique seeds' buckets, a 4096-counter sketch, repeat seeds staged 256 survivors at a time.
 // One pass whatever the hit count (the exact kernel takes ceil(hits / 768) passes over its 1024-slot table: five on
-// such reads).  Works through the list the wavefront kernel leaves (`big`).
+// such reads).  Works through the list the wavefront kernel leaves (`big`).  A thread keeps up to FB_LIMIT / 256 hits.
 #define FB_SLOTS 2048
 #define FB_SK_WORDS 2048
 struct FastBlockLds {
-    uint64_t key[FB_SLOTS];
-    uint64_t cf[FB_SLOTS];
+    uint32_t ident[FB_SLOTS];
+    uint32_t count[FB_SLOTS];
     uint64_t srec[T3_CHUNK];
+    uint64_t list[FB_LIST];
     uint32_t off[T3_CHUNK + 4];
     uint32_t sq[T3_CHUNK];
     uint32_t sketch[FB_SK_WORDS];
 };
+__device__ __forceinline__ RankTop block_top_rank(const RankTop *s_rk) {
+    RankTop r = {0, 0};
+    for (int x = 0; x < 4; ++x) if (s_rk[x].r > r.r) r = s_rk[x];
+    return r;
+}
 template <int VOTE_U>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3)))
 void vote_fast_block_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, const uint32_t *__restrict__ recq,
@@ -624,15 +822,17 @@ void vote_fast_block_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, c
                             const uint64_t *__restrict__ big, const unsigned long long *__restrict__ big_n,
                             uint64_t *__restrict__ redo, unsigned long long *redo_n) {
     __shared__ FastBlockLds L;
-    __shared__ uint32_t s_wsum[8], s_m[4];
-    __shared__ Top2 s_top[4];
+    __shared__ uint32_t s_wsum[8], s_m[4], s_or[4], s_list_n;
+    __shared__ RankTop s_rk[2][4];
     __shared__ unsigned long long s_at;
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     const uint32_t P = (uint32_t) seed_len + 1;
     const uint32_t np = (uint32_t) (phase_hi - phase_lo + 1);
     const uint64_t n_big = (uint64_t) *big_n;
+    constexpr int NU = FB_LIMIT / 256;
+    constexpr int NL = FB_LIST / 256;
     for (;;) {
-        if (tid == 0) s_at = atomicAdd(ticket, 1ull);
+        if (tid == 0) { s_at = atomicAdd(ticket, 1ull); s_list_n = 0; }
         __syncthreads();
         const uint64_t at = s_at;
         if (at >= n_big) break;
@@ -642,56 +842,91 @@ void vote_fast_block_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, c
         const uint32_t iter = ii.iter, cnt = gcnt[id];
         const uint64_t *irec = rec + id * cap_q;
         const uint32_t *iq = recq + id * cap_q;
-        const VoteTable t = {L.key, L.cf, table_slots_for(cnt, load, FB_SLOTS)};
-        for (uint32_t s = tid; s < t.slots; s += 256) { t.key[s] = EMPTY_KEY; t.cf[s] = 0; }
-        for (uint32_t s = tid; s < FB_SK_WORDS; s += 256) L.sketch[s] = 0;
+        const FastTable t = {L.ident, L.count, table_slots_for(cnt, load, FB_SLOTS)};
+        for (uint32_t s = tid; s < t.slots; s += 256) { t.ident[s] = EMPTY_ID; t.count[s] = 0; }
         __syncthreads();
-        // A: the unique seeds' hits make the table
+        // A: the unique seeds' hits make the table; every thread keeps its hits
         bool ok = true;
         uint32_t any_big = 0;
-        for (uint32_t c0 = 0; c0 < cnt; c0 += 256) {
-            const uint64_t e0 = c0 + tid < cnt ? irec[c0 + tid] : 0ull;
+        uint64_t hr[NU + NL];
+        uint32_t hw[NU + NL], ho[NU];
+#pragma unroll
+        for (int k = 0; k < NU; ++k) {
+            const uint32_t s = (uint32_t) k * 256 + tid;
+            hw[k] = FAST_NONE; ho[k] = 0;
+            const uint64_t e0 = s < cnt ? irec[s] : 0ull;
             const uint32_t r0 = (uint32_t) (e0 >> 40);
             any_big |= r0 > 1 ? 1u : 0u;
             if (r0 == 1) {
-                const uint32_t q0 = iq[c0 + tid];
-                const uint64_t v0 = sa_of_unique(ix, e0);
-                ok &= vote_admit(t, v0 - (uint64_t) (iter + q0 * P), q0 << tbits, 1u, 0u);
+                const uint32_t q0 = iq[s];
+                const uint64_t key = sa_of_unique(ix, e0) - (uint64_t) (iter + q0 * P);
+                const uint32_t slot = fast_insert(t, (uint32_t) (key >> 4), bucket_hash(key >> 4));
+                ok &= slot != FAST_NONE && !key_wide(key);
+                if (slot != FAST_NONE) { hw[k] = hit_word(slot, key); ho[k] = 0xFFFFFFFFu - (q0 << tbits); }
             }
         }
         const bool block_big = __syncthreads_or((int) any_big) != 0;
-        // B: the repeat seeds' hits, 256 survivors at a time
+        // B: the repeat seeds' hits, 256 survivors at a time (the sketch is cleared and scanned only for items with a repeat seed)
         if (block_big) {
+            for (uint32_t s = tid; s < FB_SK_WORDS; s += 256) L.sketch[s] = 0;       // (stage_repeats_block ends with a barrier)
+            uint32_t unused = 0;
+            bool wide = false;
             for (uint32_t c0 = 0; c0 < cnt; c0 += 256) {
                 const uint64_t e0 = c0 + tid < cnt ? irec[c0 + tid] : 0ull;
                 const uint32_t q0 = c0 + tid < cnt ? iq[c0 + tid] : 0u;
                 const uint32_t r0 = (uint32_t) (e0 >> 40);
                 const BlockStage st = stage_repeats_block<false>(L.off, L.srec, L.sq, s_wsum, e0, q0, r0);
-                if (st.nbig) fast_hits<256, VOTE_U>(ix, t, Staged{L.off, L.srec, L.sq, st.nbig, st.total, iter, P, tbits}, L.sketch, 2 * FB_SK_WORDS - 1, tid);
+                if (st.nbig) fast_hits<256, VOTE_U>(ix, t, Staged{L.off, L.srec, L.sq, st.nbig, st.total, iter, P, tbits}, L.sketch, 2 * FB_SK_WORDS - 1, tid,
+                                                    L.list, (uint32_t) FB_LIST, unused, &s_list_n, wide);
                 __syncthreads();                                   // the staging is rewritten by the next chunk
             }
+            ok &= !wide;
         }
+        // rank: the top two from the hits (the table is final: a barrier lies behind A and behind every chunk of B)
+        const uint32_t n_list = s_list_n;
+#pragma unroll
+        for (int k = 0; k < NU; ++k)
+            hr[k] = hw[k] != FAST_NONE ? ((uint64_t) t.count[hw[k] >> 4] << 32) | ho[k] : 0ull;
+#pragma unroll
+        for (int l = 0; l < NL; ++l) {
+            const uint32_t i = (uint32_t) l * 256 + tid;
+            hr[NU + l] = 0; hw[NU + l] = FAST_NONE;
+            if (i < n_list && i < (uint32_t) FB_LIST) {
+                const uint64_t x = L.list[i];
+                hw[NU + l] = (uint32_t) x;
+                hr[NU + l] = ((uint64_t) t.count[(uint32_t) x >> 4] << 32) | (x >> 32);
+            }
+        }
+        const RankTop wa = wave_top_rank(lane_top_rank(hr, hw, FAST_NONE));
+        if (lane == 0) s_rk[0][wave] = wa;
+        __syncthreads();
+        const RankTop a = block_top_rank(s_rk[0]);
+        const RankTop wb = wave_top_rank(lane_top_rank(hr, hw, a.r ? a.s : FAST_NONE));
+        if (lane == 0) s_rk[1][wave] = wb;
+        __syncthreads();
+        const RankTop b = block_top_rank(s_rk[1]);
+        const uint32_t lowm = wave_or_u32(lane_low4_mask(hr, hw, a, b));
         // C
-        const Top2 w = table_top2<256>(t, tid);
         uint32_t m = 0;
-        for (uint32_t s = tid; s < FB_SK_WORDS; s += 256) {
-            const uint32_t x = L.sketch[s];
-            const uint32_t a = x & 0xffffu, b = x >> 16;
-            m = a > m ? a : m;
-            m = b > m ? b : m;
+        if (block_big) {
+            for (uint32_t s = tid; s < FB_SK_WORDS; s += 256) {
+                const uint32_t x = L.sketch[s];
+                const uint32_t lo = x & 0xffffu, hi = x >> 16;
+                m = lo > m ? lo : m;
+                m = hi > m ? hi : m;
+            }
+            m = wave_max_u32(m);
         }
-        m = (uint32_t) wave_max_u64((uint64_t) m);
-        if (lane == 0) { s_top[wave] = w; s_m[wave] = m; }
+        if (lane == 0) { s_or[wave] = lowm; s_m[wave] = m; }
         const bool all_ok = __syncthreads_and((int) ok) != 0;
         if (tid == 0) {
-            const Top2 c = block_top2(s_top);
-            uint32_t M = 0;
-            for (int x = 0; x < 4; ++x) M = s_m[x] > M ? s_m[x] : M;
-            const bool settled = all_ok && (!block_big || M < (uint32_t) (c.k2 >> 32));
-            if (settled) write_phase(&phase_res[id], phase_of(t, c.k1, c.s1, c.k2, c.s2));
+            uint32_t M = 0, lm = 0;
+            for (int x = 0; x < 4; ++x) { M = s_m[x] > M ? s_m[x] : M; lm |= s_or[x]; }
+            const bool settled = all_ok && n_list <= (uint32_t) FB_LIST && (!block_big || M < (uint32_t) (b.r >> 32));
+            if (settled) write_phase(&phase_res[id], PhaseTop{fast_entry(t, a, lm >> 16), fast_entry(t, b, lm & 0xffffu)});
             else redo[atomicAdd(redo_n, 1ull)] = item;
         }
-        __syncthreads();                                           // s_at, the table and s_top are rewritten by the next item
+        __syncthreads();                                           // s_at, s_list_n, the table and s_rk are rewritten by the next item
     }
 }
 
@@ -786,7 +1021,9 @@ static void launch_vote_u(lrm_index *idx, lrm_workspace *ws, const LrmVoteLaunch
     const uint64_t items = v.n * (uint64_t) (v.phase_hi - v.phase_lo + 1);
     const uint64_t *list = nullptr;
     const unsigned long long *list_n = nullptr;
-    if (v.mt->vote_fast) {
+    // the fast kernels name a bucket by 32 bits of it (FastTable): exact on a text of fewer than 2^35 rows, and only taken there
+    const bool ident32 = idx->view.length < (1ull << 35);
+    if (v.mt->vote_fast && ident32) {
         uint64_t fblocks = (items + 4 * FAST_CH - 1) / (4 * FAST_CH);
         if (fblocks > LRM_VOTE_FAST_GRID) fblocks = LRM_VOTE_FAST_GRID;
         hipLaunchKernelGGL(vote_fast_kernel<U>, dim3((uint32_t) fblocks), dim3(256), 0, stream, idx->view, ws->d_rec, ws->d_recq, ws->d_cnt,

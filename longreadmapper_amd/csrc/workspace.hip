@@ -138,6 +138,15 @@ extern "C" int lrm_workspace_stats(lrm_workspace *ws, lrm_stats *out, void *stre
     return lrm_ws_take_error(ws);
 }
 
+extern "C" int lrm_debug_vote_results(lrm_workspace *ws, uint64_t n, uint64_t *out, void *stream) {
+    if (!ws || !out || !ws->d_phase) { lrm_set_error("null argument"); return -1; }
+    if (n > ws->n_last) { lrm_set_error("the last seed call on this workspace had %llu reads", (unsigned long long) ws->n_last); return -1; }
+    HIPCHK(hipSetDevice(ws->device));
+    HIPCHK(hipMemcpyAsync(out, ws->d_phase, n * (uint64_t) ws->P * sizeof(LrmPhaseRes), hipMemcpyDeviceToHost, (hipStream_t) stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t) stream));
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------
 // per-kernel timing
 // ------------------------------------------------------------------------------------------

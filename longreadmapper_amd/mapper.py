@@ -511,6 +511,13 @@ class DeviceMapper:
                     seeds_evaluated=int(st.seeds_evaluated), seed_table_lookups=int(st.seed_table_lookups),
                     seed_rank_requests=int(st.seed_rank_requests), vote_redo_items=int(st.vote_redo_items))
 
+    def debug_vote_results(self, n):
+        """lrm_debug_vote_results: (n, seed_len + 1, 6) uint64 -- key1, val1, bucket1, key2, val2, bucket2 of every (read, phase)
+        of the last seed() call as the vote kernels left them; only the phases that call evaluated are meaningful."""
+        out = np.zeros((n, self.seed_len + 1, 6), dtype=np.uint64)
+        check(lib.lrm_debug_vote_results(self.ws, n, out.ctypes.data, self._stream()), "lrm_debug_vote_results")
+        return out
+
     def set_counting(self, enable=True):
         """The next seed calls run the counting build of the seed kernel (stats(): requests of the device layout)."""
         check(lib.lrm_workspace_set_counting(self.ws, int(enable)), "lrm_workspace_set_counting")
