@@ -356,6 +356,42 @@ int lrm_map_batch_submit_mapq(lrm_index *idx, char *reads_buf, uint64_t stride, 
                               uint8_t *store_mem, uint64_t store_stride, int *score_out, lrm_seq_meta *meta_out,
                               int *meta_r_out, const lrm_map_options *opt, lrm_mapq *mapq_out, lrm_ticket **ticket_out);
 
+/* ALIGNMENT SUMMARY (docs/GACT_SPEC.md, "Alignment summary and PAF").  With lrm_map_options.cigar_text only the run-length
+ * text of an alignment crosses the link, and it prints '=' and 'X' both as M: what the alignment consists of is counted on
+ * the device, over the op bytes while they are still in HBM, into one fixed-size record per read.  A read without an
+ * alignment (n_cigar_op <= 0, meta_r == 0 or score == -1: the reads whose CIGAR prints as "*"): all zeros.  A row made only
+ * of 'S': clip_left = n_cigar_op, clip_right = 0.  A byte outside "=XIDS" is counted nowhere (it still ends a run, and it
+ * is a column that is not 'S').  An 'I' run right behind a 'D' run, or the reverse, is a run of its own; the classic mode's
+ * 'I' tail ("target exhausted") is insertion columns and one run.  From a record:
+ *   NM            = n_x + n_ins + n_del        (the score of the spec: the edit distance of the ops)
+ *   target span   = n_eq + n_x + n_del
+ *   block length  = n_eq + n_x + n_ins + n_del
+ *   aligned query = [clip_left, len - clip_right) in the orientation of the ops
+ * Like the mapping quality it is asked for per CALL, not through lrm_map_options. */
+typedef struct lrm_aln_summary {          /* 32 bytes, all columns counted over the read's n_cigar_op op bytes */
+    uint32_t n_eq, n_x, n_ins, n_del;     /* '=' , 'X', 'I', 'D' columns */
+    uint32_t ins_runs, del_runs;          /* maximal runs of 'I' / of 'D' columns (gap opens) */
+    uint32_t clip_left, clip_right;       /* 'S' columns before the first / after the last column that is not 'S' */
+} lrm_aln_summary;
+/* The rule on the host, for callers that hold op bytes: pure arithmetic, usable without a GPU.  n_ops <= 0: zeros. */
+void lrm_aln_summary_host(const uint8_t *ops, int n_ops, lrm_aln_summary *out);
+
+/* Per-call extras of the host-buffer path: output arrays of n entries each that a batch fills on top of the arguments of
+ * lrm_map_batch_submit (NULL: that output is not computed, nothing runs or is allocated for it).  struct_size:
+ * sizeof(lrm_batch_extras) of the caller's header (0: all of it). */
+typedef struct lrm_batch_extras {
+    uint32_t struct_size, reserved;
+    lrm_mapq *mapq_out;                   /* the mapping-quality records (lrm_map_batch_submit_mapq) */
+    lrm_aln_summary *summary_out;         /* the alignment summary records: the stage runs per extension group, behind the group's
+                                             extension (clip and stitch included), and the records come down with the small arrays */
+} lrm_batch_extras;
+/* lrm_map_batch_submit plus the extras (ex == NULL or both arrays NULL: lrm_map_batch_submit).  Filled when the wait
+ * returns; group handles write every share in place; every other output is the same bytes with the extras or without. */
+int lrm_map_batch_submit_ex(lrm_index *idx, char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
+                            lrm_params p, lrm_gact_params gp, lrm_entry *best_out, lrm_cigar *cig_out,
+                            uint8_t *store_mem, uint64_t store_stride, int *score_out, lrm_seq_meta *meta_out,
+                            int *meta_r_out, const lrm_map_options *opt, const lrm_batch_extras *ex, lrm_ticket **ticket_out);
+
 /* ---------------------------------------------------------------------------
  * Batch entry points with DEVICE buffers (inputs/outputs resident in HBM;
  * asynchronous on `stream`, a hipStream_t passed as void*, may be NULL).
@@ -428,6 +464,13 @@ int lrm_extend_batch_clipped_dev(lrm_index *idx, lrm_workspace *ws, char *d_read
                                  uint64_t store_stride, int32_t *d_n_ops, int32_t *d_score,
                                  lrm_seq_meta *d_meta, int32_t *d_meta_r, lrm_anchor *d_anchor, uint32_t min_len,
                                  uint32_t clip_penalty, uint32_t clip_end_bonus, lrm_clip *d_clip, void *stream);
+
+/* The ALIGNMENT SUMMARY records (lrm_aln_summary above) of a batch whose op bytes sit in device memory: call it behind any
+ * of the three extension calls on the same stream, with that call's d_store, store_stride, d_n_ops, d_score, d_meta_r.
+ * d_out: n records in device memory, 16-byte aligned.  One streaming kernel, one byte read per column; no workspace. */
+int lrm_aln_summary_dev(lrm_index *idx, const uint8_t *d_store, uint64_t store_stride,
+                        const int32_t *d_n_ops, const int32_t *d_score, const int32_t *d_meta_r,
+                        uint64_t n, lrm_aln_summary *d_out, void *stream);
 
 /* SPLIT READS (lrm_map_options.split; docs/GACT_SPEC.md, "Split reads"): the soft-clipped ends of a batch that went through
  * the anchored extension with end clipping, mapped as reads of their own.  For read i with n = lens[i] bases, R the read as

@@ -8,6 +8,7 @@
  *   SAM record printing               alnmain.c:485-527                  -> lrm_sam_format (_split, _mapq)
  *   parse_cigar (gact submodule, source absent; PARITY UNPINNED)         -> lrm_parse_cigar
  *   single_end                        alnmain.c:277-551                  -> lrm_accaln
+ *   (no counterpart: the reference prints SAM only)                      -> lrm_paf_format, lrm_accaln_paf
  */
 #ifndef LRM_IO_HOST_H
 #define LRM_IO_HOST_H
@@ -79,6 +80,20 @@ char *lrm_sam_format_mapq(const lrm_read_batch *reads, const lrm_mta_entry *mta,
                           const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t n, int cigar_is_text,
                           int revcomp_here, const lrm_split_out *split, const lrm_mapq *mq, uint64_t *len_out);
 
+/* PAF (docs/GACT_SPEC.md, "Alignment summary and PAF"): one line per MAPPED read -- an unmapped one (meta_r == 0 or score == -1)
+ * prints nothing --, every number of it taken from the read's alignment summary record (sum: required, what
+ * lrm_map_batch_submit_ex or lrm_aln_summary_dev returned for this batch).  Tab-separated, with cl / cr the record's clips:
+ *   qname  qlen  qstart  qend  strand  tname  tlen  tstart  tend  matches  block  mapq  tags
+ * qstart, qend: on the read as sequenced -- cl, qlen - cr on the forward strand; cr, qlen - cl on the reverse strand
+ * (meta.strand == 1).  tstart = meta.off, tend = meta.off + target span, matches = n_eq, block = the block length, mapq =
+ * mq[i].mapq (255 without mq).  Tags: NM:i  ED:i:<score>  tp:A:P  de:f:<%.4f of (n_x + ins_runs + del_runs) / (n_eq + n_x +
+ * ins_runs + del_runs), 0.0000 for a zero denominator>  cg:Z:<the run-length CIGAR as lrm_parse_cigar prints it>, and with
+ * mq v1:i:<n1>  v2:i:<n2>.  cigar_is_text: cig[i].cigar is run-length text (lrm_map_options.cigar_text), not op bytes.
+ * Returns malloc'd text (free with lrm_free); NULL on a bad argument. */
+char *lrm_paf_format(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig,
+                     const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t n, int cigar_is_text,
+                     const lrm_aln_summary *sum, const lrm_mapq *mq, uint64_t *len_out);
+
 /* `accaln genome reads [batch seed_len thres]` on the GPU path: loads the index files next to
  * `genome`, maps `reads_path` batch by batch, writes SAM to `sam_path`.  total/valid are the
  * reference's "Sensitivity: valid/total" counters (alnmain.c:541). */
@@ -97,6 +112,12 @@ int lrm_accaln_opt(const char *genome, const char *reads_path, const char *sam_p
 int lrm_accaln_mapq(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
                     lrm_gact_params gp, int device, long rg_id, uint64_t *total, uint64_t *valid,
                     const lrm_map_options *opt, int mapq);
+/* The flow of lrm_accaln_mapq with PAF output: every batch goes through lrm_map_batch_submit_ex with summary_out (and
+ * mapq_out when mapq != 0) and is printed by lrm_paf_format; the file has no header.  total / valid count as in the SAM flow.
+ * opt->split != 0 is refused (-1): PAF lines for split segments need summary records of the segment batch, which the
+ * fixed-size lrm_split_out cannot carry. */
+int lrm_accaln_paf(const char *genome, const char *reads_path, const char *paf_path, lrm_params p, lrm_gact_params gp,
+                   int device, uint64_t *total, uint64_t *valid, const lrm_map_options *opt, int mapq);
 
 #ifdef __cplusplus
 }

@@ -125,6 +125,15 @@ class Mapq(C.Structure):               # lrm_mapq
                 ("flags", C.c_uint8), ("pad", C.c_uint8)]
 
 
+class AlnSummary(C.Structure):         # lrm_aln_summary
+    _fields_ = [("n_eq", C.c_uint32), ("n_x", C.c_uint32), ("n_ins", C.c_uint32), ("n_del", C.c_uint32),
+                ("ins_runs", C.c_uint32), ("del_runs", C.c_uint32), ("clip_left", C.c_uint32), ("clip_right", C.c_uint32)]
+
+
+class BatchExtras(C.Structure):        # lrm_batch_extras (host pointers)
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("mapq_out", C.c_void_p), ("summary_out", C.c_void_p)]
+
+
 MAPQ_SLOTS, MAPQ_OVERFLOW = 4096, 1    # LRM_MAPQ_SLOTS, LRM_MAPQ_OVERFLOW (lrm_mapq.flags)
 SEG_RIGHT, SEG_ALIGNED = 1, 2          # lrm_segment.flags
 SPLIT_MIN_DEFAULT = 200                # LRM_SPLIT_MIN_DEFAULT
@@ -152,7 +161,7 @@ class HostIndex(C.Structure):          # lrm_index_host.h
 
 assert C.sizeof(Ui40) == 8 and C.sizeof(Entry) == 24 and C.sizeof(SeqMeta) == 24
 assert C.sizeof(MapOptions) == 76 and C.sizeof(Anchor) == 32 and C.sizeof(Clip) == 8
-assert C.sizeof(Mapq) == 16
+assert C.sizeof(Mapq) == 16 and C.sizeof(AlnSummary) == 32 and C.sizeof(BatchExtras) == 24
 assert MapOptions.split.offset == 68 and C.sizeof(Segment) == 16 and C.sizeof(SplitDev) == 112 and C.sizeof(SplitOut) == 120
 
 # every symbol include/*.h declares: (restype, argtypes)
@@ -192,7 +201,13 @@ SYMBOLS = {
     "lrm_map_batch_submit_mapq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, Params, GactParams,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.POINTER(MapOptions), C.c_void_p, C.POINTER(C.c_void_p)]),
+    "lrm_map_batch_submit_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, Params, GactParams,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(MapOptions), C.POINTER(BatchExtras), C.POINTER(C.c_void_p)]),
     "lrm_map_batch_wait": (C.c_int, [C.c_void_p]),
+    "lrm_aln_summary_host": (None, [C.c_void_p, C.c_int, C.POINTER(AlnSummary)]),
+    "lrm_aln_summary_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                      C.c_void_p, C.c_void_p]),
     "lrm_debug_reload_env": (C.c_int, [C.c_void_p]),
     "lrm_debug_set_vote_limits": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "lrm_debug_set_mapq_slots": (C.c_int, [C.c_void_p, C.c_uint32]),
@@ -290,6 +305,10 @@ SYMBOLS = {
                                           C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(SplitOut), u64p]),
     "lrm_sam_format_mapq": (C.c_void_p, [C.POINTER(ReadBatch), C.POINTER(MtaEntry), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(SplitOut), C.c_void_p, u64p]),
+    "lrm_paf_format": (C.c_void_p, [C.POINTER(ReadBatch), C.POINTER(MtaEntry), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, u64p]),
+    "lrm_accaln_paf": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, Params, GactParams, C.c_int, u64p, u64p,
+                                 C.POINTER(MapOptions), C.c_int]),
     "lrm_accaln": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, Params, GactParams, C.c_int, C.c_long, u64p, u64p]),
     "lrm_accaln_opt": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, Params, GactParams, C.c_int, C.c_long, u64p, u64p,
                                  C.POINTER(MapOptions)]),

@@ -1,4 +1,4 @@
-// accaln_flow.cpp -- `accaln genome reads` on the GPU path (lrm_accaln, lrm_accaln_opt, lrm_accaln_mapq,
+// accaln_flow.cpp -- `accaln genome reads` on the GPU path (lrm_accaln, lrm_accaln_opt, lrm_accaln_mapq, lrm_accaln_paf,
 // include/lrm_io_host.h): single_end() (alnmain.c:277-551) as a pipeline of threads around the asynchronous batch calls.
 // Host-side C++; the kernels are reached only through the C-ABI.
 //
@@ -29,6 +29,7 @@
 #include <vector>
 #include "../../include/lrm_index_host.h"
 #include "sam_text.h"
+#include "paf_text.h"
 #include "lrm_internal.h"
 #include "extend_stage.h"
 
@@ -108,6 +109,7 @@ struct BatchSet {
     lrm_ticket *ticket = nullptr;
     SplitBufs sp;                                // split reads: the second pass over this batch's clipped ends (lrm_split_batch)
     std::vector<lrm_mapq> mq;                    // lrm_accaln_mapq: the records of the batch
+    std::vector<lrm_aln_summary> sum;            // lrm_accaln_paf: the alignment summary records of the batch
     BatchSet() { memset(&b, 0, sizeof(b)); }
     ~BatchSet() { lrm_host_free(reads_pin); lrm_host_free(store_pin); free(store_pg); }
 };
@@ -136,6 +138,7 @@ struct AccalnRun {
     const lrm_gact_params gp;
     int device;
     const bool mapq;                                     // the mapping-quality records come back with every batch and are printed
+    const bool paf;                                      // PAF instead of SAM: the summary records come back too, no header
     const bool verbose = getenv("LRM_HOST_VERBOSE") != nullptr;            // stage times on stderr (tuning aid)
     lrm_map_options mopt;
     bool split = false;                                  // after a batch's wait its clipped ends go through lrm_split_batch
@@ -168,8 +171,8 @@ struct AccalnRun {
     double t_write = 0;                                  // flusher
     uint64_t out_off = 0;                                // flusher (main sets it behind the header before the threads start)
 
-    AccalnRun(lrm_params p_, lrm_gact_params gp_, int device_, bool mapq_)
-        : p(p_), gp(gp_), device(device_), mapq(mapq_), bs(p_.batch_size ? p_.batch_size : 1000) {}
+    AccalnRun(lrm_params p_, lrm_gact_params gp_, int device_, bool mapq_, bool paf_ = false)
+        : p(p_), gp(gp_), device(device_), mapq(mapq_), paf(paf_), bs(p_.batch_size ? p_.batch_size : 1000) {}
 
     // op bytes per read: alnmain.c:316-320, a multiple of 16; the anchored mode's targets are an eighth longer than the reads
     uint64_t store_stride_of(uint64_t max_len) const {
@@ -189,6 +192,7 @@ struct AccalnRun {
         lrm_options_take_fields(&u, user, offsetof(lrm_map_options, anchored), offsetof(lrm_map_options, clip));
         lrm_options_take_fields(&u, user, offsetof(lrm_map_options, clip), offsetof(lrm_map_options, split));
         lrm_options_take_fields(&u, user, offsetof(lrm_map_options, split), offsetof(lrm_map_options, split_min_len) + sizeof(uint32_t));
+        if (u.split && paf) { lrm_set_error("PAF output of split reads is not there yet: the segments have no alignment summary records (lrm_split_out is fixed-size)"); return -1; }
         if (u.split && !u.clip) { lrm_set_error("lrm_map_options.split needs lrm_map_options.clip"); return -1; }
         lrm_map_options_init(&mopt);
         mopt.cigar_text = 1;                        // parse_cigar (alnmain.c:497-498) runs on the device: the SAM CIGAR text comes back
@@ -219,11 +223,13 @@ struct AccalnRun {
         if (rc) return rc;
         out_fd = open(sam_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
         if (out_fd < 0) { lrm_set_error("cannot create: %s", sam_path); return -1; }
-        uint64_t hl = 0;
-        char *h = lrm_sam_header(hi.mta, hi.mta_len, rg_id, &hl);
-        if (pwrite(out_fd, h, hl, 0) != (ssize_t) hl) { lrm_set_error("cannot write: %s", sam_path); rc = -1; }
-        out_off = hl;
-        free(h);
+        if (!paf) {                                                   // (PAF has no header)
+            uint64_t hl = 0;
+            char *h = lrm_sam_header(hi.mta, hi.mta_len, rg_id, &hl);
+            if (pwrite(out_fd, h, hl, 0) != (ssize_t) hl) { lrm_set_error("cannot write: %s", sam_path); rc = -1; }
+            out_off = hl;
+            free(h);
+        }
         return rc ? rc : lrm_reader_open(&rd, reads_path);
     }
 
@@ -281,9 +287,15 @@ struct AccalnRun {
             if (!err.get() && free_texts.pop(tb)) {
                 const uint64_t n = s->b.n;
                 const double t0 = now();
-                const SamBatch sb = {&s->b, hi.mta, hi.mta_len, s->cig.data(), s->score.data(), s->meta.data(), s->meta_r.data(), n,
-                                     /* cigar_is_text */ true, /* revcomp_here */ true, split ? &s->sp.out : nullptr, mapq ? s->mq.data() : nullptr};
-                sam_format_parts(sb, io_threads, tb->parts);
+                if (paf) {
+                    const PafBatch pb = {&s->b, hi.mta, hi.mta_len, s->cig.data(), s->score.data(), s->meta.data(), s->meta_r.data(), n,
+                                         /* cigar_is_text */ true, s->sum.data(), mapq ? s->mq.data() : nullptr};
+                    paf_format_parts(pb, io_threads, tb->parts);
+                } else {
+                    const SamBatch sb = {&s->b, hi.mta, hi.mta_len, s->cig.data(), s->score.data(), s->meta.data(), s->meta_r.data(), n,
+                                         /* cigar_is_text */ true, /* revcomp_here */ true, split ? &s->sp.out : nullptr, mapq ? s->mq.data() : nullptr};
+                    sam_format_parts(sb, io_threads, tb->parts);
+                }
                 t_fmt += now() - t0;
                 if (verbose) fprintf(stderr, "[lrm accaln] %.3f formatted %llu reads in %.3f s\n", now() - t_upload, (unsigned long long) n, now() - t0);
                 total += n;
@@ -357,6 +369,7 @@ struct AccalnRun {
         const size_t n = (size_t) s->b.n;
         s->best.resize(n); s->cig.resize(n); s->score.resize(n); s->meta_r.resize(n); s->meta.resize(n);
         if (mapq) s->mq.resize(n);
+        if (paf) s->sum.resize(n);
         s->sstride = store_stride_of(s->b.max_len);
         if (s->pin_ready.load(std::memory_order_acquire) && n * s->sstride <= s->store_cap) { s->store = s->store_pin; return true; }
         if (n * s->sstride > s->store_pg_cap) {
@@ -376,9 +389,10 @@ struct AccalnRun {
             if (err.get()) { recycle(s); continue; }                          // drain what the loader already parsed
             if (!fit_results(s)) { err.set(-1); recycle(s); continue; }
             const double t0 = now();
-            const int src = lrm_map_batch_submit_mapq(gpu, s->b.seqs, s->b.stride, s->b.lens, s->b.n, p, gp, s->best.data(), s->cig.data(),
-                                                      s->store, s->sstride, s->score.data(), s->meta.data(), s->meta_r.data(), &mopt,
-                                                      mapq ? s->mq.data() : nullptr, &s->ticket);
+            const lrm_batch_extras ex = {(uint32_t) sizeof(lrm_batch_extras), 0, mapq ? s->mq.data() : nullptr, paf ? s->sum.data() : nullptr};
+            const int src = lrm_map_batch_submit_ex(gpu, s->b.seqs, s->b.stride, s->b.lens, s->b.n, p, gp, s->best.data(), s->cig.data(),
+                                                    s->store, s->sstride, s->score.data(), s->meta.data(), s->meta_r.data(), &mopt,
+                                                    &ex, &s->ticket);
             t_map += now() - t0;
             if (verbose) fprintf(stderr, "[lrm accaln] %.3f submitted %llu reads (%s store) in %.3f s\n", now() - t_upload, (unsigned long long) s->b.n, s->store == s->store_pin ? "pinned" : "pageable", now() - t0);
             if (!first_submitted) { { std::lock_guard<std::mutex> lk(dims_m); first_submitted = true; } dims_cv.notify_all(); }
@@ -427,19 +441,29 @@ struct AccalnRun {
 
 }  // namespace
 
-// mapq: the mapping-quality records come back with every batch, column 5 and v1:i / v2:i print them (lrm_sam_format_mapq)
-extern "C" int lrm_accaln_mapq(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
-                               lrm_gact_params gp, int device, long rg_id, uint64_t *total_out, uint64_t *valid_out,
-                               const lrm_map_options *user, int mapq) {
-    AccalnRun r(p, gp, device, mapq != 0);
+// one run of the flow: SAM (lrm_accaln*) or PAF (lrm_accaln_paf) into out_path
+static int accaln_run(const char *genome, const char *reads_path, const char *out_path, lrm_params p, lrm_gact_params gp, int device,
+                      long rg_id, uint64_t *total_out, uint64_t *valid_out, const lrm_map_options *user, bool mapq, bool paf) {
+    AccalnRun r(p, gp, device, mapq, paf);
     if (r.take_options(user)) return -1;
     if (lrm_host_index_read(genome, &r.hi)) return -1;
-    int rc = r.begin(reads_path, sam_path, rg_id);
+    int rc = r.begin(reads_path, out_path, rg_id);
     if (rc == 0) rc = r.run();
     r.end();
     if (total_out) *total_out = r.total;
     if (valid_out) *valid_out = r.valid;
     return rc;
+}
+// mapq: the mapping-quality records come back with every batch, column 5 and v1:i / v2:i print them (lrm_sam_format_mapq)
+extern "C" int lrm_accaln_mapq(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
+                               lrm_gact_params gp, int device, long rg_id, uint64_t *total_out, uint64_t *valid_out,
+                               const lrm_map_options *user, int mapq) {
+    return accaln_run(genome, reads_path, sam_path, p, gp, device, rg_id, total_out, valid_out, user, mapq != 0, false);
+}
+// PAF: the alignment summary records come back with every batch, lrm_paf_format's lines print them; no header
+extern "C" int lrm_accaln_paf(const char *genome, const char *reads_path, const char *paf_path, lrm_params p, lrm_gact_params gp,
+                              int device, uint64_t *total_out, uint64_t *valid_out, const lrm_map_options *user, int mapq) {
+    return accaln_run(genome, reads_path, paf_path, p, gp, device, 0, total_out, valid_out, user, mapq != 0, true);
 }
 extern "C" int lrm_accaln_opt(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
                               lrm_gact_params gp, int device, long rg_id, uint64_t *total_out, uint64_t *valid_out,

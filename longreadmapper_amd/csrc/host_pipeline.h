@@ -87,11 +87,12 @@ struct MapJob {
     lrm_cigar *cig; uint8_t *store_mem; uint64_t store_stride; int *score; lrm_seq_meta *meta; int *meta_r;
     lrm_anchor *anchor_out;           // anchored mode: the anchor records too (null: they stay in the workspace)
     lrm_mapq *mapq_out;               // mapping quality: the stage runs behind every seed sub-batch, the records come down with the small arrays (null: no stage)
+    lrm_aln_summary *summary_out;     // alignment summary: the stage runs behind every group's extension, the records come down likewise (null: no stage)
     MapJob slice(uint64_t o, uint64_t m) const {        // reads [o, o + m): every array of the caller moves on by o elements
         MapJob j = *this;
         j.n = m;
         auto adv = [o](auto *&ptr, uint64_t pitch = 1) { if (ptr) ptr += o * pitch; };
-        adv(j.reads, stride); adv(j.lens); adv(j.best_in); adv(j.best_out); adv(j.anchor_out); adv(j.mapq_out);
+        adv(j.reads, stride); adv(j.lens); adv(j.best_in); adv(j.best_out); adv(j.anchor_out); adv(j.mapq_out); adv(j.summary_out);
         adv(j.cig); adv(j.store_mem, store_stride); adv(j.score); adv(j.meta); adv(j.meta_r);
         return j;
     }
@@ -99,7 +100,7 @@ struct MapJob {
 
 // The per-read arrays of a slice on the device.  The first N_SMALL come down with every unit through the pinned staging of
 // the slot, in this order on the download stream; the others are uploaded (reads, lens) or leave as the dense image (store).
-enum { A_BEST, A_NOPS, A_SCORE, A_META, A_MR, A_TLEN, A_ANCHOR, A_MAPQ, N_SMALL, A_READS = N_SMALL, A_LENS, A_STORE, N_ARRAYS };
+enum { A_BEST, A_NOPS, A_SCORE, A_META, A_MR, A_TLEN, A_ANCHOR, A_MAPQ, A_SUMMARY, N_SMALL, A_READS = N_SMALL, A_LENS, A_STORE, N_ARRAYS };
 struct SliceArray {
     uint64_t elem;                    // bytes per read
     bool on_dev;                      // the slice needs the device mirror
@@ -108,7 +109,7 @@ struct SliceArray {
     uint64_t stage;                   // where the part starts in a unit's pinned staging, in bytes per read of the unit
 };
 static_assert(alignof(lrm_entry) <= 8 && alignof(lrm_seq_meta) <= 8 && alignof(lrm_anchor) <= 8 && alignof(lrm_mapq) <= 8 &&
-              sizeof(lrm_mapq) % 4 == 0, "SliceJob::plan_arrays places an array of 8-byte multiples at a multiple of 8, any other at a multiple of 4");
+              alignof(lrm_aln_summary) <= 8 && sizeof(lrm_mapq) % 4 == 0, "SliceJob::plan_arrays places an array of 8-byte multiples at a multiple of 8, any other at a multiple of 4");
 
 // device-side resources of one slice in flight
 struct Slot {
@@ -138,7 +139,7 @@ struct SliceJob {
     std::vector<size_t> ends, unit_of;
     uint64_t dstride = 0;
     bool seed_only = false;
-    bool want_anchor = false, want_mapq = false, text = false;     // the anchor records, the mapping-quality records, run-length CIGAR text
+    bool want_anchor = false, want_mapq = false, want_summary = false, text = false;     // the anchor, mapping-quality and summary records, run-length CIGAR text
     SliceArray arr[N_ARRAYS] = {};
     uint64_t stage_off = 0, stage_len = 0, stage_row = 0;           // staging of a unit's offset table (2 x u64) and lengths (2 x u32); bytes per read in all
     void plan_arrays();

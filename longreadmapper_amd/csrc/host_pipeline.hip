@@ -240,6 +240,7 @@ void SliceJob::plan_arrays() {
     const bool seed = (j.mode & DO_SEED) != 0, ext = (j.mode & DO_EXTEND) != 0;
     want_anchor = j.anchor_out && ext && mt.anchored;
     want_mapq = j.mapq_out && seed;
+    want_summary = j.summary_out && ext;
     text = mt.cigar_text != 0 && ext;
     //               bytes per read        on the device  downloaded   the caller's array
     arr[A_BEST]   = {sizeof(lrm_entry),    true,          seed,        j.best_out};
@@ -250,6 +251,7 @@ void SliceJob::plan_arrays() {
     arr[A_TLEN]   = {4,                    text,          text,        nullptr};          // sizes the text rows of the dense image
     arr[A_ANCHOR] = {sizeof(lrm_anchor),   want_anchor,   want_anchor, j.anchor_out};
     arr[A_MAPQ]   = {sizeof(lrm_mapq),     want_mapq,     want_mapq,   j.mapq_out};
+    arr[A_SUMMARY] = {sizeof(lrm_aln_summary), want_summary, want_summary, j.summary_out};
     arr[A_READS]  = {j.stride,             true,          false,       nullptr};          // uploaded per sub-batch
     arr[A_LENS]   = {4,                    true,          false,       nullptr};
     arr[A_STORE]  = {dstride,              ext,           false,       nullptr};          // leaves in the dense image
@@ -305,7 +307,8 @@ int plan_and_issue(LrmHostCtx &c, SliceJob &sj) {
     DevSlot *const d = S.dev;
     for (int a = 0; a < N_ARRAYS; ++a)
         if (sj.arr[a].on_dev && d[a].ensure(n * sj.arr[a].elem)) {
-            lrm_set_error(a == A_ANCHOR ? "allocation for the anchor records failed" : a == A_MAPQ ? "allocation for the mapping-quality records failed" : "device allocation failed");
+            lrm_set_error(a == A_ANCHOR ? "allocation for the anchor records failed" : a == A_MAPQ ? "allocation for the mapping-quality records failed" :
+                          a == A_SUMMARY ? "allocation for the alignment summary records failed" : "device allocation failed");
             return -1;
         }
     // (the dense result buffers and offset tables at their worst-case size for a unit, so that the collector never
@@ -349,6 +352,8 @@ int plan_and_issue(LrmHostCtx &c, SliceJob &sj) {
                 if (lrm_launch_extend_anchored(idx, S.ws_ext[xs].get(), b, j.gp, (lrm_anchor *) d[A_ANCHOR].p + u.off, mt.anchor_min_len, lrm_clip_of(mt),
                                                mt, c.ext[xs])) return -1;
             } else if (lrm_launch_extend(idx, S.ws_ext[xs].get(), b, j.gp, mt, c.ext[xs])) return -1;
+            if (sj.want_summary &&                                             // what the alignments consist of, while the op bytes are in HBM
+                lrm_launch_aln_summary(b.store, dstride, b.n_ops, b.score, b.meta_r, u.m, (lrm_aln_summary *) d[A_SUMMARY].p + u.off, c.ext[xs])) return -1;
             if (mt.cigar_text &&                                               // length of every read's run-length CIGAR text
                 lrm_launch_cigar_text(b.store, dstride, b.n_ops, b.score, b.meta_r, (uint32_t *) d[A_TLEN].p + u.off, nullptr, nullptr, u.m, c.ext[xs])) return -1;
             HIPCHK(hipEventRecord(S.ev_ext[g], c.ext[xs]));

@@ -302,6 +302,39 @@ extern "C" int lrm_extend_batch_clipped_dev(lrm_index *idx, lrm_workspace *ws, c
 }
 
 // ------------------------------------------------------------------------------------------
+// alignment summary (docs/GACT_SPEC.md, "Alignment summary and PAF"): the rule on the host, and the device-buffer entry point
+// ------------------------------------------------------------------------------------------
+extern "C" void lrm_aln_summary_host(const uint8_t *ops, int n_ops, lrm_aln_summary *out) {
+    if (!out) return;
+    memset(out, 0, sizeof(*out));
+    if (!ops || n_ops <= 0) return;
+    int first = -1, last = -1;                                       // the first and the last column that is not 'S'
+    uint8_t before = 0;                                              // the column before this one; column -1 is no op
+    for (int i = 0; i < n_ops; ++i) {
+        const uint8_t o = ops[i];
+        switch (o) {
+            case '=': out->n_eq++; break;
+            case 'X': out->n_x++; break;
+            case 'I': out->n_ins++; out->ins_runs += before != 'I'; break;
+            case 'D': out->n_del++; out->del_runs += before != 'D'; break;
+            default: break;                                          // 'S', or a byte outside the alphabet: counted nowhere
+        }
+        if (o != 'S') { if (first < 0) first = i; last = i; }
+        before = o;
+    }
+    out->clip_left = first < 0 ? (uint32_t) n_ops : (uint32_t) first;
+    out->clip_right = first < 0 ? 0u : (uint32_t) (n_ops - 1 - last);
+}
+
+extern "C" int lrm_aln_summary_dev(lrm_index *idx, const uint8_t *d_store, uint64_t store_stride, const int32_t *d_n_ops,
+                                   const int32_t *d_score, const int32_t *d_meta_r, uint64_t n, lrm_aln_summary *d_out, void *stream) {
+    if (!idx || (n && (!d_store || !d_n_ops || !d_score || !d_meta_r || !d_out))) { lrm_set_error("null argument"); return -1; }
+    if ((uintptr_t) d_out & 15u) { lrm_set_error("alignment summary records must be 16-byte aligned"); return -1; }
+    if (lrm_require_device(idx->device)) return -1;
+    return lrm_launch_aln_summary(d_store, store_stride, d_n_ops, d_score, d_meta_r, n, d_out, stream);
+}
+
+// ------------------------------------------------------------------------------------------
 // split reads (docs/GACT_SPEC.md, "Split reads"): the rule on the host, and the device-buffer entry point
 // ------------------------------------------------------------------------------------------
 int lrm_split_min_len(uint32_t m, uint32_t *out) {

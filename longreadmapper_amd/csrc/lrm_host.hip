@@ -181,16 +181,29 @@ extern "C" int lrm_map_batch(lrm_index *idx, char *reads_buf, uint64_t stride, c
     return run_job(idx, j, nullptr, nullptr);
 }
 
-// mapq_out != null: the mapping-quality stage behind every seed sub-batch (docs/GACT_SPEC.md, "Mapping quality")
+// The per-call extras (lrm_batch_extras).  mapq_out: the mapping-quality stage behind every seed sub-batch (docs/GACT_SPEC.md,
+// "Mapping quality"); summary_out: the alignment summary stage behind every group's extension ("Alignment summary and PAF").
+extern "C" int lrm_map_batch_submit_ex(lrm_index *idx, char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
+                                       lrm_params p, lrm_gact_params gp, lrm_entry *best_out, lrm_cigar *cig_out,
+                                       uint8_t *store_mem, uint64_t store_stride, int *score_out, lrm_seq_meta *meta_out,
+                                       int *meta_r_out, const lrm_map_options *opt, const lrm_batch_extras *ex, lrm_ticket **ticket_out) {
+    if (!ticket_out) { lrm_set_error("null argument"); return -1; }
+    MapJob j;
+    if (map_job_of(j, idx, reads_buf, stride, lens, n, p, gp, best_out, cig_out, store_mem, store_stride, score_out, meta_out, meta_r_out)) return -1;
+    if (ex) {                                                        // as many fields as the caller's struct holds (0: all)
+        const size_t have = ex->struct_size ? ex->struct_size : sizeof(*ex);
+        if (have >= offsetof(lrm_batch_extras, mapq_out) + sizeof(ex->mapq_out)) j.mapq_out = ex->mapq_out;
+        if (have >= offsetof(lrm_batch_extras, summary_out) + sizeof(ex->summary_out)) j.summary_out = ex->summary_out;
+    }
+    return run_job(idx, j, opt, ticket_out);
+}
 extern "C" int lrm_map_batch_submit_mapq(lrm_index *idx, char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
                                          lrm_params p, lrm_gact_params gp, lrm_entry *best_out, lrm_cigar *cig_out,
                                          uint8_t *store_mem, uint64_t store_stride, int *score_out, lrm_seq_meta *meta_out,
                                          int *meta_r_out, const lrm_map_options *opt, lrm_mapq *mapq_out, lrm_ticket **ticket_out) {
-    if (!ticket_out) { lrm_set_error("null argument"); return -1; }
-    MapJob j;
-    if (map_job_of(j, idx, reads_buf, stride, lens, n, p, gp, best_out, cig_out, store_mem, store_stride, score_out, meta_out, meta_r_out)) return -1;
-    j.mapq_out = mapq_out;
-    return run_job(idx, j, opt, ticket_out);
+    const lrm_batch_extras ex = {(uint32_t) sizeof(lrm_batch_extras), 0, mapq_out, nullptr};
+    return lrm_map_batch_submit_ex(idx, reads_buf, stride, lens, n, p, gp, best_out, cig_out, store_mem, store_stride, score_out,
+                                   meta_out, meta_r_out, opt, &ex, ticket_out);
 }
 extern "C" int lrm_map_batch_submit(lrm_index *idx, char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
                                     lrm_params p, lrm_gact_params gp, lrm_entry *best_out, lrm_cigar *cig_out,

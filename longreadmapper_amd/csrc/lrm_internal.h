@@ -319,6 +319,10 @@ int lrm_launch_pack_rows(const uint8_t *d_src, uint64_t pitch, uint64_t row_cap,
                          uint8_t *d_dense, uint64_t rows, void *stream);
 int lrm_launch_cigar_text(const uint8_t *d_store, uint64_t pitch, const int32_t *d_n_ops, const int32_t *d_score, const int32_t *d_meta_r,
                           uint32_t *d_tlen, const uint64_t *d_off, uint8_t *d_dense, uint64_t rows, void *stream);
+// the alignment summary records (aln_summary_kernels.hip; docs/GACT_SPEC.md, "Alignment summary and PAF") of rows whose op
+// bytes start at d_store + row * pitch: behind the extension that wrote them, on its stream
+int lrm_launch_aln_summary(const uint8_t *d_store, uint64_t pitch, const int32_t *d_n_ops, const int32_t *d_score, const int32_t *d_meta_r,
+                           uint64_t rows, lrm_aln_summary *d_out, void *stream);
 int lrm_launch_seed(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint64_t stride,
                     const uint32_t *d_lens, uint64_t n, uint32_t seed_len,
                     uint32_t thres, lrm_entry *d_best, const LrmMapTune &mt, void *stream, uint8_t *d_phase_out = nullptr);

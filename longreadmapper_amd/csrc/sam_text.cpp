@@ -9,16 +9,7 @@
 #include "sam_text.h"
 #include "lrm_internal.h"
 
-// ---- the writers every field goes through ------------------------------------------------------------------------------------
-static inline int put_uint(char *dst, uint64_t v) {           // decimal text of v, returns its length (<= 20)
-    char tmp[24];
-    int n = 0;
-    do { tmp[n++] = (char) ('0' + v % 10); v /= 10; } while (v);
-    for (int i = 0; i < n; ++i) dst[i] = tmp[n - 1 - i];
-    return n;
-}
-static inline void put_num(std::string &s, uint64_t v) { char num[24]; s.append(num, (size_t) put_uint(num, v)); }
-static inline void put_int(std::string &s, int64_t v) { if (v < 0) { s += '-'; put_num(s, (uint64_t) -v); } else put_num(s, (uint64_t) v); }
+// (the writers every field goes through -- put_uint, put_num, put_int -- are in sam_text.h: the PAF formatter uses them too)
 
 // class of an op byte for the run-length CIGAR: '=' and 'X' print as M, every other byte as itself
 static inline char op_class(uint8_t o) { return (o == '=' || o == 'X') ? 'M' : (char) o; }
@@ -73,6 +64,7 @@ __attribute__((always_inline)) static inline void put_cigar(std::string &s, cons
         s.resize(at + (size_t) rle_write<false>(c.cigar, c.n_cigar_op, &s[at]));
     }
 }
+void sam_append_cigar(std::string &s, const lrm_cigar &c, bool is_text) { put_cigar(s, c, is_text); }
 // the name of reference sequence seq_id; "*" if there is none
 static inline void put_rname(std::string &s, const SamBatch &b, int seq_id) {
     if (seq_id >= 0 && seq_id < b.mta_len) s.append(b.mta[seq_id].name, b.mta[seq_id].name_len); else s += '*';

@@ -18,6 +18,19 @@ struct SamBatch {
     const lrm_mapq *mq;            // null: column 5 is 255, no v1:i / v2:i
 };
 
+// ---- the writers every field goes through (sam_text.cpp, paf_text.cpp) ----
+static inline int put_uint(char *dst, uint64_t v) {           // decimal text of v, returns its length (<= 20)
+    char tmp[24];
+    int n = 0;
+    do { tmp[n++] = (char) ('0' + v % 10); v /= 10; } while (v);
+    for (int i = 0; i < n; ++i) dst[i] = tmp[n - 1 - i];
+    return n;
+}
+static inline void put_num(std::string &s, uint64_t v) { char num[24]; s.append(num, (size_t) put_uint(num, v)); }
+static inline void put_int(std::string &s, int64_t v) { if (v < 0) { s += '-'; put_num(s, (uint64_t) -v); } else put_num(s, (uint64_t) v); }
+// the CIGAR column of one alignment as lrm_parse_cigar prints it: the text as it is, or the run-length text of the op bytes
+void sam_append_cigar(std::string &s, const lrm_cigar &c, bool is_text);
+
 // Up to nt threads format a contiguous range of reads each into a buffer of their own: the text is parts[0] + parts[1] + ...
 void sam_format_parts(const SamBatch &b, int nt, std::vector<std::string> &parts);
 // at[k]: where parts[k] begins in a text that begins at `base`; at[parts.size()]: where the text ends

@@ -28,6 +28,17 @@ MAPQ_DT = np.dtype([("n1", "<u4"), ("n2", "<u4"), ("radius", "<u4"), ("mapq", "u
                     ("_pad", "u1")])                              # lrm_mapq (docs/GACT_SPEC.md, "Mapping quality")
 assert MAPQ_DT.itemsize == 16
 MAPQ_OVERFLOW = capi.MAPQ_OVERFLOW
+SUMMARY_DT = np.dtype([("n_eq", "<u4"), ("n_x", "<u4"), ("n_ins", "<u4"), ("n_del", "<u4"), ("ins_runs", "<u4"), ("del_runs", "<u4"),
+                       ("clip_left", "<u4"), ("clip_right", "<u4")])      # lrm_aln_summary (docs/GACT_SPEC.md, "Alignment summary and PAF")
+assert SUMMARY_DT.itemsize == 32
+
+
+def aln_summary_host(ops):
+    """lrm_aln_summary_host: the alignment summary record of one alignment's op bytes -> dict of the lrm_aln_summary fields."""
+    data = bytes(ops)
+    a = capi.AlnSummary()
+    lib.lrm_aln_summary_host(data, len(data), C.byref(a))
+    return {f: int(getattr(a, f)) for f, _ in a._fields_}
 
 
 def anchored_store_stride(max_len):
@@ -121,8 +132,9 @@ def pinned_free(arr):
 class PendingBatch:
     """A batch submitted with map_batch_submit: wait() blocks until its results are in the caller's arrays."""
 
-    def __init__(self, ticket, keep, n, dense, text=False):
+    def __init__(self, ticket, keep, n, dense, text=False, extras=None):
         self.ticket, self._keep, self.n, self.dense, self.text = ticket, keep, n, dense, text
+        self._extras = extras or {}          # "mapq" / "summary": the record arrays the batch fills on top
 
     def wait(self):
         t, self.ticket = self.ticket, None
@@ -132,8 +144,7 @@ class PendingBatch:
         n = self.n
         cv = np.ctypeslib.as_array(C.cast(cig, C.POINTER(C.c_int32)), shape=(max(n, 1), 4))[:n]
         out = dict(best=best, ops=store, n_ops=cv[:, 2].copy(), score=score, meta=meta, meta_r=meta_r)
-        if len(self._keep) > 8:
-            out["mapq"] = self._keep[8]
+        out.update(self._extras)
         if self.dense:          # cig[i].cigar = store_mem + off[i]
             ptr = np.ctypeslib.as_array(C.cast(cig, C.POINTER(C.c_uint64)), shape=(max(n, 1), 2))[:n, 0]
             out["ops_off"] = (ptr - np.uint64(store.ctypes.data)).astype(np.int64)
@@ -165,9 +176,10 @@ def ops_of(res, i):
 
 
 def map_batch_submit(index, reads, lens, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT, store=None,
-                     options=None, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0, mapq=False):
-    """lrm_map_batch_submit (mapq=True: lrm_map_batch_submit_mapq -- the result gains "mapq", the MAPQ_DT records of the
-    batch): queues the batch and returns a PendingBatch.  `reads` is modified in place like
+                     options=None, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0, mapq=False,
+                     summary=False):
+    """lrm_map_batch_submit_ex (mapq=True: the result gains "mapq", the MAPQ_DT records of the batch; summary=True: it gains
+    "summary", the SUMMARY_DT records; neither: lrm_map_batch_submit): queues the batch and returns a PendingBatch.  `reads` is modified in place like
     extend_batch once the batch runs; `store` may be a caller-provided (n, >= 2*max_len) uint8 array (e.g. pinned;
     anchored: >= anchored_store_stride(max_len)); `options`: dict of lrm_map_options fields (None: the handle's
     defaults); anchored=True adds the anchored extension mode to them, clip=True that mode with its end clipping
@@ -189,27 +201,34 @@ def map_batch_submit(index, reads, lens, seed_len=DEFAULT_SEED_LEN, thres=DEFAUL
     meta_r = np.zeros(n, dtype=np.int32)
     opt = capi.map_options(**options) if options is not None else None
     ticket = C.c_void_p()
-    mq = np.zeros(n, dtype=MAPQ_DT) if mapq else None
-    check(lib.lrm_map_batch_submit_mapq(index.handle, reads.ctypes.data, stride, lens.ctypes.data, n,
-                                        capi.Params(n, seed_len, thres), capi.GactParams(*gact), best.ctypes.data,
-                                        C.cast(cig, C.c_void_p), store.ctypes.data, store_stride, score.ctypes.data,
-                                        meta.ctypes.data, meta_r.ctypes.data, C.byref(opt) if opt is not None else None,
-                                        mq.ctypes.data if mapq else None, C.byref(ticket)), "lrm_map_batch_submit_mapq")
+    extras = {}
+    if mapq:
+        extras["mapq"] = np.zeros(n, dtype=MAPQ_DT)
+    if summary:
+        extras["summary"] = np.zeros(n, dtype=SUMMARY_DT)
+    ex = capi.BatchExtras(C.sizeof(capi.BatchExtras), 0, extras["mapq"].ctypes.data if mapq else None,
+                          extras["summary"].ctypes.data if summary else None)
+    check(lib.lrm_map_batch_submit_ex(index.handle, reads.ctypes.data, stride, lens.ctypes.data, n,
+                                      capi.Params(n, seed_len, thres), capi.GactParams(*gact), best.ctypes.data,
+                                      C.cast(cig, C.c_void_p), store.ctypes.data, store_stride, score.ctypes.data,
+                                      meta.ctypes.data, meta_r.ctypes.data, C.byref(opt) if opt is not None else None,
+                                      C.byref(ex) if extras else None, C.byref(ticket)), "lrm_map_batch_submit_ex")
     text = bool(opt.cigar_text) if opt is not None else False
     dense = (bool(opt.dense_results) or text) if opt is not None else False
     keep = (best, store, cig, score, meta, meta_r, reads, lens)
-    return PendingBatch(ticket, keep + (mq,) if mapq else keep, n, dense, text)
+    return PendingBatch(ticket, keep, n, dense, text, extras)
 
 
 def map_batch(index, reads, lens, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT, store=None,
-              options=None, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0, mapq=False):
+              options=None, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0, mapq=False, summary=False):
     """PART 1 + PART 2 in one device pass; `reads` is modified in place like extend_batch.
     Without `options` this is lrm_map_batch (the handle's default options), with them (or with anchored=True or
     clip=True, which are among them) submit + wait.  mapq=True: the mapping-quality records (MAPQ_DT) come back as
-    res["mapq"] next to the other results, which do not change (submit + wait through lrm_map_batch_submit_mapq)."""
+    res["mapq"] next to the other results, which do not change; summary=True: the alignment summary records (SUMMARY_DT) as
+    res["summary"], likewise (submit + wait through lrm_map_batch_submit_ex)."""
     options = _anchor_options(options, anchored, anchor_min_len, clip, clip_penalty, clip_end_bonus)
-    if options is not None or mapq:
-        return map_batch_submit(index, reads, lens, seed_len, thres, gact, store, options, mapq=mapq).wait()
+    if options is not None or mapq or summary:
+        return map_batch_submit(index, reads, lens, seed_len, thres, gact, store, options, mapq=mapq, summary=summary).wait()
     assert reads.dtype == np.uint8 and reads.flags.c_contiguous and reads.flags.writeable
     lens = np.ascontiguousarray(lens, dtype=np.uint32)
     n, stride = reads.shape
@@ -362,8 +381,10 @@ class DeviceMapper:
 
     def __init__(self, index, n_max, max_len, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT,
                  device=0, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0, split=False,
-                 split_min_len=0, seg_cap=None, seg_rows=None, mapq=False):
-        """mapq: seed() runs the mapping-quality stage behind the seed stage (lrm_seed_batch_mapq_dev); mapq_records(n) and
+                 split_min_len=0, seg_cap=None, seg_rows=None, mapq=False, summary=False):
+        """summary: extend() runs the alignment summary stage behind the extension, whichever mode (lrm_aln_summary_dev);
+        summary_records(n) and results(n)["summary"] are the SUMMARY_DT records of the last extend call.
+        mapq: seed() runs the mapping-quality stage behind the seed stage (lrm_seed_batch_mapq_dev); mapq_records(n) and
         results(n)["mapq"] are the MAPQ_DT records of the last seed call.
         split (needs clip): split() after extend() maps the soft-clipped ends of at least split_min_len bases (0 = 200) as
         reads of their own (lrm_split_batch_dev), results() returns them as res["split"].  seg_cap: room for that many
@@ -394,6 +415,7 @@ class DeviceMapper:
         self.anchor = torch.zeros((n_max, 32), dtype=torch.uint8, device=self.dev) if anchored else None     # lrm_anchor
         self.clip = torch.zeros((n_max, 2), dtype=torch.int32, device=self.dev) if clip else None           # lrm_clip
         self.mapq = torch.zeros((n_max, 16), dtype=torch.uint8, device=self.dev) if mapq else None           # lrm_mapq
+        self.summary = torch.zeros((n_max, 32), dtype=torch.uint8, device=self.dev) if summary else None    # lrm_aln_summary
         self.split_on, self.split_min_len, self.ws_seg, self.n_seg = bool(split), split_min_len, None, 0
         if split:
             if not clip:
@@ -440,8 +462,20 @@ class DeviceMapper:
         assert self.mapq is not None
         return self.mapq[:n].cpu().numpy().reshape(-1).view(MAPQ_DT)
 
+    def summary_records(self, n):
+        """The lrm_aln_summary records (SUMMARY_DT) of the last extend() -- DeviceMapper(..., summary=True)."""
+        assert self.summary is not None
+        return self.summary[:n].cpu().numpy().reshape(-1).view(SUMMARY_DT)
+
     def extend(self, d_reads, d_lens, n=None):
         n = d_reads.shape[0] if n is None else n
+        self._extend(d_reads, d_lens, n)
+        if self.summary is not None:
+            check(lib.lrm_aln_summary_dev(self.index.handle, self.store.data_ptr(), self.store_stride, self.n_ops.data_ptr(),
+                                          self.score.data_ptr(), self.meta_r.data_ptr(), n, self.summary.data_ptr(),
+                                          self._stream()), "lrm_aln_summary_dev")
+
+    def _extend(self, d_reads, d_lens, n):
         gp = capi.GactParams(*self.gact)
         if self.clip_on:
             check(lib.lrm_extend_batch_clipped_dev(self.index.handle, self.ws, d_reads.data_ptr(), d_reads.stride(0),
@@ -549,6 +583,8 @@ class DeviceMapper:
             res["split"] = self.split_results()
         if self.mapq is not None:
             res["mapq"] = self.mapq_records(n)
+        if self.summary is not None:
+            res["summary"] = self.summary_records(n)
         return res
 
     def close(self):
