@@ -561,8 +561,18 @@ typedef struct lrm_stats {
     uint64_t seed_table_lookups;    /* 8-byte entries of the seed tables (lchash image or long table) read */
     uint64_t seed_rank_requests;    /* 16-byte {prefix, mask} pairs of the occ blocks read (1 or 2 per backward step) */
     uint64_t vote_redo_items;       /* (read, phase) items the fast vote kernel left to the exact one */
+    /* with lrm_workspace_set_counting(ws, 1): the paths the bit-sliced extension kernel took, added up over its launches
+     * since the last seed call (or since the workspace was made) */
+    uint64_t bs_wave_tiles;         /* rounds of a wavefront's tile loop (64 lanes, one tile each) */
+    uint64_t bs_pass1_pairs_masked; /* pass-1 pairs of anti-diagonals whose even step ran the masked (free-exit) form */
+    uint64_t bs_pass1_pairs_plain;  /* ... the plain form */
+    uint64_t bs_blocks_full;        /* traceback blocks recomputed in full width with the masked step */
+    uint64_t bs_blocks_windowed;    /* ... on the 32-point window */
+    uint64_t bs_blocks_skipped;     /* ... left out: no lane of the wavefront was still walking */
+    uint64_t bs_refill_rounds;      /* rounds of the read queue (one atomic each) */
 } lrm_stats;
-/* Counting build of the seed kernel for the NEXT calls on this workspace (bench bookkeeping: slower, never timed). */
+/* Counting builds of the seed kernel and of the bit-sliced extension kernel for the NEXT calls on this workspace
+ * (bench bookkeeping: slower, never timed). */
 int lrm_workspace_set_counting(lrm_workspace *ws, int enable);
 int lrm_workspace_stats(lrm_workspace *ws, lrm_stats *out, void *stream);
 

@@ -142,10 +142,16 @@ ANCHOR_SOFT_LEFT, ANCHOR_SOFT_RIGHT = 32, 64      # end clipping (lrm_map_option
 ANCHOR_DIAGS = 64                      # LRM_ANCHOR_DIAGS
 
 
+# the counting build of gact_bs_kernel (lrm_stats, after vote_redo_items)
+BS_COUNTERS = ("bs_wave_tiles", "bs_pass1_pairs_masked", "bs_pass1_pairs_plain", "bs_blocks_full", "bs_blocks_windowed",
+               "bs_blocks_skipped", "bs_refill_rounds")
+
+
 class Stats(C.Structure):
     _fields_ = [("vote_tier2_items", C.c_uint64), ("vote_tier3_items", C.c_uint64),
                 ("reads_decided_phase0", C.c_uint64), ("gact_tiles", C.c_uint64), ("seeds_evaluated", C.c_uint64),
-                ("seed_table_lookups", C.c_uint64), ("seed_rank_requests", C.c_uint64), ("vote_redo_items", C.c_uint64)]
+                ("seed_table_lookups", C.c_uint64), ("seed_rank_requests", C.c_uint64), ("vote_redo_items", C.c_uint64)] + \
+               [(name, C.c_uint64) for name in BS_COUNTERS]
 
 
 class ReadBatch(C.Structure):          # lrm_io_host.h

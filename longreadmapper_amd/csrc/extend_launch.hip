@@ -48,9 +48,9 @@ int lrm_gact_plan(const LrmGactJobs &j, lrm_gact_params gp, int impl, bool plana
 
 // the extension proper over a table of jobs (anchor_kernels.hip builds one; the classic mode's table is the batch itself)
 int lrm_gact_launch_jobs(const LrmGactJobs &j, lrm_gact_params gp, const LrmGactPlan &plan, const LrmBsScratch *bs,
-                         LrmDevCounters *counters, uint32_t bs_waves, void *stream) {
+                         LrmDevCounters *counters, uint32_t bs_waves, bool count, void *stream) {
     if (plan.kernel == LRM_GACT_BS) {
-        if (lrm_bs_launch(j, gp, *bs, counters, bs_waves, stream)) return -1;
+        if (lrm_bs_launch(j, gp, *bs, counters, bs_waves, count, stream)) return -1;
         // reads holding a byte other than ACGT (rare): one read per wavefront, flagged reads only
         return lrm_gact_launch_wide(j, gp, plan, counters, bs->rflags, stream);
     }
@@ -66,7 +66,7 @@ int lrm_gact_run_jobs(lrm_workspace *ws, const LrmGactJobs &j, uint32_t max_len,
         lrm_time_end(ws, stream);
     }
     lrm_time_begin(ws, plan.slot, stream);
-    if (lrm_gact_launch_jobs(j, gp, plan, &bs, counters, bs_waves, stream)) return -1;
+    if (lrm_gact_launch_jobs(j, gp, plan, &bs, counters, bs_waves, ws && ws->counting, stream)) return -1;
     lrm_time_end(ws, stream);
     return 0;
 }

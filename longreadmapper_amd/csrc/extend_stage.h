@@ -92,9 +92,10 @@ static inline bool lrm_planar_ready(const lrm_index *idx, const lrm_workspace *w
 int lrm_gact_resolve_params(lrm_gact_params *gp);
 // THE choice of the extension kernel for a job table.  planar: lrm_planar_ready, and the scratch holds this table
 int lrm_gact_plan(const LrmGactJobs &j, lrm_gact_params gp, int gact_impl, bool planar, LrmGactPlan *out);
-// the launch the plan names (bs: packed reads and scratch, used by LRM_GACT_BS only; bs_waves: 0 or a smaller grid, tests)
+// the launch the plan names (bs: packed reads and scratch, used by LRM_GACT_BS only; bs_waves: 0 or a smaller grid, tests;
+// count: the counting build of the bit-sliced kernel)
 int lrm_gact_launch_jobs(const LrmGactJobs &j, lrm_gact_params gp, const LrmGactPlan &plan, const LrmBsScratch *bs,
-                         LrmDevCounters *counters, uint32_t bs_waves, void *stream);
+                         LrmDevCounters *counters, uint32_t bs_waves, bool count, void *stream);
 // running a job table: the planar image of its reads (up to max_len bases) when the plan is LRM_GACT_BS, in the
 // LRM_K_PACK_PLANAR slot, then lrm_gact_launch_jobs in the plan's slot.  ws: whose timing records the slots (null: none)
 LRM_LOCAL int lrm_gact_run_jobs(lrm_workspace *ws, const LrmGactJobs &j, uint32_t max_len, lrm_gact_params gp,
@@ -116,7 +117,7 @@ void lrm_bs_free_index(lrm_index *idx);
 uint64_t lrm_bs_code_words(uint32_t max_len);
 uint64_t lrm_bs_ckpt_words(uint64_t n);
 int lrm_bs_launch(const LrmGactJobs &j, lrm_gact_params gp, const LrmBsScratch &bs, LrmDevCounters *counters,
-                  uint32_t max_waves, void *stream);
+                  uint32_t max_waves, bool count, void *stream);
 
 // ---- the modes -------------------------------------------------------------------------------------------------------------
 // a batch as the extension entry points receive it (device pointers; field order of the extern "C" parameter lists)

@@ -45,6 +45,7 @@
 #define BS_H (BS_K / 2)
 #define LRM_BS_MAX_WAVES 2048ull  // 2 per SIMD on 256 CUs
 #define BS_PADW LRM_BS_PADW
+#define BS_NO_EXIT 0x40000000   // tq, tt of a lane without a tile: no stream word holds its free-exit point
 
 struct __attribute__((aligned(8))) BsPair { uint64_t a, b; };
 
@@ -171,6 +172,33 @@ __device__ __forceinline__ void bs_step(BsState &x, const BsStream &st, BsPl &N,
                           x.V1.hi, x.V0.hi, x.H1.hi, x.H0.hi, N.hi, G.hi);
 }
 
+__device__ __forceinline__ void bs_ckpt_store(uint32_t *ckl, int s, const BsState &x) {   // ckl: the wavefront's checkpoints + lane
+    uint32_t *c_ = ckl + (size_t) (s / BS_K - 1) * 512;
+    c_[0] = x.V1.lo; c_[64] = x.V1.hi; c_[128] = x.V0.lo; c_[192] = x.V0.hi;
+    c_[256] = x.H1.lo; c_[320] = x.H1.hi; c_[384] = x.H0.lo; c_[448] = x.H0.hi;
+}
+
+// np step pairs of pass 1 between two events (a stream refill, the tile's last anti-diagonal): nothing but the two steps,
+// the two window shifts and a checkpoint store where one is due, HB fixed, in a loop of its own -- in one loop with the
+// events the compiler rotates the stream words through copies on every pair (31 v_mov of 95 instructions,
+// profiles/r5/README.md)
+template <bool HB>
+__device__ __forceinline__ void bs_pass1_pairs(BsState &x, BsStream &st, uint32_t &shq, uint32_t &shd, int &s, int &ck_s,
+                                               uint32_t *ckl, int np) {
+    BsPl nN, nG;
+#pragma nounroll
+    for (int k = 0; k < np; ++k) {
+        bs_step<false, HB, false>(x, st, nN, nG);
+        if (s == ck_s) { bs_ckpt_store(ckl, s, x); ck_s -= BS_K; }
+        ++shq;
+        bs_extract_q<HB>(st, shq);
+        bs_step<true, HB, false>(x, st, nN, nG);
+        --shd;
+        bs_extract_d<HB>(st, shd);
+        s -= 2;
+    }
+}
+
 __device__ __forceinline__ int bs_wave_max(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
@@ -192,6 +220,9 @@ __device__ __forceinline__ void bs_block_prefetch(BsBlockRaw &raw, const BsTile 
     for (int e = 0; e < 8; ++e) raw.ck[e] = cp[64 * e];
 }
 
+// COUNT: the counting build (lrm_workspace_set_counting; bookkeeping, never in a timed region) adds up, per wavefront,
+// which path every pass-1 step pair and every pass-2 block took (LrmDevCounters::bs_count, LRM_BSC_*)
+template <bool COUNT>
 __global__ __launch_bounds__(64) void gact_bs_kernel(const uint64_t *__restrict__ qpl, uint64_t wpr,
                                                      const uint32_t *__restrict__ lens,
                                                      const lrm_seq_meta *__restrict__ meta,
@@ -231,6 +262,7 @@ __global__ __launch_bounds__(64) void gact_bs_kernel(const uint64_t *__restrict_
     uint64_t pend = 0;             // a full code word whose store is delayed past the next block's loads
     bool has_pend = false;
     unsigned tiles = 0;
+    unsigned nc[LRM_BSC_N] = {};   // COUNT only; wave-uniform
 
     while (true) {
         if (alive && (score < 0 || !(i < n && j < m))) {          // this lane's read is finished: write it out
@@ -247,6 +279,7 @@ __global__ __launch_bounds__(64) void gact_bs_kernel(const uint64_t *__restrict_
             const bool need = !alive && !exhausted;
             const uint64_t needmask = __ballot(need);
             if (needmask == 0) break;
+            if (COUNT) nc[LRM_BSC_REFILLS]++;
             unsigned long long base = 0;
             if (lane == 0) base = atomicAdd(queue, (unsigned long long) __popcll(needmask));
             base = __shfl(base, 0);
@@ -276,12 +309,18 @@ __global__ __launch_bounds__(64) void gact_bs_kernel(const uint64_t *__restrict_
         const uint64_t actmask = __ballot(act);
         if (actmask == 0) break;
         tiles += (unsigned) __popcll(actmask);
+        if (COUNT) nc[LRM_BSC_WAVE_TILES]++;
         t.i = i;
         t.dpos = loc + j;
-        t.tq = act ? min(T, n - i) : 0;
-        t.tt = act ? min(T, m - j) : 0;
-        const bool last = i + t.tq == n;
-        const int S0 = ((bs_wave_max(t.tq + t.tt) + BS_K - 1) / BS_K) * BS_K;
+        const int tq = act ? min(T, n - i) : 0, tt = act ? min(T, m - j) : 0;
+        // A lane without a tile (batch exhausted, read finished, fenced or flagged) carries no free-exit point: with
+        // tq = tt = 0 it would hold one in the stream words near the anchor and put its whole wavefront on the masked
+        // step and on full-width blocks, for planes nobody reads.  BS_NO_EXIT is out of bs_onehot's reach for every
+        // a_hi and b_lo of a tile (|a_hi|, |b_lo| < 2^12).
+        t.tq = act ? tq : BS_NO_EXIT;
+        t.tt = act ? tt : BS_NO_EXIT;
+        const bool last = i + tq == n;
+        const int S0 = ((bs_wave_max(tq + tt) + BS_K - 1) / BS_K) * BS_K;
         const int nb = min(nblk, S0 / BS_K);
 
         BsState x = {{0u, 0u}, {~0u, ~0u}, {0u, 0u}, {~0u, ~0u}};
@@ -296,14 +335,11 @@ __global__ __launch_bounds__(64) void gact_bs_kernel(const uint64_t *__restrict_
         uint32_t shq = 0, shd = 31;
         bool hb = bs_any_sentinel(st);
         int ck_s = nb * BS_K;                                      // next anti-diagonal whose state is kept
-        for (int s = S0;; s -= 2) {
+        for (int s = S0;;) {
+            // a pair with an event: the way out after the even step, the refills around the odd one
+            if (COUNT) { if (hb) nc[LRM_BSC_P1_MASKED]++; else nc[LRM_BSC_P1_PLAIN]++; }
             if (hb) bs_step<false, true, false>(x, st, nN, nG); else bs_step<false, false, false>(x, st, nN, nG);
-            if (s == ck_s) {
-                uint32_t *c_ = ckw + (size_t) (s / BS_K - 1) * 512 + lane;
-                c_[0] = x.V1.lo; c_[64] = x.V1.hi; c_[128] = x.V0.lo; c_[192] = x.V0.hi;
-                c_[256] = x.H1.lo; c_[320] = x.H1.hi; c_[384] = x.H0.lo; c_[448] = x.H0.hi;
-                ck_s -= BS_K;
-            }
+            if (s == ck_s) { bs_ckpt_store(ckw + lane, s, x); ck_s -= BS_K; }
             if (s == BS_K) break;
             if (++shq == 32) {
                 st.q0 = st.q1; st.q1 = st.q2; st.q2 = bs_q_conv(t, st.qnext, pq);
@@ -330,16 +366,22 @@ __global__ __launch_bounds__(64) void gact_bs_kernel(const uint64_t *__restrict_
             }
             --shd;
             if (hb) bs_extract_d<true>(st, shd); else bs_extract_d<false>(st, shd);
+            s -= 2;
+            // the pairs up to the next event: ++shq stays below 32, shd above 0, s above the last anti-diagonal
+            const int np = min(min(31 - (int) shq, (int) shd), (s - BS_K) >> 1);
+            if (COUNT) { if (hb) nc[LRM_BSC_P1_MASKED] += (unsigned) np; else nc[LRM_BSC_P1_PLAIN] += (unsigned) np; }
+            if (hb) bs_pass1_pairs<true>(x, st, shq, shd, s, ck_s, ckw + lane, np);
+            else bs_pass1_pairs<false>(x, st, shq, shd, s, ck_s, ckw + lane, np);
         }
         // ---- pass 2: per block recompute with decision planes, then walk through the block ----
         // the walk keeps at most T-O bases of either sequence; in the read's last tile it may run on to the edge
         // but not past anti-diagonal 2(T-O) (docs/GACT_SPEC.md)
-        const int amax = last ? t.tq : min(t.tq, cap), bmax = last ? t.tt : min(t.tt, cap);
+        const int amax = last ? tq : min(tq, cap), bmax = last ? tt : min(tt, cap);
         BsWalk wk = {act ? -amax : 0, act ? -bmax : 0, act ? -lim2 : 0, score};
         BsBlockRaw raw;
         bs_block_prefetch(raw, t, 0, ckw, lane);
         for (int c = 0; c < nb; ++c) {
-            if (__ballot(bs_walk_running(&wk)) == 0) break;
+            if (__ballot(bs_walk_running(&wk)) == 0) { if (COUNT) nc[LRM_BSC_P2_SKIPPED] += (unsigned) (nb - c); break; }
             const int A0 = BS_H * (c + 1) + 31, b_lo = BS_H * c - 32;
             st.q0 = bs_q_conv(t, A0, raw.q0); st.q1 = bs_q_conv(t, A0 - 32, raw.q1); st.q2 = bs_q_conv(t, A0 - 64, raw.q2);
             st.d0 = bs_d_conv(t, b_lo, raw.d0); st.d1 = bs_d_conv(t, b_lo + 32, raw.d1); st.d2 = bs_d_conv(t, b_lo + 64, raw.d2);
@@ -347,6 +389,7 @@ __global__ __launch_bounds__(64) void gact_bs_kernel(const uint64_t *__restrict_
             // with the masked step.  Every other block on the 32 points per anti-diagonal that the lane's walk can reach
             // from where it stands (gact_bs_circuit.h); lanes that do not walk compute something nobody reads.
             const bool full = bs_any_sentinel(st);
+            if (COUNT) { if (full) nc[LRM_BSC_P2_FULL]++; else nc[LRM_BSC_P2_WINDOWED]++; }
             const int32_t boff = bmax - BS_H * c + 32;
             const uint32_t o = bs_win_origin(wk.nb + boff);
             BsWinIn win;
@@ -403,6 +446,12 @@ __global__ __launch_bounds__(64) void gact_bs_kernel(const uint64_t *__restrict_
         }
     }
     if (lane == 0 && tiles) atomicAdd(&counters->gact_tiles, (unsigned long long) tiles);
+    if (COUNT && lane < LRM_BSC_N) {
+        unsigned v = 0;
+#pragma unroll
+        for (int e = 0; e < LRM_BSC_N; ++e) v = lane == e ? nc[e] : v;
+        atomicAdd(&counters->bs_count[lane], (unsigned long long) v);
+    }
 }
 
 // codes -> CIGAR bytes ('=' 'X' 'I' 'D', one per alignment column): one thread per 16 columns (one 16-byte store
@@ -476,15 +525,15 @@ void lrm_bs_scratch_free(LrmBsScratch *s) {
 }
 
 int lrm_bs_launch(const LrmGactJobs &j, lrm_gact_params gp, const LrmBsScratch &bs, LrmDevCounters *counters,
-                  uint32_t max_waves, void *stream_) {
+                  uint32_t max_waves, bool count, void *stream_) {
     hipStream_t stream = (hipStream_t) stream_;
     uint64_t blocks = (j.n + 63) / 64;
     if (blocks > LRM_BS_MAX_WAVES) blocks = LRM_BS_MAX_WAVES;              // resident wavefronts; lanes refill from the queue
     if (max_waves >= 1 && max_waves < blocks) blocks = max_waves;          // (tests: a small grid forces refills)
     HIPCHK(hipMemsetAsync(&counters->bs_queue, 0, sizeof(unsigned long long), stream));
-    hipLaunchKernelGGL(gact_bs_kernel, dim3((uint32_t) blocks), dim3(64), 0, stream, bs.qpl, bs.wpr, j.lens, j.meta,
-                       j.meta_r, j.cpl + BS_PADW, j.tlens, bs.rflags, j.n, gp.T, gp.O, gp.W, bs.ckpt, bs.codes, bs.cw,
-                       bs.ncodes, j.n_ops, j.score, counters);
+    hipLaunchKernelGGL(count ? gact_bs_kernel<true> : gact_bs_kernel<false>, dim3((uint32_t) blocks), dim3(64), 0, stream,
+                       bs.qpl, bs.wpr, j.lens, j.meta, j.meta_r, j.cpl + BS_PADW, j.tlens, bs.rflags, j.n, gp.T, gp.O, gp.W,
+                       bs.ckpt, bs.codes, bs.cw, bs.ncodes, j.n_ops, j.score, counters);
     const uint32_t bpr = (uint32_t) ((bs.cw * 32 + 4095) / 4096);           // 256 threads x 16 columns per block
     uint32_t grid;
     if (lrm_grid_1d(j.n * bpr, "expand", &grid)) return -1;

@@ -189,8 +189,13 @@ struct LrmDevCounters {
     unsigned long long vote_redo_n[2];        //   items it left to the exact kernel
     unsigned long long vote_big_n[2];         //   items it left to its workgroup form, and that kernel's ticket
     unsigned long long vote_big_ticket[2];
+    unsigned long long bs_count[7];           // counting build of gact_bs_kernel, LRM_BSC_*
 };
-static_assert(offsetof(LrmDevCounters, decided_phase0) == 64 && sizeof(LrmDevCounters) == 160, "counters are addressed by the device as laid out here");
+// bs_count: wave-tiles (rounds of the outer loop), pass-1 step pairs whose even step was masked / plain, pass-2 blocks
+// recomputed full-width / on the 32-point window / left out because no lane of the wavefront still walked, refill rounds
+enum { LRM_BSC_WAVE_TILES = 0, LRM_BSC_P1_MASKED, LRM_BSC_P1_PLAIN, LRM_BSC_P2_FULL, LRM_BSC_P2_WINDOWED, LRM_BSC_P2_SKIPPED,
+       LRM_BSC_REFILLS, LRM_BSC_N };
+static_assert(offsetof(LrmDevCounters, decided_phase0) == 64 && sizeof(LrmDevCounters) == 216, "counters are addressed by the device as laid out here");
 // Error word of a workspace: ONE dword of host-coherent pinned memory that kernels set with a plain store (bit 0:
 // vote table overflow in the multi-pass tier).  It is never cleared by a launch, so an error raised by any
 // sub-batch survives until the host reads it: lrm_workspace_stats and every *_dev entry point check it (the
@@ -229,7 +234,7 @@ struct lrm_workspace {
     int parts;               // LRM_WS_SEED | LRM_WS_EXTEND: which scratch this workspace owns
     // optional per-kernel timing (HIP events recorded on the launch stream)
     int timing;
-    int counting;            // seed_search runs its counting build (lrm_workspace_set_counting)
+    int counting;            // seed_search and gact_bs run their counting builds (lrm_workspace_set_counting)
     int n_timed;
     void *ev_start[LRM_MAX_TIMED], *ev_stop[LRM_MAX_TIMED];
     int ev_kernel[LRM_MAX_TIMED];

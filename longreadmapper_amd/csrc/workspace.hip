@@ -135,6 +135,13 @@ extern "C" int lrm_workspace_stats(lrm_workspace *ws, lrm_stats *out, void *stre
     out->seeds_evaluated = c.seed_traffic[0];
     out->seed_table_lookups = c.seed_traffic[1];
     out->seed_rank_requests = c.seed_traffic[2];
+    out->bs_wave_tiles = c.bs_count[LRM_BSC_WAVE_TILES];
+    out->bs_pass1_pairs_masked = c.bs_count[LRM_BSC_P1_MASKED];
+    out->bs_pass1_pairs_plain = c.bs_count[LRM_BSC_P1_PLAIN];
+    out->bs_blocks_full = c.bs_count[LRM_BSC_P2_FULL];
+    out->bs_blocks_windowed = c.bs_count[LRM_BSC_P2_WINDOWED];
+    out->bs_blocks_skipped = c.bs_count[LRM_BSC_P2_SKIPPED];
+    out->bs_refill_rounds = c.bs_count[LRM_BSC_REFILLS];
     return lrm_ws_take_error(ws);
 }
 

@@ -543,7 +543,8 @@ class DeviceMapper:
         return dict(vote_tier2_items=int(st.vote_tier2_items), vote_tier3_items=int(st.vote_tier3_items),
                     reads_decided_phase0=int(st.reads_decided_phase0), gact_tiles=int(st.gact_tiles),
                     seeds_evaluated=int(st.seeds_evaluated), seed_table_lookups=int(st.seed_table_lookups),
-                    seed_rank_requests=int(st.seed_rank_requests), vote_redo_items=int(st.vote_redo_items))
+                    seed_rank_requests=int(st.seed_rank_requests), vote_redo_items=int(st.vote_redo_items),
+                    **{name: int(getattr(st, name)) for name in capi.BS_COUNTERS})
 
     def debug_vote_results(self, n):
         """lrm_debug_vote_results: (n, seed_len + 1, 6) uint64 -- key1, val1, bucket1, key2, val2, bucket2 of every (read, phase)
@@ -553,7 +554,8 @@ class DeviceMapper:
         return out
 
     def set_counting(self, enable=True):
-        """The next seed calls run the counting build of the seed kernel (stats(): requests of the device layout)."""
+        """The next seed and extend calls run the counting builds of the seed kernel (stats(): requests of the device
+        layout) and of the bit-sliced extension kernel (stats(): bs_* path counts)."""
         check(lib.lrm_workspace_set_counting(self.ws, int(enable)), "lrm_workspace_set_counting")
 
     def set_timing(self, enable=True):
