@@ -628,6 +628,23 @@ int lrm_debug_gact(const char *q, int n, const char *d, int m, lrm_gact_params g
 int lrm_debug_gact_impl(const char *q, int n, const char *d, int m, lrm_gact_params gp, int impl,
                         uint8_t *ops, int *n_ops, int *score, int device);
 
+/* Job-table tap (tests only): n (read, target) pairs as ONE job table through the extension's own plan and launch, target
+ * lengths set.  Job k is read row k (reads + k * stride, lens[k] bases) against text[toffs[k], toffs[k] + tlens[k]): the
+ * caller lays the targets out, so it decides the locus residue and what follows a target.  meta_r: null, or per job 0 =
+ * fenced.  store (n rows of store_stride >= lens[k] + tlens[k] bytes), n_ops and score go to the device as they are and
+ * come back as the kernels left them.  counters: null, or 8 words: gact_tiles, then the counters of the bit-sliced
+ * kernel's counting build in the order of lrm_stats (bs_wave_tiles .. bs_refill_rounds; all 0 unless `count`). */
+typedef struct lrm_debug_gact_table {
+    uint64_t n;
+    const char *reads; uint64_t stride; const uint32_t *lens;
+    const char *text; uint64_t text_len; const uint64_t *toffs; const uint32_t *tlens;
+    const int32_t *meta_r;
+    uint8_t *store; uint64_t store_stride; int32_t *n_ops; int32_t *score;
+    uint64_t *counters;
+} lrm_debug_gact_table;
+/* impl, bs_waves: as lrm_map_options.gact_impl / bs_waves; count: the counting build of the bit-sliced kernel */
+int lrm_debug_gact_jobs(const lrm_debug_gact_table *t, lrm_gact_params gp, int impl, uint32_t bs_waves, int count, int device);
+
 #ifdef __cplusplus
 }
 #endif

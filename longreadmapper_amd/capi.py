@@ -134,6 +134,13 @@ class BatchExtras(C.Structure):        # lrm_batch_extras (host pointers)
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("mapq_out", C.c_void_p), ("summary_out", C.c_void_p)]
 
 
+class GactTable(C.Structure):          # lrm_debug_gact_table (host pointers)
+    _fields_ = [("n", C.c_uint64), ("reads", C.c_void_p), ("stride", C.c_uint64), ("lens", C.c_void_p), ("text", C.c_void_p),
+                ("text_len", C.c_uint64), ("toffs", C.c_void_p), ("tlens", C.c_void_p), ("meta_r", C.c_void_p),
+                ("store", C.c_void_p), ("store_stride", C.c_uint64), ("n_ops", C.c_void_p), ("score", C.c_void_p),
+                ("counters", C.c_void_p)]
+
+
 MAPQ_SLOTS, MAPQ_OVERFLOW = 4096, 1    # LRM_MAPQ_SLOTS, LRM_MAPQ_OVERFLOW (lrm_mapq.flags)
 SEG_RIGHT, SEG_ALIGNED = 1, 2          # lrm_segment.flags
 SPLIT_MIN_DEFAULT = 200                # LRM_SPLIT_MIN_DEFAULT
@@ -167,7 +174,7 @@ class HostIndex(C.Structure):          # lrm_index_host.h
 
 assert C.sizeof(Ui40) == 8 and C.sizeof(Entry) == 24 and C.sizeof(SeqMeta) == 24
 assert C.sizeof(MapOptions) == 76 and C.sizeof(Anchor) == 32 and C.sizeof(Clip) == 8
-assert C.sizeof(Mapq) == 16 and C.sizeof(AlnSummary) == 32 and C.sizeof(BatchExtras) == 24
+assert C.sizeof(GactTable) == 112 and C.sizeof(Mapq) == 16 and C.sizeof(AlnSummary) == 32 and C.sizeof(BatchExtras) == 24
 assert MapOptions.split.offset == 68 and C.sizeof(Segment) == 16 and C.sizeof(SplitDev) == 112 and C.sizeof(SplitOut) == 120
 
 # every symbol include/*.h declares: (restype, argtypes)
@@ -219,6 +226,7 @@ SYMBOLS = {
     "lrm_debug_set_mapq_slots": (C.c_int, [C.c_void_p, C.c_uint32]),
     "lrm_debug_gact_impl": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, GactParams, C.c_int, C.c_void_p,
                                       C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
+    "lrm_debug_gact_jobs": (C.c_int, [C.POINTER(GactTable), GactParams, C.c_int, C.c_uint32, C.c_int, C.c_int]),
     "lrm_index_adopt_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_uint64, C.c_int]),
     "lrm_index_upload_blob": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_uint64, C.c_int]),
     "lrm_index_free": (None, [C.c_void_p]),

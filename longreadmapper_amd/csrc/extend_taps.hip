@@ -1,7 +1,10 @@
-// extend_taps.hip -- debug taps of the extension stage (tests only): one read through the extension kernels
-// (lrm_debug_gact, lrm_debug_gact_impl) or through the anchor scan (lrm_debug_anchor), without an index walk or a workspace
+// extend_taps.hip -- debug taps of the extension stage (tests only): a table of (read, target) jobs through the extension
+// kernels (lrm_debug_gact_jobs; one pair: lrm_debug_gact, lrm_debug_gact_impl) or one read through the anchor scan
+// (lrm_debug_anchor), without an index walk or a workspace
 #include <hip/hip_runtime.h>
 #include <cstdlib>
+#include <cstring>
+#include <vector>
 #include "lrm_hip_util.h"
 #include "extend_stage.h"
 #include "anchor_plan.h"
@@ -37,42 +40,94 @@ extern "C" int lrm_debug_gact(const char *q, int n, const char *d, int m, lrm_ga
     return lrm_debug_gact_impl(q, n, d, m, gp, (int) impl, ops, n_ops, score, device);
 }
 
-extern "C" int lrm_debug_gact_impl(const char *q, int n, const char *d, int m, lrm_gact_params gp, int impl, uint8_t *ops,
-                                   int *n_ops, int *score, int device) {
-    if (!q || !d || !ops || !n_ops || !score || n < 0 || m < 0) { lrm_set_error("bad argument"); return -1; }
+// One job table through the plan and the launch path of the product (lrm_gact_plan, lrm_bs_pack_reads, lrm_gact_launch_jobs),
+// with tlens set: job k is read row k against text[toffs[k], toffs[k] + tlens[k])
+extern "C" int lrm_debug_gact_jobs(const lrm_debug_gact_table *t, lrm_gact_params gp, int impl, uint32_t bs_waves, int count,
+                                   int device) {
+    if (!t || !t->reads || !t->lens || !t->text || !t->toffs || !t->tlens || !t->store || !t->n_ops || !t->score || t->n == 0 ||
+        t->n > (1u << 24)) { lrm_set_error("bad argument"); return -1; }
     if (lrm_require_device(device) || lrm_gact_resolve_params(&gp)) return -1;
-    TapRead t;
-    DevBuf bd, bops, bc, bcpl, btf;
-    lrm_seq_meta hm = {};
-    if (t.upload(q, (uint32_t) n, (uint32_t) m, hm)) return -1;
-    if (bd.alloc((size_t) m + 16) || bops.alloc((size_t) n + m + 16) || bc.alloc(sizeof(LrmDevCounters))) { lrm_set_error("device allocation failed"); return -1; }
-    char *dd = (char *) bd.p;
-    int32_t *dr = t.d_res();
+    const uint64_t n = t->n;
+    uint32_t max_len = 0, ops_len = 0;
+    std::vector<lrm_seq_meta> hm(n);
+    std::vector<int32_t> hr(n, 1);
+    for (uint64_t k = 0; k < n; ++k) {
+        const uint64_t nk = t->lens[k], mk = t->tlens[k];
+        if (nk > t->stride || t->toffs[k] > t->text_len || mk > t->text_len - t->toffs[k] || nk + mk > t->store_stride ||
+            nk > 0x3fffffffu || mk > 0x3fffffffu) {
+            lrm_set_error("job %llu: read, target or op row out of bounds", (unsigned long long) k);
+            return -1;
+        }
+        max_len = nk > max_len ? (uint32_t) nk : max_len;
+        ops_len = (nk > mk ? nk : mk) > ops_len ? (uint32_t) (nk > mk ? nk : mk) : ops_len;
+        hm[k] = lrm_seq_meta{};
+        hm[k].loc = t->toffs[k];
+        if (t->meta_r) hr[k] = t->meta_r[k];
+    }
+    DevBuf reads, lens, tlens, meta, res, nops, score, text, store, bc, bcpl, btf;
+    const uint64_t store_bytes = n * t->store_stride;
+    if (reads.alloc(n * t->stride + 32) || lens.alloc(n * 4) || tlens.alloc(n * 4) || meta.alloc(n * sizeof(lrm_seq_meta)) ||
+        res.alloc(n * 4) || nops.alloc(n * 4) || score.alloc(n * 4) || text.alloc(t->text_len + 16) || store.alloc(store_bytes + 16) ||
+        bc.alloc(sizeof(LrmDevCounters))) { lrm_set_error("device allocation failed"); return -1; }
     LrmDevCounters *dc = (LrmDevCounters *) bc.p;
     HIPCHK(hipMemset(dc, 0, sizeof(LrmDevCounters)));
-    HIPCHK(hipMemcpy(dd, d, (size_t) m, hipMemcpyHostToDevice));
-    LrmGactJobs jobs = {t.d_reads(), 0, t.d_lens(), t.d_lens() + 1, t.d_meta(), dr, dd, nullptr, 1, (uint8_t *) bops.p, 0, dr + 1, dr + 2};
+    HIPCHK(hipMemcpy(reads.p, t->reads, n * t->stride, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(lens.p, t->lens, n * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(tlens.p, t->tlens, n * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(meta.p, hm.data(), n * sizeof(lrm_seq_meta), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(res.p, hr.data(), n * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(nops.p, t->n_ops, n * 4, hipMemcpyHostToDevice));      // what a kernel leaves alone comes back as it went in
+    HIPCHK(hipMemcpy(score.p, t->score, n * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(store.p, t->store, store_bytes, hipMemcpyHostToDevice));
+    if (t->text_len) HIPCHK(hipMemcpy(text.p, t->text, t->text_len, hipMemcpyHostToDevice));
+    LrmGactJobs jobs = {(const char *) reads.p, t->stride, (const uint32_t *) lens.p, (const uint32_t *) tlens.p,
+                        (const lrm_seq_meta *) meta.p, (const int32_t *) res.p, (const char *) text.p, nullptr, n,
+                        (uint8_t *) store.p, t->store_stride, (int32_t *) nops.p, (int32_t *) score.p};
     struct BsGuard { LrmBsScratch s = {}; ~BsGuard() { lrm_bs_scratch_free(&s); } } bs;
     LrmGactPlan plan;
     if (lrm_gact_plan(jobs, gp, impl, true, &plan)) return -1;
     if (plan.kernel == LRM_GACT_BS) {                       // planar image of the text; one that is not pure ACGT plans again
         uint64_t bytes = 0;
-        if (lrm_bs_scratch_alloc(&bs.s, 1, (uint32_t) n, (uint32_t) (n > m ? n : m), &bytes)) return -1;
-        if (bcpl.alloc(lrm_bs_planar_words((uint64_t) m) * 8 + 16) || btf.alloc(4)) { lrm_set_error("device allocation failed"); return -1; }
-        if (lrm_bs_pack_text(dd, (uint64_t) m, (uint64_t *) bcpl.p, (uint32_t *) btf.p, nullptr)) return -1;
+        if (lrm_bs_scratch_alloc(&bs.s, n, max_len, ops_len, &bytes)) return -1;
+        if (bcpl.alloc(lrm_bs_planar_words(t->text_len) * 8 + 16) || btf.alloc(4)) { lrm_set_error("device allocation failed"); return -1; }
+        if (lrm_bs_pack_text((const char *) text.p, t->text_len, (uint64_t *) bcpl.p, (uint32_t *) btf.p, nullptr)) return -1;
         uint32_t tf = 0;
         HIPCHK(hipMemcpy(&tf, btf.p, 4, hipMemcpyDeviceToHost));
         if (!tf) jobs.cpl = (const uint64_t *) bcpl.p;
         else if (lrm_gact_plan(jobs, gp, impl, false, &plan)) return -1;
     }
-    if (lrm_gact_run_jobs(nullptr, jobs, (uint32_t) n, gp, plan, bs.s, dc, 0, nullptr)) return -1;
+    if (plan.kernel == LRM_GACT_BS && lrm_bs_pack_reads(jobs.reads, jobs.stride, jobs.lens, n, max_len, bs.s, nullptr)) return -1;
+    if (lrm_gact_launch_jobs(jobs, gp, plan, &bs.s, dc, bs_waves, count != 0, nullptr)) return -1;
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
-    int32_t hr[3];
-    HIPCHK(hipMemcpy(hr, dr, 12, hipMemcpyDeviceToHost));
-    *n_ops = hr[1];
-    *score = hr[2];
-    if (hr[1] > 0) HIPCHK(hipMemcpy(ops, jobs.store, (size_t) hr[1], hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(t->n_ops, nops.p, n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(t->score, score.p, n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(t->store, store.p, store_bytes, hipMemcpyDeviceToHost));
+    if (t->counters) {
+        LrmDevCounters hc;
+        HIPCHK(hipMemcpy(&hc, dc, sizeof(hc), hipMemcpyDeviceToHost));
+        t->counters[0] = hc.gact_tiles;
+        for (int e = 0; e < LRM_BSC_N; ++e) t->counters[1 + e] = hc.bs_count[e];
+    }
+    return 0;
+}
+
+// ... and its one-pair call
+extern "C" int lrm_debug_gact_impl(const char *q, int n, const char *d, int m, lrm_gact_params gp, int impl, uint8_t *ops,
+                                   int *n_ops, int *score, int device) {
+    if (!q || !d || !ops || !n_ops || !score || n < 0 || m < 0) { lrm_set_error("bad argument"); return -1; }
+    const uint32_t len = (uint32_t) n, tlen = (uint32_t) m;
+    const uint64_t toff = 0;
+    std::vector<uint8_t> row(((size_t) n + m + 19) & ~(size_t) 3);    // a row the bit-sliced kernel's expansion may store words into
+    int32_t hn = 0, hs = 0;
+    lrm_debug_gact_table t = {};
+    t.n = 1; t.reads = q; t.stride = len; t.lens = &len;
+    t.text = d; t.text_len = tlen; t.toffs = &toff; t.tlens = &tlen;
+    t.store = row.data(); t.store_stride = row.size(); t.n_ops = &hn; t.score = &hs;
+    if (lrm_debug_gact_jobs(&t, gp, impl, 0, 0, device)) return -1;
+    *n_ops = hn;
+    *score = hs;
+    if (hn > 0) memcpy(ops, row.data(), (size_t) hn);
     return 0;
 }
 

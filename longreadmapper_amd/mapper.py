@@ -66,6 +66,36 @@ def debug_anchor(index, read, loc, min_len=0):
     return {f: int(getattr(a, f)) for f, _ in a._fields_}
 
 
+def debug_gact_jobs(reads, lens, text, toffs, tlens, gact=DEFAULT_GACT, gact_impl=0, bs_waves=0, counting=False, meta_r=None,
+                    store_stride=None, fill=0, device=0):
+    """lrm_debug_gact_jobs (tests only): read row k against text[toffs[k] : toffs[k] + tlens[k]] as one job table through the
+    extension's plan and launch.  -> dict(ops=(n, store_stride) uint8, rows preset to `fill`; n_ops, score (preset to the
+    same byte); counters: gact_tiles and capi.BS_COUNTERS of the launch)."""
+    reads = np.ascontiguousarray(reads, dtype=np.uint8)
+    lens = np.ascontiguousarray(lens, dtype=np.uint32)
+    text = np.ascontiguousarray(np.frombuffer(bytes(text), dtype=np.uint8))
+    toffs = np.ascontiguousarray(toffs, dtype=np.uint64)
+    tlens = np.ascontiguousarray(tlens, dtype=np.uint32)
+    n, stride = reads.shape
+    assert len(lens) == len(toffs) == len(tlens) == n
+    if store_stride is None:
+        store_stride = (int((lens.astype(np.int64) + tlens).max()) + 3) & ~3
+    ops = np.full((n, store_stride), fill, dtype=np.uint8)
+    n_ops = np.full(n, fill * 0x01010101, dtype=np.uint32).view(np.int32)
+    score = n_ops.copy()
+    counters = np.zeros(1 + len(capi.BS_COUNTERS), dtype=np.uint64)
+    if meta_r is not None:
+        meta_r = np.ascontiguousarray(meta_r, dtype=np.int32)
+        assert len(meta_r) == n
+    t = capi.GactTable(n, reads.ctypes.data, stride, lens.ctypes.data, text.ctypes.data, len(text), toffs.ctypes.data,
+                       tlens.ctypes.data, None if meta_r is None else meta_r.ctypes.data, ops.ctypes.data, store_stride,
+                       n_ops.ctypes.data, score.ctypes.data, counters.ctypes.data)
+    check(lib.lrm_debug_gact_jobs(C.byref(t), capi.GactParams(*gact), gact_impl, bs_waves, int(bool(counting)), device),
+          "lrm_debug_gact_jobs")
+    return dict(ops=ops, n_ops=n_ops, score=score,
+                counters=dict(zip(("gact_tiles",) + capi.BS_COUNTERS, (int(x) for x in counters))))
+
+
 def seed_batch(index, reads, lens, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES):
     """Host buffers in, best[] out (numpy structured array key/val/bucket)."""
     reads = np.ascontiguousarray(reads, dtype=np.uint8)

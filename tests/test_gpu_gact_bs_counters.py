@@ -2,7 +2,7 @@
 control flow, on constructed batches: ONT-profile reads over a random text the test lays out itself (gact_cases.batch_of),
 T = 320, O = 120, W = 128 unless a test says otherwise.
 
-The model (`_wave`) is written from the stream-word formulas of gact_bs_kernels.hip, not from its output: a stream word
+The model (tests/bs_flow.py, `_wave`) is written from the stream-word formulas of gact_bs_kernels.hip, not from its output: a stream word
 of the query whose bit 0 is read base a_hi holds a lane's free-exit point iff 0 <= a_hi - tq < 32, a word of the text
 starting at b_lo iff 0 <= tt - b_lo < 32, for lanes that have a tile -- a lane without one holds none.  Pass 1 starts at
 anti-diagonal S0 (the wavefront's largest tq + tt, rounded up to 32) with the words a_hi = A0, A0 - 32, A0 - 64 and
@@ -21,6 +21,7 @@ import pytest
 import gact_cases
 import gact_ref
 import orc
+from bs_flow import _holds, _tile, _wave, _model  # noqa: F401  (the model, shared with the company tests)
 from longreadmapper_amd import capi, index, mapper
 
 pytestmark = pytest.mark.gpu
@@ -64,100 +65,6 @@ def _reference(pairs, gact):
         assert at + trace.tail == len(ops)
         _REF[(q, d, gact)] = ((score, ops), row)
     return [_REF[p + (gact,)][0] for p in pairs], [_REF[p + (gact,)][1] for p in pairs]
-
-
-def _holds(q_words, d_words, tqs, tts):
-    return any(0 <= a - tq < 32 for a in q_words for tq in tqs) or any(0 <= tt - b < 32 for b in d_words for tt in tts)
-
-
-def _tile(cnt, lanes, gact):
-    """One wave-tile.  lanes: (tq, tt, last_step) of the lanes that have a tile."""
-    T_, O_, W_ = gact
-    narrow = W_ < 128
-    nblk = (2 * (T_ - O_) + BS_K - 1) // BS_K
-    tqs, tts = {l[0] for l in lanes}, {l[1] for l in lanes}
-    S0 = (max(l[0] + l[1] for l in lanes) + BS_K - 1) // BS_K * BS_K
-    nb = min(nblk, S0 // BS_K)
-    A0 = (S0 + 64) >> 1
-    B0 = S0 - A0
-    qw, qnext = [A0, A0 - 32, A0 - 64], A0 - 96
-    dw, dnext = [B0 - 31, B0 + 1, B0 + 33], B0 - 63
-    shq, shd = 0, 31
-    hb = narrow or _holds(qw, dw, tqs, tts)
-    s = S0
-    while True:
-        cnt["bs_pass1_pairs_masked" if hb else "bs_pass1_pairs_plain"] += 1
-        if s == BS_K:
-            break
-        shq += 1
-        if shq == 32:
-            qw, qnext, shq = [qw[1], qw[2], qnext], qnext - 32, 0
-            hb = narrow or _holds(qw, dw, tqs, tts)
-        if shd == 0:
-            dw, dnext, shd = [dnext, dw[0], dw[1]], dnext - 32, 32
-            hb = narrow or _holds(qw, dw, tqs, tts)
-        shd -= 1
-        s -= 2
-    only_full_tiles = tqs == {T_} and tts == {T_}
-    for c in range(nb):
-        if not any(l[2] >= BS_K * c for l in lanes):
-            cnt["bs_blocks_skipped"] += nb - c
-            break
-        a_hi, b_lo = BS_K // 2 * (c + 1) + 31, BS_K // 2 * c - 32
-        full = narrow or _holds([a_hi, a_hi - 32, a_hi - 64], [b_lo, b_lo + 32, b_lo + 64], tqs, tts)
-        assert narrow or not (full and only_full_tiles), "a wave-tile of whole tiles has no free-exit point in pass 2"
-        cnt["bs_blocks_full" if full else "bs_blocks_windowed"] += 1
-    cnt["blocks_per_tile_sum"] += nb
-
-
-def _wave(cnt, take, n_reads, tiles, fenced, gact):
-    """One wavefront to its end.  take(k) -> first of k queue tickets."""
-    lane = [None] * 64                        # [read, next tile] of a lane that has a read
-    exhausted = [False] * 64
-    while True:
-        for l in range(64):
-            if lane[l] and lane[l][1] == len(tiles[lane[l][0]]):
-                lane[l] = None
-        while True:
-            need = [l for l in range(64) if lane[l] is None and not exhausted[l]]
-            if not need:
-                break
-            cnt["bs_refill_rounds"] += 1
-            base = take(len(need))
-            for k, l in enumerate(need):
-                r = base + k
-                if r >= n_reads:
-                    exhausted[l] = True
-                elif r not in fenced:
-                    lane[l] = [r, 0]
-        live = [l for l in range(64) if lane[l]]
-        if not live:
-            return
-        cnt["bs_wave_tiles"] += 1
-        cnt["gact_tiles"] += len(live)
-        _tile(cnt, [tiles[lane[l][0]][lane[l][1]] for l in live], gact)
-        for l in live:
-            lane[l][1] += 1
-
-
-def _model(tiles, fenced, waves, gact):
-    """The whole launch.  One wavefront: the queue is its own.  More (the batch must fit the grid and hold no fenced read):
-    each takes one run of 64 tickets, whichever comes first, and finds the queue empty afterwards."""
-    n = len(tiles)
-    cnt = dict.fromkeys(capi.BS_COUNTERS + ("gact_tiles", "blocks_per_tile_sum"), 0)
-    if waves == 1:
-        head = [0]
-
-        def take(k):
-            head[0] += k
-            return head[0] - k
-        _wave(cnt, take, n, tiles, fenced, gact)
-    else:
-        assert not fenced and n <= 64 * waves
-        for w in range(waves):
-            first = [64 * w]
-            _wave(cnt, lambda k: first.pop() if first else n, n, tiles, fenced, gact)
-    return cnt
 
 
 class _Batch:

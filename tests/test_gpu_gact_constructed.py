@@ -2,9 +2,11 @@
 the specification in executable form; tests/test_gact_constructed_cpu.py shows on the CPU that they are also the
 oracle's.  One process, one device, sequential calls.
 
-Per pair through lrm_debug_gact_impl (the only GPU route for m != n), and in batches through lrm_extend_batch on an
-index of a text the test built, with best[] rows the test wrote: the path the product takes, where the bit-sliced
-kernel reads its target window out of the index's planar text at whatever locus and strand the key names."""
+Per pair through lrm_debug_gact_impl (one job, so the case's own tile decides everything its wavefront decides; the
+same cases beside live neighbours, m != n included, are in tests/test_gpu_gact_company.py through the job-table tap
+lrm_debug_gact_jobs), and in batches through lrm_extend_batch on an index of a text the test built, with best[] rows
+the test wrote: the path the product takes, where the bit-sliced kernel reads its target window out of the index's
+planar text at whatever locus and strand the key names."""
 import ctypes as C
 
 import numpy as np
