@@ -3,8 +3,8 @@
 // 32-bit half of an anti-diagonal, the bookkeeping of one traceback block's walk, and the recompute and walk of a
 // block on the 32 lattice points per anti-diagonal that one lane's walk can reach.  The file compiles for the
 // device (hipcc: v_bitop3_b32, v_bfe_u32, v_alignbit_b32) and as plain C for the host (the same truth tables
-// evaluated bit by bit), so tests/test_gact_bs_circuit.py and tests/test_gact_bs_window.py check on the CPU the
-// very source the kernel runs.
+// evaluated bit by bit), so tests/test_gact_bs_circuit.py, tests/test_gact_bs_window.py and
+// tests/test_gact_bs_walk_recurrence.py check on the CPU the very source the kernel runs.
 #ifndef LRM_GACT_BS_CIRCUIT_H
 #define LRM_GACT_BS_CIRCUIT_H
 #include <stdint.h>
@@ -20,6 +20,7 @@ enum { TA = 0xF0, TB = 0xCC, TC = 0xAA };
 #define BS_ALIGNBIT(hi, lo, sh) __builtin_amdgcn_alignbit((hi), (lo), (sh))      // bits sh .. sh+31 of hi:lo, sh mod 32
 // keeps the compiler from rewriting a value's arithmetic (it would track sums a second time, or turn a 0/1 into selects)
 #define BS_OPAQUE(x) asm("" : "+v"(x))
+#define BS_OPAQUE_S(x) asm("" : "+s"(x))                                          // the same for a wave-uniform value
 #else
 #define BS_FN static inline
 static inline uint32_t bs_lop3_eval(uint32_t a, uint32_t b, uint32_t c, uint32_t table) {
@@ -36,6 +37,7 @@ static inline uint32_t bs_bfe_eval(uint32_t x, uint32_t off, uint32_t width) {
 #define BS_BFE(x, off, width) bs_bfe_eval((x), (off), (width))
 #define BS_ALIGNBIT(hi, lo, sh) ((uint32_t) ((((uint64_t) (hi) << 32) | (uint64_t) (lo)) >> ((sh) & 31u)))
 #define BS_OPAQUE(x) (void) (x)
+#define BS_OPAQUE_S(x) (void) (x)
 #endif
 
 // ----------------------------------------------------------------------------------------
@@ -91,63 +93,73 @@ BS_FN struct BsHalf bs_half_circuit(int bound, int track, uint32_t u1, uint32_t 
 
 struct BsPl { uint32_t lo, hi; };                    // one bit-plane of an anti-diagonal: 64 lattice points
 
-// A lane's place on its path, kept in the form the stop rule and the step test read directly:
+// A lane's place on its path, kept in the form the stop rule reads directly:
 //   na = a - amax, nb = b - bmax: negative while the walk may go on;
 //   ns = a + b - 2(T-O): the anti-diagonal, negative below the one no walk passes.  (Only a read's last tile has
 //        amax or bmax above T-O, so the rule a + b < 2(T-O) binds there alone and can be applied to every lane.)
 // "Still walking" is bit 30 of na & nb & ns; a walk that has stopped gets bit 30 of ns cleared, so ns never again
-// equals a step's anti-diagonal, and `ns == anti-diagonal of this step` is the whole test for "this lane takes a
-// step here".  A lane that never walks starts with ns = 0.
+// equals an anti-diagonal's number.  A lane that never walks starts with ns = 0.
+//
+// Which anti-diagonals of a block a lane steps on (`on`) is a recurrence, not a comparison per step.  Blocks are
+// walked in order, so a lane that is still walking stands on the block's first anti-diagonal or on its second (a
+// diagonal step from the last one of the block before): on = (ns == anti-diagonal) is compared ONCE, for k = 0.
+// From there a gap (n = 1) leads to the next anti-diagonal, a diagonal (n = 0) over it, and an anti-diagonal that
+// was passed over is followed by one the lane is on:
+//     on' = (on ? n : 1)  &  still walking after this step  &  the next anti-diagonal is below 2(T-O)
+// The last term is wave-uniform (`may`, 0 or 1).  With it no lane is `on` from 2(T-O) upwards, so inside a block
+// "still walking" needs na and nb only -- and the block's entry ns, whose bit 30 says whether the lane walked at
+// all when the block began: ns itself is not advanced step by step.  It is brought up to date once, behind the
+// block's last step, from what na and nb moved by (a + b), and loses bit 30 there if the walk has stopped.
 struct BsWalk { int32_t na, nb, ns, score; };
 
 #define BS_WALK_STOPPED_BIT 0x40000000u
-#define BS_WALK_NO_STEP 0x7fffff00u        // the value `ns` is compared with on anti-diagonals from 2(T-O) on
+#define BS_WALK_NO_STEP 0x7fffff00u        // the value `ns` is compared with when the block starts at 2(T-O) or above
 
 BS_FN int bs_walk_running(const struct BsWalk *w) {
     return ((uint32_t) (w->na & w->nb & w->ns) & BS_WALK_STOPPED_BIT) != 0u;
 }
 
-// One anti-diagonal.  k: its number inside the block; sk: that anti-diagonal minus 2(T-O), or BS_WALK_NO_STEP;
-// boff: bmax - (anti-diagonal of the block's first plane) / 2 + 32, so that the lane's lattice point is bit
-// nb + boff - ceil(k/2) of the 64-bit plane.  The codes (0 X, 1 =, 2 I, 3 D) are appended to *bw at bit *e2.
-// the lane's decision (n, g; both 0 where `on` is 0) taken: code appended, place advanced, stop rule applied
-BS_FN void bs_walk_take(struct BsWalk *w, uint32_t on, uint32_t n, uint32_t g, uint32_t *bw, uint32_t *e2) {
+// One anti-diagonal.  k: its number inside the block; *t: the plane bit of the lane's lattice point on it, which is
+// nb + boff - ceil(k/2) with boff = bmax - (anti-diagonal of the block's first plane) / 2 + 32; it is carried from step
+// to step (+1 with every column but 'I', -1 behind every even anti-diagonal) instead of being added up again from nb.
+// The codes (0 X, 1 =, 2 I, 3 D) are appended to *bw at bit *e2.
+// the lane's decision (n, g; both 0 where *on is 0) taken: code appended, place advanced, *on for the next anti-diagonal.
+// may: 1 if that anti-diagonal is below 2(T-O), else 0.  w->ns is the block's entry value throughout.
+BS_FN void bs_walk_take(struct BsWalk *w, int k, uint32_t *on, uint32_t may, uint32_t *t, uint32_t n, uint32_t g,
+                        uint32_t *bw, uint32_t *e2) {
     *bw |= ((n << 1) | g) << *e2;
-    *e2 += on << 1;
-    const uint32_t ia = BS_LOP3(on, n, g, TA & ~(TB & TC));                  // every column but 'D'
-    const uint32_t ib = BS_LOP3(on, n, g, TA & ~(TB & ~TC));                 // every column but 'I'
+    *e2 += *on << 1;
+    const uint32_t ia = BS_LOP3(*on, n, g, TA & ~(TB & TC));                 // every column but 'D'
+    const uint32_t ib = BS_LOP3(*on, n, g, TA & ~(TB & ~TC));                // every column but 'I'
     w->na += (int32_t) ia;
     w->nb += (int32_t) ib;
-    w->ns += (int32_t) (ia + ib);
+    *t = (k & 1) ? *t + ib : *t + ib + 0xFFFFFFFFu;
     const uint32_t in = BS_LOP3((uint32_t) w->na, (uint32_t) w->nb, (uint32_t) w->ns, TA & TB & TC);
-    w->ns = (int32_t) BS_LOP3((uint32_t) w->ns, in, BS_WALK_STOPPED_BIT, TA & (TB | ~TC));
+    const uint32_t nx = BS_LOP3(*on, n, may, (~TA | TB) & TC);               // 0 or 1: the field width that reads `in`
+    *on = BS_BFE(in, 30, nx);
 }
 
-BS_FN void bs_walk_step(struct BsWalk *w, int k, int sk, int32_t boff, struct BsPl N, struct BsPl G, uint32_t *bw,
-                        uint32_t *e2) {
-    uint32_t on = w->ns == sk ? 1u : 0u;
-    BS_OPAQUE(on);
-    BS_OPAQUE(w->nb);
+BS_FN void bs_walk_step(struct BsWalk *w, int k, uint32_t *on, uint32_t may, uint32_t *t, struct BsPl N, struct BsPl G,
+                        uint32_t *bw, uint32_t *e2) {
+    BS_OPAQUE(*on);
+    BS_OPAQUE(*t);
     BS_OPAQUE(*e2);
     BS_OPAQUE(*bw);
-    const uint32_t t = (uint32_t) (w->nb + boff - ((k + 1) >> 1));
-    const int up = t > 31u;
-    const uint32_t n = BS_BFE(up ? N.hi : N.lo, t, on), g = BS_BFE(up ? G.hi : G.lo, t, on);   // width 0: not on this one
-    bs_walk_take(w, on, n, g, bw, e2);
+    const int up = *t > 31u;
+    const uint32_t n = BS_BFE(up ? N.hi : N.lo, *t, *on), g = BS_BFE(up ? G.hi : G.lo, *t, *on);   // width 0: not on this one
+    bs_walk_take(w, k, on, may, t, n, g, bw, e2);
 }
 
-// The same on the block's 32-point window (below): N, G hold plane bits o .. o+31 and boffw = boff - o, so the
-// lane's lattice point is bit nb + boffw - ceil(k/2), always inside the word while the lane steps in this block.
-BS_FN void bs_walk_step_win(struct BsWalk *w, int k, int sk, int32_t boffw, uint32_t N, uint32_t G, uint32_t *bw,
-                            uint32_t *e2) {
-    uint32_t on = w->ns == sk ? 1u : 0u;
-    BS_OPAQUE(on);
-    BS_OPAQUE(w->nb);
+// The same on the block's 32-point window (below): N, G hold plane bits o .. o+31 and *t starts at nb + boff - o, always
+// inside the word while the lane steps in this block.
+BS_FN void bs_walk_step_win(struct BsWalk *w, int k, uint32_t *on, uint32_t may, uint32_t *t, uint32_t N, uint32_t G,
+                            uint32_t *bw, uint32_t *e2) {
+    BS_OPAQUE(*on);
+    BS_OPAQUE(*t);
     BS_OPAQUE(*e2);
     BS_OPAQUE(*bw);
-    const uint32_t t = (uint32_t) (w->nb + boffw - ((k + 1) >> 1));
-    const uint32_t n = BS_BFE(N, t, on), g = BS_BFE(G, t, on);
-    bs_walk_take(w, on, n, g, bw, e2);
+    const uint32_t n = BS_BFE(N, *t, *on), g = BS_BFE(G, *t, *on);
+    bs_walk_take(w, k, on, may, t, n, g, bw, e2);
 }
 
 BS_FN uint32_t bs_popcount32(uint32_t x) {
@@ -161,38 +173,54 @@ BS_FN uint32_t bs_popcount32(uint32_t x) {
 // The whole block: anti-diagonals sbase .. sbase + BS_K - 1 (sbase a multiple of BS_K), lim2 = 2(T-O),
 // boff = bmax - sbase/2 + 32.  Returns the block's codes, *e2 = twice their number.  The score (one per column
 // that is not '=') is counted from the code words afterwards instead of step by step.
-BS_FN int32_t bs_walk_sk(int sbase, int lim2, int k) {
-    const uint32_t sk = (uint32_t) (sbase - lim2 + k);                        // negative, or past the last anti-diagonal
-    return (int32_t) (sk > BS_WALK_NO_STEP ? sk : BS_WALK_NO_STEP);
+struct BsWalkIn { int32_t na, nb; };                 // where the block was entered
+// is the lane on the block's first anti-diagonal?
+BS_FN uint32_t bs_walk_enter(const struct BsWalk *w, struct BsWalkIn *in, int sbase, int lim2) {
+    const uint32_t s0 = (uint32_t) (sbase - lim2);                            // negative, or past the last anti-diagonal
+    in->na = w->na; in->nb = w->nb;
+    return w->ns == (int32_t) (s0 > BS_WALK_NO_STEP ? s0 : BS_WALK_NO_STEP) ? 1u : 0u;
 }
-BS_FN uint64_t bs_walk_join(struct BsWalk *w, const uint32_t *bw, const uint32_t *e, uint32_t *e2) {
+// 1 if anti-diagonal k of the block is below 2(T-O)
+BS_FN uint32_t bs_walk_may(int sbase, int lim2, int k) {
+    int32_t d = sbase + k - lim2;
+    BS_OPAQUE_S(d);                                                          // the sign bit by a scalar shift, not a select per lane
+    return (uint32_t) d >> 31;
+}
+BS_FN uint64_t bs_walk_join(struct BsWalk *w, const struct BsWalkIn *in, const uint32_t *bw, const uint32_t *e, uint32_t *e2) {
     const uint32_t eq = bs_popcount32(BS_LOP3(bw[0], bw[0] >> 1, 0x55555555u, TA & ~TB & TC)) +
                         bs_popcount32(BS_LOP3(bw[1], bw[1] >> 1, 0x55555555u, TA & ~TB & TC));
     *e2 = e[0] + e[1];
     w->score += (int32_t) ((*e2 >> 1) - eq);
+    // the anti-diagonal the lane has reached, and the stop rule on it
+    w->ns += (w->na - in->na) + (w->nb - in->nb);
+    const uint32_t run = BS_LOP3((uint32_t) w->na, (uint32_t) w->nb, (uint32_t) w->ns, TA & TB & TC);
+    w->ns = (int32_t) BS_LOP3((uint32_t) w->ns, run, BS_WALK_STOPPED_BIT, TA & (TB | ~TC));
     return (uint64_t) bw[0] | ((uint64_t) bw[1] << e[0]);                   // e[0] <= 32
 }
 
 BS_FN uint64_t bs_walk_block(struct BsWalk *w, const struct BsPl *N, const struct BsPl *G, int sbase, int lim2, int32_t boff,
                              uint32_t *e2) {
     uint32_t bw[2] = {0u, 0u}, e[2] = {0u, 0u};
-    BS_OPAQUE(boff);
+    struct BsWalkIn in;
+    uint32_t on = bs_walk_enter(w, &in, sbase, lim2);
+    uint32_t t = (uint32_t) (w->nb + boff);
 #pragma unroll
     for (int k = 0; k < BS_K; ++k)
-        bs_walk_step(w, k, bs_walk_sk(sbase, lim2, k), boff, N[k], G[k], &bw[k >= BS_K / 2], &e[k >= BS_K / 2]);
-    return bs_walk_join(w, bw, e, e2);
+        bs_walk_step(w, k, &on, bs_walk_may(sbase, lim2, k + 1), &t, N[k], G[k], &bw[k >= BS_K / 2], &e[k >= BS_K / 2]);
+    return bs_walk_join(w, &in, bw, e, e2);
 }
 
 // on the window planes of bs_win_block, o the window's origin
 BS_FN uint64_t bs_walk_block_win(struct BsWalk *w, const uint32_t *N, const uint32_t *G, int sbase, int lim2, int32_t boff,
                                  uint32_t o, uint32_t *e2) {
     uint32_t bw[2] = {0u, 0u}, e[2] = {0u, 0u};
-    int32_t boffw = boff - (int32_t) o;
-    BS_OPAQUE(boffw);
+    struct BsWalkIn in;
+    uint32_t on = bs_walk_enter(w, &in, sbase, lim2);
+    uint32_t t = (uint32_t) (w->nb + boff) - o;
 #pragma unroll
     for (int k = 0; k < BS_K; ++k)
-        bs_walk_step_win(w, k, bs_walk_sk(sbase, lim2, k), boffw, N[k], G[k], &bw[k >= BS_K / 2], &e[k >= BS_K / 2]);
-    return bs_walk_join(w, bw, e, e2);
+        bs_walk_step_win(w, k, &on, bs_walk_may(sbase, lim2, k + 1), &t, N[k], G[k], &bw[k >= BS_K / 2], &e[k >= BS_K / 2]);
+    return bs_walk_join(w, &in, bw, e, e2);
 }
 
 // ----------------------------------------------------------------------------------------

@@ -74,12 +74,14 @@ __device__ __forceinline__ BsPair bs_q_raw(const BsTile &t, int a_hi) {
     __builtin_memcpy(&p, t.qpl + ((t.i + a_hi - 31) >> 5), sizeof(p));
     return p;
 }
+// SENT: with the one-hot word of the free-exit point (a == tq); a block on the window needs none
+template <bool SENT = true>
 __device__ __forceinline__ BsWord bs_q_conv(const BsTile &t, int a_hi, const BsPair &p) {
     const uint32_t sh = (uint32_t) (t.i + a_hi - 31) & 31u;
     BsWord w;
     w.lo = __builtin_bitreverse32(bs_alignbit((uint32_t) p.b, (uint32_t) p.a, sh));
     w.hi = __builtin_bitreverse32(bs_alignbit((uint32_t) (p.b >> 32), (uint32_t) (p.a >> 32), sh));
-    w.sent = bs_onehot(a_hi - t.tq);
+    w.sent = SENT ? bs_onehot(a_hi - t.tq) : 0u;
     return w;
 }
 __device__ __forceinline__ BsWord bs_q_word(const BsTile &t, int a_hi) { return bs_q_conv(t, a_hi, bs_q_raw(t, a_hi)); }
@@ -89,12 +91,13 @@ __device__ __forceinline__ BsPair bs_d_raw(const BsTile &t, int b_lo) {
     __builtin_memcpy(&p, t.dpl + ((t.dpos + b_lo) >> 5), sizeof(p));
     return p;
 }
+template <bool SENT = true>
 __device__ __forceinline__ BsWord bs_d_conv(const BsTile &t, int b_lo, const BsPair &p) {
     const uint32_t sh = (uint32_t) (t.dpos + b_lo) & 31u;
     BsWord w;
     w.lo = bs_alignbit((uint32_t) p.b, (uint32_t) p.a, sh);
     w.hi = bs_alignbit((uint32_t) (p.b >> 32), (uint32_t) (p.a >> 32), sh);
-    w.sent = bs_onehot(t.tt - b_lo);
+    w.sent = SENT ? bs_onehot(t.tt - b_lo) : 0u;
     return w;
 }
 __device__ __forceinline__ BsWord bs_d_word(const BsTile &t, int b_lo) { return bs_d_conv(t, b_lo, bs_d_raw(t, b_lo)); }
@@ -186,6 +189,10 @@ template <bool HB>
 __device__ __forceinline__ void bs_pass1_pairs(BsState &x, BsStream &st, uint32_t &shq, uint32_t &shd, int &s, int &ck_s,
                                                uint32_t *ckl, int np) {
     BsPl nN, nG;
+    // the two shifts and the anti-diagonal are wave-uniform and are counted in scalar registers here, wherever the code
+    // around this loop keeps them (short of scalar registers it holds them in vector ones: one v_add more per pair)
+    shq = (uint32_t) __builtin_amdgcn_readfirstlane((int) shq);
+    shd = (uint32_t) __builtin_amdgcn_readfirstlane((int) shd);
 #pragma nounroll
     for (int k = 0; k < np; ++k) {
         bs_step<false, HB, false>(x, st, nN, nG);
@@ -205,20 +212,47 @@ __device__ __forceinline__ int bs_wave_max(int v) {
     return __builtin_amdgcn_readfirstlane(v);
 }
 
+__device__ __forceinline__ uint32_t bs_wave_or(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v |= (uint32_t) __shfl_xor((int) v, o);
+    return (uint32_t) __builtin_amdgcn_readfirstlane((int) v);
+}
+
+// Which traceback blocks of a tile run in full width, bit c for block c (at most 32 blocks: T - O <= 512), decided once per
+// tile by the rule bs_any_sentinel applies to a block's stream words: some lane holds a free-exit point in the six words of
+// block c.  Those cover a = BS_H c - 48 .. BS_H c + 47 of the read and b = BS_H c - 32 .. BS_H c + 63 of the text
+// (bs_block_prefetch), so tq puts blocks ceil((tq - 47) / BS_H) .. floor((tq + 48) / BS_H) in full width and tt blocks
+// ceil((tt - 63) / BS_H) .. floor((tt + 32) / BS_H).  BS_NO_EXIT gives an empty range.
+__device__ __forceinline__ uint32_t bs_block_range(int lo, int hi) {      // bits max(lo, 0) .. min(hi, 31)
+    lo = max(lo, 0); hi = min(hi, 31);
+    return lo <= hi ? ((2u << hi) - 1u) & ~((1u << lo) - 1u) : 0u;
+}
+__device__ __forceinline__ uint32_t bs_full_blocks(int tq, int tt, bool narrow) {
+    static_assert(BS_H == 16, "the block ranges below divide by BS_H as a shift by 4");
+    if (narrow) return ~0u;
+    return bs_wave_or(bs_block_range((tq - 32) >> 4, (tq + 48) >> 4) | bs_block_range((tt - 48) >> 4, (tt + 32) >> 4));
+}
+
 // ----------------------------------------------------------------------------------------
 // the kernel: one wavefront per workgroup, lane = read
 // ----------------------------------------------------------------------------------------
-// everything a traceback block needs from memory, fetched one block ahead (during the previous walk)
-struct BsBlockRaw { BsPair q0, q1, q2, d0, d1, d2; uint32_t ck[8]; };
+// everything a traceback block needs from memory, fetched one block ahead (during the previous walk).  The three stream
+// words of a sequence are cut from four consecutive planar words, each fetched once: q[j] is planar word
+// ((i + A0 - 31) >> 5) - 2 + j of the read, d[j] word ((dpos + b_lo) >> 5) + j of the text.
+struct BsBlockRaw { uint64_t q[4], d[4]; uint32_t ck[8]; };
 
 __device__ __forceinline__ void bs_block_prefetch(BsBlockRaw &raw, const BsTile &t, int c, const uint32_t *ckw, int lane) {
     const int A0 = BS_H * (c + 1) + 31, b_lo = BS_H * c - 32;      // anti-diagonal K(c+1)-1: A0, and B0 - K/2
-    raw.q0 = bs_q_raw(t, A0); raw.q1 = bs_q_raw(t, A0 - 32); raw.q2 = bs_q_raw(t, A0 - 64);
-    raw.d0 = bs_d_raw(t, b_lo); raw.d1 = bs_d_raw(t, b_lo + 32); raw.d2 = bs_d_raw(t, b_lo + 64);
+    const uint64_t *qp = t.qpl + (((t.i + A0 - 31) >> 5) - 2), *dp = t.dpl + ((t.dpos + b_lo) >> 5);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { raw.q[e] = qp[e]; raw.d[e] = dp[e]; }
     const uint32_t *cp = ckw + (size_t) c * 512 + lane;      // checkpoint c+1 = state after anti-diagonal K(c+1)
 #pragma unroll
     for (int e = 0; e < 8; ++e) raw.ck[e] = cp[64 * e];
 }
+// the pair of planar words that holds stream word e of the read (e = 0: the one at A0) or of the text (the one at b_lo)
+__device__ __forceinline__ BsPair bs_raw_q(const BsBlockRaw &raw, int e) { return BsPair{raw.q[2 - e], raw.q[3 - e]}; }
+__device__ __forceinline__ BsPair bs_raw_d(const BsBlockRaw &raw, int e) { return BsPair{raw.d[e], raw.d[e + 1]}; }
 
 // COUNT: the counting build (lrm_workspace_set_counting; bookkeeping, never in a timed region) adds up, per wavefront,
 // which path every pass-1 step pair and every pass-2 block took (LrmDevCounters::bs_count, LRM_BSC_*)
@@ -380,39 +414,30 @@ __global__ __launch_bounds__(64) void gact_bs_kernel(const uint64_t *__restrict_
         BsWalk wk = {act ? -amax : 0, act ? -bmax : 0, act ? -lim2 : 0, score};
         BsBlockRaw raw;
         bs_block_prefetch(raw, t, 0, ckw, lane);
+        const uint32_t fullmask = bs_full_blocks(t.tq, t.tt, st.narrow);
         for (int c = 0; c < nb; ++c) {
             if (__ballot(bs_walk_running(&wk)) == 0) { if (COUNT) nc[LRM_BSC_P2_SKIPPED] += (unsigned) (nb - c); break; }
             const int A0 = BS_H * (c + 1) + 31, b_lo = BS_H * c - 32;
-            st.q0 = bs_q_conv(t, A0, raw.q0); st.q1 = bs_q_conv(t, A0 - 32, raw.q1); st.q2 = bs_q_conv(t, A0 - 64, raw.q2);
-            st.d0 = bs_d_conv(t, b_lo, raw.d0); st.d1 = bs_d_conv(t, b_lo + 32, raw.d1); st.d2 = bs_d_conv(t, b_lo + 64, raw.d2);
-            // A free-exit point near the band, or a band narrower than the planes (wave-uniform): the block in full width
-            // with the masked step.  Every other block on the 32 points per anti-diagonal that the lane's walk can reach
-            // from where it stands (gact_bs_circuit.h); lanes that do not walk compute something nobody reads.
-            const bool full = bs_any_sentinel(st);
+            // A free-exit point near the band, or a band narrower than the planes (wave-uniform, bs_full_blocks): the block in
+            // full width with the masked step.  Every other block on the 32 points per anti-diagonal that the lane's walk can
+            // reach from where it stands (gact_bs_circuit.h); lanes that do not walk compute something nobody reads.
+            const bool full = (fullmask >> c) & 1u;
             if (COUNT) { if (full) nc[LRM_BSC_P2_FULL]++; else nc[LRM_BSC_P2_WINDOWED]++; }
             const int32_t boff = bmax - BS_H * c + 32;
-            const uint32_t o = bs_win_origin(wk.nb + boff);
-            BsWinIn win;
+            // walk: the lane's path crosses each anti-diagonal at most once; codes 0 X, 1 =, 2 I, 3 D.
+            // Branch-free: every step runs in all lanes, gated by "my path is on this anti-diagonal".
+            // Either form takes what it needs out of `raw`, fetches the next block's words and checkpoint a block ahead (the
+            // tile's last block fetches itself again: one fetch in either form, no path on which `raw` stays as it is) and
+            // sends the previous block's full code word out behind those loads, which it must not delay.
+            uint32_t e2;
+            uint64_t bw;
             if (full) {
+                st.q0 = bs_q_conv(t, A0, bs_raw_q(raw, 0)); st.q1 = bs_q_conv(t, A0 - 32, bs_raw_q(raw, 1)); st.q2 = bs_q_conv(t, A0 - 64, bs_raw_q(raw, 2));
+                st.d0 = bs_d_conv(t, b_lo, bs_raw_d(raw, 0)); st.d1 = bs_d_conv(t, b_lo + 32, bs_raw_d(raw, 1)); st.d2 = bs_d_conv(t, b_lo + 64, bs_raw_d(raw, 2));
                 x.V1.lo = raw.ck[0]; x.V1.hi = raw.ck[1]; x.V0.lo = raw.ck[2]; x.V0.hi = raw.ck[3];
                 x.H1.lo = raw.ck[4]; x.H1.hi = raw.ck[5]; x.H0.lo = raw.ck[6]; x.H0.hi = raw.ck[7];
                 bs_extract_q<true>(st, 0);
                 bs_extract_d<true>(st, BS_H);
-            } else {
-                bs_win_cut_ck(&win, raw.ck, o);
-                bs_win_cut_seq(win.ql, st.q0.lo, st.q1.lo, st.q2.lo, o); bs_win_cut_seq(win.qh, st.q0.hi, st.q1.hi, st.q2.hi, o);
-                bs_win_cut_seq(win.dl, st.d0.lo, st.d1.lo, st.d2.lo, o); bs_win_cut_seq(win.dh, st.d0.hi, st.d1.hi, st.d2.hi, o);
-            }
-            // the next block's words and checkpoint are fetched a whole block ahead (248 VGPRs: still two wavefronts per SIMD;
-            // behind the recompute, with only the walk in between: 11.72 against 11.57 ms)
-            if (c + 1 < nb) bs_block_prefetch(raw, t, c + 1, ckw, lane);
-            // the previous block's full code word goes out here, behind the loads it must not delay
-            if (has_pend) { cout[widx++] = pend; has_pend = false; }
-            // walk: the lane's path crosses each anti-diagonal at most once; codes 0 X, 1 =, 2 I, 3 D.
-            // Branch-free: every step runs in all lanes, gated by "my path is on this anti-diagonal".
-            uint32_t e2;
-            uint64_t bw;
-            if (full) {
                 BsPl N[BS_K], G[BS_K];
 #pragma unroll
                 for (int k = BS_K - 1; k >= 1; k -= 2) {
@@ -421,8 +446,33 @@ __global__ __launch_bounds__(64) void gact_bs_kernel(const uint64_t *__restrict_
                     bs_step<false, true, true>(x, st, N[k - 1], G[k - 1]);
                     if (k > 1) bs_extract_q<true>(st, (uint32_t) (BS_H - ((k - 1) >> 1)));   // 1 .. K/2-1
                 }
+                if (has_pend) { cout[widx++] = pend; has_pend = false; }
                 bw = bs_walk_block(&wk, N, G, BS_K * c, lim2, boff, &e2);
+                // Beside the 128 words of the planes there is no room for the next block's 24 (256 VGPRs: two wavefronts per
+                // SIMD), so here they are fetched behind the walk.  The addresses are made to depend on the walk's result
+                // through an empty asm; without it the compiler moves the loads up to the block's start and the arm needs
+                // 266 registers (256 VGPRs + 10 AGPRs, one wavefront per SIMD); with the fetch tied between the recompute
+                // and the walk instead, 381.  If a compiler update changes `.vgpr_count` of this kernel, look here first.
+                {
+                    BsTile tn = t;
+                    int ln = lane;
+                    asm volatile("" : "+v"(tn.i), "+v"(tn.dpos), "+v"(ln) : "v"(e2));
+                    bs_block_prefetch(raw, tn, min(c + 1, nb - 1), ckw, ln);
+                }
             } else {
+                const uint32_t o = bs_win_origin(wk.nb + boff);
+                BsWinIn win;
+                {
+                    const BsWord q0 = bs_q_conv<false>(t, A0, bs_raw_q(raw, 0)), q1 = bs_q_conv<false>(t, A0 - 32, bs_raw_q(raw, 1)),
+                                 q2 = bs_q_conv<false>(t, A0 - 64, bs_raw_q(raw, 2));
+                    const BsWord d0 = bs_d_conv<false>(t, b_lo, bs_raw_d(raw, 0)), d1 = bs_d_conv<false>(t, b_lo + 32, bs_raw_d(raw, 1)),
+                                 d2 = bs_d_conv<false>(t, b_lo + 64, bs_raw_d(raw, 2));
+                    bs_win_cut_ck(&win, raw.ck, o);
+                    bs_win_cut_seq(win.ql, q0.lo, q1.lo, q2.lo, o); bs_win_cut_seq(win.qh, q0.hi, q1.hi, q2.hi, o);
+                    bs_win_cut_seq(win.dl, d0.lo, d1.lo, d2.lo, o); bs_win_cut_seq(win.dh, d0.hi, d1.hi, d2.hi, o);
+                }
+                bs_block_prefetch(raw, t, min(c + 1, nb - 1), ckw, lane);
+                if (has_pend) { cout[widx++] = pend; has_pend = false; }
                 uint32_t N[BS_K], G[BS_K];
                 bs_win_block(&win, N, G);
                 bw = bs_walk_block_win(&wk, N, G, BS_K * c, lim2, boff, o, &e2);
