@@ -1,181 +1,14 @@
 """ctypes binding of liblrm_accel.so (include/lrm_accel.h, include/lrm_index_host.h).
 
-This is what a Python host would bind; the structs mirror the reference's own
-(accaln.h / alnmain.h / fmidx.h / lchash.h / histo.h).  There is no fallback: if the
-library is missing the import of this module fails loudly.
+This is what a Python host would bind: the entry points here, the structs (which mirror the
+reference's own: accaln.h / alnmain.h / fmidx.h / lchash.h / histo.h) in records.py.  There is
+no fallback: if the library is missing the import of this module fails loudly.
 """
 import ctypes as C
 import os
 
 from . import _build
-
-u8p = C.POINTER(C.c_uint8)
-u32p = C.POINTER(C.c_uint32)
-u64p = C.POINTER(C.c_uint64)
-i32p = C.POINTER(C.c_int32)
-
-
-class Entry(C.Structure):              # histo.h:21-23
-    _fields_ = [("key", C.c_uint64), ("val", C.c_uint64), ("bucket", C.c_uint64)]
-
-
-class Params(C.Structure):             # alnmain.h:10-13
-    _fields_ = [("batch_size", C.c_uint64), ("seed_len", C.c_uint32), ("thres", C.c_uint32)]
-
-
-class DnaFmi(C.Structure):             # fmidx.h:16-21
-    _fields_ = [("length", C.c_uint64), ("o_len", C.c_uint64), ("csa_len", C.c_uint64),
-                ("c", u64p), ("o", u64p), ("csa", u64p),
-                ("o_ratio", C.c_int), ("csa_ratio", C.c_int), ("bwt", C.c_void_p)]
-
-
-class LcHash(C.Structure):             # lchash.h:16-20
-    _fields_ = [("lc", u64p), ("len", C.c_uint64), ("hlen", C.c_int)]
-
-
-class Ui40(C.Structure):               # sa_use.h:17-20 (8 bytes in RAM)
-    _fields_ = [("low", C.c_uint32), ("high", C.c_uint8)]
-
-
-class SaMem(C.Structure):              # fmidx.h:23-26
-    _fields_ = [("start", C.c_uint64), ("len", C.c_uint64), ("mem", C.POINTER(Ui40))]
-
-
-class MtaEntry(C.Structure):           # accaln.h:67-71 flattened
-    _fields_ = [("name_len", C.c_uint64), ("name", C.c_char_p), ("name_own", C.c_int),
-                ("offset", C.c_uint64), ("seq_len", C.c_size_t)]
-
-
-class SeqMeta(C.Structure):            # alnmain.c:143-148
-    _fields_ = [("loc", C.c_uint64), ("off", C.c_uint64), ("seq_id", C.c_int32), ("strand", C.c_uint8)]
-
-
-class Cigar(C.Structure):              # gact cigar (mutils.c:97-103)
-    _fields_ = [("cigar", u8p), ("n_cigar_op", C.c_int), ("score", C.c_int)]
-
-
-class GactParams(C.Structure):
-    _fields_ = [("T", C.c_int), ("O", C.c_int), ("W", C.c_int)]
-
-
-class IndexOptions(C.Structure):       # lrm_index_options
-    _fields_ = [("struct_size", C.c_uint32), ("sa_sampled", C.c_int32), ("lc_long", C.c_int32),
-                ("lc_long_max", C.c_int32), ("lc_pair", C.c_int32), ("lcx_threshold", C.c_uint32),
-                ("lc_entry_bytes", C.c_uint32), ("lc_core", C.c_int32), ("lc_count_bits", C.c_uint32),
-                ("seed_table", C.c_int32), ("seed_table_len", C.c_uint32), ("seed_table_share", C.c_uint32),
-                ("seed_table_bits", C.c_uint32), ("seed_table_count_bits", C.c_uint32), ("reserved", C.c_uint32 * 2)]
-
-
-class IndexTables(C.Structure):        # lrm_index_tables
-    _fields_ = [("lc_long", C.c_int32), ("lc_pair", C.c_int32), ("lc_entry_bytes", C.c_int32), ("lc_core", C.c_int32),
-                ("seed_table_len", C.c_int32), ("seed_table_share", C.c_int32), ("seed_table_bits", C.c_int32),
-                ("seed_table_slot_bytes", C.c_int32), ("seed_table_count_bits", C.c_int32), ("reserved0", C.c_int32),
-                ("seed_table_side_entries", C.c_uint64), ("derived_bytes", C.c_uint64), ("reserved", C.c_uint64 * 4)]
-
-
-class _SplitWords(C.Structure):        # the last two words of lrm_map_options
-    _fields_ = [("split", C.c_uint32), ("split_min_len", C.c_uint32)]
-
-
-class _MapTail(C.Union):               # ... which were `reserved` until the split fields took them: both names reach them
-    _anonymous_ = ("_split",)
-    _fields_ = [("_split", _SplitWords), ("reserved", C.c_uint32 * 2)]
-
-
-class MapOptions(C.Structure):         # lrm_map_options
-    _anonymous_ = ("_tail",)
-    _fields_ = [("struct_size", C.c_uint32), ("dense_results", C.c_int32), ("gact_impl", C.c_int32),
-                ("seed_rounds", C.c_int32), ("vote_exact_only", C.c_int32), ("slice_reads", C.c_uint32),
-                ("sub_batches", C.c_uint32), ("group_subs", C.c_uint32), ("bs_waves", C.c_uint32),
-                ("cigar_text", C.c_uint32), ("copy_threads", C.c_uint32), ("keep_reads", C.c_uint32), ("anchored", C.c_uint32),
-                ("anchor_min_len", C.c_uint32), ("clip", C.c_uint32), ("clip_penalty", C.c_uint32),
-                ("clip_end_bonus", C.c_uint32), ("_tail", _MapTail)]
-
-
-class Anchor(C.Structure):             # lrm_anchor
-    _fields_ = [("text_pos", C.c_uint64), ("read_pos", C.c_uint32), ("len", C.c_uint32), ("delta", C.c_int32),
-                ("left_ops", C.c_uint32), ("flags", C.c_uint32)]
-
-
-
-
-class Clip(C.Structure):               # lrm_clip
-    _fields_ = [("left", C.c_uint32), ("right", C.c_uint32)]
-
-
-class Segment(C.Structure):            # lrm_segment
-    _fields_ = [("read", C.c_uint32), ("start", C.c_uint32), ("len", C.c_uint32), ("flags", C.c_uint32)]
-
-
-class SplitDev(C.Structure):           # lrm_split_dev (device pointers)
-    _fields_ = [("cap", C.c_uint64), ("seg", C.c_void_p), ("rows", C.c_void_p), ("row_stride", C.c_uint64), ("lens", C.c_void_p),
-                ("best", C.c_void_p), ("store", C.c_void_p), ("store_stride", C.c_uint64), ("n_ops", C.c_void_p),
-                ("score", C.c_void_p), ("meta", C.c_void_p), ("meta_r", C.c_void_p), ("anchor", C.c_void_p), ("clip", C.c_void_p)]
-
-
-class SplitOut(C.Structure):           # lrm_split_out (host pointers)
-    _fields_ = [("cap", C.c_uint64), ("n_seg", C.c_uint64), ("seg", C.c_void_p), ("rows", C.c_void_p), ("row_stride", C.c_uint64),
-                ("lens", C.c_void_p), ("best", C.c_void_p), ("cig", C.c_void_p), ("store", C.c_void_p),
-                ("store_stride", C.c_uint64), ("score", C.c_void_p), ("meta", C.c_void_p), ("meta_r", C.c_void_p),
-                ("anchor", C.c_void_p), ("clip", C.c_void_p)]
-
-
-class Mapq(C.Structure):               # lrm_mapq
-    _fields_ = [("n1", C.c_uint32), ("n2", C.c_uint32), ("radius", C.c_uint32), ("mapq", C.c_uint8), ("phase", C.c_uint8),
-                ("flags", C.c_uint8), ("pad", C.c_uint8)]
-
-
-class AlnSummary(C.Structure):         # lrm_aln_summary
-    _fields_ = [("n_eq", C.c_uint32), ("n_x", C.c_uint32), ("n_ins", C.c_uint32), ("n_del", C.c_uint32),
-                ("ins_runs", C.c_uint32), ("del_runs", C.c_uint32), ("clip_left", C.c_uint32), ("clip_right", C.c_uint32)]
-
-
-class BatchExtras(C.Structure):        # lrm_batch_extras (host pointers)
-    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("mapq_out", C.c_void_p), ("summary_out", C.c_void_p)]
-
-
-class GactTable(C.Structure):          # lrm_debug_gact_table (host pointers)
-    _fields_ = [("n", C.c_uint64), ("reads", C.c_void_p), ("stride", C.c_uint64), ("lens", C.c_void_p), ("text", C.c_void_p),
-                ("text_len", C.c_uint64), ("toffs", C.c_void_p), ("tlens", C.c_void_p), ("meta_r", C.c_void_p),
-                ("store", C.c_void_p), ("store_stride", C.c_uint64), ("n_ops", C.c_void_p), ("score", C.c_void_p),
-                ("counters", C.c_void_p)]
-
-
-MAPQ_SLOTS, MAPQ_OVERFLOW = 4096, 1    # LRM_MAPQ_SLOTS, LRM_MAPQ_OVERFLOW (lrm_mapq.flags)
-SEG_RIGHT, SEG_ALIGNED = 1, 2          # lrm_segment.flags
-SPLIT_MIN_DEFAULT = 200                # LRM_SPLIT_MIN_DEFAULT
-ANCHOR_ANCHORED, ANCHOR_FALLBACK, ANCHOR_NO_LEFT, ANCHOR_LEFT_CLIPPED, ANCHOR_RIGHT_CLIPPED = 1, 2, 4, 8, 16
-ANCHOR_SOFT_LEFT, ANCHOR_SOFT_RIGHT = 32, 64      # end clipping (lrm_map_options.clip)
-ANCHOR_DIAGS = 64                      # LRM_ANCHOR_DIAGS
-
-
-# the counting build of gact_bs_kernel (lrm_stats, after vote_redo_items)
-BS_COUNTERS = ("bs_wave_tiles", "bs_pass1_pairs_masked", "bs_pass1_pairs_plain", "bs_blocks_full", "bs_blocks_windowed",
-               "bs_blocks_skipped", "bs_refill_rounds")
-
-
-class Stats(C.Structure):
-    _fields_ = [("vote_tier2_items", C.c_uint64), ("vote_tier3_items", C.c_uint64),
-                ("reads_decided_phase0", C.c_uint64), ("gact_tiles", C.c_uint64), ("seeds_evaluated", C.c_uint64),
-                ("seed_table_lookups", C.c_uint64), ("seed_rank_requests", C.c_uint64), ("vote_redo_items", C.c_uint64)] + \
-               [(name, C.c_uint64) for name in BS_COUNTERS]
-
-
-class ReadBatch(C.Structure):          # lrm_io_host.h
-    _fields_ = [("n", C.c_uint64), ("stride", C.c_uint64), ("max_len", C.c_uint32), ("seqs", C.c_void_p),
-                ("lens", u32p), ("names", C.POINTER(C.c_char_p)), ("quals", C.POINTER(C.c_char_p)),
-                ("name_arena", C.c_void_p), ("qual_arena", C.c_void_p), ("seqs_borrowed", C.c_int)]
-
-
-class HostIndex(C.Structure):          # lrm_index_host.h
-    _fields_ = [("fmi", DnaFmi), ("lch", LcHash), ("sa", SaMem), ("content", C.c_void_p),
-                ("con_len", C.c_uint64), ("mta", C.POINTER(MtaEntry)), ("mta_len", C.c_int)]
-
-
-assert C.sizeof(Ui40) == 8 and C.sizeof(Entry) == 24 and C.sizeof(SeqMeta) == 24
-assert C.sizeof(MapOptions) == 76 and C.sizeof(Anchor) == 32 and C.sizeof(Clip) == 8
-assert C.sizeof(GactTable) == 112 and C.sizeof(Mapq) == 16 and C.sizeof(AlnSummary) == 32 and C.sizeof(BatchExtras) == 24
-assert MapOptions.split.offset == 68 and C.sizeof(Segment) == 16 and C.sizeof(SplitDev) == 112 and C.sizeof(SplitOut) == 120
+from .records import *  # noqa: F401,F403  (every struct, record dtype and constant of the headers: capi.Entry, capi.META_DT, ...)
 
 # every symbol include/*.h declares: (restype, argtypes)
 SYMBOLS = {
@@ -383,7 +216,14 @@ class LrmError(RuntimeError):
     pass
 
 
+def failure(what="", **fields):
+    """The LrmError of a call that failed: lrm_last_error() behind `what`; fields (rc, n_seg) become its attributes."""
+    e = LrmError("%s: %s" % (what or "liblrm_accel", lib.lrm_last_error().decode(errors="replace")))
+    e.__dict__.update(fields)
+    return e
+
+
 def check(rc, what=""):
     if rc < 0:
-        raise LrmError("%s: %s" % (what or "liblrm_accel", lib.lrm_last_error().decode(errors="replace")))
+        raise failure(what)
     return rc

@@ -1,0 +1,227 @@
+"""Device-resident batches: DeviceMapper runs the stages on buffers that torch tensors own (host buffers: mapper.py)."""
+import ctypes as C
+
+import numpy as np
+
+from . import capi
+from .capi import check, lib
+from .records import (ANCHOR_DT, CLIP_DT, DEFAULT_GACT, DEFAULT_SEED_LEN, DEFAULT_THRES, ENTRY_DT, MAPQ_DT, META_DT, N_KERNELS,
+                      SEGMENT_DT, SUMMARY_DT, store_need, units16)
+
+
+def _records(t, dt):
+    """The rows of a device tensor as a numpy array of the records (dtype dt) they hold."""
+    return t.cpu().numpy().reshape(-1).view(dt)
+
+
+def _timing(ws, stream):
+    """lrm_workspace_timing -> {kernel name: (total ms, launches)}."""
+    ms = np.zeros(N_KERNELS, dtype=np.float64)
+    launches = np.zeros(N_KERNELS, dtype=np.uint64)
+    check(lib.lrm_workspace_timing(ws, ms.ctypes.data, launches.ctypes.data, stream), "lrm_workspace_timing")
+    return {lib.lrm_kernel_name(i).decode(): (float(ms[i]), int(launches[i])) for i in range(N_KERNELS)}
+
+
+class DeviceMapper:
+    """Device-resident batches: torch tensors own the HBM buffers, kernels run on torch's
+    current stream (so torch.cuda.Event brackets them)."""
+
+    def __init__(self, index, n_max, max_len, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT,
+                 device=0, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0, split=False,
+                 split_min_len=0, seg_cap=None, seg_rows=None, mapq=False, summary=False):
+        """summary: extend() runs the alignment summary stage behind the extension, whichever mode (lrm_aln_summary_dev);
+        summary_records(n) and results(n)["summary"] are the SUMMARY_DT records of the last extend call.
+        mapq: seed() runs the mapping-quality stage behind the seed stage (lrm_seed_batch_mapq_dev); mapq_records(n) and
+        results(n)["mapq"] are the MAPQ_DT records of the last seed call.
+        split (needs clip): split() after extend() maps the soft-clipped ends of at least split_min_len bases (0 = 200) as
+        reads of their own (lrm_split_batch_dev), results() returns them as res["split"].  seg_cap: room for that many
+        segments (None: 2 * n_max, every possible one); seg_rows: rows of the segment workspace (None: min(seg_cap, n_max);
+        0: no workspace of its own -- the primary's is used a second time); more segments than rows run in chunks."""
+        import torch
+        self.torch = torch
+        self.index = index
+        self.n_max, self.max_len = n_max, max_len
+        self.seed_len, self.thres, self.gact = seed_len, thres, gact
+        self.dev = torch.device("cuda", device)
+        ws = C.c_void_p()
+        check(lib.lrm_workspace_create(C.byref(ws), index.handle, n_max, max_len, seed_len, thres),
+              "lrm_workspace_create")
+        self.ws = ws
+        anchored = bool(anchored or clip)
+        self.anchored, self.anchor_min_len = anchored, anchor_min_len
+        self.clip_on, self.clip_penalty, self.clip_end_bonus = bool(clip), clip_penalty, clip_end_bonus
+        # anchored: lrm_extend_batch_anchored_dev, results() also returns the lrm_anchor records; clip (implies anchored):
+        # lrm_extend_batch_clipped_dev, results() also returns the lrm_clip records (soft-clipped bases per read)
+        self.store_stride = units16(store_need(max_len, True)) if anchored else store_need(max_len, False)
+        t = self._result_tensors(n_max)
+        self.best, self.store, self.n_ops = t["best"], t["store"], t["n_ops"]
+        self.score, self.meta, self.meta_r = t["score"], t["meta"], t["meta_r"]
+        self.anchor = self._record_tensor(n_max, ANCHOR_DT) if anchored else None
+        self.clip = self._record_tensor(n_max, CLIP_DT, torch.int32) if clip else None
+        self.mapq = self._record_tensor(n_max, MAPQ_DT) if mapq else None
+        self.summary = self._record_tensor(n_max, SUMMARY_DT) if summary else None
+        self.split_on, self.split_min_len, self.ws_seg, self.n_seg = bool(split), split_min_len, None, 0
+        if split:
+            if not clip:
+                raise capi.LrmError("DeviceMapper: split needs clip")
+            cap = self.seg_cap = 2 * n_max if seg_cap is None else seg_cap
+            rows = min(cap, n_max) if seg_rows is None else seg_rows
+            if rows:
+                wseg = C.c_void_p()
+                check(lib.lrm_workspace_create(C.byref(wseg), index.handle, rows, max_len, seed_len, thres), "lrm_workspace_create")
+                self.ws_seg = wseg
+            k = max(cap, 1)
+            self.seg_row_stride = (max_len + 16) // 16 * 16
+            g = self.seg = dict(seg=self._record_tensor(k, SEGMENT_DT, torch.int32),
+                                rows=torch.zeros((k, self.seg_row_stride), dtype=torch.uint8, device=self.dev),
+                                lens=torch.zeros(k, dtype=torch.int32, device=self.dev), **self._result_tensors(k),
+                                anchor=self._record_tensor(k, ANCHOR_DT), clip=self._record_tensor(k, CLIP_DT, torch.int32))
+            self.split_dev = capi.SplitDev(cap, g["seg"].data_ptr(), g["rows"].data_ptr(), self.seg_row_stride, g["lens"].data_ptr(),
+                                           g["best"].data_ptr(), g["store"].data_ptr(), self.store_stride, g["n_ops"].data_ptr(),
+                                           g["score"].data_ptr(), g["meta"].data_ptr(), g["meta_r"].data_ptr(),
+                                           g["anchor"].data_ptr(), g["clip"].data_ptr())
+
+    def _record_tensor(self, rows, dt, word=None):
+        """Device buffer of `rows` records of dtype dt, as columns of `word` (default: bytes)."""
+        word = word or self.torch.uint8
+        return self.torch.zeros((rows, dt.itemsize // word.itemsize), dtype=word, device=self.dev)
+
+    def _result_tensors(self, rows):
+        """The result buffer set of `rows` reads: what an extension call writes, and best[] in front of it."""
+        i32 = dict(dtype=self.torch.int32, device=self.dev)
+        return dict(best=self._record_tensor(rows, ENTRY_DT, self.torch.int64),
+                    store=self.torch.zeros((rows, self.store_stride), dtype=self.torch.uint8, device=self.dev),
+                    n_ops=self.torch.zeros(rows, **i32), score=self.torch.zeros(rows, **i32),
+                    meta=self._record_tensor(rows, META_DT), meta_r=self.torch.zeros(rows, **i32))
+
+    def workspace_bytes(self):
+        return int(lib.lrm_workspace_bytes(self.ws))
+
+    def _stream(self):
+        return C.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
+
+    def seed(self, d_reads, d_lens, n=None):
+        n = d_reads.shape[0] if n is None else n
+        p = capi.Params(n, self.seed_len, self.thres)
+        if self.mapq is not None:
+            check(lib.lrm_seed_batch_mapq_dev(self.index.handle, self.ws, d_reads.data_ptr(), d_reads.stride(0),
+                                              d_lens.data_ptr(), n, self.max_len, p, self.best.data_ptr(),
+                                              self.mapq.data_ptr(), self._stream()), "lrm_seed_batch_mapq_dev")
+            return
+        check(lib.lrm_seed_batch_dev(self.index.handle, self.ws, d_reads.data_ptr(), d_reads.stride(0),
+                                     d_lens.data_ptr(), n, self.max_len, p, self.best.data_ptr(), self._stream()),
+              "lrm_seed_batch_dev")
+
+    def mapq_records(self, n):
+        """The lrm_mapq records (MAPQ_DT) of the last seed() -- DeviceMapper(..., mapq=True)."""
+        assert self.mapq is not None
+        return _records(self.mapq[:n], MAPQ_DT)
+
+    def summary_records(self, n):
+        """The lrm_aln_summary records (SUMMARY_DT) of the last extend() -- DeviceMapper(..., summary=True)."""
+        assert self.summary is not None
+        return _records(self.summary[:n], SUMMARY_DT)
+
+    def extend(self, d_reads, d_lens, n=None):
+        n = d_reads.shape[0] if n is None else n
+        self._extend(d_reads, d_lens, n)
+        if self.summary is not None:
+            check(lib.lrm_aln_summary_dev(self.index.handle, self.store.data_ptr(), self.store_stride, self.n_ops.data_ptr(),
+                                          self.score.data_ptr(), self.meta_r.data_ptr(), n, self.summary.data_ptr(),
+                                          self._stream()), "lrm_aln_summary_dev")
+
+    def _extend(self, d_reads, d_lens, n):
+        args = (self.index.handle, self.ws, d_reads.data_ptr(), d_reads.stride(0), d_lens.data_ptr(), n, self.max_len,
+                self.best.data_ptr(), capi.GactParams(*self.gact), self.store.data_ptr(), self.store_stride, self.n_ops.data_ptr(),
+                self.score.data_ptr(), self.meta.data_ptr(), self.meta_r.data_ptr())
+        if self.clip_on:
+            check(lib.lrm_extend_batch_clipped_dev(*args, self.anchor.data_ptr(), self.anchor_min_len, self.clip_penalty,
+                                                   self.clip_end_bonus, self.clip.data_ptr(), self._stream()),
+                  "lrm_extend_batch_clipped_dev")
+        elif self.anchored:
+            check(lib.lrm_extend_batch_anchored_dev(*args, self.anchor.data_ptr(), self.anchor_min_len, self._stream()),
+                  "lrm_extend_batch_anchored_dev")
+        else:
+            check(lib.lrm_extend_batch_dev(*args, self._stream()), "lrm_extend_batch_dev")
+
+    def split(self, d_reads, d_lens, n=None):
+        """lrm_split_batch_dev after extend() on the same stream -> number of segments (the call waits for that count).
+        More than seg_cap raise LrmError with .rc == -3 and .n_seg."""
+        assert self.split_on
+        n = d_reads.shape[0] if n is None else n
+        k = C.c_uint64()
+        rc = lib.lrm_split_batch_dev(self.index.handle, self.ws_seg or self.ws, d_reads.data_ptr(), d_reads.stride(0), d_lens.data_ptr(),
+                                     n, self.clip.data_ptr(), capi.Params(n, self.seed_len, self.thres), capi.GactParams(*self.gact),
+                                     self.anchor_min_len, self.clip_penalty, self.clip_end_bonus, self.split_min_len,
+                                     C.byref(self.split_dev), C.byref(k), self._stream())
+        self.n_seg = int(k.value) if rc >= 0 else 0
+        if rc < 0:
+            raise capi.failure("lrm_split_batch_dev", rc=rc, n_seg=int(k.value))
+        return self.n_seg
+
+    def seg_timing(self):
+        """timing() of the segment workspace (the split stage's own kernels are in the revcomp_kernel slot)."""
+        return _timing(self.ws_seg or self.ws, self._stream())
+
+    def split_results(self):
+        """The outputs of the last split() as numpy arrays (same keys as split_batch, `ops` in rows)."""
+        k, g = self.n_seg, self.seg
+        h = {"ops" if name == "store" else name: t[:k].cpu().numpy() for name, t in g.items()}
+        for name, dt in (("seg", SEGMENT_DT), ("best", ENTRY_DT), ("meta", META_DT), ("anchor", ANCHOR_DT), ("clip", CLIP_DT)):
+            h[name] = h[name].reshape(-1).view(dt)
+        h["lens"] = h["lens"].view(np.uint32)
+        return dict(h, is_text=False)
+
+    def stats(self):
+        st = capi.Stats()
+        check(lib.lrm_workspace_stats(self.ws, C.byref(st), self._stream()), "lrm_workspace_stats")
+        return {name: int(getattr(st, name)) for name, _ in capi.Stats._fields_}
+
+    def debug_vote_results(self, n):
+        """lrm_debug_vote_results: (n, seed_len + 1, 6) uint64 -- key1, val1, bucket1, key2, val2, bucket2 of every (read, phase)
+        of the last seed() call as the vote kernels left them; only the phases that call evaluated are meaningful."""
+        out = np.zeros((n, self.seed_len + 1, 6), dtype=np.uint64)
+        check(lib.lrm_debug_vote_results(self.ws, n, out.ctypes.data, self._stream()), "lrm_debug_vote_results")
+        return out
+
+    def set_counting(self, enable=True):
+        """The next seed and extend calls run the counting builds of the seed kernel (stats(): requests of the device
+        layout) and of the bit-sliced extension kernel (stats(): bs_* path counts)."""
+        check(lib.lrm_workspace_set_counting(self.ws, int(enable)), "lrm_workspace_set_counting")
+
+    def set_timing(self, enable=True):
+        check(lib.lrm_workspace_set_timing(self.ws, int(enable)), "lrm_workspace_set_timing")
+
+    def timing(self):
+        """-> {kernel name: (total ms, launches)} accumulated since set_timing / the last call."""
+        return _timing(self.ws, self._stream())
+
+    def results(self, n):
+        """Copy the outputs of the last seed+extend to numpy (host)."""
+        res = dict(best=_records(self.best[:n], ENTRY_DT), ops=self.store[:n].cpu().numpy(), n_ops=self.n_ops[:n].cpu().numpy(),
+                   score=self.score[:n].cpu().numpy(), meta=_records(self.meta[:n], META_DT), meta_r=self.meta_r[:n].cpu().numpy())
+        if self.anchored:
+            res["anchor"] = _records(self.anchor[:n], ANCHOR_DT)
+        if self.clip_on:
+            res["clip"] = _records(self.clip[:n], CLIP_DT)
+        if self.split_on:
+            res["split"] = self.split_results()
+        if self.mapq is not None:
+            res["mapq"] = self.mapq_records(n)
+        if self.summary is not None:
+            res["summary"] = self.summary_records(n)
+        return res
+
+    def close(self):
+        if getattr(self, "ws_seg", None):
+            lib.lrm_workspace_free(self.ws_seg)
+            self.ws_seg = None
+        if self.ws:
+            lib.lrm_workspace_free(self.ws)
+            self.ws = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -1,0 +1,129 @@
+"""The host text stage either side of the hot path (include/lrm_io_host.h): the FASTA / FASTQ batch reader, the SAM and
+PAF formatters and the whole-file flows (lrm_accaln*).  Record arrays are numpy arrays of the records.py dtypes."""
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import capi
+from .capi import lib
+
+
+class Reader:
+    """lrm_reader: `with Reader(path) as rd: n = rd.next(1000)`; rd.batch is the lrm_read_batch of the last next() that
+    returned reads.  It is freed by the following next(), by free() and on the way out."""
+
+    def __init__(self, path):
+        self.handle, self.batch = C.c_void_p(), None
+        capi.check(lib.lrm_reader_open(C.byref(self.handle), os.fsencode(path)), "lrm_reader_open")
+
+    def next(self, n, into=None, into_bytes=None):
+        """Up to n reads -> their number (0: end of file; < 0: the parser's code, text in lrm_last_error).  into: a uint8
+        array that takes the sequences when they fit its into_bytes (default: all of it) -- lrm_reader_next_into."""
+        self.free()
+        b = capi.ReadBatch()
+        if into is None:
+            got = lib.lrm_reader_next(self.handle, n, C.byref(b))
+        else:
+            got = lib.lrm_reader_next_into(self.handle, n, C.byref(b), into.ctypes.data, into.nbytes if into_bytes is None else into_bytes)
+        if got > 0:
+            self.batch = b
+        return got
+
+    def free(self):
+        if self.batch is not None:
+            lib.lrm_read_batch_free(C.byref(self.batch))
+            self.batch = None
+
+    def close(self):
+        self.free()
+        if self.handle:
+            lib.lrm_reader_close(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def mta_table(entries):
+    """lrm_mta_entry array of (name, offset, seq_len) tuples; the array keeps the names alive."""
+    mta = (capi.MtaEntry * len(entries))()
+    for m, (name, offset, seq_len) in zip(mta, entries):
+        name = name.encode() if isinstance(name, str) else name
+        m.name_len, m.name, m.offset, m.seq_len = len(name), name, offset, seq_len
+    return mta
+
+
+def cigar_table(addr, n_ops, score):
+    """lrm_cigar records (CIGAR_DT, at least one) of alignments whose bytes start at the addresses `addr`."""
+    cig = np.zeros(max(len(addr), 1), dtype=capi.CIGAR_DT)
+    k = len(addr)
+    cig["cigar"][:k], cig["n_cigar_op"][:k], cig["score"][:k] = addr, n_ops, score
+    return cig
+
+
+def cigar_array(ops_list, scores, texts=None):
+    """lrm_cigar records of alignments given as op byte strings.  texts: the run-length CIGAR text of each, which the
+    records then point to (the cigar_text layout: n_cigar_op stays the number of columns).  -> (records, the buffer they
+    point into, which the caller keeps for as long as the records are in use)."""
+    rows = [bytes(r) + b"\0" for r in (ops_list if texts is None else texts)]
+    blob = np.frombuffer(b"".join(rows) + b"\0", dtype=np.uint8)
+    starts = np.cumsum([0] + [len(r) for r in rows[:-1]], dtype=np.uint64)[:len(rows)]
+    return cigar_table(starts + np.uint64(blob.ctypes.data), [len(o) for o in ops_list], scores), blob
+
+
+def _text(entry, *args):
+    """What a formatter returned as str (None where it refused: lrm_last_error)."""
+    length = C.c_uint64()
+    p = entry(*args, C.byref(length))
+    if not p:
+        return None
+    try:
+        return C.string_at(p, length.value).decode()
+    finally:
+        lib.lrm_free(p)
+
+
+def _at(a):
+    return None if a is None else a.ctypes.data if isinstance(a, np.ndarray) else C.byref(a)
+
+
+def sam_header(mta, rg_id):
+    return _text(lib.lrm_sam_header, mta, len(mta), rg_id)
+
+
+def sam_format(batch, mta, cig, score, meta, meta_r, n, *, is_text=0, keep=0, split=None, mapq=None, entry=None):
+    """The SAM records of a batch: lrm_sam_format_mapq with mapq (MAPQ_DT records), lrm_sam_format_split with split (an
+    lrm_split_out), run-length text (is_text) or untouched reads (keep), else lrm_sam_format; entry names one of the three
+    instead (the later ones take NULL for what the earlier ones lack)."""
+    entry = entry or ("lrm_sam_format_mapq" if mapq is not None else
+                      "lrm_sam_format_split" if split is not None or is_text or keep else "lrm_sam_format")
+    args = (C.byref(batch), mta, len(mta), _at(cig), _at(score), _at(meta), _at(meta_r), n)
+    assert entry == "lrm_sam_format_mapq" or mapq is None, "%s takes no mapq records" % entry
+    assert entry != "lrm_sam_format" or (split is None and not is_text and not keep), "lrm_sam_format takes op bytes and no split"
+    if entry != "lrm_sam_format":
+        args += (int(is_text), int(keep), _at(split)) + ((_at(mapq),) if entry == "lrm_sam_format_mapq" else ())
+    return _text(getattr(lib, entry), *args)
+
+
+def paf_format(batch, mta, cig, score, meta, meta_r, n, summary, *, is_text=0, mapq=None):
+    """lrm_paf_format: the PAF lines of a batch from its SUMMARY_DT records [and MAPQ_DT records]."""
+    return _text(lib.lrm_paf_format, C.byref(batch), mta, len(mta), _at(cig), _at(score), _at(meta), _at(meta_r), n, int(is_text),
+                 _at(summary), _at(mapq))
+
+
+def accaln(genome, reads, out, batch_size, seed_len=20, thres=300, gact=(0, 0, 0), device=0, rg_id=1, options=None, mapq=0, paf=False):
+    """A whole reads file to SAM (paf: PAF) -> (total, valid): lrm_accaln_paf, or the first of lrm_accaln_mapq / lrm_accaln_opt
+    / lrm_accaln that takes what was given (options: an lrm_map_options).  A failure raises LrmError with the code in .rc."""
+    total, valid = C.c_uint64(), C.c_uint64()
+    head = (os.fsencode(genome), os.fsencode(reads), os.fsencode(out), capi.Params(batch_size, seed_len, thres), capi.GactParams(*gact), device)
+    counts, opt = (C.byref(total), C.byref(valid)), _at(options)
+    entry, tail = (("lrm_accaln_paf", (*counts, opt, mapq)) if paf else ("lrm_accaln_mapq", (rg_id, *counts, opt, mapq)) if mapq else
+                   ("lrm_accaln_opt", (rg_id, *counts, opt)) if options is not None else ("lrm_accaln", (rg_id, *counts)))
+    rc = getattr(lib, entry)(*head, *tail)
+    if rc < 0:
+        raise capi.failure(entry, rc=rc)
+    return int(total.value), int(valid.value)

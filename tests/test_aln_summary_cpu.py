@@ -14,7 +14,7 @@ import anchored_cases
 import clip_ref
 import gact_cases
 import orc
-from longreadmapper_amd import capi, mapper
+from longreadmapper_amd import capi, mapper, textio
 from longreadmapper_amd.capi import lib
 
 
@@ -101,27 +101,15 @@ def test_clips_and_nm_after_end_clipping(P, B):
 def _batch(tmp_path, recs):
     p = tmp_path / "r.fq"
     p.write_bytes(b"".join(b"@%s\n%s\n+\n%s\n" % (nm, s, q) for nm, s, q in recs))
-    rd = C.c_void_p()
-    capi.check(lib.lrm_reader_open(C.byref(rd), str(p).encode()))
-    b = capi.ReadBatch()
-    assert lib.lrm_reader_next(rd, 100, C.byref(b)) == len(recs)
-    return rd, b
-
-
-def _cigars(rows, n_ops, scores):
-    keep = [C.create_string_buffer(o + b"\0") for o in rows]
-    cig = (capi.Cigar * len(rows))()
-    for i in range(len(rows)):
-        cig[i].cigar, cig[i].n_cigar_op, cig[i].score = C.cast(keep[i], capi.u8p), n_ops[i], int(scores[i])
-    return cig, keep
+    rd = textio.Reader(p)
+    assert rd.next(100) == len(recs)
+    return rd, rd.batch
 
 
 def test_paf_lines(tmp_path):
     rng = np.random.default_rng(12)
-    mta = (capi.MtaEntry * 2)()
     tn = ((b"chrA", 0, 100000), (b"chrB", 200000, 50000))
-    for i, (nm, off, ln) in enumerate(tn):
-        mta[i].name_len, mta[i].name, mta[i].offset, mta[i].seq_len = len(nm), nm, off, ln
+    mta = textio.mta_table(tn)
     # 0: forward, clipped on the left only; 1: reverse, clipped on the left (of the ops) only; 2: unmapped (no locus);
     # 3: reverse, clipped on the right only, gaps; 4: unmapped (score -1); 5: forward, 'S' only: a zero denominator; 6: forward, gaps
     ops = [b"S" * 100 + b"=" * 500 + b"X" + b"=" * 299,
@@ -147,15 +135,11 @@ def test_paf_lines(tmp_path):
     mq = np.zeros(7, dtype=mapper.MAPQ_DT)
     mq["n1"], mq["n2"], mq["mapq"] = [31, 12, 0, 9, 5, 3, 40], [2, 12, 0, 0, 1, 3, 0], [56, 0, 0, 54, 33, 0, 60]
     texts = [ref.sam_ref.rle(o).encode() for o in ops]
-    ln_out = C.c_uint64()
 
     def fmt(is_text, mqp):
-        cig, keep = _cigars(texts if is_text else ops, [len(o) for o in ops], score)
-        t = lib.lrm_paf_format(C.byref(b), mta, 2, C.cast(cig, C.c_void_p), score.ctypes.data, meta.ctypes.data, meta_r.ctypes.data, 7,
-                               int(is_text), sums.ctypes.data, mqp, C.byref(ln_out))
-        assert t
-        got = C.string_at(t, ln_out.value).decode()
-        lib.lrm_free(t)
+        cig, keep = textio.cigar_array(ops, score, texts if is_text else None)
+        got = textio.paf_format(b, mta, cig, score, meta, meta_r, 7, sums, is_text=is_text, mapq=mqp)
+        assert got is not None
         return got
 
     for with_mq in (False, True):
@@ -163,7 +147,7 @@ def test_paf_lines(tmp_path):
                                     int(meta["off"][i]), ops[i], int(score[i]), int(meta_r[i]),
                                     (int(mq["mapq"][i]), int(mq["n1"][i]), int(mq["n2"][i])) if with_mq else None) for i in range(7))
         for is_text in (False, True):
-            assert fmt(is_text, mq.ctypes.data if with_mq else None) == want, (with_mq, is_text)
+            assert fmt(is_text, mq if with_mq else None) == want, (with_mq, is_text)
     lines = [l.split("\t") for l in want.splitlines()]
     assert [l[0] for l in lines] == ["q0", "q1", "q3", "q5", "q6"]                   # the unmapped reads print nothing
     # the lines by hand: a swapped qstart / qend on the reverse strand would show
@@ -173,10 +157,8 @@ def test_paf_lines(tmp_path):
     assert lines[2][12:17] == ["NM:i:8", "ED:i:8", "tp:A:P", "de:f:%.4f" % (5 / 251), "cg:Z:100M3D50M2I1D98M50S"]
     assert lines[3][1:11] == ["120", "120", "120", "+", "chrA", "100000", "77", "77", "0", "0"] and lines[3][15] == "de:f:0.0000"
     assert lines[4][12:19] == ["NM:i:8", "ED:i:8", "tp:A:P", "de:f:%.4f" % (2 / 94), "cg:Z:10M1I10M7I72M", "v1:i:40", "v2:i:0"]
-    assert lib.lrm_paf_format(C.byref(b), mta, 2, None, score.ctypes.data, meta.ctypes.data, meta_r.ctypes.data, 7, 0, None, None,
-                              C.byref(ln_out)) is None            # the records are required
-    lib.lrm_read_batch_free(C.byref(b))
-    lib.lrm_reader_close(rd)
+    assert textio.paf_format(b, mta, None, score, meta, meta_r, 7, None) is None            # the records are required
+    rd.close()
 
 
 def test_struct_sizes_and_entry_points():
@@ -196,8 +178,7 @@ def test_struct_sizes_and_entry_points():
 def test_paf_flow_refuses_split_reads(tmp_path):
     """Refused before anything is opened: no index files, no device needed."""
     opt = capi.map_options(anchored=1, clip=1, split=1)
-    total, valid = C.c_uint64(), C.c_uint64()
-    rc = lib.lrm_accaln_paf(b"/nonexistent/ref.fa", b"/nonexistent/reads.fq", str(tmp_path / "o.paf").encode(), capi.Params(64, 20, 300),
-                            capi.GactParams(0, 0, 0), 0, C.byref(total), C.byref(valid), C.byref(opt), 0)
-    assert rc == -1 and b"split" in lib.lrm_last_error()
+    with pytest.raises(capi.LrmError) as refused:
+        textio.accaln("/nonexistent/ref.fa", "/nonexistent/reads.fq", tmp_path / "o.paf", 64, options=opt, paf=True)
+    assert refused.value.rc == -1 and b"split" in lib.lrm_last_error()
     assert not (tmp_path / "o.paf").exists()

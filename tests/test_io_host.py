@@ -8,28 +8,25 @@ import pytest
 
 import orc
 import sam_ref
-from longreadmapper_amd import capi, mapper
+from longreadmapper_amd import mapper, textio
 from longreadmapper_amd.capi import lib
 
 
 def _read_all(path, batch):
-    rd = C.c_void_p()
-    capi.check(lib.lrm_reader_open(C.byref(rd), str(path).encode()), "open")
     out = []
-    while True:
-        b = capi.ReadBatch()
-        n = lib.lrm_reader_next(rd, batch, C.byref(b))
-        assert n >= 0, lib.lrm_last_error()
-        if n == 0:
-            break
-        assert b.stride == b.max_len + 1
-        raw = np.ctypeslib.as_array(C.cast(b.seqs, C.POINTER(C.c_uint8)), shape=(n, b.stride)).copy()
-        for i in range(n):
-            ln = b.lens[i]
-            assert not raw[i, ln:].any()                                   # NUL padded (calloc, alnmain.c:94)
-            out.append((b.names[i].decode(), bytes(raw[i, :ln]), b.quals[i], n))
-        lib.lrm_read_batch_free(C.byref(b))
-    lib.lrm_reader_close(rd)
+    with textio.Reader(path) as rd:
+        while True:
+            n = rd.next(batch)
+            assert n >= 0, lib.lrm_last_error()
+            if n == 0:
+                break
+            b = rd.batch
+            assert b.stride == b.max_len + 1
+            raw = np.ctypeslib.as_array(C.cast(b.seqs, C.POINTER(C.c_uint8)), shape=(n, b.stride)).copy()
+            for i in range(n):
+                ln = b.lens[i]
+                assert not raw[i, ln:].any()                                   # NUL padded (calloc, alnmain.c:94)
+                out.append((b.names[i].decode(), bytes(raw[i, :ln]), b.quals[i], n))
     return out
 
 
@@ -53,11 +50,8 @@ def test_fastq_fasta_reader(tmp_path):
     assert [(g[0], g[1], g[2]) for g in _read_all(fa, 10)] == [("a", b"ACGTAC", None), ("b", b"TTTT", None)]
     bad = tmp_path / "bad.fq"
     bad.write_bytes(b"@x\nACGT\n+\nII\n")
-    rd = C.c_void_p()
-    capi.check(lib.lrm_reader_open(C.byref(rd), str(bad).encode()))
-    b = capi.ReadBatch()
-    assert lib.lrm_reader_next(rd, 4, C.byref(b)) == -2                      # kseq: -2 truncated quality
-    lib.lrm_reader_close(rd)
+    with textio.Reader(bad) as rd:
+        assert rd.next(4) == -2                                              # kseq: -2 truncated quality
 
 
 @pytest.mark.parametrize("batch", [1, 7, 1000, 100000])
@@ -94,20 +88,17 @@ def test_parallel_fastq_parser(tmp_path, batch, trailing_newline):
         gz.write_bytes(gzip.compress(txt, 1))
         assert [(g[0], g[1], g[2]) for g in _read_all(gz, batch)] == want
         # sequences into a caller's buffer, too small for the second call
-        rd = C.c_void_p()
-        capi.check(lib.lrm_reader_open(C.byref(rd), str(p).encode()))
         mine = np.full(1000 * 9001, 0x55, dtype=np.uint8)
-        b = capi.ReadBatch()
-        assert lib.lrm_reader_next_into(rd, 1000, C.byref(b), mine.ctypes.data, mine.nbytes) == 1000
-        assert b.seqs_borrowed == 1 and b.seqs == mine.ctypes.data
-        rows = mine[:1000 * b.stride].reshape(1000, b.stride)
-        for i in (0, 1, 17, 999):
-            assert bytes(rows[i, :b.lens[i]]) == recs[i][1] and not rows[i, b.lens[i]:].any()
-        lib.lrm_read_batch_free(C.byref(b))
-        assert lib.lrm_reader_next_into(rd, 1000, C.byref(b), mine.ctypes.data, 10) == 1000
-        assert b.seqs_borrowed == 0 and b.seqs != mine.ctypes.data
-        lib.lrm_read_batch_free(C.byref(b))
-        lib.lrm_reader_close(rd)
+        with textio.Reader(p) as rd:
+            assert rd.next(1000, into=mine) == 1000
+            b = rd.batch
+            assert b.seqs_borrowed == 1 and b.seqs == mine.ctypes.data
+            rows = mine[:1000 * b.stride].reshape(1000, b.stride)
+            for i in (0, 1, 17, 999):
+                assert bytes(rows[i, :b.lens[i]]) == recs[i][1] and not rows[i, b.lens[i]:].any()
+            assert rd.next(1000, into=mine, into_bytes=10) == 1000
+            b = rd.batch
+            assert b.seqs_borrowed == 0 and b.seqs != mine.ctypes.data
 
 
 def test_parser_falls_back_in_the_middle_of_a_file(tmp_path):
@@ -138,42 +129,23 @@ def test_parse_cigar_rle():
 
 
 def test_sam_header_and_records(tmp_path):
-    names = [b"chrA", b"contig_two"]
-    mta = (capi.MtaEntry * 2)()
-    for i, (nm, off, ln) in enumerate(zip(names, (0, 2000), (1000, 321))):
-        mta[i].name_len, mta[i].name, mta[i].offset, mta[i].seq_len = len(nm), nm, off, ln
-    ln_out = C.c_uint64()
-    h = lib.lrm_sam_header(mta, 2, 1234567, C.byref(ln_out))
-    txt = C.string_at(h, ln_out.value).decode()
-    lib.lrm_free(h)
     pymta = [("chrA", 0, 1000), ("contig_two", 2000, 321)]
-    assert txt == sam_ref.header(pymta, 1234567)
+    mta = textio.mta_table(pymta)
+    assert textio.sam_header(mta, 1234567) == sam_ref.header(pymta, 1234567)
 
     p = tmp_path / "r.fq"
     p.write_bytes(b"@q0\nACGTAC\n+\nIIIIII\n@q1\nGGGG\n+\n####\n@q2\nTT\n+\n!!\n@q3\nACG\n+\n;;;\n")
-    rd = C.c_void_p()
-    capi.check(lib.lrm_reader_open(C.byref(rd), str(p).encode()))
-    b = capi.ReadBatch()
-    assert lib.lrm_reader_next(rd, 10, C.byref(b)) == 4
+    rd = textio.Reader(p)
+    assert rd.next(10) == 4
     ops = [b"==X=I=", b"=D==="[:5], b"", b"==="]
-    store = np.zeros((4, 12), dtype=np.uint8)
-    cig = (capi.Cigar * 4)()
-    for i, o in enumerate(ops):
-        store[i, :len(o)] = np.frombuffer(o, dtype=np.uint8) if o else []
-        cig[i].cigar = C.cast(store[i].ctypes.data, capi.u8p)
-        cig[i].n_cigar_op = len(o)
     score = np.array([2, 1, -1, 0], dtype=np.int32)
+    cig, _ops = textio.cigar_array(ops, score)
     meta_r = np.array([1, 1, 1, 0], dtype=np.int32)
     meta = np.zeros(4, dtype=mapper.META_DT)
     meta["seq_id"] = [0, 1, 0, -1]
     meta["off"] = [41, 7, 3, 0]
     meta["strand"] = [0, 1, 0, 0]
-    for i, sc in enumerate(score):
-        cig[i].score = int(sc)
-    t = lib.lrm_sam_format(C.byref(b), mta, 2, C.cast(cig, C.c_void_p), score.ctypes.data, meta.ctypes.data,
-                           meta_r.ctypes.data, 4, C.byref(ln_out))
-    got = C.string_at(t, ln_out.value).decode()
-    lib.lrm_free(t)
+    got = textio.sam_format(rd.batch, mta, cig, score, meta, meta_r, 4)
     seqs = ["ACGTAC", "GGGG", "TT", "ACG"]
     quals = ["IIIIII", "####", "!!", ";;;"]
     want = "".join(sam_ref.record("q%d" % i, seqs[i], quals[i], pymta, ops[i], int(score[i]), int(meta_r[i]),
@@ -181,5 +153,4 @@ def test_sam_header_and_records(tmp_path):
     assert got == want
     assert got.splitlines()[0] == "q0\t0\tchrA\t42\t255\t4M1I1M\t*\t0\t0\tACGTAC\tIIIIII\tED:I:2"
     assert got.splitlines()[2].split("\t")[1:6] == ["4", "*", "0", "0", "*"]
-    lib.lrm_read_batch_free(C.byref(b))
-    lib.lrm_reader_close(rd)
+    rd.close()

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import mapq_ref
-from longreadmapper_amd import capi, mapper
+from longreadmapper_amd import capi, mapper, textio
 from longreadmapper_amd.capi import lib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -171,27 +171,14 @@ def test_result_flags_with_and_without_records():
 def _batch(tmp_path, recs):
     p = tmp_path / "r.fq"
     p.write_bytes(b"".join(b"@%s\n%s\n+\n%s\n" % (nm, s, q) for nm, s, q in recs))
-    rd = C.c_void_p()
-    capi.check(lib.lrm_reader_open(C.byref(rd), str(p).encode()))
-    b = capi.ReadBatch()
-    assert lib.lrm_reader_next(rd, 100, C.byref(b)) == len(recs)
-    return rd, b
-
-
-def _cigars(ops_list, scores):
-    keep = [C.create_string_buffer(o + b"\0") for o in ops_list]
-    cig = (capi.Cigar * len(ops_list))()
-    for i, o in enumerate(ops_list):
-        cig[i].cigar, cig[i].n_cigar_op, cig[i].score = C.cast(keep[i], capi.u8p), len(o), int(scores[i])
-    return cig, keep
+    rd = textio.Reader(p)
+    assert rd.next(100) == len(recs)
+    return rd, rd.batch
 
 
 def test_sam_lines_with_records(tmp_path):
     rng = np.random.default_rng(11)
-    names = [b"chrA", b"chrB"]
-    mta = (capi.MtaEntry * 2)()
-    for i, (nm, off, ln) in enumerate(((b"chrA", 0, 100000), (b"chrB", 200000, 50000))):
-        mta[i].name_len, mta[i].name, mta[i].offset, mta[i].seq_len = len(nm), nm, off, ln
+    mta = textio.mta_table([(b"chrA", 0, 100000), (b"chrB", 200000, 50000)])
     lens = [900, 400, 300, 250]
     seqs = [bytes(b"ACGT"[x] for x in rng.integers(0, 4, k)) for k in lens]
     quals = [bytes(33 + (i + j) % 60 for j in range(k)) for i, k in enumerate(lens)]
@@ -202,7 +189,7 @@ def test_sam_lines_with_records(tmp_path):
     meta = np.zeros(4, dtype=mapper.META_DT)
     meta["seq_id"], meta["off"], meta["strand"] = [0, 1, 0, 0], [17, 2017, 4017, 0], [0, 1, 0, 0]
     rd, b = _batch(tmp_path, [(b"q%d" % i, seqs[i], quals[i]) for i in range(4)])
-    cig, keep1 = _cigars(ops, score)
+    cig, keep1 = textio.cigar_array(ops, score)
     seg = np.zeros(1, dtype=mapper.SEGMENT_DT)
     seg[0] = (0, 600, 300, capi.SEG_RIGHT | capi.SEG_ALIGNED)
     rows = np.zeros((1, 320), dtype=np.uint8)
@@ -210,31 +197,22 @@ def test_sam_lines_with_records(tmp_path):
     sscore, smeta_r = np.array([7], dtype=np.int32), np.array([1], dtype=np.int32)
     smeta = np.zeros(1, dtype=mapper.META_DT)
     smeta["seq_id"], smeta["off"] = 1, 5000
-    scig, keep2 = _cigars([b"=" * 300], sscore)
-    out = capi.SplitOut(1, 1, seg.ctypes.data, rows.ctypes.data, 320, None, None, C.cast(scig, C.c_void_p), None, 0,
+    scig, keep2 = textio.cigar_array([b"=" * 300], sscore)
+    out = capi.SplitOut(1, 1, seg.ctypes.data, rows.ctypes.data, 320, None, None, scig.ctypes.data, None, 0,
                         sscore.ctypes.data, smeta.ctypes.data, smeta_r.ctypes.data, None, None)
     rec = np.zeros(4, dtype=mapper.MAPQ_DT)
     rec["n1"], rec["n2"], rec["mapq"], rec["radius"] = [31, 12, 9, 5], [2, 12, 0, 1], [56, 0, 54, 33], 512
-    ln_out = C.c_uint64()
 
     def fmt(split, mqp):
-        t = lib.lrm_sam_format_mapq(C.byref(b), mta, 2, C.cast(cig, C.c_void_p), score.ctypes.data, meta.ctypes.data,
-                                    meta_r.ctypes.data, 4, 0, 0, split, mqp, C.byref(ln_out))
-        got = C.string_at(t, ln_out.value).decode()
-        lib.lrm_free(t)
-        return got
+        return textio.sam_format(b, mta, cig, score, meta, meta_r, 4, split=split, mapq=mqp, entry="lrm_sam_format_mapq")
 
     def fmt_split(split):
-        t = lib.lrm_sam_format_split(C.byref(b), mta, 2, C.cast(cig, C.c_void_p), score.ctypes.data, meta.ctypes.data,
-                                     meta_r.ctypes.data, 4, 0, 0, split, C.byref(ln_out))
-        got = C.string_at(t, ln_out.value).decode()
-        lib.lrm_free(t)
-        return got
+        return textio.sam_format(b, mta, cig, score, meta, meta_r, 4, split=split, entry="lrm_sam_format_split")
 
-    for split in (None, C.byref(out)):
+    for split in (None, out):
         plain = fmt_split(split)
         assert fmt(split, None) == plain                                  # NULL: lrm_sam_format_split byte for byte
-        got = fmt(split, rec.ctypes.data).splitlines()
+        got = fmt(split, rec).splitlines()
         base = plain.splitlines()
         assert len(got) == len(base) == (5 if split else 4)
         want = []
@@ -251,10 +229,9 @@ def test_sam_lines_with_records(tmp_path):
             want.append("\t".join(f))
         assert got == want
         assert [x.split("\t")[4] for x in got if not int(x.split("\t")[1]) & 2048] == ["56", "0", "54", "0"]
-    first = fmt(C.byref(out), rec.ctypes.data).splitlines()[0].split("\t")
+    first = fmt(out, rec).splitlines()[0].split("\t")
     assert first[-3:] == ["v1:i:31", "v2:i:2", "SA:Z:chrB,5001,+,600S300M,255,7;"]       # the segment's own entry keeps 255
-    lib.lrm_read_batch_free(C.byref(b))
-    lib.lrm_reader_close(rd)
+    rd.close()
 
 
 def test_reference_on_the_oracle_agrees_with_the_scalar_rule():

@@ -7,7 +7,7 @@ import pytest
 
 import sam_ref
 import split_ref
-from longreadmapper_amd import capi, mapper
+from longreadmapper_amd import capi, mapper, textio
 from longreadmapper_amd.capi import lib
 
 
@@ -71,19 +71,13 @@ def test_clip_of_cigar_bytes_and_text(ops):
 def _batch(tmp_path, recs):
     p = tmp_path / "r.fq"
     p.write_bytes(b"".join((b"@%s\n%s\n+\n%s\n" % (nm, s, q)) if q is not None else (b">%s\n%s\n" % (nm, s)) for nm, s, q in recs))
-    rd = C.c_void_p()
-    capi.check(lib.lrm_reader_open(C.byref(rd), str(p).encode()))
-    b = capi.ReadBatch()
-    assert lib.lrm_reader_next(rd, 100, C.byref(b)) == len(recs)
-    return rd, b
+    rd = textio.Reader(p)
+    assert rd.next(100) == len(recs)
+    return rd, rd.batch
 
 
 def _cigars(ops_list, scores, as_text):
-    keep = [C.create_string_buffer((sam_ref.rle(o).encode() if as_text else o) + b"\0") for o in ops_list]
-    cig = (capi.Cigar * max(len(ops_list), 1))()
-    for i, o in enumerate(ops_list):
-        cig[i].cigar, cig[i].n_cigar_op, cig[i].score = C.cast(keep[i], capi.u8p), len(o), int(scores[i])
-    return cig, keep
+    return textio.cigar_array(ops_list, scores, [sam_ref.rle(o).encode() for o in ops_list] if as_text else None)
 
 
 COMP = bytes.maketrans(b"ACGT", b"TGCA")
@@ -94,10 +88,7 @@ COMP = bytes.maketrans(b"ACGT", b"TGCA")
 def test_sam_lines_equal_the_reference_formatter(tmp_path, as_text, fasta):
     rng = np.random.default_rng(5)
     pymta = [("chrA", 0, 100000), ("contig_two", 200000, 50000)]
-    names = [b"chrA", b"contig_two"]
-    mta = (capi.MtaEntry * 2)()
-    for i, (nm, (_, off, ln)) in enumerate(zip(names, pymta)):
-        mta[i].name_len, mta[i].name, mta[i].offset, mta[i].seq_len = len(nm), nm, off, ln
+    mta = textio.mta_table(pymta)
 
     def rnd(k):
         return bytes(b"ACGT"[x] for x in rng.integers(0, 4, k))
@@ -147,18 +138,13 @@ def test_sam_lines_equal_the_reference_formatter(tmp_path, as_text, fasta):
     meta["seq_id"], meta["off"], meta["strand"] = [p["seq_id"] for p in prim], [p["off"] for p in prim], ps
     cig, keep1 = _cigars(prim_ops, score, as_text)
     scig, keep2 = _cigars(seg_ops, sscore, as_text)
-    out = capi.SplitOut(k, k, seg.ctypes.data, rows.ctypes.data, row_stride, None, None, C.cast(scig, C.c_void_p), None, 0,
+    out = capi.SplitOut(k, k, seg.ctypes.data, rows.ctypes.data, row_stride, None, None, scig.ctypes.data, None, 0,
                         sscore.ctypes.data, smeta.ctypes.data, smeta_r.ctypes.data, None, None)
-    ln_out = C.c_uint64()
 
     def fmt(split):
-        t = lib.lrm_sam_format_split(C.byref(b), mta, 2, C.cast(cig, C.c_void_p), score.ctypes.data, meta.ctypes.data, meta_r.ctypes.data,
-                                     n_reads, int(as_text), 0, split, C.byref(ln_out))
-        got = C.string_at(t, ln_out.value).decode()
-        lib.lrm_free(t)
-        return got
+        return textio.sam_format(b, mta, cig, score, meta, meta_r, n_reads, is_text=as_text, split=split, entry="lrm_sam_format_split")
 
-    got = fmt(C.byref(out))
+    got = fmt(out)
     want = "".join(split_ref.records("q%d" % i, printed[i].decode(), quals[i].decode() if quals[i] else None, pymta, prim[i], segs_of[i])
                    for i in range(n_reads))
     assert got == want
@@ -179,15 +165,11 @@ def test_sam_lines_equal_the_reference_formatter(tmp_path, as_text, fasta):
         assert f[5][10] == quals[2][:300][::-1].decode() and f[7][10] == quals[3][600:].decode()
     # without segments: exactly lrm_sam_format (which takes op bytes)
     if not as_text:
-        t = lib.lrm_sam_format(C.byref(b), mta, 2, C.cast(cig, C.c_void_p), score.ctypes.data, meta.ctypes.data, meta_r.ctypes.data,
-                               n_reads, C.byref(ln_out))
-        plain = C.string_at(t, ln_out.value).decode()
-        lib.lrm_free(t)
+        plain = textio.sam_format(b, mta, cig, score, meta, meta_r, n_reads, entry="lrm_sam_format")
         none = capi.SplitOut()
-        assert fmt(None) == plain and fmt(C.byref(none)) == plain
+        assert fmt(None) == plain and fmt(none) == plain
         assert [ln for ln in lines if "SA:Z" not in ln] == [ln for ln in plain.splitlines() if ln.split("\t")[0] in ("q5", "q6", "q7")]
-    lib.lrm_read_batch_free(C.byref(b))
-    lib.lrm_reader_close(rd)
+    rd.close()
 
 
 def test_fields_mirrors_and_entry_points():

@@ -1,13 +1,12 @@
 """End-to-end probe (GPU box): `accidx` + `accaln` on an E. coli-sized reference and N x 10 kbp reads from a
 FASTQ file, SAM out -- wall time of the whole flow, i.e. with the text stages either side of the hot path.
 python tools/accaln_probe.py [n_reads] [batch]"""
-import ctypes as C
 import os
 import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from longreadmapper_amd import capi, synth
+from longreadmapper_amd import synth, textio
 from longreadmapper_amd.capi import lib
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 40000
@@ -27,18 +26,16 @@ q = b"I" * Lr
 with open(fq, "wb") as f:
     for i in range(n):
         f.write(b"@read%d\n" % i + r["reads"][i, :Lr].tobytes() + b"\n+\n" + q + b"\n")
-total, valid = C.c_uint64(), C.c_uint64()
 os.environ.setdefault("LRM_HOST_VERBOSE", "1")        # stage times of lrm_accaln on stderr
 for rep in range(3):
     if os.path.exists(sam):
         os.remove(sam)                      # (truncating the previous run's gigabytes would be timed otherwise)
     t0 = time.perf_counter()
-    capi.check(lib.lrm_accaln(fa.encode(), fq.encode(), sam.encode(), capi.Params(batch, 20, 300), capi.GactParams(0, 0, 0), 0,
-                              1, C.byref(total), C.byref(valid)), "lrm_accaln")
+    total, valid = textio.accaln(fa, fq, sam, batch)
     t = time.perf_counter() - t0
     print("accaln run %d: %d reads x %d bp in batches of %d: %.2f s = %.3f Gbp/s end to end (index load + upload included); "
           "valid %d / %d; FASTQ %.0f MB, SAM %.0f MB; accidx %.1f s"
-          % (rep, n, Lr, batch, t, n * Lr / t / 1e9, valid.value, total.value, os.path.getsize(fq) / 1e6,
+          % (rep, n, Lr, batch, t, n * Lr / t / 1e9, valid, total, os.path.getsize(fq) / 1e6,
              os.path.getsize(sam) / 1e6, t_idx), flush=True)
 for p in os.listdir(d):
     os.remove(os.path.join(d, p))
