@@ -108,7 +108,7 @@ __device__ __forceinline__ uint32_t wave_or_u32(uint32_t v) {
     return (uint32_t) __builtin_amdgcn_readlane((int) v, 63);
 }
 
-// ---- index gathers and hit expansion shared by the vote kernels (vote_kernels.hip), the seed-table build (index_tables.hip) and the mapping-quality vote (mapq_kernels.hip) ----
+// ---- index gathers shared by the seed-table build (index_tables.hip), the hit walk of the vote kernels (vote_hits.h) and the mapping-quality vote (mapq_kernels.hip) ----
 // ----------------------------------------------------------------------------------------
 // FM LF-mapping: lf(c, loc) = C[c] + rank(c, loc), rank = # of c in bwt[0..loc] == _occ_access (fmidx.c:277-293)
 // and C[] as fmi_aln adds it (fmidx.c:305-311).  One 16-byte gather {C[c] + prefix, mask}, one shift and one
@@ -160,19 +160,5 @@ __device__ __forceinline__ uint64_t sa_of_unique(const LrmIndexView &ix, uint64_
 // # of set bits of a wave mask below this lane
 __device__ __forceinline__ uint32_t mask_rank(unsigned long long m) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t) (m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m, 0u));
-}
-
-// survivor s of the hit h: off[s] <= h < off[s + 1]  (off: exclusive prefix of the staged survivors' hit counts,
-// strictly increasing because every survivor has at least one hit; cnt >= 1)
-// (Measured alternative for the wavefront tier [r2]: a marker byte where the hits of each staged seed begin + a DPP
-//  prefix maximum over the 64 consecutive hits of the lanes, i.e. one LDS read instead of seven dependent ones:
-//  9.80 vs 9.76 ms per Gbp -- the search is not what the tier waits for.)
-__device__ __forceinline__ uint32_t find_seed(const uint32_t *off, uint32_t cnt, uint32_t h) {
-    uint32_t lo = 0, hi = cnt;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (off[mid] <= h) lo = mid; else hi = mid;
-    }
-    return lo;
 }
 #endif

@@ -11,11 +11,14 @@
 //
 // One workgroup of 256 per read.  A wavefront takes chunks of 64 survivors (phase by phase, chunks dealt round-robin
 // to the four wavefronts): a unique seed (rr == 1) is voted by the lane that loaded it, repeat seeds are staged in the
-// wavefront's own LDS lists and their rows expanded flat, VOTE_U gathers in flight per lane, as vote_item_wave does.
+// wavefront's own LDS lists and their rows expanded flat, MQ_U gathers in flight per lane, as vote_item_wave does.  The
+// staging and the walk are this kernel's own copies of stage_repeats_wave and for_each_hit (vote_hits.h, whose find_seed it
+// calls): through the shared ones it measured 0.4 % (staging alone) and 1.8 % (both) slower (profiles/r7/README.md, section 5) --
+// the walk here reads the seed ordinal before the gathers are issued, which in the vote kernels costs scratch.
 // The histograms are ONE open-addressing table in LDS, {tag, count} per slot, tag = bucket << 1 | histogram, claimed by
 // compare-and-swap like the slots of the exact vote kernel.  Then one sweep for the largest count.
 #include <hip/hip_runtime.h>
-#include "lrm_hip_util.h"
+#include "vote_hits.h"
 #include "mapq_rule.h"
 
 #define MQ_U 4                              // SA gathers in flight per lane

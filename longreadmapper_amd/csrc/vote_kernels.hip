@@ -1,6 +1,6 @@
-// vote_kernels.hip -- K2 of PART 1: the LDS vote over the survivor lists seed_search leaves (seed_kernels.hip)
+// vote_kernels.hip -- K2 of PART 1: the LDS vote over the survivor lists seed_search leaves (seed_kernels.hip); staging and hit walk: vote_hits.h
 #include <hip/hip_runtime.h>
-#include "lrm_hip_util.h"
+#include "vote_hits.h"
 
 // ----------------------------------------------------------------------------------------
 // K2 vote.
@@ -58,6 +58,11 @@ struct VoteTable {
     uint64_t *cf;
     uint32_t slots;
 };
+
+template <int NT>
+__device__ __forceinline__ void table_clear(const VoteTable &t, uint32_t tid) {
+    for (uint32_t s = tid; s < t.slots; s += NT) { t.key[s] = EMPTY_KEY; t.cf[s] = 0; }
+}
 
 // a hit lands in its bucket's slot: the smaller key (when the caller saw a larger one there), the count, the first-seen order
 __device__ __forceinline__ void slot_count(const VoteTable &t, uint32_t slot, bool lower, uint64_t key, uint32_t order, uint32_t n) {
@@ -171,49 +176,27 @@ __device__ __forceinline__ uint32_t table_slots_for(uint32_t x, uint32_t load, u
     return eff < cap ? eff : cap;
 }
 
+// What every vote kernel is given by value (the launcher fills it once): the items' geometry -- n reads x np phases from
+// phase_lo, P = seed_len + 1, cap_q survivor records per (read, phase) --, the order key's shift, the table load in percent,
+// and where the results go.  The survivor lists seed_search left (rec, recq, their counts gcnt and hit counts ghits, the
+// reads already decided) stay kernel arguments of their own: only there does __restrict__ reach the compiler, and without
+// it the per-item loads of ghits / gcnt are vector loads instead of scalar ones (vote slot 3.47 -> 3.68 ms: profiles/r7/README.md, section 5).
+struct VoteItems {
+    uint64_t n;
+    uint32_t P, np, phase_lo, cap_q, tbits, load;
+    LrmPhaseRes *phase_res;
+};
+// one of them: survivor list, survivor and hit count, phase, result
+struct Item { const uint64_t *rec; const uint32_t *recq; uint32_t cnt, H, iter; LrmPhaseRes *out; };
+
 // item number -> read, phase and id = read * P + phase (a 64-bit division: ~150 instructions, so once per item at most)
 struct ItemId { uint64_t read, id; uint32_t iter; };
-__device__ __forceinline__ ItemId item_decode(uint64_t item, uint32_t np, int phase_lo, uint32_t P) {
+__device__ __forceinline__ ItemId item_decode(uint64_t item, const VoteItems &v) {
     ItemId r;
-    r.read = item / np;
-    r.iter = (uint32_t) phase_lo + (uint32_t) (item - r.read * np);
-    r.id = r.read * (uint64_t) P + r.iter;
+    r.read = item / v.np;
+    r.iter = v.phase_lo + (uint32_t) (item - r.read * v.np);
+    r.id = r.read * (uint64_t) v.P + r.iter;
     return r;
-}
-
-// Survivors come in two kinds.  UNIQUE seeds (rr == 1: the read's true locus, ~3/4 of the survivors of a noisy
-// read) are voted by the lane that loaded them: one SA gather, no staging.  REPEAT seeds (rr > 1) are compacted
-// into LDS with the prefix sums of their hit counts and their hits are expanded flat: hit h finds its seed by a
-// binary search over the (few) staged repeat seeds.
-// The hits [0, total) of the staged survivors (off / srec / sq; geometry of the item: iter, P, tbits), expanded by NT
-// threads (tid of NT): all gathers of a step first, then sink(h, key, order key) for each of them.
-struct Staged { const uint32_t *off; const uint64_t *srec; const uint32_t *sq; uint32_t cnt, total, iter, P, tbits; };
-
-template <int NT, int VOTE_U, typename Sink>               // VOTE_U: SA gathers in flight per lane
-__device__ __forceinline__ void for_each_hit(const LrmIndexView &ix, const Staged &g, uint32_t tid, Sink sink) {
-    for (uint32_t hb = 0; hb < g.total; hb += NT * VOTE_U) {
-        uint64_t v[VOTE_U];
-        uint32_t ss[VOTE_U], tt[VOTE_U];
-#pragma unroll
-        for (int u = 0; u < VOTE_U; ++u) {
-            const uint32_t h = hb + (uint32_t) u * NT + tid;
-            v[u] = 0; ss[u] = 0; tt[u] = 0;
-            if (h < g.total) {
-                const uint32_t s = find_seed(g.off, g.cnt, h);
-                ss[u] = s;
-                tt[u] = h - g.off[s];
-                v[u] = sa_locate(ix, (g.srec[s] & ((1ull << 40) - 1ull)) + tt[u]);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < VOTE_U; ++u) {
-            const uint32_t h = hb + (uint32_t) u * NT + tid;
-            if (h < g.total) {
-                const uint32_t q = g.sq[ss[u]];
-                sink(h, v[u] - (uint64_t) (g.iter + q * g.P), (q << g.tbits) | tt[u]);       // alnmain.c:363-365 (u64 wrap kept); j < 2^32
-            }
-        }
-    }
 }
 
 // exact vote of the staged hits; kc_key / kc_ord (multi-pass items): keys kept for the later passes
@@ -221,7 +204,8 @@ template <int NT, int VOTE_U>
 __device__ __forceinline__ bool vote_hits(const LrmIndexView &ix, const VoteTable &t, const Staged &g, uint32_t tid, uint32_t passes,
                                           uint32_t pass, uint64_t *kc_key = nullptr, uint32_t *kc_ord = nullptr) {
     bool ok = true;
-    for_each_hit<NT, VOTE_U>(ix, g, tid, [&](uint32_t h, uint64_t key, uint32_t order) __attribute__((always_inline)) {
+    for_each_hit<NT, VOTE_U>(ix, g, tid, [&](bool live, uint32_t h, uint64_t key, uint32_t order) __attribute__((always_inline)) {
+        if (!live) return;
         if (kc_key) { kc_key[h] = key; kc_ord[h] = order; }
         ok &= vote_admit(t, key, order, passes, pass);
     });
@@ -238,50 +222,34 @@ struct WaveLds {
 };
 
 template <int VOTE_U>
-__device__ __forceinline__ void vote_item_wave(const LrmIndexView &ix, const uint64_t *__restrict__ rec,
-                                               const uint32_t *__restrict__ recq, uint32_t cnt, uint32_t H,
-                                               uint32_t iter, uint32_t P, uint32_t tbits, int lane, WaveLds &L,
-                                               LrmPhaseRes *out, uint32_t load) {
-    const VoteTable t = {L.key, L.cf, table_slots_for(H, load, T1_SLOTS)};
+__device__ __forceinline__ void vote_item_wave(const LrmIndexView &ix, const VoteItems &v, const Item &it, uint32_t lane, WaveLds &L) {
+    const VoteTable t = {L.key, L.cf, table_slots_for(it.H, v.load, T1_SLOTS)};
     constexpr int NU = (T1_LIMIT + 63) / 64;
     uint64_t e[NU], sv[NU];
     uint32_t qq[NU];
 #pragma unroll
     for (int u = 0; u < NU; ++u) {                                   // survivor loads first, table clear behind them
-        const uint32_t s = (uint32_t) u * 64 + (uint32_t) lane;
-        e[u] = s < cnt ? rec[s] : 0ull;
-        qq[u] = s < cnt ? recq[s] : 0u;
+        const uint32_t s = (uint32_t) u * 64 + lane;
+        e[u] = s < it.cnt ? it.rec[s] : 0ull;
+        qq[u] = s < it.cnt ? it.recq[s] : 0u;
     }
-    for (uint32_t s = lane; s < t.slots; s += 64) { t.key[s] = EMPTY_KEY; t.cf[s] = 0; }
-    uint32_t run = 0, nbig = 0;
+    table_clear<64>(t, lane);
 #pragma unroll
-    for (int u = 0; u < NU; ++u) {
-        const uint32_t rr = (uint32_t) (e[u] >> 40);
-        sv[u] = rr == 1 ? sa_of_unique(ix, e[u]) : 0ull;       // unique seeds: gather at once (or nothing to gather)
-        const bool big = rr > 1;
-        const unsigned long long bm = __ballot(big);
-        const uint32_t incl = wave_incl_scan(big ? rr : 0u);
-        if (big) {
-            const uint32_t idx = nbig + mask_rank(bm);
-            L.off[idx] = run + incl - rr; L.srec[idx] = e[u]; L.sq[idx] = qq[u];
-        }
-        run += (uint32_t) __builtin_amdgcn_readlane((int) incl, 63);
-        nbig += (uint32_t) __popcll(bm);
-    }
-    if (lane == 0) L.off[nbig] = run;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    for (int u = 0; u < NU; ++u) sv[u] = (uint32_t) (e[u] >> 40) == 1 ? sa_of_unique(ix, e[u]) : 0ull;       // unique seeds: gather at once (or nothing to gather)
+    WaveStage st = {0, 0};                                           // one staging of all chunks: each goes behind the ones before it
+#pragma unroll
+    for (int u = 0; u < NU; ++u) st = stage_repeats_wave(L.off, L.srec, L.sq, e[u], qq[u], st, lane);
     // (peeling the most frequent buckets of a batch off with ballots + wave reductions, so that one lane adds a whole
     //  group of equal votes, measured SLOWER: 18.8 vs 13.4 ms per Gbp [r2] -- same-slot contention is not the cost)
 #pragma unroll
     for (int u = 0; u < NU; ++u)
-        if ((uint32_t) (e[u] >> 40) == 1) vote_admit(t, sv[u] - (uint64_t) (iter + qq[u] * P), qq[u] << tbits, 1u, 0u);
-    if (nbig) vote_hits<64, VOTE_U>(ix, t, Staged{L.off, L.srec, L.sq, nbig, run, iter, P, tbits}, (uint32_t) lane, 1u, 0u);
+        if ((uint32_t) (e[u] >> 40) == 1) vote_admit(t, sv[u] - (uint64_t) (it.iter + qq[u] * v.P), qq[u] << v.tbits, 1u, 0u);
+    if (st.n) vote_hits<64, VOTE_U>(ix, t, Staged{L.off, L.srec, L.sq, st.n, st.hits, it.iter, v.P, v.tbits}, lane, 1u, 0u);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
 
-    const Top2 w = table_top2<64>(t, (uint32_t) lane);
-    if (lane == 0) write_phase(out, phase_of(t, w.k1, w.s1, w.k2, w.s2));
+    const Top2 w = table_top2<64>(t, lane);
+    if (lane == 0) write_phase(it.out, phase_of(t, w.k1, w.s1, w.k2, w.s2));
     __builtin_amdgcn_wave_barrier();
 }
 
@@ -295,54 +263,15 @@ struct BlockLds {
 };
 union VoteLds { WaveLds w[4]; BlockLds b; };
 
-// One chunk of up to 256 survivors, one per thread (record e0, seed ordinal q0, hit count r0; zeros past the chunk): the
-// repeat seeds are compacted into the staging arrays with the exclusive prefix of their hit counts -- a wave scan, the four
-// wave totals through s_wsum, the rank inside the wave by mask_rank.  Ends with a barrier: the staging is complete.
-// EXACT (the exact tier): the previous chunk or pass may still be reading the staging, so a barrier comes first; and the
-// unique seeds are counted too (s_wsum[8..11]): their keys go to the key scratch in front of the chunk's repeat hits.
-struct BlockStage { uint32_t nbig, total, nuni, urank; };      // repeat seeds, their hits, unique seeds, this thread's rank among those
-template <bool EXACT>
-__device__ __forceinline__ BlockStage stage_repeats_block(uint32_t *off, uint64_t *srec, uint32_t *sq, uint32_t *s_wsum, uint64_t e0,
-                                                          uint32_t q0, uint32_t r0) {
-    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
-    const bool b0 = r0 > 1;
-    const uint32_t h0 = b0 ? r0 : 0u;
-    const unsigned long long bm = __ballot(b0), um = EXACT ? __ballot(r0 == 1) : 0ull;
-    const uint32_t incl_h = wave_incl_scan(h0);
-    if (EXACT) __syncthreads();
-    if (lane == 63) {
-        s_wsum[wave] = incl_h; s_wsum[4 + wave] = (uint32_t) __popcll(bm);
-        if (EXACT) s_wsum[8 + wave] = (uint32_t) __popcll(um);
-    }
-    __syncthreads();
-    BlockStage r = {0, 0, 0, 0};
-    uint32_t woff_h = 0, woff_n = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < 4; ++w) {
-        const uint32_t x = s_wsum[w], y = s_wsum[4 + w], z = EXACT ? s_wsum[8 + w] : 0u;
-        r.total += x; r.nbig += y; r.nuni += z;
-        if (w < wave) { woff_h += x; woff_n += y; r.urank += z; }
-    }
-    r.urank += mask_rank(um);
-    if (b0) {
-        const uint32_t idx = woff_n + mask_rank(bm);
-        off[idx] = woff_h + incl_h - h0; srec[idx] = e0; sq[idx] = q0;
-    }
-    if (tid == 0) off[r.nbig] = r.total;
-    __syncthreads();
-    return r;
-}
-
 struct KeyScratch { uint64_t *key; uint32_t *ord; uint32_t cap; };       // this workgroup's slice of the key scratch, in hits
 struct GlobalPool { uint64_t *tab; uint32_t *lock; uint32_t slices, slots; uint32_t *s_slice; };   // global-memory tables; s_slice: LDS word
 
 template <int VOTE_U>
-__device__ __forceinline__ void vote_item_block(const LrmIndexView &ix, const uint64_t *__restrict__ rec,
-                                                const uint32_t *__restrict__ recq, uint32_t cnt, uint32_t H,
-                                                uint32_t iter, uint32_t P, uint32_t tbits, uint32_t slots, uint32_t limit,
-                                                BlockLds &L, uint32_t *s_wsum, Top2 *s_top, LrmPhaseRes *out,
-                                                uint32_t *err_word, uint32_t load, const KeyScratch &kc, const GlobalPool &gp) {
+__device__ __forceinline__ void vote_item_block(const LrmIndexView &ix, const VoteItems &v, const Item &it, uint32_t slots, uint32_t limit,
+                                                BlockLds &L, uint32_t *s_wsum, Top2 *s_top, uint32_t *err_word, const KeyScratch &kc,
+                                                const GlobalPool &gp) {
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    const uint32_t H = it.H, cnt = it.cnt;
     VoteTable t = {L.key, L.cf, slots};
     uint32_t passes = (H + limit - 1) / limit;
     // Items with more hits than the key scratch holds (a read made of a 100-299-copy repeat family: up to
@@ -374,10 +303,10 @@ __device__ __forceinline__ void vote_item_block(const LrmIndexView &ix, const ui
     // (12 coalesced bytes per hit) instead of searching, gathering and subtracting again.
     // (from three passes on: with two, writing and re-reading 12 B per hit costs as much traffic as it saves)
     const bool cache = passes > 2 && H <= kc.cap;
-    if (!big) t.slots = table_slots_for(passes > 1 ? limit : H, load, slots);
+    if (!big) t.slots = table_slots_for(passes > 1 ? limit : H, v.load, slots);
     PhaseTop best = {};
     for (uint32_t pass = 0; pass < passes; ++pass) {
-        for (uint32_t s = tid; s < t.slots; s += 256) { t.key[s] = EMPTY_KEY; t.cf[s] = 0; }
+        table_clear<256>(t, tid);
         if (big) { __threadfence(); __syncthreads(); }             // the cleared slots are in L2 before the first atomic of another thread
         bool ok = true;
         if (cache && pass > 0) {
@@ -388,17 +317,17 @@ __device__ __forceinline__ void vote_item_block(const LrmIndexView &ix, const ui
         for (uint32_t c0 = 0; c0 < cnt; c0 += T3_CHUNK) {
             const uint32_t nc = cnt - c0 < (uint32_t) T3_CHUNK ? cnt - c0 : (uint32_t) T3_CHUNK;
             // one survivor per thread; unique seeds gather at once, repeat seeds are compacted into LDS
-            const uint64_t e0 = tid < nc ? rec[c0 + tid] : 0ull;
-            const uint32_t q0 = tid < nc ? recq[c0 + tid] : 0u;
+            const uint64_t e0 = tid < nc ? it.rec[c0 + tid] : 0ull;
+            const uint32_t q0 = tid < nc ? it.recq[c0 + tid] : 0u;
             const uint32_t r0 = (uint32_t) (e0 >> 40);
             const uint64_t v0 = r0 == 1 ? sa_of_unique(ix, e0) : 0ull;
             const BlockStage st = stage_repeats_block<true>(L.off, L.srec, L.sq, s_wsum, e0, q0, r0);
             if (r0 == 1) {
-                const uint64_t key = v0 - (uint64_t) (iter + q0 * P);
-                if (cache) { const uint32_t i = kbase + st.urank; kc.key[i] = key; kc.ord[i] = q0 << tbits; }
-                ok &= vote_admit(t, key, q0 << tbits, passes, pass);
+                const uint64_t key = v0 - (uint64_t) (it.iter + q0 * v.P);
+                if (cache) { const uint32_t i = kbase + st.urank; kc.key[i] = key; kc.ord[i] = q0 << v.tbits; }
+                ok &= vote_admit(t, key, q0 << v.tbits, passes, pass);
             }
-            if (st.nbig) ok &= vote_hits<256, VOTE_U>(ix, t, Staged{L.off, L.srec, L.sq, st.nbig, st.total, iter, P, tbits}, tid, passes, pass,
+            if (st.nbig) ok &= vote_hits<256, VOTE_U>(ix, t, Staged{L.off, L.srec, L.sq, st.nbig, st.total, it.iter, v.P, v.tbits}, tid, passes, pass,
                                                       cache ? kc.key + kbase + st.nuni : nullptr, cache ? kc.ord + kbase + st.nuni : nullptr);
             kbase += st.nuni + st.total;
         }
@@ -430,7 +359,7 @@ __device__ __forceinline__ void vote_item_block(const LrmIndexView &ix, const ui
         }
         __syncthreads();
     }
-    if (tid == 0) write_phase(out, best);
+    if (tid == 0) write_phase(it.out, best);
     if (big) {                                                     // the slice goes back to the pool
         __syncthreads();
         if (tid == 0) { __threadfence(); atomicExch(&gp.lock[*gp.s_slice], 0u); }
@@ -470,6 +399,10 @@ __device__ __forceinline__ void vote_item_block(const LrmIndexView &ix, const ui
 #define EMPTY_ID 0x80000000u                 // in neither range
 #define FAST_NONE 0xFFFFFFFFu                // no slot / no hit
 struct FastTable { uint32_t *ident, *count; uint32_t slots; };
+template <int NT>
+__device__ __forceinline__ void table_clear(const FastTable &t, uint32_t tid) {
+    for (uint32_t s = tid; s < t.slots; s += NT) { t.ident[s] = EMPTY_ID; t.count[s] = 0; }
+}
 
 // a key outside the two ranges (an index whose suffix-array values reach 2^35: the ui40 format holds 2^40): its bucket has
 // no 32-bit name, and the item it belongs to goes to the exact kernel
@@ -517,61 +450,41 @@ __device__ __forceinline__ uint32_t fast_find(const FastTable &t, uint32_t id, u
 #define FB_LIST 512                          // workgroup form: items of up to FB_LIMIT survivors
 __device__ __forceinline__ uint32_t hit_word(uint32_t slot, uint64_t key) { return (slot << 4) | ((uint32_t) key & 15u); }
 
-// B over the staged repeat seeds (for_each_hit's shape: all gathers of a step first).  n_list: entries so far, a wave-uniform
-// register in the wavefront form (NT == 64); the workgroup form counts in the LDS word list_n instead.
+// B over the staged repeat seeds, a sink of for_each_hit that every lane enters (it holds a ballot).  n_list: entries so far,
+// a wave-uniform register in the wavefront form (NT == 64); the workgroup form counts in the LDS word list_n instead.
 template <int NT, int VOTE_U>
 __device__ __forceinline__ void fast_hits(const LrmIndexView &ix, const FastTable &t, const Staged &g, uint32_t *sketch, uint32_t sk_mask,
                                           uint32_t tid, uint64_t *list, uint32_t cap, uint32_t &n_list, uint32_t *list_n, bool &wide) {
-    for (uint32_t hb = 0; hb < g.total; hb += NT * VOTE_U) {
-        uint64_t v[VOTE_U];
-        uint32_t ss[VOTE_U], tt[VOTE_U];
-#pragma unroll
-        for (int u = 0; u < VOTE_U; ++u) {
-            const uint32_t h = hb + (uint32_t) u * NT + tid;
-            v[u] = 0; ss[u] = 0; tt[u] = 0;
-            if (h < g.total) {
-                const uint32_t s = find_seed(g.off, g.cnt, h);
-                ss[u] = s;
-                tt[u] = h - g.off[s];
-                v[u] = sa_locate(ix, (g.srec[s] & ((1ull << 40) - 1ull)) + tt[u]);
+    for_each_hit<NT, VOTE_U>(ix, g, tid, [&](bool live, uint32_t, uint64_t key, uint32_t order) __attribute__((always_inline)) {
+        uint32_t hw = FAST_NONE, oinv = 0;
+        if (live) {
+            const uint32_t hash = bucket_hash(key >> 4);
+            wide |= key_wide(key);
+            const uint32_t slot = fast_find(t, (uint32_t) (key >> 4), hash);
+            if (slot != FAST_NONE) {
+                atomicAdd(&t.count[slot], 1u);
+                hw = hit_word(slot, key);
+                oinv = 0xFFFFFFFFu - order;
+            } else {
+                const uint32_t c = (hash >> 5) & sk_mask;
+                atomicAdd(&sketch[c >> 1], 1u << (16 * (c & 1)));          // < 2^16 hits per bucket: 16 per seed at most
             }
         }
-#pragma unroll
-        for (int u = 0; u < VOTE_U; ++u) {
-            const uint32_t h = hb + (uint32_t) u * NT + tid;
-            uint32_t hw = FAST_NONE, oinv = 0;
-            if (h < g.total) {
-                const uint32_t q = g.sq[ss[u]];
-                const uint64_t key = v[u] - (uint64_t) (g.iter + q * g.P);                    // alnmain.c:363-365 (u64 wrap kept); j < 2^32
-                const uint32_t hash = bucket_hash(key >> 4);
-                wide |= key_wide(key);
-                const uint32_t slot = fast_find(t, (uint32_t) (key >> 4), hash);
-                if (slot != FAST_NONE) {
-                    atomicAdd(&t.count[slot], 1u);
-                    hw = hit_word(slot, key);
-                    oinv = 0xFFFFFFFFu - ((q << g.tbits) | tt[u]);
-                } else {
-                    const uint32_t c = (hash >> 5) & sk_mask;
-                    atomicAdd(&sketch[c >> 1], 1u << (16 * (c & 1)));          // < 2^16 hits per bucket: 16 per seed at most
-                }
+        const unsigned long long bm = __ballot(hw != FAST_NONE);
+        if (bm) {
+            uint32_t base;
+            if (NT == 64) { base = n_list; n_list += (uint32_t) __popcll(bm); }
+            else {
+                uint32_t b0 = 0;
+                if ((tid & 63u) == 0) b0 = atomicAdd(list_n, (uint32_t) __popcll(bm));
+                base = (uint32_t) __builtin_amdgcn_readfirstlane((int) b0);
             }
-            // (the loop bounds are uniform, so every lane of the wavefront is here)
-            const unsigned long long bm = __ballot(hw != FAST_NONE);
-            if (bm) {
-                uint32_t base;
-                if (NT == 64) { base = n_list; n_list += (uint32_t) __popcll(bm); }
-                else {
-                    uint32_t b0 = 0;
-                    if ((tid & 63u) == 0) b0 = atomicAdd(list_n, (uint32_t) __popcll(bm));
-                    base = (uint32_t) __builtin_amdgcn_readfirstlane((int) b0);
-                }
-                if (hw != FAST_NONE) {
-                    const uint32_t i = base + mask_rank(bm);
-                    if (i < cap) list[i] = ((uint64_t) oinv << 32) | hw;
-                }
+            if (hw != FAST_NONE) {
+                const uint32_t i = base + mask_rank(bm);
+                if (i < cap) list[i] = ((uint64_t) oinv << 32) | hw;
             }
         }
-    }
+    });
 }
 
 // ---- the rank step: the stable top two from the hits ------------------------------------------------------------------
@@ -625,6 +538,37 @@ __device__ __forceinline__ TopEntry fast_entry(const FastTable &t, const RankTop
     return e;
 }
 
+// the list entries (step B) of this thread of NT, i = l * NT + tid of the n_list entries (at most cap), as inputs of the rank
+// step behind the thread's own hits: hw = the entry's word, hr = count << 32 | ~order with the table final
+template <int NT, int NL, int N>
+__device__ __forceinline__ void list_ranks(const FastTable &t, const uint64_t *list, uint32_t n_list, uint32_t cap, uint32_t tid,
+                                           uint64_t (&hr)[N], uint32_t (&hw)[N]) {
+#pragma unroll
+    for (int l = 0; l < NL; ++l) {
+        const uint32_t i = (uint32_t) l * NT + tid;
+        hr[N - NL + l] = 0; hw[N - NL + l] = FAST_NONE;
+        if (i < n_list && i < cap) {
+            const uint64_t x = list[i];
+            hw[N - NL + l] = (uint32_t) x;
+            hr[N - NL + l] = ((uint64_t) t.count[(uint32_t) x >> 4] << 32) | (x >> 32);
+        }
+    }
+}
+// the largest 16-bit counter of a sketch of WORDS words, scanned by NT threads: this wavefront's maximum, in every lane
+template <int NT, int WORDS>
+__device__ __forceinline__ uint32_t sketch_max(const uint32_t *sketch, uint32_t tid) {
+    static_assert(WORDS % NT == 0, "every thread scans WORDS / NT words");
+    uint32_t m = 0;
+#pragma unroll
+    for (uint32_t s = 0; s < WORDS / NT; ++s) {
+        const uint32_t x = sketch[s * NT + tid];
+        const uint32_t lo = x & 0xffffu, hi = x >> 16;
+        m = lo > m ? lo : m;
+        m = hi > m ? hi : m;
+    }
+    return wave_max_u32(m);
+}
+
 // ---- fast path, wavefront form ------------------------------------------------------------------------------------------
 struct FastLds {
     uint32_t ident[T1_SLOTS];
@@ -645,18 +589,13 @@ struct FastLds {
 #define FAST_CH 16                           // items per ticket of a wavefront
 template <int VOTE_U>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LRM_VOTE_FAST_WAVES, LRM_VOTE_FAST_WAVES)))
-void vote_fast_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, const uint32_t *__restrict__ recq,
-                      const uint32_t *__restrict__ gcnt, const uint32_t *__restrict__ ghits,
-                      const uint8_t *__restrict__ decided, uint64_t n, int seed_len, int phase_lo, int phase_hi,
-                      uint32_t cap_q, uint32_t tbits, uint32_t load, unsigned long long *ticket,
-                      LrmPhaseRes *__restrict__ phase_res, uint64_t *__restrict__ redo, unsigned long long *redo_n,
+void vote_fast_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, const uint32_t *__restrict__ recq, const uint32_t *__restrict__ gcnt,
+                      const uint32_t *__restrict__ ghits, const uint8_t *__restrict__ decided, VoteItems v, unsigned long long *ticket, uint64_t *__restrict__ redo, unsigned long long *redo_n,
                       uint64_t *__restrict__ big, unsigned long long *big_n) {
     __shared__ FastLds lds[4];
     const uint32_t lane = threadIdx.x & 63u;
     FastLds &L = lds[threadIdx.x >> 6];
-    const uint32_t P = (uint32_t) seed_len + 1;
-    const uint32_t np = (uint32_t) (phase_hi - phase_lo + 1);
-    const uint64_t n_items = n * (uint64_t) np;
+    const uint64_t n_items = v.n * (uint64_t) v.np;
     constexpr int NU = (T1_LIMIT + 63) / 64;
     constexpr int NL = (FAST_LIST + 63) / 64;
     for (;;) {
@@ -665,16 +604,16 @@ void vote_fast_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, const u
         base = ((unsigned long long) (uint32_t) __builtin_amdgcn_readfirstlane((int) (uint32_t) (base >> 32)) << 32) |
                (uint32_t) __builtin_amdgcn_readfirstlane((int) (uint32_t) base);
         if (base >= n_items) break;
-        ItemId ii = item_decode(base, np, phase_lo, P);                        // once per ticket: its items follow by increments
+        ItemId ii = item_decode(base, v);                                      // once per ticket: its items follow by increments
         for (uint32_t it = 0; it < FAST_CH && base + it < n_items; ++it, ++ii.iter) {
-            if (ii.iter == (uint32_t) phase_lo + np) { ii.iter = (uint32_t) phase_lo; ++ii.read; }
+            if (ii.iter == v.phase_lo + v.np) { ii.iter = v.phase_lo; ++ii.read; }
             const uint64_t item = base + it;
             const uint32_t iter = ii.iter;
-            const uint64_t id = ii.read * (uint64_t) P + iter;
+            const uint64_t id = ii.read * (uint64_t) v.P + iter;
             if (decided && decided[ii.read]) continue;
             const uint32_t H = ghits[id], cnt = gcnt[id];
             if (H == 0) {
-                if (lane == 0) { LrmPhaseRes z = {0, 0, 0, 0, 0, 0}; phase_res[id] = z; }
+                if (lane == 0) { LrmPhaseRes z = {0, 0, 0, 0, 0, 0}; v.phase_res[id] = z; }
                 continue;
             }
             if (cnt > (uint32_t) T1_LIMIT) {                                   // more survivors than the wavefront table is sized for:
@@ -684,18 +623,18 @@ void vote_fast_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, const u
                 }
                 continue;
             }
-            const FastTable t = {L.ident, L.count, table_slots_for(cnt, load, T1_SLOTS)};
-            const uint64_t *irec = rec + id * cap_q;
-            const uint32_t *iq = recq + id * cap_q;
+            const FastTable t = {L.ident, L.count, table_slots_for(cnt, v.load, T1_SLOTS)};
             uint64_t e[NU], sv[NU];
             uint32_t qq[NU];
+            const uint64_t *irec = rec + id * v.cap_q;
+            const uint32_t *iq = recq + id * v.cap_q;
 #pragma unroll
             for (int u = 0; u < NU; ++u) {                                   // survivor loads first, clears behind them
                 const uint32_t s = (uint32_t) u * 64 + lane;
                 e[u] = s < cnt ? irec[s] : 0ull;
                 qq[u] = s < cnt ? iq[s] : 0u;
             }
-            for (uint32_t s = lane; s < t.slots; s += 64) { t.ident[s] = EMPTY_ID; t.count[s] = 0; }
+            table_clear<64>(t, lane);
             unsigned long long any_big = 0;
 #pragma unroll
             for (int u = 0; u < NU; ++u) {
@@ -717,7 +656,7 @@ void vote_fast_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, const u
             for (int u = 0; u < NU; ++u) {
                 hw[u] = FAST_NONE;
                 if ((uint32_t) (e[u] >> 40) == 1) {
-                    const uint64_t key = sv[u] - (uint64_t) (iter + qq[u] * P);
+                    const uint64_t key = sv[u] - (uint64_t) (iter + qq[u] * v.P);
                     wide |= key_wide(key);
                     const uint32_t slot = fast_insert(t, (uint32_t) (key >> 4), bucket_hash(key >> 4));
                     if (slot != FAST_NONE) hw[u] = hit_word(slot, key);
@@ -730,21 +669,9 @@ void vote_fast_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, const u
             if (any_big) {
 #pragma unroll
                 for (int u = 0; u < NU; ++u) {
-                    const uint32_t rr = (uint32_t) (e[u] >> 40);
-                    const bool big = rr > 1;
-                    const unsigned long long bm = __ballot(big);
-                    if (bm == 0) continue;
-                    const uint32_t incl = wave_incl_scan(big ? rr : 0u);
-                    if (big) {
-                        const uint32_t idx = mask_rank(bm);
-                        L.off[idx] = incl - rr; L.srec[idx] = e[u]; L.sq[idx] = qq[u];
-                    }
-                    const uint32_t nb = (uint32_t) __popcll(bm);
-                    const uint32_t run = (uint32_t) __builtin_amdgcn_readlane((int) incl, 63);
-                    if (lane == 0) L.off[nb] = run;
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    fast_hits<64, VOTE_U>(ix, t, Staged{L.off, L.srec, L.sq, nb, run, iter, P, tbits}, L.sketch, 2 * FAST_SK_WORDS - 1, lane,
+                    if (__ballot((uint32_t) (e[u] >> 40) > 1) == 0) continue;             // a chunk without a repeat seed stages nothing
+                    const WaveStage st = stage_repeats_wave(L.off, L.srec, L.sq, e[u], qq[u], WaveStage{0, 0}, lane);
+                    fast_hits<64, VOTE_U>(ix, t, Staged{L.off, L.srec, L.sq, st.n, st.hits, iter, v.P, v.tbits}, L.sketch, 2 * FAST_SK_WORDS - 1, lane,
                                           L.list, (uint32_t) FAST_LIST, n_list, nullptr, wide);
                     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                     __builtin_amdgcn_wave_barrier();
@@ -756,36 +683,17 @@ void vote_fast_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, const u
             for (int u = 0; u < NU; ++u) {
                 const bool uniq = (uint32_t) (e[u] >> 40) == 1;
                 lost |= uniq && hw[u] == FAST_NONE;
-                hr[u] = uniq && hw[u] != FAST_NONE ? ((uint64_t) t.count[hw[u] >> 4] << 32) | (0xFFFFFFFFu - (qq[u] << tbits)) : 0ull;
+                hr[u] = uniq && hw[u] != FAST_NONE ? ((uint64_t) t.count[hw[u] >> 4] << 32) | (0xFFFFFFFFu - (qq[u] << v.tbits)) : 0ull;
             }
-#pragma unroll
-            for (int l = 0; l < NL; ++l) {
-                const uint32_t i = (uint32_t) l * 64 + lane;
-                hr[NU + l] = 0; hw[NU + l] = FAST_NONE;
-                if (i < n_list && i < (uint32_t) FAST_LIST) {
-                    const uint64_t x = L.list[i];
-                    hw[NU + l] = (uint32_t) x;
-                    hr[NU + l] = ((uint64_t) t.count[(uint32_t) x >> 4] << 32) | (x >> 32);
-                }
-            }
+            list_ranks<64, NL>(t, L.list, n_list, (uint32_t) FAST_LIST, lane, hr, hw);
             const RankTop a = wave_top_rank(lane_top_rank(hr, hw, FAST_NONE));
             const RankTop b = wave_top_rank(lane_top_rank(hr, hw, a.r ? a.s : FAST_NONE));
             const uint32_t lowm = wave_or_u32(lane_low4_mask(hr, hw, a, b));
             // C
             bool settled = n_list <= (uint32_t) FAST_LIST && __ballot(lost) == 0;
-            if (any_big) {
-                uint32_t m = 0;
-#pragma unroll
-                for (uint32_t s = 0; s < FAST_SK_WORDS / 64; ++s) {
-                    const uint32_t x = L.sketch[s * 64 + lane];
-                    const uint32_t lo = x & 0xffffu, hi = x >> 16;
-                    m = lo > m ? lo : m;
-                    m = hi > m ? hi : m;
-                }
-                settled = settled && wave_max_u32(m) < (uint32_t) (b.r >> 32);
-            }
+            if (any_big) settled = settled && sketch_max<64, FAST_SK_WORDS>(L.sketch, lane) < (uint32_t) (b.r >> 32);
             if (lane == 0) {
-                if (settled) write_phase(&phase_res[id], PhaseTop{fast_entry(t, a, lowm >> 16), fast_entry(t, b, lowm & 0xffffu)});
+                if (settled) write_phase(&v.phase_res[id], PhaseTop{fast_entry(t, a, lowm >> 16), fast_entry(t, b, lowm & 0xffffu)});
                 else redo[atomicAdd(redo_n, 1ull)] = item;
             }
             __builtin_amdgcn_wave_barrier();
@@ -816,18 +724,13 @@ __device__ __forceinline__ RankTop block_top_rank(const RankTop *s_rk) {
 template <int VOTE_U>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3)))
 void vote_fast_block_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, const uint32_t *__restrict__ recq,
-                            const uint32_t *__restrict__ gcnt, const uint32_t *__restrict__ ghits, int seed_len,
-                            int phase_lo, int phase_hi, uint32_t cap_q, uint32_t tbits, uint32_t load,
-                            unsigned long long *ticket, LrmPhaseRes *__restrict__ phase_res,
-                            const uint64_t *__restrict__ big, const unsigned long long *__restrict__ big_n,
-                            uint64_t *__restrict__ redo, unsigned long long *redo_n) {
+                            const uint32_t *__restrict__ gcnt, VoteItems v, unsigned long long *ticket, const uint64_t *__restrict__ big,
+                            const unsigned long long *__restrict__ big_n, uint64_t *__restrict__ redo, unsigned long long *redo_n) {
     __shared__ FastBlockLds L;
     __shared__ uint32_t s_wsum[8], s_m[4], s_or[4], s_list_n;
     __shared__ RankTop s_rk[2][4];
     __shared__ unsigned long long s_at;
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
-    const uint32_t P = (uint32_t) seed_len + 1;
-    const uint32_t np = (uint32_t) (phase_hi - phase_lo + 1);
     const uint64_t n_big = (uint64_t) *big_n;
     constexpr int NU = FB_LIMIT / 256;
     constexpr int NL = FB_LIST / 256;
@@ -837,13 +740,13 @@ void vote_fast_block_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, c
         const uint64_t at = s_at;
         if (at >= n_big) break;
         const uint64_t item = big[at];
-        const ItemId ii = item_decode(item, np, phase_lo, P);
+        const ItemId ii = item_decode(item, v);
         const uint64_t id = ii.id;
         const uint32_t iter = ii.iter, cnt = gcnt[id];
-        const uint64_t *irec = rec + id * cap_q;
-        const uint32_t *iq = recq + id * cap_q;
-        const FastTable t = {L.ident, L.count, table_slots_for(cnt, load, FB_SLOTS)};
-        for (uint32_t s = tid; s < t.slots; s += 256) { t.ident[s] = EMPTY_ID; t.count[s] = 0; }
+        const uint64_t *irec = rec + id * v.cap_q;
+        const uint32_t *iq = recq + id * v.cap_q;
+        const FastTable t = {L.ident, L.count, table_slots_for(cnt, v.load, FB_SLOTS)};
+        table_clear<256>(t, tid);
         __syncthreads();
         // A: the unique seeds' hits make the table; every thread keeps its hits
         bool ok = true;
@@ -859,10 +762,10 @@ void vote_fast_block_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, c
             any_big |= r0 > 1 ? 1u : 0u;
             if (r0 == 1) {
                 const uint32_t q0 = iq[s];
-                const uint64_t key = sa_of_unique(ix, e0) - (uint64_t) (iter + q0 * P);
+                const uint64_t key = sa_of_unique(ix, e0) - (uint64_t) (iter + q0 * v.P);
                 const uint32_t slot = fast_insert(t, (uint32_t) (key >> 4), bucket_hash(key >> 4));
                 ok &= slot != FAST_NONE && !key_wide(key);
-                if (slot != FAST_NONE) { hw[k] = hit_word(slot, key); ho[k] = 0xFFFFFFFFu - (q0 << tbits); }
+                if (slot != FAST_NONE) { hw[k] = hit_word(slot, key); ho[k] = 0xFFFFFFFFu - (q0 << v.tbits); }
             }
         }
         const bool block_big = __syncthreads_or((int) any_big) != 0;
@@ -876,7 +779,7 @@ void vote_fast_block_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, c
                 const uint32_t q0 = c0 + tid < cnt ? iq[c0 + tid] : 0u;
                 const uint32_t r0 = (uint32_t) (e0 >> 40);
                 const BlockStage st = stage_repeats_block<false>(L.off, L.srec, L.sq, s_wsum, e0, q0, r0);
-                if (st.nbig) fast_hits<256, VOTE_U>(ix, t, Staged{L.off, L.srec, L.sq, st.nbig, st.total, iter, P, tbits}, L.sketch, 2 * FB_SK_WORDS - 1, tid,
+                if (st.nbig) fast_hits<256, VOTE_U>(ix, t, Staged{L.off, L.srec, L.sq, st.nbig, st.total, iter, v.P, v.tbits}, L.sketch, 2 * FB_SK_WORDS - 1, tid,
                                                     L.list, (uint32_t) FB_LIST, unused, &s_list_n, wide);
                 __syncthreads();                                   // the staging is rewritten by the next chunk
             }
@@ -887,16 +790,7 @@ void vote_fast_block_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, c
 #pragma unroll
         for (int k = 0; k < NU; ++k)
             hr[k] = hw[k] != FAST_NONE ? ((uint64_t) t.count[hw[k] >> 4] << 32) | ho[k] : 0ull;
-#pragma unroll
-        for (int l = 0; l < NL; ++l) {
-            const uint32_t i = (uint32_t) l * 256 + tid;
-            hr[NU + l] = 0; hw[NU + l] = FAST_NONE;
-            if (i < n_list && i < (uint32_t) FB_LIST) {
-                const uint64_t x = L.list[i];
-                hw[NU + l] = (uint32_t) x;
-                hr[NU + l] = ((uint64_t) t.count[(uint32_t) x >> 4] << 32) | (x >> 32);
-            }
-        }
+        list_ranks<256, NL>(t, L.list, n_list, (uint32_t) FB_LIST, tid, hr, hw);
         const RankTop wa = wave_top_rank(lane_top_rank(hr, hw, FAST_NONE));
         if (lane == 0) s_rk[0][wave] = wa;
         __syncthreads();
@@ -907,23 +801,14 @@ void vote_fast_block_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, c
         const RankTop b = block_top_rank(s_rk[1]);
         const uint32_t lowm = wave_or_u32(lane_low4_mask(hr, hw, a, b));
         // C
-        uint32_t m = 0;
-        if (block_big) {
-            for (uint32_t s = tid; s < FB_SK_WORDS; s += 256) {
-                const uint32_t x = L.sketch[s];
-                const uint32_t lo = x & 0xffffu, hi = x >> 16;
-                m = lo > m ? lo : m;
-                m = hi > m ? hi : m;
-            }
-            m = wave_max_u32(m);
-        }
+        const uint32_t m = block_big ? sketch_max<256, FB_SK_WORDS>(L.sketch, tid) : 0u;
         if (lane == 0) { s_or[wave] = lowm; s_m[wave] = m; }
         const bool all_ok = __syncthreads_and((int) ok) != 0;
         if (tid == 0) {
             uint32_t M = 0, lm = 0;
             for (int x = 0; x < 4; ++x) { M = s_m[x] > M ? s_m[x] : M; lm |= s_or[x]; }
             const bool settled = all_ok && n_list <= (uint32_t) FB_LIST && (!block_big || M < (uint32_t) (b.r >> 32));
-            if (settled) write_phase(&phase_res[id], PhaseTop{fast_entry(t, a, lm >> 16), fast_entry(t, b, lm & 0xffffu)});
+            if (settled) write_phase(&v.phase_res[id], PhaseTop{fast_entry(t, a, lm >> 16), fast_entry(t, b, lm & 0xffffu)});
             else redo[atomicAdd(redo_n, 1ull)] = item;
         }
         __syncthreads();                                           // s_at, s_list_n, the table and s_rk are rewritten by the next item
@@ -931,22 +816,15 @@ void vote_fast_block_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, c
 }
 
 #ifndef LRM_VOTE_WAVES_PER_EU
-#define LRM_VOTE_WAVES_PER_EU 6     // 79 VGPRs and 23.7 KB of LDS per workgroup: six workgroups per CU
+#define LRM_VOTE_WAVES_PER_EU 6     // 80 VGPRs (and a spill: DESIGN.md, "vote") and 23.5 KB of LDS per workgroup: six workgroups per CU
 #endif
 template <int VOTE_U>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LRM_VOTE_WAVES_PER_EU, LRM_VOTE_WAVES_PER_EU)))
-void vote_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec,
-                                                   const uint32_t *__restrict__ recq,
-                                                   const uint32_t *__restrict__ gcnt,
-                                                   const uint32_t *__restrict__ ghits,
-                                                   const uint8_t *__restrict__ decided, uint64_t n, int seed_len,
-                                                   int phase_lo, int phase_hi, uint32_t cap_q, uint32_t tbits,
-                                                   uint32_t slots3, uint32_t limit3, uint32_t vg, uint32_t limit1, uint32_t load,
-                                                   unsigned long long *ticket, uint64_t *__restrict__ kc_key_all,
-                                                   uint32_t *__restrict__ kc_ord_all, uint32_t kc_cap,
-                                                   LrmPhaseRes *__restrict__ phase_res, uint32_t *err_word,
-                                                   const uint64_t *__restrict__ list, const unsigned long long *__restrict__ list_n,
-                                                   uint64_t *gtab, uint32_t *glock, uint32_t g_slices, uint32_t g_slots) {
+void vote_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, const uint32_t *__restrict__ recq, const uint32_t *__restrict__ gcnt,
+                 const uint32_t *__restrict__ ghits, const uint8_t *__restrict__ decided, VoteItems v, uint32_t slots3, uint32_t limit3, uint32_t vg, uint32_t limit1, unsigned long long *ticket,
+                 uint64_t *__restrict__ kc_key_all, uint32_t *__restrict__ kc_ord_all, uint32_t kc_cap, uint32_t *err_word,
+                 const uint64_t *__restrict__ list, const unsigned long long *__restrict__ list_n, uint64_t *gtab, uint32_t *glock,
+                 uint32_t g_slices, uint32_t g_slots) {
     __shared__ VoteLds lds;
     __shared__ uint32_t g_H[VG_MAX], g_cnt[VG_MAX], g_ph[VG_MAX];
     __shared__ uint64_t g_id[VG_MAX];
@@ -954,12 +832,9 @@ void vote_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec,
     __shared__ Top2 s_top[4];
     __shared__ unsigned long long s_grp;
     __shared__ uint32_t s_slice;
-    const uint32_t tid = threadIdx.x, wave = tid >> 6;
-    const int lane = (int) (tid & 63);
-    const uint32_t P = (uint32_t) seed_len + 1;
-    const uint32_t np = (uint32_t) (phase_hi - phase_lo + 1);
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     // list mode: the items the fast kernel could not settle (vote_fast_kernel), by their item numbers
-    const uint64_t n_items = list ? (uint64_t) *list_n : n * (uint64_t) np;
+    const uint64_t n_items = list ? (uint64_t) *list_n : v.n * (uint64_t) v.np;
     const uint64_t n_groups = (n_items + vg - 1) / vg;
     const KeyScratch kc = {kc_key_all + (uint64_t) blockIdx.x * kc_cap, kc_ord_all + (uint64_t) blockIdx.x * kc_cap, kc_cap};
     const GlobalPool gp = {gtab, glock, g_slices, g_slots, &s_slice};
@@ -976,12 +851,12 @@ void vote_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec,
         uint32_t H = 0, c = 0, ph = 0;
         uint64_t id = 0;
         if (li < n_items) {
-            const ItemId ii = item_decode(item, np, phase_lo, P);
+            const ItemId ii = item_decode(item, v);
             ph = ii.iter; id = ii.id;                                        // (kept in LDS: decoding again per wavefront costs a 64-bit division)
             if (!(decided && decided[ii.read])) {
                 H = ghits[id];
                 c = gcnt[id];
-                if (H == 0) { LrmPhaseRes z = {0, 0, 0, 0, 0, 0}; phase_res[id] = z; }
+                if (H == 0) { LrmPhaseRes z = {0, 0, 0, 0, 0, 0}; v.phase_res[id] = z; }
             }
         }
         g_H[tid] = H; g_cnt[tid] = c; g_id[tid] = id; g_ph[tid] = ph;
@@ -991,16 +866,15 @@ void vote_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec,
         const uint32_t H = g_H[g];
         if (H == 0 || H > limit1) continue;
         const uint64_t id = g_id[g];
-        vote_item_wave<VOTE_U>(ix, rec + id * cap_q, recq + id * cap_q, g_cnt[g], H, g_ph[g], P, tbits, lane,
-                       lds.w[wave], &phase_res[id], load);
+        vote_item_wave<VOTE_U>(ix, v, Item{rec + id * v.cap_q, recq + id * v.cap_q, g_cnt[g], H, g_ph[g], &v.phase_res[id]}, lane, lds.w[wave]);
     }
     __syncthreads();
     for (uint32_t g = 0; g < vg; ++g) {                       // workgroup tier: one item after the other
         const uint32_t H = g_H[g];
         if (H <= limit1) continue;
         const uint64_t id = g_id[g];
-        vote_item_block<VOTE_U>(ix, rec + id * cap_q, recq + id * cap_q, g_cnt[g], H, g_ph[g], P, tbits, slots3,
-                        limit3, lds.b, s_wsum, s_top, &phase_res[id], err_word, load, kc, gp);
+        vote_item_block<VOTE_U>(ix, v, Item{rec + id * v.cap_q, recq + id * v.cap_q, g_cnt[g], H, g_ph[g], &v.phase_res[id]}, slots3, limit3, lds.b,
+                                s_wsum, s_top, err_word, kc, gp);
         __syncthreads();
     }
     __syncthreads();                                          // s_grp, g_* are rewritten by the next round
@@ -1017,8 +891,10 @@ struct VoteKnobs { uint32_t t3_limit, t3_slots, vg, t1_limit, load; uint64_t *bi
 template <int U>
 static void launch_vote_u(lrm_index *idx, lrm_workspace *ws, const LrmVoteLaunch &v, const VoteKnobs &k, hipStream_t stream) {
     LrmDevCounters *c = ws->d_counters;
-    const int r = v.round, seed_len = (int) v.seed_len;
-    const uint64_t items = v.n * (uint64_t) (v.phase_hi - v.phase_lo + 1);
+    const int r = v.round;
+    const uint32_t np = (uint32_t) (v.phase_hi - v.phase_lo + 1);
+    const uint64_t items = v.n * (uint64_t) np;
+    const VoteItems vi = {v.n, (uint32_t) v.seed_len + 1, np, (uint32_t) v.phase_lo, ws->cap_q, v.tbits, k.load, ws->d_phase};
     const uint64_t *list = nullptr;
     const unsigned long long *list_n = nullptr;
     // the fast kernels name a bucket by 32 bits of it (FastTable): exact on a text of fewer than 2^35 rows, and only taken there
@@ -1026,22 +902,21 @@ static void launch_vote_u(lrm_index *idx, lrm_workspace *ws, const LrmVoteLaunch
     if (v.mt->vote_fast && ident32) {
         uint64_t fblocks = (items + 4 * FAST_CH - 1) / (4 * FAST_CH);
         if (fblocks > LRM_VOTE_FAST_GRID) fblocks = LRM_VOTE_FAST_GRID;
-        hipLaunchKernelGGL(vote_fast_kernel<U>, dim3((uint32_t) fblocks), dim3(256), 0, stream, idx->view, ws->d_rec, ws->d_recq, ws->d_cnt,
-                           ws->d_hcount, v.decided, v.n, seed_len, v.phase_lo, v.phase_hi, ws->cap_q, v.tbits, k.load,
-                           &c->vote_fast_ticket[r], ws->d_phase, ws->d_redo, &c->vote_redo_n[r], ws->d_big, &c->vote_big_n[r]);
+        hipLaunchKernelGGL(vote_fast_kernel<U>, dim3((uint32_t) fblocks), dim3(256), 0, stream, idx->view, ws->d_rec, ws->d_recq, ws->d_cnt, ws->d_hcount,
+                           v.decided, vi, &c->vote_fast_ticket[r], ws->d_redo,
+                           &c->vote_redo_n[r], ws->d_big, &c->vote_big_n[r]);
         const uint64_t bblocks = items < 768 ? items : 768;                     // three workgroups per CU
-        hipLaunchKernelGGL(vote_fast_block_kernel<U>, dim3((uint32_t) bblocks), dim3(256), 0, stream, idx->view, ws->d_rec, ws->d_recq,
-                           ws->d_cnt, ws->d_hcount, seed_len, v.phase_lo, v.phase_hi, ws->cap_q, v.tbits, k.load, &c->vote_big_ticket[r],
-                           ws->d_phase, (const uint64_t *) ws->d_big, (const unsigned long long *) &c->vote_big_n[r], ws->d_redo,
-                           &c->vote_redo_n[r]);
+        hipLaunchKernelGGL(vote_fast_block_kernel<U>, dim3((uint32_t) bblocks), dim3(256), 0, stream, idx->view, ws->d_rec, ws->d_recq, ws->d_cnt, vi,
+                           &c->vote_big_ticket[r],
+                           (const uint64_t *) ws->d_big, (const unsigned long long *) &c->vote_big_n[r], ws->d_redo, &c->vote_redo_n[r]);
         list = ws->d_redo; list_n = &c->vote_redo_n[r];
     }
     uint64_t vblocks = (items + k.vg - 1) / k.vg;
     if (vblocks > LRM_VOTE_GRID) vblocks = LRM_VOTE_GRID;              // resident workgroups; groups of items go by ticket
     hipLaunchKernelGGL(vote_kernel<U>, dim3((uint32_t) vblocks), dim3(256), 0, stream, idx->view, ws->d_rec, ws->d_recq, ws->d_cnt,
-                       ws->d_hcount, v.decided, v.n, seed_len, v.phase_lo, v.phase_hi, ws->cap_q, v.tbits, k.t3_slots, k.t3_limit, k.vg,
-                       k.t1_limit, k.load, &c->vote_ticket[r], ws->d_kc_key, ws->d_kc_ord, (uint32_t) LRM_VOTE_KC_CAP, ws->d_phase,
-                       ws->d_err, list, list_n, k.big_tab, ws->d_glock, ws->g_slices, ws->g_slots);
+                       ws->d_hcount, v.decided, vi, k.t3_slots, k.t3_limit, k.vg, k.t1_limit,
+                       &c->vote_ticket[r], ws->d_kc_key, ws->d_kc_ord, (uint32_t) LRM_VOTE_KC_CAP, ws->d_err, list, list_n, k.big_tab, ws->d_glock,
+                       ws->g_slices, ws->g_slots);
 }
 
 int lrm_launch_vote(lrm_index *idx, lrm_workspace *ws, const LrmVoteLaunch &v, void *stream_) {

@@ -139,7 +139,50 @@ def _limit(rng):
 
     def prop(tops, streams):
         assert [t[1] for t in tops[0]] == [100, T1_LIMIT - 112] and [t[1] for t in tops[1]] == [100, T1_LIMIT - 111]
-    return pl.seq, reads, prop, None
+
+    def survivors(surv):
+        assert [len(x) for x in surv] == [T1_LIMIT, T1_LIMIT + 1]
+    return pl.seq, reads, prop, None, survivors
+
+
+def _second_chunk(rng):
+    """102 survivors: 64 unique seeds fill the first chunk of 64, the 24 repeat seeds (two hits each) follow in the second,
+    then 14 unique ones -- 126 hits, one item of the wavefront tier.  The first chunk stages nothing, so the repeat seeds
+    are staged by the second call of the chunk loop and the third rewrites the terminator behind them (appending behind
+    an earlier chunk's repeat seeds is "list-overflow": 64 in the first chunk, the 65th in the second).
+    The bucket w gets 12 votes: one hit each of ra (5 seeds, diagonal A + 3; ra[0] is survivor 64, the bucket's first hit)
+    and of rb (5 seeds, diagonal A: the bucket's smallest key) and two unique seeds (A + 5).  x ties with it at 12 unique votes and is first seen at survivor 90: w wins by ra[0]'s order alone, with rb's key."""
+    c = [K.segment(rng, 8) for _ in range(8)]
+    ra, rb, rc = K.kmers(rng, 5), K.kmers(rng, 5), K.kmers(rng, 14)
+    w, x = K.segment(rng, 2), K.segment(rng, 12)
+    Ra, Rb, Rc = K.read_of(ra), K.read_of(rb), K.read_of(rc)
+    read = b"".join(c) + Ra + Rc + Rb + w + x
+    ja = len(b"".join(c))
+    jb, jw = ja + len(Ra + Rc), ja + len(Ra + Rc + Rb)
+    A = 4096
+    assert A > len(read) + 64 and A % 16 == 0
+    # (second copies as in _list_case: a base on either side that differs from the read's spacers there)
+    flank = lambda i: b"ACGT"[(i + 1) % 4:(i + 1) % 4 + 1]
+    spec = [dict(name="c%d" % i, seq=c[i], at=64 if i == 0 else None) for i in range(8)]
+    spec += [dict(name="x", seq=x, at=3000), dict(name="Ra", seq=Ra, at=A + 3 + ja), dict(name="Rb", seq=Rb, at=A + jb), dict(name="w", seq=w, at=A + 5 + jw)]
+    spec += [dict(name="r%d" % i, seq=flank(i) + k + flank(i), copies=1 if i < 10 else 2) for i, k in enumerate(ra + rb + rc)]
+    pl = K.plant(spec, seed=8)
+
+    def prop(tops, streams):
+        assert len(streams[0]) == 78 + 2 * 24
+        kx = pl.where["x"][0] - (jw + len(w))
+        assert tops[0] == [(A, 12, A >> 4), (kx, 12, kx >> 4)]
+        in_w = [(i, k) for i, k in enumerate(streams[0]) if k >> 4 == A >> 4]
+        assert len(in_w) == 12 and in_w[0][1] == A + 3 and 64 <= in_w[0][0] < 66        # first seen: a hit of ra[0], survivor 64
+        assert sorted(k for _, k in in_w) == [A] * 5 + [A + 3] * 5 + [A + 5] * 2
+        # without the repeat seeds' hits x would win
+        assert K.vote_top2([k for k in streams[0] if k >> 4 != A >> 4 or k == A + 5])[1][0] == (kx, 12, kx >> 4)
+
+    def survivors(surv):
+        assert len(surv[0]) == 102 and sum(surv[0]) == 126 and 126 <= T1_LIMIT
+        assert [i for i, rr in enumerate(surv[0]) if rr > 1] == list(range(64, 88))    # every repeat seed in the second chunk
+        assert all(rr == 2 for rr in surv[0][64:88])
+    return pl.seq, [read], prop, 0, survivors
 
 
 def _no_repeat(rng):
@@ -163,13 +206,13 @@ def _only_repeats(rng):
 CASES = {"tie-both-arrival-orders": _tie, "three-tied-at-the-second-count": _second_tie,
          "repeat-hit-lowers-key-and-order": _repeat_hit_lowers, "list-at-capacity": _list_case(FAST_LIST),
          "list-overflow": _list_case(FAST_LIST + 1), "wrapped-next-to-plain": _wrapped, "t1-limit-and-one-more": _limit,
-         "no-repeat-seed": _no_repeat, "only-repeat-seeds": _only_repeats}
+         "no-repeat-seed": _no_repeat, "only-repeat-seeds": _only_repeats, "repeat-seeds-in-the-second-chunk": _second_chunk}
 
 
 def _cpu_side(name):
     """The case with its references, computed once: brute force in phase 0, the oracle's trace in every phase it runs."""
     import zlib
-    seq, reads, prop, redo = CASES[name](np.random.default_rng(zlib.crc32(name.encode())))
+    seq, reads, prop, redo, *survivors = CASES[name](np.random.default_rng(zlib.crc32(name.encode())))
     hi = index.HostIndex.build([np.frombuffer(bytes(seq), dtype=np.uint8)], hlen=8)
     assert bytes(hi.content()) == K.index_text([seq])
     K.check_sa(hi.content(), hi.sa())
@@ -185,9 +228,8 @@ def _cpu_side(name):
         rec = tr["phase_recs"][0]
         assert rec["iter"] == 0 and [rec["top1"], rec["top2"]] == t          # the two references agree
     prop(tops, streams)
-    if name == "t1-limit-and-one-more":
-        surv = [sum(1 for j, rr, _, _ in tr["seeds"] if j % (S + 1) == 0 and 0 < rr < THRES) for tr in traces]
-        assert surv == [T1_LIMIT, T1_LIMIT + 1]
+    for check in survivors:                  # the hit counts of the phase-0 survivors of every read, in seed order
+        check([[rr for j, rr, _, _ in sorted(tr["seeds"]) if j % (S + 1) == 0 and 0 < rr < THRES] for tr in traces])
     return dict(hi=hi, reads=reads, tops=tops, traces=traces, redo=redo)
 
 
