@@ -21,6 +21,7 @@
  *   params (run-time options), alnmain.h:10-13,                  lrm_index_options / lrm_map_options
  *     alnmain.c:574-588
  *   PART 3 result flags, alnmain.c:458-477                      lrm_result_flags (lrm_result_flags_mapq: a real MAPQ)
+ *   (no counterpart: the reference prints neither NM nor MD)     lrm_aln_summary_dev, lrm_aln_diff_dev (lrm_md_format: MD:Z)
  *   context_destroy(), accaln.c:7-43                            lrm_index_free
  *   host batch loop over devices, alnmain.c:302-330             lrm_index_upload_multi (+ the same batch calls)
  *   pair_end(), alnmain.c:554-557 (unimplemented, returns -1)   lrm_pair_end
@@ -392,6 +393,28 @@ int lrm_map_batch_submit_ex(lrm_index *idx, char *reads_buf, uint64_t stride, co
                             uint8_t *store_mem, uint64_t store_stride, int *score_out, lrm_seq_meta *meta_out,
                             int *meta_r_out, const lrm_map_options *opt, const lrm_batch_extras *ex, lrm_ticket **ticket_out);
 
+/* The DIFFERENCE EVENTS of a host-buffer batch (above; docs/GACT_SPEC.md, "Difference events and MD:Z").  Read i's events are
+ * events_out[off_out[i] .. off_out[i] + cnt_out[i]).  The stage runs per extension group (every share of a group handle
+ * too), and a group takes its place in events_out when it is collected: the offsets of different groups come in any order.
+ * A group whose events do not fit below cap gives its reads off_out = UINT64_MAX with their true counts; *needed_out is the
+ * batch's total in any case and the wait still returns 0 -- the caller compares needed with cap.  The request runs the
+ * summary stage whether lrm_batch_extras.summary_out is given or not.  struct_size: sizeof(lrm_batch_diff) of the caller's header. */
+typedef struct lrm_batch_diff {
+    uint32_t struct_size, reserved;
+    uint64_t *off_out;                    /* n entries */
+    uint32_t *cnt_out;                    /* n entries: n_x + n_del of every read */
+    uint32_t *events_out;                 /* cap events (may be NULL when cap == 0: counting only) */
+    uint64_t cap;
+    uint64_t *needed_out;                 /* one entry, written when the wait returns */
+} lrm_batch_diff;
+/* lrm_map_batch_submit_ex plus the events (diff == NULL: exactly lrm_map_batch_submit_ex).  Every other output is the same
+ * bytes with them or without. */
+int lrm_map_batch_submit_ex2(lrm_index *idx, char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
+                             lrm_params p, lrm_gact_params gp, lrm_entry *best_out, lrm_cigar *cig_out,
+                             uint8_t *store_mem, uint64_t store_stride, int *score_out, lrm_seq_meta *meta_out,
+                             int *meta_r_out, const lrm_map_options *opt, const lrm_batch_extras *ex,
+                             const lrm_batch_diff *diff, lrm_ticket **ticket_out);
+
 /* ---------------------------------------------------------------------------
  * Batch entry points with DEVICE buffers (inputs/outputs resident in HBM;
  * asynchronous on `stream`, a hipStream_t passed as void*, may be NULL).
@@ -471,6 +494,37 @@ int lrm_extend_batch_clipped_dev(lrm_index *idx, lrm_workspace *ws, char *d_read
 int lrm_aln_summary_dev(lrm_index *idx, const uint8_t *d_store, uint64_t store_stride,
                         const int32_t *d_n_ops, const int32_t *d_score, const int32_t *d_meta_r,
                         uint64_t n, lrm_aln_summary *d_out, void *stream);
+
+/* DIFFERENCE EVENTS (docs/GACT_SPEC.md, "Difference events and MD:Z"): what MD:Z needs and the run-length text has lost --
+ * one 32-bit word per 'X' or 'D' column of an alignment, in column order:
+ *   bits 0-7    the reference base of the column, content[meta.loc + t] as stored (0 for a position at or behind the end of the text)
+ *   bits 8-9    the kind: LRM_DIFF_X, LRM_DIFF_D_OPEN (a 'D' whose previous column is not 'D'), LRM_DIFF_D_MORE
+ *   bits 10-31  the '=' columns before it
+ * A read has n_x + n_del events of its summary record; a read without an alignment has none.  The events of a batch are
+ * packed per read at exclusive prefix sums of those counts.  store_stride <= 2^22 (checked): the '=' count fits its bits. */
+#define LRM_DIFF_X 0u
+#define LRM_DIFF_D_OPEN 1u
+#define LRM_DIFF_D_MORE 2u
+#define LRM_DIFF_BASE(w) ((uint32_t) (w) & 0xFFu)
+#define LRM_DIFF_KIND(w) (((uint32_t) (w) >> 8) & 3u)
+#define LRM_DIFF_EQ_BEFORE(w) ((uint32_t) (w) >> 10)
+/* d_off[0 .. n]: exclusive prefix sums of n_x + n_del over the n summary records in device memory (d_off[n]: the batch's
+ * total).  One small scan kernel on `stream`. */
+int lrm_aln_diff_offsets_dev(const lrm_aln_summary *d_summary, uint64_t n, uint64_t *d_off, void *stream);
+/* The events of a batch whose op bytes sit in device memory: call it behind any of the three extension calls and the summary
+ * (and lrm_aln_diff_offsets_dev) on the same stream, with the extension's d_store, store_stride, d_n_ops, d_score, d_meta_r,
+ * d_meta.  Read i's events go to d_events[d_off[i] .. d_off[i + 1]); a read with d_off[i + 1] > cap writes nothing (cap: the
+ * room of d_events, in events).  One streaming kernel: a byte of ops and a byte of text read per column; no workspace. */
+int lrm_aln_diff_dev(lrm_index *idx, const uint8_t *d_store, uint64_t store_stride, const int32_t *d_n_ops,
+                     const int32_t *d_score, const int32_t *d_meta_r, const lrm_seq_meta *d_meta, uint64_t n,
+                     const uint64_t *d_off, uint64_t cap, uint32_t *d_events, void *stream);
+/* The rule on the host, for callers that hold op bytes and the text they were aligned against: target[0] is the first
+ * aligned target base (content + meta.loc), target_len what is left of the text from there.  events_out: room for every
+ * 'X' and 'D' column of ops (NULL: count only).  Returns the number of events; n_ops <= 0: 0.  Usable without a GPU. */
+int64_t lrm_aln_diff_host(const uint8_t *ops, int n_ops, const uint8_t *target, uint64_t target_len, uint32_t *events_out);
+/* MD:Z text of one read from its events and the n_eq of its summary record, NUL-terminated ("10A0C5", "5^AC0T").  Returns
+ * the text length, < 0 when buf (buflen bytes, the NUL included) is too small. */
+int lrm_md_format(const uint32_t *events, uint64_t count, uint32_t n_eq, char *buf, int buflen);
 
 /* SPLIT READS (lrm_map_options.split; docs/GACT_SPEC.md, "Split reads"): the soft-clipped ends of a batch that went through
  * the anchored extension with end clipping, mapped as reads of their own.  For read i with n = lens[i] bases, R the read as

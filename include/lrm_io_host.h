@@ -5,7 +5,7 @@
  *
  *   reads_load + refactor_reads_seq   accaln.c:45-58, alnmain.c:87-103   -> lrm_reader_*
  *   gen_sam_header                    alnmain.c:62-75                    -> lrm_sam_header
- *   SAM record printing               alnmain.c:485-527                  -> lrm_sam_format (_split, _mapq)
+ *   SAM record printing               alnmain.c:485-527                  -> lrm_sam_format (_split, _mapq, _md)
  *   parse_cigar (gact submodule, source absent; PARITY UNPINNED)         -> lrm_parse_cigar
  *   single_end                        alnmain.c:277-551                  -> lrm_accaln
  *   (no counterpart: the reference prints SAM only)                      -> lrm_paf_format, lrm_accaln_paf
@@ -79,6 +79,16 @@ char *lrm_sam_format_split(const lrm_read_batch *reads, const lrm_mta_entry *mta
 char *lrm_sam_format_mapq(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig,
                           const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t n, int cigar_is_text,
                           int revcomp_here, const lrm_split_out *split, const lrm_mapq *mq, uint64_t *len_out);
+/* The same with NM:i and MD:Z (docs/GACT_SPEC.md, "Difference events and MD:Z"): sum, diff_off, diff_cnt and events are what
+ * lrm_map_batch_submit_ex2 returned for this batch -- the summary records, and read i's events at events[diff_off[i] ..
+ * diff_off[i] + diff_cnt[i]) (events == NULL: exactly the lines of lrm_sam_format_mapq).  A mapped read's primary line gains
+ * NM:i:<n_x + n_ins + n_del>\tMD:Z:<lrm_md_format's text> behind ED:I (behind v1:i / v2:i with mq); a read without an
+ * alignment, or one whose events found no room (diff_off[i] == UINT64_MAX), gains nothing.  Supplementary lines gain nothing:
+ * the segment batch of lrm_split_out has no records. */
+char *lrm_sam_format_md(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig,
+                        const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t n, int cigar_is_text,
+                        int revcomp_here, const lrm_split_out *split, const lrm_mapq *mq, const lrm_aln_summary *sum,
+                        const uint64_t *diff_off, const uint32_t *diff_cnt, const uint32_t *events, uint64_t *len_out);
 
 /* PAF (docs/GACT_SPEC.md, "Alignment summary and PAF"): one line per MAPPED read -- an unmapped one (meta_r == 0 or score == -1)
  * prints nothing --, every number of it taken from the read's alignment summary record (sum: required, what
@@ -112,6 +122,12 @@ int lrm_accaln_opt(const char *genome, const char *reads_path, const char *sam_p
 int lrm_accaln_mapq(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
                     lrm_gact_params gp, int device, long rg_id, uint64_t *total, uint64_t *valid,
                     const lrm_map_options *opt, int mapq);
+/* ... with NM:i and MD:Z (md == 0: lrm_accaln_mapq): every batch goes through lrm_map_batch_submit_ex2 and is printed by
+ * lrm_sam_format_md.  The event buffer of a batch has room for the bound, the sum of its store strides (a read has no more
+ * events than columns; pages the events never touch cost nothing); more events than that is an error of the flow. */
+int lrm_accaln_md(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
+                  lrm_gact_params gp, int device, long rg_id, uint64_t *total, uint64_t *valid,
+                  const lrm_map_options *opt, int mapq, int md);
 /* The flow of lrm_accaln_mapq with PAF output: every batch goes through lrm_map_batch_submit_ex with summary_out (and
  * mapq_out when mapq != 0) and is printed by lrm_paf_format; the file has no header.  total / valid count as in the SAM flow.
  * opt->split != 0 is refused (-1): PAF lines for split segments need summary records of the segment batch, which the

@@ -50,7 +50,15 @@ SYMBOLS = {
     "lrm_map_batch_submit_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, Params, GactParams,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.POINTER(MapOptions), C.POINTER(BatchExtras), C.POINTER(C.c_void_p)]),
+    "lrm_map_batch_submit_ex2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, Params, GactParams,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(MapOptions), C.POINTER(BatchExtras), C.POINTER(BatchDiff), C.POINTER(C.c_void_p)]),
     "lrm_map_batch_wait": (C.c_int, [C.c_void_p]),
+    "lrm_aln_diff_offsets_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "lrm_aln_diff_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                   C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "lrm_aln_diff_host": (C.c_int64, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "lrm_md_format": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_int]),
     "lrm_aln_summary_host": (None, [C.c_void_p, C.c_int, C.POINTER(AlnSummary)]),
     "lrm_aln_summary_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                       C.c_void_p, C.c_void_p]),
@@ -152,6 +160,11 @@ SYMBOLS = {
                                           C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(SplitOut), u64p]),
     "lrm_sam_format_mapq": (C.c_void_p, [C.POINTER(ReadBatch), C.POINTER(MtaEntry), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(SplitOut), C.c_void_p, u64p]),
+    "lrm_sam_format_md": (C.c_void_p, [C.POINTER(ReadBatch), C.POINTER(MtaEntry), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(SplitOut), C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, u64p]),
+    "lrm_accaln_md": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, Params, GactParams, C.c_int, C.c_long, u64p, u64p,
+                                C.POINTER(MapOptions), C.c_int, C.c_int]),
     "lrm_paf_format": (C.c_void_p, [C.POINTER(ReadBatch), C.POINTER(MtaEntry), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, u64p]),
     "lrm_accaln_paf": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, Params, GactParams, C.c_int, u64p, u64p,

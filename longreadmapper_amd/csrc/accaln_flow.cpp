@@ -1,4 +1,4 @@
-// accaln_flow.cpp -- `accaln genome reads` on the GPU path (lrm_accaln, lrm_accaln_opt, lrm_accaln_mapq, lrm_accaln_paf,
+// accaln_flow.cpp -- `accaln genome reads` on the GPU path (lrm_accaln, lrm_accaln_opt, lrm_accaln_mapq, lrm_accaln_md, lrm_accaln_paf,
 // include/lrm_io_host.h): single_end() (alnmain.c:277-551) as a pipeline of threads around the asynchronous batch calls.
 // Host-side C++; the kernels are reached only through the C-ABI.
 //
@@ -109,9 +109,14 @@ struct BatchSet {
     lrm_ticket *ticket = nullptr;
     SplitBufs sp;                                // split reads: the second pass over this batch's clipped ends (lrm_split_batch)
     std::vector<lrm_mapq> mq;                    // lrm_accaln_mapq: the records of the batch
-    std::vector<lrm_aln_summary> sum;            // lrm_accaln_paf: the alignment summary records of the batch
+    std::vector<lrm_aln_summary> sum;            // lrm_accaln_paf, lrm_accaln_md: the alignment summary records of the batch
+    // lrm_accaln_md: the difference events of the batch.  The buffer has room for the bound (a read has no more events than
+    // columns) and is never cleared: the pages the events do not reach are never touched
+    std::vector<uint64_t> diff_off;
+    std::vector<uint32_t> diff_cnt;
+    uint32_t *events = nullptr; uint64_t events_cap = 0, events_needed = 0;
     BatchSet() { memset(&b, 0, sizeof(b)); }
-    ~BatchSet() { lrm_host_free(reads_pin); lrm_host_free(store_pin); free(store_pg); }
+    ~BatchSet() { lrm_host_free(reads_pin); lrm_host_free(store_pin); free(store_pg); free(events); }
 };
 
 struct TextBatch { std::vector<std::string> parts; };   // the SAM text of one batch, one part per formatting thread
@@ -139,6 +144,7 @@ struct AccalnRun {
     int device;
     const bool mapq;                                     // the mapping-quality records come back with every batch and are printed
     const bool paf;                                      // PAF instead of SAM: the summary records come back too, no header
+    const bool md;                                       // NM:i and MD:Z: the summary records and the difference events come back and are printed
     const bool verbose = getenv("LRM_HOST_VERBOSE") != nullptr;            // stage times on stderr (tuning aid)
     lrm_map_options mopt;
     bool split = false;                                  // after a batch's wait its clipped ends go through lrm_split_batch
@@ -171,8 +177,8 @@ struct AccalnRun {
     double t_write = 0;                                  // flusher
     uint64_t out_off = 0;                                // flusher (main sets it behind the header before the threads start)
 
-    AccalnRun(lrm_params p_, lrm_gact_params gp_, int device_, bool mapq_, bool paf_ = false)
-        : p(p_), gp(gp_), device(device_), mapq(mapq_), paf(paf_), bs(p_.batch_size ? p_.batch_size : 1000) {}
+    AccalnRun(lrm_params p_, lrm_gact_params gp_, int device_, bool mapq_, bool paf_ = false, bool md_ = false)
+        : p(p_), gp(gp_), device(device_), mapq(mapq_), paf(paf_), md(md_), bs(p_.batch_size ? p_.batch_size : 1000) {}
 
     // op bytes per read: alnmain.c:316-320, a multiple of 16; the anchored mode's targets are an eighth longer than the reads
     uint64_t store_stride_of(uint64_t max_len) const {
@@ -293,7 +299,8 @@ struct AccalnRun {
                     paf_format_parts(pb, io_threads, tb->parts);
                 } else {
                     const SamBatch sb = {&s->b, hi.mta, hi.mta_len, s->cig.data(), s->score.data(), s->meta.data(), s->meta_r.data(), n,
-                                         /* cigar_is_text */ true, /* revcomp_here */ true, split ? &s->sp.out : nullptr, mapq ? s->mq.data() : nullptr};
+                                         /* cigar_is_text */ true, /* revcomp_here */ true, split ? &s->sp.out : nullptr, mapq ? s->mq.data() : nullptr,
+                                         md ? s->sum.data() : nullptr, md ? s->diff_off.data() : nullptr, md ? s->diff_cnt.data() : nullptr, md ? s->events : nullptr};
                     sam_format_parts(sb, io_threads, tb->parts);
                 }
                 t_fmt += now() - t0;
@@ -356,6 +363,10 @@ struct AccalnRun {
         inflight.pop_front();
         const double t0 = now();
         int mrc = lrm_map_batch_wait(s->ticket);
+        if (!mrc && md && s->events_needed > s->events_cap) {
+            lrm_set_error("difference events: a batch needs %llu, more than the bound of %llu", (unsigned long long) s->events_needed, (unsigned long long) s->events_cap);
+            mrc = -1;
+        }
         if (!mrc && split) mrc = split_pass(s);
         t_map += now() - t0;
         if (verbose) fprintf(stderr, "[lrm accaln] %.3f waited %.3f s for a batch of %llu\n", now() - t_upload, now() - t0, (unsigned long long) s->b.n);
@@ -369,8 +380,17 @@ struct AccalnRun {
         const size_t n = (size_t) s->b.n;
         s->best.resize(n); s->cig.resize(n); s->score.resize(n); s->meta_r.resize(n); s->meta.resize(n);
         if (mapq) s->mq.resize(n);
-        if (paf) s->sum.resize(n);
+        if (paf || md) s->sum.resize(n);
         s->sstride = store_stride_of(s->b.max_len);
+        if (md) {
+            s->diff_off.resize(n); s->diff_cnt.resize(n);
+            if (n * s->sstride > s->events_cap) {
+                free(s->events);
+                s->events_cap = n * s->sstride;
+                s->events = (uint32_t *) malloc((size_t) s->events_cap * sizeof(uint32_t));
+                if (!s->events) { s->events_cap = 0; lrm_set_error("out of memory"); return false; }
+            }
+        }
         if (s->pin_ready.load(std::memory_order_acquire) && n * s->sstride <= s->store_cap) { s->store = s->store_pin; return true; }
         if (n * s->sstride > s->store_pg_cap) {
             free(s->store_pg);
@@ -389,10 +409,11 @@ struct AccalnRun {
             if (err.get()) { recycle(s); continue; }                          // drain what the loader already parsed
             if (!fit_results(s)) { err.set(-1); recycle(s); continue; }
             const double t0 = now();
-            const lrm_batch_extras ex = {(uint32_t) sizeof(lrm_batch_extras), 0, mapq ? s->mq.data() : nullptr, paf ? s->sum.data() : nullptr};
-            const int src = lrm_map_batch_submit_ex(gpu, s->b.seqs, s->b.stride, s->b.lens, s->b.n, p, gp, s->best.data(), s->cig.data(),
+            const lrm_batch_extras ex = {(uint32_t) sizeof(lrm_batch_extras), 0, mapq ? s->mq.data() : nullptr, paf || md ? s->sum.data() : nullptr};
+            const lrm_batch_diff df = {(uint32_t) sizeof(lrm_batch_diff), 0, s->diff_off.data(), s->diff_cnt.data(), s->events, s->events_cap, &s->events_needed};
+            const int src = lrm_map_batch_submit_ex2(gpu, s->b.seqs, s->b.stride, s->b.lens, s->b.n, p, gp, s->best.data(), s->cig.data(),
                                                     s->store, s->sstride, s->score.data(), s->meta.data(), s->meta_r.data(), &mopt,
-                                                    &ex, &s->ticket);
+                                                    &ex, md ? &df : nullptr, &s->ticket);
             t_map += now() - t0;
             if (verbose) fprintf(stderr, "[lrm accaln] %.3f submitted %llu reads (%s store) in %.3f s\n", now() - t_upload, (unsigned long long) s->b.n, s->store == s->store_pin ? "pinned" : "pageable", now() - t0);
             if (!first_submitted) { { std::lock_guard<std::mutex> lk(dims_m); first_submitted = true; } dims_cv.notify_all(); }
@@ -443,8 +464,8 @@ struct AccalnRun {
 
 // one run of the flow: SAM (lrm_accaln*) or PAF (lrm_accaln_paf) into out_path
 static int accaln_run(const char *genome, const char *reads_path, const char *out_path, lrm_params p, lrm_gact_params gp, int device,
-                      long rg_id, uint64_t *total_out, uint64_t *valid_out, const lrm_map_options *user, bool mapq, bool paf) {
-    AccalnRun r(p, gp, device, mapq, paf);
+                      long rg_id, uint64_t *total_out, uint64_t *valid_out, const lrm_map_options *user, bool mapq, bool paf, bool md = false) {
+    AccalnRun r(p, gp, device, mapq, paf, md);
     if (r.take_options(user)) return -1;
     if (lrm_host_index_read(genome, &r.hi)) return -1;
     int rc = r.begin(reads_path, out_path, rg_id);
@@ -459,6 +480,12 @@ extern "C" int lrm_accaln_mapq(const char *genome, const char *reads_path, const
                                lrm_gact_params gp, int device, long rg_id, uint64_t *total_out, uint64_t *valid_out,
                                const lrm_map_options *user, int mapq) {
     return accaln_run(genome, reads_path, sam_path, p, gp, device, rg_id, total_out, valid_out, user, mapq != 0, false);
+}
+// md: the summary records and the difference events come back with every batch, NM:i and MD:Z print them (lrm_sam_format_md)
+extern "C" int lrm_accaln_md(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
+                             lrm_gact_params gp, int device, long rg_id, uint64_t *total_out, uint64_t *valid_out,
+                             const lrm_map_options *user, int mapq, int md) {
+    return accaln_run(genome, reads_path, sam_path, p, gp, device, rg_id, total_out, valid_out, user, mapq != 0, false, md != 0);
 }
 // PAF: the alignment summary records come back with every batch, lrm_paf_format's lines print them; no header
 extern "C" int lrm_accaln_paf(const char *genome, const char *reads_path, const char *paf_path, lrm_params p, lrm_gact_params gp,

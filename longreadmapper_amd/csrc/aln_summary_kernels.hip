@@ -3,43 +3,21 @@
 // read per column, 32 bytes written per read.
 #include <hip/hip_runtime.h>
 #include "lrm_hip_util.h"
+#include "aln_diff_step.h"
 
 namespace {
 
-constexpr uint32_t ONES = 0x01010101u, LOW7 = 0x7F7F7F7Fu, TOPS = 0x80808080u;
+constexpr uint32_t TOPS = 0x80808080u;
 
-// 0x80 in every byte of w that equals c, 0 in every other: the EXACT zero-byte test on w ^ cccc (the cheaper form,
-// (t - 0x01010101) & ~t & 0x80808080, lets a borrow run into the byte above a match: 'I' 'H' would count twice)
-__device__ __forceinline__ uint32_t bytes_equal(uint32_t w, uint32_t c) {
-    const uint32_t t = w ^ (c * ONES);
-    return ~(((t & LOW7) + LOW7) | t | LOW7);
-}
+// the exact byte mask of both kernels over op bytes (aln_diff_step.h)
+__device__ __forceinline__ uint32_t bytes_equal(uint32_t w, uint32_t c) { return diff_bytes_equal(w, c); }
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
     return (uint32_t) __builtin_amdgcn_readlane((int) wave_incl_scan(v), 63);
 }
 
-// 16 op bytes of a row from column c0 on.  Rows start at any byte (the hardware takes the unaligned dwords, as in
-// pack_rows_kernel).  load_step: a step that lies whole inside the row, one 16-byte load per lane.  load_last_step: the
-// row's last step -- zeros from column n on, and nothing at or behind ops + n is read.
-__device__ __forceinline__ uint4 load_step(const uint8_t *__restrict__ ops, uint32_t c0) {
-    uint4 v;
-    __builtin_memcpy(&v, ops + c0, 16);
-    return v;
-}
-__device__ __forceinline__ uint32_t load_word(const uint8_t *__restrict__ ops, uint32_t col, uint32_t n) {
-    uint32_t v = 0;
-    if (col + 4 <= n) __builtin_memcpy(&v, ops + col, 4);
-    else if (col < n) {
-        v = ops[col];
-        if (col + 1 < n) v |= (uint32_t) ops[col + 1] << 8;
-        if (col + 2 < n) v |= (uint32_t) ops[col + 2] << 16;
-    }
-    return v;
-}
-__device__ __forceinline__ uint4 load_last_step(const uint8_t *__restrict__ ops, uint32_t c0, uint32_t n) {
-    if (c0 + 16 <= n) return load_step(ops, c0);
-    return make_uint4(load_word(ops, c0, n), load_word(ops, c0 + 4, n), load_word(ops, c0 + 8, n), load_word(ops, c0 + 12, n));
-}
+// 16 op bytes of a row from column c0 on (lrm_hip_util.h): a step whole inside the row, and the row's last step
+__device__ __forceinline__ uint4 load_step(const uint8_t *__restrict__ ops, uint32_t c0) { return row_load_step<uint32_t>(ops, c0); }
+__device__ __forceinline__ uint4 load_last_step(const uint8_t *__restrict__ ops, uint32_t c0, uint32_t n) { return row_load_last_step<uint32_t>(ops, c0, n); }
 
 // what a wavefront has counted so far in its row; `carry`: the last byte of the previous step (uniform), 0 before column 0
 struct RowCounts {

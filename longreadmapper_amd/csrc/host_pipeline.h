@@ -21,6 +21,8 @@ struct lrm_ticket {
     int pending = 0;
     int rc = 0;
     std::string err;
+    std::atomic<uint64_t> diff_total{0};     // difference events: every extension group adds its events and takes what was there as its base
+    uint64_t *diff_needed_out = nullptr;     // ... and the wait writes the batch's total here
     void part_done(int code, const std::string &msg) {
         std::lock_guard<std::mutex> g(m);
         if (code && !rc) { rc = code; err = msg; }
@@ -88,11 +90,14 @@ struct MapJob {
     lrm_anchor *anchor_out;           // anchored mode: the anchor records too (null: they stay in the workspace)
     lrm_mapq *mapq_out;               // mapping quality: the stage runs behind every seed sub-batch, the records come down with the small arrays (null: no stage)
     lrm_aln_summary *summary_out;     // alignment summary: the stage runs behind every group's extension, the records come down likewise (null: no stage)
+    // difference events (lrm_batch_diff): per read where its events are and how many (null: no stage); the event buffer and
+    // its room are the batch's, shared by every slice
+    uint64_t *diff_off; uint32_t *diff_cnt; uint32_t *diff_events; uint64_t diff_cap;
     MapJob slice(uint64_t o, uint64_t m) const {        // reads [o, o + m): every array of the caller moves on by o elements
         MapJob j = *this;
         j.n = m;
         auto adv = [o](auto *&ptr, uint64_t pitch = 1) { if (ptr) ptr += o * pitch; };
-        adv(j.reads, stride); adv(j.lens); adv(j.best_in); adv(j.best_out); adv(j.anchor_out); adv(j.mapq_out); adv(j.summary_out);
+        adv(j.reads, stride); adv(j.lens); adv(j.best_in); adv(j.best_out); adv(j.anchor_out); adv(j.mapq_out); adv(j.summary_out); adv(j.diff_off); adv(j.diff_cnt);
         adv(j.cig); adv(j.store_mem, store_stride); adv(j.score); adv(j.meta); adv(j.meta_r);
         return j;
     }
@@ -117,6 +122,7 @@ struct Slot {
     WsPtr ws_ext[N_EXT_STREAMS];                   // extension scratch (group sized), one per extension stream
     DevSlot dev[N_ARRAYS];                         // device mirrors of the caller's arrays
     DevSlot dense[2], offs[2];                     // dense result image + offset table, alternating over the groups
+    DevSlot diff_ev, diff_off;                     // difference events of a group and their offsets (the download stream runs group after group)
     Event ev_dense[2];                             // the last transfer out of dense[b] has drained
     bool dense_used[2] = {false, false};
     PinSlot h_small;                               // pinned staging of the small result arrays and offset tables (SliceJob::stage_row bytes per read)
@@ -140,6 +146,8 @@ struct SliceJob {
     uint64_t dstride = 0;
     bool seed_only = false;
     bool want_anchor = false, want_mapq = false, want_summary = false, text = false;     // the anchor, mapping-quality and summary records, run-length CIGAR text
+    bool want_diff = false;                                          // the difference events (they need the summary records on the host)
+    uint64_t stage_diff = 0;                                         // staging of a unit's event offsets (m + 1 x u64)
     SliceArray arr[N_ARRAYS] = {};
     uint64_t stage_off = 0, stage_len = 0, stage_row = 0;           // staging of a unit's offset table (2 x u64) and lengths (2 x u32); bytes per read in all
     void plan_arrays();

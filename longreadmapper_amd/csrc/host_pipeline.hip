@@ -240,7 +240,8 @@ void SliceJob::plan_arrays() {
     const bool seed = (j.mode & DO_SEED) != 0, ext = (j.mode & DO_EXTEND) != 0;
     want_anchor = j.anchor_out && ext && mt.anchored;
     want_mapq = j.mapq_out && seed;
-    want_summary = j.summary_out && ext;
+    want_diff = j.diff_off && ext;
+    want_summary = (j.summary_out || want_diff) && ext;              // (the events are sized and placed by the records' counts)
     text = mt.cigar_text != 0 && ext;
     //               bytes per read        on the device  downloaded   the caller's array
     arr[A_BEST]   = {sizeof(lrm_entry),    true,          seed,        j.best_out};
@@ -262,6 +263,7 @@ void SliceJob::plan_arrays() {
     for (int a = 0; a < N_SMALL; ++a) if (arr[a].down) arr[a].stage = place(arr[a].elem);
     stage_off = place(2 * sizeof(uint64_t));
     stage_len = place(2 * sizeof(uint32_t));
+    if (want_diff) stage_diff = place(2 * sizeof(uint64_t));         // m + 1 entries fit the 2 m of a unit
     stage_row = (at + 7) & ~7ull;
 }
 
@@ -316,6 +318,11 @@ int plan_and_issue(LrmHostCtx &c, SliceJob &sj) {
     if (j.mode & DO_EXTEND)
         for (int b = 0; b < 2; ++b)
             if (S.dense[b].ensure(unit_max * (dstride + j.stride + 32)) || S.offs[b].ensure(unit_max * 2 * 12)) { lrm_set_error("device allocation failed"); return -1; }
+    // (the event buffer of a group like the buffers above, so that the collector does not reallocate: sized here for one event
+    //  in four of the longest read's bases per read -- twice what ONT reads give -- and never below what an earlier group of
+    //  this slot needed; only a group beyond that grows it in the collector)
+    if (sj.want_diff && (S.diff_off.ensure((unit_max + 1) * sizeof(uint64_t)) ||
+                         S.diff_ev.ensure(unit_max * ((uint64_t) sj.max_len / 4 + 64) * sizeof(uint32_t)))) { lrm_set_error("allocation for the difference events failed"); return -1; }
     if (S.h_small.ensure(n * sj.stage_row)) { lrm_set_error("pinned staging allocation failed"); return -1; }
     S.dense_used[0] = S.dense_used[1] = false;
 
@@ -369,6 +376,38 @@ int plan_and_issue(LrmHostCtx &c, SliceJob &sj) {
     return 0;
 }
 
+// ---- collector: the difference events of one unit (docs/GACT_SPEC.md, "Difference events and MD:Z") --------------------------
+// The unit's summary records are on the host and its op bytes still in HBM: the counts n_x + n_del become offsets, the unit
+// takes its place in the caller's buffer with one atomic add on the batch's running total, the kernel writes into a device
+// buffer of the unit's true total and one copy brings the events down (behind everything on the download stream).  A unit
+// that does not fit leaves off = UINT64_MAX with the true counts; the total goes on counting.
+int collect_diff(LrmHostCtx &c, SliceJob &sj, const Range &u, const lrm_aln_summary *h_sum, uint64_t *h_doff) {
+    const MapJob &j = sj.j;
+    Slot &S = *sj.slot;
+    DevSlot *const d = S.dev;
+    const uint64_t m = u.m, o = u.off;
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < m; ++i) {
+        h_doff[i] = total;
+        j.diff_cnt[o + i] = h_sum[i].n_x + h_sum[i].n_del;
+        total += (uint64_t) h_sum[i].n_x + h_sum[i].n_del;
+    }
+    h_doff[m] = total;
+    const uint64_t base = sj.ticket->diff_total.fetch_add(total);
+    const bool fits = base + total <= j.diff_cap;
+    for (uint64_t i = 0; i < m; ++i) j.diff_off[o + i] = fits ? base + h_doff[i] : UINT64_MAX;
+    if (!fits || total == 0) return 0;
+    if (S.diff_ev.ensure((total + total / 4) * sizeof(uint32_t))) { lrm_set_error("allocation for the difference events failed"); return -1; }
+    HIPCHK(hipMemcpyAsync(S.diff_off.p, h_doff, (m + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c.down));
+    if (lrm_launch_aln_diff((const uint8_t *) d[A_STORE].p + o * sj.dstride, sj.dstride, (const int32_t *) d[A_NOPS].p + o,
+                            (const int32_t *) d[A_SCORE].p + o, (const int32_t *) d[A_MR].p + o, (const lrm_seq_meta *) d[A_META].p + o,
+                            c.idx->view.content, c.idx->view.con_len, m, (const uint64_t *) S.diff_off.p, total, (uint32_t *) S.diff_ev.p, c.down)) return -1;
+    uint8_t *dst = (uint8_t *) (j.diff_events + base);
+    if (is_pinned(dst)) { HIPCHK(hipMemcpyAsync(dst, S.diff_ev.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, c.down)); return 0; }
+    return d2h_ring(c, (const uint8_t *) S.diff_ev.p, total * sizeof(uint32_t), nullptr, nullptr, nullptr, 0, dst,
+                    sj.mt.copy_threads ? (int) sj.mt.copy_threads : c.copy_threads, []() { return 0; });
+}
+
 // ---- collector: one unit [off, off + m) of the slice, once `done` has fired ------------------------------------------------
 int collect(LrmHostCtx &c, SliceJob &sj, size_t g) {
     const MapJob &j = sj.j;
@@ -395,6 +434,7 @@ int collect(LrmHostCtx &c, SliceJob &sj, size_t g) {
         if (A.down && A.host) memcpy((uint8_t *) A.host + o * A.elem, staged(a), m * A.elem);
     }
     if (!(j.mode & DO_EXTEND)) return 0;
+    if (sj.want_diff && collect_diff(c, sj, u, (const lrm_aln_summary *) staged(A_SUMMARY), (uint64_t *) (hs + m * sj.stage_diff))) return -1;
     const int32_t *h_nops = (const int32_t *) staged(A_NOPS), *h_score = (const int32_t *) staged(A_SCORE), *h_mr = (const int32_t *) staged(A_MR);
     const lrm_seq_meta *h_meta = (const lrm_seq_meta *) staged(A_META);
     const uint32_t *h_tlen = (const uint32_t *) staged(A_TLEN);       // (read with cigar_text only)

@@ -12,6 +12,7 @@
 #include <omp.h>
 #include "lrm_hip_util.h"
 #include "extend_stage.h"
+#include "aln_diff_step.h"
 
 static thread_local char g_err[512] = "";
 
@@ -332,6 +333,57 @@ extern "C" int lrm_aln_summary_dev(lrm_index *idx, const uint8_t *d_store, uint6
     if ((uintptr_t) d_out & 15u) { lrm_set_error("alignment summary records must be 16-byte aligned"); return -1; }
     if (lrm_require_device(idx->device)) return -1;
     return lrm_launch_aln_summary(d_store, store_stride, d_n_ops, d_score, d_meta_r, n, d_out, stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// difference events (docs/GACT_SPEC.md, "Difference events and MD:Z"): the rule on the host, and the device-buffer entry points
+// ------------------------------------------------------------------------------------------
+// The host rule walks the row as a lane of aln_diff_kernel does, 16 columns at a time through diff_word_step
+// (aln_diff_step.h): zeros from column n_ops on, the 16 target bytes from the lane's first target position on (zeros from
+// the end of the text on), the previous column of a word's first byte carried along.
+static inline uint32_t diff_host_word(const uint8_t *p, uint64_t at, uint64_t n) {
+    uint32_t v = 0;
+    for (uint64_t k = 0; k < 4 && at + k < n; ++k) v |= (uint32_t) p[at + k] << (8 * k);
+    return v;
+}
+extern "C" int64_t lrm_aln_diff_host(const uint8_t *ops, int n_ops, const uint8_t *target, uint64_t target_len, uint32_t *events_out) {
+    if (!ops || n_ops <= 0) return 0;
+    if (!target) target_len = 0;
+    const uint64_t n = (uint64_t) n_ops;
+    uint64_t t_row = 0, count = 0;
+    uint32_t e = 0, prev = 0;
+    for (uint64_t c0 = 0; c0 < n; c0 += 16) {
+        uint32_t text[4];
+        for (int k = 0; k < 4; ++k) text[k] = diff_host_word(target, t_row + 4u * (uint64_t) k, target_len);
+        uint32_t t = 0;
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t cw = diff_host_word(ops, c0 + 4u * (uint64_t) k, n);
+            const DiffMasks m = diff_masks(cw, (cw << 8) | prev);
+            prev = cw >> 24;
+            diff_word_step(m, t, e, text[0], text[1], text[2], text[3], [&](uint32_t word) {
+                if (events_out) events_out[count] = word;
+                ++count;
+            });
+        }
+        t_row += t;
+    }
+    return (int64_t) count;
+}
+
+extern "C" int lrm_aln_diff_offsets_dev(const lrm_aln_summary *d_summary, uint64_t n, uint64_t *d_off, void *stream) {
+    if (!d_off || (n && !d_summary)) { lrm_set_error("null argument"); return -1; }
+    return lrm_launch_aln_diff_offsets(d_summary, n, d_off, stream);
+}
+
+extern "C" int lrm_aln_diff_dev(lrm_index *idx, const uint8_t *d_store, uint64_t store_stride, const int32_t *d_n_ops,
+                                const int32_t *d_score, const int32_t *d_meta_r, const lrm_seq_meta *d_meta, uint64_t n,
+                                const uint64_t *d_off, uint64_t cap, uint32_t *d_events, void *stream) {
+    if (!idx || (n && (!d_store || !d_n_ops || !d_score || !d_meta_r || !d_meta || !d_off)) || (cap && !d_events)) { lrm_set_error("null argument"); return -1; }
+    if (store_stride > LRM_DIFF_MAX_STRIDE) { lrm_set_error("difference events: store_stride %llu above 2^22 (the '=' count of an event has 22 bits)", (unsigned long long) store_stride); return -1; }
+    if ((uintptr_t) d_events & 3u) { lrm_set_error("difference events must be 4-byte aligned"); return -1; }
+    if (lrm_require_device(idx->device)) return -1;
+    return lrm_launch_aln_diff(d_store, store_stride, d_n_ops, d_score, d_meta_r, d_meta, idx->view.content, idx->view.con_len, n, d_off, cap,
+                               d_events, stream);
 }
 
 // ------------------------------------------------------------------------------------------

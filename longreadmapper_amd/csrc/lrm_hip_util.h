@@ -108,6 +108,33 @@ __device__ __forceinline__ uint32_t wave_or_u32(uint32_t v) {
     return (uint32_t) __builtin_amdgcn_readlane((int) v, 63);
 }
 
+// ---- row loads of the stream kernels over op bytes (aln_summary_kernels.hip, aln_diff_kernels.hip) ----
+// 16 bytes of a row of n bytes from position c0 on.  Rows start at any byte (the hardware takes the unaligned dwords, as in
+// pack_rows_kernel).  row_load_step: a step that lies whole inside the row, one 16-byte load per lane.  row_load_last_step:
+// the row's last step -- zeros from position n on, and nothing at or behind p + n is read.  I: the type positions are counted in.
+template <typename I>
+__device__ __forceinline__ uint4 row_load_step(const uint8_t *__restrict__ p, I c0) {
+    uint4 v;
+    __builtin_memcpy(&v, p + c0, 16);
+    return v;
+}
+template <typename I>
+__device__ __forceinline__ uint32_t row_load_word(const uint8_t *__restrict__ p, I col, I n) {
+    uint32_t v = 0;
+    if (col + 4 <= n) __builtin_memcpy(&v, p + col, 4);
+    else if (col < n) {
+        v = p[col];
+        if (col + 1 < n) v |= (uint32_t) p[col + 1] << 8;
+        if (col + 2 < n) v |= (uint32_t) p[col + 2] << 16;
+    }
+    return v;
+}
+template <typename I>
+__device__ __forceinline__ uint4 row_load_last_step(const uint8_t *__restrict__ p, I c0, I n) {
+    if (c0 + 16 <= n) return row_load_step(p, c0);
+    return make_uint4(row_load_word<I>(p, c0, n), row_load_word<I>(p, c0 + 4, n), row_load_word<I>(p, c0 + 8, n), row_load_word<I>(p, c0 + 12, n));
+}
+
 // ---- index gathers shared by the seed-table build (index_tables.hip), the hit walk of the vote kernels (vote_hits.h) and the mapping-quality vote (mapq_kernels.hip) ----
 // ----------------------------------------------------------------------------------------
 // FM LF-mapping: lf(c, loc) = C[c] + rank(c, loc), rank = # of c in bwt[0..loc] == _occ_access (fmidx.c:277-293)

@@ -69,7 +69,7 @@ int submit_replica(lrm_index *ix, const MapJob &j, const LrmMapTune &mt, lrm_tic
     return 0;
 }
 
-int submit_impl(lrm_index *idx, const MapJob &j, const lrm_map_options *opt, lrm_ticket **out) {
+int submit_impl(lrm_index *idx, const MapJob &j, const lrm_map_options *opt, lrm_ticket **out, uint64_t *diff_needed_out = nullptr) {
     LrmMapTune mt = idx->mtune;
     if (opt) lrm_call_map_tune(idx, opt, &mt);
     const uint32_t max_len = max_of(j.lens, j.n);
@@ -82,7 +82,12 @@ int submit_impl(lrm_index *idx, const MapJob &j, const lrm_map_options *opt, lrm
         return -1;
     }
     if ((j.mode & DO_EXTEND) && mt.dense && (j.store_stride & 15u)) { lrm_set_error("dense results need store_stride to be a multiple of 16"); return -1; }
+    if (j.diff_off && ((j.store_stride + 3) & ~3ull) > (1ull << 22)) {
+        lrm_set_error("difference events: store_stride %llu above 2^22 (the '=' count of an event has 22 bits)", (unsigned long long) j.store_stride);
+        return -1;
+    }
     std::unique_ptr<lrm_ticket> t(new lrm_ticket);
+    t->diff_needed_out = diff_needed_out;
     if (j.n) {
         if (idx->n_peers <= 1 || !idx->peers) {
             if (submit_replica(idx, j, mt, t.get(), 1)) return -1;
@@ -114,16 +119,17 @@ int wait_impl(lrm_ticket *t) {
         t->cv.wait(lk, [&] { return t->pending == 0; });
         rc = t->rc;
         if (rc) lrm_set_error("%s", t->err.c_str());
+        if (t->diff_needed_out) *t->diff_needed_out = t->diff_total.load();
     }
     delete t;
     return rc;
 }
 
 // C ABI: no C++ exception may leave the library (allocation failures of the host-side bookkeeping, thread creation)
-int run_job(lrm_index *idx, const MapJob &j, const lrm_map_options *opt, lrm_ticket **ticket_out) {
+int run_job(lrm_index *idx, const MapJob &j, const lrm_map_options *opt, lrm_ticket **ticket_out, uint64_t *diff_needed_out = nullptr) {
     try {
         lrm_ticket *t = nullptr;
-        if (submit_impl(idx, j, opt, &t)) return -1;
+        if (submit_impl(idx, j, opt, &t, diff_needed_out)) return -1;
         if (ticket_out) { *ticket_out = t; return 0; }
         return wait_impl(t);
     } catch (const std::exception &e) {
@@ -183,10 +189,13 @@ extern "C" int lrm_map_batch(lrm_index *idx, char *reads_buf, uint64_t stride, c
 
 // The per-call extras (lrm_batch_extras).  mapq_out: the mapping-quality stage behind every seed sub-batch (docs/GACT_SPEC.md,
 // "Mapping quality"); summary_out: the alignment summary stage behind every group's extension ("Alignment summary and PAF").
-extern "C" int lrm_map_batch_submit_ex(lrm_index *idx, char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
-                                       lrm_params p, lrm_gact_params gp, lrm_entry *best_out, lrm_cigar *cig_out,
-                                       uint8_t *store_mem, uint64_t store_stride, int *score_out, lrm_seq_meta *meta_out,
-                                       int *meta_r_out, const lrm_map_options *opt, const lrm_batch_extras *ex, lrm_ticket **ticket_out) {
+// diff: the difference events on top (lrm_batch_diff; docs/GACT_SPEC.md, "Difference events and MD:Z"): the stage runs when every
+// extension group is collected, into the one buffer the whole batch shares.
+extern "C" int lrm_map_batch_submit_ex2(lrm_index *idx, char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
+                                        lrm_params p, lrm_gact_params gp, lrm_entry *best_out, lrm_cigar *cig_out,
+                                        uint8_t *store_mem, uint64_t store_stride, int *score_out, lrm_seq_meta *meta_out,
+                                        int *meta_r_out, const lrm_map_options *opt, const lrm_batch_extras *ex,
+                                        const lrm_batch_diff *diff, lrm_ticket **ticket_out) {
     if (!ticket_out) { lrm_set_error("null argument"); return -1; }
     MapJob j;
     if (map_job_of(j, idx, reads_buf, stride, lens, n, p, gp, best_out, cig_out, store_mem, store_stride, score_out, meta_out, meta_r_out)) return -1;
@@ -195,7 +204,22 @@ extern "C" int lrm_map_batch_submit_ex(lrm_index *idx, char *reads_buf, uint64_t
         if (have >= offsetof(lrm_batch_extras, mapq_out) + sizeof(ex->mapq_out)) j.mapq_out = ex->mapq_out;
         if (have >= offsetof(lrm_batch_extras, summary_out) + sizeof(ex->summary_out)) j.summary_out = ex->summary_out;
     }
-    return run_job(idx, j, opt, ticket_out);
+    uint64_t *needed_out = nullptr;
+    if (diff) {
+        if (diff->struct_size < sizeof(lrm_batch_diff)) { lrm_set_error("lrm_batch_diff.struct_size %u: the struct has %zu bytes", diff->struct_size, sizeof(lrm_batch_diff)); return -1; }
+        if (!diff->needed_out || (n && (!diff->off_out || !diff->cnt_out)) || (diff->cap && !diff->events_out)) { lrm_set_error("null array in lrm_batch_diff"); return -1; }
+        *diff->needed_out = 0;
+        j.diff_off = diff->off_out; j.diff_cnt = diff->cnt_out; j.diff_events = diff->events_out; j.diff_cap = diff->cap;
+        needed_out = diff->needed_out;
+    }
+    return run_job(idx, j, opt, ticket_out, needed_out);
+}
+extern "C" int lrm_map_batch_submit_ex(lrm_index *idx, char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
+                                       lrm_params p, lrm_gact_params gp, lrm_entry *best_out, lrm_cigar *cig_out,
+                                       uint8_t *store_mem, uint64_t store_stride, int *score_out, lrm_seq_meta *meta_out,
+                                       int *meta_r_out, const lrm_map_options *opt, const lrm_batch_extras *ex, lrm_ticket **ticket_out) {
+    return lrm_map_batch_submit_ex2(idx, reads_buf, stride, lens, n, p, gp, best_out, cig_out, store_mem, store_stride, score_out,
+                                    meta_out, meta_r_out, opt, ex, nullptr, ticket_out);
 }
 extern "C" int lrm_map_batch_submit_mapq(lrm_index *idx, char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
                                          lrm_params p, lrm_gact_params gp, lrm_entry *best_out, lrm_cigar *cig_out,

@@ -328,6 +328,13 @@ int lrm_launch_cigar_text(const uint8_t *d_store, uint64_t pitch, const int32_t 
 // bytes start at d_store + row * pitch: behind the extension that wrote them, on its stream
 int lrm_launch_aln_summary(const uint8_t *d_store, uint64_t pitch, const int32_t *d_n_ops, const int32_t *d_score, const int32_t *d_meta_r,
                            uint64_t rows, lrm_aln_summary *d_out, void *stream);
+// the difference events (aln_diff_kernels.hip; docs/GACT_SPEC.md, "Difference events and MD:Z") of the same rows: d_off holds
+// rows + 1 exclusive prefix sums of n_x + n_del (lrm_launch_aln_diff_offsets makes them from the summary records), row i's
+// events go to d_events + d_off[i]; a row whose events end behind cap writes nothing
+int lrm_launch_aln_diff(const uint8_t *d_store, uint64_t pitch, const int32_t *d_n_ops, const int32_t *d_score, const int32_t *d_meta_r,
+                        const lrm_seq_meta *d_meta, const char *d_content, uint64_t con_len, uint64_t rows, const uint64_t *d_off,
+                        uint64_t cap, uint32_t *d_events, void *stream);
+int lrm_launch_aln_diff_offsets(const lrm_aln_summary *d_sum, uint64_t rows, uint64_t *d_off, void *stream);
 int lrm_launch_seed(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint64_t stride,
                     const uint32_t *d_lens, uint64_t n, uint32_t seed_len,
                     uint32_t thres, lrm_entry *d_best, const LrmMapTune &mt, void *stream, uint8_t *d_phase_out = nullptr);

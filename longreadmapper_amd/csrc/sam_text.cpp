@@ -65,6 +65,32 @@ __attribute__((always_inline)) static inline void put_cigar(std::string &s, cons
     }
 }
 void sam_append_cigar(std::string &s, const lrm_cigar &c, bool is_text) { put_cigar(s, c, is_text); }
+
+// MD:Z from a read's difference events (docs/GACT_SPEC.md, "Difference events and MD:Z"): before an 'X' and before the first
+// 'D' of a run the '=' columns since the previous such event ("0" included), '^' in front of a run of deleted bases, the
+// base; a 'D' that continues a run prints its base alone; at the end the '=' columns that are left
+void sam_append_md(std::string &s, const uint32_t *events, uint64_t count, uint32_t n_eq) {
+    uint32_t prev = 0;
+    for (uint64_t k = 0; k < count; ++k) {
+        const uint32_t w = events[k], kind = LRM_DIFF_KIND(w), e = LRM_DIFF_EQ_BEFORE(w);
+        if (kind != LRM_DIFF_D_MORE) {
+            put_num(s, e - prev);
+            if (kind == LRM_DIFF_D_OPEN) s += '^';
+            prev = e;
+        }
+        s += (char) LRM_DIFF_BASE(w);
+    }
+    put_num(s, n_eq - prev);
+}
+extern "C" int lrm_md_format(const uint32_t *events, uint64_t count, uint32_t n_eq, char *buf, int buflen) {
+    if (!buf || buflen < 1 || (count && !events)) return -1;
+    std::string s;
+    sam_append_md(s, events, count, n_eq);
+    if (s.size() + 1 > (size_t) buflen) return -1;
+    memcpy(buf, s.data(), s.size());
+    buf[s.size()] = 0;
+    return (int) s.size();
+}
 // the name of reference sequence seq_id; "*" if there is none
 static inline void put_rname(std::string &s, const SamBatch &b, int seq_id) {
     if (seq_id >= 0 && seq_id < b.mta_len) s.append(b.mta[seq_id].name, b.mta[seq_id].name_len); else s += '*';
@@ -240,6 +266,11 @@ static void sam_format_range(const SamBatch &b, uint64_t lo, uint64_t hi, std::s
             s += "\tv1:i:"; put_num(s, mq[i].n1);
             s += "\tv2:i:"; put_num(s, mq[i].n2);
         }
+        if (b.events && !unmapped && b.cig[i].n_cigar_op > 0 && b.diff_off[i] != UINT64_MAX) {   // (UINT64_MAX: the read's events found no room)
+            const lrm_aln_summary &a = b.sum[i];
+            s += "\tNM:i:"; put_num(s, (uint64_t) a.n_x + a.n_ins + a.n_del);
+            s += "\tMD:Z:"; sam_append_md(s, b.events + b.diff_off[i], b.diff_cnt[i], a.n_eq);
+        }
         if (sx && !unmapped) sam_split_lines(b, i, *sx, s);
         else s += '\n';
     }
@@ -262,10 +293,13 @@ std::vector<uint64_t> sam_part_offsets(const std::vector<std::string> &parts, ui
     return at;
 }
 
-extern "C" char *lrm_sam_format_mapq(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig,
-                                     const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t n, int cigar_is_text,
-                                     int revcomp_here, const lrm_split_out *split, const lrm_mapq *mq, uint64_t *len_out) {
-    const SamBatch b = {reads, mta, mta_len, cig, score, meta, meta_r, n, cigar_is_text != 0, revcomp_here != 0, split, mq};
+extern "C" char *lrm_sam_format_md(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig,
+                                   const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t n, int cigar_is_text,
+                                   int revcomp_here, const lrm_split_out *split, const lrm_mapq *mq, const lrm_aln_summary *sum,
+                                   const uint64_t *diff_off, const uint32_t *diff_cnt, const uint32_t *events, uint64_t *len_out) {
+    if (events && (!sum || !diff_off || !diff_cnt)) { lrm_set_error("lrm_sam_format_md: events without summary records, offsets or counts"); return nullptr; }
+    const SamBatch b = {reads, mta, mta_len, cig, score, meta, meta_r, n, cigar_is_text != 0, revcomp_here != 0, split, mq,
+                        sum, diff_off, diff_cnt, events};
     std::vector<std::string> parts;
     sam_format_parts(b, lrm_host_threads(), parts);
     const std::vector<uint64_t> at = sam_part_offsets(parts, 0);
@@ -277,6 +311,12 @@ extern "C" char *lrm_sam_format_mapq(const lrm_read_batch *reads, const lrm_mta_
     out[total] = 0;
     if (len_out) *len_out = total;
     return out;
+}
+extern "C" char *lrm_sam_format_mapq(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig,
+                                     const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t n, int cigar_is_text,
+                                     int revcomp_here, const lrm_split_out *split, const lrm_mapq *mq, uint64_t *len_out) {
+    return lrm_sam_format_md(reads, mta, mta_len, cig, score, meta, meta_r, n, cigar_is_text, revcomp_here, split, mq, nullptr, nullptr,
+                             nullptr, nullptr, len_out);
 }
 extern "C" char *lrm_sam_format_split(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig,
                                       const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t n, int cigar_is_text,

@@ -16,6 +16,8 @@ struct SamBatch {
     bool revcomp_here;             // the batch ran with keep_reads: reverse-strand reads are reverse-complemented while they are printed
     const lrm_split_out *split;    // null or no segment: no supplementary lines
     const lrm_mapq *mq;            // null: column 5 is 255, no v1:i / v2:i
+    // the difference events of the batch (docs/GACT_SPEC.md, "Difference events and MD:Z"); events null: no NM:i / MD:Z
+    const lrm_aln_summary *sum; const uint64_t *diff_off; const uint32_t *diff_cnt; const uint32_t *events;
 };
 
 // ---- the writers every field goes through (sam_text.cpp, paf_text.cpp) ----
@@ -28,6 +30,8 @@ static inline int put_uint(char *dst, uint64_t v) {           // decimal text of
 }
 static inline void put_num(std::string &s, uint64_t v) { char num[24]; s.append(num, (size_t) put_uint(num, v)); }
 static inline void put_int(std::string &s, int64_t v) { if (v < 0) { s += '-'; put_num(s, (uint64_t) -v); } else put_num(s, (uint64_t) v); }
+// MD:Z text of one read from its events and its n_eq, appended to s (lrm_md_format)
+void sam_append_md(std::string &s, const uint32_t *events, uint64_t count, uint32_t n_eq);
 // the CIGAR column of one alignment as lrm_parse_cigar prints it: the text as it is, or the run-length text of the op bytes
 void sam_append_cigar(std::string &s, const lrm_cigar &c, bool is_text);
 

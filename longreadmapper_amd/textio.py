@@ -95,10 +95,27 @@ def sam_header(mta, rg_id):
     return _text(lib.lrm_sam_header, mta, len(mta), rg_id)
 
 
-def sam_format(batch, mta, cig, score, meta, meta_r, n, *, is_text=0, keep=0, split=None, mapq=None, entry=None):
-    """The SAM records of a batch: lrm_sam_format_mapq with mapq (MAPQ_DT records), lrm_sam_format_split with split (an
+def md_text(events, n_eq):
+    """lrm_md_format: the MD:Z text of one read from its difference events (uint32 words) and the n_eq of its summary record."""
+    ev = np.ascontiguousarray(events, dtype=np.uint32)
+    buf = C.create_string_buffer(12 * len(ev) + 24)
+    k = lib.lrm_md_format(ev.ctypes.data if len(ev) else None, len(ev), int(n_eq), buf, len(buf))
+    assert k >= 0
+    return buf.raw[:k].decode()
+
+
+def sam_format(batch, mta, cig, score, meta, meta_r, n, *, is_text=0, keep=0, split=None, mapq=None, entry=None, md=None):
+    """md: (summary records, offsets, counts, events) of the batch, or a map_batch(md=True) result with summary=True --
+    lrm_sam_format_md: NM:i and MD:Z behind ED:I (None for events: the lines of lrm_sam_format_mapq).
+    The SAM records of a batch: lrm_sam_format_mapq with mapq (MAPQ_DT records), lrm_sam_format_split with split (an
     lrm_split_out), run-length text (is_text) or untouched reads (keep), else lrm_sam_format; entry names one of the three
     instead (the later ones take NULL for what the earlier ones lack)."""
+    if md is not None or entry == "lrm_sam_format_md":
+        if isinstance(md, dict):
+            md = (md["summary"], md["md_off"], md["md_cnt"], md["md_events"])
+        md = (None,) * 4 if md is None else md
+        return _text(lib.lrm_sam_format_md, C.byref(batch), mta, len(mta), _at(cig), _at(score), _at(meta), _at(meta_r), n, int(is_text),
+                     int(keep), _at(split), _at(mapq), *(_at(x) for x in md))
     entry = entry or ("lrm_sam_format_mapq" if mapq is not None else
                       "lrm_sam_format_split" if split is not None or is_text or keep else "lrm_sam_format")
     args = (C.byref(batch), mta, len(mta), _at(cig), _at(score), _at(meta), _at(meta_r), n)
@@ -115,13 +132,15 @@ def paf_format(batch, mta, cig, score, meta, meta_r, n, summary, *, is_text=0, m
                  _at(summary), _at(mapq))
 
 
-def accaln(genome, reads, out, batch_size, seed_len=20, thres=300, gact=(0, 0, 0), device=0, rg_id=1, options=None, mapq=0, paf=False):
-    """A whole reads file to SAM (paf: PAF) -> (total, valid): lrm_accaln_paf, or the first of lrm_accaln_mapq / lrm_accaln_opt
+def accaln(genome, reads, out, batch_size, seed_len=20, thres=300, gact=(0, 0, 0), device=0, rg_id=1, options=None, mapq=0, paf=False, md=False):
+    """md: NM:i and MD:Z on every mapped primary line (lrm_accaln_md).
+    A whole reads file to SAM (paf: PAF) -> (total, valid): lrm_accaln_paf, or the first of lrm_accaln_mapq / lrm_accaln_opt
     / lrm_accaln that takes what was given (options: an lrm_map_options).  A failure raises LrmError with the code in .rc."""
     total, valid = C.c_uint64(), C.c_uint64()
     head = (os.fsencode(genome), os.fsencode(reads), os.fsencode(out), capi.Params(batch_size, seed_len, thres), capi.GactParams(*gact), device)
     counts, opt = (C.byref(total), C.byref(valid)), _at(options)
-    entry, tail = (("lrm_accaln_paf", (*counts, opt, mapq)) if paf else ("lrm_accaln_mapq", (rg_id, *counts, opt, mapq)) if mapq else
+    assert not (md and paf), "PAF lines carry no MD:Z"
+    entry, tail = (("lrm_accaln_paf", (*counts, opt, mapq)) if paf else ("lrm_accaln_md", (rg_id, *counts, opt, mapq, 1)) if md else ("lrm_accaln_mapq", (rg_id, *counts, opt, mapq)) if mapq else
                    ("lrm_accaln_opt", (rg_id, *counts, opt)) if options is not None else ("lrm_accaln", (rg_id, *counts)))
     rc = getattr(lib, entry)(*head, *tail)
     if rc < 0:

@@ -1,6 +1,7 @@
 """End-to-end probe (GPU box): `accidx` + `accaln` on an E. coli-sized reference and N x 10 kbp reads from a
 FASTQ file, SAM out -- wall time of the whole flow, i.e. with the text stages either side of the hot path.
-python tools/accaln_probe.py [n_reads] [batch]"""
+python tools/accaln_probe.py [n_reads] [batch]       PROBE_MD=1: runs alternate between md off and md on (NM:i / MD:Z,
+docs/GACT_SPEC.md "Difference events and MD:Z"), PROBE_RUNS of them (default 3, with PROBE_MD 6)"""
 import os
 import sys
 import time
@@ -27,15 +28,17 @@ with open(fq, "wb") as f:
     for i in range(n):
         f.write(b"@read%d\n" % i + r["reads"][i, :Lr].tobytes() + b"\n+\n" + q + b"\n")
 os.environ.setdefault("LRM_HOST_VERBOSE", "1")        # stage times of lrm_accaln on stderr
-for rep in range(3):
+with_md = os.environ.get("PROBE_MD", "0") not in ("", "0")
+for rep in range(int(os.environ.get("PROBE_RUNS", "6" if with_md else "3"))):
+    md = with_md and rep % 2 == 1
     if os.path.exists(sam):
         os.remove(sam)                      # (truncating the previous run's gigabytes would be timed otherwise)
     t0 = time.perf_counter()
-    total, valid = textio.accaln(fa, fq, sam, batch)
+    total, valid = textio.accaln(fa, fq, sam, batch, md=True) if md else textio.accaln(fa, fq, sam, batch)
     t = time.perf_counter() - t0
-    print("accaln run %d: %d reads x %d bp in batches of %d: %.2f s = %.3f Gbp/s end to end (index load + upload included); "
+    print("accaln run %d%s: %d reads x %d bp in batches of %d: %.2f s = %.3f Gbp/s end to end (index load + upload included); "
           "valid %d / %d; FASTQ %.0f MB, SAM %.0f MB; accidx %.1f s"
-          % (rep, n, Lr, batch, t, n * Lr / t / 1e9, valid, total, os.path.getsize(fq) / 1e6,
+          % (rep, " (md)" if md else "", n, Lr, batch, t, n * Lr / t / 1e9, valid, total, os.path.getsize(fq) / 1e6,
              os.path.getsize(sam) / 1e6, t_idx), flush=True)
 for p in os.listdir(d):
     os.remove(os.path.join(d, p))
