@@ -602,6 +602,116 @@ int lrm_split_batch(lrm_index *idx, const char *reads_buf, uint64_t stride, cons
                     const lrm_cigar *cig, const lrm_seq_meta *meta, const int *meta_r, lrm_params p, lrm_gact_params gp,
                     const lrm_map_options *opt, lrm_split_out *out);
 
+/* SECONDARY ALIGNMENTS (docs/GACT_SPEC.md, "Secondary alignments"): the mapping-quality stage counts the seed hits of the
+ * best OTHER place (lrm_mapq.n2); this stage finds where that place is and extends the read there.  Asked for per CALL, like
+ * the mapping quality: nothing runs or is allocated unless one of the entry points below is called, and every other output
+ * is the same bytes with it or without.  A read is a CANDIDATE iff it has a locus, its record has no LRM_MAPQ_OVERFLOW,
+ * n2 >= H and 100 * n2 >= pct * n1 (H = min_hits: 0 = 8, else 1..65535; pct = ratio_pct: 0 = 50, else 1..100).  Its RIVAL
+ * entry: of the fullest (histogram, bucket) pair of the rival vote (ties: the smallest bucket, histogram 0 first) the fullest
+ * sub-bucket of 2^s diagonals (s = max(4, log2(radius) - 10); ties: the smallest) -- key = its smallest hit, val = its hits,
+ * bucket = key >> 4.  A read that is not a candidate has an all-zero entry.  One secondary per read; secondaries of split
+ * segments are out of scope. */
+#define LRM_SEC_ALIGNED 1u             /* lrm_secondary.flags: REPORTED -- resolved, extended (in the anchored modes: from an
+                                          anchor of its own) and not a duplicate */
+#define LRM_SEC_DUPLICATE 2u           /*   resolved to the primary's sequence and strand, less than len/2 bases from it: the
+                                          tail of the primary's own cluster */
+typedef struct lrm_secondary { uint32_t read, hits, flags, pad; } lrm_secondary;     /* 16 bytes; hits: the rival entry's val */
+typedef struct lrm_secondary_options {
+    uint32_t struct_size;      /* sizeof(lrm_secondary_options) of the caller's header (0: all of it) */
+    uint32_t min_hits;         /* H */
+    uint32_t ratio_pct;        /* pct */
+    uint32_t anchored;         /* the extension the candidates go through: 0 classic, 1 anchored (clip implies it) */
+    uint32_t anchor_min_len;   /*   as lrm_map_options.anchor_min_len */
+    uint32_t clip;             /*   1: anchored with end clipping */
+    uint32_t clip_penalty;     /*   P */
+    uint32_t clip_end_bonus;   /*   B */
+} lrm_secondary_options;
+
+/* The rival entries of a batch (d_rival: n lrm_entry in device memory): call it behind lrm_seed_batch_mapq_dev on the same
+ * workspace and stream, with that call's d_lens, n, p, d_best and d_mapq, BEFORE any other seed stage runs on that workspace
+ * -- it walks the survivor lists that call left there.  (The split stage, handed the primary's workspace as ws_seg, is such a
+ * stage: lrm_rival_dev / lrm_secondary_batch_dev first, then lrm_split_batch_dev.)  One kernel, asynchronous; it checks what
+ * the mapping-quality stage checks. */
+int lrm_rival_dev(lrm_index *idx, lrm_workspace *ws, const uint32_t *d_lens, uint64_t n, lrm_params p,
+                  const lrm_entry *d_best, const lrm_mapq *d_mapq, uint32_t min_hits, uint32_t ratio_pct,
+                  lrm_entry *d_rival, void *stream);
+/* The rule on the host over the hits of ONE read (keys: SA[row] - j of every survivor of the evidence phases, 64-bit wrap
+ * kept), usable without a GPU: *out = the rival entry (zeros for a read that is not a candidate).  slots: 0 = LRM_MAPQ_SLOTS.
+ * Returns 1 for a candidate, 0 otherwise, -1 for a bad argument. */
+int lrm_rival_host(const uint64_t *keys, uint64_t n_keys, const lrm_entry *best, uint32_t len, uint32_t min_hits,
+                   uint32_t ratio_pct, uint32_t slots, lrm_entry *out);
+/* The candidate table from the records: reads ascending, hits = 0 (the rival's val is known only behind the rival kernel),
+ * flags = 0.  Pure host arithmetic.  table holds up to cap records (may be NULL when cap == 0); *n_sec is the number of
+ * candidates in any case.  0 ok, -3 more than cap candidates (nothing written), -1 bad argument. */
+int lrm_secondary_plan(const lrm_mapq *mapq, uint64_t n, uint32_t min_hits, uint32_t ratio_pct, lrm_secondary *table,
+                       uint64_t cap, uint64_t *n_sec);
+
+/* Device buffers of the stage, owned by the caller, for up to cap candidates: the table, the candidate batch (row s = read
+ * table[s].read AS SEQUENCED at rows + s*row_stride, 16-byte aligned, row_stride a multiple of 16 and > the longest
+ * candidate; every byte of a row behind the read's end is 0), their lengths, their rival entries and, per candidate,
+ * everything the extension call of the chosen mode returns for a batch made of those rows with best = the rival entries
+ * (store_stride as that call wants it for the longest candidate, a multiple of 4; anchor / clip may be NULL in the modes
+ * that do not write them). */
+typedef struct lrm_secondary_dev {
+    uint64_t cap;
+    lrm_secondary *table;
+    char *rows; uint64_t row_stride;
+    uint32_t *lens;
+    lrm_entry *rival;
+    uint8_t *store; uint64_t store_stride;
+    int32_t *n_ops, *score;
+    lrm_seq_meta *meta; int32_t *meta_r;
+    lrm_anchor *anchor;
+    lrm_clip *clip;
+} lrm_secondary_dev;
+/* Call behind the primary's seed stage WITH mapping quality and its extension, on the same workspace and stream: d_reads
+ * (as the extension left them: a read with d_meta_r != 0 && d_meta.strand == 1 was reverse-complemented in place, the gather
+ * undoes that), d_lens, d_best, d_mapq, d_meta, d_meta_r are those calls'.  d_meta == NULL (then d_meta_r too): the reads are
+ * as sequenced, and no candidate is tested for LRM_SEC_DUPLICATE.  The stage runs the rival kernel, counts the candidates on
+ * the device, and THE COUNT CROSSES TO THE HOST (8 bytes; the call sleeps on an event, as lrm_split_batch_dev does); then it
+ * marks the table, gathers the rows, runs the unchanged extension stage so names over them on ws with gp, and sets the flags.
+ * *n_sec = the number of candidates.  More than out->cap: -3, *n_sec says how many, no result array is written.  The first
+ * call on a workspace allocates 24 bytes per read of its n_max, 8 bytes per 256 reads and 8 bytes; lrm_workspace_bytes grows
+ * by it.  "As sequenced" holds for reads of upper-case A, C, G, T and N: the gather undoes the reverse complement with the
+ * extension's own base map, which folds case and turns every other byte into N.
+ * so == NULL: the defaults, classic extension. */
+int lrm_secondary_batch_dev(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint64_t stride, const uint32_t *d_lens,
+                            uint64_t n, const lrm_entry *d_best, const lrm_mapq *d_mapq, const lrm_seq_meta *d_meta,
+                            const int32_t *d_meta_r, lrm_params p, lrm_gact_params gp, const lrm_secondary_options *so,
+                            const lrm_secondary_dev *out, uint64_t *n_sec, void *stream);
+
+/* The results of the stage in HOST memory, for the callers that print them (lrm_sam_format_secondary): what a caller
+ * downloads from an lrm_secondary_dev, with cig[s] = {the op bytes of candidate s inside store (or its run-length text),
+ * n_ops, score}.  n_sec: the number of candidates the arrays hold. */
+typedef struct lrm_secondary_out {
+    uint64_t cap, n_sec;
+    lrm_secondary *table;
+    char *rows; uint64_t row_stride;
+    uint32_t *lens;
+    lrm_entry *rival;
+    lrm_cigar *cig;
+    uint8_t *store; uint64_t store_stride;
+    int *score;
+    lrm_seq_meta *meta; int *meta_r;
+    lrm_anchor *anchor;
+    lrm_clip *clip;
+} lrm_secondary_out;
+/* The stage with HOST buffers, over a batch the caller has just got back from lrm_map_batch_submit_mapq / _wait: reads_buf,
+ * lens, mapq, meta, meta_r as returned (meta == NULL, then meta_r too: the reads are as sequenced, no duplicate test).  It plans
+ * the candidates from the records (lrm_secondary_plan), gathers them on the host as sequenced (without opt->keep_reads the
+ * caller's copy of a read with meta_r != 0 && strand == 1 was reverse-complemented in place: the gather undoes that, A/C/G/T of
+ * either case to the upper-case complement, any other byte to N, as the device does), uploads only those rows and runs seed +
+ * mapping quality + rival + the extension `so` names for them in ONE synchronous device pass on a workspace of its own, then
+ * downloads.  The host pipeline is not touched.  A read's records do not depend on its batch, so the table and the
+ * per-candidate results equal lrm_secondary_batch_dev's.  out->cig[s] is in opt's layout inside out->store (rows; dense_results:
+ * the used op bytes back to back in 16-byte units; cigar_text: the NUL-terminated run-length text, likewise); row_stride a
+ * multiple of 16 above the longest candidate, store_stride a multiple of 16 and what the extension mode needs.  On a group
+ * handle the first device does the pass.  opt == NULL: the handle's default options.  -3: more than out->cap candidates
+ * (out->n_sec says how many, nothing else is written). */
+int lrm_secondary_batch(lrm_index *idx, const char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
+                        const lrm_mapq *mapq, const lrm_seq_meta *meta, const int *meta_r, lrm_params p, lrm_gact_params gp,
+                        const lrm_map_options *opt, const lrm_secondary_options *so, lrm_secondary_out *out);
+
 /* Counters of the last *_dev call on this workspace (device->host copy, syncs
  * the stream): vote items per table tier, reads decided in
  * phase 0, GACT tiles.  For tests / bench bookkeeping only. */

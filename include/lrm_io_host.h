@@ -89,6 +89,16 @@ char *lrm_sam_format_md(const lrm_read_batch *reads, const lrm_mta_entry *mta, i
                         const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t n, int cigar_is_text,
                         int revcomp_here, const lrm_split_out *split, const lrm_mapq *mq, const lrm_aln_summary *sum,
                         const uint64_t *diff_off, const uint32_t *diff_cnt, const uint32_t *events, uint64_t *len_out);
+/* The same with SECONDARY ALIGNMENTS (docs/GACT_SPEC.md, "Secondary alignments"): sec holds the results of the secondary
+ * stage for this batch (NULL or no candidate: exactly the text of lrm_sam_format_md).  Behind a read's primary and supplementary
+ * lines comes one line per REPORTED secondary (LRM_SEC_ALIGNED): FLAG 256 (+ 16 when it is on the reverse strand of the read as
+ * sequenced), its own RNAME and POS = off + 1, MAPQ 0, its own run-length CIGAR with soft clips as S, SEQ * and QUAL *,
+ * ED:I:<score>\ttp:A:S.  Every other line is unchanged. */
+char *lrm_sam_format_secondary(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig,
+                               const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t n, int cigar_is_text,
+                               int revcomp_here, const lrm_split_out *split, const lrm_mapq *mq, const lrm_aln_summary *sum,
+                               const uint64_t *diff_off, const uint32_t *diff_cnt, const uint32_t *events,
+                               const lrm_secondary_out *sec, uint64_t *len_out);
 
 /* PAF (docs/GACT_SPEC.md, "Alignment summary and PAF"): one line per MAPPED read -- an unmapped one (meta_r == 0 or score == -1)
  * prints nothing --, every number of it taken from the read's alignment summary record (sum: required, what
@@ -128,6 +138,13 @@ int lrm_accaln_mapq(const char *genome, const char *reads_path, const char *sam_
 int lrm_accaln_md(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
                   lrm_gact_params gp, int device, long rg_id, uint64_t *total, uint64_t *valid,
                   const lrm_map_options *opt, int mapq, int md);
+/* ... with SECONDARY ALIGNMENTS (docs/GACT_SPEC.md, "Secondary alignments"; so == NULL: lrm_accaln_mapq with its mode on): the
+ * flow of lrm_accaln_mapq, and after a batch's wait its candidates go through lrm_secondary_batch with `so` (thresholds and the
+ * extension mode of the candidates) and the batch is printed by lrm_sam_format_secondary: one FLAG 256 line behind the lines
+ * of every read with a reported secondary, every other line as lrm_accaln_mapq prints it. */
+int lrm_accaln_secondary(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
+                         lrm_gact_params gp, int device, long rg_id, uint64_t *total, uint64_t *valid,
+                         const lrm_map_options *opt, const lrm_secondary_options *so);
 /* The flow of lrm_accaln_mapq with PAF output: every batch goes through lrm_map_batch_submit_ex with summary_out (and
  * mapq_out when mapq != 0) and is printed by lrm_paf_format; the file has no header.  total / valid count as in the SAM flow.
  * opt->split != 0 is refused (-1): PAF lines for split segments need summary records of the segment batch, which the

@@ -115,6 +115,18 @@ SYMBOLS = {
                                       C.c_void_p]),
     "lrm_split_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                   Params, GactParams, C.POINTER(MapOptions), C.POINTER(SplitOut)]),
+    "lrm_rival_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, Params, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                C.c_void_p, C.c_void_p]),
+    "lrm_rival_host": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(Entry), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                 C.POINTER(Entry)]),
+    "lrm_secondary_plan": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, u64p]),
+    "lrm_secondary_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, Params, GactParams, C.POINTER(SecondaryOptions),
+                                          C.POINTER(SecondaryDev), u64p, C.c_void_p]),
+    "lrm_secondary_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      Params, GactParams, C.POINTER(MapOptions), C.POINTER(SecondaryOptions), C.POINTER(SecondaryOut)]),
+    "lrm_accaln_secondary": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, Params, GactParams, C.c_int, C.c_long, u64p, u64p,
+                                       C.POINTER(MapOptions), C.POINTER(SecondaryOptions)]),
     "lrm_debug_anchor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(Anchor)]),
     "lrm_workspace_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats), C.c_void_p]),
     "lrm_debug_vote_results": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
@@ -163,6 +175,9 @@ SYMBOLS = {
     "lrm_sam_format_md": (C.c_void_p, [C.POINTER(ReadBatch), C.POINTER(MtaEntry), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(SplitOut), C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, u64p]),
+    "lrm_sam_format_secondary": (C.c_void_p, [C.POINTER(ReadBatch), C.POINTER(MtaEntry), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(SplitOut), C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SecondaryOut), u64p]),
     "lrm_accaln_md": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, Params, GactParams, C.c_int, C.c_long, u64p, u64p,
                                 C.POINTER(MapOptions), C.c_int, C.c_int]),
     "lrm_paf_format": (C.c_void_p, [C.POINTER(ReadBatch), C.POINTER(MtaEntry), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

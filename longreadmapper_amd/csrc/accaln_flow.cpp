@@ -91,6 +91,32 @@ struct SplitBufs {
     }
 };
 
+// what lrm_secondary_batch writes for one batch (docs/GACT_SPEC.md, "Secondary alignments"), grown on demand like SplitBufs
+struct SecBufs {
+    lrm_secondary_out out;
+    std::vector<lrm_secondary> table;
+    std::vector<char> rows;
+    std::vector<uint8_t> store;
+    std::vector<uint32_t> lens;
+    std::vector<lrm_entry> rival;
+    std::vector<lrm_cigar> cig;
+    std::vector<int> score, meta_r;
+    std::vector<lrm_seq_meta> meta;
+    std::vector<lrm_anchor> anchor;
+    std::vector<lrm_clip> clip;
+    SecBufs() { memset(&out, 0, sizeof(out)); }
+    lrm_secondary_out *fit(uint64_t k, uint64_t row_stride, uint64_t store_stride) {
+        memset(&out, 0, sizeof(out));
+        if (k == 0) return &out;
+        auto room = [](auto &v, uint64_t n) { v.resize((size_t) n); return v.data(); };
+        out.cap = k; out.row_stride = row_stride; out.store_stride = store_stride;
+        out.table = room(table, k); out.rows = room(rows, k * row_stride); out.store = room(store, k * store_stride);
+        out.lens = room(lens, k); out.rival = room(rival, k); out.cig = room(cig, k); out.score = room(score, k);
+        out.meta_r = room(meta_r, k); out.meta = room(meta, k); out.anchor = room(anchor, k); out.clip = room(clip, k);
+        return &out;
+    }
+};
+
 // one batch on its way through the pipeline, with the caller-side buffers of the hot path (pinned: the DMA engines
 // read the reads and write the dense op bytes straight from / into them); recycled.  A set belongs to the thread that
 // popped it from a queue, until that thread pushes it on.
@@ -107,6 +133,7 @@ struct BatchSet {
     std::vector<lrm_seq_meta> meta;
     uint64_t sstride = 0;
     lrm_ticket *ticket = nullptr;
+    SecBufs sc;                                  // secondary alignments: the second pass over this batch's candidates (lrm_secondary_batch)
     SplitBufs sp;                                // split reads: the second pass over this batch's clipped ends (lrm_split_batch)
     std::vector<lrm_mapq> mq;                    // lrm_accaln_mapq: the records of the batch
     std::vector<lrm_aln_summary> sum;            // lrm_accaln_paf, lrm_accaln_md: the alignment summary records of the batch
@@ -148,6 +175,8 @@ struct AccalnRun {
     const bool verbose = getenv("LRM_HOST_VERBOSE") != nullptr;            // stage times on stderr (tuning aid)
     lrm_map_options mopt;
     bool split = false;                                  // after a batch's wait its clipped ends go through lrm_split_batch
+    bool sec = false;                                    // ... and its candidates through lrm_secondary_batch (needs mapq)
+    lrm_secondary_options so;
     bool want_pinned = false;
     lrm_host_index hi;
     lrm_index *gpu = nullptr;
@@ -300,7 +329,8 @@ struct AccalnRun {
                 } else {
                     const SamBatch sb = {&s->b, hi.mta, hi.mta_len, s->cig.data(), s->score.data(), s->meta.data(), s->meta_r.data(), n,
                                          /* cigar_is_text */ true, /* revcomp_here */ true, split ? &s->sp.out : nullptr, mapq ? s->mq.data() : nullptr,
-                                         md ? s->sum.data() : nullptr, md ? s->diff_off.data() : nullptr, md ? s->diff_cnt.data() : nullptr, md ? s->events : nullptr};
+                                         md ? s->sum.data() : nullptr, md ? s->diff_off.data() : nullptr, md ? s->diff_cnt.data() : nullptr, md ? s->events : nullptr,
+                                         sec ? &s->sc.out : nullptr};
                     sam_format_parts(sb, io_threads, tb->parts);
                 }
                 t_fmt += now() - t0;
@@ -358,6 +388,18 @@ struct AccalnRun {
         return lrm_split_batch(gpu, s->b.seqs, s->b.stride, s->b.lens, n, s->cig.data(), s->meta.data(), s->meta_r.data(), p, gp, &mopt, o);
     }
 
+    // ... and over its candidates: size the buffers from the plan, then lrm_secondary_batch
+    int secondary_pass(BatchSet *s) {
+        const uint64_t n = s->b.n;
+        uint64_t k = 0;
+        if (lrm_secondary_plan(s->mq.data(), n, so.min_hits, so.ratio_pct, nullptr, 0, &k) == -1) return -1;
+        const uint64_t L = s->b.max_len;
+        const uint64_t need = (so.anchored || so.clip) ? 2 * L + L / 8 + 2 : 2 * L;
+        lrm_secondary_out *o = s->sc.fit(k, (L + 16) & ~15ull, ((need + 15) & ~15ull) + 16);
+        if (k == 0) return 0;
+        return lrm_secondary_batch(gpu, s->b.seqs, s->b.stride, s->b.lens, n, s->mq.data(), s->meta.data(), s->meta_r.data(), p, gp, &mopt, &so, o);
+    }
+
     void finish_oldest() {
         BatchSet *s = inflight.front();
         inflight.pop_front();
@@ -368,6 +410,7 @@ struct AccalnRun {
             mrc = -1;
         }
         if (!mrc && split) mrc = split_pass(s);
+        if (!mrc && sec) mrc = secondary_pass(s);
         t_map += now() - t0;
         if (verbose) fprintf(stderr, "[lrm accaln] %.3f waited %.3f s for a batch of %llu\n", now() - t_upload, now() - t0, (unsigned long long) s->b.n);
         s->ticket = nullptr;
@@ -464,8 +507,11 @@ struct AccalnRun {
 
 // one run of the flow: SAM (lrm_accaln*) or PAF (lrm_accaln_paf) into out_path
 static int accaln_run(const char *genome, const char *reads_path, const char *out_path, lrm_params p, lrm_gact_params gp, int device,
-                      long rg_id, uint64_t *total_out, uint64_t *valid_out, const lrm_map_options *user, bool mapq, bool paf, bool md = false) {
+                      long rg_id, uint64_t *total_out, uint64_t *valid_out, const lrm_map_options *user, bool mapq, bool paf, bool md = false,
+                      const lrm_secondary_options *so = nullptr) {
     AccalnRun r(p, gp, device, mapq, paf, md);
+    memset(&r.so, 0, sizeof(r.so));
+    if (so) { r.sec = true; lrm_options_over_defaults(&r.so, so); }
     if (r.take_options(user)) return -1;
     if (lrm_host_index_read(genome, &r.hi)) return -1;
     int rc = r.begin(reads_path, out_path, rg_id);
@@ -486,6 +532,13 @@ extern "C" int lrm_accaln_md(const char *genome, const char *reads_path, const c
                              lrm_gact_params gp, int device, long rg_id, uint64_t *total_out, uint64_t *valid_out,
                              const lrm_map_options *user, int mapq, int md) {
     return accaln_run(genome, reads_path, sam_path, p, gp, device, rg_id, total_out, valid_out, user, mapq != 0, false, md != 0);
+}
+// so: after a batch's wait its candidates go through lrm_secondary_batch, FLAG 256 lines print the reported ones
+// (lrm_sam_format_secondary); so == NULL: lrm_accaln_mapq with its mode on
+extern "C" int lrm_accaln_secondary(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
+                                    lrm_gact_params gp, int device, long rg_id, uint64_t *total_out, uint64_t *valid_out,
+                                    const lrm_map_options *user, const lrm_secondary_options *so) {
+    return accaln_run(genome, reads_path, sam_path, p, gp, device, rg_id, total_out, valid_out, user, true, false, false, so);
 }
 // PAF: the alignment summary records come back with every batch, lrm_paf_format's lines print them; no header
 extern "C" int lrm_accaln_paf(const char *genome, const char *reads_path, const char *paf_path, lrm_params p, lrm_gact_params gp,

@@ -168,3 +168,30 @@ struct LrmSplitArgs {                                      // lrm_split_batch_de
 int lrm_launch_split(lrm_index *idx, lrm_workspace *ws_seg, const LrmSplitArgs &a, const lrm_split_dev &out, uint64_t *n_seg,
                      void *stream);
 void lrm_split_scratch_free(lrm_workspace *ws);
+// secondary alignments (secondary_kernels.hip; docs/GACT_SPEC.md, "Secondary alignments")
+struct LrmSecArgs {                                        // lrm_secondary_batch_dev after its checks
+    const char *reads; uint64_t stride; const uint32_t *lens; uint64_t n;
+    const lrm_entry *best; const lrm_mapq *mapq;
+    const lrm_seq_meta *meta; const int32_t *meta_r;       // the primary's; null: the reads are as sequenced
+    uint32_t seed_len; lrm_gact_params gp;
+    uint32_t min_hits, ratio_pct, anchored, anchor_min_len, clip, clip_penalty, clip_end_bonus;
+};
+// lrm_secondary.flags of one candidate of `len` bases from the primary's locus (has_p: there is one to compare with) and its
+// own results; anchored: LRM_SEC_ALIGNED needs an anchor of the candidate's own.  THE rule: sec_flag_kernel and the
+// host-buffer path both go through it
+LRM_HD static inline uint32_t lrm_sec_flags(bool has_p, int32_t meta_r_p, const lrm_seq_meta &mp, int32_t meta_r, const lrm_seq_meta &m,
+                                            int32_t score, uint32_t len, bool anchored, uint32_t anchor_flags) {
+    uint32_t flags = 0;
+    if (has_p && meta_r_p != 0 && meta_r != 0 && m.seq_id == mp.seq_id && m.strand == mp.strand) {
+        const uint64_t a = m.off, b = mp.off;
+        if ((a > b ? a - b : b - a) < (uint64_t) (len / 2u)) flags |= LRM_SEC_DUPLICATE;
+    }
+    if (meta_r != 0 && score != -1 && !flags && (!anchored || (anchor_flags & LRM_ANCHOR_ANCHORED))) flags |= LRM_SEC_ALIGNED;
+    return flags;
+}
+// the rival entries of the batch whose survivor lists are in ws, right behind lrm_launch_mapq
+int lrm_launch_rival(lrm_index *idx, lrm_workspace *ws, const uint32_t *d_lens, uint64_t n, uint32_t seed_len, const lrm_entry *d_best,
+                     const lrm_mapq *d_mapq, uint32_t min_hits, uint32_t ratio_pct, lrm_entry *d_rival, void *stream);
+int lrm_launch_secondary(lrm_index *idx, lrm_workspace *ws, const LrmSecArgs &a, const lrm_secondary_dev &out, uint64_t *n_sec,
+                         void *stream);
+void lrm_sec_scratch_free(lrm_workspace *ws);

@@ -7,12 +7,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <vector>
 #include <sched.h>
 #include <omp.h>
 #include "lrm_hip_util.h"
 #include "extend_stage.h"
 #include "aln_diff_step.h"
+#include "rival_rule.h"
 
 static thread_local char g_err[512] = "";
 
@@ -468,6 +470,107 @@ extern "C" int lrm_split_batch_dev(lrm_index *idx, lrm_workspace *ws_seg, const 
     HIPCHK(hipSetDevice(idx->device));
     if (n == 0) return 0;
     return lrm_launch_split(idx, ws_seg, a, *out, n_seg, stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// secondary alignments (docs/GACT_SPEC.md, "Secondary alignments"): the rules on the host, and the device-buffer entry points
+// ------------------------------------------------------------------------------------------
+// The host rule sorts where the kernel hashes: the hits outside the winner's window as (bucket << 1 | histogram) words,
+// their runs are the pairs; then the offsets of the fullest pair's hits, their runs per sub-bucket.
+extern "C" int lrm_rival_host(const uint64_t *keys, uint64_t n_keys, const lrm_entry *best, uint32_t len, uint32_t min_hits,
+                              uint32_t ratio_pct, uint32_t slots, lrm_entry *out) {
+    if (!out || !best || (n_keys && !keys)) { lrm_set_error("null argument"); return -1; }
+    const uint32_t H = rv_min_hits(min_hits), pct = rv_ratio_pct(ratio_pct);
+    if (!H || !pct) { lrm_set_error("secondary: min_hits %u outside [1, 65535] or ratio_pct %u outside [1, 100]", min_hits, ratio_pct); return -1; }
+    if (slots == 0) slots = LRM_MAPQ_SLOTS;
+    out->key = out->val = out->bucket = 0;
+    if (best->val == 0) return 0;
+    const uint32_t r = mq_radius_log2(len);
+    struct Pair { uint64_t bucket; uint32_t h; uint64_t key; };
+    std::vector<Pair> hits;
+    uint32_t n1 = 0;
+    for (uint64_t i = 0; i < n_keys; ++i) {
+        if (mq_inside(keys[i], best->key, r)) { ++n1; continue; }
+        for (uint32_t h = 0; h < 2; ++h) hits.push_back(Pair{mq_bucket(keys[i], r, h), h, keys[i]});
+    }
+    std::sort(hits.begin(), hits.end(), [](const Pair &a, const Pair &b) { return a.bucket != b.bucket ? a.bucket < b.bucket : a.h < b.h; });
+    uint64_t pairs = 0, lo = 0, n2 = 0;                       // the first fullest run in (bucket, histogram) order
+    for (uint64_t i = 0, j; i < hits.size(); i = j, ++pairs) {
+        for (j = i + 1; j < hits.size() && hits[j].bucket == hits[i].bucket && hits[j].h == hits[i].h; ++j) {}
+        if (j - i > n2) { n2 = j - i; lo = i; }
+    }
+    const uint32_t flags = pairs > slots ? LRM_MAPQ_OVERFLOW : 0u;
+    if (!rv_candidate(n1, flags ? n1 : (uint32_t) n2, flags, H, pct)) return 0;
+    const uint32_t s = rv_sub_shift(r), h = hits[lo].h;
+    std::vector<uint32_t> offs;
+    for (uint64_t i = lo; i < lo + n2; ++i) offs.push_back(rv_off(hits[i].key, r, h));
+    std::sort(offs.begin(), offs.end());
+    uint64_t best_at = 0, best_n = 0;
+    for (uint64_t i = 0, j; i < offs.size(); i = j) {
+        for (j = i + 1; j < offs.size() && (offs[j] >> s) == (offs[i] >> s); ++j) {}
+        if (j - i > best_n) { best_n = j - i; best_at = i; }
+    }
+    out->key = rv_key_of(mq_tag(hits[lo].key, r, h), r, offs[best_at]);
+    out->val = best_n;
+    out->bucket = out->key >> 4;
+    return 1;
+}
+
+extern "C" int lrm_secondary_plan(const lrm_mapq *mapq, uint64_t n, uint32_t min_hits, uint32_t ratio_pct, lrm_secondary *table,
+                                  uint64_t cap, uint64_t *n_sec) {
+    if (!n_sec || (n && !mapq) || (cap && !table)) { lrm_set_error("null argument"); return -1; }
+    if (n > 0xFFFFFFFFull) { lrm_set_error("batch too large"); return -1; }
+    const uint32_t H = rv_min_hits(min_hits), pct = rv_ratio_pct(ratio_pct);
+    if (!H || !pct) { lrm_set_error("secondary: min_hits %u outside [1, 65535] or ratio_pct %u outside [1, 100]", min_hits, ratio_pct); return -1; }
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n; ++i) total += rv_candidate(mapq[i].n1, mapq[i].n2, mapq[i].flags, H, pct) != 0;
+    *n_sec = total;
+    if (total > cap) {
+        lrm_set_error("%llu secondary candidates, room for %llu", (unsigned long long) total, (unsigned long long) cap);
+        return -3;
+    }
+    uint64_t at = 0;
+    for (uint64_t i = 0; i < n; ++i)
+        if (rv_candidate(mapq[i].n1, mapq[i].n2, mapq[i].flags, H, pct)) table[at++] = lrm_secondary{(uint32_t) i, 0u, 0u, 0u};
+    return 0;
+}
+
+extern "C" int lrm_rival_dev(lrm_index *idx, lrm_workspace *ws, const uint32_t *d_lens, uint64_t n, lrm_params p,
+                             const lrm_entry *d_best, const lrm_mapq *d_mapq, uint32_t min_hits, uint32_t ratio_pct,
+                             lrm_entry *d_rival, void *stream) {
+    if (!idx || !ws || (n && (!d_lens || !d_best || !d_mapq || !d_rival))) { lrm_set_error("null argument"); return -1; }
+    if (ws->idx != idx) { lrm_set_error("workspace does not belong to this index"); return -1; }
+    if ((uintptr_t) d_mapq & 15u) { lrm_set_error("mapping-quality records must be 16-byte aligned"); return -1; }
+    if (lrm_ws_take_error(ws)) return -2;
+    HIPCHK(hipSetDevice(idx->device));
+    return lrm_launch_rival(idx, ws, d_lens, n, p.seed_len, d_best, d_mapq, min_hits, ratio_pct, d_rival, stream);
+}
+
+extern "C" int lrm_secondary_batch_dev(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint64_t stride, const uint32_t *d_lens,
+                                       uint64_t n, const lrm_entry *d_best, const lrm_mapq *d_mapq, const lrm_seq_meta *d_meta,
+                                       const int32_t *d_meta_r, lrm_params p, lrm_gact_params gp, const lrm_secondary_options *so,
+                                       const lrm_secondary_dev *out, uint64_t *n_sec, void *stream) {
+    if (!idx || !ws || !out || !n_sec || (n && (!d_reads || !d_lens || !d_best || !d_mapq))) { lrm_set_error("null argument"); return -1; }
+    *n_sec = 0;
+    if ((d_meta == nullptr) != (d_meta_r == nullptr)) { lrm_set_error("secondary: d_meta and d_meta_r come together"); return -1; }
+    lrm_secondary_options o;
+    memset(&o, 0, sizeof(o));
+    lrm_options_over_defaults(&o, so);
+    const uint32_t anchored = o.anchored || o.clip;
+    if (out->cap && (!out->table || !out->rows || !out->lens || !out->rival || !out->store || !out->n_ops || !out->score || !out->meta ||
+                     !out->meta_r || (anchored && !out->anchor) || (o.clip && !out->clip))) { lrm_set_error("null array in lrm_secondary_dev"); return -1; }
+    if (n > 0x7fffffffull) { lrm_set_error("batch too large"); return -1; }
+    if (ws->idx != idx) { lrm_set_error("workspace does not belong to this index"); return -1; }
+    if ((ws->parts & (LRM_WS_SEED | LRM_WS_EXTEND)) != (LRM_WS_SEED | LRM_WS_EXTEND)) { lrm_set_error("secondary: the workspace needs seed and extension scratch"); return -1; }
+    if (out->cap && (((uintptr_t) out->rows | out->row_stride | (uintptr_t) out->table) & 15u)) { lrm_set_error("secondary: table and rows must be 16-byte aligned, row_stride a multiple of 16"); return -1; }
+    if (out->cap && (out->store_stride & 3u)) { lrm_set_error("secondary: store_stride must be a multiple of 4"); return -1; }
+    if ((uintptr_t) d_mapq & 15u) { lrm_set_error("mapping-quality records must be 16-byte aligned"); return -1; }
+    const LrmSecArgs a = {d_reads, stride, d_lens, n, d_best, d_mapq, d_meta, d_meta_r, p.seed_len, gp, o.min_hits, o.ratio_pct, anchored,
+                          o.anchor_min_len, o.clip, o.clip_penalty, o.clip_end_bonus};
+    if (lrm_ws_take_error(ws)) return -2;
+    HIPCHK(hipSetDevice(idx->device));
+    if (n == 0) return 0;
+    return lrm_launch_secondary(idx, ws, a, *out, n_sec, stream);
 }
 
 extern "C" void lrm_result_flags(const int *score, const int *meta_r, const lrm_seq_meta *meta, uint64_t n,

@@ -11,6 +11,7 @@
 #include <cstring>
 #include <exception>
 #include "host_pipeline.h"
+#include "../../include/lrm_io_host.h"     // lrm_parse_cigar: the CIGAR text of the secondary pass
 
 namespace {
 
@@ -314,6 +315,143 @@ extern "C" int lrm_split_batch(lrm_index *idx, const char *reads_buf, uint64_t s
     if (out->cap && (!out->seg || !out->rows || !out->lens || !out->best || !out->cig || !out->store || !out->score || !out->meta ||
                      !out->meta_r || !out->anchor || !out->clip)) { lrm_set_error("null array in lrm_split_out"); return -1; }
     try { return split_batch_impl(idx, reads_buf, stride, lens, n, cig, meta, meta_r, p, gp, opt, out); }
+    catch (const std::exception &e) { lrm_set_error("host-side failure: %s", e.what()); return -1; }
+}
+
+// ---- secondary alignments: the second pass over a batch that came back with MAPQ records (docs/GACT_SPEC.md, "Secondary
+// alignments").  The host pipeline is not touched: the candidates -- few reads -- go through ONE synchronous device pass on
+// a workspace of their own: seed + mapping quality + rival on the candidate rows (a read's records do not depend on its
+// batch, so every row is a candidate again and gets the entry it has in the primary batch), the extension `so` names,
+// download, flags. ----
+namespace {
+struct SecWs {                                            // the pass's workspace, freed on every way out
+    lrm_workspace *ws = nullptr;
+    ~SecWs() { if (ws) lrm_workspace_free(ws); }
+};
+template <typename T>
+int sec_download(T *dst, const DevBuf &src, uint64_t count) {
+    HIPCHK(hipMemcpy(dst, src.p, count * sizeof(T), hipMemcpyDeviceToHost));
+    return 0;
+}
+}  // namespace
+
+static int secondary_batch_impl(lrm_index *idx, const char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
+                                const lrm_mapq *mapq, const lrm_seq_meta *meta, const int *meta_r, lrm_params p, lrm_gact_params gp,
+                                const lrm_map_options *opt, const lrm_secondary_options *so, lrm_secondary_out *out) {
+    lrm_index *ix = idx->peers ? idx->peers[0] : idx;     // a group handle: its first device does this pass
+    LrmMapTune mt = ix->mtune;
+    if (opt) lrm_call_map_tune(ix, opt, &mt);
+    lrm_secondary_options o;
+    memset(&o, 0, sizeof(o));
+    lrm_options_over_defaults(&o, so);
+    const bool anchored = o.anchored || o.clip;
+    if (out->cap && ((anchored && !out->anchor) || (o.clip && !out->clip))) { lrm_set_error("null array in lrm_secondary_out"); return -1; }
+    uint64_t k = 0;
+    const int prc = lrm_secondary_plan(mapq, n, o.min_hits, o.ratio_pct, out->table, out->cap, &k);
+    out->n_sec = k;
+    if (prc) return prc;
+    if (k == 0) return 0;
+    uint32_t longest = 0;
+    for (uint64_t s = 0; s < k; ++s) longest = lens[out->table[s].read] > longest ? lens[out->table[s].read] : longest;
+    if ((out->row_stride & 15u) || out->row_stride <= longest) {
+        lrm_set_error("secondary: row_stride %llu must be a multiple of 16 above the longest candidate (%u)", (unsigned long long) out->row_stride, longest);
+        return -1;
+    }
+    const uint64_t need = anchored ? lrm_anchored_store_stride(longest) : 2ull * longest;
+    if ((out->store_stride & 15u) || out->store_stride < need) {
+        lrm_set_error("secondary: store_stride %llu must be a multiple of 16 of at least %llu", (unsigned long long) out->store_stride, (unsigned long long) need);
+        return -1;
+    }
+    // gather on the host, as sequenced: without keep_reads the caller's copy of a reverse-strand read was reverse-complemented
+    const int nt = lrm_host_threads();
+#pragma omp parallel for schedule(dynamic, 64) num_threads(nt)
+    for (uint64_t s = 0; s < k; ++s) {
+        const uint32_t read = out->table[s].read, len = lens[read];
+        const char *src = reads_buf + (uint64_t) read * stride;
+        char *dst = out->rows + s * out->row_stride;
+        if (!mt.keep_reads && meta && meta_r[read] != 0 && meta[read].strand == 1)
+            for (uint32_t c = 0; c < len; ++c) dst[c] = split_comp(src[len - 1 - c]);
+        else memcpy(dst, src, len);
+        memset(dst + len, 0, (size_t) (out->row_stride - len));
+        out->lens[s] = len;
+    }
+    // the device pass
+    if (lrm_require_device(ix->device)) return -1;
+    SecWs w;
+    if (lrm_workspace_create(&w.ws, ix, k, longest, p.seed_len, p.thres)) return -1;
+    DevBuf d_rows, d_lens, d_best, d_mapq, d_rival, d_store, d_n_ops, d_score, d_meta, d_meta_r, d_anchor, d_clip;
+    if (d_rows.alloc(k * out->row_stride) || d_lens.alloc(k * 4) || d_best.alloc(k * sizeof(lrm_entry)) || d_mapq.alloc(k * sizeof(lrm_mapq)) ||
+        d_rival.alloc(k * sizeof(lrm_entry)) || d_store.alloc(k * out->store_stride) || d_n_ops.alloc(k * 4) || d_score.alloc(k * 4) ||
+        d_meta.alloc(k * sizeof(lrm_seq_meta)) || d_meta_r.alloc(k * 4) || d_anchor.alloc(k * sizeof(lrm_anchor)) || d_clip.alloc(k * sizeof(lrm_clip))) {
+        (void) hipGetLastError();
+        lrm_set_error("secondary: device allocation for %llu candidates failed", (unsigned long long) k);
+        return -1;
+    }
+    HIPCHK(hipMemcpy(d_rows.p, out->rows, k * out->row_stride, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_lens.p, out->lens, k * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_meta.p, 0, k * sizeof(lrm_seq_meta)));          // (the padding bytes of the records come down too)
+    HIPCHK(hipMemset(d_anchor.p, 0, k * sizeof(lrm_anchor)));
+    HIPCHK(hipMemset(d_clip.p, 0, k * sizeof(lrm_clip)));
+    uint8_t *d_phase = lrm_mapq_phase_buf(w.ws);
+    if (!d_phase) return -1;
+    const uint32_t *dl = (const uint32_t *) d_lens.p;
+    if (int rc = lrm_launch_seed(ix, w.ws, (const char *) d_rows.p, out->row_stride, dl, k, p.seed_len, p.thres, (lrm_entry *) d_best.p, mt, nullptr, d_phase)) return rc;
+    if (int rc = lrm_launch_mapq(ix, w.ws, dl, k, p.seed_len, p.thres, (const lrm_entry *) d_best.p, (lrm_mapq *) d_mapq.p, nullptr)) return rc;
+    if (int rc = lrm_launch_rival(ix, w.ws, dl, k, p.seed_len, (const lrm_entry *) d_best.p, (const lrm_mapq *) d_mapq.p, o.min_hits, o.ratio_pct,
+                                  (lrm_entry *) d_rival.p, nullptr)) return rc;
+    const LrmExtendBatch b = {(char *) d_rows.p, out->row_stride, dl, k, longest, (const lrm_entry *) d_rival.p, (uint8_t *) d_store.p,
+                              out->store_stride, (int32_t *) d_n_ops.p, (int32_t *) d_score.p, (lrm_seq_meta *) d_meta.p, (int32_t *) d_meta_r.p};
+    if (anchored) {
+        const LrmClipOpt clip = o.clip ? LrmClipOpt{1, o.clip_penalty, o.clip_end_bonus, (lrm_clip *) d_clip.p} : LrmClipOpt{};
+        if (int rc = lrm_launch_extend_anchored(ix, w.ws, b, gp, (lrm_anchor *) d_anchor.p, o.anchor_min_len, clip, mt, nullptr)) return rc;
+    } else if (int rc = lrm_launch_extend(ix, w.ws, b, gp, mt, nullptr)) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    if (lrm_ws_take_error(w.ws)) return -2;
+    // download: the rows as the extension left them, the small arrays, the op bytes in the layout opt names
+    std::vector<int32_t> n_ops((size_t) k);
+    std::vector<uint8_t> ops((size_t) (k * out->store_stride));
+    HIPCHK(hipMemcpy(out->rows, d_rows.p, k * out->row_stride, hipMemcpyDeviceToHost));
+    if (sec_download(out->rival, d_rival, k) || sec_download(n_ops.data(), d_n_ops, k) || sec_download(out->score, d_score, k) ||
+        sec_download(out->meta, d_meta, k) || sec_download(out->meta_r, d_meta_r, k) || sec_download(ops.data(), d_store, k * out->store_stride)) return -1;
+    if (anchored && sec_download(out->anchor, d_anchor, k)) return -1;
+    if (o.clip && sec_download(out->clip, d_clip, k)) return -1;
+    const uint64_t room = out->cap * out->store_stride;
+    uint64_t at = 0;                                      // dense layouts: where the next alignment goes
+    for (uint64_t s = 0; s < k; ++s) {
+        const bool aligned = out->meta_r[s] != 0 && out->score[s] != -1;
+        const uint8_t *src = ops.data() + s * out->store_stride;
+        lrm_cigar &c = out->cig[s];
+        c.n_cigar_op = n_ops[s]; c.score = out->score[s];
+        if (mt.cigar_text) {                              // the run-length text parse_cigar prints, NUL-terminated, 16-byte units
+            const int len = lrm_parse_cigar(src, aligned ? n_ops[s] : 0, (char *) out->store + at, (int) (room - at < 0x7fffffffull ? room - at : 0x7fffffffull));
+            if (len < 0) { lrm_set_error("secondary: the store has no room for the CIGAR text of candidate %llu", (unsigned long long) s); return -1; }
+            c.cigar = out->store + at;
+            at += ((uint64_t) len + 1 + 15) & ~15ull;
+        } else {
+            const uint64_t bytes = n_ops[s] > 0 ? (uint64_t) n_ops[s] : 0;
+            c.cigar = out->store + (mt.dense ? at : s * out->store_stride);
+            memcpy(c.cigar, src, bytes);
+            if (mt.dense) at += (bytes + 15) & ~15ull;
+        }
+        out->table[s].hits = (uint32_t) out->rival[s].val;
+        const uint32_t read = out->table[s].read;
+        const lrm_seq_meta none = {0, 0, -1, 0};
+        out->table[s].flags = lrm_sec_flags(meta != nullptr, meta ? meta_r[read] : 0, meta ? meta[read] : none, out->meta_r[s], out->meta[s],
+                                            out->score[s], out->lens[s], anchored, anchored ? out->anchor[s].flags : 0u);
+    }
+    return 0;
+}
+
+extern "C" int lrm_secondary_batch(lrm_index *idx, const char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
+                                   const lrm_mapq *mapq, const lrm_seq_meta *meta, const int *meta_r, lrm_params p, lrm_gact_params gp,
+                                   const lrm_map_options *opt, const lrm_secondary_options *so, lrm_secondary_out *out) {
+    if (!idx || !out || (n && (!reads_buf || !lens || !mapq))) { lrm_set_error("null argument"); return -1; }
+    out->n_sec = 0;
+    if ((meta == nullptr) != (meta_r == nullptr)) { lrm_set_error("secondary: meta and meta_r come together"); return -1; }
+    if (out->cap && (!out->table || !out->rows || !out->lens || !out->rival || !out->cig || !out->store || !out->score || !out->meta ||
+                     !out->meta_r)) { lrm_set_error("null array in lrm_secondary_out"); return -1; }
+    if (n > 0x7fffffffull) { lrm_set_error("batch too large"); return -1; }
+    try { return secondary_batch_impl(idx, reads_buf, stride, lens, n, mapq, meta, meta_r, p, gp, opt, so, out); }
     catch (const std::exception &e) { lrm_set_error("host-side failure: %s", e.what()); return -1; }
 }
 

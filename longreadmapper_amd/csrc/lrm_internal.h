@@ -269,6 +269,7 @@ struct lrm_workspace {
     struct LrmAnchorScratch *an;   // anchored mode (anchor_kernels.hip): allocated by its first call on this workspace
     struct LrmSplitScratch *sp;    // split stage (split_kernels.hip): allocated by its first call with this workspace as ws_seg
     uint8_t *d_mq_phase;           // mapping quality (mapq_kernels.hip): deciding phase per read, allocated by the first mapq call
+    struct LrmSecScratch *sec;     // secondary alignments (secondary_kernels.hip): allocated by the first lrm_secondary_batch_dev
 };
 
 int lrm_lcl_prepare_index(lrm_index *idx);       // index_tables.hip: the long lc table, the core table, the seed table

@@ -226,7 +226,32 @@ static void sam_split_lines(const SamBatch &b, uint64_t i, const SplitCtx &sx, s
 
 // SAM lines of reads [lo, hi) written to s (alnmain.c:500-525 field for field).  No snprintf on the hot path: a 10 kbp
 // ONT read has ~2000 CIGAR runs.  sx: the batch's split table, if it has segments.
-static void sam_format_range(const SamBatch &b, uint64_t lo, uint64_t hi, std::string &s, const SplitCtx *sx) {
+// ---- secondary alignments (docs/GACT_SPEC.md, "Secondary alignments") -------------------------------------------------------
+// the FLAG 256 line of candidate c of read i, if it is reported: its own locus and run-length CIGAR (soft clips as S), MAPQ 0,
+// no SEQ and no QUAL (the primary line has them), tp:A:S
+static void sam_secondary_line(const SamBatch &b, uint64_t i, uint64_t c, std::string &s) {
+    const lrm_secondary_out &o = *b.sec;
+    if (!(o.table[c].flags & LRM_SEC_ALIGNED)) return;
+    s += b.reads->names[i];
+    s += '\t'; put_num(s, 256u + (o.meta[c].strand == 1 ? 16u : 0u));
+    s += '\t'; put_rname(s, b, o.meta[c].seq_id);
+    s += '\t'; put_num(s, o.meta[c].off + 1);
+    s += "\t0\t";
+    put_cigar(s, o.cig[c], b.cigar_is_text);
+    s += "\t*\t0\t0\t*\t*\tED:I:"; put_int(s, o.score[c]);
+    s += "\ttp:A:S\n";
+}
+// where read i's candidate is in the table (reads ascending, one per read): sec_at[i], or UINT64_MAX
+static std::vector<uint64_t> sec_index(const lrm_secondary_out *o, uint64_t n) {
+    std::vector<uint64_t> at;
+    if (!o || !o->n_sec) return at;
+    at.assign((size_t) n, UINT64_MAX);
+    for (uint64_t c = 0; c < o->n_sec; ++c) if (o->table[c].read < n) at[o->table[c].read] = c;
+    return at;
+}
+
+static void sam_format_range(const SamBatch &b, uint64_t lo, uint64_t hi, std::string &s, const SplitCtx *sx,
+                             const std::vector<uint64_t> &sec_at) {
     const lrm_read_batch *reads = b.reads;
     const lrm_mapq *mq = b.mq;
     uint64_t est = 0;
@@ -273,6 +298,7 @@ static void sam_format_range(const SamBatch &b, uint64_t lo, uint64_t hi, std::s
         }
         if (sx && !unmapped) sam_split_lines(b, i, *sx, s);
         else s += '\n';
+        if (!sec_at.empty() && sec_at[(size_t) i] != UINT64_MAX) sam_secondary_line(b, i, sec_at[(size_t) i], s);
     }
 }
 
@@ -282,9 +308,10 @@ void sam_format_parts(const SamBatch &b, int nt, std::vector<std::string> &parts
     parts.resize((size_t) nt);
     const bool segs = b.split && b.split->n_seg;
     const SplitCtx sx(segs ? b.split : nullptr, segs ? b.n : 0);
+    const std::vector<uint64_t> sec_at = sec_index(b.sec, b.n);
     const uint64_t n = b.n, T = (uint64_t) nt;
 #pragma omp parallel for schedule(static, 1) num_threads(nt)
-    for (int t = 0; t < nt; ++t) sam_format_range(b, n * (uint64_t) t / T, n * (uint64_t) (t + 1) / T, parts[(size_t) t], segs ? &sx : nullptr);
+    for (int t = 0; t < nt; ++t) sam_format_range(b, n * (uint64_t) t / T, n * (uint64_t) (t + 1) / T, parts[(size_t) t], segs ? &sx : nullptr, sec_at);
 }
 
 std::vector<uint64_t> sam_part_offsets(const std::vector<std::string> &parts, uint64_t base) {
@@ -293,13 +320,15 @@ std::vector<uint64_t> sam_part_offsets(const std::vector<std::string> &parts, ui
     return at;
 }
 
-extern "C" char *lrm_sam_format_md(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig,
-                                   const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t n, int cigar_is_text,
-                                   int revcomp_here, const lrm_split_out *split, const lrm_mapq *mq, const lrm_aln_summary *sum,
-                                   const uint64_t *diff_off, const uint32_t *diff_cnt, const uint32_t *events, uint64_t *len_out) {
+extern "C" char *lrm_sam_format_secondary(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig,
+                                          const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t n, int cigar_is_text,
+                                          int revcomp_here, const lrm_split_out *split, const lrm_mapq *mq, const lrm_aln_summary *sum,
+                                          const uint64_t *diff_off, const uint32_t *diff_cnt, const uint32_t *events,
+                                          const lrm_secondary_out *sec, uint64_t *len_out) {
     if (events && (!sum || !diff_off || !diff_cnt)) { lrm_set_error("lrm_sam_format_md: events without summary records, offsets or counts"); return nullptr; }
+    if (sec && sec->n_sec && (!sec->table || !sec->cig || !sec->score || !sec->meta)) { lrm_set_error("lrm_sam_format_secondary: null array in lrm_secondary_out"); return nullptr; }
     const SamBatch b = {reads, mta, mta_len, cig, score, meta, meta_r, n, cigar_is_text != 0, revcomp_here != 0, split, mq,
-                        sum, diff_off, diff_cnt, events};
+                        sum, diff_off, diff_cnt, events, sec};
     std::vector<std::string> parts;
     sam_format_parts(b, lrm_host_threads(), parts);
     const std::vector<uint64_t> at = sam_part_offsets(parts, 0);
@@ -311,6 +340,13 @@ extern "C" char *lrm_sam_format_md(const lrm_read_batch *reads, const lrm_mta_en
     out[total] = 0;
     if (len_out) *len_out = total;
     return out;
+}
+extern "C" char *lrm_sam_format_md(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig,
+                                   const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t n, int cigar_is_text,
+                                   int revcomp_here, const lrm_split_out *split, const lrm_mapq *mq, const lrm_aln_summary *sum,
+                                   const uint64_t *diff_off, const uint32_t *diff_cnt, const uint32_t *events, uint64_t *len_out) {
+    return lrm_sam_format_secondary(reads, mta, mta_len, cig, score, meta, meta_r, n, cigar_is_text, revcomp_here, split, mq, sum, diff_off,
+                                    diff_cnt, events, nullptr, len_out);
 }
 extern "C" char *lrm_sam_format_mapq(const lrm_read_batch *reads, const lrm_mta_entry *mta, int mta_len, const lrm_cigar *cig,
                                      const int *score, const lrm_seq_meta *meta, const int *meta_r, uint64_t n, int cigar_is_text,

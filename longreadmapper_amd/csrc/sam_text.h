@@ -18,6 +18,7 @@ struct SamBatch {
     const lrm_mapq *mq;            // null: column 5 is 255, no v1:i / v2:i
     // the difference events of the batch (docs/GACT_SPEC.md, "Difference events and MD:Z"); events null: no NM:i / MD:Z
     const lrm_aln_summary *sum; const uint64_t *diff_off; const uint32_t *diff_cnt; const uint32_t *events;
+    const lrm_secondary_out *sec;  // null or no candidate: no FLAG 256 lines (docs/GACT_SPEC.md, "Secondary alignments")
 };
 
 // ---- the writers every field goes through (sam_text.cpp, paf_text.cpp) ----

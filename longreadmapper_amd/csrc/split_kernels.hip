@@ -21,9 +21,7 @@
 #include <hip/hip_runtime.h>
 #include "lrm_hip_util.h"
 #include "extend_stage.h"
-
-#define SP_BLOCK 256                          // reads per workgroup of split_count / split_mark
-#define SP_CHUNK 4096                         // bytes of a row one workgroup of split_gather moves
+#include "compact_rows.h"                     // SP_BLOCK, SP_CHUNK, sp_block_totals, sp_load16
 
 struct LrmSplitScratch {
     uint2 *blk; uint64_t blk_cap;             // per workgroup {segments, longest}; after split_scan .x = segments before it
@@ -38,23 +36,6 @@ __device__ __forceinline__ uint32_t sp_segments(const uint32_t *__restrict__ len
     if (r >= n) return 0;
     const uint2 c = *reinterpret_cast<const uint2 *>(clip + r);
     return lrm_split_segments((uint32_t) r, lens[r], c.x, c.y, M, two);
-}
-
-// sum and maximum over the workgroup's 4 wavefronts; `before`: the sum of the wavefronts below this one
-__device__ __forceinline__ void sp_block_totals(uint32_t wave_sum, uint32_t wave_max, uint32_t *s_sum, uint32_t *s_max,
-                                                uint32_t *before, uint32_t *all, uint32_t *longest) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (lane == 63) { s_sum[wave] = wave_sum; s_max[wave] = wave_max; }
-    __syncthreads();
-    uint32_t b = 0, a = 0, m = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < SP_BLOCK / 64; ++w) {
-        const uint32_t t = s_sum[w];
-        a += t;
-        b += w < wave ? t : 0u;
-        m = max(m, s_max[w]);
-    }
-    *before = b; *all = a; *longest = m;
 }
 
 __global__ __launch_bounds__(SP_BLOCK) void split_count_kernel(const uint32_t *__restrict__ lens, const lrm_clip *__restrict__ clip,
@@ -121,22 +102,9 @@ __global__ __launch_bounds__(256) void split_gather_kernel(const char *__restric
     const uint64_t d = (uint64_t) blockIdx.y * SP_CHUNK + 16ull * threadIdx.x;
     if (d >= len || d + 16 > row_stride) return;                   // (row_stride > len and % 16 == 0: the second never cuts a row short)
     const uint32_t cnt = len - d < 16 ? (uint32_t) (len - d) : 16u;
-    const char *src = reads + (uint64_t) sg.x * stride + sg.y + d;
-    const uint32_t off = (uint32_t) ((uintptr_t) src & 15u);
-    const uint4 *a = reinterpret_cast<const uint4 *>(src - off);
-    const uint4 lo = a[0];
-    const uint4 hi = off + cnt > 16 ? a[1] : make_uint4(0, 0, 0, 0);       // only when the lane's bytes reach into it
-    uint64_t w0 = lo.x | ((uint64_t) lo.y << 32), w1 = lo.z | ((uint64_t) lo.w << 32);
-    uint64_t w2 = hi.x | ((uint64_t) hi.y << 32);
-    const uint64_t w3 = hi.z | ((uint64_t) hi.w << 32);
-    if (off & 8u) { w0 = w1; w1 = w2; w2 = w3; }
-    const uint32_t sh = (off & 7u) * 8;
-    uint64_t o0 = sh ? (w0 >> sh) | (w1 << (64 - sh)) : w0;
-    uint64_t o1 = sh ? (w1 >> sh) | (w2 << (64 - sh)) : w1;
-    if (cnt < 16) {                                                 // the segment's last word: zeros behind its end
-        o0 &= cnt >= 8 ? ~0ull : (1ull << (8 * cnt)) - 1;
-        o1 &= cnt > 8 ? (1ull << (8 * (cnt - 8))) - 1 : 0ull;
-    }
+    uint64_t o0, o1;
+    sp_load16(reads + (uint64_t) sg.x * stride + sg.y + d, cnt, o0, o1);
+    if (cnt < 16) sp_keep_bytes(cnt, o0, o1);                       // the segment's last word: zeros behind its end
     *reinterpret_cast<uint4 *>(rows + s * row_stride + d) =
         make_uint4((uint32_t) o0, (uint32_t) (o0 >> 32), (uint32_t) o1, (uint32_t) (o1 >> 32));
 }

@@ -17,6 +17,7 @@ extern "C" void lrm_workspace_free(lrm_workspace *ws) {
     lrm_bs_scratch_free(&ws->bs);
     lrm_anchor_scratch_free(ws);
     lrm_split_scratch_free(ws);
+    lrm_sec_scratch_free(ws);
     if (ws->h_err) (void) hipHostFree((void *) ws->h_err);
     for (int i = 0; i < LRM_MAX_TIMED; ++i) {
         if (ws->ev_start[i]) (void) hipEventDestroy((hipEvent_t) ws->ev_start[i]);

@@ -6,7 +6,7 @@ import numpy as np
 from . import capi
 from .capi import check, lib
 from .records import (ANCHOR_DT, CLIP_DT, DEFAULT_GACT, DEFAULT_SEED_LEN, DEFAULT_THRES, ENTRY_DT, MAPQ_DT, META_DT, N_KERNELS,
-                      SEGMENT_DT, SUMMARY_DT, store_need, units16)
+                      SECONDARY_DT, SEGMENT_DT, SUMMARY_DT, store_need, units16)
 
 
 def _records(t, dt):
@@ -28,8 +28,15 @@ class DeviceMapper:
 
     def __init__(self, index, n_max, max_len, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT,
                  device=0, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0, split=False,
-                 split_min_len=0, seg_cap=None, seg_rows=None, mapq=False, summary=False, md=False):
-        """md (implies summary): extend() also makes the difference events of the batch (docs/GACT_SPEC.md, "Difference events
+                 split_min_len=0, seg_cap=None, seg_rows=None, mapq=False, summary=False, md=False, secondary=False, sec_cap=None,
+                 sec_min_hits=0, sec_ratio_pct=0):
+        """secondary (needs mapq): secondary() after seed() and extend() finds the rival locus of every candidate read and
+        extends the read there, in this mapper's extension mode (lrm_secondary_batch_dev; docs/GACT_SPEC.md, "Secondary
+        alignments"); secondary_results() returns the table and the per-candidate outputs.  sec_cap: room for that many
+        candidates (None: n_max, every read); sec_min_hits, sec_ratio_pct: H and pct of the candidate test (0: 8, 50).  Nothing is
+        allocated without it.  With split as well: secondary() comes before split() when the split stage runs on this
+        mapper's own workspace (seg_rows=0).
+        md (implies summary): extend() also makes the difference events of the batch (docs/GACT_SPEC.md, "Difference events
         and MD:Z": lrm_aln_diff_offsets_dev, then lrm_aln_diff_dev into a buffer of the batch's true total -- the one place
         extend() waits for the device: the total crosses to the host); diff_records(n) returns (offsets, events).
         summary: extend() runs the alignment summary stage behind the extension, whichever mode (lrm_aln_summary_dev);
@@ -65,6 +72,32 @@ class DeviceMapper:
         self.summary = self._record_tensor(n_max, SUMMARY_DT) if summary or md else None
         self.diff_off = torch.zeros(n_max + 1, dtype=torch.int64, device=self.dev) if md else None
         self.diff_events = torch.zeros(1, dtype=torch.int32, device=self.dev) if md else None
+        self.sec, self.n_sec = None, 0
+        if secondary:
+            if not mapq:
+                raise capi.LrmError("DeviceMapper: secondary needs mapq")
+            cap = self.sec_cap = n_max if sec_cap is None else sec_cap
+            k = max(cap, 1)
+            self.sec_row_stride = (max_len + 16) // 16 * 16
+            self.sec_store_stride = units16(self.store_stride)
+            g = self.sec = dict(table=self._record_tensor(k, SECONDARY_DT, torch.int32),
+                                rows=torch.zeros((k, self.sec_row_stride), dtype=torch.uint8, device=self.dev),
+                                lens=torch.zeros(k, dtype=torch.int32, device=self.dev),
+                                rival=self._record_tensor(k, ENTRY_DT, torch.int64),
+                                store=torch.zeros((k, self.sec_store_stride), dtype=torch.uint8, device=self.dev),
+                                n_ops=torch.zeros(k, dtype=torch.int32, device=self.dev),
+                                score=torch.zeros(k, dtype=torch.int32, device=self.dev), meta=self._record_tensor(k, META_DT),
+                                meta_r=torch.zeros(k, dtype=torch.int32, device=self.dev))
+            if anchored:
+                g["anchor"] = self._record_tensor(k, ANCHOR_DT)
+            if clip:
+                g["clip"] = self._record_tensor(k, CLIP_DT, torch.int32)
+            ptr = {name: t.data_ptr() for name, t in g.items()}
+            self.sec_dev = capi.SecondaryDev(cap, ptr["table"], ptr["rows"], self.sec_row_stride, ptr["lens"], ptr["rival"], ptr["store"],
+                                             self.sec_store_stride, ptr["n_ops"], ptr["score"], ptr["meta"], ptr["meta_r"],
+                                             ptr.get("anchor"), ptr.get("clip"))
+            self.sec_opt = capi.SecondaryOptions(C.sizeof(capi.SecondaryOptions), sec_min_hits, sec_ratio_pct, int(anchored),
+                                                 anchor_min_len, int(bool(clip)), clip_penalty, clip_end_bonus)
         self.split_on, self.split_min_len, self.ws_seg, self.n_seg = bool(split), split_min_len, None, 0
         if split:
             if not clip:
@@ -179,6 +212,43 @@ class DeviceMapper:
         if rc < 0:
             raise capi.failure("lrm_split_batch_dev", rc=rc, n_seg=int(k.value))
         return self.n_seg
+
+    def rival(self, d_lens, n, min_hits=0, ratio_pct=0):
+        """lrm_rival_dev right behind seed() (mapq=True) -> the (n, 3) int64 device tensor of the rival entries."""
+        assert self.mapq is not None
+        out = self._record_tensor(max(n, 1), ENTRY_DT, self.torch.int64)
+        check(lib.lrm_rival_dev(self.index.handle, self.ws, d_lens.data_ptr(), n, capi.Params(n, self.seed_len, self.thres),
+                                self.best.data_ptr(), self.mapq.data_ptr(), min_hits, ratio_pct, out.data_ptr(), self._stream()),
+              "lrm_rival_dev")
+        return out[:n]
+
+    def secondary(self, d_reads, d_lens, n=None, as_sequenced=False):
+        """lrm_secondary_batch_dev after seed() and extend() on the same stream -> number of candidates (the call waits for
+        that count).  as_sequenced: extend() has not run on d_reads (no duplicate test).  More than sec_cap raise LrmError
+        with .rc == -3 and .n_sec."""
+        assert self.sec is not None
+        n = d_reads.shape[0] if n is None else n
+        k = C.c_uint64()
+        meta, meta_r = (None, None) if as_sequenced else (self.meta.data_ptr(), self.meta_r.data_ptr())
+        rc = lib.lrm_secondary_batch_dev(self.index.handle, self.ws, d_reads.data_ptr(), d_reads.stride(0), d_lens.data_ptr(), n,
+                                         self.best.data_ptr(), self.mapq.data_ptr(), meta, meta_r,
+                                         capi.Params(n, self.seed_len, self.thres), capi.GactParams(*self.gact), C.byref(self.sec_opt),
+                                         C.byref(self.sec_dev), C.byref(k), self._stream())
+        self.n_sec = int(k.value) if rc >= 0 else 0
+        if rc < 0:
+            raise capi.failure("lrm_secondary_batch_dev", rc=rc, n_sec=int(k.value))
+        return self.n_sec
+
+    def secondary_results(self):
+        """The outputs of the last secondary() as numpy arrays: table (SECONDARY_DT), rows, lens, rival, ops, n_ops, score,
+        meta, meta_r and, in the anchored modes, anchor / clip."""
+        k = self.n_sec
+        h = {"ops" if name == "store" else name: t[:k].cpu().numpy() for name, t in self.sec.items()}
+        for name, dt in (("table", SECONDARY_DT), ("rival", ENTRY_DT), ("meta", META_DT), ("anchor", ANCHOR_DT), ("clip", CLIP_DT)):
+            if name in h:
+                h[name] = h[name].reshape(-1).view(dt)
+        h["lens"] = h["lens"].view(np.uint32)
+        return h
 
     def seg_timing(self):
         """timing() of the segment workspace (the split stage's own kernels are in the revcomp_kernel slot)."""

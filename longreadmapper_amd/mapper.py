@@ -12,7 +12,7 @@ from . import capi
 from .capi import check, lib
 from .device import DeviceMapper  # noqa: F401  (every public name of the binding stays importable from here)
 from .records import (ANCHOR_DT, CIGAR_DT, CLIP_DT, DEFAULT_GACT, DEFAULT_SEED_LEN, DEFAULT_THRES, ENTRY_DT, MAPQ_DT,  # noqa: F401
-                      MAPQ_OVERFLOW, META_DT, N_KERNELS, DIFF_NO_ROOM, SEG_ALIGNED, SEG_RIGHT, SEGMENT_DT, SUMMARY_DT, anchored_store_stride,
+                      MAPQ_OVERFLOW, META_DT, N_KERNELS, DIFF_NO_ROOM, SEC_ALIGNED, SEC_DUPLICATE, SECONDARY_DT, SEG_ALIGNED, SEG_RIGHT, SEGMENT_DT, SUMMARY_DT, anchored_store_stride,
                       store_need, units16)
 from .textio import cigar_table
 
@@ -393,6 +393,62 @@ def split_batch(index, reads, lens, res, seed_len=DEFAULT_SEED_LEN, thres=DEFAUL
                              C.byref(buffers.out))
     if rc < 0:
         raise capi.failure("lrm_split_batch", rc=rc, n_seg=int(buffers.out.n_seg))
+    return buffers.result(dense=dense, text=text)
+
+
+class SecondaryBuffers(ResultBuffers):
+    """Host arrays of an lrm_secondary_out for up to cap candidates of up to max_len bases."""
+
+    def __init__(self, cap, max_len, anchored):
+        self.cap = cap
+        self.row_stride = (max_len + 16) // 16 * 16
+        self.store_stride = max(units16(store_need(max_len, anchored)), 16)
+        k = max(cap, 1)
+        super().__init__(k, self.store_stride)
+        self.table = np.zeros(k, dtype=SECONDARY_DT)
+        self.rows = np.zeros((k, self.row_stride), dtype=np.uint8)
+        self.lens = np.zeros(k, dtype=np.uint32)
+        self.anchor = np.zeros(k, dtype=ANCHOR_DT)
+        self.clip = np.zeros(k, dtype=CLIP_DT)
+        cig, store, store_stride, score, meta, meta_r = self.out_args
+        self.out = capi.SecondaryOut(cap, 0, self.table.ctypes.data, self.rows.ctypes.data, self.row_stride, self.lens.ctypes.data,
+                                     self.best.ctypes.data, cig, store, store_stride, score, meta, meta_r, self.anchor.ctypes.data,
+                                     self.clip.ctypes.data)
+
+    def result(self, dense=False, text=None):
+        res = super().result(int(self.out.n_sec), dense, text, table=self.table, rows=self.rows, lens=self.lens, anchor=self.anchor,
+                             clip=self.clip)
+        res["rival"] = res.pop("best")
+        res["buffers"] = self
+        return res
+
+
+def secondary_batch(index, reads, lens, res, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT, options=None,
+                    anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0, min_hits=0, ratio_pct=0, cap=None):
+    """lrm_secondary_batch: the second pass over `res`, what map_batch(index, reads, lens, mapq=True, ...) returned for `reads`
+    (as that call left them; options: that call's -- keep_reads says whether reverse-strand reads were turned round, cigar_text
+    / dense_results the layout of the candidates' alignments).  anchored / clip ...: the extension the candidates go through.
+    -> dict(table=SECONDARY_DT, rows, lens, rival, ops, n_ops, score, meta, meta_r, anchor, clip [, ops_off]); ops_of / text_of
+    read a candidate's alignment like a read's; res["buffers"].out is the lrm_secondary_out (textio.sam_format(secondary=...)).
+    cap: room for that many candidates (None: every read); more raise LrmError with .rc == -3 and .n_sec."""
+    reads = np.ascontiguousarray(reads, dtype=np.uint8)
+    lens = np.ascontiguousarray(lens, dtype=np.uint32)
+    n, stride = reads.shape
+    opt = capi.map_options(**options) if options is not None else None
+    text = bool(opt.cigar_text) if opt is not None else False
+    dense = (bool(opt.dense_results) or text) if opt is not None else False
+    anchored = bool(anchored or clip)
+    so = capi.SecondaryOptions(C.sizeof(capi.SecondaryOptions), min_hits, ratio_pct, int(anchored), anchor_min_len, int(bool(clip)),
+                               clip_penalty, clip_end_bonus)
+    buffers = SecondaryBuffers(n if cap is None else cap, int(lens.max()) if n else 0, anchored)
+    mq = np.ascontiguousarray(res["mapq"], dtype=MAPQ_DT)
+    meta = np.ascontiguousarray(res["meta"], dtype=META_DT)
+    meta_r = np.ascontiguousarray(res["meta_r"], dtype=np.int32)
+    rc = lib.lrm_secondary_batch(index.handle, reads.ctypes.data, stride, lens.ctypes.data, n, mq.ctypes.data, meta.ctypes.data,
+                                 meta_r.ctypes.data, capi.Params(n, seed_len, thres), capi.GactParams(*gact),
+                                 C.byref(opt) if opt is not None else None, C.byref(so), C.byref(buffers.out))
+    if rc < 0:
+        raise capi.failure("lrm_secondary_batch", rc=rc, n_sec=int(buffers.out.n_sec))
     return buffers.result(dense=dense, text=text)
 
 

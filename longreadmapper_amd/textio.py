@@ -104,12 +104,21 @@ def md_text(events, n_eq):
     return buf.raw[:k].decode()
 
 
-def sam_format(batch, mta, cig, score, meta, meta_r, n, *, is_text=0, keep=0, split=None, mapq=None, entry=None, md=None):
-    """md: (summary records, offsets, counts, events) of the batch, or a map_batch(md=True) result with summary=True --
+def sam_format(batch, mta, cig, score, meta, meta_r, n, *, is_text=0, keep=0, split=None, mapq=None, entry=None, md=None,
+               secondary=None):
+    """secondary: an lrm_secondary_out (or entry == "lrm_sam_format_secondary", then None stands for NULL) --
+    lrm_sam_format_secondary: a FLAG 256 line behind the lines of every read with a reported secondary.
+    md: (summary records, offsets, counts, events) of the batch, or a map_batch(md=True) result with summary=True --
     lrm_sam_format_md: NM:i and MD:Z behind ED:I (None for events: the lines of lrm_sam_format_mapq).
     The SAM records of a batch: lrm_sam_format_mapq with mapq (MAPQ_DT records), lrm_sam_format_split with split (an
     lrm_split_out), run-length text (is_text) or untouched reads (keep), else lrm_sam_format; entry names one of the three
     instead (the later ones take NULL for what the earlier ones lack)."""
+    if secondary is not None or entry == "lrm_sam_format_secondary":
+        if isinstance(md, dict):
+            md = (md["summary"], md["md_off"], md["md_cnt"], md["md_events"])
+        md = (None,) * 4 if md is None else md
+        return _text(lib.lrm_sam_format_secondary, C.byref(batch), mta, len(mta), _at(cig), _at(score), _at(meta), _at(meta_r), n,
+                     int(is_text), int(keep), _at(split), _at(mapq), *(_at(x) for x in md), _at(secondary))
     if md is not None or entry == "lrm_sam_format_md":
         if isinstance(md, dict):
             md = (md["summary"], md["md_off"], md["md_cnt"], md["md_events"])
@@ -126,21 +135,42 @@ def sam_format(batch, mta, cig, score, meta, meta_r, n, *, is_text=0, keep=0, sp
     return _text(getattr(lib, entry), *args)
 
 
+def secondary_out(res):
+    """The lrm_secondary_out of DeviceMapper.secondary_results() (op bytes in rows) for sam_format(secondary=...) -> (the
+    struct, the arrays it points into, which the caller keeps for as long as the struct is in use)."""
+    k = len(res["table"])
+    held = {name: np.ascontiguousarray(res[name]) for name in ("table", "rows", "lens", "rival", "ops", "score", "meta", "meta_r")}
+    held["score"], held["meta_r"] = held["score"].astype(np.int32), held["meta_r"].astype(np.int32)
+    ops = held["ops"]
+    stride = ops.strides[0] if k else 0
+    held["cig"] = cigar_table(np.uint64(ops.ctypes.data) + np.uint64(stride) * np.arange(k, dtype=np.uint64), res["n_ops"], held["score"])
+    for name in ("anchor", "clip"):
+        held[name] = np.ascontiguousarray(res[name]) if name in res else None
+    at = {name: (a.ctypes.data if a is not None else None) for name, a in held.items()}
+    out = capi.SecondaryOut(k, k, at["table"], at["rows"], held["rows"].strides[0] if k else 0, at["lens"], at["rival"], at["cig"],
+                            at["ops"], stride, at["score"], at["meta"], at["meta_r"], at["anchor"], at["clip"])
+    return out, held
+
+
 def paf_format(batch, mta, cig, score, meta, meta_r, n, summary, *, is_text=0, mapq=None):
     """lrm_paf_format: the PAF lines of a batch from its SUMMARY_DT records [and MAPQ_DT records]."""
     return _text(lib.lrm_paf_format, C.byref(batch), mta, len(mta), _at(cig), _at(score), _at(meta), _at(meta_r), n, int(is_text),
                  _at(summary), _at(mapq))
 
 
-def accaln(genome, reads, out, batch_size, seed_len=20, thres=300, gact=(0, 0, 0), device=0, rg_id=1, options=None, mapq=0, paf=False, md=False):
-    """md: NM:i and MD:Z on every mapped primary line (lrm_accaln_md).
+def accaln(genome, reads, out, batch_size, seed_len=20, thres=300, gact=(0, 0, 0), device=0, rg_id=1, options=None, mapq=0, paf=False, md=False,
+           secondary=None):
+    """secondary: an lrm_secondary_options (capi.SecondaryOptions) -- lrm_accaln_secondary: the flow of lrm_accaln_mapq plus a FLAG
+    256 line for every reported secondary alignment.
+    md: NM:i and MD:Z on every mapped primary line (lrm_accaln_md).
     A whole reads file to SAM (paf: PAF) -> (total, valid): lrm_accaln_paf, or the first of lrm_accaln_mapq / lrm_accaln_opt
     / lrm_accaln that takes what was given (options: an lrm_map_options).  A failure raises LrmError with the code in .rc."""
     total, valid = C.c_uint64(), C.c_uint64()
     head = (os.fsencode(genome), os.fsencode(reads), os.fsencode(out), capi.Params(batch_size, seed_len, thres), capi.GactParams(*gact), device)
     counts, opt = (C.byref(total), C.byref(valid)), _at(options)
     assert not (md and paf), "PAF lines carry no MD:Z"
-    entry, tail = (("lrm_accaln_paf", (*counts, opt, mapq)) if paf else ("lrm_accaln_md", (rg_id, *counts, opt, mapq, 1)) if md else ("lrm_accaln_mapq", (rg_id, *counts, opt, mapq)) if mapq else
+    assert secondary is None or not (md or paf), "the secondary flow prints SAM without MD:Z"
+    entry, tail = (("lrm_accaln_secondary", (rg_id, *counts, opt, C.byref(secondary))) if secondary is not None else ("lrm_accaln_paf", (*counts, opt, mapq)) if paf else ("lrm_accaln_md", (rg_id, *counts, opt, mapq, 1)) if md else ("lrm_accaln_mapq", (rg_id, *counts, opt, mapq)) if mapq else
                    ("lrm_accaln_opt", (rg_id, *counts, opt)) if options is not None else ("lrm_accaln", (rg_id, *counts)))
     rc = getattr(lib, entry)(*head, *tail)
     if rc < 0:
