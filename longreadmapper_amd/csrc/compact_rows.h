@@ -1,6 +1,8 @@
 // compact_rows.h -- what the stages that make a second, compact batch on the device share (split_kernels.hip: the clipped
 // ends; secondary_kernels.hip: the candidates of a secondary alignment): the workgroup step of the count / scan / mark order
-// and the realigned 16-byte load of the row gather (device code only)
+// and the realigned 16-byte load of the row gather (device code only).  Past one workgroup, one scan tile and one chunk both
+// stages are pinned by tests/test_gpu_compact_rows.py on the inputs of tests/compact_cases.py (tests/test_compact_cases_cpu.py
+// ties those inputs to the host plans)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -252,27 +252,17 @@ def _same_meta(a, b):
     return all(np.array_equal(a[f], b[f]) for f in ("loc", "off", "seq_id", "strand"))
 
 
-@pytest.mark.parametrize("mode", list(MODES))
-def test_the_stage_launches_the_stages_unchanged(planted, gpu, mode):
+def _same_as_the_extension_call(di, gpu, mode, reads, lens, cand, entries, out):
+    """Every per-candidate output of a stage result `out` against the unchanged extension call of the mode over a batch made of
+    the reads[cand] as sequenced, with best = entries[cand] ((n, 3) uint64 rival entries)."""
     import torch
-    r, di = planted["r"], planted["di"]
-    reads, lens = r["reads"], r["lens"].astype(np.uint32)
-    prim, _, oriented, _, out, _, _ = _stage(di, gpu, reads, lens, mode)
-    cand = np.flatnonzero(planted["want"][:, 1] > 0)
     k = len(cand)
-    assert k >= 40 and np.array_equal(out["table"]["read"], cand) and not out["table"]["_pad"].any()
-    assert np.array_equal(out["table"]["hits"], planted["want"][cand, 1]) and np.array_equal(out["lens"], lens[cand])
-    for f, col in (("key", 0), ("val", 1), ("bucket", 2)):
-        assert np.array_equal(out["rival"][f], planted["want"][cand, col]), f
-    # the candidate batch as sequenced, through the unchanged extension call of the mode
-    mirrored = (prim["meta_r"][cand] != 0) & (prim["meta"]["strand"][cand] == 1)
-    assert mirrored.sum() >= 5 and (~mirrored).sum() >= 5 and not np.array_equal(oriented[cand[mirrored]], reads[cand[mirrored]])
     rows = np.zeros((k, out["rows"].shape[1]), dtype=np.uint8)
     rows[:, :reads.shape[1]] = reads[cand]
     d2 = mapper.DeviceMapper(di, k, reads.shape[1] - 1, device=gpu, **MODES[mode])
     try:
         d_rows, d_lens = torch.from_numpy(rows).cuda(), torch.from_numpy(lens[cand].astype(np.int32)).cuda()
-        d2.best[:k] = torch.from_numpy(planted["want"][cand].view(np.int64)).cuda()
+        d2.best[:k] = torch.from_numpy(entries[cand].view(np.int64)).cuda()
         d2.extend(d_rows, d_lens)
         torch.cuda.synchronize()
         want, rows_after = d2.results(k), d_rows.cpu().numpy()
@@ -288,6 +278,23 @@ def test_the_stage_launches_the_stages_unchanged(planted, gpu, mode):
         if name in want:
             assert out[name].tobytes() == want[name].tobytes(), name
     assert np.array_equal(out["rows"], rows_after)
+
+
+@pytest.mark.parametrize("mode", list(MODES))
+def test_the_stage_launches_the_stages_unchanged(planted, gpu, mode):
+    r, di = planted["r"], planted["di"]
+    reads, lens = r["reads"], r["lens"].astype(np.uint32)
+    prim, _, oriented, _, out, _, _ = _stage(di, gpu, reads, lens, mode)
+    cand = np.flatnonzero(planted["want"][:, 1] > 0)
+    k = len(cand)
+    assert k >= 40 and np.array_equal(out["table"]["read"], cand) and not out["table"]["_pad"].any()
+    assert np.array_equal(out["table"]["hits"], planted["want"][cand, 1]) and np.array_equal(out["lens"], lens[cand])
+    for f, col in (("key", 0), ("val", 1), ("bucket", 2)):
+        assert np.array_equal(out["rival"][f], planted["want"][cand, col]), f
+    # the candidate batch as sequenced, through the unchanged extension call of the mode
+    mirrored = (prim["meta_r"][cand] != 0) & (prim["meta"]["strand"][cand] == 1)
+    assert mirrored.sum() >= 5 and (~mirrored).sum() >= 5 and not np.array_equal(oriented[cand[mirrored]], reads[cand[mirrored]])
+    _same_as_the_extension_call(di, gpu, mode, reads, lens, cand, planted["want"], out)
     # the rows are the reads as sequenced -- turned round by THIS extension where the rival resolved to the reverse strand --
     # and every byte behind a row's end is 0
     turned = (out["meta_r"] != 0) & (out["meta"]["strand"] == 1)
