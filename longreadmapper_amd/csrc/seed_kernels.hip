@@ -102,6 +102,16 @@ __device__ __forceinline__ uint64_t read_window(const uint64_t *__restrict__ wor
     return (w.a >> sh) | ((w.b << 1) << (63 - sh));       // sh == 0: the second term shifts out entirely
 }
 
+// One survivor into the LDS list of its phase.  s_tot[ph] holds the phase's survivor count in its low word and the sum of
+// their rr in its high word, so ONE returning 64-bit LDS add reserves the slot and adds the hits (the sum wraps at 32 bits
+// out of the top of the word, as the 32-bit global sum it goes into does).
+__device__ __forceinline__ void ss_append(uint64_t *s_tot, uint64_t *s_rec, uint32_t *s_q, uint32_t cap_pp, uint32_t ph, uint32_t q, uint64_t k,
+                                          uint64_t rr) {
+    const uint32_t slot = (uint32_t) atomicAdd(reinterpret_cast<unsigned long long *>(&s_tot[ph]), 1ull | (rr << 32));
+    s_rec[ph * cap_pp + slot] = k | (rr << 40);
+    s_q[ph * cap_pp + slot] = q;
+}
+
 // ----------------------------------------------------------------------------------------
 // K1 seed_search: one lane per seed, SS_ITEMS seeds per workgroup (4 or 8 per thread).  Work items of a read are
 // (q, iter) with iter fastest, so the 64 lanes of a wavefront hold 64 CONSECUTIVE read positions.
@@ -121,7 +131,10 @@ __device__ __forceinline__ uint64_t read_window(const uint64_t *__restrict__ wor
 // COUNT: the counting build (lrm_workspace_set_counting; bench bookkeeping, never in a timed region) adds up the
 // memory requests the device layout really makes -- seeds evaluated, 8-byte table lookups, 16-byte rank requests --
 // into counters->seed_traffic.
-template <int SS_ITEMS, bool COUNT>
+// SD48: the instantiation for the seed table's usual form (E. coli- to chr1-sized texts: four positions per line, 8-byte
+// slots, tags of at most 32 bits; the launcher checks idx->view): the shared-lines loop is compiled for that form alone,
+// with no branch on the other table forms in it.  Every other handle, and the counting build, take the generic one.
+template <int SS_ITEMS, bool COUNT, bool SD48>
 __global__ __launch_bounds__(256) void seed_search_kernel(LrmIndexView ix, const uint64_t *__restrict__ reads2,
                                                           uint64_t words_per_read,
                                                           const uint32_t *__restrict__ lens,
@@ -136,7 +149,8 @@ __global__ __launch_bounds__(256) void seed_search_kernel(LrmIndexView ix, const
     uint32_t my_cnt[2] = {0, 0}, my_seeds = 0;
     if (COUNT && threadIdx.x < 3) s_traffic[threadIdx.x] = 0;
     __shared__ uint32_t s_q[SS_ITEMS + 64];
-    __shared__ uint32_t s_cnt[64], s_hits[64], s_base[64];
+    __shared__ uint64_t s_tot[64];
+    __shared__ uint32_t s_base[64];
     const uint64_t read = blockIdx.x / blocks_per_read;
     const uint32_t chunk = blockIdx.x % blocks_per_read;
     if (read >= n) return;
@@ -145,7 +159,7 @@ __global__ __launch_bounds__(256) void seed_search_kernel(LrmIndexView ix, const
     const uint32_t np = (uint32_t) (phase_hi - phase_lo + 1);
     const uint32_t cap_pp = SS_ITEMS / np + 1;                 // survivors of one phase in one workgroup
     const uint32_t tid = threadIdx.x;
-    if (tid < np) { s_cnt[tid] = 0; s_hits[tid] = 0; }
+    if (tid < np) s_tot[tid] = 0;
     __syncthreads();
     // iter fastest: neighbouring seeds overlap, so they share their fate (a sequencing error kills ~20 consecutive
     // seeds, a clean stretch lets all of them run the full backward extension): wavefronts diverge little.
@@ -170,6 +184,8 @@ __global__ __launch_bounds__(256) void seed_search_kernel(LrmIndexView ix, const
     const bool shared_lines = ix.sd && seed_len == ix.sd_len && np == (uint32_t) P && phase_lo == 0;
     LrmIndexView ix_nosd = ix;
     ix_nosd.sd = nullptr;
+    LrmIndexView ixs = ix;                                        // the seed table as the shared-lines loop sees it
+    if (SD48) { ixs.sd_f = 4; ixs.sd_slot = 8; }
     if (shared_lines) {
         // All phases in this launch: a lane's item IS its read position j, lane id == j mod sd_f, and the lanes that share a
         // line of the seed table fetch it together (sd_issue_shared): every lane of the wavefront stays in until the line is
@@ -177,8 +193,18 @@ __global__ __launch_bounds__(256) void seed_search_kernel(LrmIndexView ix, const
         const uint32_t lim = jl < cap_q * np ? jl : cap_q * np;                                     // positions with a seed
         const uint32_t np_inv = 0xFFFFFFFFu / np;
         const uint64_t smask = (1ull << (2 * seed_len)) - 1ull;
+        // (q, ph) = (j / np, j % np) of the lane's position: worked out once (no division: a multiply-high and two fix-ups),
+        // then carried -- j grows by 256 per iteration, so by 256 / np and 256 % np with one wrap
+        const uint32_t dq = 256u / np, dph = 256u % np;
+        uint32_t q = __umulhi(chunk * SS_ITEMS + tid, np_inv), ph = chunk * SS_ITEMS + tid - q * np;
+        if (ph >= np) { ++q; ph -= np; }
+        if (ph >= np) { ++q; ph -= np; }
 #pragma unroll 1
         for (uint32_t it = 0; it < SS_ITEMS / 256; ++it) {
+            if (it) {
+                q += dq; ph += dph;
+                if (ph >= np) { ++q; ph -= np; }
+            }
             const uint32_t j = chunk * SS_ITEMS + it * 256 + tid;
             const bool have = j < lim;
             const uint32_t j0 = (uint32_t) __builtin_amdgcn_readfirstlane((int) (j & ~63u));        // lane 0's position: a multiple of 64
@@ -188,24 +214,19 @@ __global__ __launch_bounds__(256) void seed_search_kernel(LrmIndexView ix, const
             const uint32_t rel = j - j0, sh = (rel & 31u) * 2u;
             const uint64_t lo = rel < 32u ? W0 : W1, hi = rel < 32u ? W1 : W2;
             const uint64_t code = have ? ((lo >> sh) | ((hi << 1) << (63 - sh))) & smask : 0ull;
-            const SdKey key = sd_key_of(ix, code, j & (uint32_t) (ix.sd_f - 1));
+            const SdKey key = sd_key_of(ixs, code, j & (uint32_t) (ixs.sd_f - 1));
+            if (SD48) __builtin_assume(key.tb <= 32u);
             ulonglong2 xa, xb;
-            sd_issue_shared(ix, key, xa, xb);
+            sd_issue_shared(ixs, key, xa, xb);
             uint64_t k = 0, l = 0, c = 0, rr;
-            const int st = sd_finish_shared(ix, key, code, xa, xb, k, c, COUNT ? my_cnt : nullptr);
+            const int st = sd_finish_shared(ixs, key, code, xa, xb, k, c, COUNT ? my_cnt : nullptr);
             if (!have) continue;
             if (st == 1) rr = c;
             else if (st == 0) rr = 0;
             else rr = seed_one(ix_nosd, code, seed_len, j, k, l, COUNT ? my_cnt : nullptr);           // (a count beyond 24 bits)
             if (COUNT) my_seeds++;
             if (rr > 0 && rr < (uint64_t) thres) {
-                uint32_t q = __umulhi(j, np_inv), ph = j - q * np;                                  // j / np, j % np without a division
-                if (ph >= np) { ++q; ph -= np; }
-                if (ph >= np) { ++q; ph -= np; }
-                const uint32_t slot = atomicAdd(&s_cnt[ph], 1u);
-                atomicAdd(&s_hits[ph], (uint32_t) rr);
-                s_rec[ph * cap_pp + slot] = k | (rr << 40);
-                s_q[ph * cap_pp + slot] = q;
+                ss_append(s_tot, s_rec, s_q, cap_pp, ph, q, k, rr);
             }
         }
     } else {
@@ -243,34 +264,39 @@ __global__ __launch_bounds__(256) void seed_search_kernel(LrmIndexView ix, const
         }
         const uint64_t rr = seed_one(ix, win, seed_len, j, k, l, COUNT ? my_cnt : nullptr);
         if (COUNT) my_seeds++;
-        if (rr > 0 && rr < (uint64_t) thres) {
-            const uint32_t slot = atomicAdd(&s_cnt[ph], 1u);
-            atomicAdd(&s_hits[ph], (uint32_t) rr);
-            s_rec[ph * cap_pp + slot] = k | (rr << 40);
-            s_q[ph * cap_pp + slot] = q;
-        }
+        if (rr > 0 && rr < (uint64_t) thres) ss_append(s_tot, s_rec, s_q, cap_pp, ph, q, k, rr);
     }
     }
     if (COUNT) { atomicAdd(&s_traffic[0], my_seeds); atomicAdd(&s_traffic[1], my_cnt[0]); atomicAdd(&s_traffic[2], my_cnt[1]); }
     __syncthreads();
     if (COUNT && tid < 3) atomicAdd(&counters->seed_traffic[tid], (unsigned long long) s_traffic[tid]);
     if (tid < np) {
-        const uint32_t c = s_cnt[tid];
+        const uint64_t tot = s_tot[tid];                                   // survivors | sum of rr << 32
+        const uint32_t c = (uint32_t) tot;
         if (c) {
             const uint64_t id = read * (uint64_t) P + (uint64_t) (phase_lo + (int) tid);
             s_base[tid] = atomicAdd(&gcnt[id], c);
-            atomicAdd(&ghits[id], s_hits[tid]);
+            atomicAdd(&ghits[id], (uint32_t) (tot >> 32));
         }
     }
     __syncthreads();
-    const uint32_t cpp_inv = 0xFFFFFFFFu / cap_pp;                         // e / cap_pp without a division (e < 2^16: exact after one fix-up)
-    for (uint32_t e = tid; e < np * cap_pp; e += 256) {
-        uint32_t ph = __umulhi(e, cpp_inv), sl = e - ph * cap_pp;
-        if (sl >= cap_pp) { ++ph; sl -= cap_pp; }
-        if (sl < s_cnt[ph]) {
-            const uint64_t o = (read * (uint64_t) P + (uint64_t) (phase_lo + (int) ph)) * cap_q + s_base[ph] + sl;
-            rec[o] = s_rec[e];
-            recq[o] = s_q[e];
+    // Write-out by phase: a wavefront takes whole lists, so a list's length, its place in LDS and its place in the global
+    // list are the same for all 64 lanes (scalar registers), and a lane copies slots lane, lane + 64, ... with nothing per
+    // entry but two LDS reads and two stores.  Lane ph keeps count and global base of phase ph (np <= 64).  With fewer than
+    // four lists (np = 1: up to SS_ITEMS entries in one) the four wavefronts share every list instead.
+    const uint32_t lane = tid & 63u, wave = (uint32_t) __builtin_amdgcn_readfirstlane((int) (tid >> 6));
+    const uint32_t cnt_l = lane < np ? (uint32_t) s_tot[lane] : 0u;
+    const uint32_t base_l = lane < np && cnt_l ? s_base[lane] : 0u;
+    const bool share = np < 4u;
+    for (uint32_t ph = share ? 0u : wave; ph < np; ph += share ? 1u : 4u) {
+        const uint32_t c = (uint32_t) __builtin_amdgcn_readlane((int) cnt_l, (int) ph);
+        const uint64_t o = (read * (uint64_t) P + (uint64_t) (phase_lo + (int) ph)) * cap_q + (uint32_t) __builtin_amdgcn_readlane((int) base_l, (int) ph);
+        uint64_t *rec_o = rec + o;
+        uint32_t *recq_o = recq + o;
+        const uint32_t lb = ph * cap_pp;
+        for (uint32_t sl = share ? tid : lane; sl < c; sl += share ? 256u : 64u) {
+            rec_o[sl] = s_rec[lb + sl];
+            recq_o[sl] = s_q[lb + sl];
         }
     }
 }
@@ -426,8 +452,12 @@ int lrm_launch_seed(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint
         uint32_t grid;
         if (lrm_grid_1d(n * bpr, "seed_search", &grid)) return -1;
         lrm_time_begin(ws, LRM_K_SEED_SEARCH, stream);
-        auto sk = ws->counting ? seed_search_kernel<2048, true>
-                               : ss_items == 1024u ? seed_search_kernel<1024, false> : ss_items == 4096u ? seed_search_kernel<4096, false> : seed_search_kernel<2048, false>;
+        // (the tag's bits as sd_key_of counts them: role 2, outside bases 6, residue = core bits - line bits)
+        const LrmIndexView &v = idx->view;
+        const bool sd48 = v.sd && v.sd_f == 4 && v.sd_slot == 8 && 8 + 2 * (v.sd_len - 3) - v.sd_bits <= 32;
+        auto sk = ws->counting ? seed_search_kernel<2048, true, false>
+                  : sd48 ? (ss_items == 1024u ? seed_search_kernel<1024, false, true> : ss_items == 4096u ? seed_search_kernel<4096, false, true> : seed_search_kernel<2048, false, true>)
+                         : (ss_items == 1024u ? seed_search_kernel<1024, false, false> : ss_items == 4096u ? seed_search_kernel<4096, false, false> : seed_search_kernel<2048, false, false>);
         if (ws->counting) bpr = (uint32_t) (((uint64_t) np * cap_q + 2047) / 2048);
         if (ws->counting) grid = (uint32_t) (n * bpr);
         // (mt.ss_lds_pad: extra dynamic LDS per workgroup, i.e. fewer resident workgroups per CU -- see DESIGN 5)
