@@ -41,6 +41,7 @@
 #include "lrm_hip_util.h"
 #include "extend_stage.h"
 #include "gact_bs_circuit.h"    // BS_K, the difference circuit, the walk's bookkeeping
+#include "base_words.h"         // ops4: four CIGAR bytes per permute
 
 #define BS_H (BS_K / 2)
 #define LRM_BS_MAX_WAVES 2048ull  // 2 per SIMD on 256 CUs
@@ -504,8 +505,13 @@ __global__ __launch_bounds__(64) void gact_bs_kernel(const uint64_t *__restrict_
     }
 }
 
-// codes -> CIGAR bytes ('=' 'X' 'I' 'D', one per alignment column): one thread per 16 columns (one 16-byte store
-// when the row is 16-byte aligned, four 4-byte stores otherwise)
+// codes -> CIGAR bytes ('=' 'X' 'I' 'D', one per alignment column): one thread per code word -- 32 columns, the word
+// loaded once -- in two halves of 16 columns (one 16-byte store each when the row is 16-byte aligned, four 4-byte stores
+// otherwise, single bytes at the row's end).  Four columns per permute (ops4, base_words.h) and no compare per column: the
+// one dword that holds the end of the coded columns, and the dwords behind it, take their 'I's by a byte mask.
+// (One thread per 16 columns -- five workgroups per read instead of three on the bench workload, every code word loaded
+// by two threads -- took 0.63 ms per Gbp against 0.50, with 85 vector instructions per wavefront as with 32: profiles/r10.)
+// bs_ops4: the per-column form that ops4 and ops4_tail replaced in the kernel
 __device__ __forceinline__ uint32_t bs_ops4(uint32_t c8, int o, int nc) {
     uint32_t w = 0;
 #pragma unroll
@@ -514,6 +520,25 @@ __device__ __forceinline__ uint32_t bs_ops4(uint32_t c8, int o, int nc) {
         w |= op << (8 * e);
     }
     return w;
+}
+// 16 columns from c32; left (> 0) columns and left_c coded columns of the row begin at out
+__device__ __forceinline__ void bs_expand16(uint32_t c32, int left, int left_c, uint8_t *out) {
+    uint32_t w[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) w[q] = ops4((c32 >> (8 * q)) & 0xffu);
+    if (left_c < 16) {                                           // the 'I' tail begins in these 16 columns or before them
+#pragma unroll
+        for (int q = 0; q < 4; ++q) w[q] = ops4_tail(w[q], bw_keep(left_c > 4 * q ? (uint32_t) (left_c - 4 * q) : 0u));
+    }
+    if (left >= 16 && (((uintptr_t) out) & 15u) == 0) {
+        *reinterpret_cast<uint4 *>(out) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (4 * q + 4 <= left) *reinterpret_cast<uint32_t *>(out + 4 * q) = w[q];
+            else for (int e = 0; 4 * q + e < left; ++e) out[4 * q + e] = (uint8_t) (w[q] >> (8 * e));
+        }
+    }
 }
 __global__ __launch_bounds__(256) void bs_expand_kernel(const uint64_t *__restrict__ codes, uint64_t cw,
                                                         const int32_t *__restrict__ n_codes,
@@ -526,23 +551,13 @@ __global__ __launch_bounds__(256) void bs_expand_kernel(const uint64_t *__restri
     if (r >= n_reads) return;
     if (meta_r[r] == 0 || (rflags && rflags[r])) return;         // fenced, or written by the byte kernel
     const int no = n_ops[r], nc = n_codes[r];
-    const int o = (int) ((blockIdx.x % blocks_per_read) * 256 + threadIdx.x) * 16;
+    const uint32_t cwi = (blockIdx.x % blocks_per_read) * 256 + threadIdx.x;      // this thread's code word
+    const int o = (int) cwi * 32;
     if (o >= no) return;
-    const uint32_t c32 = (uint32_t) (codes[r * cw + (uint64_t) (o >> 5)] >> ((o & 31) * 2));
-    uint32_t w[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) w[q] = bs_ops4((c32 >> (8 * q)) & 0xffu, o + 4 * q, nc);
+    const uint64_t c64 = codes[r * cw + cwi];
     uint8_t *out = store + r * store_stride + o;
-    if (o + 16 <= no && (((uintptr_t) out) & 15u) == 0) {
-        *reinterpret_cast<uint4 *>(out) = make_uint4(w[0], w[1], w[2], w[3]);
-    } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int oq = o + 4 * q;
-            if (oq + 4 <= no) *reinterpret_cast<uint32_t *>(out + 4 * q) = w[q];
-            else for (int e = 0; oq + e < no; ++e) out[4 * q + e] = (uint8_t) (w[q] >> (8 * e));
-        }
-    }
+    bs_expand16((uint32_t) c64, no - o, nc - o, out);
+    if (o + 16 < no) bs_expand16((uint32_t) (c64 >> 32), no - o - 16, nc - o - 16, out + 16);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -584,7 +599,7 @@ int lrm_bs_launch(const LrmGactJobs &j, lrm_gact_params gp, const LrmBsScratch &
     hipLaunchKernelGGL(count ? gact_bs_kernel<true> : gact_bs_kernel<false>, dim3((uint32_t) blocks), dim3(64), 0, stream,
                        bs.qpl, bs.wpr, j.lens, j.meta, j.meta_r, j.cpl + BS_PADW, j.tlens, bs.rflags, j.n, gp.T, gp.O, gp.W,
                        bs.ckpt, bs.codes, bs.cw, bs.ncodes, j.n_ops, j.score, counters);
-    const uint32_t bpr = (uint32_t) ((bs.cw * 32 + 4095) / 4096);           // 256 threads x 16 columns per block
+    const uint32_t bpr = (uint32_t) ((bs.cw + 255) / 256);                  // 256 threads x one code word per block
     uint32_t grid;
     if (lrm_grid_1d(j.n * bpr, "expand", &grid)) return -1;
     hipLaunchKernelGGL(bs_expand_kernel, dim3(grid), dim3(256), 0, stream, bs.codes, bs.cw, bs.ncodes, j.n_ops, bs.rflags,

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include "lrm_hip_util.h"
 #include "extend_stage.h"
+#include "base_words.h"
 
 #define BS_PADW LRM_BS_PADW
 
@@ -34,6 +35,7 @@ __device__ __forceinline__ void bs_pack_group(const uint8_t *src, uint64_t len, 
 // high plane bits with multiplies (no ballots), and pairs of lanes assemble the 64-bit words.  (The first version
 // loaded one byte per lane and built the planes with 48 ballots per KiB: 0.72 ms per Gbp [r2].)
 #define BS_PACK_G 16
+// the per-byte test that not_acgt4 (base_words.h) replaced in the kernel below: ~(A | C | G | T matches) & 0x80808080
 __device__ __forceinline__ uint32_t bs_bytes_equal(uint32_t x, uint32_t c4) {    // 0x80 in every byte of x equal to c4's
     const uint32_t z = x ^ c4;
     return ~(((z & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | z | 0x7F7F7F7Fu);
@@ -69,24 +71,30 @@ __global__ __launch_bounds__(256) void bs_pack_reads_kernel(const char *__restri
         }
     }
     const uint32_t ws = sh >> 2, bs = sh & 3;                          // dword and byte part of the shift (wave-uniform)
-    uint32_t lo = 0, hi = 0, bad = 0;
+    uint32_t lo = 0, hi = 0, bad = 0, xs[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         uint32_t a_ = d[k], b_ = d[k + 1];
         if (ws == 1) { a_ = d[k + 1]; b_ = d[k + 2]; }
         else if (ws == 2) { a_ = d[k + 2]; b_ = d[k + 3]; }
         else if (ws == 3) { a_ = d[k + 3]; b_ = d[k + 4]; }
-        uint32_t x = __builtin_amdgcn_alignbyte(b_, a_, bs);           // bases p0 + 4k .. p0 + 4k + 3
-        const uint32_t pk = p0 + 4 * (uint32_t) k;
-        const uint32_t nv = len > pk ? (len - pk < 4 ? len - pk : 4) : 0;          // bases of this dword inside the read
-        const uint32_t keep = nv >= 4 ? 0xFFFFFFFFu : ((1u << (8 * nv)) - 1u);
-        x = (x & keep) | (0x41414141u & ~keep);                        // bases past the end pack as A, unflagged
-        const uint32_t code = ((x >> 1) ^ (x >> 2)) & 0x03030303u;
+        xs[k] = __builtin_amdgcn_alignbyte(b_, a_, bs);                // bases p0 + 4k .. p0 + 4k + 3
+    }
+    if (p0 + 16 > len) {                                               // only the lanes at and past the read's end
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t pk = p0 + 4 * (uint32_t) k;
+            const uint32_t keep = bw_keep(len > pk ? len - pk : 0u);   // bases of this dword inside the read
+            xs[k] = (xs[k] & keep) | (0x41414141u & ~keep);            // bases past the end pack as A, unflagged
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t x = xs[k];
+        const uint32_t code = codes4(x);
         lo |= ((((code & 0x01010101u) * 0x01020408u) >> 24) & 0xFu) << (4 * k);
         hi |= (((((code >> 1) & 0x01010101u) * 0x01020408u) >> 24) & 0xFu) << (4 * k);
-        const uint32_t ok = bs_bytes_equal(x, 0x41414141u) | bs_bytes_equal(x, 0x43434343u) |
-                            bs_bytes_equal(x, 0x47474747u) | bs_bytes_equal(x, 0x54545454u);
-        bad |= ~ok & 0x80808080u;
+        bad |= not_acgt4(x);                                           // by the codes already made, a permute and an xor
     }
     const uint32_t mine = lo | (hi << 16);
     const uint32_t other = (uint32_t) __shfl_xor((int) mine, 1);

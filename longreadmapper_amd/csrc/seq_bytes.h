@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "base_words.h"
 
 // alnmain.c:31-52: A/a -> T, C/c -> G, G/g -> C, T/t -> A, anything else -> N.  Branch-free on purpose: a `switch`
 // compiles to a cascade of divergent branches per byte (the first revcomp kernel spent 1.5 ms per Gbp in them).
@@ -21,13 +22,19 @@ __device__ __forceinline__ uint32_t bytes_equal(uint32_t x, uint32_t c4) {     /
     return (t >> 7) * 0xFFu;
 }
 
-__device__ __forceinline__ uint32_t revcomp4(uint32_t w) {       // 4 bases: reversed and complemented
+__device__ __forceinline__ uint32_t revcomp4_exact(uint32_t w) {       // 4 bytes: reversed, comp_base of each
     const uint32_t x = w & 0xDFDFDFDFu;
     const uint32_t a = bytes_equal(x, 0x41414141u), c = bytes_equal(x, 0x43434343u);
     const uint32_t g = bytes_equal(x, 0x47474747u), t = bytes_equal(x, 0x54545454u);
     const uint32_t o = (a & 0x54545454u) | (c & 0x47474747u) | (g & 0x43434343u) | (t & 0x41414141u) |
                        (~(a | c | g | t) & 0x4E4E4E4Eu);
     return __builtin_bswap32(o);
+}
+
+// 4 bases: reversed and complemented.  Four letters of ACGTacgt take the word form (base_words.h: a code per byte, then
+// two byte permutes -- the reversal and the table T, G, C, A); a word with any other byte takes revcomp4_exact.
+__device__ __forceinline__ uint32_t revcomp4(uint32_t w) {
+    return not_letter4(w) == 0 ? revcomp4_letters(w) : revcomp4_exact(w);
 }
 
 // 16 bases reversed and complemented; word(e), e = 0 .. 3: the four dwords in memory order (a callable, so that each
