@@ -259,15 +259,10 @@ def read_of(kmers, spacers=None):
 def phase0_hits(read, S, thres, cen, sa_rank):
     """The phase-0 hit stream of `read` from first principles: seed j contributes, when 0 < count < thres, the keys
     pos - j (mod 2^64) of its occurrences in the order of their suffix-array rows (sa_rank[pos]: row of the suffix at pos,
-    the inverse of a suffix array that check_sa has accepted)."""
-    keys = []
-    read = bytes(read)
-    for j in range(0, max(len(read) - S, 0), S + 1):
-        pos = cen.positions(read[j:j + S])
-        if 0 < len(pos) < thres:
-            for p in sorted(pos, key=lambda x: sa_rank[x]):
-                keys.append((p - j) & U64)
-    return keys
+    the inverse of a suffix array that check_sa has accepted).  Phase 0 of phase_cases.phase_hits (which builds on this
+    module, hence the import here)."""
+    from phase_cases import phase_hits
+    return phase_hits(read, 0, S, thres, cen, sa_rank)
 
 
 # ---------------------------------------------------------------------------------------------------------------
