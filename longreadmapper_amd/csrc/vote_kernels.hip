@@ -1,6 +1,7 @@
 // vote_kernels.hip -- K2 of PART 1: the LDS vote over the survivor lists seed_search leaves (seed_kernels.hip); staging and hit walk: vote_hits.h
 #include <hip/hip_runtime.h>
 #include "vote_hits.h"
+#include "vote_hash.h"              // bucket_hash, bucket_pass, sketch_counter
 
 // ----------------------------------------------------------------------------------------
 // K2 vote.
@@ -40,13 +41,6 @@
 
 // never a vote key: keys are SA - j (u64 wrap) with SA < 2^40 and j < 2^32, i.e. in [0, 2^40) or [2^64 - 2^32, 2^64)
 #define EMPTY_KEY 0x8000000000000000ull
-
-__device__ __forceinline__ uint32_t bucket_hash(uint64_t bucket) {
-    uint32_t x = (uint32_t) bucket ^ (uint32_t) (bucket >> 29);
-    x *= 0x9E3779B1u;
-    x ^= x >> 15;
-    return x * 0x85EBCA6Bu;
-}
 
 // One slot = {min key of the bucket, count, min order key}: the bucket is key >> 4 (histo.c:26-28) and the entry's
 // key is the minimum key added to it (histo.c:45-49), so the smallest key IS the slot's identity and its payload.
@@ -92,7 +86,7 @@ __device__ __forceinline__ bool vote_insert(const VoteTable &t, uint64_t key, ui
 
 __device__ __forceinline__ bool vote_admit(const VoteTable &t, uint64_t key, uint32_t order, uint32_t passes, uint32_t pass) {
     const uint32_t hash = bucket_hash(key >> 4);
-    if (passes == 1 || (hash >> 16) % passes == pass) return vote_insert(t, key, order, hash);
+    if (passes == 1 || bucket_pass(hash, passes) == pass) return vote_insert(t, key, order, hash);
     return true;
 }
 
@@ -466,7 +460,7 @@ __device__ __forceinline__ void fast_hits(const LrmIndexView &ix, const FastTabl
                 hw = hit_word(slot, key);
                 oinv = 0xFFFFFFFFu - order;
             } else {
-                const uint32_t c = (hash >> 5) & sk_mask;
+                const uint32_t c = sketch_counter(hash, sk_mask);
                 atomicAdd(&sketch[c >> 1], 1u << (16 * (c & 1)));          // < 2^16 hits per bucket: 16 per seed at most
             }
         }

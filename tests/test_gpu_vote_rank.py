@@ -236,7 +236,8 @@ def _cpu_side(name):
 _cache = {}
 
 
-def _vote(di, gpu, reads, exact):
+def _vote(di, gpu, reads, exact, with_best=False):
+    """-> the six words of every (read, phase), vote_redo_items; with_best: best[] of the same call between them"""
     import torch
     arr, lens = _rows(reads)
     di.set_map_options(vote_exact_only=exact)
@@ -245,7 +246,10 @@ def _vote(di, gpu, reads, exact):
         dev = torch.device("cuda", gpu)
         dm.seed(torch.from_numpy(arr).to(dev), torch.from_numpy(lens.astype(np.int32)).to(dev))
         torch.cuda.synchronize(dev)
-        return dm.debug_vote_results(len(reads)), dm.stats()["vote_redo_items"]
+        votes, redo = dm.debug_vote_results(len(reads)), dm.stats()["vote_redo_items"]
+        if with_best:
+            return votes, dm.best[:len(reads)].cpu().numpy().reshape(-1).view(mapper.ENTRY_DT), redo
+        return votes, redo
     finally:
         dm.close()
 
