@@ -12,6 +12,7 @@
 // Also read by plain C++ (lrm_split_segments for lrm_split_plan): nothing here needs the HIP runtime.
 #pragma once
 #include "lrm_internal.h"
+#include "rival_rule.h"
 
 #if defined(__HIPCC__)
 #define LRM_HD __host__ __device__
@@ -150,14 +151,21 @@ void lrm_anchor_scratch_free(lrm_workspace *ws);
 static inline uint64_t lrm_anchored_store_stride(uint32_t max_len) { return 2ull * max_len + max_len / 8 + 2; }
 // split reads (split_kernels.hip; docs/GACT_SPEC.md, "Split reads")
 int lrm_split_min_len(uint32_t m, uint32_t *out);          // 0 -> the default; -1 + message outside 50..2^20
-// the segments of read i from its length and clip counts, appended at out (room for two); returns how many.  THE rule:
-// the device kernels, lrm_split_plan and the host gather all go through it
-LRM_HD static inline uint32_t lrm_split_segments(uint32_t read, uint32_t n, uint32_t cl, uint32_t cr, uint32_t M, lrm_segment *out) {
-    uint32_t k = 0;
+// the two sides of a read of n bases from its clip counts: the left segment is R[0 .. left), the right one
+// R[right_start .. right_start + right); a side shorter than M (> 0) does not qualify and has length 0.  THE rule: the
+// device kernels, lrm_split_plan and the host gather all go through it
+struct LrmSplitSides { uint32_t left, right_start, right; };
+LRM_HD static inline LrmSplitSides lrm_split_sides(uint32_t n, uint32_t cl, uint32_t cr, uint32_t M) {
     if (cl > n) cl = n;                                    // (clip counts never exceed the read: keeps a bad input inside its row)
     if (cr > n) cr = n;
-    if (cl >= M) { out[k].read = read; out[k].start = 0; out[k].len = cl; out[k].flags = 0; ++k; }
-    if (cr >= M) { out[k].read = read; out[k].start = n - cr; out[k].len = cr; out[k].flags = LRM_SEG_RIGHT; ++k; }
+    return LrmSplitSides{cl >= M ? cl : 0u, n - cr, cr >= M ? cr : 0u};
+}
+// ... as the records of read i, appended at out (room for two); returns how many
+LRM_HD static inline uint32_t lrm_split_segments(uint32_t read, uint32_t n, uint32_t cl, uint32_t cr, uint32_t M, lrm_segment *out) {
+    const LrmSplitSides s = lrm_split_sides(n, cl, cr, M);
+    uint32_t k = 0;
+    if (s.left) out[k++] = lrm_segment{read, 0u, s.left, 0u};
+    if (s.right) out[k++] = lrm_segment{read, s.right_start, s.right, LRM_SEG_RIGHT};
     return k;
 }
 struct LrmSplitArgs {                                      // lrm_split_batch_dev after its checks
@@ -188,6 +196,13 @@ LRM_HD static inline uint32_t lrm_sec_flags(bool has_p, int32_t meta_r_p, const 
     }
     if (meta_r != 0 && score != -1 && !flags && (!anchored || (anchor_flags & LRM_ANCHOR_ANCHORED))) flags |= LRM_SEC_ALIGNED;
     return flags;
+}
+// H and pct (rival_rule.h) from the caller's min_hits / ratio_pct; -1 + message for a word outside its range
+static inline int lrm_rival_options(uint32_t min_hits, uint32_t ratio_pct, uint32_t *H, uint32_t *pct) {
+    *H = rv_min_hits(min_hits); *pct = rv_ratio_pct(ratio_pct);
+    if (*H && *pct) return 0;
+    lrm_set_error("secondary: min_hits %u outside [1, 65535] or ratio_pct %u outside [1, 100]", min_hits, ratio_pct);
+    return -1;
 }
 // the rival entries of the batch whose survivor lists are in ws, right behind lrm_launch_mapq
 int lrm_launch_rival(lrm_index *idx, lrm_workspace *ws, const uint32_t *d_lens, uint64_t n, uint32_t seed_len, const lrm_entry *d_best,

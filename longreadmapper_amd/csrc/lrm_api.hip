@@ -480,8 +480,8 @@ extern "C" int lrm_split_batch_dev(lrm_index *idx, lrm_workspace *ws_seg, const 
 extern "C" int lrm_rival_host(const uint64_t *keys, uint64_t n_keys, const lrm_entry *best, uint32_t len, uint32_t min_hits,
                               uint32_t ratio_pct, uint32_t slots, lrm_entry *out) {
     if (!out || !best || (n_keys && !keys)) { lrm_set_error("null argument"); return -1; }
-    const uint32_t H = rv_min_hits(min_hits), pct = rv_ratio_pct(ratio_pct);
-    if (!H || !pct) { lrm_set_error("secondary: min_hits %u outside [1, 65535] or ratio_pct %u outside [1, 100]", min_hits, ratio_pct); return -1; }
+    uint32_t H, pct;
+    if (lrm_rival_options(min_hits, ratio_pct, &H, &pct)) return -1;
     if (slots == 0) slots = LRM_MAPQ_SLOTS;
     out->key = out->val = out->bucket = 0;
     if (best->val == 0) return 0;
@@ -520,8 +520,8 @@ extern "C" int lrm_secondary_plan(const lrm_mapq *mapq, uint64_t n, uint32_t min
                                   uint64_t cap, uint64_t *n_sec) {
     if (!n_sec || (n && !mapq) || (cap && !table)) { lrm_set_error("null argument"); return -1; }
     if (n > 0xFFFFFFFFull) { lrm_set_error("batch too large"); return -1; }
-    const uint32_t H = rv_min_hits(min_hits), pct = rv_ratio_pct(ratio_pct);
-    if (!H || !pct) { lrm_set_error("secondary: min_hits %u outside [1, 65535] or ratio_pct %u outside [1, 100]", min_hits, ratio_pct); return -1; }
+    uint32_t H, pct;
+    if (lrm_rival_options(min_hits, ratio_pct, &H, &pct)) return -1;
     uint64_t total = 0;
     for (uint64_t i = 0; i < n; ++i) total += rv_candidate(mapq[i].n1, mapq[i].n2, mapq[i].flags, H, pct) != 0;
     *n_sec = total;

@@ -243,6 +243,18 @@ extern "C" int lrm_map_batch_submit(lrm_index *idx, char *reads_buf, uint64_t st
 static inline char split_comp(char ch) {
     switch (ch & 0xDF) { case 'A': return 'T'; case 'C': return 'G'; case 'G': return 'C'; case 'T': return 'A'; default: return 'N'; }
 }
+// row = R[start .. start + len) of a read of len_read bases, zeros behind it up to pad_to; mirrored: src holds R's reverse
+// complement
+static void host_gather_row(char *dst, const char *src, uint32_t start, uint32_t len, uint32_t len_read, bool mirrored, uint64_t pad_to) {
+    if (mirrored) for (uint32_t k = 0; k < len; ++k) dst[k] = split_comp(src[len_read - 1 - (start + k)]);
+    else memcpy(dst, src + start, len);
+    memset(dst + len, 0, (size_t) (pad_to - len));
+}
+static int host_row_stride(const char *stage, const char *row, uint64_t row_stride, uint32_t longest) {
+    if (!(row_stride & 15u) && row_stride > longest) return 0;
+    lrm_set_error("%s: row_stride %llu must be a multiple of 16 above the longest %s (%u)", stage, (unsigned long long) row_stride, row, longest);
+    return -1;
+}
 static int split_batch_impl(lrm_index *idx, const char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
                             const lrm_cigar *cig, const lrm_seq_meta *meta, const int *meta_r, lrm_params p, lrm_gact_params gp,
                             const lrm_map_options *opt, lrm_split_out *out) {
@@ -265,22 +277,14 @@ static int split_batch_impl(lrm_index *idx, const char *reads_buf, uint64_t stri
     if (n_seg == 0) return 0;
     uint32_t longest = 0;
     for (uint64_t s = 0; s < n_seg; ++s) longest = out->seg[s].len > longest ? out->seg[s].len : longest;
-    if ((out->row_stride & 15u) || out->row_stride <= longest) {
-        lrm_set_error("split: row_stride %llu must be a multiple of 16 above the longest segment (%u)", (unsigned long long) out->row_stride, longest);
-        return -1;
-    }
+    if (host_row_stride("split", "segment", out->row_stride, longest)) return -1;
     // gather on the host: R is the caller's row, or its reverse complement when the caller kept its reads as they were
     const int nt = lrm_host_threads();
 #pragma omp parallel for schedule(dynamic, 64) num_threads(nt)
     for (uint64_t s = 0; s < n_seg; ++s) {
         const lrm_segment &g = out->seg[s];
-        const char *src = reads_buf + (uint64_t) g.read * stride;
-        char *dst = out->rows + s * out->row_stride;
-        const uint32_t len_r = lens[g.read];
-        if (mt.keep_reads && meta_r[g.read] != 0 && meta[g.read].strand == 1)
-            for (uint32_t k = 0; k < g.len; ++k) dst[k] = split_comp(src[len_r - 1 - (g.start + k)]);
-        else memcpy(dst, src + g.start, g.len);
-        memset(dst + g.len, 0, (size_t) (((uint64_t) g.len + 16) & ~15ull) - g.len);
+        host_gather_row(out->rows + s * out->row_stride, reads_buf + (uint64_t) g.read * stride, g.start, g.len, lens[g.read],
+                        mt.keep_reads && meta_r[g.read] != 0 && meta[g.read].strand == 1, ((uint64_t) g.len + 16) & ~15ull);
         out->lens[s] = g.len;
     }
     // the segment batch through the pipeline, in the caller's result layout
@@ -353,10 +357,7 @@ static int secondary_batch_impl(lrm_index *idx, const char *reads_buf, uint64_t 
     if (k == 0) return 0;
     uint32_t longest = 0;
     for (uint64_t s = 0; s < k; ++s) longest = lens[out->table[s].read] > longest ? lens[out->table[s].read] : longest;
-    if ((out->row_stride & 15u) || out->row_stride <= longest) {
-        lrm_set_error("secondary: row_stride %llu must be a multiple of 16 above the longest candidate (%u)", (unsigned long long) out->row_stride, longest);
-        return -1;
-    }
+    if (host_row_stride("secondary", "candidate", out->row_stride, longest)) return -1;
     const uint64_t need = anchored ? lrm_anchored_store_stride(longest) : 2ull * longest;
     if ((out->store_stride & 15u) || out->store_stride < need) {
         lrm_set_error("secondary: store_stride %llu must be a multiple of 16 of at least %llu", (unsigned long long) out->store_stride, (unsigned long long) need);
@@ -367,12 +368,8 @@ static int secondary_batch_impl(lrm_index *idx, const char *reads_buf, uint64_t 
 #pragma omp parallel for schedule(dynamic, 64) num_threads(nt)
     for (uint64_t s = 0; s < k; ++s) {
         const uint32_t read = out->table[s].read, len = lens[read];
-        const char *src = reads_buf + (uint64_t) read * stride;
-        char *dst = out->rows + s * out->row_stride;
-        if (!mt.keep_reads && meta && meta_r[read] != 0 && meta[read].strand == 1)
-            for (uint32_t c = 0; c < len; ++c) dst[c] = split_comp(src[len - 1 - c]);
-        else memcpy(dst, src, len);
-        memset(dst + len, 0, (size_t) (out->row_stride - len));
+        host_gather_row(out->rows + s * out->row_stride, reads_buf + (uint64_t) read * stride, 0, len, len,
+                        !mt.keep_reads && meta && meta_r[read] != 0 && meta[read].strand == 1, out->row_stride);
         out->lens[s] = len;
     }
     // the device pass

@@ -267,7 +267,7 @@ struct lrm_workspace {
     uint32_t *d_err;
     LrmBsScratch bs;         // bit-sliced GACT over up to n_max reads of up to max_len bases (LRM_WS_EXTEND)
     struct LrmAnchorScratch *an;   // anchored mode (anchor_kernels.hip): allocated by its first call on this workspace
-    struct LrmSplitScratch *sp;    // split stage (split_kernels.hip): allocated by its first call with this workspace as ws_seg
+    struct LrmCompactScratch *sp;  // split stage (split_kernels.hip, compact_rows.h): allocated by its first call with this workspace as ws_seg
     uint8_t *d_mq_phase;           // mapping quality (mapq_kernels.hip): deciding phase per read, allocated by the first mapq call
     struct LrmSecScratch *sec;     // secondary alignments (secondary_kernels.hip): allocated by the first lrm_secondary_batch_dev
 };

@@ -3,10 +3,8 @@
 //
 //   rival_locus     one workgroup per read: the fullest (histogram, bucket) pair of the rival vote, its fullest sub-bucket,
 //                   the smallest hit of that -- an lrm_entry the extension can start from (zeros: not a candidate)
-//   sec_count       per workgroup of 256 reads: how many candidates, and the longest
-//   sec_scan        ONE workgroup: exclusive scan of those counts in place, the total and the longest candidate
-//   (host)          the 8 bytes {total, longest} cross to pinned memory; the call sleeps on an event until they are there
-//   sec_mark        one lane per read: its lrm_secondary record, its length and its rival entry at its place in the order
+//   compact_count / compact_scan / (host) / compact_mark<SecRule>   the candidate table in its order (compact_rows.h):
+//                   a candidate's lrm_secondary record, its length and its rival entry
 //   sec_gather      the read AS SEQUENCED into row s of the candidate batch (the primary extension reverse-complemented
 //                   reverse-strand reads in place: those are read mirrored and complemented)
 //   (extension)     lrm_launch_extend / lrm_launch_extend_anchored, unchanged, over the rows with best = the rival entries
@@ -22,7 +20,7 @@
 // The walk is the shared one of the vote kernels (vote_hits.h: stage_repeats_wave, for_each_hit), a wavefront per chunk of 64
 // survivors; mapq_vote_kernel keeps its own copy for the 1.8 % it measured (mapq_kernels.hip) and is not touched.
 //
-// Order of the table: exclusive prefix sums without atomics, as in split_kernels.hip (compact_rows.h is the shared part).
+// Order of the table: exclusive prefix sums without atomics, as in split_kernels.hip (compact_rows.h: the one copy of it).
 #include <hip/hip_runtime.h>
 #include "vote_hits.h"
 #include "rival_rule.h"
@@ -33,10 +31,7 @@
 
 struct LrmSecScratch {
     lrm_entry *rival; uint64_t rival_cap;     // the rival entry of every read of the batch
-    uint2 *blk; uint64_t blk_cap;             // per workgroup {candidates, longest}; after sec_scan .x = candidates before it
-    uint32_t *d_tot;                          // {total, longest}
-    uint32_t *h_tot;                          // ... in pinned host memory
-    hipEvent_t ev;
+    LrmCompactScratch c;                      // the candidate table's order
 };
 
 // every hit SA[row] - j of the phases 0 .. d of one read, chunks of 64 survivors dealt round-robin to the four wavefronts:
@@ -161,63 +156,26 @@ void rival_locus_kernel(LrmIndexView ix, const uint64_t *__restrict__ rec, const
 static_assert(RV_SUB_BUCKETS <= LRM_MAPQ_SLOTS, "the sub-buckets live in the pair table's memory");
 
 // ---- the candidate table -----------------------------------------------------------------------------------------------------
-// is this lane's read a candidate (false beyond the batch)
-__device__ __forceinline__ bool sec_is_candidate(const lrm_mapq *__restrict__ mapq, uint64_t n, uint64_t r, uint32_t H, uint32_t pct) {
-    if (r >= n) return false;
-    const uint4 q = *reinterpret_cast<const uint4 *>(mapq + r);
-    return rv_candidate(q.x, q.y, (q.w >> 16) & 0xFFu, H, pct) != 0;
-}
-
-__global__ __launch_bounds__(SP_BLOCK) void sec_count_kernel(const lrm_mapq *__restrict__ mapq, const uint32_t *__restrict__ lens,
-                                                             uint64_t n, uint32_t H, uint32_t pct, uint2 *__restrict__ blk) {
-    __shared__ uint32_t s_sum[SP_BLOCK / 64], s_max[SP_BLOCK / 64];
-    const uint64_t r = (uint64_t) blockIdx.x * SP_BLOCK + threadIdx.x;
-    const uint32_t k = sec_is_candidate(mapq, n, r, H, pct) ? 1u : 0u;
-    const uint32_t incl = wave_incl_scan(k);
-    const uint32_t wmax = (uint32_t) wave_max_u64(k ? lens[r] : 0u);
-    uint32_t before, all, lmax;
-    sp_block_totals(incl, wmax, s_sum, s_max, &before, &all, &lmax);
-    if (threadIdx.x == 0) blk[blockIdx.x] = make_uint2(all, lmax);
-}
-
-// one workgroup walks the workgroup totals in tiles of 256 with a carried sum
-__global__ __launch_bounds__(SP_BLOCK) void sec_scan_kernel(uint2 *__restrict__ blk, uint32_t n_blk, uint32_t *__restrict__ tot) {
-    __shared__ uint32_t s_sum[SP_BLOCK / 64], s_max[SP_BLOCK / 64];
-    uint32_t carry = 0, longest = 0;
-    for (uint32_t base = 0; base < n_blk; base += SP_BLOCK) {
-        const uint32_t i = base + threadIdx.x;
-        const uint2 v = i < n_blk ? blk[i] : make_uint2(0, 0);
-        const uint32_t incl = wave_incl_scan(v.x);
-        const uint32_t wmax = (uint32_t) wave_max_u64(v.y);
-        uint32_t before, all, lmax;
-        __syncthreads();                                           // the totals of the tile before have been read
-        sp_block_totals(incl, wmax, s_sum, s_max, &before, &all, &lmax);
-        if (i < n_blk) blk[i].x = carry + before + incl - v.x;
-        carry += all;
-        longest = max(longest, lmax);
+// the stage's rule: a candidate read is one row, as long as the read
+struct SecRule {
+    const lrm_mapq *__restrict__ mapq; const uint32_t *__restrict__ lens; const lrm_entry *__restrict__ rival; uint32_t H, pct;
+    lrm_secondary *__restrict__ table; uint32_t *__restrict__ sec_lens; lrm_entry *__restrict__ sec_rival;
+    struct Item {};                                                           // (the record is made of r alone)
+    __device__ uint32_t items(uint64_t n, uint64_t r, Item &, uint32_t &longest) const {
+        if (r >= n) return 0;
+        const uint4 q = *reinterpret_cast<const uint4 *>(mapq + r);
+        if (!rv_candidate(q.x, q.y, (q.w >> 16) & 0xFFu, H, pct)) return 0;
+        longest = lens[r];
+        return 1;
     }
-    if (threadIdx.x == 0) { tot[0] = carry; tot[1] = longest; }
-}
-
-__global__ __launch_bounds__(SP_BLOCK) void sec_mark_kernel(const lrm_mapq *__restrict__ mapq, const uint32_t *__restrict__ lens,
-                                                            const lrm_entry *__restrict__ rival, uint64_t n, uint32_t H, uint32_t pct,
-                                                            const uint2 *__restrict__ blk, lrm_secondary *__restrict__ table,
-                                                            uint32_t *__restrict__ sec_lens, lrm_entry *__restrict__ sec_rival,
-                                                            uint64_t cap) {
-    __shared__ uint32_t s_sum[SP_BLOCK / 64], s_max[SP_BLOCK / 64];
-    const uint64_t r = (uint64_t) blockIdx.x * SP_BLOCK + threadIdx.x;
-    const uint32_t k = sec_is_candidate(mapq, n, r, H, pct) ? 1u : 0u;
-    const uint32_t incl = wave_incl_scan(k);
-    uint32_t before, all, lmax;
-    sp_block_totals(incl, 0, s_sum, s_max, &before, &all, &lmax);
-    const uint64_t at = (uint64_t) blk[blockIdx.x].x + before + incl - k;
-    if (k && at < cap) {
+    __device__ void write(uint64_t r, const Item &, uint32_t, uint64_t at, uint64_t cap) const {
+        if (at >= cap) return;
         const lrm_entry e = rival[r];
         *reinterpret_cast<uint4 *>(table + at) = make_uint4((uint32_t) r, (uint32_t) e.val, 0u, 0u);
         sec_lens[at] = lens[r];
         rv_store_entry(sec_rival + at, e.key, e.val, e.bucket);
     }
-}
+};
 
 // grid (candidates, chunks of SP_CHUNK row bytes); every lane one aligned 16-byte store, zeros from the read's end to the
 // end of the row
@@ -236,12 +194,8 @@ __global__ __launch_bounds__(256) void sec_gather_kernel(const char *__restrict_
         const uint32_t cnt = len - d < 16 ? (uint32_t) (len - d) : 16u;
         const char *src = reads + (uint64_t) read * stride;
         const bool mirrored = meta && meta_r[read] != 0 && meta[read].strand == 1;     // the primary extension turned it round
-        if (!mirrored) {
-            uint64_t o0, o1;
-            sp_load16(src + d, cnt, o0, o1);
-            if (cnt < 16) sp_keep_bytes(cnt, o0, o1);
-            o = make_uint4((uint32_t) o0, (uint32_t) (o0 >> 32), (uint32_t) o1, (uint32_t) (o1 >> 32));
-        } else if (cnt == 16) {                                      // row[d + k] = comp(src[len - 1 - d - k]): 16 bytes mirrored
+        if (!mirrored) o = sp_row16(src + d, cnt);
+        else if (cnt == 16) {                                      // row[d + k] = comp(src[len - 1 - d - k]): 16 bytes mirrored
             uint64_t o0, o1;
             sp_load16(src + (len - d - 16), 16u, o0, o1);
             const uint32_t w[4] = {(uint32_t) o0, (uint32_t) (o0 >> 32), (uint32_t) o1, (uint32_t) (o1 >> 32)};
@@ -274,41 +228,34 @@ __global__ __launch_bounds__(256) void sec_flag_kernel(lrm_secondary *__restrict
 void lrm_sec_scratch_free(lrm_workspace *ws) {
     LrmSecScratch *s = ws ? ws->sec : nullptr;
     if (!s) return;
-    lrm_dev_free({s->rival, s->blk, s->d_tot});
-    if (s->h_tot) (void) hipHostFree(s->h_tot);
-    if (s->ev) (void) hipEventDestroy(s->ev);
+    lrm_dev_free({s->rival});
+    lrm_compact_scratch_free(&s->c);
     free(s);
     ws->sec = nullptr;
 }
 
-// the stage's own scratch: a rival entry per read of the workspace, 8 bytes per 256 reads, the total on the device and in
-// pinned memory
+// the stage's own scratch, sized once from the workspace: a rival entry per read, the order's 8 bytes per 256 reads
+// (what a failed call did allocate stays, booked, for the next call and for lrm_sec_scratch_free)
 static int sec_scratch(lrm_workspace *ws) {
-    if (ws->sec) return 0;
-    LrmSecScratch *s = (LrmSecScratch *) calloc(1, sizeof(LrmSecScratch));
-    if (!s) { lrm_set_error("out of memory"); return -1; }
-    ws->sec = s;
-    const uint64_t n_blk = (ws->n_max + SP_BLOCK - 1) / SP_BLOCK;
-    const uint64_t bytes = ws->n_max * sizeof(lrm_entry) + n_blk * sizeof(uint2) + 8;
-    if (hipMalloc((void **) &s->rival, ws->n_max * sizeof(lrm_entry)) != hipSuccess ||
-        hipMalloc((void **) &s->blk, n_blk * sizeof(uint2)) != hipSuccess || hipMalloc((void **) &s->d_tot, 8) != hipSuccess ||
-        hipHostMalloc((void **) &s->h_tot, 64, hipHostMallocDefault) != hipSuccess ||
-        hipEventCreateWithFlags(&s->ev, hipEventDisableTiming) != hipSuccess) {
+    if (!ws->sec && !(ws->sec = (LrmSecScratch *) calloc(1, sizeof(LrmSecScratch)))) { lrm_set_error("out of memory"); return -1; }
+    LrmSecScratch *s = ws->sec;
+    if (lrm_compact_scratch(ws, &s->c, (ws->n_max + SP_BLOCK - 1) / SP_BLOCK, "secondary")) return -1;
+    if (s->rival) return 0;
+    if (hipMalloc((void **) &s->rival, ws->n_max * sizeof(lrm_entry)) != hipSuccess) {
         (void) hipGetLastError();
-        lrm_sec_scratch_free(ws);
-        lrm_set_error("allocation of %llu bytes of secondary-stage scratch failed", (unsigned long long) bytes);
+        lrm_set_error("hipMalloc of %llu bytes of secondary-stage scratch failed", (unsigned long long) (ws->n_max * sizeof(lrm_entry)));
         return -1;
     }
-    s->rival_cap = ws->n_max; s->blk_cap = n_blk;
-    ws->bytes += bytes;
+    s->rival_cap = ws->n_max;
+    ws->bytes += ws->n_max * sizeof(lrm_entry);
     return 0;
 }
 
 int lrm_launch_rival(lrm_index *idx, lrm_workspace *ws, const uint32_t *d_lens, uint64_t n, uint32_t seed_len, const lrm_entry *d_best,
                      const lrm_mapq *d_mapq, uint32_t min_hits, uint32_t ratio_pct, lrm_entry *d_rival, void *stream_) {
     hipStream_t stream = (hipStream_t) stream_;
-    const uint32_t H = rv_min_hits(min_hits), pct = rv_ratio_pct(ratio_pct);
-    if (!H || !pct) { lrm_set_error("secondary: min_hits %u outside [1, 65535] or ratio_pct %u outside [1, 100]", min_hits, ratio_pct); return -1; }
+    uint32_t H, pct;
+    if (lrm_rival_options(min_hits, ratio_pct, &H, &pct)) return -1;
     if (n == 0) return 0;
     if (!ws->d_mq_phase || !ws->d_rec || seed_len != ws->seed_len || n > ws->n_max) {
         lrm_set_error("rival locus: the workspace did not run the seed stage of this batch with the phase output");
@@ -330,49 +277,25 @@ int lrm_launch_secondary(lrm_index *idx, lrm_workspace *ws, const LrmSecArgs &a,
                          void *stream_) {
     hipStream_t stream = (hipStream_t) stream_;
     const uint64_t n = a.n;
-    const uint32_t H = rv_min_hits(a.min_hits), pct = rv_ratio_pct(a.ratio_pct);
+    uint32_t H, pct;
     if (n > ws->n_max) { lrm_set_error("secondary: %llu reads, the workspace holds %llu", (unsigned long long) n, (unsigned long long) ws->n_max); return -1; }
-    if (sec_scratch(ws)) return -1;
+    if (lrm_rival_options(a.min_hits, a.ratio_pct, &H, &pct) || sec_scratch(ws)) return -1;
     LrmSecScratch &s = *ws->sec;
     if (int rc = lrm_launch_rival(idx, ws, a.lens, n, a.seed_len, a.best, a.mapq, a.min_hits, a.ratio_pct, s.rival, stream_)) return rc;
     const uint32_t n_blk = (uint32_t) ((n + SP_BLOCK - 1) / SP_BLOCK);
 
-    // count, then the one wait of the stage
-    lrm_time_begin(ws, LRM_K_REVCOMP, stream);
-    hipLaunchKernelGGL(sec_count_kernel, dim3(n_blk), dim3(SP_BLOCK), 0, stream, a.mapq, a.lens, n, H, pct, s.blk);
-    hipLaunchKernelGGL(sec_scan_kernel, dim3(1), dim3(SP_BLOCK), 0, stream, s.blk, n_blk, s.d_tot);
-    lrm_time_end(ws, stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(s.h_tot, s.d_tot, 8, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipEventRecord(s.ev, stream));
-    if (lrm_wait_event(s.ev)) return -1;
-    const uint64_t n_sec = s.h_tot[0];
-    const uint32_t longest = s.h_tot[1];
+    const SecRule rule = {a.mapq, a.lens, s.rival, H, pct, out.table, out.lens, out.rival};
+    uint64_t n_sec;
+    uint32_t longest;
+    if (lrm_compact_count(ws, s.c, rule, n, n_blk, stream, &n_sec, &longest)) return -1;
     *n_sec_out = n_sec;
-    if (n_sec > out.cap) {
-        lrm_set_error("%llu secondary candidates, room for %llu", (unsigned long long) n_sec, (unsigned long long) out.cap);
-        return -3;
-    }
-    if (n_sec == 0) return 0;
-    if (out.row_stride <= longest) {
-        lrm_set_error("secondary: row_stride %llu <= longest candidate %u", (unsigned long long) out.row_stride, longest);
-        return -1;
-    }
-    const uint64_t need = a.anchored ? lrm_anchored_store_stride(longest) : 2ull * longest;
-    if (out.store_stride < need) {
-        lrm_set_error("secondary: store_stride %llu < %llu for the longest candidate", (unsigned long long) out.store_stride,
-                      (unsigned long long) need);
-        return -1;
-    }
-    if (longest > ws->max_len) { lrm_set_error("secondary: the workspace holds reads of up to %u bases, the longest candidate has %u", ws->max_len, longest); return -1; }
-    const uint64_t chunks = (out.row_stride + SP_CHUNK - 1) / SP_CHUNK;
-    uint32_t gx;
-    if (lrm_grid_1d(n_sec, "secondary gather", &gx)) return -1;
-    if (chunks > 65535u) { lrm_set_error("secondary: rows of %llu bytes too long", (unsigned long long) out.row_stride); return -1; }
+    dim3 grid;                                                       // (chunks over the whole row: the gather fills it with zeros to its end)
+    const int room = lrm_compact_room(ws, LrmCompactNouns{"secondary", "secondary candidates", "candidate"}, n_sec, longest, out.cap, out.row_stride,
+                                      out.store_stride, a.anchored ? lrm_anchored_store_stride(longest) : 2ull * longest, out.row_stride, &grid);
+    if (room || n_sec == 0) return room;
     lrm_time_begin(ws, LRM_K_REVCOMP, stream);
-    hipLaunchKernelGGL(sec_mark_kernel, dim3(n_blk), dim3(SP_BLOCK), 0, stream, a.mapq, a.lens, (const lrm_entry *) s.rival, n, H, pct,
-                       (const uint2 *) s.blk, out.table, out.lens, out.rival, out.cap);
-    hipLaunchKernelGGL(sec_gather_kernel, dim3(gx, (uint32_t) chunks), dim3(256), 0, stream, a.reads, a.stride,
+    hipLaunchKernelGGL(compact_mark_kernel<SecRule>, dim3(n_blk), dim3(SP_BLOCK), 0, stream, rule, n, (const uint2 *) s.c.blk, out.cap);
+    hipLaunchKernelGGL(sec_gather_kernel, grid, dim3(256), 0, stream, a.reads, a.stride,
                        (const lrm_secondary *) out.table, (const uint32_t *) out.lens, a.meta, a.meta_r, n_sec, out.rows, out.row_stride);
     lrm_time_end(ws, stream);
     HIPCHK(hipGetLastError());

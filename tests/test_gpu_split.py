@@ -247,6 +247,49 @@ def test_chunks_capacity_and_empty_batches(ref3, gpu):
     assert len(mapper.split_batch(di, r["reads"][:0], r["lens"][:0], {k2: v[:0] for k2, v in res.items() if k2 != "is_text"})["seg"]) == 0
 
 
+def test_scratch_grows_with_a_larger_second_batch(ref3, gpu):
+    """Two calls on one segment workspace: 200 reads (one workgroup of the count / mark kernels), then 600 (three; the
+    per-workgroup scratch of the first call is too small) with a two-segment read in lane 255 of the first workgroup."""
+    import torch
+    seqs, hi, di = ref3
+    di.set_map_options()
+    rng = np.random.default_rng(23)
+    n, M = 600, 50
+    lens = rng.integers(200, 301, n).astype(np.uint32)
+    reads = np.zeros((n, 304), dtype=np.uint8)
+    for i in range(n):
+        reads[i, :lens[i]] = _random(rng, int(lens[i]))
+    cl, cr = (rng.integers(0, 100, n) * (rng.random(n) < 0.6)).astype(np.uint32), (rng.integers(0, 100, n) * (rng.random(n) < 0.6)).astype(np.uint32)
+    cl[255], cr[255] = 70, 90
+    comp = bytes.maketrans(b"ACGT", b"TGCA")
+    dm = mapper.DeviceMapper(di, n, 300, device=gpu, clip=True, split=True, split_min_len=M)
+    try:
+        clip = np.zeros(n, dtype=mapper.CLIP_DT)
+        clip["left"], clip["right"] = cl, cr
+        dm.clip.copy_(torch.from_numpy(clip.view(np.int32).reshape(n, 2)).cuda())
+        d_reads, d_lens = torch.from_numpy(reads).cuda(), torch.from_numpy(lens.astype(np.int32)).cuda()
+        grown = []
+        for m in (200, 600):
+            k = dm.split(d_reads, d_lens, m)
+            torch.cuda.synchronize()
+            grown.append(int(lib.lrm_workspace_bytes(dm.ws_seg)))
+            sp = dm.split_results()
+            table = split_ref.plan(lens[:m], cl[:m], cr[:m], M)
+            assert k == len(table) > m // 2 and _table(sp["seg"]) == table
+            assert np.array_equal(sp["lens"], [t[2] for t in table])
+            rows, seg_lens = _rows_of(reads, lens, table)
+            for s, t in enumerate(table):                           # (a segment with a reverse-strand locus was turned round)
+                row = bytes(rows[s, :t[2]])
+                if sp["meta_r"][s] != 0 and sp["meta"]["strand"][s] == 1:
+                    row = row.translate(comp)[::-1]
+                assert bytes(sp["rows"][s, :t[2]]) == row, (m, s)
+        assert [t for t in table if t[0] == 255] == [(255, 0, 70, 0), (255, int(lens[255]) - 90, 90, 1)]
+        assert grown[1] - grown[0] == 8 * (3 - 1)                   # 8 bytes per workgroup of 256 reads
+    finally:
+        dm.close()
+    assert np.array_equal(d_reads.cpu().numpy(), reads)
+
+
 def test_off_means_off(ref3, chimeras, gpu):
     seqs, hi, di = ref3
     di.set_map_options()

@@ -58,6 +58,17 @@ def test_plan_edges():
     assert _rows(mapper.split_plan(lens, _clip(cl, cr), 1 << 20)) == []
 
 
+def test_plan_clamps_clip_counts_and_lets_sides_overlap():
+    """cl > n, cr > n (each becomes n, and qualifies or not as n does), cl + cr > n with both sides qualifying"""
+    M = 200
+    lens = np.array([300, 300, 300, 250, 150, 199, 200], dtype=np.uint32)
+    cl = np.array([301, 0, 250, 5000, 400, 0xFFFFFFFF, 200], dtype=np.uint32)
+    cr = np.array([0, 1000, 200, 6000, 400, 0, 0xFFFFFFFF], dtype=np.uint32)
+    got = _rows(mapper.split_plan(lens, _clip(cl, cr), M))
+    assert got == split_ref.plan(lens, cl, cr, M) == [(0, 0, 300, 0), (1, 0, 300, 1), (2, 0, 250, 0), (2, 100, 200, 1),
+                                                       (3, 0, 250, 0), (3, 0, 250, 1), (6, 0, 200, 0), (6, 0, 200, 1)]
+
+
 @pytest.mark.parametrize("ops", [b"==X=I=D=", b"SSS==X=", b"==X=SS", b"S==DD=I=SSSS", b"=", b"", b"S" * 300 + b"=" * 20 + b"S" * 1234])
 def test_clip_of_cigar_bytes_and_text(ops):
     want = split_ref.clip_of_ops(ops)
