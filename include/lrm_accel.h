@@ -745,7 +745,7 @@ int lrm_workspace_stats(lrm_workspace *ws, lrm_stats *out, void *stream);
  * bs_pack_reads, gact_bs (bit-sliced kernel + expansion).  The anchored mode adds its anchor scan to the
  * locus_resolve slot, its job builder to the revcomp slot, its end clipping and its stitch to the slot of the extension
  * kernel.  The split stage (lrm_split_batch_dev) books its own kernels -- compact_count / compact_scan / compact_mark,
- * split_gather, split_flag -- into the revcomp slot of ws_seg, next to the seed and extension kernels of the segment batch.
+ * compact_gather, split_flag -- into the revcomp slot of ws_seg, next to the seed and extension kernels of the segment batch.
  * lrm_workspace_timing synchronises the stream, ADDS the elapsed milliseconds and launch counts
  * of everything recorded since the last call into ms[LRM_N_KERNELS] / launches[LRM_N_KERNELS], and
  * resets the record. */

@@ -64,58 +64,36 @@ struct StageQueue {
     void close() { std::lock_guard<std::mutex> lk(m); closed = true; cv.notify_all(); }
 };
 
-// what lrm_split_batch writes for one batch: pageable buffers grown on demand, and the table that points at them
-struct SplitBufs {
-    lrm_split_out out;
-    std::vector<lrm_segment> seg;
+// what a second pass writes for one batch (lrm_split_batch, lrm_secondary_batch): pageable buffers grown on demand, and the
+// table that points at them.  The two out structs differ in their record (TABLE) and in the name of their entries (ENTRY)
+template <typename Out, typename Rec, Rec *Out::*TABLE, lrm_entry *Out::*ENTRY>
+struct PassBufs {
+    Out out;
+    std::vector<Rec> table;
     std::vector<char> rows;
     std::vector<uint8_t> store;
     std::vector<uint32_t> lens;
-    std::vector<lrm_entry> best;
+    std::vector<lrm_entry> entry;
     std::vector<lrm_cigar> cig;
     std::vector<int> score, meta_r;
     std::vector<lrm_seq_meta> meta;
     std::vector<lrm_anchor> anchor;
     std::vector<lrm_clip> clip;
-    SplitBufs() { memset(&out, 0, sizeof(out)); }
-    // an empty table for k == 0, else room for k segments with rows and op bytes at these strides
-    lrm_split_out *fit(uint64_t k, uint64_t row_stride, uint64_t store_stride) {
+    PassBufs() { memset(&out, 0, sizeof(out)); }
+    // an empty table for k == 0, else room for k rows with rows and op bytes at these strides
+    Out *fit(uint64_t k, uint64_t row_stride, uint64_t store_stride) {
         memset(&out, 0, sizeof(out));
         if (k == 0) return &out;
         auto room = [](auto &v, uint64_t n) { v.resize((size_t) n); return v.data(); };
         out.cap = k; out.row_stride = row_stride; out.store_stride = store_stride;
-        out.seg = room(seg, k); out.rows = room(rows, k * row_stride); out.store = room(store, k * store_stride);
-        out.lens = room(lens, k); out.best = room(best, k); out.cig = room(cig, k); out.score = room(score, k);
+        out.*TABLE = room(table, k); out.rows = room(rows, k * row_stride); out.store = room(store, k * store_stride);
+        out.lens = room(lens, k); out.*ENTRY = room(entry, k); out.cig = room(cig, k); out.score = room(score, k);
         out.meta_r = room(meta_r, k); out.meta = room(meta, k); out.anchor = room(anchor, k); out.clip = room(clip, k);
         return &out;
     }
 };
-
-// what lrm_secondary_batch writes for one batch (docs/GACT_SPEC.md, "Secondary alignments"), grown on demand like SplitBufs
-struct SecBufs {
-    lrm_secondary_out out;
-    std::vector<lrm_secondary> table;
-    std::vector<char> rows;
-    std::vector<uint8_t> store;
-    std::vector<uint32_t> lens;
-    std::vector<lrm_entry> rival;
-    std::vector<lrm_cigar> cig;
-    std::vector<int> score, meta_r;
-    std::vector<lrm_seq_meta> meta;
-    std::vector<lrm_anchor> anchor;
-    std::vector<lrm_clip> clip;
-    SecBufs() { memset(&out, 0, sizeof(out)); }
-    lrm_secondary_out *fit(uint64_t k, uint64_t row_stride, uint64_t store_stride) {
-        memset(&out, 0, sizeof(out));
-        if (k == 0) return &out;
-        auto room = [](auto &v, uint64_t n) { v.resize((size_t) n); return v.data(); };
-        out.cap = k; out.row_stride = row_stride; out.store_stride = store_stride;
-        out.table = room(table, k); out.rows = room(rows, k * row_stride); out.store = room(store, k * store_stride);
-        out.lens = room(lens, k); out.rival = room(rival, k); out.cig = room(cig, k); out.score = room(score, k);
-        out.meta_r = room(meta_r, k); out.meta = room(meta, k); out.anchor = room(anchor, k); out.clip = room(clip, k);
-        return &out;
-    }
-};
+using SplitBufs = PassBufs<lrm_split_out, lrm_segment, &lrm_split_out::seg, &lrm_split_out::best>;
+using SecBufs = PassBufs<lrm_secondary_out, lrm_secondary, &lrm_secondary_out::table, &lrm_secondary_out::rival>;   // (docs/GACT_SPEC.md, "Secondary alignments")
 
 // one batch on its way through the pipeline, with the caller-side buffers of the hot path (pinned: the DMA engines
 // read the reads and write the dense op bytes straight from / into them); recycled.  A set belongs to the thread that
@@ -211,7 +189,7 @@ struct AccalnRun {
 
     // op bytes per read: alnmain.c:316-320, a multiple of 16; the anchored mode's targets are an eighth longer than the reads
     uint64_t store_stride_of(uint64_t max_len) const {
-        const uint64_t s = ((mopt.anchored ? 2 * max_len + max_len / 8 + 2 : 2 * max_len) + 15) & ~15ull;
+        const uint64_t s = ((mopt.anchored ? lrm_anchored_store_stride((uint32_t) max_len) : 2 * max_len) + 15) & ~15ull;
         return s > 0 ? s : (uint64_t) 16;
     }
     void recycle(BatchSet *s) { lrm_read_batch_free(&s->b); free_sets.push(s); }
@@ -375,12 +353,9 @@ struct AccalnRun {
     int split_pass(BatchSet *s) {
         const uint64_t n = s->b.n;
         std::vector<lrm_clip> cl((size_t) n);
+        lrm_clips_of_batch(s->cig.data(), s->meta_r.data(), s->score.data(), 1, n, cl.data());
         uint32_t longest = 0;
-        for (uint64_t i = 0; i < n; ++i) {
-            cl[i].left = cl[i].right = 0;
-            if (s->meta_r[i] != 0 && s->score[i] != -1) (void) lrm_clip_of_cigar(&s->cig[i], 1, &cl[i].left, &cl[i].right);
-            longest = std::max(longest, std::max(cl[i].left, cl[i].right));
-        }
+        for (uint64_t i = 0; i < n; ++i) longest = std::max(longest, std::max(cl[i].left, cl[i].right));
         uint64_t k = 0;
         if (lrm_split_plan(s->b.lens, cl.data(), n, mopt.split_min_len, nullptr, 0, &k) == -1) return -1;
         lrm_split_out *o = s->sp.fit(k, ((uint64_t) longest + 16) & ~15ull, store_stride_of(longest));
@@ -394,7 +369,7 @@ struct AccalnRun {
         uint64_t k = 0;
         if (lrm_secondary_plan(s->mq.data(), n, so.min_hits, so.ratio_pct, nullptr, 0, &k) == -1) return -1;
         const uint64_t L = s->b.max_len;
-        const uint64_t need = (so.anchored || so.clip) ? 2 * L + L / 8 + 2 : 2 * L;
+        const uint64_t need = (so.anchored || so.clip) ? lrm_anchored_store_stride((uint32_t) L) : 2 * L;
         lrm_secondary_out *o = s->sc.fit(k, (L + 16) & ~15ull, ((need + 15) & ~15ull) + 16);
         if (k == 0) return 0;
         return lrm_secondary_batch(gpu, s->b.seqs, s->b.stride, s->b.lens, n, s->mq.data(), s->meta.data(), s->meta_r.data(), p, gp, &mopt, &so, o);

@@ -43,8 +43,6 @@ struct LrmAnchorScratch {
     LrmBsScratch bs;                          // bit-sliced extension over the job table
 };
 
-struct __attribute__((packed, aligned(1))) An16 { uint32_t x, y, z, w; };     // 16 bytes at any address
-
 // ---- scan ------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool an_is_acgt(uint32_t c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; }
 
@@ -159,15 +157,14 @@ __global__ __launch_bounds__(256) void anchor_scan_kernel(const char *__restrict
 
 // ---- jobs ------------------------------------------------------------------------------------------------------------
 // dst[k] = src[k] (right job) or comp(src[cnt - 1 - k]) (left job), k in [c0, c1): 16 bytes per thread, aligned stores
-// (job rows are 16-byte aligned), loads at any address inside the source span
+// (job rows are 16-byte aligned), the source at any byte (seq_bytes.h: the row steps of the gathers, with the one unaligned
+// load that measured faster here).  The row's last bytes go one by one: nothing is written behind a job's length
 template <bool REV>
 __device__ __forceinline__ void an_fill_row(char *__restrict__ dst, const char *__restrict__ src, uint32_t cnt, uint32_t c0,
                                             uint32_t c1, uint32_t tid) {
     for (uint32_t k = c0 + 16 * tid; k < c1; k += 16 * 256) {
         if (k + 16 <= cnt) {
-            const An16 v = *reinterpret_cast<const An16 *>(REV ? src + (cnt - 16 - k) : src + k);
-            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-            *reinterpret_cast<uint4 *>(dst + k) = REV ? revcomp16([&](int e) { return w[e]; }) : make_uint4(w[0], w[1], w[2], w[3]);
+            *reinterpret_cast<uint4 *>(dst + k) = REV ? sp_row16_mirrored<true>(src + (cnt - k), 16u) : sp_row16<true>(src + k, 16u);
         } else {
             for (uint32_t e = k; e < cnt; ++e) dst[e] = REV ? comp_base(src[cnt - 1 - e]) : src[e];
         }
@@ -279,6 +276,7 @@ __device__ __forceinline__ void an_store_meta(lrm_seq_meta *dst, uint64_t loc, u
     uint64_t *w = reinterpret_cast<uint64_t *>(dst);
     w[0] = loc; w[1] = off; w[2] = (uint64_t) (uint32_t) seq_id | ((uint64_t) strand << 32);
 }
+struct __attribute__((packed, aligned(1))) An16 { uint32_t x, y, z, w; };     // 16 op bytes at any address, loaded or stored
 __global__ __launch_bounds__(256) void anchor_stitch_kernel(const uint32_t *__restrict__ lens,
                                                             lrm_seq_meta *__restrict__ meta,
                                                             const int32_t *__restrict__ meta_r, uint64_t n_reads,

@@ -1,6 +1,6 @@
 // SPDX-License-Identifier: MIT
 // base_words.h -- four bases, or four CIGAR columns, per instruction: the word forms of the per-byte helpers that the
-// byte kernels around the extension stage run (bs_pack_reads, revcomp and sec_gather through seq_bytes.h, bs_expand).
+// byte kernels around the extension stage run (bs_pack_reads, revcomp, the row gathers and the anchored job rows through seq_bytes.h, bs_expand).
 // A table of four bytes is looked up for four bytes at once by v_perm_b32.  The file compiles for the device (hipcc)
 // and as plain C for the host (the permute in software), so tests/test_base_words_cpu.py checks on the CPU the very
 // source the kernels run, against the per-byte definitions that stand next to each word form.

@@ -7,7 +7,7 @@
 //   (host)               the 8 bytes {total, longest} cross to pinned memory; the call sleeps on an event until they are there
 //   (host)               the room check: table, row stride, store stride, workspace, gather grid
 //   compact_mark<Rule>   one lane per read: the rule's records at the read's place in the order
-//   sp_row16             the realigned 16-byte step of the stage's row gather
+//   compact_gather<Rule> row s of the compact batch: the source span the rule names, straight or mirrored, zeros behind it
 //
 // Order: a read's first row index is an exclusive prefix sum of the per-read counts -- wave_incl_scan on the DPP network
 // inside a wavefront, the wavefront totals through LDS inside a workgroup, the workgroup totals through compact_scan.  No
@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "lrm_hip_util.h"
+#include "seq_bytes.h"
 
 #define SP_BLOCK 256                          // reads per workgroup of the count / mark kernels
 #define SP_CHUNK 4096                         // bytes of a row one workgroup of a gather kernel moves
@@ -47,6 +48,7 @@ __device__ __forceinline__ void sp_block_totals(uint32_t wave_sum, uint32_t wave
 //   uint32_t items(n, r, Item &item, uint32_t &longest)  rows of read r and the longest of them; 0 beyond the batch, and
 //                                                        `longest` stays the 0 it comes with
 //   void write(r, item, k, at, cap)                      the records of the read's k > 0 rows at `at`; none from `cap` on
+// (and what the gather asks: below)
 template <typename Rule>
 __global__ __launch_bounds__(SP_BLOCK) void compact_count_kernel(Rule rule, uint64_t n, uint2 *__restrict__ blk) {
     __shared__ uint32_t s_sum[SP_BLOCK / 64], s_max[SP_BLOCK / 64];
@@ -73,33 +75,30 @@ __global__ __launch_bounds__(SP_BLOCK) void compact_mark_kernel(Rule rule, uint6
     if (k) rule.write(r, item, k, (uint64_t) blk[blockIdx.x].x + before + incl - k, cap);
 }
 
-// the bytes src[0 .. cnt), cnt in 1 .. 16, as two 64-bit words (o0: bytes 0 .. 7); src at any byte: the lane loads the two
-// aligned 16-byte words that hold its bytes -- the second only when its bytes reach into it -- and realigns them in registers
-// (one 64-bit select for the word offset, one funnel shift for the byte offset).  Bytes from cnt on are whatever follows.
-__device__ __forceinline__ void sp_load16(const char *src, uint32_t cnt, uint64_t &o0, uint64_t &o1) {
-    const uint32_t off = (uint32_t) ((uintptr_t) src & 15u);
-    const uint4 *a = reinterpret_cast<const uint4 *>(src - off);
-    const uint4 lo = a[0];
-    const uint4 hi = off + cnt > 16 ? a[1] : make_uint4(0, 0, 0, 0);       // only when the lane's bytes reach into it
-    uint64_t w0 = lo.x | ((uint64_t) lo.y << 32), w1 = lo.z | ((uint64_t) lo.w << 32);
-    uint64_t w2 = hi.x | ((uint64_t) hi.y << 32);
-    const uint64_t w3 = hi.z | ((uint64_t) hi.w << 32);
-    if (off & 8u) { w0 = w1; w1 = w2; w2 = w3; }
-    const uint32_t sh = (off & 7u) * 8;
-    o0 = sh ? (w0 >> sh) | (w1 << (64 - sh)) : w0;
-    o1 = sh ? (w1 >> sh) | (w2 << (64 - sh)) : w1;
-}
-// zeros from byte cnt on (cnt < 16)
-__device__ __forceinline__ void sp_keep_bytes(uint32_t cnt, uint64_t &o0, uint64_t &o1) {
-    o0 &= cnt >= 8 ? ~0ull : (1ull << (8 * cnt)) - 1;
-    o1 &= cnt > 8 ? (1ull << (8 * (cnt - 8))) - 1 : 0ull;
-}
-// the straight step of a row gather: src[0 .. cnt) as the 16 bytes of one aligned store, zeros behind them
-__device__ __forceinline__ uint4 sp_row16(const char *src, uint32_t cnt) {
-    uint64_t o0, o1;
-    sp_load16(src, cnt, o0, o1);
-    if (cnt < 16) sp_keep_bytes(cnt, o0, o1);
-    return make_uint4((uint32_t) o0, (uint32_t) (o0 >> 32), (uint32_t) o1, (uint32_t) (o1 >> 32));
+// The gather: row s of the compact batch from the table the mark kernel wrote.  The rule adds
+//   static constexpr bool MIRRORS                        can a source span be mirrored at all (false: the path is not compiled)
+//   Span span(s)                                         {first byte, bases} of row s's source
+//   bool mirrored(s)                                     (when MIRRORS) is the row the reverse complement of that span
+//   static uint64_t zeros_to(len, row_stride)            the row byte before which the zeros behind the span end
+// Grid (rows, chunks of SP_CHUNK row bytes); every lane one aligned 16-byte store, the source realigned in registers
+// (seq_bytes.h: sp_row16, sp_row16_mirrored).
+struct CompactSpan { const char *src; uint32_t len; };
+template <typename Rule>
+__global__ __launch_bounds__(256) void compact_gather_kernel(Rule rule, uint64_t n_rows, char *__restrict__ rows, uint64_t row_stride) {
+    const uint64_t s = blockIdx.x;
+    if (s >= n_rows) return;
+    const uint64_t d = (uint64_t) blockIdx.y * SP_CHUNK + 16ull * threadIdx.x;
+    if (d + 16 > row_stride) return;                                 // (row_stride > len and % 16 == 0: never cuts a row short)
+    const CompactSpan sp = rule.span(s);
+    if (d >= Rule::zeros_to(sp.len, row_stride)) return;
+    uint4 o = make_uint4(0, 0, 0, 0);
+    if (d < sp.len) {
+        const uint32_t cnt = sp.len - d < 16 ? (uint32_t) (sp.len - d) : 16u;     // (below 16: the span's last word, zeros behind its end)
+        bool mirrored = false;
+        if constexpr (Rule::MIRRORS) mirrored = rule.mirrored(s);
+        o = mirrored ? sp_row16_mirrored(sp.src + (sp.len - d), cnt) : sp_row16(sp.src + d, cnt);     // mirrored: row[d + k] = comp(src[len - 1 - d - k])
+    }
+    *reinterpret_cast<uint4 *>(rows + s * row_stride + d) = o;
 }
 
 // ---- host side (compact_rows.hip) -----------------------------------------------------------------------------------------

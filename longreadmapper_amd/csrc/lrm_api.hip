@@ -447,6 +447,13 @@ extern "C" int lrm_clip_of_cigar(const lrm_cigar *cig, int is_text, uint32_t *le
     return 0;
 }
 
+void lrm_clips_of_batch(const lrm_cigar *cig, const int *meta_r, const int *score, int is_text, uint64_t n, lrm_clip *out) {
+    for (uint64_t i = 0; i < n; ++i) {
+        out[i].left = out[i].right = 0;
+        if (meta_r[i] != 0 && (score ? score[i] : cig[i].score) != -1) (void) lrm_clip_of_cigar(&cig[i], is_text, &out[i].left, &out[i].right);
+    }
+}
+
 extern "C" int lrm_split_batch_dev(lrm_index *idx, lrm_workspace *ws_seg, const char *d_reads, uint64_t stride,
                                    const uint32_t *d_lens, uint64_t n, const lrm_clip *d_clip, lrm_params p, lrm_gact_params gp,
                                    uint32_t anchor_min_len, uint32_t clip_penalty, uint32_t clip_end_bonus, uint32_t split_min_len,

@@ -238,55 +238,62 @@ extern "C" int lrm_map_batch_submit(lrm_index *idx, char *reads_buf, uint64_t st
                                      meta_out, meta_r_out, opt, nullptr, ticket_out);
 }
 
-// ---- split reads: the second pass over a batch that came back with end clipping (docs/GACT_SPEC.md, "Split reads") ----------
-// alnmain.c:31-52 on the host, as the device's comp_base has it
-static inline char split_comp(char ch) {
-    switch (ch & 0xDF) { case 'A': return 'T'; case 'C': return 'G'; case 'G': return 'C'; case 'T': return 'A'; default: return 'N'; }
-}
-// row = R[start .. start + len) of a read of len_read bases, zeros behind it up to pad_to; mirrored: src holds R's reverse
-// complement
-static void host_gather_row(char *dst, const char *src, uint32_t start, uint32_t len, uint32_t len_read, bool mirrored, uint64_t pad_to) {
-    if (mirrored) for (uint32_t k = 0; k < len; ++k) dst[k] = split_comp(src[len_read - 1 - (start + k)]);
-    else memcpy(dst, src + start, len);
-    memset(dst + len, 0, (size_t) (pad_to - len));
-}
-static int host_row_stride(const char *stage, const char *row, uint64_t row_stride, uint32_t longest) {
+// ---- the second passes over a batch that has come back (split reads, secondary alignments): a plan names the rows of a
+// compact batch, the rows are gathered on the host.  What both begin with: ----
+// the handle's tune under the call's options
+static LrmMapTune host_tune(lrm_index *ix, const lrm_map_options *opt) { LrmMapTune mt = ix->mtune; if (opt) lrm_call_map_tune(ix, opt, &mt); return mt; }
+struct HostSpan { uint32_t read, start, len; };           // row s is R[start .. start + len) of this read
+// the longest of the k planned rows (span(s): row s), checked against the row stride
+template <typename SpanOf>
+static int host_longest_row(const char *stage, const char *row, uint64_t k, uint64_t row_stride, SpanOf span, uint32_t *longest_out) {
+    uint32_t longest = 0;
+    for (uint64_t s = 0; s < k; ++s) longest = span(s).len > longest ? span(s).len : longest;
+    *longest_out = longest;
     if (!(row_stride & 15u) && row_stride > longest) return 0;
     lrm_set_error("%s: row_stride %llu must be a multiple of 16 above the longest %s (%u)", stage, (unsigned long long) row_stride, row, longest);
     return -1;
 }
+// the k rows and their lengths: row s = R[start .. start + len), zeros behind it to the end of the row (pad_row) or to the next
+// multiple of 16.  turned: the caller's copy of a mapped reverse-strand read holds R's reverse complement
+template <typename SpanOf>
+static void host_gather_rows(const char *reads_buf, uint64_t stride, const uint32_t *lens, const lrm_seq_meta *meta, const int *meta_r,
+                             bool turned, uint64_t k, SpanOf span, char *rows, uint64_t row_stride, bool pad_row, uint32_t *row_lens) {
+    const int nt = lrm_host_threads();
+#pragma omp parallel for schedule(dynamic, 64) num_threads(nt)
+    for (uint64_t s = 0; s < k; ++s) {
+        const HostSpan g = span(s);
+        const char *src = reads_buf + (uint64_t) g.read * stride;
+        char *dst = rows + s * row_stride;
+        if (turned && meta_r[g.read] != 0 && meta[g.read].strand == 1)
+            for (uint32_t x = 0; x < g.len; ++x) dst[x] = lrm_comp_table.t[(uint8_t) src[lens[g.read] - 1 - (g.start + x)]];
+        else memcpy(dst, src + g.start, g.len);
+        memset(dst + g.len, 0, (size_t) ((pad_row ? row_stride : ((uint64_t) g.len + 16) & ~15ull) - g.len));
+        row_lens[s] = g.len;
+    }
+}
+
+// ---- split reads: the second pass over a batch that came back with end clipping (docs/GACT_SPEC.md, "Split reads") ----------
 static int split_batch_impl(lrm_index *idx, const char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
                             const lrm_cigar *cig, const lrm_seq_meta *meta, const int *meta_r, lrm_params p, lrm_gact_params gp,
                             const lrm_map_options *opt, lrm_split_out *out) {
-    LrmMapTune mt = idx->mtune;
-    if (opt) lrm_call_map_tune(idx, opt, &mt);
+    const LrmMapTune mt = host_tune(idx, opt);
     if (!mt.clip || !mt.anchored) { lrm_set_error("lrm_split_batch needs lrm_map_options.clip (and with it .anchored)"); return -1; }
     uint32_t M;
     if (lrm_split_min_len(mt.split_min_len, &M)) return -1;
     if (n > 0x7fffffffull) { lrm_set_error("batch too large"); return -1; }
     // the clip counts, as the op bytes or the text of every read have them
     std::vector<lrm_clip> clip((size_t) n);
-    for (uint64_t i = 0; i < n; ++i) {
-        clip[i].left = clip[i].right = 0;
-        if (meta_r[i] != 0 && cig[i].score != -1) (void) lrm_clip_of_cigar(&cig[i], mt.cigar_text, &clip[i].left, &clip[i].right);
-    }
+    lrm_clips_of_batch(cig, meta_r, nullptr, mt.cigar_text, n, clip.data());
     uint64_t n_seg = 0;
     const int prc = lrm_split_plan(lens, clip.data(), n, M, out->seg, out->cap, &n_seg);
     out->n_seg = n_seg;
     if (prc) return prc;
     if (n_seg == 0) return 0;
-    uint32_t longest = 0;
-    for (uint64_t s = 0; s < n_seg; ++s) longest = out->seg[s].len > longest ? out->seg[s].len : longest;
-    if (host_row_stride("split", "segment", out->row_stride, longest)) return -1;
+    const auto span = [&](uint64_t s) { const lrm_segment &g = out->seg[s]; return HostSpan{g.read, g.start, g.len}; };
+    uint32_t longest;
+    if (host_longest_row("split", "segment", n_seg, out->row_stride, span, &longest)) return -1;
     // gather on the host: R is the caller's row, or its reverse complement when the caller kept its reads as they were
-    const int nt = lrm_host_threads();
-#pragma omp parallel for schedule(dynamic, 64) num_threads(nt)
-    for (uint64_t s = 0; s < n_seg; ++s) {
-        const lrm_segment &g = out->seg[s];
-        host_gather_row(out->rows + s * out->row_stride, reads_buf + (uint64_t) g.read * stride, g.start, g.len, lens[g.read],
-                        mt.keep_reads && meta_r[g.read] != 0 && meta[g.read].strand == 1, ((uint64_t) g.len + 16) & ~15ull);
-        out->lens[s] = g.len;
-    }
+    host_gather_rows(reads_buf, stride, lens, meta, meta_r, mt.keep_reads != 0, n_seg, span, out->rows, out->row_stride, false, out->lens);
     // the segment batch through the pipeline, in the caller's result layout
     lrm_map_options o2;
     lrm_map_options_init(&o2);
@@ -303,11 +310,9 @@ static int split_batch_impl(lrm_index *idx, const char *reads_buf, uint64_t stri
     j.best_out = out->best; j.cig = out->cig; j.store_mem = out->store; j.store_stride = out->store_stride; j.score = out->score;
     j.meta = out->meta; j.meta_r = out->meta_r; j.anchor_out = out->anchor;
     if (int rc = run_job(idx, j, &o2, nullptr)) return rc;
-    for (uint64_t s = 0; s < n_seg; ++s) {
-        out->clip[s].left = out->clip[s].right = 0;
-        if (out->meta_r[s] != 0 && out->score[s] != -1) (void) lrm_clip_of_cigar(&out->cig[s], mt.cigar_text, &out->clip[s].left, &out->clip[s].right);
+    lrm_clips_of_batch(out->cig, out->meta_r, out->score, mt.cigar_text, n_seg, out->clip);
+    for (uint64_t s = 0; s < n_seg; ++s)
         if (out->meta_r[s] != 0 && (out->anchor[s].flags & LRM_ANCHOR_ANCHORED)) out->seg[s].flags |= LRM_SEG_ALIGNED;
-    }
     return 0;
 }
 
@@ -343,8 +348,7 @@ static int secondary_batch_impl(lrm_index *idx, const char *reads_buf, uint64_t 
                                 const lrm_mapq *mapq, const lrm_seq_meta *meta, const int *meta_r, lrm_params p, lrm_gact_params gp,
                                 const lrm_map_options *opt, const lrm_secondary_options *so, lrm_secondary_out *out) {
     lrm_index *ix = idx->peers ? idx->peers[0] : idx;     // a group handle: its first device does this pass
-    LrmMapTune mt = ix->mtune;
-    if (opt) lrm_call_map_tune(ix, opt, &mt);
+    const LrmMapTune mt = host_tune(ix, opt);
     lrm_secondary_options o;
     memset(&o, 0, sizeof(o));
     lrm_options_over_defaults(&o, so);
@@ -355,23 +359,16 @@ static int secondary_batch_impl(lrm_index *idx, const char *reads_buf, uint64_t 
     out->n_sec = k;
     if (prc) return prc;
     if (k == 0) return 0;
-    uint32_t longest = 0;
-    for (uint64_t s = 0; s < k; ++s) longest = lens[out->table[s].read] > longest ? lens[out->table[s].read] : longest;
-    if (host_row_stride("secondary", "candidate", out->row_stride, longest)) return -1;
+    const auto span = [&](uint64_t s) { const uint32_t read = out->table[s].read; return HostSpan{read, 0u, lens[read]}; };
+    uint32_t longest;
+    if (host_longest_row("secondary", "candidate", k, out->row_stride, span, &longest)) return -1;
     const uint64_t need = anchored ? lrm_anchored_store_stride(longest) : 2ull * longest;
     if ((out->store_stride & 15u) || out->store_stride < need) {
         lrm_set_error("secondary: store_stride %llu must be a multiple of 16 of at least %llu", (unsigned long long) out->store_stride, (unsigned long long) need);
         return -1;
     }
     // gather on the host, as sequenced: without keep_reads the caller's copy of a reverse-strand read was reverse-complemented
-    const int nt = lrm_host_threads();
-#pragma omp parallel for schedule(dynamic, 64) num_threads(nt)
-    for (uint64_t s = 0; s < k; ++s) {
-        const uint32_t read = out->table[s].read, len = lens[read];
-        host_gather_row(out->rows + s * out->row_stride, reads_buf + (uint64_t) read * stride, 0, len, len,
-                        !mt.keep_reads && meta && meta_r[read] != 0 && meta[read].strand == 1, out->row_stride);
-        out->lens[s] = len;
-    }
+    host_gather_rows(reads_buf, stride, lens, meta, meta_r, !mt.keep_reads && meta, k, span, out->rows, out->row_stride, true, out->lens);
     // the device pass
     if (lrm_require_device(ix->device)) return -1;
     SecWs w;

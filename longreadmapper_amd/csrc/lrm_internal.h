@@ -283,6 +283,14 @@ static inline int base_code(char c) {
     switch (c) { case 'A': return 0; case 'C': return 1; case 'G': return 2; case 'T': return 3; default: return -1; }
 }
 
+// THE complement of a base on the host, as the device's comp_base has it (_rev_comp_in_place, alnmain.c:29-52): ACGT of
+// either case -> the upper-case complement, anything else -> 'N'.  A table: the SAM formatter's hot loop looks it up per base
+struct LrmCompTable {
+    char t[256];
+    constexpr LrmCompTable() : t() { for (int c = 0; c < 256; ++c) t[c] = 'N'; t['A'] = t['a'] = 'T'; t['C'] = t['c'] = 'G'; t['G'] = t['g'] = 'C'; t['T'] = t['t'] = 'A'; }
+};
+inline constexpr LrmCompTable lrm_comp_table;
+
 // THE accessors of a suffix-array slot.  lrm_ui40 is {u32 low; u8 high} in 8 bytes (sa_use.h:17-20), 5 bytes low-first on
 // disk.  This library writes a slot as one little-endian u64: the value is < 2^40, so the three padding bytes are zero and
 // the slot read as a u64 is the value (HostIndex.sa() is such a view).
@@ -302,6 +310,9 @@ static inline bool lrm_alloc(T *&p, uint64_t n, const char *what, bool zero = fa
 // (affinity mask, cgroup CPU quota) -- a GPU box hands a job 16 of its 256 hardware threads, and a team of 256 on a
 // quota of 16 is throttled to a crawl.  OMP_NUM_THREADS still lowers it.
 int lrm_host_threads(void);
+// left / right clip of every alignment of a batch (lrm_clip_of_cigar; zeros for a read that is fenced or has score -1);
+// score null: the scores in cig
+LRM_LOCAL void lrm_clips_of_batch(const lrm_cigar *cig, const int *meta_r, const int *score, int is_text, uint64_t n, lrm_clip *out);
 int lrm_require_device(int device);                 // hipSetDevice + "no CPU fallback" error
 int lrm_workspace_create_parts(lrm_workspace **out, lrm_index *idx, uint64_t n_max, uint32_t max_len, uint32_t seed_len,
                                uint32_t thres, int parts);

@@ -120,9 +120,6 @@ extern "C" char *lrm_sam_header(const lrm_mta_entry *mta, int mta_len, long rg_i
     return dup_out(s, len_out);
 }
 
-// _rev_comp_in_place's base map (alnmain.c:29-52): ACGT of either case -> upper-case complement, anything else -> 'N'
-static const struct CompTable { char t[256]; CompTable() { for (int c = 0; c < 256; ++c) t[c] = 'N'; t['A'] = t['a'] = 'T'; t['C'] = t['c'] = 'G'; t['G'] = t['g'] = 'C'; t['T'] = t['t'] = 'A'; } } k_comp;
-
 // ---- split reads: supplementary records and SA:Z (docs/GACT_SPEC.md, "Split reads") ----------------------------------------
 struct AlnShape { uint64_t q, t, sl, sr; };        // aligned query bases, target span, 'S' columns at the start / at the end
 static AlnShape aln_shape(const lrm_cigar &c, bool is_text) {
@@ -280,7 +277,7 @@ static void sam_format_range(const SamBatch &b, uint64_t lo, uint64_t hi, std::s
             s.resize(at + len);
             const char *src = reads->seqs + i * reads->stride;
             char *dst = &s[at];
-            for (uint32_t x = 0; x < len; ++x) dst[x] = k_comp.t[(uint8_t) src[len - 1 - x]];
+            for (uint32_t x = 0; x < len; ++x) dst[x] = lrm_comp_table.t[(uint8_t) src[len - 1 - x]];
         } else {
             s.append(reads->seqs + i * reads->stride, len);           // the (possibly rev-comped) read
         }

@@ -5,8 +5,9 @@
 //                   the smallest hit of that -- an lrm_entry the extension can start from (zeros: not a candidate)
 //   compact_count / compact_scan / (host) / compact_mark<SecRule>   the candidate table in its order (compact_rows.h):
 //                   a candidate's lrm_secondary record, its length and its rival entry
-//   sec_gather      the read AS SEQUENCED into row s of the candidate batch (the primary extension reverse-complemented
-//                   reverse-strand reads in place: those are read mirrored and complemented)
+//   compact_gather<SecRule>   the read AS SEQUENCED into row s of the candidate batch (the primary extension
+//                   reverse-complemented reverse-strand reads in place: those are read mirrored and complemented), zeros
+//                   from the read's end to the end of the row
 //   (extension)     lrm_launch_extend / lrm_launch_extend_anchored, unchanged, over the rows with best = the rival entries
 //   sec_flag        LRM_SEC_DUPLICATE and LRM_SEC_ALIGNED
 //
@@ -158,6 +159,7 @@ static_assert(RV_SUB_BUCKETS <= LRM_MAPQ_SLOTS, "the sub-buckets live in the pai
 // ---- the candidate table -----------------------------------------------------------------------------------------------------
 // the stage's rule: a candidate read is one row, as long as the read
 struct SecRule {
+    const char *__restrict__ reads; uint64_t stride; const lrm_seq_meta *__restrict__ meta; const int32_t *__restrict__ meta_r;
     const lrm_mapq *__restrict__ mapq; const uint32_t *__restrict__ lens; const lrm_entry *__restrict__ rival; uint32_t H, pct;
     lrm_secondary *__restrict__ table; uint32_t *__restrict__ sec_lens; lrm_entry *__restrict__ sec_rival;
     struct Item {};                                                           // (the record is made of r alone)
@@ -175,40 +177,15 @@ struct SecRule {
         sec_lens[at] = lens[r];
         rv_store_entry(sec_rival + at, e.key, e.val, e.bucket);
     }
-};
-
-// grid (candidates, chunks of SP_CHUNK row bytes); every lane one aligned 16-byte store, zeros from the read's end to the
-// end of the row
-__global__ __launch_bounds__(256) void sec_gather_kernel(const char *__restrict__ reads, uint64_t stride,
-                                                         const lrm_secondary *__restrict__ table,
-                                                         const uint32_t *__restrict__ sec_lens,
-                                                         const lrm_seq_meta *__restrict__ meta, const int32_t *__restrict__ meta_r,
-                                                         uint64_t n_sec, char *__restrict__ rows, uint64_t row_stride) {
-    const uint64_t s = blockIdx.x;
-    if (s >= n_sec) return;
-    const uint64_t d = (uint64_t) blockIdx.y * SP_CHUNK + 16ull * threadIdx.x;
-    if (d + 16 > row_stride) return;                                 // (row_stride > len and % 16 == 0: never cuts a row short)
-    const uint32_t read = table[s].read, len = sec_lens[s];
-    uint4 o = make_uint4(0, 0, 0, 0);
-    if (d < len) {
-        const uint32_t cnt = len - d < 16 ? (uint32_t) (len - d) : 16u;
-        const char *src = reads + (uint64_t) read * stride;
-        const bool mirrored = meta && meta_r[read] != 0 && meta[read].strand == 1;     // the primary extension turned it round
-        if (!mirrored) o = sp_row16(src + d, cnt);
-        else if (cnt == 16) {                                      // row[d + k] = comp(src[len - 1 - d - k]): 16 bytes mirrored
-            uint64_t o0, o1;
-            sp_load16(src + (len - d - 16), 16u, o0, o1);
-            const uint32_t w[4] = {(uint32_t) o0, (uint32_t) (o0 >> 32), (uint32_t) o1, (uint32_t) (o1 >> 32)};
-            o = revcomp16([&](int e) { return w[e]; });
-        } else {                                                     // the row's last bytes: the read's first, one by one
-            uint32_t w[4] = {0, 0, 0, 0};
-            for (uint32_t k = 0; k < cnt; ++k)
-                w[k >> 2] |= (uint32_t) (uint8_t) comp_base(src[len - 1 - d - k]) << (8 * (k & 3u));
-            o = make_uint4(w[0], w[1], w[2], w[3]);
-        }
+    // the gather: the whole read; mirrored when the primary extension turned it round
+    static constexpr bool MIRRORS = true;
+    __device__ CompactSpan span(uint64_t s) const { return CompactSpan{reads + (uint64_t) table[s].read * stride, sec_lens[s]}; }
+    __device__ bool mirrored(uint64_t s) const {
+        const uint32_t read = table[s].read;
+        return meta && meta_r[read] != 0 && meta[read].strand == 1;
     }
-    *reinterpret_cast<uint4 *>(rows + s * row_stride + d) = o;
-}
+    __device__ static uint64_t zeros_to(uint32_t, uint64_t row_stride) { return row_stride; }
+};
 
 // one lane per candidate.  anchored: LRM_SEC_ALIGNED needs an anchor of the candidate's own
 __global__ __launch_bounds__(256) void sec_flag_kernel(lrm_secondary *__restrict__ table, const uint32_t *__restrict__ sec_lens,
@@ -284,7 +261,7 @@ int lrm_launch_secondary(lrm_index *idx, lrm_workspace *ws, const LrmSecArgs &a,
     if (int rc = lrm_launch_rival(idx, ws, a.lens, n, a.seed_len, a.best, a.mapq, a.min_hits, a.ratio_pct, s.rival, stream_)) return rc;
     const uint32_t n_blk = (uint32_t) ((n + SP_BLOCK - 1) / SP_BLOCK);
 
-    const SecRule rule = {a.mapq, a.lens, s.rival, H, pct, out.table, out.lens, out.rival};
+    const SecRule rule = {a.reads, a.stride, a.meta, a.meta_r, a.mapq, a.lens, s.rival, H, pct, out.table, out.lens, out.rival};
     uint64_t n_sec;
     uint32_t longest;
     if (lrm_compact_count(ws, s.c, rule, n, n_blk, stream, &n_sec, &longest)) return -1;
@@ -295,8 +272,7 @@ int lrm_launch_secondary(lrm_index *idx, lrm_workspace *ws, const LrmSecArgs &a,
     if (room || n_sec == 0) return room;
     lrm_time_begin(ws, LRM_K_REVCOMP, stream);
     hipLaunchKernelGGL(compact_mark_kernel<SecRule>, dim3(n_blk), dim3(SP_BLOCK), 0, stream, rule, n, (const uint2 *) s.c.blk, out.cap);
-    hipLaunchKernelGGL(sec_gather_kernel, grid, dim3(256), 0, stream, a.reads, a.stride,
-                       (const lrm_secondary *) out.table, (const uint32_t *) out.lens, a.meta, a.meta_r, n_sec, out.rows, out.row_stride);
+    hipLaunchKernelGGL(compact_gather_kernel<SecRule>, grid, dim3(256), 0, stream, rule, n_sec, out.rows, out.row_stride);
     lrm_time_end(ws, stream);
     HIPCHK(hipGetLastError());
 

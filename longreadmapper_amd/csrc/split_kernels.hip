@@ -3,14 +3,14 @@
 //
 //   compact_count / compact_scan / (host) / compact_mark<SplitRule>   the segment table in its order (compact_rows.h):
 //                   a read has 0, 1 or 2 lrm_segment records, lrm_split_sides says which
-//   split_gather    R[start .. start + len) of every segment into row s of the segment batch
+//   compact_gather<SplitRule>   R[start .. start + len) of every segment into row s of the segment batch
 //   (seed, ext.)    lrm_launch_seed and lrm_launch_extend_anchored (clip on), unchanged, over the segment rows on ws_seg,
 //                   in chunks of ws_seg->n_max rows
 //   split_flag      LRM_SEG_ALIGNED from the segment's meta_r and its anchor record
 //
-// Gather: a lane moves 16 bytes per step.  The destination row is 16-byte aligned, the source is not (a right segment
-// starts at n - cr): sp_row16 realigns it in registers.  The bytes between the segment's end and the next multiple of 16
-// are written as 0.
+// Gather: the shared kernel (compact_rows.h), never mirrored -- the rows are cut from the reads as the extension left them.
+// The destination row is 16-byte aligned, the source is not (a right segment starts at n - cr).  The bytes between the
+// segment's end and the next multiple of 16 are written as 0, nothing behind that.
 #include <hip/hip_runtime.h>
 #include "lrm_hip_util.h"
 #include "extend_stage.h"
@@ -18,6 +18,7 @@
 
 // the stage's rule: the sides of a read that qualify, left before right
 struct SplitRule {
+    const char *__restrict__ reads; uint64_t stride;
     const uint32_t *__restrict__ lens; const lrm_clip *__restrict__ clip; uint32_t M;
     lrm_segment *__restrict__ seg; uint32_t *__restrict__ seg_lens;
     typedef LrmSplitSides Item;
@@ -37,21 +38,14 @@ struct SplitRule {
         at += s.left != 0;
         if (s.right && at < cap) put(at, (uint32_t) r, s.right_start, s.right, LRM_SEG_RIGHT);
     }
+    // the gather: a segment's span is in its record
+    static constexpr bool MIRRORS = false;
+    __device__ CompactSpan span(uint64_t s) const {
+        const uint4 sg = *reinterpret_cast<const uint4 *>(seg + s);    // read, start, len, flags
+        return CompactSpan{reads + (uint64_t) sg.x * stride + sg.y, sg.z};
+    }
+    __device__ static uint64_t zeros_to(uint32_t len, uint64_t) { return len; }     // (the store that holds the last base: to the next multiple of 16)
 };
-
-// grid (segments, chunks of SP_CHUNK row bytes); every lane one aligned 16-byte store
-__global__ __launch_bounds__(256) void split_gather_kernel(const char *__restrict__ reads, uint64_t stride,
-                                                           const lrm_segment *__restrict__ seg, uint64_t n_seg,
-                                                           char *__restrict__ rows, uint64_t row_stride) {
-    const uint64_t s = blockIdx.x;
-    if (s >= n_seg) return;
-    const uint4 sg = *reinterpret_cast<const uint4 *>(seg + s);    // read, start, len, flags
-    const uint32_t len = sg.z;
-    const uint64_t d = (uint64_t) blockIdx.y * SP_CHUNK + 16ull * threadIdx.x;
-    if (d >= len || d + 16 > row_stride) return;                   // (row_stride > len and % 16 == 0: the second never cuts a row short)
-    const uint32_t cnt = len - d < 16 ? (uint32_t) (len - d) : 16u;   // (below 16: the segment's last word, zeros behind its end)
-    *reinterpret_cast<uint4 *>(rows + s * row_stride + d) = sp_row16(reads + (uint64_t) sg.x * stride + sg.y + d, cnt);
-}
 
 __global__ __launch_bounds__(256) void split_flag_kernel(lrm_segment *__restrict__ seg, const int32_t *__restrict__ meta_r,
                                                          const lrm_anchor *__restrict__ anchor, uint64_t n_seg) {
@@ -78,7 +72,7 @@ int lrm_launch_split(lrm_index *idx, lrm_workspace *ws, const LrmSplitArgs &a, c
     LrmCompactScratch &s = *ws->sp;
     if (lrm_compact_scratch(ws, &s, n_blk, "split")) return -1;
 
-    const SplitRule rule = {a.lens, a.clip, a.split_min_len, out.seg, out.lens};
+    const SplitRule rule = {a.reads, a.stride, a.lens, a.clip, a.split_min_len, out.seg, out.lens};
     uint64_t n_seg;
     uint32_t longest;
     if (lrm_compact_count(ws, s, rule, n, n_blk, stream, &n_seg, &longest)) return -1;
@@ -89,7 +83,7 @@ int lrm_launch_split(lrm_index *idx, lrm_workspace *ws, const LrmSplitArgs &a, c
     if (room || n_seg == 0) return room;
     lrm_time_begin(ws, LRM_K_REVCOMP, stream);
     hipLaunchKernelGGL(compact_mark_kernel<SplitRule>, dim3(n_blk), dim3(SP_BLOCK), 0, stream, rule, n, (const uint2 *) s.blk, out.cap);
-    hipLaunchKernelGGL(split_gather_kernel, grid, dim3(256), 0, stream, a.reads, a.stride, out.seg, n_seg, out.rows, out.row_stride);
+    hipLaunchKernelGGL(compact_gather_kernel<SplitRule>, grid, dim3(256), 0, stream, rule, n_seg, out.rows, out.row_stride);
     lrm_time_end(ws, stream);
     HIPCHK(hipGetLastError());
 

@@ -336,30 +336,66 @@ def clip_of_cigar(ops_or_text, is_text=False):
     return int(left.value), int(right.value)
 
 
-class SplitBuffers(ResultBuffers):
-    """Host arrays of an lrm_split_out for up to cap segments of up to max_seg bases."""
+class _PassBuffers(ResultBuffers):
+    """Host arrays of a second pass's out struct (lrm_split_out, lrm_secondary_out) for up to cap rows of up to max_len bases.
+    A subclass names the dtype of its table and its struct; both structs have their fields in the same order."""
+    TABLE_DT = OUT = None
 
-    def __init__(self, cap, max_seg):
+    def __init__(self, cap, max_len, anchored):
         self.cap = cap
-        self.row_stride = (max_seg + 16) // 16 * 16
-        self.store_stride = units16(store_need(max_seg, True))
+        self.row_stride = (max_len + 16) // 16 * 16
+        self.store_stride = max(units16(store_need(max_len, anchored)), 16)
         k = max(cap, 1)
         super().__init__(k, self.store_stride)
-        self.seg = np.zeros(k, dtype=SEGMENT_DT)
+        self.table = np.zeros(k, dtype=self.TABLE_DT)
         self.rows = np.zeros((k, self.row_stride), dtype=np.uint8)
         self.lens = np.zeros(k, dtype=np.uint32)
         self.anchor = np.zeros(k, dtype=ANCHOR_DT)
         self.clip = np.zeros(k, dtype=CLIP_DT)
         cig, store, store_stride, score, meta, meta_r = self.out_args
-        self.out = capi.SplitOut(cap, 0, self.seg.ctypes.data, self.rows.ctypes.data, self.row_stride, self.lens.ctypes.data,
-                                 self.best.ctypes.data, cig, store, store_stride, score, meta, meta_r, self.anchor.ctypes.data,
-                                 self.clip.ctypes.data)
+        self.out = self.OUT(cap, 0, self.table.ctypes.data, self.rows.ctypes.data, self.row_stride, self.lens.ctypes.data,
+                            self.best.ctypes.data, cig, store, store_stride, score, meta, meta_r, self.anchor.ctypes.data,
+                            self.clip.ctypes.data)
 
-    def result(self, k=None, dense=False, text=None):
-        res = super().result(int(self.out.n_seg) if k is None else k, dense, text, seg=self.seg, rows=self.rows, lens=self.lens,
-                             anchor=self.anchor, clip=self.clip)
+    def _result(self, k, dense, text, table, entry="best"):
+        res = super().result(k, dense, text, **{table: self.table}, rows=self.rows, lens=self.lens, anchor=self.anchor, clip=self.clip)
+        if entry != "best":
+            res[entry] = res.pop("best")
         res["buffers"] = self
         return res
+
+
+class SplitBuffers(_PassBuffers):
+    """Host arrays of an lrm_split_out for up to cap segments of up to max_seg bases."""
+    TABLE_DT, OUT = SEGMENT_DT, capi.SplitOut
+
+    def __init__(self, cap, max_seg):
+        super().__init__(cap, max_seg, True)
+        self.seg = self.table
+
+    def result(self, k=None, dense=False, text=None):
+        return self._result(int(self.out.n_seg) if k is None else k, dense, text, "seg")
+
+
+class SecondaryBuffers(_PassBuffers):
+    """Host arrays of an lrm_secondary_out for up to cap candidates of up to max_len bases."""
+    TABLE_DT, OUT = SECONDARY_DT, capi.SecondaryOut
+
+    def result(self, dense=False, text=None):
+        return self._result(int(self.out.n_sec), dense, text, "table", "rival")
+
+
+def _second_pass_args(reads, lens, res, options):
+    """What split_batch and secondary_batch hand to the library alike: the caller's arrays in the library's types, the
+    lrm_map_options (None: the handle's defaults) and the layout they give -> reads, lens, meta, meta_r, opt, text, dense"""
+    reads = np.ascontiguousarray(reads, dtype=np.uint8)
+    lens = np.ascontiguousarray(lens, dtype=np.uint32)
+    opt = capi.map_options(**options) if options is not None else None
+    text = bool(opt.cigar_text) if opt is not None else False
+    dense = (bool(opt.dense_results) or text) if opt is not None else False
+    meta = np.ascontiguousarray(res["meta"], dtype=META_DT)
+    meta_r = np.ascontiguousarray(res["meta_r"], dtype=np.int32)
+    return reads, lens, meta, meta_r, opt, text, dense
 
 
 def _cigars_of(res, n):
@@ -375,52 +411,19 @@ def split_batch(index, reads, lens, res, seed_len=DEFAULT_SEED_LEN, thres=DEFAUL
     (as that call left them), with the same options.  -> dict(seg=SEGMENT_DT table, rows, lens, best, ops, n_ops, score, meta,
     meta_r, anchor, clip [, ops_off]); ops_of / text_of read a segment's alignment like a read's.  cap: room for that many
     segments (None: for every possible one); more raise LrmError, the count is in .n_seg of the exception."""
-    reads = np.ascontiguousarray(reads, dtype=np.uint8)
-    lens = np.ascontiguousarray(lens, dtype=np.uint32)
-    n, stride = reads.shape
     options = _anchor_options(options, True, anchor_min_len, True, clip_penalty, clip_end_bonus)
     options = {**options, "split": 1, "split_min_len": split_min_len}
-    opt = capi.map_options(**options)
-    text = bool(opt.cigar_text)
-    dense = bool(opt.dense_results) or text
+    reads, lens, meta, meta_r, opt, text, dense = _second_pass_args(reads, lens, res, options)
+    n, stride = reads.shape
     if buffers is None:
         buffers = SplitBuffers(2 * n if cap is None else cap, int(lens.max()) if n else 0)
     cig = _cigars_of(res, n)
-    meta = np.ascontiguousarray(res["meta"], dtype=META_DT)
-    meta_r = np.ascontiguousarray(res["meta_r"], dtype=np.int32)
     rc = lib.lrm_split_batch(index.handle, reads.ctypes.data, stride, lens.ctypes.data, n, cig.ctypes.data, meta.ctypes.data,
                              meta_r.ctypes.data, capi.Params(n, seed_len, thres), capi.GactParams(*gact), C.byref(opt),
                              C.byref(buffers.out))
     if rc < 0:
         raise capi.failure("lrm_split_batch", rc=rc, n_seg=int(buffers.out.n_seg))
     return buffers.result(dense=dense, text=text)
-
-
-class SecondaryBuffers(ResultBuffers):
-    """Host arrays of an lrm_secondary_out for up to cap candidates of up to max_len bases."""
-
-    def __init__(self, cap, max_len, anchored):
-        self.cap = cap
-        self.row_stride = (max_len + 16) // 16 * 16
-        self.store_stride = max(units16(store_need(max_len, anchored)), 16)
-        k = max(cap, 1)
-        super().__init__(k, self.store_stride)
-        self.table = np.zeros(k, dtype=SECONDARY_DT)
-        self.rows = np.zeros((k, self.row_stride), dtype=np.uint8)
-        self.lens = np.zeros(k, dtype=np.uint32)
-        self.anchor = np.zeros(k, dtype=ANCHOR_DT)
-        self.clip = np.zeros(k, dtype=CLIP_DT)
-        cig, store, store_stride, score, meta, meta_r = self.out_args
-        self.out = capi.SecondaryOut(cap, 0, self.table.ctypes.data, self.rows.ctypes.data, self.row_stride, self.lens.ctypes.data,
-                                     self.best.ctypes.data, cig, store, store_stride, score, meta, meta_r, self.anchor.ctypes.data,
-                                     self.clip.ctypes.data)
-
-    def result(self, dense=False, text=None):
-        res = super().result(int(self.out.n_sec), dense, text, table=self.table, rows=self.rows, lens=self.lens, anchor=self.anchor,
-                             clip=self.clip)
-        res["rival"] = res.pop("best")
-        res["buffers"] = self
-        return res
 
 
 def secondary_batch(index, reads, lens, res, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT, options=None,
@@ -431,19 +434,13 @@ def secondary_batch(index, reads, lens, res, seed_len=DEFAULT_SEED_LEN, thres=DE
     -> dict(table=SECONDARY_DT, rows, lens, rival, ops, n_ops, score, meta, meta_r, anchor, clip [, ops_off]); ops_of / text_of
     read a candidate's alignment like a read's; res["buffers"].out is the lrm_secondary_out (textio.sam_format(secondary=...)).
     cap: room for that many candidates (None: every read); more raise LrmError with .rc == -3 and .n_sec."""
-    reads = np.ascontiguousarray(reads, dtype=np.uint8)
-    lens = np.ascontiguousarray(lens, dtype=np.uint32)
+    reads, lens, meta, meta_r, opt, text, dense = _second_pass_args(reads, lens, res, options)
     n, stride = reads.shape
-    opt = capi.map_options(**options) if options is not None else None
-    text = bool(opt.cigar_text) if opt is not None else False
-    dense = (bool(opt.dense_results) or text) if opt is not None else False
     anchored = bool(anchored or clip)
     so = capi.SecondaryOptions(C.sizeof(capi.SecondaryOptions), min_hits, ratio_pct, int(anchored), anchor_min_len, int(bool(clip)),
                                clip_penalty, clip_end_bonus)
     buffers = SecondaryBuffers(n if cap is None else cap, int(lens.max()) if n else 0, anchored)
     mq = np.ascontiguousarray(res["mapq"], dtype=MAPQ_DT)
-    meta = np.ascontiguousarray(res["meta"], dtype=META_DT)
-    meta_r = np.ascontiguousarray(res["meta_r"], dtype=np.int32)
     rc = lib.lrm_secondary_batch(index.handle, reads.ctypes.data, stride, lens.ctypes.data, n, mq.ctypes.data, meta.ctypes.data,
                                  meta_r.ctypes.data, capi.Params(n, seed_len, thres), capi.GactParams(*gact),
                                  C.byref(opt) if opt is not None else None, C.byref(so), C.byref(buffers.out))

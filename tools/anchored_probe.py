@@ -4,7 +4,7 @@ end clipping (its kernel is recorded in the extension kernel's slot, next to the
 repeats each, ms per kernel slot (mean, and the spread of the per-repeat totals), and the median ED / len.
 The last leg is the split stage (lrm_split_batch_dev): the bench workload with PROBE_CHIMERAS (default 0.05) of its reads
 turned into chimeras (the second 40 % of the read replaced by the start of another read), per-slot times of the segment
-workspace -- compact_count / scan / mark, split_gather / flag in the revcomp slot, seed and extension of the segment batch in
+workspace -- compact_count / scan / mark / gather, split_flag in the revcomp slot, seed and extension of the segment batch in
 theirs -- and the wall time of the call, which holds the stage's one host wait.
     python tools/anchored_probe.py          PROBE_READS / PROBE_LEN / PROBE_REF scale it down"""
 import time
