@@ -59,8 +59,9 @@ __device__ __forceinline__ uint64_t quad_perm64(uint64_t v) {
 // Every lane of the wavefront must be here (lanes without a seed come with win = 0 and ignore the answer); a lane whose
 // group's first lane has no seed has none either (positions grow with the lane id).
 // sd_issue_shared starts the fetch (the lane's piece: a, and b with two positions per line), sd_finish_shared gathers the
-// line and searches it.  (Keeping the fetches of 2 / 4 / 8 of a lane's seeds in flight between the two: 7.85 / 8.56 / 10.3 ms
-// per Gbp on the bench workload against 7.63 for one -- the kernel is not short of requests in flight.)
+// line and searches it.  (Keeping the fetches of 2 / 4 / 8 of a lane's seeds in flight between the two, all issued together
+// and all waited for together: 7.85 / 8.56 / 10.3 ms per Gbp on the bench workload against 7.63 for one.  What pays is the
+// fetch of the NEXT position under way while THIS one is searched -- the loop of seed_search_kernel, 6.84 against 7.3 [r13].)
 __device__ __forceinline__ void sd_issue_shared(const LrmIndexView &ix, const SdKey &key, ulonglong2 &a, ulonglong2 &b) {
     const uint32_t lane = __lane_id();
     if (ix.sd_f == 4) {
@@ -128,6 +129,16 @@ __device__ __forceinline__ void ss_append(uint64_t *s_tot, uint64_t *s_rec, uint
 // Measured per 1-Gbp step [r2]: E. coli-sized text 512 / 1024 / 2048 / 4096 seeds: 26.2 / 25.5 / 24.9 / 31.6 ms;
 // GRCh38-sized text 1024 / 2048 / 4096: 44.0 / 40.9 / 42.7 ms.  More resident wavefronts (1024: eight workgroups per
 // CU instead of six) do NOT help: the kernel is bound by the memory system's random-request rate, not by latency.
+// FEWER hurt [r13, profiles/r13, ms of the kernel alone on the chip per 1-Gbp step]: six workgroups per CU (2048 seeds,
+// 26 112 B of LDS) 7.0 - 7.3 with one fetch in flight per lane, 6.5 - 6.85 with two (the shared-lines loop below); FOUR per
+// CU -- room for one extension wavefront of 248 VGPRs beside them on every SIMD -- 9.0 - 9.1 with one fetch (LRM_SS_PAD;
+// r3: 16.2 -> 21.8 on the kernel of that time), 7.7 with two, and 4096 seeds (three per CU) with two 8.06; the bench on
+// three streams follows the kernel alone (60.0 parent, 63.0 six with two fetches, 57.9 four with two, 54.3 four with
+// one, 56.9 three with two Gbp/s): the extension's launches get a tenth shorter in the room, a third of what this kernel's
+// lose.  So the occupancy stays where the LDS puts it, and
+// the attribute only says so to the register allocator: at least six wavefronts per SIMD (the pipelined loop takes 64
+// VGPRs, the generic instantiation 61; no scratch).  It is the build that was measured: without it the compiler allocates
+// the pipelined loop differently.
 // COUNT: the counting build (lrm_workspace_set_counting; bench bookkeeping, never in a timed region) adds up the
 // memory requests the device layout really makes -- seeds evaluated, 8-byte table lookups, 16-byte rank requests --
 // into counters->seed_traffic.
@@ -135,7 +146,8 @@ __device__ __forceinline__ void ss_append(uint64_t *s_tot, uint64_t *s_rec, uint
 // slots, tags of at most 32 bits; the launcher checks idx->view): the shared-lines loop is compiled for that form alone,
 // with no branch on the other table forms in it.  Every other handle, and the counting build, take the generic one.
 template <int SS_ITEMS, bool COUNT, bool SD48>
-__global__ __launch_bounds__(256) void seed_search_kernel(LrmIndexView ix, const uint64_t *__restrict__ reads2,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COUNT ? 1 : 6, 8)))
+void seed_search_kernel(LrmIndexView ix, const uint64_t *__restrict__ reads2,
                                                           uint64_t words_per_read,
                                                           const uint32_t *__restrict__ lens,
                                                           const uint8_t *__restrict__ decided, uint64_t n,
@@ -199,34 +211,75 @@ __global__ __launch_bounds__(256) void seed_search_kernel(LrmIndexView ix, const
         uint32_t q = __umulhi(chunk * SS_ITEMS + tid, np_inv), ph = chunk * SS_ITEMS + tid - q * np;
         if (ph >= np) { ++q; ph -= np; }
         if (ph >= np) { ++q; ph -= np; }
-#pragma unroll 1
-        for (uint32_t it = 0; it < SS_ITEMS / 256; ++it) {
-            if (it) {
-                q += dq; ph += dph;
-                if (ph >= np) { ++q; ph -= np; }
+        // The loop is software-pipelined, two line fetches in flight per lane: a step starts the fetch of the NEXT position
+        // (look: cut the window, work out the key, sd_issue_shared) and then searches the line of its own (take).  The two
+        // fetches land in two sets of registers that change roles -- a copy of a fetch's registers would have to wait for the
+        // fetch -- so the loop body is written out for both.  The number of iterations is wave-uniform (j0 is lane 0's
+        // position, a multiple of 64, and positions only grow), and the loop leaves at its end only: every lane of the
+        // wavefront takes part in every fetch, and the count of fetches in flight is the same on every path, which is what
+        // lets the compiler wait for the older of two (a fetch past the last iteration reads line 0 and is never looked at).
+        struct Look { uint64_t code; SdKey key; ulonglong2 a, b; bool have; };
+        auto look = [&](bool real, uint32_t j, uint32_t j0) {
+            Look f;
+            f.have = real && j < lim;
+            f.code = 0;
+            f.key.line = 0; f.key.tag = 0; f.key.tb = 0;
+            if (real) {
+                const uint64_t *wp = words + (j0 >> 5);                                            // wave-uniform address: scalar loads
+                const uint64_t W0 = wp[0], W1 = wp[1], W2 = wp[2];
+                const uint32_t rel = j - j0, sh = (rel & 31u) * 2u;
+                const uint64_t lo = rel < 32u ? W0 : W1, hi = rel < 32u ? W1 : W2;
+                f.code = f.have ? ((lo >> sh) | ((hi << 1) << (63 - sh))) & smask : 0ull;
+                f.key = sd_key_of(ixs, f.code, j & (uint32_t) (ixs.sd_f - 1));
             }
-            const uint32_t j = chunk * SS_ITEMS + it * 256 + tid;
-            const bool have = j < lim;
-            const uint32_t j0 = (uint32_t) __builtin_amdgcn_readfirstlane((int) (j & ~63u));        // lane 0's position: a multiple of 64
-            if (j0 >= lim) break;                                                                  // (positions only grow)
-            const uint64_t *wp = words + (j0 >> 5);                                                // wave-uniform address: scalar loads
-            const uint64_t W0 = wp[0], W1 = wp[1], W2 = wp[2];
-            const uint32_t rel = j - j0, sh = (rel & 31u) * 2u;
-            const uint64_t lo = rel < 32u ? W0 : W1, hi = rel < 32u ? W1 : W2;
-            const uint64_t code = have ? ((lo >> sh) | ((hi << 1) << (63 - sh))) & smask : 0ull;
-            const SdKey key = sd_key_of(ixs, code, j & (uint32_t) (ixs.sd_f - 1));
-            if (SD48) __builtin_assume(key.tb <= 32u);
-            ulonglong2 xa, xb;
-            sd_issue_shared(ixs, key, xa, xb);
+            if (SD48) __builtin_assume(f.key.tb <= 32u);
+            sd_issue_shared(ixs, f.key, f.a, f.b);
+            if (SD48) __builtin_amdgcn_sched_barrier(0);          // the fetch leaves BEFORE the search that follows waits for the one before it
+            return f;
+        };
+        uint32_t j = chunk * SS_ITEMS + tid;
+        uint32_t j0 = (uint32_t) __builtin_amdgcn_readfirstlane((int) (j & ~63u));                  // lane 0's position
+        auto take = [&](const Look &f) {
             uint64_t k = 0, l = 0, c = 0, rr;
-            const int st = sd_finish_shared(ixs, key, code, xa, xb, k, c, COUNT ? my_cnt : nullptr);
-            if (!have) continue;
-            if (st == 1) rr = c;
-            else if (st == 0) rr = 0;
-            else rr = seed_one(ix_nosd, code, seed_len, j, k, l, COUNT ? my_cnt : nullptr);           // (a count beyond 24 bits)
-            if (COUNT) my_seeds++;
-            if (rr > 0 && rr < (uint64_t) thres) {
-                ss_append(s_tot, s_rec, s_q, cap_pp, ph, q, k, rr);
+            const int st = sd_finish_shared(ixs, f.key, f.code, f.a, f.b, k, c, COUNT ? my_cnt : nullptr);
+            if (f.have) {
+                if (st == 1) rr = c;
+                else if (st == 0) rr = 0;
+                else rr = seed_one(ix_nosd, f.code, seed_len, j, k, l, COUNT ? my_cnt : nullptr);     // (a count beyond 24 bits)
+                if (COUNT) my_seeds++;
+                if (rr > 0 && rr < (uint64_t) thres) ss_append(s_tot, s_rec, s_q, cap_pp, ph, q, k, rr);
+            }
+        };
+        auto step = [&]() {
+            j += 256u; j0 += 256u;
+            q += dq; ph += dph;
+            if (ph >= np) { ++q; ph -= np; }
+        };
+        if (j0 < lim) {
+            const uint32_t left = (lim - j0 + 255u) >> 8;                                          // iterations with a position below lim
+            const uint32_t n_it = left < (uint32_t) (SS_ITEMS / 256) ? left : (uint32_t) (SS_ITEMS / 256);
+            if (SD48) {
+                Look fa = look(true, j, j0), fb;
+                uint32_t it = 0;
+#pragma unroll 1
+                do {
+                    fb = look(it + 1 < n_it, j + 256u, j0 + 256u);
+                    take(fa);
+                    step();
+                    fa = look(it + 2 < n_it, j + 256u, j0 + 256u);
+                    if (it + 1 < n_it) take(fb);
+                    step();
+                    it += 2;
+                } while (it < n_it);
+            } else {
+                // The other table forms (two 16-byte requests per fetch, 6-byte slots) keep one fetch in flight: on the
+                // GRCh38-sized text two were 0.8 % slower in the bench (profiles/r13, section 6).
+#pragma unroll 1
+                for (uint32_t it = 0; it < n_it; ++it) {
+                    const Look f = look(true, j, j0);
+                    take(f);
+                    step();
+                }
             }
         }
     } else {
