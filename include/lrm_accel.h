@@ -22,6 +22,7 @@
  *     alnmain.c:574-588
  *   PART 3 result flags, alnmain.c:458-477                      lrm_result_flags (lrm_result_flags_mapq: a real MAPQ)
  *   (no counterpart: the reference prints neither NM nor MD)     lrm_aln_summary_dev, lrm_aln_diff_dev (lrm_md_format: MD:Z)
+ *   (no counterpart: the reference has no per-position output)   lrm_pileup_create, lrm_pileup_add_dev, lrm_pileup_read_dev
  *   context_destroy(), accaln.c:7-43                            lrm_index_free
  *   host batch loop over devices, alnmain.c:302-330             lrm_index_upload_multi (+ the same batch calls)
  *   pair_end(), alnmain.c:554-557 (unimplemented, returns -1)   lrm_pair_end
@@ -525,6 +526,59 @@ int64_t lrm_aln_diff_host(const uint8_t *ops, int n_ops, const uint8_t *target, 
 /* MD:Z text of one read from its events and the n_eq of its summary record, NUL-terminated ("10A0C5", "5^AC0T").  Returns
  * the text length, < 0 when buf (buflen bytes, the NUL included) is too small. */
 int lrm_md_format(const uint32_t *events, uint64_t count, uint32_t n_eq, char *buf, int buflen);
+
+/* PILEUP (docs/GACT_SPEC.md, "Pileup"): per text position of a window [lo, hi) of content[] -- the coordinate of
+ * lrm_seq_meta.loc -- how many alignments cover it, which read bases their 'X' columns show there, how many 'D' columns
+ * fall on it and how many 'I' runs open behind it.  A reduction over all reads of all batches that stays in device memory:
+ * an accumulator is created once, every batch is added behind its extension, and the records come down when the caller
+ * asks, 32 bytes per position.  Asked for per CALL like the summary and the events: nothing runs or is allocated unless a
+ * caller creates an accumulator, and every other output is the same bytes with it or without it.
+ *   depth   the alignments that cover the position, 'D' columns included
+ *   n_eq    depth - (every 'X' count, the class `other` included) - n_del
+ *   x_a, x_c, x_g, x_t   'X' columns whose read byte is A/a, C/c, G/g, T/t; any other read byte counts in `other`, which is
+ *           depth - n_eq - x_a - x_c - x_g - x_t - n_del
+ *   n_del   'D' columns
+ *   n_ins   'I' runs that open right behind this position
+ * All counters are 32-bit and wrap. */
+typedef struct lrm_pileup_col { uint32_t depth, n_eq, x_a, x_c, x_g, x_t, n_del, n_ins; } lrm_pileup_col;   /* 32 bytes */
+#define LRM_PILEUP_TILE 2048           /* positions per workgroup of the read-back: the depth is a prefix sum, scanned by tiles */
+typedef struct lrm_pileup lrm_pileup;  /* opaque: the accumulator of one window on one device */
+/* lo < hi <= con_len of the handle's text (checked; a group handle is refused: its replicas would each hold a part).  The
+ * accumulator is 32 * (hi - lo) + 4 bytes of counters, zeroed, with 64 guard bytes behind them, and 8 bytes per tile of
+ * read-back scratch; lrm_pileup_bytes: all of it. */
+int lrm_pileup_create(lrm_pileup **out, lrm_index *idx, uint64_t lo, uint64_t hi);
+void lrm_pileup_free(lrm_pileup *pl);
+uint64_t lrm_pileup_bytes(const lrm_pileup *pl);
+int lrm_pileup_reset(lrm_pileup *pl, void *stream);      /* all counters back to zero, asynchronous on `stream` */
+/* Adds a batch whose op bytes sit in device memory: call it behind any of the three extension calls on the same stream, with
+ * that call's d_reads, stride, d_lens (the reads as the extension left them: reverse-strand reads reverse-complemented in
+ * place), d_store, store_stride, d_n_ops, d_score, d_meta_r, d_meta.  d_mapq (n lrm_mapq records in device memory, may be
+ * NULL): a read with mapq < min_mapq adds nothing.  store_stride <= 2^31 (checked: the column counts of a row are 32-bit).
+ * One streaming kernel: a byte of ops read per column, 16 read bytes per lane that holds an 'X'; one atomic add per 'X',
+ * 'D' and opening 'I' column inside the window, and two per read for the depth. */
+int lrm_pileup_add_dev(lrm_pileup *pl, const char *d_reads, uint64_t stride, const uint32_t *d_lens, const uint8_t *d_store,
+                       uint64_t store_stride, const int32_t *d_n_ops, const int32_t *d_score, const int32_t *d_meta_r,
+                       const lrm_seq_meta *d_meta, uint64_t n, const lrm_mapq *d_mapq, uint32_t min_mapq, void *stream);
+/* The records of the positions lo + first .. lo + first + count - 1 into d_out (count records in device memory, 16-byte
+ * aligned); first + count <= hi - lo (checked).  Three small kernels on `stream`; the counters are not modified, so more
+ * batches can be added afterwards and read back again. */
+int lrm_pileup_read_dev(lrm_pileup *pl, uint64_t first, uint64_t count, lrm_pileup_col *d_out, void *stream);
+/* The rule on the host, usable without a GPU.  planes: 8 * (hi - lo) + 1 words, zeroed by the caller before the first read
+ * (the device accumulator's own layout: the depth as a difference plane of hi - lo + 1 words, then seven event planes).
+ * One ALIGNED read: its op bytes, its bases in the orientation of the ops, meta.loc.  n_ops <= 0: nothing. */
+void lrm_pileup_add_host(const uint8_t *ops, int n_ops, const uint8_t *read, uint32_t read_len, uint64_t loc, uint64_t lo,
+                         uint64_t hi, uint32_t *planes);
+/* ... and the records of lo + first .. lo + first + count - 1 from such planes.  0 ok, -1 bad range. */
+int lrm_pileup_cols_host(const uint32_t *planes, uint64_t lo, uint64_t hi, uint64_t first, uint64_t count, lrm_pileup_col *out);
+/* Tab-separated text of count positions of sequence seq from its base seq_pos (0-based) on, one line each, no header:
+ * name, 1-based position, reference base, depth, n_eq, x_a, x_c, x_g, x_t, other, n_del, n_ins.  cols[k]: the record of
+ * text position mta[seq].offset + seq_pos + k; content: the text (host memory).  Returns the text length (NUL-terminated,
+ * the NUL not counted), < 0 when buf (buflen bytes) is too small or an argument is bad. */
+int64_t lrm_pileup_format(const lrm_mta_entry *mta, int mta_len, int seq, uint64_t seq_pos, uint64_t count, const char *content,
+                          const lrm_pileup_col *cols, char *buf, int64_t buflen);
+/* Test-only: the first `words` words of the accumulator's allocation (the 8 * (hi - lo) + 1 counter words, then 16 guard
+ * words of 0xC5C5C5C5) into host memory; waits for `stream`. */
+int lrm_debug_pileup_raw(lrm_pileup *pl, uint32_t *out, uint64_t words, void *stream);
 
 /* SPLIT READS (lrm_map_options.split; docs/GACT_SPEC.md, "Split reads"): the soft-clipped ends of a batch that went through
  * the anchored extension with end clipping, mapped as reads of their own.  For read i with n = lens[i] bases, R the read as

@@ -59,6 +59,18 @@ SYMBOLS = {
                                    C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "lrm_aln_diff_host": (C.c_int64, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]),
     "lrm_md_format": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_int]),
+    "lrm_pileup_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_uint64, C.c_uint64]),
+    "lrm_pileup_free": (None, [C.c_void_p]),
+    "lrm_pileup_bytes": (C.c_uint64, [C.c_void_p]),
+    "lrm_pileup_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "lrm_pileup_add_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "lrm_pileup_read_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "lrm_pileup_add_host": (None, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "lrm_pileup_cols_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "lrm_pileup_format": (C.c_int64, [C.POINTER(MtaEntry), C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_int64]),
+    "lrm_debug_pileup_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "lrm_aln_summary_host": (None, [C.c_void_p, C.c_int, C.POINTER(AlnSummary)]),
     "lrm_aln_summary_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                       C.c_void_p, C.c_void_p]),

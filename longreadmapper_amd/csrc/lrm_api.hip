@@ -14,6 +14,7 @@
 #include "lrm_hip_util.h"
 #include "extend_stage.h"
 #include "aln_diff_step.h"
+#include "pileup_step.h"
 #include "rival_rule.h"
 
 static thread_local char g_err[512] = "";
@@ -386,6 +387,92 @@ extern "C" int lrm_aln_diff_dev(lrm_index *idx, const uint8_t *d_store, uint64_t
     if (lrm_require_device(idx->device)) return -1;
     return lrm_launch_aln_diff(d_store, store_stride, d_n_ops, d_score, d_meta_r, d_meta, idx->view.content, idx->view.con_len, n, d_off, cap,
                                d_events, stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// pileup (docs/GACT_SPEC.md, "Pileup"): the rule on the host, the accumulator object and its device-buffer entry points
+// ------------------------------------------------------------------------------------------
+// The host rule is pileup_step.h's: the row walked as a lane of pileup_add_kernel walks it, through pile_word_step.
+extern "C" void lrm_pileup_add_host(const uint8_t *ops, int n_ops, const uint8_t *read, uint32_t read_len, uint64_t loc, uint64_t lo,
+                                    uint64_t hi, uint32_t *planes) {
+    if (!ops || n_ops <= 0 || !planes || lo >= hi) return;
+    pile_host_add(ops, (uint64_t) n_ops, read, read ? read_len : 0u, loc, lo, hi, planes);
+}
+
+extern "C" int lrm_pileup_cols_host(const uint32_t *planes, uint64_t lo, uint64_t hi, uint64_t first, uint64_t count, lrm_pileup_col *out) {
+    if (lo >= hi || first > hi - lo || count > hi - lo - first) { lrm_set_error("pileup: positions [%llu, +%llu) outside a window of %llu", (unsigned long long) first, (unsigned long long) count, (unsigned long long) (hi > lo ? hi - lo : 0)); return -1; }
+    if (!planes || (count && !out)) { lrm_set_error("null argument"); return -1; }
+    pile_host_cols(planes, hi - lo, first, count, out);
+    return 0;
+}
+
+extern "C" void lrm_pileup_free(lrm_pileup *pl) {
+    if (!pl) return;
+    if (hipSetDevice(pl->device) == hipSuccess) lrm_dev_free({pl->d_planes, pl->d_tiles});
+    free(pl);
+}
+
+extern "C" int lrm_pileup_create(lrm_pileup **out, lrm_index *idx, uint64_t lo, uint64_t hi) {
+    if (!out || !idx) { lrm_set_error("null argument"); return -1; }
+    *out = nullptr;
+    if (idx->n_peers > 1) { lrm_set_error("pileup: a group handle holds one text per replica; create the accumulator on one replica (lrm_index_replica)"); return -1; }
+    const uint64_t con_len = idx->view.con_len;
+    if (lo >= hi || hi > con_len) { lrm_set_error("pileup: window [%llu, %llu) is empty or ends behind the text (%llu positions)", (unsigned long long) lo, (unsigned long long) hi, (unsigned long long) con_len); return -1; }
+    if (lrm_require_device(idx->device)) return -1;
+    lrm_pileup *pl;
+    if (!lrm_alloc(pl, 1, "pileup", true)) return -1;
+    pl->idx = idx;
+    pl->device = idx->device;
+    pl->lo = lo; pl->hi = hi; pl->W = hi - lo;
+    pl->n_tiles = (pl->W + LRM_PILEUP_TILE - 1) / LRM_PILEUP_TILE;
+    const uint64_t plane_bytes = 4ull * LRM_PILEUP_WORDS(pl->W), guard_bytes = 4ull * LRM_PILEUP_GUARD_WORDS;
+    const LrmDevAlloc table[] = {{(void **) &pl->d_planes, plane_bytes + guard_bytes}, {(void **) &pl->d_tiles, 8ull * pl->n_tiles}};
+    if (lrm_dev_alloc_table(table, "pileup bytes", &pl->bytes)) { lrm_pileup_free(pl); return -1; }
+    if (hipMemset(pl->d_planes, 0, plane_bytes) != hipSuccess || hipMemset((char *) pl->d_planes + plane_bytes, LRM_PILEUP_GUARD & 0xFF, guard_bytes) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess) {
+        lrm_set_error("pileup: clearing %llu bytes failed", (unsigned long long) plane_bytes);
+        lrm_pileup_free(pl);
+        return -1;
+    }
+    *out = pl;
+    return 0;
+}
+
+extern "C" uint64_t lrm_pileup_bytes(const lrm_pileup *pl) { return pl ? pl->bytes : 0; }
+
+extern "C" int lrm_pileup_reset(lrm_pileup *pl, void *stream) {
+    if (!pl) { lrm_set_error("null argument"); return -1; }
+    if (lrm_require_device(pl->device)) return -1;
+    HIPCHK(hipMemsetAsync(pl->d_planes, 0, 4ull * LRM_PILEUP_WORDS(pl->W), (hipStream_t) stream));
+    return 0;
+}
+
+extern "C" int lrm_pileup_add_dev(lrm_pileup *pl, const char *d_reads, uint64_t stride, const uint32_t *d_lens, const uint8_t *d_store,
+                                  uint64_t store_stride, const int32_t *d_n_ops, const int32_t *d_score, const int32_t *d_meta_r,
+                                  const lrm_seq_meta *d_meta, uint64_t n, const lrm_mapq *d_mapq, uint32_t min_mapq, void *stream) {
+    if (!pl || (n && (!d_reads || !d_lens || !d_store || !d_n_ops || !d_score || !d_meta_r || !d_meta))) { lrm_set_error("null argument"); return -1; }
+    if (store_stride > LRM_PILEUP_MAX_STRIDE) { lrm_set_error("pileup: store_stride %llu above 2^31 (the column counts of a row are 32-bit)", (unsigned long long) store_stride); return -1; }
+    if (lrm_require_device(pl->device)) return -1;
+    return lrm_launch_pileup_add(pl, (const uint8_t *) d_reads, stride, d_lens, d_store, store_stride, d_n_ops, d_score, d_meta_r, d_meta, n,
+                                 d_mapq, min_mapq, stream);
+}
+
+extern "C" int lrm_pileup_read_dev(lrm_pileup *pl, uint64_t first, uint64_t count, lrm_pileup_col *d_out, void *stream) {
+    if (!pl || (count && !d_out)) { lrm_set_error("null argument"); return -1; }
+    if (first > pl->W || count > pl->W - first) { lrm_set_error("pileup: positions [%llu, +%llu) outside a window of %llu", (unsigned long long) first, (unsigned long long) count, (unsigned long long) pl->W); return -1; }
+    if ((uintptr_t) d_out & 15u) { lrm_set_error("pileup records must be 16-byte aligned"); return -1; }
+    if (count == 0) return 0;
+    if (lrm_require_device(pl->device)) return -1;
+    return lrm_launch_pileup_read(pl, first, count, d_out, stream);
+}
+
+extern "C" int lrm_debug_pileup_raw(lrm_pileup *pl, uint32_t *out, uint64_t words, void *stream) {
+    if (!pl || !out) { lrm_set_error("null argument"); return -1; }
+    if (words > LRM_PILEUP_WORDS(pl->W) + LRM_PILEUP_GUARD_WORDS) { lrm_set_error("pileup: the accumulator holds %llu words", (unsigned long long) (LRM_PILEUP_WORDS(pl->W) + LRM_PILEUP_GUARD_WORDS)); return -1; }
+    if (lrm_require_device(pl->device)) return -1;
+    HIPCHK(hipMemcpyAsync(out, pl->d_planes, 4ull * words, hipMemcpyDeviceToHost, (hipStream_t) stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t) stream));
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -1,0 +1,215 @@
+// pileup_kernels.hip -- the pileup (docs/GACT_SPEC.md, "Pileup"): per text position of a window, the depth and the allele
+// counts of every alignment of every batch, accumulated in HBM.  pileup_add_kernel is a stream like aln_diff_kernel -- one
+// byte of ops read per column -- whose atomics are proportional to the DIFFERENCES, not to the columns: one add per 'X',
+// 'D' and opening 'I' column into planar event arrays, and two adds per read into a difference plane of the depth.  The
+// read-back turns the difference plane into depths by a tiled prefix sum and writes the 32-byte records; it leaves the
+// planes as they are.
+#include <hip/hip_runtime.h>
+#include "lrm_hip_util.h"
+#include "pileup_step.h"
+
+namespace {
+
+// relaxed, agent scope, result unused: one global_atomic_add_u32 without return (read in the gfx950 disassembly: no
+// compare-and-swap loop)
+__device__ __forceinline__ void pile_add(uint32_t *p, uint32_t v) {
+    (void) __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// what a wavefront carries from step to step of its row, all uniform: the target-consuming and the query-consuming columns
+// so far, and the last op byte of the previous step (0 before column 0)
+struct PileRow { uint32_t t = 0, q = 0, carry = 0; };
+
+// the window as a kernel sees it: text positions [lo, hi), W = hi - lo, the event planes behind the W + 1 depth words
+struct PileWindow { uint64_t lo, hi, W; uint32_t *planes; };
+
+// One step: the lane's 16 columns (zeros from column n on).  The lane's count of target-consuming columns and its count of
+// query-consuming columns share one word, so ONE inclusive scan gives the lane's target column and its first query byte.
+// The lane's at most 16 query bytes are contiguous: one unaligned 16-byte read (nothing at or behind read + len), every 'X'
+// column's byte picked out of the four registers.  The previous column of a lane's first byte comes over the DPP network
+// (wave_shr:1), as in diff_step.
+__device__ __forceinline__ void pile_step(PileRow &r, const uint4 cur, const uint8_t *__restrict__ read, uint32_t len, uint64_t loc,
+                                          const PileWindow &win) {
+    const uint32_t w[4] = {cur.x, cur.y, cur.z, cur.w};
+    const uint32_t mine = w[3] >> 24;
+    uint32_t prev = (uint32_t) __builtin_amdgcn_update_dpp((int) r.carry, (int) mine, 0x138, 0xf, 0xf, false);   // wave_shr:1; lane 0 keeps the carry
+    r.carry = (uint32_t) __builtin_amdgcn_readlane((int) mine, 63);
+    PileMasks m[4];
+    uint32_t tc = 0, qc = 0, any = 0, any_x = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+        m[k] = pile_masks(w[k], (w[k] << 8) | prev);
+        prev = w[k] >> 24;
+        tc += (uint32_t) __popc(m[k].eq | m[k].x | m[k].d);
+        qc += (uint32_t) __popc(m[k].eq | m[k].x | m[k].i | m[k].s);
+        any |= m[k].x | m[k].d | m[k].i_open;
+        any_x |= m[k].x;
+    }
+    const uint32_t mine2 = tc | (qc << 16);                          // at most 1024 each in a step: the halves never meet
+    const uint32_t incl = wave_incl_scan(mine2), excl = incl - mine2;
+    const uint32_t t_lane = r.t + (excl & 0xFFFFu), q_lane = r.q + (excl >> 16);
+    const uint32_t total = (uint32_t) __builtin_amdgcn_readlane((int) incl, 63);
+    r.t += total & 0xFFFFu;
+    r.q += total >> 16;
+    if (!any) return;
+    uint4 qb = make_uint4(0u, 0u, 0u, 0u);
+    if (any_x) qb = row_load_last_step<uint32_t>(read, q_lane, len);
+    uint32_t t = t_lane, q = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k)
+        pile_word_step(m[k], t, q, qb.x, qb.y, qb.z, qb.w, [&](uint32_t plane, uint32_t tcol) {
+            const uint64_t pos = loc + tcol;
+            if (pos >= win.lo && pos < win.hi) pile_add(win.planes + LRM_PILEUP_EVENT_PLANE(win.W, plane) + (pos - win.lo), 1u);
+        });
+}
+
+// One wavefront per read, four per workgroup; no LDS, no barrier.  As in the summary and the difference kernels two steps
+// are asked for together wherever both lie whole inside the row, and the end of a row goes through the masked loads.  A
+// read without an alignment, a filtered read and a read that starts at or behind the window's end leave before their
+// first row load.  Lane 0 makes the two depth adds once the row's target span is known.
+__global__ __launch_bounds__(256) void pileup_add_kernel(const uint8_t *__restrict__ reads, uint64_t stride, const uint32_t *__restrict__ lens,
+                                                         const uint8_t *__restrict__ store, uint64_t pitch, const int32_t *__restrict__ n_ops,
+                                                         const int32_t *__restrict__ score, const int32_t *__restrict__ meta_r,
+                                                         const lrm_seq_meta *__restrict__ meta, uint64_t rows, const lrm_mapq *__restrict__ mapq,
+                                                         uint32_t min_mapq, PileWindow win) {
+    const uint64_t row = (uint64_t) blockIdx.x * 4u + (uint64_t) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
+    if (row >= rows) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const int nn = n_ops[row];
+    if (nn <= 0 || meta_r[row] == 0 || score[row] == -1) return;
+    if (mapq && (uint32_t) mapq[row].mapq < min_mapq) return;
+    const uint64_t loc = meta[row].loc;
+    if (loc >= win.hi) return;                                       // every count of the read lies at or behind loc
+    const uint32_t n = (uint32_t) nn;                                // (uniform: every branch on it is a scalar one)
+    const uint8_t *ops = store + row * pitch;
+    const uint8_t *read = reads + row * stride;
+    const uint32_t len = lens[row];
+    PileRow r;
+    uint32_t base = 0;
+    for (; base + 2048u <= n; base += 2048u) {                       // two steps whole inside the row: both loads in flight
+        const uint32_t c0 = base + lane * 16u;
+        const uint4 a = row_load_step<uint32_t>(ops, c0), b = row_load_step<uint32_t>(ops, c0 + 1024u);
+        pile_step(r, a, read, len, loc, win);
+        pile_step(r, b, read, len, loc, win);
+    }
+    for (; base < n; base += 1024u)
+        pile_step(r, row_load_last_step<uint32_t>(ops, base + lane * 16u, n), read, len, loc, win);
+    if (lane == 0) {
+        const uint64_t a = loc > win.lo ? loc : win.lo, end = loc + r.t, b = end < win.hi ? end : win.hi;
+        if (a < b) {                                                 // the covered interval clipped to the window
+            pile_add(win.planes + (a - win.lo), 1u);
+            pile_add(win.planes + (b - win.lo), 0xFFFFFFFFu);        // -1; word W when the interval reaches hi
+        }
+    }
+}
+
+// the sum over the 256 threads of a workgroup, returned in every thread, and the inclusive prefix of this thread: a scan
+// over the wavefront on the DPP network, the four wavefront totals through LDS (lds: 4 words; two barriers)
+__device__ __forceinline__ uint32_t block256_incl_scan(uint32_t v, uint32_t *lds, uint32_t &all) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t incl = wave_incl_scan(v);
+    __syncthreads();                                                 // lds is read by the previous round
+    if (lane == 63u) lds[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0;
+    all = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) {
+        const uint32_t wt = lds[k];
+        before += k < wave ? wt : 0u;
+        all += wt;
+    }
+    return before + incl;
+}
+
+// read-back 1: the sum of the difference plane over every tile of LRM_PILEUP_TILE positions, one workgroup per tile
+__global__ __launch_bounds__(256) void pileup_tile_sums_kernel(const uint32_t *__restrict__ diff, uint64_t W, uint32_t *__restrict__ tile_sum) {
+    __shared__ uint32_t lds[4];
+    const uint64_t base = (uint64_t) blockIdx.x * LRM_PILEUP_TILE;
+    uint32_t v = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < LRM_PILEUP_TILE / 256u; ++j) {
+        const uint64_t g = base + j * 256u + threadIdx.x;
+        v += g < W ? diff[g] : 0u;
+    }
+    uint32_t all;
+    (void) block256_incl_scan(v, lds, all);
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = all;
+}
+
+// read-back 2: exclusive prefix sums of the tile sums (the depth in front of every tile), 32-bit and wrapping like the
+// counters: one workgroup of 1024 that loops over the tiles as aln_diff_offsets_kernel loops over the records
+__global__ __launch_bounds__(1024) void pileup_tile_scan_kernel(const uint32_t *__restrict__ tile_sum, uint64_t n, uint32_t *__restrict__ tile_base) {
+    __shared__ uint32_t wave_total[16];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    uint32_t running = 0;
+    for (uint64_t base = 0; base < n; base += 1024u) {
+        const uint64_t i = base + tid;
+        const uint32_t mine = i < n ? tile_sum[i] : 0u;
+        const uint32_t incl = wave_incl_scan(mine);
+        if (lane == 63u) wave_total[wave] = incl;
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < 16u; ++k) {
+            const uint32_t wt = wave_total[k];
+            before += k < wave ? wt : 0u;
+            all += wt;
+        }
+        if (i < n) tile_base[i] = running + before + incl - mine;
+        running += all;
+        __syncthreads();                                             // wave_total is rewritten by the next round
+    }
+}
+
+// read-back 3: the records of the window positions [first, first + count), one workgroup per tile that holds any of them
+// (tile0: the tile of `first`).  The workgroup rescans its tile from the tile's base, 256 positions a round; a position
+// inside the range reads its seven event words and writes its record with two aligned 16-byte stores.
+__global__ __launch_bounds__(256) void pileup_cols_kernel(const uint32_t *__restrict__ planes, uint64_t W, const uint32_t *__restrict__ tile_base,
+                                                          uint64_t tile0, uint64_t first, uint64_t count, lrm_pileup_col *__restrict__ out) {
+    __shared__ uint32_t lds[4];
+    const uint64_t tile = tile0 + blockIdx.x;
+    uint32_t running = tile_base[tile];
+#pragma unroll 1
+    for (uint32_t j = 0; j < LRM_PILEUP_TILE / 256u; ++j) {
+        const uint64_t g = tile * LRM_PILEUP_TILE + j * 256u + threadIdx.x;
+        uint32_t all;
+        const uint32_t depth = running + block256_incl_scan(g < W ? planes[g] : 0u, lds, all);
+        running += all;
+        if (g < first || g - first >= count) continue;               // (first + count <= W: g < W here)
+        uint32_t e[LRM_PILEUP_PLANES];
+#pragma unroll
+        for (uint32_t k = 0; k < LRM_PILEUP_PLANES; ++k) e[k] = planes[LRM_PILEUP_EVENT_PLANE(W, k) + g];
+        const uint32_t x_all = e[LRM_PILEUP_X_A] + e[LRM_PILEUP_X_C] + e[LRM_PILEUP_X_G] + e[LRM_PILEUP_X_T] + e[LRM_PILEUP_X_OTHER];
+        uint4 *o = reinterpret_cast<uint4 *>(out + (g - first));
+        o[0] = make_uint4(depth, depth - x_all - e[LRM_PILEUP_DEL], e[LRM_PILEUP_X_A], e[LRM_PILEUP_X_C]);
+        o[1] = make_uint4(e[LRM_PILEUP_X_G], e[LRM_PILEUP_X_T], e[LRM_PILEUP_DEL], e[LRM_PILEUP_INS]);
+    }
+}
+
+}  // namespace
+
+int lrm_launch_pileup_add(const lrm_pileup *pl, const uint8_t *d_reads, uint64_t stride, const uint32_t *d_lens, const uint8_t *d_store,
+                          uint64_t pitch, const int32_t *d_n_ops, const int32_t *d_score, const int32_t *d_meta_r, const lrm_seq_meta *d_meta,
+                          uint64_t rows, const lrm_mapq *d_mapq, uint32_t min_mapq, void *stream) {
+    if (rows == 0) return 0;
+    uint32_t grid;
+    if (lrm_grid_1d((rows + 3) / 4, "pileup", &grid)) return -1;
+    const PileWindow win = {pl->lo, pl->hi, pl->W, pl->d_planes};
+    hipLaunchKernelGGL(pileup_add_kernel, dim3(grid), dim3(256), 0, (hipStream_t) stream, d_reads, stride, d_lens, d_store, pitch, d_n_ops,
+                       d_score, d_meta_r, d_meta, rows, d_mapq, min_mapq, win);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int lrm_launch_pileup_read(const lrm_pileup *pl, uint64_t first, uint64_t count, lrm_pileup_col *d_out, void *stream) {
+    const uint64_t tile0 = first / LRM_PILEUP_TILE, tile_end = (first + count + LRM_PILEUP_TILE - 1) / LRM_PILEUP_TILE;   // tiles [0, tile_end) are summed
+    uint32_t grid_sums, grid_cols;
+    if (lrm_grid_1d(tile_end, "pileup read-back", &grid_sums) || lrm_grid_1d(tile_end - tile0, "pileup read-back", &grid_cols)) return -1;
+    uint32_t *sums = pl->d_tiles, *bases = pl->d_tiles + pl->n_tiles;
+    hipLaunchKernelGGL(pileup_tile_sums_kernel, dim3(grid_sums), dim3(256), 0, (hipStream_t) stream, pl->d_planes, pl->W, sums);
+    hipLaunchKernelGGL(pileup_tile_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t) stream, sums, tile_end, bases);
+    hipLaunchKernelGGL(pileup_cols_kernel, dim3(grid_cols), dim3(256), 0, (hipStream_t) stream, pl->d_planes, pl->W, bases, tile0, first, count, d_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}

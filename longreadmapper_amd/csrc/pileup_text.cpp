@@ -1,0 +1,42 @@
+// pileup_text.cpp -- pileup records as text (lrm_pileup_format, include/lrm_accel.h; docs/GACT_SPEC.md, "Pileup").  Host-side
+// C++; the numbers go through put_uint of sam_text.h.
+#include <cstdint>
+#include <cstring>
+#include <initializer_list>
+#include "pileup_text.h"
+#include "sam_text.h"
+#include "lrm_internal.h"
+
+int pileup_put_line(char *dst, const char *name, uint64_t name_len, uint64_t pos1, char base, const lrm_pileup_col &c) {
+    char *p = dst;
+    memcpy(p, name, name_len);
+    p += name_len;
+    *p++ = '\t';
+    p += put_uint(p, pos1);
+    *p++ = '\t';
+    *p++ = base;
+    const uint32_t other = c.depth - c.n_eq - c.x_a - c.x_c - c.x_g - c.x_t - c.n_del;
+    for (const uint32_t v : {c.depth, c.n_eq, c.x_a, c.x_c, c.x_g, c.x_t, other, c.n_del, c.n_ins}) {
+        *p++ = '\t';
+        p += put_uint(p, v);
+    }
+    *p++ = '\n';
+    return (int) (p - dst);
+}
+
+extern "C" int64_t lrm_pileup_format(const lrm_mta_entry *mta, int mta_len, int seq, uint64_t seq_pos, uint64_t count, const char *content,
+                                     const lrm_pileup_col *cols, char *buf, int64_t buflen) {
+    if (!mta || !buf || buflen <= 0 || (count && (!content || !cols))) { lrm_set_error("null argument"); return -1; }
+    if (seq < 0 || seq >= mta_len) { lrm_set_error("pileup text: sequence %d of %d", seq, mta_len); return -1; }
+    const lrm_mta_entry &m = mta[seq];
+    if (seq_pos > m.seq_len || count > m.seq_len - seq_pos) { lrm_set_error("pileup text: positions [%llu, +%llu) outside a sequence of %llu bases", (unsigned long long) seq_pos, (unsigned long long) count, (unsigned long long) m.seq_len); return -1; }
+    const char *name = m.name ? m.name : "";
+    const uint64_t name_len = m.name ? m.name_len : 0, room = pileup_line_room(name_len);
+    int64_t at = 0;
+    for (uint64_t k = 0; k < count; ++k) {
+        if ((uint64_t) (buflen - at) < room + 1) { lrm_set_error("pileup text: buffer of %lld bytes too small", (long long) buflen); return -2; }   // (+1: the NUL)
+        at += pileup_put_line(buf + at, name, name_len, seq_pos + k + 1, content[m.offset + seq_pos + k], cols[k]);
+    }
+    buf[at] = '\0';
+    return at;
+}

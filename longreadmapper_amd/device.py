@@ -29,8 +29,12 @@ class DeviceMapper:
     def __init__(self, index, n_max, max_len, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT,
                  device=0, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0, split=False,
                  split_min_len=0, seg_cap=None, seg_rows=None, mapq=False, summary=False, md=False, secondary=False, sec_cap=None,
-                 sec_min_hits=0, sec_ratio_pct=0):
-        """secondary (needs mapq): secondary() after seed() and extend() finds the rival locus of every candidate read and
+                 sec_min_hits=0, sec_ratio_pct=0, pileup=None, pileup_min_mapq=0):
+        """pileup=(lo, hi): an accumulator over the text positions [lo, hi) (lrm_pileup_create; docs/GACT_SPEC.md, "Pileup";
+        index.text_window gives a sequence's).  extend() adds every batch behind the summary and the event stages
+        (lrm_pileup_add_dev) -- with mapq=True only the reads whose lrm_mapq record says mapq >= pileup_min_mapq -- and it
+        stays in device memory across batches: pileup_columns() returns the PILEUP_COL_DT records, pileup_reset() clears it.
+        secondary (needs mapq): secondary() after seed() and extend() finds the rival locus of every candidate read and
         extends the read there, in this mapper's extension mode (lrm_secondary_batch_dev; docs/GACT_SPEC.md, "Secondary
         alignments"); secondary_results() returns the table and the per-candidate outputs.  sec_cap: room for that many
         candidates (None: n_max, every read); sec_min_hits, sec_ratio_pct: H and pct of the candidate test (0: 8, 50).  Nothing is
@@ -72,6 +76,11 @@ class DeviceMapper:
         self.summary = self._record_tensor(n_max, SUMMARY_DT) if summary or md else None
         self.diff_off = torch.zeros(n_max + 1, dtype=torch.int64, device=self.dev) if md else None
         self.diff_events = torch.zeros(1, dtype=torch.int32, device=self.dev) if md else None
+        self.pileup, self.pileup_window, self.pileup_min_mapq = None, None, pileup_min_mapq
+        if pileup is not None:
+            pl = C.c_void_p()
+            check(lib.lrm_pileup_create(C.byref(pl), index.handle, int(pileup[0]), int(pileup[1])), "lrm_pileup_create")
+            self.pileup, self.pileup_window = pl, (int(pileup[0]), int(pileup[1]))
         self.sec, self.n_sec = None, 0
         if secondary:
             if not mapq:
@@ -183,6 +192,28 @@ class DeviceMapper:
             check(lib.lrm_aln_diff_dev(self.index.handle, self.store.data_ptr(), self.store_stride, self.n_ops.data_ptr(),
                                        self.score.data_ptr(), self.meta_r.data_ptr(), self.meta.data_ptr(), n, self.diff_off.data_ptr(),
                                        total, self.diff_events.data_ptr(), self._stream()), "lrm_aln_diff_dev")
+        if self.pileup is not None:
+            check(lib.lrm_pileup_add_dev(self.pileup, d_reads.data_ptr(), d_reads.stride(0), d_lens.data_ptr(), self.store.data_ptr(),
+                                         self.store_stride, self.n_ops.data_ptr(), self.score.data_ptr(), self.meta_r.data_ptr(),
+                                         self.meta.data_ptr(), n, self.mapq.data_ptr() if self.mapq is not None else None,
+                                         self.pileup_min_mapq if self.mapq is not None else 0, self._stream()), "lrm_pileup_add_dev")
+
+    def pileup_columns(self, first=None, count=None):
+        """The PILEUP_COL_DT records of window positions first .. first + count - 1 (default: the whole window) of everything
+        extend() has added since the accumulator was created or reset -- DeviceMapper(..., pileup=(lo, hi))."""
+        assert self.pileup is not None
+        first = 0 if first is None else first
+        count = self.pileup_window[1] - self.pileup_window[0] - first if count is None else count
+        out = self._record_tensor(max(count, 1), capi.PILEUP_COL_DT, self.torch.int32)
+        check(lib.lrm_pileup_read_dev(self.pileup, first, count, out.data_ptr(), self._stream()), "lrm_pileup_read_dev")
+        return _records(out[:count], capi.PILEUP_COL_DT)
+
+    def pileup_reset(self):
+        assert self.pileup is not None
+        check(lib.lrm_pileup_reset(self.pileup, self._stream()), "lrm_pileup_reset")
+
+    def pileup_bytes(self):
+        return int(lib.lrm_pileup_bytes(self.pileup)) if self.pileup is not None else 0
 
     def _extend(self, d_reads, d_lens, n):
         args = (self.index.handle, self.ws, d_reads.data_ptr(), d_reads.stride(0), d_lens.data_ptr(), n, self.max_len,
@@ -306,6 +337,9 @@ class DeviceMapper:
         return res
 
     def close(self):
+        if getattr(self, "pileup", None):
+            lib.lrm_pileup_free(self.pileup)
+            self.pileup = None
         if getattr(self, "ws_seg", None):
             lib.lrm_workspace_free(self.ws_seg)
             self.ws_seg = None

@@ -140,6 +140,16 @@ class HostIndex:
         return out
 
 
+def text_window(host, s):
+    """(lo, hi) of sequence s of a HostIndex in text positions -- the coordinate of lrm_seq_meta.loc: base p of the sequence sits
+    at mta[s].offset + p, its forward half, where reads align.  The window of a pileup over the whole sequence
+    (DeviceMapper(..., pileup=text_window(host, s)))."""
+    if not 0 <= s < host.mta_len:
+        raise IndexError("sequence %d of %d" % (s, host.mta_len))
+    m = host.h.mta[s]
+    return int(m.offset), int(m.offset) + int(m.seq_len)
+
+
 class DeviceIndex:
     """Device-resident index image (lrm_index*)."""
 

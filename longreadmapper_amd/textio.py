@@ -158,6 +158,34 @@ def paf_format(batch, mta, cig, score, meta, meta_r, n, summary, *, is_text=0, m
                  _at(summary), _at(mapq))
 
 
+def pileup_text(host, s, seq_pos, cols):
+    """lrm_pileup_format: the lines of len(cols) positions of sequence s of a HostIndex from its base seq_pos (0-based) on;
+    cols: PILEUP_COL_DT records, cols[k] for text position mta[s].offset + seq_pos + k."""
+    cols = np.ascontiguousarray(cols, dtype=capi.PILEUP_COL_DT)
+    room = (int(host.h.mta[s].name_len) + 128) * len(cols) + 1
+    buf = C.create_string_buffer(room)
+    k = lib.lrm_pileup_format(host.h.mta, host.mta_len, s, seq_pos, len(cols), host.h.content, cols.ctypes.data if len(cols) else None, buf, room)
+    if k < 0:
+        raise capi.failure("lrm_pileup_format", rc=k)
+    return buf.raw[:k]
+
+
+def write_pileup(path, host, cols, lo, chunk=1 << 16):
+    """The pileup records of a window as text: cols[k] is the record of text position lo + k (DeviceMapper.pileup_columns()
+    of a window that starts at lo).  One line per position that lies in a sequence of the HostIndex (index.text_window), in
+    text order; no header.  -> the number of lines."""
+    lines = 0
+    with open(path, "wb") as f:
+        for s in range(host.mta_len):
+            off, n = int(host.h.mta[s].offset), int(host.h.mta[s].seq_len)
+            a, b = max(lo, off), min(lo + len(cols), off + n)
+            for p in range(a, b, chunk):
+                e = min(p + chunk, b)
+                f.write(pileup_text(host, s, p - off, cols[p - lo:e - lo]))
+                lines += e - p
+    return lines
+
+
 def accaln(genome, reads, out, batch_size, seed_len=20, thres=300, gact=(0, 0, 0), device=0, rg_id=1, options=None, mapq=0, paf=False, md=False,
            secondary=None):
     """secondary: an lrm_secondary_options (capi.SecondaryOptions) -- lrm_accaln_secondary: the flow of lrm_accaln_mapq plus a FLAG

@@ -1,0 +1,95 @@
+"""Probe (run on the GPU box): what the pileup costs (docs/GACT_SPEC.md, "Pileup").  The bench workload (ONT reads on an
+E. coli-sized text with planted repeat families) is seeded and extended once through DeviceMapper, so that its op rows sit in
+HBM; the window is the whole text.  Then, with events on the stream, a warm-up and REPEATS timed launches each of
+pileup_add_kernel, of the read-back of the whole window (tile sums, their scan, the records), and -- as yardsticks of the same
+stream shape -- of aln_diff_kernel and aln_summary_kernel.  Printed: ms per Gbp of reads (mean, min, max), the number of
+atomic adds of one pileup_add launch (from the accumulator itself) and the adds per second at the fastest launch.
+    python tools/pileup_probe.py       PROBE_READS / PROBE_LEN / PROBE_REF scale it down, PROBE_REPEATS (default 10)"""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from longreadmapper_amd import capi, index, mapper, synth
+from longreadmapper_amd.capi import check, lib
+
+REPEATS = int(os.environ.get("PROBE_REPEATS", "10"))
+n = int(os.environ.get("PROBE_READS", "100000"))
+length = int(os.environ.get("PROBE_LEN", "10000"))
+ref_len = int(os.environ.get("PROBE_REF", "4641652"))
+ref = synth.reference(ref_len, seed=1, repeat_frac=0.05, rep_len=300, rep_copies=1000, rep_div=0.05)
+hi = index.HostIndex.build([ref], hlen=12)
+di = index.DeviceIndex.upload(hi, 0)
+r = synth.reads([ref], n, length, synth.ONT, seed=11)
+gbp = float(r["lens"].sum()) / 1e9
+d_reads = torch.from_numpy(r["reads"]).cuda()
+d_lens = torch.from_numpy(r["lens"].astype(np.int32)).cuda()
+window = (0, int(hi.h.con_len))
+W = window[1] - window[0]
+print("bench workload (ONT %d bp): %d reads, %.3f Gbp, window of %d positions (%.1f MB of counters), %d timed repeats" %
+      (length, n, gbp, W, (32 * W + 4) / 1e6, REPEATS), flush=True)
+dm = mapper.DeviceMapper(di, n, length, md=True, pileup=window)
+dm.seed(d_reads, d_lens)
+dm.extend(d_reads, d_lens)                                   # (runs the stages once: the warm-up; the accumulator holds one batch)
+torch.cuda.synchronize()
+stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+n_ops = dm.n_ops[:n].cpu().numpy()
+cols = int(n_ops[n_ops > 0].sum())
+off, ev = dm.diff_records(n)
+total = int(off[n])
+# the adds of one launch, counted from the accumulator: every event word is the number of adds that hit it, and a covered
+# read made two adds to the difference plane
+raw = np.zeros(8 * W + 1, dtype=np.uint32)
+check(lib.lrm_debug_pileup_raw(dm.pileup, raw.ctypes.data, len(raw), stream), "lrm_debug_pileup_raw")
+event_adds = int(raw[W + 1:].astype(np.int64).sum())
+covered = int(((dm.meta_r[:n].cpu().numpy() != 0) & (dm.score[:n].cpu().numpy() != -1) & (n_ops > 0)).sum())
+adds = event_adds + 2 * covered
+print("  op rows in HBM: %.3f G columns; %.3f G 'X' / 'D' events (%.3f per column); one pileup_add launch: %.4f G event adds "
+      "(%.4f per column: %s) + 2 x %d depth adds" % (cols / 1e9, total / 1e9, total / max(cols, 1), event_adds / 1e9, event_adds / max(cols, 1),
+      ", ".join("%s %.4f G" % (name, raw[W + 1 + k * W:W + 1 + (k + 1) * W].astype(np.int64).sum() / 1e9) for k, name in enumerate(capi.PILEUP_PLANES)),
+      covered), flush=True)
+hot = raw[W + 1:].max()
+print("  the hottest event word took %d adds; mean depth %.1f" % (int(hot), float(np.cumsum(raw[:W].astype(np.int32), dtype=np.int64).mean())), flush=True)
+d_out = torch.zeros((W, 8), dtype=torch.int32, device="cuda")
+
+
+def timed(what, call, per=None):
+    call()                                                   # warm-up
+    torch.cuda.synchronize()
+    ms = []
+    for rep in range(REPEATS):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        call()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    tail = "" if per is None else "; %.2f G %s per second at the fastest" % (per[0] / (min(ms) * 1e-3) / 1e9, per[1])
+    print("  %s: %.3f ms per Gbp (min %.3f, max %.3f over the repeats; %.3f ms per launch)%s" %
+          (what, np.mean(ms) / gbp, min(ms) / gbp, max(ms) / gbp, np.mean(ms), tail), flush=True)
+    return ms
+
+
+timed("pileup_add_kernel", lambda: check(lib.lrm_pileup_add_dev(
+    dm.pileup, d_reads.data_ptr(), d_reads.stride(0), d_lens.data_ptr(), dm.store.data_ptr(), dm.store_stride, dm.n_ops.data_ptr(),
+    dm.score.data_ptr(), dm.meta_r.data_ptr(), dm.meta.data_ptr(), n, None, 0, stream), "lrm_pileup_add_dev"), per=(adds, "adds"))
+timed("pileup read-back, whole window", lambda: check(lib.lrm_pileup_read_dev(dm.pileup, 0, W, d_out.data_ptr(), stream), "lrm_pileup_read_dev"),
+      per=(64 * W, "bytes (32 read, 32 written per position)"))
+timed("aln_diff_kernel", lambda: check(lib.lrm_aln_diff_dev(
+    di.handle, dm.store.data_ptr(), dm.store_stride, dm.n_ops.data_ptr(), dm.score.data_ptr(), dm.meta_r.data_ptr(), dm.meta.data_ptr(), n,
+    dm.diff_off.data_ptr(), total, dm.diff_events.data_ptr(), stream), "lrm_aln_diff_dev"))
+timed("aln_summary_kernel", lambda: check(lib.lrm_aln_summary_dev(
+    di.handle, dm.store.data_ptr(), dm.store_stride, dm.n_ops.data_ptr(), dm.score.data_ptr(), dm.meta_r.data_ptr(), n, dm.summary.data_ptr(),
+    stream), "lrm_aln_summary_dev"))
+# the accumulator now holds 2 + REPEATS launches of the same batch (extend's, the warm-up, the timed ones): every counter is that multiple of the first launch's
+cols_now = dm.pileup_columns()
+k = 2 + REPEATS
+raw2 = np.zeros(8 * W + 1, dtype=np.uint32)
+check(lib.lrm_debug_pileup_raw(dm.pileup, raw2.ctypes.data, len(raw2), stream), "lrm_debug_pileup_raw")
+print("  after %d launches every counter word is %d times the first launch's: %s; deepest position %d" %
+      (k, k, bool(np.array_equal(raw2, raw * np.uint32(k))), int(cols_now["depth"].max())), flush=True)
+dm.close()
+di.close()
