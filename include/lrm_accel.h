@@ -426,7 +426,25 @@ typedef struct lrm_workspace lrm_workspace;   /* opaque: device scratch for a ba
 /* Scratch for batches of up to n_max reads of up to max_len bases.
  * Preconditions of the *_dev calls (not checked on the device): d_lens[i] <= max_len <= stride, and
  * store_stride >= 2*max_len.  A kernel-side error of a batch (vote table overflow) is sticky: the NEXT *_dev
- * call on the workspace, or lrm_workspace_stats, returns -2 and clears it. */
+ * call on the workspace, or lrm_workspace_stats, returns -2 and clears it.
+ *
+ * Read extents.  stride == max_len is supported: rows may abut, and the last row may end on the buffer's last byte.  The
+ * result of every call is a function of d_reads[i*stride .. i*stride + d_lens[i]) and d_lens alone: whatever lies between,
+ * in front of and behind the reads -- zeros, bases, the next read -- is never compared, packed or copied.  A kernel may
+ * LOAD the aligned 16-byte lines that hold a read's first and last base, so up to 15 bytes in front of the first read and
+ * behind the last one: d_reads need not be aligned, but those two lines must lie in memory the device can read (any
+ * allocation does: its granularity is coarser).  Rows >= n of any array are neither read nor written.
+ *
+ * Written extents.  The extension calls turn the d_lens[i] bases of a reverse-strand read round in place and write no
+ * other byte of d_reads.  Of every output array they write the rows < n only.  Of op row i (d_store + i*store_stride) no
+ * byte at or behind n_ops[i] rounded up to 4 (lrm_extend_batch_dev) or to 16 (the anchored and the clipped call, which move
+ * 16-byte groups) is written; a read without a locus (meta_r == 0) gets no op byte at all.  One exception: a read of
+ * lrm_extend_batch_dev with a locus whose alignment is abandoned (score == -1, n_ops == 0) may leave the columns walked so
+ * far, at most 2*d_lens[i] bytes.  (Today's kernels end on byte n_ops[i]; the rounding is granted on purpose, so that a
+ * kernel may come to store whole groups without breaking a caller that packs something of its own behind a row.)
+ * The per-segment and per-candidate stores of the split and secondary stages follow the clipped call's rule; their rows
+ * arrays are written to the next multiple of 16 behind a segment (split) or to row_stride (secondary), zeros behind the
+ * bases. */
 int lrm_workspace_create(lrm_workspace **out, lrm_index *idx, uint64_t n_max,
                          uint32_t max_len, uint32_t seed_len, uint32_t thres);
 void lrm_workspace_free(lrm_workspace *ws);

@@ -74,8 +74,8 @@ class DeviceMapper:
         self.clip = self._record_tensor(n_max, CLIP_DT, torch.int32) if clip else None
         self.mapq = self._record_tensor(n_max, MAPQ_DT) if mapq else None
         self.summary = self._record_tensor(n_max, SUMMARY_DT) if summary or md else None
-        self.diff_off = torch.zeros(n_max + 1, dtype=torch.int64, device=self.dev) if md else None
-        self.diff_events = torch.zeros(1, dtype=torch.int32, device=self.dev) if md else None
+        self.diff_off = self._alloc(n_max + 1, torch.int64) if md else None
+        self.diff_events = self._alloc(1, torch.int32) if md else None
         self.pileup, self.pileup_window, self.pileup_min_mapq = None, None, pileup_min_mapq
         if pileup is not None:
             pl = C.c_void_p()
@@ -90,13 +90,11 @@ class DeviceMapper:
             self.sec_row_stride = (max_len + 16) // 16 * 16
             self.sec_store_stride = units16(self.store_stride)
             g = self.sec = dict(table=self._record_tensor(k, SECONDARY_DT, torch.int32),
-                                rows=torch.zeros((k, self.sec_row_stride), dtype=torch.uint8, device=self.dev),
-                                lens=torch.zeros(k, dtype=torch.int32, device=self.dev),
+                                rows=self._alloc((k, self.sec_row_stride), torch.uint8), lens=self._alloc(k, torch.int32),
                                 rival=self._record_tensor(k, ENTRY_DT, torch.int64),
-                                store=torch.zeros((k, self.sec_store_stride), dtype=torch.uint8, device=self.dev),
-                                n_ops=torch.zeros(k, dtype=torch.int32, device=self.dev),
-                                score=torch.zeros(k, dtype=torch.int32, device=self.dev), meta=self._record_tensor(k, META_DT),
-                                meta_r=torch.zeros(k, dtype=torch.int32, device=self.dev))
+                                store=self._alloc((k, self.sec_store_stride), torch.uint8), n_ops=self._alloc(k, torch.int32),
+                                score=self._alloc(k, torch.int32), meta=self._record_tensor(k, META_DT),
+                                meta_r=self._alloc(k, torch.int32))
             if anchored:
                 g["anchor"] = self._record_tensor(k, ANCHOR_DT)
             if clip:
@@ -120,26 +118,30 @@ class DeviceMapper:
             k = max(cap, 1)
             self.seg_row_stride = (max_len + 16) // 16 * 16
             g = self.seg = dict(seg=self._record_tensor(k, SEGMENT_DT, torch.int32),
-                                rows=torch.zeros((k, self.seg_row_stride), dtype=torch.uint8, device=self.dev),
-                                lens=torch.zeros(k, dtype=torch.int32, device=self.dev), **self._result_tensors(k),
+                                rows=self._alloc((k, self.seg_row_stride), torch.uint8), lens=self._alloc(k, torch.int32),
+                                **self._result_tensors(k),
                                 anchor=self._record_tensor(k, ANCHOR_DT), clip=self._record_tensor(k, CLIP_DT, torch.int32))
             self.split_dev = capi.SplitDev(cap, g["seg"].data_ptr(), g["rows"].data_ptr(), self.seg_row_stride, g["lens"].data_ptr(),
                                            g["best"].data_ptr(), g["store"].data_ptr(), self.store_stride, g["n_ops"].data_ptr(),
                                            g["score"].data_ptr(), g["meta"].data_ptr(), g["meta_r"].data_ptr(),
                                            g["anchor"].data_ptr(), g["clip"].data_ptr())
 
+    def _alloc(self, shape, dtype):
+        """Every buffer this mapper owns comes from here: zeros of the shape (tests override it to place guards around them)."""
+        return self.torch.zeros(shape, dtype=dtype, device=self.dev)
+
     def _record_tensor(self, rows, dt, word=None):
         """Device buffer of `rows` records of dtype dt, as columns of `word` (default: bytes)."""
         word = word or self.torch.uint8
-        return self.torch.zeros((rows, dt.itemsize // word.itemsize), dtype=word, device=self.dev)
+        return self._alloc((rows, dt.itemsize // word.itemsize), word)
 
     def _result_tensors(self, rows):
         """The result buffer set of `rows` reads: what an extension call writes, and best[] in front of it."""
-        i32 = dict(dtype=self.torch.int32, device=self.dev)
+        i32 = self.torch.int32
         return dict(best=self._record_tensor(rows, ENTRY_DT, self.torch.int64),
-                    store=self.torch.zeros((rows, self.store_stride), dtype=self.torch.uint8, device=self.dev),
-                    n_ops=self.torch.zeros(rows, **i32), score=self.torch.zeros(rows, **i32),
-                    meta=self._record_tensor(rows, META_DT), meta_r=self.torch.zeros(rows, **i32))
+                    store=self._alloc((rows, self.store_stride), self.torch.uint8),
+                    n_ops=self._alloc(rows, i32), score=self._alloc(rows, i32),
+                    meta=self._record_tensor(rows, META_DT), meta_r=self._alloc(rows, i32))
 
     def workspace_bytes(self):
         return int(lib.lrm_workspace_bytes(self.ws))
@@ -188,7 +190,7 @@ class DeviceMapper:
                   "lrm_aln_diff_offsets_dev")
             total = int(self.diff_off[n].item())
             if total > self.diff_events.numel():
-                self.diff_events = self.torch.zeros(total, dtype=self.torch.int32, device=self.dev)
+                self.diff_events = self._alloc(total, self.torch.int32)
             check(lib.lrm_aln_diff_dev(self.index.handle, self.store.data_ptr(), self.store_stride, self.n_ops.data_ptr(),
                                        self.score.data_ptr(), self.meta_r.data_ptr(), self.meta.data_ptr(), n, self.diff_off.data_ptr(),
                                        total, self.diff_events.data_ptr(), self._stream()), "lrm_aln_diff_dev")
