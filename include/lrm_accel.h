@@ -702,8 +702,11 @@ typedef struct lrm_secondary_options {
 /* The rival entries of a batch (d_rival: n lrm_entry in device memory): call it behind lrm_seed_batch_mapq_dev on the same
  * workspace and stream, with that call's d_lens, n, p, d_best and d_mapq, BEFORE any other seed stage runs on that workspace
  * -- it walks the survivor lists that call left there.  (The split stage, handed the primary's workspace as ws_seg, is such a
- * stage: lrm_rival_dev / lrm_secondary_batch_dev first, then lrm_split_batch_dev.)  One kernel, asynchronous; it checks what
- * the mapping-quality stage checks. */
+ * stage: lrm_rival_dev / lrm_secondary_batch_dev first, then lrm_split_batch_dev.)  Refused otherwise: every seed stage
+ * stamps the workspace with the d_best and n it ran for and with whether it wrote the deciding phases (a plain
+ * lrm_seed_batch_dev does not), and this call, lrm_secondary_batch_dev and the mapping-quality stage return -1 ("the
+ * workspace did not run the seed stage of this batch with the phase output") before any launch unless d_best and n are the
+ * stamp's.  One kernel, asynchronous; it checks what the mapping-quality stage checks. */
 int lrm_rival_dev(lrm_index *idx, lrm_workspace *ws, const uint32_t *d_lens, uint64_t n, lrm_params p,
                   const lrm_entry *d_best, const lrm_mapq *d_mapq, uint32_t min_hits, uint32_t ratio_pct,
                   lrm_entry *d_rival, void *stream);

@@ -204,7 +204,8 @@ static inline int lrm_rival_options(uint32_t min_hits, uint32_t ratio_pct, uint3
     lrm_set_error("secondary: min_hits %u outside [1, 65535] or ratio_pct %u outside [1, 100]", min_hits, ratio_pct);
     return -1;
 }
-// the rival entries of the batch whose survivor lists are in ws, right behind lrm_launch_mapq
+// the rival entries of the batch whose survivor lists are in ws, right behind lrm_launch_mapq; -1 before any launch if the
+// lists are not those of (d_best, n) with the deciding phases (lrm_seed_stamp_is)
 int lrm_launch_rival(lrm_index *idx, lrm_workspace *ws, const uint32_t *d_lens, uint64_t n, uint32_t seed_len, const lrm_entry *d_best,
                      const lrm_mapq *d_mapq, uint32_t min_hits, uint32_t ratio_pct, lrm_entry *d_rival, void *stream);
 int lrm_launch_secondary(lrm_index *idx, lrm_workspace *ws, const LrmSecArgs &a, const lrm_secondary_dev &out, uint64_t *n_sec,

@@ -251,6 +251,12 @@ struct lrm_workspace {
     uint64_t *d_rec;         // survivor records k | rr << 40, compact per (read, phase): n_max * P * cap_q capacity
     uint32_t *d_recq;        // seed ordinal q of every survivor record
     uint32_t *d_cnt;         // survivors per (read, phase)
+    // whose lists those are: lrm_launch_seed, the one writer of d_rec / d_recq / d_cnt / d_mq_phase, clears the stamp when it
+    // starts and sets it when every launch is queued.  lrm_launch_mapq and lrm_launch_rival walk the lists only for the
+    // best[] and n of the stamp, and only when that call wrote the deciding phases to d_mq_phase (lrm_seed_stamp_is)
+    const lrm_entry *seeded_best;
+    uint64_t seeded_n;
+    int seeded_phase;
     uint64_t *d_kc_key;      // vote kernel: per-workgroup scratch of the keys of multi-pass items (LRM_VOTE_GRID x LRM_VOTE_KC_CAP)
     uint32_t *d_kc_ord;      //              ... and their order keys
     uint64_t *d_redo;        // items the fast vote kernels left to the exact one (n_max * P)
@@ -380,8 +386,13 @@ struct LrmVoteLaunch {
 int lrm_launch_vote(lrm_index *idx, lrm_workspace *ws, const LrmVoteLaunch &v, void *stream);
 // mapping quality (mapq_kernels.hip; docs/GACT_SPEC.md, "Mapping quality"): lrm_mapq_phase_buf before lrm_launch_seed (the
 // deciding phase per read is that call's d_phase_out; the first call on a workspace allocates the n_max bytes),
-// lrm_launch_mapq right behind it on the same stream -- the survivor lists of the workspace are still those of the batch
+// lrm_launch_mapq right behind it on the same stream -- the survivor lists of the workspace are still those of the batch,
+// which the stamp of the workspace says: any other d_best or n, or a seed call without the phase output, is refused (-1)
 uint8_t *lrm_mapq_phase_buf(lrm_workspace *ws);
+// the lists and the deciding phases in ws are those lrm_launch_seed made for best[0 .. n)
+static inline bool lrm_seed_stamp_is(const lrm_workspace *ws, const lrm_entry *d_best, uint64_t n) {
+    return ws->seeded_phase && ws->seeded_best == d_best && ws->seeded_n == n;
+}
 int lrm_launch_mapq(lrm_index *idx, lrm_workspace *ws, const uint32_t *d_lens, uint64_t n, uint32_t seed_len, uint32_t thres,
                     const lrm_entry *d_best, lrm_mapq *d_mapq, void *stream);
 int lrm_wait_event(void *ev);                              // host_pipeline.hip: the sleep-poll every host wait of this library uses

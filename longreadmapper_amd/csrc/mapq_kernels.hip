@@ -137,7 +137,7 @@ int lrm_launch_mapq(lrm_index *idx, lrm_workspace *ws, const uint32_t *d_lens, u
     hipStream_t stream = (hipStream_t) stream_;
     (void) thres;                                        // (the lists hold the survivors 0 < rr < thres already)
     if (n == 0) return 0;
-    if (!ws->d_mq_phase || !ws->d_rec || seed_len != ws->seed_len || n > ws->n_max) {
+    if (!ws->d_mq_phase || !ws->d_rec || seed_len != ws->seed_len || n > ws->n_max || !lrm_seed_stamp_is(ws, d_best, n)) {
         lrm_set_error("mapping quality: the workspace did not run the seed stage of this batch with the phase output");
         return -1;
     }

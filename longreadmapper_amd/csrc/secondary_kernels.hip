@@ -234,7 +234,7 @@ int lrm_launch_rival(lrm_index *idx, lrm_workspace *ws, const uint32_t *d_lens, 
     uint32_t H, pct;
     if (lrm_rival_options(min_hits, ratio_pct, &H, &pct)) return -1;
     if (n == 0) return 0;
-    if (!ws->d_mq_phase || !ws->d_rec || seed_len != ws->seed_len || n > ws->n_max) {
+    if (!ws->d_mq_phase || !ws->d_rec || seed_len != ws->seed_len || n > ws->n_max || !lrm_seed_stamp_is(ws, d_best, n)) {
         lrm_set_error("rival locus: the workspace did not run the seed stage of this batch with the phase output");
         return -1;
     }

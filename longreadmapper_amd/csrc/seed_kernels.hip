@@ -457,6 +457,8 @@ int lrm_launch_seed(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint
                     uint32_t thres, lrm_entry *d_best, const LrmMapTune &mt, void *stream_, uint8_t *d_phase_out) {
     hipStream_t stream = (hipStream_t) stream_;
     if (n == 0) return 0;
+    // from here on the survivor lists are no batch's (a call that fails half-way leaves them so); set again at the end
+    ws->seeded_best = nullptr; ws->seeded_n = 0; ws->seeded_phase = 0;
     const int P = (int) seed_len + 1;
     const uint32_t cap_q = ws->cap_q;
     const uint64_t wpr = ws->words_per_read;
@@ -528,6 +530,8 @@ int lrm_launch_seed(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint
     HIPCHK(hipMemcpyAsync((void *) (ws->h_err + 2), &ws->d_counters->decided_phase0, 8, hipMemcpyDeviceToHost, stream));
     ws->hist_n = n;
     HIPCHK(hipGetLastError());
+    ws->seeded_best = d_best; ws->seeded_n = n;
+    ws->seeded_phase = d_phase_out != nullptr && d_phase_out == ws->d_mq_phase;     // (what mapq and rival read is d_mq_phase)
     return 0;
 }
 

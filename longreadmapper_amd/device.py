@@ -39,7 +39,9 @@ class DeviceMapper:
         alignments"); secondary_results() returns the table and the per-candidate outputs.  sec_cap: room for that many
         candidates (None: n_max, every read); sec_min_hits, sec_ratio_pct: H and pct of the candidate test (0: 8, 50).  Nothing is
         allocated without it.  With split as well: secondary() comes before split() when the split stage runs on this
-        mapper's own workspace (seg_rows=0).
+        mapper's own workspace (seg_rows=0); refused otherwise -- the split stage has seeded its segments there, and
+        secondary() / rival() raise LrmError ("the workspace did not run the seed stage of this batch with the phase output")
+        behind any seed stage on this workspace other than the last seed() of this batch.
         md (implies summary): extend() also makes the difference events of the batch (docs/GACT_SPEC.md, "Difference events
         and MD:Z": lrm_aln_diff_offsets_dev, then lrm_aln_diff_dev into a buffer of the batch's true total -- the one place
         extend() waits for the device: the total crosses to the host); diff_records(n) returns (offsets, events).
