@@ -22,7 +22,8 @@
  *     alnmain.c:574-588
  *   PART 3 result flags, alnmain.c:458-477                      lrm_result_flags (lrm_result_flags_mapq: a real MAPQ)
  *   (no counterpart: the reference prints neither NM nor MD)     lrm_aln_summary_dev, lrm_aln_diff_dev (lrm_md_format: MD:Z)
- *   (no counterpart: the reference has no per-position output)   lrm_pileup_create, lrm_pileup_add_dev, lrm_pileup_read_dev
+ *   (no counterpart: the reference has no per-position output)   lrm_pileup_create, lrm_pileup_add_dev, lrm_pileup_read_dev,
+ *                                                                  lrm_pileup_sites_dev
  *   context_destroy(), accaln.c:7-43                            lrm_index_free
  *   host batch loop over devices, alnmain.c:302-330             lrm_index_upload_multi (+ the same batch calls)
  *   pair_end(), alnmain.c:554-557 (unimplemented, returns -1)   lrm_pair_end
@@ -594,6 +595,46 @@ int lrm_pileup_cols_host(const uint32_t *planes, uint64_t lo, uint64_t hi, uint6
  * the NUL not counted), < 0 when buf (buflen bytes) is too small or an argument is bad. */
 int64_t lrm_pileup_format(const lrm_mta_entry *mta, int mta_len, int seq, uint64_t seq_pos, uint64_t count, const char *content,
                           const lrm_pileup_col *cols, char *buf, int64_t buflen);
+/* PILEUP CALLS (docs/GACT_SPEC.md, "Pileup calls"): the read side of the accumulator for a caller who wants the few
+ * positions where the reads disagree with the text, and one consensus letter per position, instead of 32 bytes per
+ * position.  With c the record of a position, b = content[pos] its text byte, rc the class of b (A, C, G, T or other, case
+ * folded) and allele[k] = x_k + (k == rc ? n_eq : 0) for k in A, C, G, T:
+ *   passes(n)  depth >= min_depth && n >= min_count && 100 * n >= min_pct * depth        (64-bit products)
+ *   kinds      LRM_CALL_SNV: some k != rc has passes(allele[k]); LRM_CALL_DEL: passes(n_del); LRM_CALL_INS: passes(n_ins).
+ *              A position is a SITE iff kinds != 0.
+ *   alt, n_alt the k != rc with the largest allele[k] (a tie: the earlier of A, C, G, T) and its count; '.' when that is 0
+ *   cons       'N' when depth < min_depth or allele[A..T] and n_del are all 0; otherwise the largest of the five, ties to
+ *              the reference class first, then A, C, G, T, then the deletion ('-').  Insertions cannot enter it: the
+ *              accumulator counts where 'I' runs open, not their bases.
+ * Options: a zero field means its default (8, 4, 25); min_pct > 100 or reserved != 0 is refused. */
+#define LRM_CALL_SNV 1u
+#define LRM_CALL_DEL 2u
+#define LRM_CALL_INS 4u
+typedef struct lrm_pileup_call_options { uint32_t min_depth, min_count, min_pct, reserved; } lrm_pileup_call_options;
+typedef struct lrm_pileup_site {       /* 32 bytes */
+    uint64_t pos;                      /* the text position */
+    uint32_t depth, n_ref, n_alt, n_del, n_ins;        /* n_ref = n_eq */
+    uint8_t ref, alt, cons, kinds;     /* ref: the text byte as stored */
+} lrm_pileup_site;
+/* The sites of window positions [first, first + count), first + count <= hi - lo (checked; count < 2^32), in ascending
+ * position into d_sites (cap records in device memory, 16-byte aligned; may be NULL with cap == 0).  *d_n_sites (device
+ * memory, 8-byte aligned) gets the number of sites in the range whether or not they fit; sites from index cap on are not
+ * written.  d_cons, when not NULL, gets count bytes: d_cons[k] = cons of position first + k.  opt NULL: the defaults.
+ * Everything is asynchronous on `stream`: no host wait.  The counters are not modified: add more batches, call again.  The
+ * first call allocates 8 bytes per tile of scratch, which lrm_pileup_bytes counts from then on. */
+int lrm_pileup_sites_dev(lrm_pileup *pl, const lrm_pileup_call_options *opt, uint64_t first, uint64_t count,
+                         lrm_pileup_site *d_sites, uint64_t cap, uint64_t *d_n_sites, uint8_t *d_cons, void *stream);
+/* The same rule on records the caller holds, usable without a GPU: cols[k] and content[k] are the record and the text byte
+ * of text position pos0 + k.  out: cap records (may be NULL with cap == 0); cons: count bytes or NULL.  Returns the number
+ * of sites whether or not they fit, < 0 for refused options or a null argument. */
+int64_t lrm_pileup_sites_host(const lrm_pileup_col *cols, const char *content, uint64_t pos0, uint64_t count,
+                              const lrm_pileup_call_options *opt, lrm_pileup_site *out, uint64_t cap, uint8_t *cons);
+/* Tab-separated text of count sites, one line each, no header: sequence name, 1-based position in it, ref, alt, the kinds
+ * as a subset of the letters SDI, depth, n_ref, n_alt, n_del, n_ins, cons.  The sequence is the entry of mta that holds
+ * pos.  Returns the text length (NUL-terminated, the NUL not counted), < 0 when buf (buflen bytes) is too small or an
+ * argument is bad (a pos in no sequence among them). */
+int64_t lrm_pileup_sites_format(const lrm_mta_entry *mta, int mta_len, const lrm_pileup_site *sites, uint64_t count,
+                                char *buf, int64_t buflen);
 /* Test-only: the first `words` words of the accumulator's allocation (the 8 * (hi - lo) + 1 counter words, then 16 guard
  * words of 0xC5C5C5C5) into host memory; waits for `stream`. */
 int lrm_debug_pileup_raw(lrm_pileup *pl, uint32_t *out, uint64_t words, void *stream);

@@ -70,6 +70,10 @@ SYMBOLS = {
     "lrm_pileup_cols_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p]),
     "lrm_pileup_format": (C.c_int64, [C.POINTER(MtaEntry), C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_int64]),
+    "lrm_pileup_sites_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    "lrm_pileup_sites_host": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "lrm_pileup_sites_format": (C.c_int64, [C.POINTER(MtaEntry), C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int64]),
     "lrm_debug_pileup_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "lrm_aln_summary_host": (None, [C.c_void_p, C.c_int, C.POINTER(AlnSummary)]),
     "lrm_aln_summary_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,

@@ -15,6 +15,7 @@
 #include "extend_stage.h"
 #include "aln_diff_step.h"
 #include "pileup_step.h"
+#include "pileup_call_step.h"
 #include "rival_rule.h"
 
 static thread_local char g_err[512] = "";
@@ -408,7 +409,7 @@ extern "C" int lrm_pileup_cols_host(const uint32_t *planes, uint64_t lo, uint64_
 
 extern "C" void lrm_pileup_free(lrm_pileup *pl) {
     if (!pl) return;
-    if (hipSetDevice(pl->device) == hipSuccess) lrm_dev_free({pl->d_planes, pl->d_tiles});
+    if (hipSetDevice(pl->device) == hipSuccess) lrm_dev_free({pl->d_planes, pl->d_tiles, pl->d_call});
     free(pl);
 }
 
@@ -464,6 +465,44 @@ extern "C" int lrm_pileup_read_dev(lrm_pileup *pl, uint64_t first, uint64_t coun
     if (count == 0) return 0;
     if (lrm_require_device(pl->device)) return -1;
     return lrm_launch_pileup_read(pl, first, count, d_out, stream);
+}
+
+// the call stage (docs/GACT_SPEC.md, "Pileup calls"): the options checked and their zero fields replaced by the defaults
+static int lrm_pileup_call_check(const lrm_pileup_call_options *opt, PileCallRule *rule) {
+    const lrm_pileup_call_options o = opt ? *opt : lrm_pileup_call_options{0, 0, 0, 0};
+    if (o.min_pct > 100u) { lrm_set_error("pileup calls: min_pct %u above 100", o.min_pct); return -1; }
+    if (o.reserved != 0u) { lrm_set_error("pileup calls: lrm_pileup_call_options.reserved is %u, not 0", o.reserved); return -1; }
+    *rule = pile_call_rule(o.min_depth, o.min_count, o.min_pct);
+    return 0;
+}
+
+extern "C" int64_t lrm_pileup_sites_host(const lrm_pileup_col *cols, const char *content, uint64_t pos0, uint64_t count,
+                                         const lrm_pileup_call_options *opt, lrm_pileup_site *out, uint64_t cap, uint8_t *cons) {
+    PileCallRule rule;
+    if (lrm_pileup_call_check(opt, &rule)) return -1;
+    if ((count && (!cols || !content)) || (cap && !out)) { lrm_set_error("null argument"); return -1; }
+    return (int64_t) pile_host_sites(cols, content, pos0, count, rule, out, cap, cons);
+}
+
+extern "C" int lrm_pileup_sites_dev(lrm_pileup *pl, const lrm_pileup_call_options *opt, uint64_t first, uint64_t count,
+                                    lrm_pileup_site *d_sites, uint64_t cap, uint64_t *d_n_sites, uint8_t *d_cons, void *stream) {
+    if (!pl || !d_n_sites || (cap && !d_sites)) { lrm_set_error("null argument"); return -1; }
+    PileCallRule rule;
+    if (lrm_pileup_call_check(opt, &rule)) return -1;
+    if (first > pl->W || count > pl->W - first) { lrm_set_error("pileup: positions [%llu, +%llu) outside a window of %llu", (unsigned long long) first, (unsigned long long) count, (unsigned long long) pl->W); return -1; }
+    if (count > 0xFFFFFFFFull) { lrm_set_error("pileup calls: %llu positions in one call (site ranks are 32-bit: at most 2^32 - 1)", (unsigned long long) count); return -1; }
+    if ((uintptr_t) d_sites & 15u) { lrm_set_error("pileup sites must be 16-byte aligned"); return -1; }
+    if ((uintptr_t) d_n_sites & 7u) { lrm_set_error("the pileup site count must be 8-byte aligned"); return -1; }
+    if (lrm_require_device(pl->device)) return -1;
+    if (count == 0) {                                                  // no tile holds a position: the total is 0
+        HIPCHK(hipMemsetAsync(d_n_sites, 0, 8, (hipStream_t) stream));
+        return 0;
+    }
+    if (!pl->d_call) {                                                 // the stage's scratch, on the first call that asks
+        const LrmDevAlloc table[] = {{(void **) &pl->d_call, 8ull * pl->n_tiles}};
+        if (lrm_dev_alloc_table(table, "pileup call bytes", &pl->bytes)) return -1;
+    }
+    return lrm_launch_pileup_sites(pl, rule, first, count, d_sites, cap, d_n_sites, d_cons, stream);
 }
 
 extern "C" int lrm_debug_pileup_raw(lrm_pileup *pl, uint32_t *out, uint64_t words, void *stream) {

@@ -355,14 +355,16 @@ int lrm_launch_aln_diff(const uint8_t *d_store, uint64_t pitch, const int32_t *d
 int lrm_launch_aln_diff_offsets(const lrm_aln_summary *d_sum, uint64_t rows, uint64_t *d_off, void *stream);
 // the pileup (pileup_kernels.hip; docs/GACT_SPEC.md, "Pileup").  An accumulator: the counter planes of pileup_step.h over
 // the window [lo, hi) (W = hi - lo positions) with LRM_PILEUP_GUARD_WORDS guard words behind them, and two words per tile
-// of read-back scratch (the tiles' sums of the difference plane, then their exclusive prefix sums)
+// of read-back scratch (the tiles' sums of the difference plane, then their exclusive prefix sums).  d_call: two more
+// words per tile for the call stage (the tiles' site counts, then their exclusive prefix sums), allocated by the first
+// lrm_pileup_sites_dev and booked into `bytes` then.
 #define LRM_PILEUP_GUARD_WORDS 16u
 #define LRM_PILEUP_GUARD 0xC5C5C5C5u
 struct lrm_pileup {
     lrm_index *idx;
     int device;
     uint64_t lo, hi, W, n_tiles, bytes;
-    uint32_t *d_planes, *d_tiles;
+    uint32_t *d_planes, *d_tiles, *d_call;
 };
 // the same rows as the summary and the events, plus the read rows (d_reads + row * stride, d_lens) the extension left; a
 // row without an alignment, or with d_mapq[row].mapq < min_mapq (d_mapq null: no filter), adds nothing
@@ -371,6 +373,11 @@ int lrm_launch_pileup_add(const lrm_pileup *pl, const uint8_t *d_reads, uint64_t
                           uint64_t rows, const lrm_mapq *d_mapq, uint32_t min_mapq, void *stream);
 // the records of window positions [first, first + count), count > 0: tile sums, their scan, the records
 int lrm_launch_pileup_read(const lrm_pileup *pl, uint64_t first, uint64_t count, lrm_pileup_col *d_out, void *stream);
+// the call stage over the same positions (docs/GACT_SPEC.md, "Pileup calls"), 0 < count < 2^32, pl->d_call allocated: tile
+// sums and their scan as the read-back makes them, the tiles' site counts [and the cons bytes], their scan, the site table
+struct PileCallRule;
+int lrm_launch_pileup_sites(const lrm_pileup *pl, const PileCallRule &rule, uint64_t first, uint64_t count, lrm_pileup_site *d_sites,
+                            uint64_t cap, uint64_t *d_n_sites, uint8_t *d_cons, void *stream);
 int lrm_launch_seed(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint64_t stride,
                     const uint32_t *d_lens, uint64_t n, uint32_t seed_len,
                     uint32_t thres, lrm_entry *d_best, const LrmMapTune &mt, void *stream, uint8_t *d_phase_out = nullptr);

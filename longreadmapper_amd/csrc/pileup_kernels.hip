@@ -3,10 +3,13 @@
 // byte of ops read per column -- whose atomics are proportional to the DIFFERENCES, not to the columns: one add per 'X',
 // 'D' and opening 'I' column into planar event arrays, and two adds per read into a difference plane of the depth.  The
 // read-back turns the difference plane into depths by a tiled prefix sum and writes the 32-byte records; it leaves the
-// planes as they are.
+// planes as they are.  The call stage (docs/GACT_SPEC.md, "Pileup calls") reads the same planes and the text: the sites --
+// the positions where the reads disagree with the text -- compacted into a table by count, scan, write at the prefix sum
+// (the idiom of compact_rows.h: no atomics, the same table whatever the scheduling), and one consensus byte per position.
 #include <hip/hip_runtime.h>
 #include "lrm_hip_util.h"
 #include "pileup_step.h"
+#include "pileup_call_step.h"
 
 namespace {
 
@@ -187,6 +190,94 @@ __global__ __launch_bounds__(256) void pileup_cols_kernel(const uint32_t *__rest
     }
 }
 
+// ---- the call stage ----
+typedef uint32_t pile_u32x4 __attribute__((ext_vector_type(4)));
+// one position inside the requested range: its seven event words, its text byte (text: content + lo), the rule
+struct PilePos { uint32_t n_eq, n_del, n_ins, byte; PileCall call; };
+__device__ __forceinline__ PilePos pile_call_at(const uint32_t *__restrict__ planes, uint64_t W, uint64_t g, uint32_t depth,
+                                                const uint8_t *__restrict__ text, const PileCallRule &rule) {
+    uint32_t e[LRM_PILEUP_PLANES];
+#pragma unroll
+    for (uint32_t k = 0; k < LRM_PILEUP_PLANES; ++k) e[k] = planes[LRM_PILEUP_EVENT_PLANE(W, k) + g];
+    const uint32_t x_all = e[LRM_PILEUP_X_A] + e[LRM_PILEUP_X_C] + e[LRM_PILEUP_X_G] + e[LRM_PILEUP_X_T] + e[LRM_PILEUP_X_OTHER];
+    PilePos p;
+    p.n_eq = depth - x_all - e[LRM_PILEUP_DEL];
+    p.n_del = e[LRM_PILEUP_DEL];
+    p.n_ins = e[LRM_PILEUP_INS];
+    p.byte = text[g];
+    p.call = pile_call(rule, depth, p.n_eq, e[LRM_PILEUP_X_A], e[LRM_PILEUP_X_C], e[LRM_PILEUP_X_G], e[LRM_PILEUP_X_T], p.n_del, p.n_ins, p.byte);
+    return p;
+}
+
+// calls 1: one workgroup per tile that holds a requested position (tile0: the tile of `first`).  The tile's depth is
+// rescanned as pileup_cols_kernel rescans it; a position inside the range is evaluated, its cons byte written when the
+// caller asked (a byte store at cons + (g - first): `first` is arbitrary, so nothing wider is aligned at the range's ends,
+// and nothing outside cons[0 .. count) is touched); the tile's number of sites goes to tile_sites[blockIdx.x].
+__global__ __launch_bounds__(256) void pileup_call_kernel(const uint32_t *__restrict__ planes, uint64_t W, const uint32_t *__restrict__ tile_base,
+                                                          uint64_t tile0, uint64_t first, uint64_t count, const uint8_t *__restrict__ text,
+                                                          PileCallRule rule, uint8_t *__restrict__ cons, uint32_t *__restrict__ tile_sites) {
+    __shared__ uint32_t lds[4];
+    const uint64_t tile = tile0 + blockIdx.x;
+    uint32_t running = tile_base[tile], mine = 0;
+#pragma unroll 1
+    for (uint32_t j = 0; j < LRM_PILEUP_TILE / 256u; ++j) {
+        const uint64_t g = tile * LRM_PILEUP_TILE + j * 256u + threadIdx.x;
+        uint32_t all;
+        const uint32_t depth = running + block256_incl_scan(g < W ? planes[g] : 0u, lds, all);
+        running += all;
+        if (g < first || g - first >= count) continue;               // (first + count <= W: g < W here)
+        const PilePos p = pile_call_at(planes, W, g, depth, text, rule);
+        if (cons) cons[g - first] = p.call.cons;
+        mine += p.call.kinds ? 1u : 0u;
+    }
+    uint32_t all;
+    (void) block256_incl_scan(mine, lds, all);
+    if (threadIdx.x == 0) tile_sites[blockIdx.x] = all;
+}
+
+// calls 2 is pileup_tile_scan_kernel over the tiles' site counts.  calls 3: one workgroup per tile again.  The last one
+// writes the total -- its own rank plus its own count -- as 64 bits.  A tile without a site, or whose first site already
+// lies at or behind cap, leaves after its scalar loads.  Otherwise the tile is evaluated again from the planes (no
+// per-position array between the two kernels: sites are few, so few tiles come back here, and a kinds byte per position
+// would be W more bytes written and kept for every call); the sites of a round are ranked by a block scan of the site flag,
+// the running rank carried as the depth is, and a record goes to sites[rank] with two aligned 16-byte stores when rank < cap.
+__global__ __launch_bounds__(256) void pileup_sites_kernel(const uint32_t *__restrict__ planes, uint64_t W, const uint32_t *__restrict__ tile_base,
+                                                           uint64_t tile0, uint64_t first, uint64_t count, uint64_t lo,
+                                                           const uint8_t *__restrict__ text, PileCallRule rule,
+                                                           const uint32_t *__restrict__ tile_sites, const uint32_t *__restrict__ tile_rank,
+                                                           lrm_pileup_site *__restrict__ sites, uint64_t cap, uint64_t *__restrict__ n_sites) {
+    __shared__ uint32_t lds[4];
+    const uint32_t n_here = tile_sites[blockIdx.x];
+    uint64_t rank = tile_rank[blockIdx.x];
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *n_sites = rank + n_here;
+    if (n_here == 0 || rank >= cap) return;
+    const uint64_t tile = tile0 + blockIdx.x;
+    uint32_t running = tile_base[tile];
+#pragma unroll 1
+    for (uint32_t j = 0; j < LRM_PILEUP_TILE / 256u; ++j) {
+        const uint64_t g = tile * LRM_PILEUP_TILE + j * 256u + threadIdx.x;
+        uint32_t all;
+        const uint32_t depth = running + block256_incl_scan(g < W ? planes[g] : 0u, lds, all);
+        running += all;
+        PilePos p = {};
+        if (g >= first && g - first < count) p = pile_call_at(planes, W, g, depth, text, rule);
+        const uint32_t flag = p.call.kinds ? 1u : 0u;
+        const uint64_t at = rank + (block256_incl_scan(flag, lds, all) - flag);
+        rank += all;
+        if (flag && at < cap) {
+            uint32_t w[8];
+            pile_call_site_words(p.call, lo + g, depth, p.n_eq, p.n_del, p.n_ins, p.byte, w);
+            // (each half pinned in four consecutive registers: left alone, the compiler merges the two stores and cuts the
+            // 32 bytes at the 64-bit position instead, 8 + 12 + 12)
+            pile_u32x4 h0 = {w[0], w[1], w[2], w[3]}, h1 = {w[4], w[5], w[6], w[7]};
+            asm volatile("" : "+v"(h0), "+v"(h1));
+            pile_u32x4 *o = reinterpret_cast<pile_u32x4 *>(sites + at);
+            o[0] = h0;
+            o[1] = h1;
+        }
+    }
+}
+
 }  // namespace
 
 int lrm_launch_pileup_add(const lrm_pileup *pl, const uint8_t *d_reads, uint64_t stride, const uint32_t *d_lens, const uint8_t *d_store,
@@ -210,6 +301,24 @@ int lrm_launch_pileup_read(const lrm_pileup *pl, uint64_t first, uint64_t count,
     hipLaunchKernelGGL(pileup_tile_sums_kernel, dim3(grid_sums), dim3(256), 0, (hipStream_t) stream, pl->d_planes, pl->W, sums);
     hipLaunchKernelGGL(pileup_tile_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t) stream, sums, tile_end, bases);
     hipLaunchKernelGGL(pileup_cols_kernel, dim3(grid_cols), dim3(256), 0, (hipStream_t) stream, pl->d_planes, pl->W, bases, tile0, first, count, d_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int lrm_launch_pileup_sites(const lrm_pileup *pl, const PileCallRule &rule, uint64_t first, uint64_t count, lrm_pileup_site *d_sites,
+                            uint64_t cap, uint64_t *d_n_sites, uint8_t *d_cons, void *stream) {
+    const uint64_t tile0 = first / LRM_PILEUP_TILE, tile_end = (first + count + LRM_PILEUP_TILE - 1) / LRM_PILEUP_TILE;
+    uint32_t grid_sums, grid_call;
+    if (lrm_grid_1d(tile_end, "pileup calls", &grid_sums) || lrm_grid_1d(tile_end - tile0, "pileup calls", &grid_call)) return -1;
+    uint32_t *sums = pl->d_tiles, *bases = pl->d_tiles + pl->n_tiles, *n_here = pl->d_call, *rank = pl->d_call + pl->n_tiles;
+    const uint8_t *text = (const uint8_t *) pl->idx->view.content + pl->lo;
+    const hipStream_t st = (hipStream_t) stream;
+    hipLaunchKernelGGL(pileup_tile_sums_kernel, dim3(grid_sums), dim3(256), 0, st, pl->d_planes, pl->W, sums);
+    hipLaunchKernelGGL(pileup_tile_scan_kernel, dim3(1), dim3(1024), 0, st, sums, tile_end, bases);
+    hipLaunchKernelGGL(pileup_call_kernel, dim3(grid_call), dim3(256), 0, st, pl->d_planes, pl->W, bases, tile0, first, count, text, rule, d_cons, n_here);
+    hipLaunchKernelGGL(pileup_tile_scan_kernel, dim3(1), dim3(1024), 0, st, n_here, (uint64_t) grid_call, rank);
+    hipLaunchKernelGGL(pileup_sites_kernel, dim3(grid_call), dim3(256), 0, st, pl->d_planes, pl->W, bases, tile0, first, count, pl->lo, text, rule,
+                       n_here, rank, d_sites, cap, d_n_sites);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -1,4 +1,4 @@
-// pileup_text.cpp -- pileup records as text (lrm_pileup_format, include/lrm_accel.h; docs/GACT_SPEC.md, "Pileup").  Host-side
+// pileup_text.cpp -- pileup records as text (lrm_pileup_format, lrm_pileup_sites_format, include/lrm_accel.h; docs/GACT_SPEC.md, "Pileup", "Pileup calls").  Host-side
 // C++; the numbers go through put_uint of sam_text.h.
 #include <cstdint>
 #include <cstring>
@@ -36,6 +36,52 @@ extern "C" int64_t lrm_pileup_format(const lrm_mta_entry *mta, int mta_len, int 
     for (uint64_t k = 0; k < count; ++k) {
         if ((uint64_t) (buflen - at) < room + 1) { lrm_set_error("pileup text: buffer of %lld bytes too small", (long long) buflen); return -2; }   // (+1: the NUL)
         at += pileup_put_line(buf + at, name, name_len, seq_pos + k + 1, content[m.offset + seq_pos + k], cols[k]);
+    }
+    buf[at] = '\0';
+    return at;
+}
+
+int pileup_put_site_line(char *dst, const char *name, uint64_t name_len, uint64_t pos1, const lrm_pileup_site &s) {
+    char *p = dst;
+    memcpy(p, name, name_len);
+    p += name_len;
+    *p++ = '\t';
+    p += put_uint(p, pos1);
+    *p++ = '\t';
+    *p++ = (char) s.ref;
+    *p++ = '\t';
+    *p++ = (char) s.alt;
+    *p++ = '\t';
+    if (s.kinds & LRM_CALL_SNV) *p++ = 'S';
+    if (s.kinds & LRM_CALL_DEL) *p++ = 'D';
+    if (s.kinds & LRM_CALL_INS) *p++ = 'I';
+    for (const uint32_t v : {s.depth, s.n_ref, s.n_alt, s.n_del, s.n_ins}) {
+        *p++ = '\t';
+        p += put_uint(p, v);
+    }
+    *p++ = '\t';
+    *p++ = (char) s.cons;
+    *p++ = '\n';
+    return (int) (p - dst);
+}
+
+extern "C" int64_t lrm_pileup_sites_format(const lrm_mta_entry *mta, int mta_len, const lrm_pileup_site *sites, uint64_t count, char *buf,
+                                           int64_t buflen) {
+    if (!mta || mta_len <= 0 || !buf || buflen <= 0 || (count && !sites)) { lrm_set_error("null argument"); return -1; }
+    int64_t at = 0;
+    int seq = 0;                                                       // sites come in ascending position: start at the last sequence found
+    for (uint64_t k = 0; k < count; ++k) {
+        const uint64_t pos = sites[k].pos;
+        int tried = 0;
+        while (tried < mta_len && !(pos >= mta[seq].offset && pos - mta[seq].offset < mta[seq].seq_len)) {
+            seq = seq + 1 < mta_len ? seq + 1 : 0;
+            ++tried;
+        }
+        if (tried == mta_len) { lrm_set_error("pileup sites text: position %llu lies in no sequence", (unsigned long long) pos); return -1; }
+        const lrm_mta_entry &m = mta[seq];
+        const uint64_t name_len = m.name ? m.name_len : 0;
+        if ((uint64_t) (buflen - at) < pileup_site_line_room(name_len) + 1) { lrm_set_error("pileup sites text: buffer of %lld bytes too small", (long long) buflen); return -2; }   // (+1: the NUL)
+        at += pileup_put_site_line(buf + at, m.name ? m.name : "", name_len, pos - m.offset + 1, sites[k]);
     }
     buf[at] = '\0';
     return at;

@@ -212,6 +212,31 @@ class DeviceMapper:
         check(lib.lrm_pileup_read_dev(self.pileup, first, count, out.data_ptr(), self._stream()), "lrm_pileup_read_dev")
         return _records(out[:count], capi.PILEUP_COL_DT)
 
+    def pileup_sites(self, first=None, count=None, cap=None, min_depth=0, min_count=0, min_pct=0, consensus=False):
+        """The call stage over the accumulator (lrm_pileup_sites_dev; docs/GACT_SPEC.md, "Pileup calls") on window positions
+        first .. first + count - 1 (default: the whole window): -> (sites, total, cons).  sites: the PILEUP_SITE_DT records of
+        the positions where the reads disagree with the text, ascending; total: their number; cons: with consensus=True one
+        letter per position (uint8), else None.  A zero option means its default (8, 4, 25).  cap: the room of the first
+        table (default: 4096 + count // 256 records); when the sites did not fit, the stage runs once more with cap = total
+        -- the counters do not move, so the second call is the same question."""
+        assert self.pileup is not None
+        first = 0 if first is None else first
+        count = self.pileup_window[1] - self.pileup_window[0] - first if count is None else count
+        cap = min(count, 4096 + count // 256) if cap is None else cap
+        opt = capi.PileupCallOptions(min_depth, min_count, min_pct, 0)
+        d_total = self._alloc(1, self.torch.int64)
+        d_cons = self._alloc(max(count, 1), self.torch.uint8) if consensus else None
+        while True:
+            d_sites = self._record_tensor(max(cap, 1), capi.PILEUP_SITE_DT, self.torch.int32)
+            check(lib.lrm_pileup_sites_dev(self.pileup, C.byref(opt), first, count, d_sites.data_ptr() if cap else None, cap, d_total.data_ptr(),
+                                           d_cons.data_ptr() if consensus else None, self._stream()), "lrm_pileup_sites_dev")
+            total = int(d_total.cpu()[0])
+            if total <= cap:
+                break
+            cap = total
+        sites = _records(d_sites[:total], capi.PILEUP_SITE_DT)
+        return sites, total, (d_cons[:count].cpu().numpy() if consensus else None)
+
     def pileup_reset(self):
         assert self.pileup is not None
         check(lib.lrm_pileup_reset(self.pileup, self._stream()), "lrm_pileup_reset")

@@ -190,7 +190,16 @@ class _PileupCol(C.Structure):         # docs/GACT_SPEC.md, "Pileup"; compared w
     _fields_ = [(name, C.c_uint32) for name in ("depth", "n_eq", "x_a", "x_c", "x_g", "x_t", "n_del", "n_ins")]
 
 
-PileupCol = _PileupCol
+class _PileupCallOptions(C.Structure):     # docs/GACT_SPEC.md, "Pileup calls"; a zero field means its default
+    _fields_ = [(name, C.c_uint32) for name in ("min_depth", "min_count", "min_pct", "reserved")]
+
+
+class _PileupSite(C.Structure):
+    _fields_ = [("pos", C.c_uint64)] + [(name, C.c_uint32) for name in ("depth", "n_ref", "n_alt", "n_del", "n_ins")] + [
+        (name, C.c_uint8) for name in ("ref", "alt", "cons", "kinds")]
+
+
+PileupCol, PileupCallOptions, PileupSite = _PileupCol, _PileupCallOptions, _PileupSite
 
 
 class GactTable(C.Structure):          # host pointers
@@ -233,7 +242,8 @@ MAP_OPTION_FIELDS = _MAP_OPTION_WORDS + ("split", "split_min_len")
 # tests/test_header_agreement.py compares exactly the 25 structs of STRUCTS with the headers; the structs that came after it
 # are listed here and compared in the same way by the tests of their feature (tests/test_aln_diff_cpu.py)
 LATER_STRUCTS = {BatchDiff: "lrm_batch_diff", Secondary: "lrm_secondary", SecondaryOptions: "lrm_secondary_options",
-                 SecondaryDev: "lrm_secondary_dev", SecondaryOut: "lrm_secondary_out", PileupCol: "lrm_pileup_col"}
+                 SecondaryDev: "lrm_secondary_dev", SecondaryOut: "lrm_secondary_out", PileupCol: "lrm_pileup_col",
+                 PileupCallOptions: "lrm_pileup_call_options", PileupSite: "lrm_pileup_site"}
 
 # the records that cross the boundary as arrays
 ENTRY_DT, META_DT, CIGAR_DT = dtype_of(Entry), dtype_of(SeqMeta), dtype_of(Cigar)
@@ -241,6 +251,7 @@ ANCHOR_DT, CLIP_DT, SEGMENT_DT = dtype_of(Anchor), dtype_of(Clip), dtype_of(Segm
 MAPQ_DT, SUMMARY_DT = dtype_of(Mapq), dtype_of(AlnSummary)
 SECONDARY_DT = dtype_of(Secondary)
 PILEUP_COL_DT = dtype_of(PileupCol)
+PILEUP_SITE_DT = dtype_of(PileupSite)
 
 N_KERNELS = 9
 MAPQ_SLOTS, MAPQ_OVERFLOW = 4096, 1    # lrm_mapq.flags
@@ -251,6 +262,7 @@ DIFF_X, DIFF_D_OPEN, DIFF_D_MORE = 0, 1, 2        # bits 8-9 of a difference eve
 DIFF_NO_ROOM = 2**64 - 1               # lrm_batch_diff.off_out of a read whose group found no room
 PILEUP_TILE = 2048                     # positions per workgroup of the pileup read-back
 PILEUP_PLANES = ("x_a", "x_c", "x_g", "x_t", "x_other", "n_del", "n_ins")     # the event planes behind the depth's difference plane
+CALL_SNV, CALL_DEL, CALL_INS = 1, 2, 4   # lrm_pileup_site.kinds
 ANCHOR_ANCHORED, ANCHOR_FALLBACK, ANCHOR_NO_LEFT, ANCHOR_LEFT_CLIPPED, ANCHOR_RIGHT_CLIPPED = 1, 2, 4, 8, 16
 ANCHOR_SOFT_LEFT, ANCHOR_SOFT_RIGHT = 32, 64      # end clipping (lrm_map_options.clip)
 ANCHOR_DIAGS = 64
@@ -259,7 +271,8 @@ DEFAULT_GACT = (320, 120, 128)
 # the header's name of every constant above
 CONSTANTS = dict(LRM_N_KERNELS=N_KERNELS, LRM_MAPQ_SLOTS=MAPQ_SLOTS, LRM_MAPQ_OVERFLOW=MAPQ_OVERFLOW, LRM_SEG_RIGHT=SEG_RIGHT,
                  LRM_SEG_ALIGNED=SEG_ALIGNED, LRM_SEC_ALIGNED=SEC_ALIGNED, LRM_SEC_DUPLICATE=SEC_DUPLICATE, LRM_SPLIT_MIN_DEFAULT=SPLIT_MIN_DEFAULT, LRM_DIFF_X=DIFF_X, LRM_DIFF_D_OPEN=DIFF_D_OPEN,
-                 LRM_DIFF_D_MORE=DIFF_D_MORE, LRM_PILEUP_TILE=PILEUP_TILE, LRM_ANCHOR_ANCHORED=ANCHOR_ANCHORED,
+                 LRM_DIFF_D_MORE=DIFF_D_MORE, LRM_PILEUP_TILE=PILEUP_TILE, LRM_CALL_SNV=CALL_SNV, LRM_CALL_DEL=CALL_DEL, LRM_CALL_INS=CALL_INS,
+                 LRM_ANCHOR_ANCHORED=ANCHOR_ANCHORED,
                  LRM_ANCHOR_FALLBACK=ANCHOR_FALLBACK, LRM_ANCHOR_NO_LEFT=ANCHOR_NO_LEFT, LRM_ANCHOR_LEFT_CLIPPED=ANCHOR_LEFT_CLIPPED,
                  LRM_ANCHOR_RIGHT_CLIPPED=ANCHOR_RIGHT_CLIPPED, LRM_ANCHOR_SOFT_LEFT=ANCHOR_SOFT_LEFT,
                  LRM_ANCHOR_SOFT_RIGHT=ANCHOR_SOFT_RIGHT, LRM_ANCHOR_DIAGS=ANCHOR_DIAGS, LRM_GACT_T_DEFAULT=DEFAULT_GACT[0],
@@ -289,7 +302,7 @@ def units16(nbytes):
 
 # what capi re-exports: the pointer types, the structs, the record dtypes and the header's constants -- not the helpers
 __all__ = ["u8p", "u32p", "u64p", "i32p", "STRUCTS", "LATER_STRUCTS", "BatchDiff", "Secondary", "SecondaryOptions", "SecondaryDev", "SecondaryOut",
-           "SECONDARY_DT", "PileupCol", "PILEUP_COL_DT", "PILEUP_TILE", "PILEUP_PLANES", "SEC_ALIGNED", "SEC_DUPLICATE", "MAP_OPTION_FIELDS", "CONSTANTS", "BS_COUNTERS", *(s.__name__ for s in STRUCTS),
+           "SECONDARY_DT", "PileupCol", "PILEUP_COL_DT", "PileupCallOptions", "PileupSite", "PILEUP_SITE_DT", "CALL_SNV", "CALL_DEL", "CALL_INS", "PILEUP_TILE", "PILEUP_PLANES", "SEC_ALIGNED", "SEC_DUPLICATE", "MAP_OPTION_FIELDS", "CONSTANTS", "BS_COUNTERS", *(s.__name__ for s in STRUCTS),
            "ENTRY_DT", "META_DT", "CIGAR_DT", "ANCHOR_DT", "CLIP_DT", "SEGMENT_DT", "MAPQ_DT", "SUMMARY_DT", "N_KERNELS", "MAPQ_SLOTS",
            "MAPQ_OVERFLOW", "SEG_RIGHT", "SEG_ALIGNED", "SPLIT_MIN_DEFAULT", "DIFF_X", "DIFF_D_OPEN", "DIFF_D_MORE", "DIFF_NO_ROOM", "ANCHOR_ANCHORED", "ANCHOR_FALLBACK", "ANCHOR_NO_LEFT",
            "ANCHOR_LEFT_CLIPPED", "ANCHOR_RIGHT_CLIPPED", "ANCHOR_SOFT_LEFT", "ANCHOR_SOFT_RIGHT", "ANCHOR_DIAGS"]

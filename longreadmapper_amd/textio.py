@@ -186,6 +186,42 @@ def write_pileup(path, host, cols, lo, chunk=1 << 16):
     return lines
 
 
+def sites_text(host, sites):
+    """lrm_pileup_sites_format: one line per PILEUP_SITE_DT record (DeviceMapper.pileup_sites()) -- sequence name, 1-based
+    position, ref, alt, the kinds as letters of SDI, depth, n_ref, n_alt, n_del, n_ins, cons."""
+    sites = np.ascontiguousarray(sites, dtype=capi.PILEUP_SITE_DT)
+    longest = max((int(host.h.mta[s].name_len) for s in range(host.mta_len)), default=0)
+    room = (longest + 96) * len(sites) + 1
+    buf = C.create_string_buffer(room)
+    k = lib.lrm_pileup_sites_format(host.h.mta, host.mta_len, sites.ctypes.data if len(sites) else None, len(sites), buf, room)
+    if k < 0:
+        raise capi.failure("lrm_pileup_sites_format", rc=k)
+    return buf.raw[:k]
+
+
+def write_sites(path, host, sites, chunk=1 << 16):
+    """The site table as text, no header -> the number of lines."""
+    with open(path, "wb") as f:
+        for p in range(0, len(sites), chunk):
+            f.write(sites_text(host, sites[p:p + chunk]))
+    return len(sites)
+
+
+def write_consensus(path, host, s, cons, lo):
+    """The consensus of sequence s of a HostIndex as FASTA: cons[k] is the letter of text position lo + k
+    (DeviceMapper.pileup_sites(consensus=True) of a window that starts at lo) and has to cover the sequence
+    (index.text_window).  Deleted positions ('-') are dropped; 60 columns a line.  -> the number of bases written."""
+    off, n = int(host.h.mta[s].offset), int(host.h.mta[s].seq_len)
+    assert lo <= off and off + n <= lo + len(cons), "the consensus does not cover the sequence"
+    letters = np.ascontiguousarray(cons, dtype=np.uint8)[off - lo:off - lo + n]
+    letters = letters[letters != ord("-")].tobytes()
+    with open(path, "wb") as f:
+        f.write(b">" + host.h.mta[s].name[:int(host.h.mta[s].name_len)] + b"\n")
+        for p in range(0, len(letters), 60):
+            f.write(letters[p:p + 60] + b"\n")
+    return len(letters)
+
+
 def accaln(genome, reads, out, batch_size, seed_len=20, thres=300, gact=(0, 0, 0), device=0, rg_id=1, options=None, mapq=0, paf=False, md=False,
            secondary=None):
     """secondary: an lrm_secondary_options (capi.SecondaryOptions) -- lrm_accaln_secondary: the flow of lrm_accaln_mapq plus a FLAG

@@ -2,7 +2,9 @@
 E. coli-sized text with planted repeat families) is seeded and extended once through DeviceMapper, so that its op rows sit in
 HBM; the window is the whole text.  Then, with events on the stream, a warm-up and REPEATS timed launches each of
 pileup_add_kernel, of the read-back of the whole window (tile sums, their scan, the records), and -- as yardsticks of the same
-stream shape -- of aln_diff_kernel and aln_summary_kernel.  Printed: ms per Gbp of reads (mean, min, max), the number of
+stream shape -- of aln_diff_kernel and aln_summary_kernel; next to the read-back, in the same process, the call stage
+(docs/GACT_SPEC.md, "Pileup calls": lrm_pileup_sites_dev over the whole window, with and without the cons bytes) and the bytes
+each path would bring down the link.  Printed: ms per Gbp of reads (mean, min, max), the number of
 atomic adds of one pileup_add launch (from the accumulator itself) and the adds per second at the fastest launch.
     python tools/pileup_probe.py       PROBE_READS / PROBE_LEN / PROBE_REF scale it down, PROBE_REPEATS (default 10)"""
 import ctypes as C
@@ -78,6 +80,22 @@ timed("pileup_add_kernel", lambda: check(lib.lrm_pileup_add_dev(
     dm.score.data_ptr(), dm.meta_r.data_ptr(), dm.meta.data_ptr(), n, None, 0, stream), "lrm_pileup_add_dev"), per=(adds, "adds"))
 timed("pileup read-back, whole window", lambda: check(lib.lrm_pileup_read_dev(dm.pileup, 0, W, d_out.data_ptr(), stream), "lrm_pileup_read_dev"),
       per=(64 * W, "bytes (32 read, 32 written per position)"))
+# the call stage over the same window: the site table and the count word, with and without one cons byte per position
+SITE_CAP = 1 << 20
+d_sites = torch.zeros((SITE_CAP, 8), dtype=torch.int32, device="cuda")
+d_n_sites = torch.zeros(1, dtype=torch.int64, device="cuda")
+d_cons = torch.zeros(W, dtype=torch.uint8, device="cuda")
+for what, cons in (("pileup calls, whole window, sites only", None), ("pileup calls, whole window, sites + cons bytes", d_cons.data_ptr())):
+    timed(what, lambda cons=cons: check(lib.lrm_pileup_sites_dev(dm.pileup, None, 0, W, d_sites.data_ptr(), SITE_CAP, d_n_sites.data_ptr(), cons, stream),
+                                        "lrm_pileup_sites_dev"))
+n_sites = int(d_n_sites.cpu()[0])
+kinds = d_sites[:min(n_sites, SITE_CAP), 7].cpu().numpy().view(np.uint32) >> 24
+letters = np.bincount(d_cons.cpu().numpy(), minlength=256)
+print("  %d sites under the default options (SNV %d, DEL %d, INS %d; table of %d records); cons letters: %s" %
+      (n_sites, int((kinds & 1 != 0).sum()), int((kinds & 2 != 0).sum()), int((kinds & 4 != 0).sum()), SITE_CAP,
+       ", ".join("%s %d" % (ch, letters[ord(ch)]) for ch in "ACGTN-")), flush=True)
+print("  down the link: the records %.1f MB; the site table %.3f MB + 8 bytes; the cons bytes %.1f MB" %
+      (32 * W / 1e6, 32 * min(n_sites, SITE_CAP) / 1e6, W / 1e6), flush=True)
 timed("aln_diff_kernel", lambda: check(lib.lrm_aln_diff_dev(
     di.handle, dm.store.data_ptr(), dm.store_stride, dm.n_ops.data_ptr(), dm.score.data_ptr(), dm.meta_r.data_ptr(), dm.meta.data_ptr(), n,
     dm.diff_off.data_ptr(), total, dm.diff_events.data_ptr(), stream), "lrm_aln_diff_dev"))
