@@ -1,48 +1,19 @@
 // aln_diff_step.h -- the per-word step of the difference events (docs/GACT_SPEC.md, "Difference events and MD:Z"): from the
 // byte masks of four op bytes to their event words.  Read by aln_diff_kernels.hip (a lane's 16 columns are four such words)
-// and, as plain C++, by lrm_aln_diff_host (lrm_api.hip): the host rule and the CPU tests run the kernel's own source.
+// and, as plain C++, by the host rule below (lrm_aln_diff_host): the host rule and the CPU tests run the kernel's own source.
 #pragma once
 #include <stdint.h>
 #include "../../include/lrm_accel.h"      // LRM_DIFF_X / _D_OPEN / _D_MORE: the kinds of an event word
-
-#if defined(__HIPCC__)
-#define LRM_DIFF_FN __host__ __device__ __forceinline__
-#else
-#define LRM_DIFF_FN inline
-#endif
+#include "op_rows.h"                      // the byte masks, a byte out of four words, the walk of a row on the host
 
 #define LRM_DIFF_E_SHIFT 10          // bits 10-31: '=' columns before the event
 #define LRM_DIFF_MAX_STRIDE (1u << 22)
-
-// 0x80 in every byte of w that equals c, 0 in every other: the EXACT zero-byte test on w ^ cccc (the cheaper form,
-// (t - 0x01010101) & ~t & 0x80808080, lets a borrow run into the byte above a match: 'I' 'H' would count twice)
-LRM_DIFF_FN uint32_t diff_bytes_equal(uint32_t w, uint32_t c) {
-    const uint32_t t = w ^ (c * 0x01010101u);
-    return ~(((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t | 0x7F7F7F7Fu);
-}
-
-// the masks of one word of op bytes; pw: the column before each of its bytes
-struct DiffMasks { uint32_t eq, x, d, d_open; };
-LRM_DIFF_FN DiffMasks diff_masks(uint32_t cw, uint32_t pw) {
-    DiffMasks m;
-    m.eq = diff_bytes_equal(cw, '=');
-    m.x = diff_bytes_equal(cw, 'X');
-    m.d = diff_bytes_equal(cw, 'D');
-    m.d_open = m.d & ~diff_bytes_equal(pw, 'D');
-    return m;
-}
-
-// byte k (0..15) of 16 text bytes held in four words; selects, no indexed register
-LRM_DIFF_FN uint32_t diff_text_byte(uint32_t t0, uint32_t t1, uint32_t t2, uint32_t t3, uint32_t k) {
-    const uint32_t w = (k & 8u) ? ((k & 4u) ? t3 : t2) : ((k & 4u) ? t1 : t0);
-    return (w >> (8u * (k & 3u))) & 0xFFu;
-}
 
 // The events of one word in column order.  t: target-consuming columns of the lane before this word (the index of the
 // word's first target byte among the lane's 16 text bytes t0..t3), e: '=' columns of the row before this word; both move on
 // by the word.  emit(word) is called once per 'X' / 'D' column.
 template <typename Emit>
-LRM_DIFF_FN void diff_word_step(const DiffMasks &m, uint32_t &t, uint32_t &e, uint32_t t0, uint32_t t1, uint32_t t2, uint32_t t3, Emit emit) {
+LRM_OP_FN void diff_word_step(const OpMasks &m, uint32_t &t, uint32_t &e, uint32_t t0, uint32_t t1, uint32_t t2, uint32_t t3, Emit emit) {
     const uint32_t tm = m.eq | m.x | m.d;
     uint32_t ev = m.x | m.d;
     while (ev) {
@@ -51,9 +22,29 @@ LRM_DIFF_FN void diff_word_step(const DiffMasks &m, uint32_t &t, uint32_t &e, ui
         const uint32_t tl = t + (uint32_t) __builtin_popcount(tm & below);
         const uint32_t ee = e + (uint32_t) __builtin_popcount(m.eq & below);
         const uint32_t kind = (m.x & bit) ? LRM_DIFF_X : ((m.d_open & bit) ? LRM_DIFF_D_OPEN : LRM_DIFF_D_MORE);
-        emit(diff_text_byte(t0, t1, t2, t3, tl) | (kind << 8) | (ee << LRM_DIFF_E_SHIFT));
+        emit(op_pick_byte(t0, t1, t2, t3, tl) | (kind << 8) | (ee << LRM_DIFF_E_SHIFT));
         ev &= ev - 1u;
     }
     t += (uint32_t) __builtin_popcount(tm);
     e += (uint32_t) __builtin_popcount(m.eq);
+}
+
+// ---- the rule on the host (lrm_aln_diff_host) ----
+// The events of a row of n op bytes into events_out (null: only the count).  The row is walked as a lane of aln_diff_kernel walks it,
+// 16 columns at a time through diff_word_step: the 16 target bytes from the lane's first target position on (zeros from target_len on).
+static inline uint64_t diff_host_events(const uint8_t *ops, uint64_t n, const uint8_t *target, uint64_t target_len, uint32_t *events_out) {
+    uint64_t t_row = 0, count = 0;
+    uint32_t e = 0;
+    op_host_walk(ops, n, [&](const uint32_t (&cw)[4], const uint32_t (&pw)[4]) {
+        uint32_t text[4];
+        for (int k = 0; k < 4; ++k) text[k] = op_host_word(target, t_row + 4u * (uint64_t) k, target_len);
+        uint32_t t = 0;
+        for (int k = 0; k < 4; ++k)
+            diff_word_step(op_masks(cw[k], pw[k]), t, e, text[0], text[1], text[2], text[3], [&](uint32_t word) {
+                if (events_out) events_out[count] = word;
+                ++count;
+            });
+        t_row += t;
+    });
+    return count;
 }

@@ -25,7 +25,6 @@
 
 #define GACT_NEG (-(1 << 28))
 #define DPP_WAVE_SHL1 0x130  // lane L <- lane L+1
-#define DPP_WAVE_SHR1 0x138  // lane L <- lane L-1
 
 // ----------------------------------------------------------------------------------------
 // GACT

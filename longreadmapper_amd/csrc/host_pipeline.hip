@@ -30,6 +30,7 @@
 #include <exception>
 #include <new>
 #include "host_pipeline.h"
+#include "op_rows.h"
 
 namespace {
 
@@ -360,7 +361,7 @@ int plan_and_issue(LrmHostCtx &c, SliceJob &sj) {
                                                mt, c.ext[xs])) return -1;
             } else if (lrm_launch_extend(idx, S.ws_ext[xs].get(), b, j.gp, mt, c.ext[xs])) return -1;
             if (sj.want_summary &&                                             // what the alignments consist of, while the op bytes are in HBM
-                lrm_launch_aln_summary(b.store, dstride, b.n_ops, b.score, b.meta_r, u.m, (lrm_aln_summary *) d[A_SUMMARY].p + u.off, c.ext[xs])) return -1;
+                lrm_launch_aln_summary(LrmOpRows{b.store, dstride, b.n_ops, b.score, b.meta_r, b.meta, u.m}, (lrm_aln_summary *) d[A_SUMMARY].p + u.off, c.ext[xs])) return -1;
             if (mt.cigar_text &&                                               // length of every read's run-length CIGAR text
                 lrm_launch_cigar_text(b.store, dstride, b.n_ops, b.score, b.meta_r, (uint32_t *) d[A_TLEN].p + u.off, nullptr, nullptr, u.m, c.ext[xs])) return -1;
             HIPCHK(hipEventRecord(S.ev_ext[g], c.ext[xs]));
@@ -399,9 +400,9 @@ int collect_diff(LrmHostCtx &c, SliceJob &sj, const Range &u, const lrm_aln_summ
     if (!fits || total == 0) return 0;
     if (S.diff_ev.ensure((total + total / 4) * sizeof(uint32_t))) { lrm_set_error("allocation for the difference events failed"); return -1; }
     HIPCHK(hipMemcpyAsync(S.diff_off.p, h_doff, (m + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c.down));
-    if (lrm_launch_aln_diff((const uint8_t *) d[A_STORE].p + o * sj.dstride, sj.dstride, (const int32_t *) d[A_NOPS].p + o,
-                            (const int32_t *) d[A_SCORE].p + o, (const int32_t *) d[A_MR].p + o, (const lrm_seq_meta *) d[A_META].p + o,
-                            c.idx->view.content, c.idx->view.con_len, m, (const uint64_t *) S.diff_off.p, total, (uint32_t *) S.diff_ev.p, c.down)) return -1;
+    const LrmOpRows rows = {(const uint8_t *) d[A_STORE].p + o * sj.dstride, sj.dstride, (const int32_t *) d[A_NOPS].p + o,
+                            (const int32_t *) d[A_SCORE].p + o, (const int32_t *) d[A_MR].p + o, (const lrm_seq_meta *) d[A_META].p + o, m};
+    if (lrm_launch_aln_diff(rows, c.idx->view.content, c.idx->view.con_len, (const uint64_t *) S.diff_off.p, total, (uint32_t *) S.diff_ev.p, c.down)) return -1;
     uint8_t *dst = (uint8_t *) (j.diff_events + base);
     if (is_pinned(dst)) { HIPCHK(hipMemcpyAsync(dst, S.diff_ev.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost, c.down)); return 0; }
     return d2h_ring(c, (const uint8_t *) S.diff_ev.p, total * sizeof(uint32_t), nullptr, nullptr, nullptr, 0, dst,

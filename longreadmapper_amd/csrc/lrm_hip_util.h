@@ -47,6 +47,7 @@ __host__ __device__ static inline T bit_range(int lo, int hi) {
 }
 
 // ---- wavefront primitives on the DPP network (seed_kernels.hip, vote_kernels.hip, anchor_kernels.hip) ----
+#define DPP_WAVE_SHR1 0x138  // wave_shr:1, lane L <- lane L-1 (gact_kernels.hip, op_rows.h)
 // inclusive prefix sum over the 64 lanes on the DPP network: four row shifts inside the rows of 16, then the
 // row totals are broadcast to the following rows (row_bcast:15 / row_bcast:31) -- six v_add_u32_dpp, no LDS
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
@@ -108,31 +109,40 @@ __device__ __forceinline__ uint32_t wave_or_u32(uint32_t v) {
     return (uint32_t) __builtin_amdgcn_readlane((int) v, 63);
 }
 
-// ---- row loads of the stream kernels over op bytes (aln_summary_kernels.hip, aln_diff_kernels.hip) ----
-// 16 bytes of a row of n bytes from position c0 on.  Rows start at any byte (the hardware takes the unaligned dwords, as in
-// pack_rows_kernel).  row_load_step: a step that lies whole inside the row, one 16-byte load per lane.  row_load_last_step:
-// the row's last step -- zeros from position n on, and nothing at or behind p + n is read.  I: the type positions are counted in.
-template <typename I>
-__device__ __forceinline__ uint4 row_load_step(const uint8_t *__restrict__ p, I c0) {
-    uint4 v;
-    __builtin_memcpy(&v, p + c0, 16);
-    return v;
-}
-template <typename I>
-__device__ __forceinline__ uint32_t row_load_word(const uint8_t *__restrict__ p, I col, I n) {
-    uint32_t v = 0;
-    if (col + 4 <= n) __builtin_memcpy(&v, p + col, 4);
-    else if (col < n) {
-        v = p[col];
-        if (col + 1 < n) v |= (uint32_t) p[col + 1] << 8;
-        if (col + 2 < n) v |= (uint32_t) p[col + 2] << 16;
+// ---- exclusive prefix sums by one workgroup of 1024 that loops over its n items (pileup_tile_scan_kernel, aln_diff_offsets_kernel); the 64-bit wave scan is on shuffles ----
+__device__ __forceinline__ uint64_t wave_incl_scan(uint64_t v) {
+    const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const uint64_t o = (uint64_t) __shfl_up((unsigned long long) v, d, 64);
+        if (lane >= d) v += o;
     }
     return v;
 }
-template <typename I>
-__device__ __forceinline__ uint4 row_load_last_step(const uint8_t *__restrict__ p, I c0, I n) {
-    if (c0 + 16 <= n) return row_load_step(p, c0);
-    return make_uint4(row_load_word<I>(p, c0, n), row_load_word<I>(p, c0 + 4, n), row_load_word<I>(p, c0 + 8, n), row_load_word<I>(p, c0 + 12, n));
+// load(i) -> the value of item i; a scan over the wavefront, the 16 wavefront totals through LDS, the total so far carried
+// from round to round; store(i, excl, mine): the sum of the items before i, and item i itself
+template <typename T, typename Load, typename Store>
+__device__ __forceinline__ void block1024_excl_scan(uint64_t n, Load load, Store store) {
+    __shared__ T wave_total[16];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    T running = 0;
+    for (uint64_t base = 0; base < n; base += 1024u) {
+        const uint64_t i = base + tid;
+        const T mine = i < n ? load(i) : (T) 0;
+        const T incl = wave_incl_scan(mine);
+        if (lane == 63u) wave_total[wave] = incl;
+        __syncthreads();
+        T before = 0, all = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < 16u; ++k) {
+            const T wt = wave_total[k];
+            before += k < wave ? wt : (T) 0;
+            all += wt;
+        }
+        if (i < n) store(i, running + before + incl - mine, mine);
+        running += all;
+        __syncthreads();                                             // wave_total is rewritten by the next round
+    }
 }
 
 // ---- index gathers shared by the seed-table build (index_tables.hip), the hit walk of the vote kernels (vote_hits.h) and the mapping-quality vote (mapq_kernels.hip) ----

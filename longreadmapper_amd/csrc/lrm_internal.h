@@ -343,15 +343,14 @@ int lrm_launch_pack_rows(const uint8_t *d_src, uint64_t pitch, uint64_t row_cap,
 int lrm_launch_cigar_text(const uint8_t *d_store, uint64_t pitch, const int32_t *d_n_ops, const int32_t *d_score, const int32_t *d_meta_r,
                           uint32_t *d_tlen, const uint64_t *d_off, uint8_t *d_dense, uint64_t rows, void *stream);
 // the alignment summary records (aln_summary_kernels.hip; docs/GACT_SPEC.md, "Alignment summary and PAF") of rows whose op
-// bytes start at d_store + row * pitch: behind the extension that wrote them, on its stream
-int lrm_launch_aln_summary(const uint8_t *d_store, uint64_t pitch, const int32_t *d_n_ops, const int32_t *d_score, const int32_t *d_meta_r,
-                           uint64_t rows, lrm_aln_summary *d_out, void *stream);
+// bytes start at store + row * pitch (LrmOpRows, op_rows.h): behind the extension that wrote them, on its stream
+struct LrmOpRows;
+int lrm_launch_aln_summary(const LrmOpRows &b, lrm_aln_summary *d_out, void *stream);
 // the difference events (aln_diff_kernels.hip; docs/GACT_SPEC.md, "Difference events and MD:Z") of the same rows: d_off holds
 // rows + 1 exclusive prefix sums of n_x + n_del (lrm_launch_aln_diff_offsets makes them from the summary records), row i's
 // events go to d_events + d_off[i]; a row whose events end behind cap writes nothing
-int lrm_launch_aln_diff(const uint8_t *d_store, uint64_t pitch, const int32_t *d_n_ops, const int32_t *d_score, const int32_t *d_meta_r,
-                        const lrm_seq_meta *d_meta, const char *d_content, uint64_t con_len, uint64_t rows, const uint64_t *d_off,
-                        uint64_t cap, uint32_t *d_events, void *stream);
+int lrm_launch_aln_diff(const LrmOpRows &b, const char *d_content, uint64_t con_len, const uint64_t *d_off, uint64_t cap, uint32_t *d_events,
+                        void *stream);
 int lrm_launch_aln_diff_offsets(const lrm_aln_summary *d_sum, uint64_t rows, uint64_t *d_off, void *stream);
 // the pileup (pileup_kernels.hip; docs/GACT_SPEC.md, "Pileup").  An accumulator: the counter planes of pileup_step.h over
 // the window [lo, hi) (W = hi - lo positions) with LRM_PILEUP_GUARD_WORDS guard words behind them, and two words per tile
@@ -368,9 +367,8 @@ struct lrm_pileup {
 };
 // the same rows as the summary and the events, plus the read rows (d_reads + row * stride, d_lens) the extension left; a
 // row without an alignment, or with d_mapq[row].mapq < min_mapq (d_mapq null: no filter), adds nothing
-int lrm_launch_pileup_add(const lrm_pileup *pl, const uint8_t *d_reads, uint64_t stride, const uint32_t *d_lens, const uint8_t *d_store,
-                          uint64_t pitch, const int32_t *d_n_ops, const int32_t *d_score, const int32_t *d_meta_r, const lrm_seq_meta *d_meta,
-                          uint64_t rows, const lrm_mapq *d_mapq, uint32_t min_mapq, void *stream);
+int lrm_launch_pileup_add(const lrm_pileup *pl, const uint8_t *d_reads, uint64_t stride, const uint32_t *d_lens, const LrmOpRows &b,
+                          const lrm_mapq *d_mapq, uint32_t min_mapq, void *stream);
 // the records of window positions [first, first + count), count > 0: tile sums, their scan, the records
 int lrm_launch_pileup_read(const lrm_pileup *pl, uint64_t first, uint64_t count, lrm_pileup_col *d_out, void *stream);
 // the call stage over the same positions (docs/GACT_SPEC.md, "Pileup calls"), 0 < count < 2^32, pl->d_call allocated: tile

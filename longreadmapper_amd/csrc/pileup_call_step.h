@@ -1,6 +1,6 @@
 // pileup_call_step.h -- the call rule of the pileup (docs/GACT_SPEC.md, "Pileup calls"): from the record of one position and
 // its text byte to the kinds of site it is, its strongest non-reference base and its consensus letter.  Read by
-// pileup_kernels.hip (pileup_call_kernel, pileup_sites_kernel) and, as plain C++, by lrm_pileup_sites_host (lrm_api.hip) and
+// pileup_kernels.hip (pileup_call_kernel, pileup_sites_kernel) and, as plain C++, by lrm_pileup_sites_host (pileup.hip) and
 // tests/models/pileup_call_harness.cpp: the host rule and the CPU tests run the kernels' own source.  All arithmetic is integer.
 #pragma once
 #include <stdint.h>
@@ -12,7 +12,7 @@
 
 // the options with every zero field replaced by its default (the refusals are the entry points': lrm_pileup_call_check)
 struct PileCallRule { uint32_t min_depth, min_count, min_pct; };
-LRM_DIFF_FN PileCallRule pile_call_rule(uint32_t min_depth, uint32_t min_count, uint32_t min_pct) {
+LRM_OP_FN PileCallRule pile_call_rule(uint32_t min_depth, uint32_t min_count, uint32_t min_pct) {
     PileCallRule r;
     r.min_depth = min_depth ? min_depth : LRM_CALL_MIN_DEPTH_DEFAULT;
     r.min_count = min_count ? min_count : LRM_CALL_MIN_COUNT_DEFAULT;
@@ -21,7 +21,7 @@ LRM_DIFF_FN PileCallRule pile_call_rule(uint32_t min_depth, uint32_t min_count, 
 }
 
 // n reads of `depth` are enough to be called: the depth, the count and the percentage, the last in 64 bits
-LRM_DIFF_FN bool pile_call_passes(const PileCallRule &r, uint32_t depth, uint32_t n) {
+LRM_OP_FN bool pile_call_passes(const PileCallRule &r, uint32_t depth, uint32_t n) {
     return depth >= r.min_depth && n >= r.min_count && 100ull * (uint64_t) n >= (uint64_t) r.min_pct * (uint64_t) depth;
 }
 
@@ -30,7 +30,7 @@ struct PileCall { uint32_t kinds, n_alt; uint8_t alt, cons; };
 
 // c: the position's record, byte: its text byte as stored.  Selects only, in the fixed order A, C, G, T: a strict `>`
 // keeps the earlier of two equal counts.
-LRM_DIFF_FN PileCall pile_call(const PileCallRule &r, uint32_t depth, uint32_t n_eq, uint32_t x_a, uint32_t x_c, uint32_t x_g, uint32_t x_t,
+LRM_OP_FN PileCall pile_call(const PileCallRule &r, uint32_t depth, uint32_t n_eq, uint32_t x_a, uint32_t x_c, uint32_t x_g, uint32_t x_t,
                                uint32_t n_del, uint32_t n_ins, uint32_t byte) {
     const uint32_t rc = pile_base_class(byte);
     const uint32_t x[4] = {x_a, x_c, x_g, x_t};
@@ -63,7 +63,7 @@ LRM_DIFF_FN PileCall pile_call(const PileCallRule &r, uint32_t depth, uint32_t n
 
 // the site record of text position pos as the four words of its two halves (lrm_pileup_site: pos, depth, n_ref | n_alt,
 // n_del, n_ins, the four bytes ref, alt, cons, kinds)
-LRM_DIFF_FN void pile_call_site_words(const PileCall &c, uint64_t pos, uint32_t depth, uint32_t n_eq, uint32_t n_del, uint32_t n_ins,
+LRM_OP_FN void pile_call_site_words(const PileCall &c, uint64_t pos, uint32_t depth, uint32_t n_eq, uint32_t n_del, uint32_t n_ins,
                                       uint32_t byte, uint32_t (&w)[8]) {
     w[0] = (uint32_t) pos; w[1] = (uint32_t) (pos >> 32); w[2] = depth; w[3] = n_eq;
     w[4] = c.n_alt; w[5] = n_del; w[6] = n_ins;

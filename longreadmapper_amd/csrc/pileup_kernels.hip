@@ -7,7 +7,6 @@
 // the positions where the reads disagree with the text -- compacted into a table by count, scan, write at the prefix sum
 // (the idiom of compact_rows.h: no atomics, the same table whatever the scheduling), and one consensus byte per position.
 #include <hip/hip_runtime.h>
-#include "lrm_hip_util.h"
 #include "pileup_step.h"
 #include "pileup_call_step.h"
 
@@ -26,34 +25,27 @@ struct PileRow { uint32_t t = 0, q = 0, carry = 0; };
 // the window as a kernel sees it: text positions [lo, hi), W = hi - lo, the event planes behind the W + 1 depth words
 struct PileWindow { uint64_t lo, hi, W; uint32_t *planes; };
 
-// One step: the lane's 16 columns (zeros from column n on).  The lane's count of target-consuming columns and its count of
-// query-consuming columns share one word, so ONE inclusive scan gives the lane's target column and its first query byte.
-// The lane's at most 16 query bytes are contiguous: one unaligned 16-byte read (nothing at or behind read + len), every 'X'
-// column's byte picked out of the four registers.  The previous column of a lane's first byte comes over the DPP network
-// (wave_shr:1), as in diff_step.
+// One step: the lane's 16 columns (zeros from column n on).  The packed scan of the lane's target-consuming and its
+// query-consuming columns gives the lane's target column and its first query byte.  The lane's at most 16 query bytes are
+// contiguous: one unaligned 16-byte read (nothing at or behind read + len), every 'X' column's byte picked out of the four
+// registers.
 __device__ __forceinline__ void pile_step(PileRow &r, const uint4 cur, const uint8_t *__restrict__ read, uint32_t len, uint64_t loc,
                                           const PileWindow &win) {
     const uint32_t w[4] = {cur.x, cur.y, cur.z, cur.w};
-    const uint32_t mine = w[3] >> 24;
-    uint32_t prev = (uint32_t) __builtin_amdgcn_update_dpp((int) r.carry, (int) mine, 0x138, 0xf, 0xf, false);   // wave_shr:1; lane 0 keeps the carry
-    r.carry = (uint32_t) __builtin_amdgcn_readlane((int) mine, 63);
-    PileMasks m[4];
+    uint32_t prev = op_prev_byte(r.carry, w[3]);
+    OpMasks m[4];
     uint32_t tc = 0, qc = 0, any = 0, any_x = 0;
 #pragma unroll
     for (uint32_t k = 0; k < 4; ++k) {
-        m[k] = pile_masks(w[k], (w[k] << 8) | prev);
+        m[k] = op_masks(w[k], (w[k] << 8) | prev);
         prev = w[k] >> 24;
         tc += (uint32_t) __popc(m[k].eq | m[k].x | m[k].d);
         qc += (uint32_t) __popc(m[k].eq | m[k].x | m[k].i | m[k].s);
         any |= m[k].x | m[k].d | m[k].i_open;
         any_x |= m[k].x;
     }
-    const uint32_t mine2 = tc | (qc << 16);                          // at most 1024 each in a step: the halves never meet
-    const uint32_t incl = wave_incl_scan(mine2), excl = incl - mine2;
-    const uint32_t t_lane = r.t + (excl & 0xFFFFu), q_lane = r.q + (excl >> 16);
-    const uint32_t total = (uint32_t) __builtin_amdgcn_readlane((int) incl, 63);
-    r.t += total & 0xFFFFu;
-    r.q += total >> 16;
+    uint32_t t_lane, q_lane;
+    op_scan_pair(tc, qc, r.t, r.q, t_lane, q_lane);
     if (!any) return;
     uint4 qb = make_uint4(0u, 0u, 0u, 0u);
     if (any_x) qb = row_load_last_step<uint32_t>(read, q_lane, len);
@@ -66,37 +58,25 @@ __device__ __forceinline__ void pile_step(PileRow &r, const uint4 cur, const uin
         });
 }
 
-// One wavefront per read, four per workgroup; no LDS, no barrier.  As in the summary and the difference kernels two steps
-// are asked for together wherever both lie whole inside the row, and the end of a row goes through the masked loads.  A
-// read without an alignment, a filtered read and a read that starts at or behind the window's end leave before their
-// first row load.  Lane 0 makes the two depth adds once the row's target span is known.
+// One wavefront per read, four per workgroup; no LDS, no barrier: the walk of op_rows.h.  A read without an alignment, a
+// filtered read and a read that starts at or behind the window's end leave before their first row load.  Lane 0 makes the
+// two depth adds once the row's target span is known.
 __global__ __launch_bounds__(256) void pileup_add_kernel(const uint8_t *__restrict__ reads, uint64_t stride, const uint32_t *__restrict__ lens,
                                                          const uint8_t *__restrict__ store, uint64_t pitch, const int32_t *__restrict__ n_ops,
                                                          const int32_t *__restrict__ score, const int32_t *__restrict__ meta_r,
                                                          const lrm_seq_meta *__restrict__ meta, uint64_t rows, const lrm_mapq *__restrict__ mapq,
                                                          uint32_t min_mapq, PileWindow win) {
-    const uint64_t row = (uint64_t) blockIdx.x * 4u + (uint64_t) __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
-    if (row >= rows) return;
-    const uint32_t lane = threadIdx.x & 63u;
+    uint64_t row; uint32_t lane;
+    if (!op_row_of_wave(rows, row, lane)) return;
     const int nn = n_ops[row];
-    if (nn <= 0 || meta_r[row] == 0 || score[row] == -1) return;
+    if (op_row_absent(nn, meta_r, score, row)) return;
     if (mapq && (uint32_t) mapq[row].mapq < min_mapq) return;
     const uint64_t loc = meta[row].loc;
     if (loc >= win.hi) return;                                       // every count of the read lies at or behind loc
-    const uint32_t n = (uint32_t) nn;                                // (uniform: every branch on it is a scalar one)
-    const uint8_t *ops = store + row * pitch;
     const uint8_t *read = reads + row * stride;
     const uint32_t len = lens[row];
     PileRow r;
-    uint32_t base = 0;
-    for (; base + 2048u <= n; base += 2048u) {                       // two steps whole inside the row: both loads in flight
-        const uint32_t c0 = base + lane * 16u;
-        const uint4 a = row_load_step<uint32_t>(ops, c0), b = row_load_step<uint32_t>(ops, c0 + 1024u);
-        pile_step(r, a, read, len, loc, win);
-        pile_step(r, b, read, len, loc, win);
-    }
-    for (; base < n; base += 1024u)
-        pile_step(r, row_load_last_step<uint32_t>(ops, base + lane * 16u, n), read, len, loc, win);
+    op_row_walk(store + row * pitch, (uint32_t) nn, lane, [&](const uint4 cur, uint32_t) { pile_step(r, cur, read, len, loc, win); });
     if (lane == 0) {
         const uint64_t a = loc > win.lo ? loc : win.lo, end = loc + r.t, b = end < win.hi ? end : win.hi;
         if (a < b) {                                                 // the covered interval clipped to the window
@@ -140,38 +120,16 @@ __global__ __launch_bounds__(256) void pileup_tile_sums_kernel(const uint32_t *_
     if (threadIdx.x == 0) tile_sum[blockIdx.x] = all;
 }
 
-// read-back 2: exclusive prefix sums of the tile sums (the depth in front of every tile), 32-bit and wrapping like the
-// counters: one workgroup of 1024 that loops over the tiles as aln_diff_offsets_kernel loops over the records
+// read-back 2: exclusive prefix sums of the tile sums (the depth in front of every tile), 32-bit and wrapping like the counters
 __global__ __launch_bounds__(1024) void pileup_tile_scan_kernel(const uint32_t *__restrict__ tile_sum, uint64_t n, uint32_t *__restrict__ tile_base) {
-    __shared__ uint32_t wave_total[16];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    uint32_t running = 0;
-    for (uint64_t base = 0; base < n; base += 1024u) {
-        const uint64_t i = base + tid;
-        const uint32_t mine = i < n ? tile_sum[i] : 0u;
-        const uint32_t incl = wave_incl_scan(mine);
-        if (lane == 63u) wave_total[wave] = incl;
-        __syncthreads();
-        uint32_t before = 0, all = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < 16u; ++k) {
-            const uint32_t wt = wave_total[k];
-            before += k < wave ? wt : 0u;
-            all += wt;
-        }
-        if (i < n) tile_base[i] = running + before + incl - mine;
-        running += all;
-        __syncthreads();                                             // wave_total is rewritten by the next round
-    }
+    block1024_excl_scan<uint32_t>(n, [&](uint64_t i) { return tile_sum[i]; }, [&](uint64_t i, uint32_t excl, uint32_t) { tile_base[i] = excl; });
 }
 
-// read-back 3: the records of the window positions [first, first + count), one workgroup per tile that holds any of them
-// (tile0: the tile of `first`).  The workgroup rescans its tile from the tile's base, 256 positions a round; a position
-// inside the range reads its seven event words and writes its record with two aligned 16-byte stores.
-__global__ __launch_bounds__(256) void pileup_cols_kernel(const uint32_t *__restrict__ planes, uint64_t W, const uint32_t *__restrict__ tile_base,
-                                                          uint64_t tile0, uint64_t first, uint64_t count, lrm_pileup_col *__restrict__ out) {
-    __shared__ uint32_t lds[4];
-    const uint64_t tile = tile0 + blockIdx.x;
+// The depth of every position of a tile, by a workgroup of 256: the tile is rescanned from its base, 256 positions a round,
+// and body(g, depth) runs in every thread of every round -- it may hold barriers.  g may lie behind W: the range test is the body's.
+template <typename Body>
+__device__ __forceinline__ void pile_tile_rescan(const uint32_t *__restrict__ planes, uint64_t W, const uint32_t *__restrict__ tile_base,
+                                                 uint64_t tile, uint32_t *lds, Body body) {
     uint32_t running = tile_base[tile];
 #pragma unroll 1
     for (uint32_t j = 0; j < LRM_PILEUP_TILE / 256u; ++j) {
@@ -179,57 +137,58 @@ __global__ __launch_bounds__(256) void pileup_cols_kernel(const uint32_t *__rest
         uint32_t all;
         const uint32_t depth = running + block256_incl_scan(g < W ? planes[g] : 0u, lds, all);
         running += all;
-        if (g < first || g - first >= count) continue;               // (first + count <= W: g < W here)
-        uint32_t e[LRM_PILEUP_PLANES];
-#pragma unroll
-        for (uint32_t k = 0; k < LRM_PILEUP_PLANES; ++k) e[k] = planes[LRM_PILEUP_EVENT_PLANE(W, k) + g];
-        const uint32_t x_all = e[LRM_PILEUP_X_A] + e[LRM_PILEUP_X_C] + e[LRM_PILEUP_X_G] + e[LRM_PILEUP_X_T] + e[LRM_PILEUP_X_OTHER];
-        uint4 *o = reinterpret_cast<uint4 *>(out + (g - first));
-        o[0] = make_uint4(depth, depth - x_all - e[LRM_PILEUP_DEL], e[LRM_PILEUP_X_A], e[LRM_PILEUP_X_C]);
-        o[1] = make_uint4(e[LRM_PILEUP_X_G], e[LRM_PILEUP_X_T], e[LRM_PILEUP_DEL], e[LRM_PILEUP_INS]);
+        body(g, depth);
     }
+}
+
+// read-back 3: the records of the window positions [first, first + count), one workgroup per tile that holds any of them
+// (tile0: the tile of `first`).  A position inside the range reads its seven event words and writes its record with two
+// aligned 16-byte stores.
+__global__ __launch_bounds__(256) void pileup_cols_kernel(const uint32_t *__restrict__ planes, uint64_t W, const uint32_t *__restrict__ tile_base,
+                                                          uint64_t tile0, uint64_t first, uint64_t count, lrm_pileup_col *__restrict__ out) {
+    __shared__ uint32_t lds[4];
+    pile_tile_rescan(planes, W, tile_base, tile0 + blockIdx.x, lds, [&](uint64_t g, uint32_t depth) {
+        if (g < first || g - first >= count) return;                 // (first + count <= W: g < W here)
+        uint32_t w[8];
+        pile_col_words(planes, W, g, depth, w);
+        uint4 *o = reinterpret_cast<uint4 *>(out + (g - first));
+        o[0] = make_uint4(w[0], w[1], w[2], w[3]);
+        o[1] = make_uint4(w[4], w[5], w[6], w[7]);
+    });
 }
 
 // ---- the call stage ----
 typedef uint32_t pile_u32x4 __attribute__((ext_vector_type(4)));
-// one position inside the requested range: its seven event words, its text byte (text: content + lo), the rule
+// one position inside the requested range: its record's words, its text byte (text: content + lo), the rule
 struct PilePos { uint32_t n_eq, n_del, n_ins, byte; PileCall call; };
 __device__ __forceinline__ PilePos pile_call_at(const uint32_t *__restrict__ planes, uint64_t W, uint64_t g, uint32_t depth,
                                                 const uint8_t *__restrict__ text, const PileCallRule &rule) {
-    uint32_t e[LRM_PILEUP_PLANES];
-#pragma unroll
-    for (uint32_t k = 0; k < LRM_PILEUP_PLANES; ++k) e[k] = planes[LRM_PILEUP_EVENT_PLANE(W, k) + g];
-    const uint32_t x_all = e[LRM_PILEUP_X_A] + e[LRM_PILEUP_X_C] + e[LRM_PILEUP_X_G] + e[LRM_PILEUP_X_T] + e[LRM_PILEUP_X_OTHER];
+    uint32_t w[8];
+    pile_col_words(planes, W, g, depth, w);
     PilePos p;
-    p.n_eq = depth - x_all - e[LRM_PILEUP_DEL];
-    p.n_del = e[LRM_PILEUP_DEL];
-    p.n_ins = e[LRM_PILEUP_INS];
+    p.n_eq = w[1];
+    p.n_del = w[6];
+    p.n_ins = w[7];
     p.byte = text[g];
-    p.call = pile_call(rule, depth, p.n_eq, e[LRM_PILEUP_X_A], e[LRM_PILEUP_X_C], e[LRM_PILEUP_X_G], e[LRM_PILEUP_X_T], p.n_del, p.n_ins, p.byte);
+    p.call = pile_call(rule, depth, p.n_eq, w[2], w[3], w[4], w[5], p.n_del, p.n_ins, p.byte);
     return p;
 }
 
-// calls 1: one workgroup per tile that holds a requested position (tile0: the tile of `first`).  The tile's depth is
-// rescanned as pileup_cols_kernel rescans it; a position inside the range is evaluated, its cons byte written when the
-// caller asked (a byte store at cons + (g - first): `first` is arbitrary, so nothing wider is aligned at the range's ends,
-// and nothing outside cons[0 .. count) is touched); the tile's number of sites goes to tile_sites[blockIdx.x].
+// calls 1: one workgroup per tile that holds a requested position (tile0: the tile of `first`).  A position inside the
+// range is evaluated, its cons byte written when the caller asked (a byte store at cons + (g - first): `first` is
+// arbitrary, so nothing wider is aligned at the range's ends, and nothing outside cons[0 .. count) is touched); the tile's
+// number of sites goes to tile_sites[blockIdx.x].
 __global__ __launch_bounds__(256) void pileup_call_kernel(const uint32_t *__restrict__ planes, uint64_t W, const uint32_t *__restrict__ tile_base,
                                                           uint64_t tile0, uint64_t first, uint64_t count, const uint8_t *__restrict__ text,
                                                           PileCallRule rule, uint8_t *__restrict__ cons, uint32_t *__restrict__ tile_sites) {
     __shared__ uint32_t lds[4];
-    const uint64_t tile = tile0 + blockIdx.x;
-    uint32_t running = tile_base[tile], mine = 0;
-#pragma unroll 1
-    for (uint32_t j = 0; j < LRM_PILEUP_TILE / 256u; ++j) {
-        const uint64_t g = tile * LRM_PILEUP_TILE + j * 256u + threadIdx.x;
-        uint32_t all;
-        const uint32_t depth = running + block256_incl_scan(g < W ? planes[g] : 0u, lds, all);
-        running += all;
-        if (g < first || g - first >= count) continue;               // (first + count <= W: g < W here)
+    uint32_t mine = 0;
+    pile_tile_rescan(planes, W, tile_base, tile0 + blockIdx.x, lds, [&](uint64_t g, uint32_t depth) {
+        if (g < first || g - first >= count) return;                 // (first + count <= W: g < W here)
         const PilePos p = pile_call_at(planes, W, g, depth, text, rule);
         if (cons) cons[g - first] = p.call.cons;
         mine += p.call.kinds ? 1u : 0u;
-    }
+    });
     uint32_t all;
     (void) block256_incl_scan(mine, lds, all);
     if (threadIdx.x == 0) tile_sites[blockIdx.x] = all;
@@ -239,8 +198,8 @@ __global__ __launch_bounds__(256) void pileup_call_kernel(const uint32_t *__rest
 // writes the total -- its own rank plus its own count -- as 64 bits.  A tile without a site, or whose first site already
 // lies at or behind cap, leaves after its scalar loads.  Otherwise the tile is evaluated again from the planes (no
 // per-position array between the two kernels: sites are few, so few tiles come back here, and a kinds byte per position
-// would be W more bytes written and kept for every call); the sites of a round are ranked by a block scan of the site flag,
-// the running rank carried as the depth is, and a record goes to sites[rank] with two aligned 16-byte stores when rank < cap.
+// would be W more bytes written and kept for every call); the sites of a round are ranked by a block scan of the site flag
+// in every thread, the running rank carried as the depth is, and a record goes to sites[rank] with two aligned 16-byte stores when rank < cap.
 __global__ __launch_bounds__(256) void pileup_sites_kernel(const uint32_t *__restrict__ planes, uint64_t W, const uint32_t *__restrict__ tile_base,
                                                            uint64_t tile0, uint64_t first, uint64_t count, uint64_t lo,
                                                            const uint8_t *__restrict__ text, PileCallRule rule,
@@ -251,17 +210,11 @@ __global__ __launch_bounds__(256) void pileup_sites_kernel(const uint32_t *__res
     uint64_t rank = tile_rank[blockIdx.x];
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *n_sites = rank + n_here;
     if (n_here == 0 || rank >= cap) return;
-    const uint64_t tile = tile0 + blockIdx.x;
-    uint32_t running = tile_base[tile];
-#pragma unroll 1
-    for (uint32_t j = 0; j < LRM_PILEUP_TILE / 256u; ++j) {
-        const uint64_t g = tile * LRM_PILEUP_TILE + j * 256u + threadIdx.x;
-        uint32_t all;
-        const uint32_t depth = running + block256_incl_scan(g < W ? planes[g] : 0u, lds, all);
-        running += all;
+    pile_tile_rescan(planes, W, tile_base, tile0 + blockIdx.x, lds, [&](uint64_t g, uint32_t depth) {
         PilePos p = {};
         if (g >= first && g - first < count) p = pile_call_at(planes, W, g, depth, text, rule);
         const uint32_t flag = p.call.kinds ? 1u : 0u;
+        uint32_t all;
         const uint64_t at = rank + (block256_incl_scan(flag, lds, all) - flag);
         rank += all;
         if (flag && at < cap) {
@@ -275,49 +228,55 @@ __global__ __launch_bounds__(256) void pileup_sites_kernel(const uint32_t *__res
             o[0] = h0;
             o[1] = h1;
         }
-    }
+    });
+}
+
+// What the read-back and the call stage start with: the sums of the difference plane over the tiles up to the last requested
+// position's, and their scan into `bases`.  tile0: the tile of `first`, grid: the tiles that hold a requested position.
+struct PileTiles { uint64_t tile0; uint32_t grid, *bases; };
+int pile_launch_tile_bases(const lrm_pileup *pl, uint64_t first, uint64_t count, const char *what, hipStream_t st, PileTiles *t) {
+    const uint64_t tile_end = (first + count + LRM_PILEUP_TILE - 1) / LRM_PILEUP_TILE;
+    *t = {first / LRM_PILEUP_TILE, 0u, pl->d_tiles + pl->n_tiles};
+    uint32_t grid_sums;
+    if (lrm_grid_1d(tile_end, what, &grid_sums) || lrm_grid_1d(tile_end - t->tile0, what, &t->grid)) return -1;
+    hipLaunchKernelGGL(pileup_tile_sums_kernel, dim3(grid_sums), dim3(256), 0, st, pl->d_planes, pl->W, pl->d_tiles);
+    hipLaunchKernelGGL(pileup_tile_scan_kernel, dim3(1), dim3(1024), 0, st, pl->d_tiles, tile_end, t->bases);
+    return 0;
 }
 
 }  // namespace
 
-int lrm_launch_pileup_add(const lrm_pileup *pl, const uint8_t *d_reads, uint64_t stride, const uint32_t *d_lens, const uint8_t *d_store,
-                          uint64_t pitch, const int32_t *d_n_ops, const int32_t *d_score, const int32_t *d_meta_r, const lrm_seq_meta *d_meta,
-                          uint64_t rows, const lrm_mapq *d_mapq, uint32_t min_mapq, void *stream) {
-    if (rows == 0) return 0;
+int lrm_launch_pileup_add(const lrm_pileup *pl, const uint8_t *d_reads, uint64_t stride, const uint32_t *d_lens, const LrmOpRows &b,
+                          const lrm_mapq *d_mapq, uint32_t min_mapq, void *stream) {
+    if (b.rows == 0) return 0;
     uint32_t grid;
-    if (lrm_grid_1d((rows + 3) / 4, "pileup", &grid)) return -1;
+    if (op_rows_grid(b.rows, "pileup", &grid)) return -1;
     const PileWindow win = {pl->lo, pl->hi, pl->W, pl->d_planes};
-    hipLaunchKernelGGL(pileup_add_kernel, dim3(grid), dim3(256), 0, (hipStream_t) stream, d_reads, stride, d_lens, d_store, pitch, d_n_ops,
-                       d_score, d_meta_r, d_meta, rows, d_mapq, min_mapq, win);
+    hipLaunchKernelGGL(pileup_add_kernel, dim3(grid), dim3(256), 0, (hipStream_t) stream, d_reads, stride, d_lens, b.store, b.pitch, b.n_ops,
+                       b.score, b.meta_r, b.meta, b.rows, d_mapq, min_mapq, win);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
 int lrm_launch_pileup_read(const lrm_pileup *pl, uint64_t first, uint64_t count, lrm_pileup_col *d_out, void *stream) {
-    const uint64_t tile0 = first / LRM_PILEUP_TILE, tile_end = (first + count + LRM_PILEUP_TILE - 1) / LRM_PILEUP_TILE;   // tiles [0, tile_end) are summed
-    uint32_t grid_sums, grid_cols;
-    if (lrm_grid_1d(tile_end, "pileup read-back", &grid_sums) || lrm_grid_1d(tile_end - tile0, "pileup read-back", &grid_cols)) return -1;
-    uint32_t *sums = pl->d_tiles, *bases = pl->d_tiles + pl->n_tiles;
-    hipLaunchKernelGGL(pileup_tile_sums_kernel, dim3(grid_sums), dim3(256), 0, (hipStream_t) stream, pl->d_planes, pl->W, sums);
-    hipLaunchKernelGGL(pileup_tile_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t) stream, sums, tile_end, bases);
-    hipLaunchKernelGGL(pileup_cols_kernel, dim3(grid_cols), dim3(256), 0, (hipStream_t) stream, pl->d_planes, pl->W, bases, tile0, first, count, d_out);
+    const hipStream_t st = (hipStream_t) stream;
+    PileTiles t;
+    if (pile_launch_tile_bases(pl, first, count, "pileup read-back", st, &t)) return -1;
+    hipLaunchKernelGGL(pileup_cols_kernel, dim3(t.grid), dim3(256), 0, st, pl->d_planes, pl->W, t.bases, t.tile0, first, count, d_out);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
 int lrm_launch_pileup_sites(const lrm_pileup *pl, const PileCallRule &rule, uint64_t first, uint64_t count, lrm_pileup_site *d_sites,
                             uint64_t cap, uint64_t *d_n_sites, uint8_t *d_cons, void *stream) {
-    const uint64_t tile0 = first / LRM_PILEUP_TILE, tile_end = (first + count + LRM_PILEUP_TILE - 1) / LRM_PILEUP_TILE;
-    uint32_t grid_sums, grid_call;
-    if (lrm_grid_1d(tile_end, "pileup calls", &grid_sums) || lrm_grid_1d(tile_end - tile0, "pileup calls", &grid_call)) return -1;
-    uint32_t *sums = pl->d_tiles, *bases = pl->d_tiles + pl->n_tiles, *n_here = pl->d_call, *rank = pl->d_call + pl->n_tiles;
-    const uint8_t *text = (const uint8_t *) pl->idx->view.content + pl->lo;
     const hipStream_t st = (hipStream_t) stream;
-    hipLaunchKernelGGL(pileup_tile_sums_kernel, dim3(grid_sums), dim3(256), 0, st, pl->d_planes, pl->W, sums);
-    hipLaunchKernelGGL(pileup_tile_scan_kernel, dim3(1), dim3(1024), 0, st, sums, tile_end, bases);
-    hipLaunchKernelGGL(pileup_call_kernel, dim3(grid_call), dim3(256), 0, st, pl->d_planes, pl->W, bases, tile0, first, count, text, rule, d_cons, n_here);
-    hipLaunchKernelGGL(pileup_tile_scan_kernel, dim3(1), dim3(1024), 0, st, n_here, (uint64_t) grid_call, rank);
-    hipLaunchKernelGGL(pileup_sites_kernel, dim3(grid_call), dim3(256), 0, st, pl->d_planes, pl->W, bases, tile0, first, count, pl->lo, text, rule,
+    PileTiles t;
+    if (pile_launch_tile_bases(pl, first, count, "pileup calls", st, &t)) return -1;
+    uint32_t *n_here = pl->d_call, *rank = pl->d_call + pl->n_tiles;
+    const uint8_t *text = (const uint8_t *) pl->idx->view.content + pl->lo;
+    hipLaunchKernelGGL(pileup_call_kernel, dim3(t.grid), dim3(256), 0, st, pl->d_planes, pl->W, t.bases, t.tile0, first, count, text, rule, d_cons, n_here);
+    hipLaunchKernelGGL(pileup_tile_scan_kernel, dim3(1), dim3(1024), 0, st, n_here, (uint64_t) t.grid, rank);
+    hipLaunchKernelGGL(pileup_sites_kernel, dim3(t.grid), dim3(256), 0, st, pl->d_planes, pl->W, t.bases, t.tile0, first, count, pl->lo, text, rule,
                        n_here, rank, d_sites, cap, d_n_sites);
     HIPCHK(hipGetLastError());
     return 0;

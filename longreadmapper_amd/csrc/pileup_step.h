@@ -1,10 +1,10 @@
 // pileup_step.h -- the per-word step of the pileup (docs/GACT_SPEC.md, "Pileup"): from the byte masks of four op bytes to
 // the counts they add -- which plane, which target column.  Read by pileup_kernels.hip (a lane's 16 columns are four such
-// words) and, as plain C++, by lrm_pileup_add_host (lrm_api.hip) and tests/models/pileup_host_harness.cpp: the host rule and
+// words) and, as plain C++, by lrm_pileup_add_host (pileup.hip) and tests/models/pileup_host_harness.cpp: the host rule and
 // the CPU tests run the kernel's own source.
 #pragma once
 #include <stdint.h>
-#include "aln_diff_step.h"               // diff_bytes_equal: the exact byte-equality masks; diff_text_byte: a byte out of four words
+#include "op_rows.h"                     // the byte masks, a byte out of four words, the walk of a row on the host
 
 // The planes of an accumulator over a window of W positions, all 32-bit words in one allocation of 8 * W + 1 words:
 //   [0, W]                     the DIFFERENCE plane of the depth: +1 where a read's covered interval starts, -1 where it ends
@@ -25,21 +25,8 @@
 // set no bound on the row; the running counts are carried as whole words.)
 #define LRM_PILEUP_MAX_STRIDE (1ull << 31)
 
-// the masks of one word of op bytes; pw: the column before each of its bytes
-struct PileMasks { uint32_t eq, x, d, i, s, i_open; };
-LRM_DIFF_FN PileMasks pile_masks(uint32_t cw, uint32_t pw) {
-    PileMasks m;
-    m.eq = diff_bytes_equal(cw, '=');
-    m.x = diff_bytes_equal(cw, 'X');
-    m.d = diff_bytes_equal(cw, 'D');
-    m.i = diff_bytes_equal(cw, 'I');
-    m.s = diff_bytes_equal(cw, 'S');
-    m.i_open = m.i & ~diff_bytes_equal(pw, 'I');
-    return m;
-}
-
 // the class of a read byte: A/a, C/c, G/g, T/t, other (selects, as comp_base of seq_bytes.h folds the case)
-LRM_DIFF_FN uint32_t pile_base_class(uint32_t byte) {
+LRM_OP_FN uint32_t pile_base_class(uint32_t byte) {
     const uint32_t u = byte & 0xDFu;
     uint32_t r = LRM_PILEUP_X_OTHER;
     r = u == 'A' ? LRM_PILEUP_X_A : r;
@@ -55,14 +42,14 @@ LRM_DIFF_FN uint32_t pile_base_class(uint32_t byte) {
 // column and once per 'I' column that opens a run behind at least one target column (tcol: the column before it); the
 // count belongs to text position loc + tcol.
 template <typename Add>
-LRM_DIFF_FN void pile_word_step(const PileMasks &m, uint32_t &t, uint32_t &q, uint32_t q0, uint32_t q1, uint32_t q2, uint32_t q3, Add add) {
+LRM_OP_FN void pile_word_step(const OpMasks &m, uint32_t &t, uint32_t &q, uint32_t q0, uint32_t q1, uint32_t q2, uint32_t q3, Add add) {
     const uint32_t tm = m.eq | m.x | m.d, qm = m.eq | m.x | m.i | m.s;
     uint32_t ev = m.x | m.d | m.i_open;
     while (ev) {
         const uint32_t bit = ev & (0u - ev);                         // 0x80 of the event's byte
         const uint32_t below = bit - 1u;                             // every mask bit of the columns before it
         const uint32_t tl = t + (uint32_t) __builtin_popcount(tm & below);
-        if (m.x & bit) add(pile_base_class(diff_text_byte(q0, q1, q2, q3, (q + (uint32_t) __builtin_popcount(qm & below)) & 15u)), tl);
+        if (m.x & bit) add(pile_base_class(op_pick_byte(q0, q1, q2, q3, (q + (uint32_t) __builtin_popcount(qm & below)) & 15u)), tl);
         else if (m.d & bit) add(LRM_PILEUP_DEL, tl);
         else if (tl) add(LRM_PILEUP_INS, tl - 1u);                   // (a run with no target column before it: nowhere)
         ev &= ev - 1u;
@@ -71,35 +58,34 @@ LRM_DIFF_FN void pile_word_step(const PileMasks &m, uint32_t &t, uint32_t &q, ui
     q += (uint32_t) __builtin_popcount(qm);
 }
 
-// ---- the rule on the host (lrm_pileup_add_host, lrm_pileup_cols_host; tests/models/pileup_host_harness.cpp) ----
-// bytes p[at .. at + 4) as a word, zeros from p + n on: nothing at or behind p + n is read
-static inline uint32_t pile_host_word(const uint8_t *p, uint64_t at, uint64_t n) {
-    uint32_t v = 0;
-    for (uint64_t k = 0; k < 4 && at + k < n; ++k) v |= (uint32_t) p[at + k] << (8 * k);
-    return v;
+// The eight words of the record of window position g (lrm_pileup_col: depth, n_eq, x_a, x_c, x_g, x_t, n_del, n_ins) from its
+// depth and its seven event words: every read that covers the position and is neither an 'X' nor a 'D' there is an '='.
+LRM_OP_FN void pile_col_words(const uint32_t *planes, uint64_t W, uint64_t g, uint32_t depth, uint32_t (&w)[8]) {
+    uint32_t e[LRM_PILEUP_PLANES];
+    for (uint32_t k = 0; k < LRM_PILEUP_PLANES; ++k) e[k] = planes[LRM_PILEUP_EVENT_PLANE(W, k) + g];
+    const uint32_t x_all = e[LRM_PILEUP_X_A] + e[LRM_PILEUP_X_C] + e[LRM_PILEUP_X_G] + e[LRM_PILEUP_X_T] + e[LRM_PILEUP_X_OTHER];
+    w[0] = depth; w[1] = depth - x_all - e[LRM_PILEUP_DEL]; w[2] = e[LRM_PILEUP_X_A]; w[3] = e[LRM_PILEUP_X_C];
+    w[4] = e[LRM_PILEUP_X_G]; w[5] = e[LRM_PILEUP_X_T]; w[6] = e[LRM_PILEUP_DEL]; w[7] = e[LRM_PILEUP_INS];
 }
+
+// ---- the rule on the host (lrm_pileup_add_host, lrm_pileup_cols_host; tests/models/pileup_host_harness.cpp) ----
 // One aligned read into planes of a window [lo, hi), lo < hi.  The row is walked as a lane of pileup_add_kernel walks it, 16
-// columns at a time through pile_word_step: zeros from column n on, the 16 read bytes from the lane's first query position
-// on (zeros from read_len on), the previous column of a word's first byte carried along.
+// columns at a time through pile_word_step: the 16 read bytes from the lane's first query position on (zeros from read_len on).
 static inline void pile_host_add(const uint8_t *ops, uint64_t n, const uint8_t *read, uint32_t read_len, uint64_t loc, uint64_t lo,
                                  uint64_t hi, uint32_t *planes) {
     const uint64_t W = hi - lo;
-    uint32_t t = 0, q_row = 0, prev = 0;
-    for (uint64_t c0 = 0; c0 < n; c0 += 16) {
+    uint32_t t = 0, q_row = 0;
+    op_host_walk(ops, n, [&](const uint32_t (&cw)[4], const uint32_t (&pw)[4]) {
         uint32_t qb[4];
-        for (int k = 0; k < 4; ++k) qb[k] = pile_host_word(read, (uint64_t) q_row + 4u * (uint64_t) k, read_len);
+        for (int k = 0; k < 4; ++k) qb[k] = op_host_word(read, (uint64_t) q_row + 4u * (uint64_t) k, read_len);
         uint32_t q = 0;
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t cw = pile_host_word(ops, c0 + 4u * (uint64_t) k, n);
-            const PileMasks m = pile_masks(cw, (cw << 8) | prev);
-            prev = cw >> 24;
-            pile_word_step(m, t, q, qb[0], qb[1], qb[2], qb[3], [&](uint32_t plane, uint32_t tcol) {
+        for (int k = 0; k < 4; ++k)
+            pile_word_step(op_masks(cw[k], pw[k]), t, q, qb[0], qb[1], qb[2], qb[3], [&](uint32_t plane, uint32_t tcol) {
                 const uint64_t pos = loc + tcol;
                 if (pos >= lo && pos < hi) planes[LRM_PILEUP_EVENT_PLANE(W, plane) + (pos - lo)] += 1u;
             });
-        }
         q_row += q;
-    }
+    });
     const uint64_t a = loc > lo ? loc : lo, end = loc + t, b = end < hi ? end : hi;
     if (a < b) {                                                     // the covered interval clipped to the window
         planes[a - lo] += 1u;
@@ -112,10 +98,8 @@ static inline void pile_host_cols(const uint32_t *planes, uint64_t W, uint64_t f
     for (uint64_t g = 0; g < first + count; ++g) {
         depth += planes[g];
         if (g < first) continue;
-        uint32_t e[LRM_PILEUP_PLANES];
-        for (uint32_t k = 0; k < LRM_PILEUP_PLANES; ++k) e[k] = planes[LRM_PILEUP_EVENT_PLANE(W, k) + g];
-        const uint32_t x_all = e[LRM_PILEUP_X_A] + e[LRM_PILEUP_X_C] + e[LRM_PILEUP_X_G] + e[LRM_PILEUP_X_T] + e[LRM_PILEUP_X_OTHER];
-        out[g - first] = lrm_pileup_col{depth, depth - x_all - e[LRM_PILEUP_DEL], e[LRM_PILEUP_X_A], e[LRM_PILEUP_X_C],
-                                        e[LRM_PILEUP_X_G], e[LRM_PILEUP_X_T], e[LRM_PILEUP_DEL], e[LRM_PILEUP_INS]};
+        uint32_t w[8];
+        pile_col_words(planes, W, g, depth, w);
+        out[g - first] = lrm_pileup_col{w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7]};
     }
 }

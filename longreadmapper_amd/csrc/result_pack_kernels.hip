@@ -3,6 +3,7 @@
 // link as contiguous DMA pieces.
 #include <hip/hip_runtime.h>
 #include "lrm_hip_util.h"
+#include "op_rows.h"                      // op_row_absent
 
 namespace {
 
@@ -75,7 +76,7 @@ __global__ __launch_bounds__(256) void cigar_text_kernel(const uint8_t *__restri
     const uint64_t row = blockIdx.x;
     if (row >= rows) return;
     const int n = n_ops[row];
-    const bool none = n <= 0 || meta_r[row] == 0 || score[row] == -1;
+    const bool none = op_row_absent(n, meta_r, score, row);
     uint8_t *out = WRITE ? dense + off[row] : nullptr;
     if (none) {
         if (threadIdx.x == 0) { if (WRITE) { out[0] = '*'; out[1] = 0; } else tlen[row] = 1; }
