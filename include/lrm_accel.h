@@ -23,7 +23,7 @@
  *   PART 3 result flags, alnmain.c:458-477                      lrm_result_flags (lrm_result_flags_mapq: a real MAPQ)
  *   (no counterpart: the reference prints neither NM nor MD)     lrm_aln_summary_dev, lrm_aln_diff_dev (lrm_md_format: MD:Z)
  *   (no counterpart: the reference has no per-position output)   lrm_pileup_create, lrm_pileup_add_dev, lrm_pileup_read_dev,
- *                                                                  lrm_pileup_sites_dev
+ *                                                                  lrm_pileup_sites_dev, lrm_pileup_create_ins, lrm_pileup_polish_dev
  *   context_destroy(), accaln.c:7-43                            lrm_index_free
  *   host batch loop over devices, alnmain.c:302-330             lrm_index_upload_multi (+ the same batch calls)
  *   pair_end(), alnmain.c:554-557 (unimplemented, returns -1)   lrm_pair_end
@@ -604,8 +604,8 @@ int64_t lrm_pileup_format(const lrm_mta_entry *mta, int mta_len, int seq, uint64
  *              A position is a SITE iff kinds != 0.
  *   alt, n_alt the k != rc with the largest allele[k] (a tie: the earlier of A, C, G, T) and its count; '.' when that is 0
  *   cons       'N' when depth < min_depth or allele[A..T] and n_del are all 0; otherwise the largest of the five, ties to
- *              the reference class first, then A, C, G, T, then the deletion ('-').  Insertions cannot enter it: the
- *              accumulator counts where 'I' runs open, not their bases.
+ *              the reference class first, then A, C, G, T, then the deletion ('-').  Insertions do not enter it: one
+ *              byte per position.  Their bases are the polished sequence's (lrm_pileup_create_ins, below).
  * Options: a zero field means its default (8, 4, 25); min_pct > 100 or reserved != 0 is refused. */
 #define LRM_CALL_SNV 1u
 #define LRM_CALL_DEL 2u
@@ -638,6 +638,59 @@ int64_t lrm_pileup_sites_format(const lrm_mta_entry *mta, int mta_len, const lrm
 /* Test-only: the first `words` words of the accumulator's allocation (the 8 * (hi - lo) + 1 counter words, then 16 guard
  * words of 0xC5C5C5C5) into host memory; waits for `stream`. */
 int lrm_debug_pileup_raw(lrm_pileup *pl, uint32_t *out, uint64_t words, void *stream);
+/* PILEUP INSERTIONS AND THE POLISHED CONSENSUS (docs/GACT_SPEC.md, "Pileup insertions and the polished consensus"): an
+ * accumulator may carry K insertion columns, 1 <= K <= LRM_PILEUP_INS_COLS_MAX: 4 * K more planes of hi - lo words in an
+ * allocation of their own, plane 4 * j + k for insertion column j < K and base class k in A, C, G, T.  An 'I' column that is
+ * the j-th of its run (j counted from 0), j < K, behind at least one target column, whose read byte is a base (case folded),
+ * adds 1 to plane (j, class) at the position of the target column before the run, when that lies in the window.  A read
+ * byte that is no base, or at or behind the read's length, is counted nowhere.  With s[j][k] a position's insertion words,
+ * sup[j] their 32-bit sum over k (it wraps like the counters), depth and n_ins the position's record:
+ *   len      the number of leading j < K with 2 * sup[j] > n_ins (64-bit products): the majority of the reads that insert here
+ *   bases[j] for j < len the class with the largest s[j][k], a tie to the earlier of A, C, G, T; 0 from len on
+ *   flags    LRM_INS_ENTERS: depth >= min_depth && 2 * n_ins > depth; LRM_INS_FULL: len == K (the run may be longer)
+ *   n_col0   sup[0]
+ * The polished sequence of a range, position by position in ascending order: the cons letter of the call rule, nothing for
+ * '-' ('N' stays), then, when LRM_INS_ENTERS, the len bases of the allele. */
+#define LRM_PILEUP_INS_COLS_MAX 8
+#define LRM_INS_ENTERS 1u
+#define LRM_INS_FULL 2u
+typedef struct lrm_pileup_ins_allele { uint32_t n_col0; uint8_t len, flags, pad[2]; uint8_t bases[8]; } lrm_pileup_ins_allele;   /* 16 bytes */
+/* lrm_pileup_create with ins_cols insertion columns.  ins_cols == 0 is lrm_pileup_create exactly; ins_cols > 8 is refused.
+ * The insertion planes are 16 * ins_cols * (hi - lo) bytes, zeroed, with 64 guard bytes behind them; lrm_pileup_bytes
+ * counts them, lrm_pileup_reset clears them.  On such an accumulator the one launch of lrm_pileup_add_dev also counts the
+ * insertion columns: about one more atomic add per 'I' column of a run's first ins_cols. */
+int lrm_pileup_create_ins(lrm_pileup **out, lrm_index *idx, uint64_t lo, uint64_t hi, uint32_t ins_cols);
+uint32_t lrm_pileup_ins_cols(const lrm_pileup *pl);
+/* The insertion words of window positions [first, first + count), position-major: d_out[(g - first) * 4K + 4j + k] (device
+ * memory, 16-byte aligned).  Refused on an accumulator without insertion planes.  Asynchronous; the counters are not modified. */
+int lrm_pileup_ins_read_dev(lrm_pileup *pl, uint64_t first, uint64_t count, uint32_t *d_out, void *stream);
+/* The polished sequence of window positions [first, first + count) into d_seq[0 .. cap) (device memory; may be NULL with
+ * cap == 0).  *d_len (device memory, 8-byte aligned) gets its length whether or not it fits; bytes from index cap on are not
+ * written and nothing outside d_seq[0 .. cap) is touched.  count * (K + 1) < 2^32 (checked).  On an accumulator without
+ * insertion planes: the cons letters without '-'.  opt as for lrm_pileup_sites_dev; asynchronous on `stream`, the counters
+ * are not modified; the scratch is that of lrm_pileup_sites_dev (allocated by the first call of either). */
+int lrm_pileup_polish_dev(lrm_pileup *pl, const lrm_pileup_call_options *opt, uint64_t first, uint64_t count, uint8_t *d_seq,
+                          uint64_t cap, uint64_t *d_len, void *stream);
+/* The inserted allele of every record of a site table of this accumulator (n records in device memory, as
+ * lrm_pileup_sites_dev wrote them: depth and n_ins are the record's) into d_out (n records, 16-byte aligned), zero-padded.
+ * A pos outside the window gives an all-zero record.  Refused on an accumulator without insertion planes. */
+int lrm_pileup_site_alleles_dev(lrm_pileup *pl, const lrm_pileup_call_options *opt, const lrm_pileup_site *d_sites, uint64_t n,
+                                lrm_pileup_ins_allele *d_out, void *stream);
+/* The rules on the host, usable without a GPU.  ins_planes: 4 * ins_cols * (hi - lo) words in the device's layout, zeroed by
+ * the caller; one ALIGNED read as for lrm_pileup_add_host (which counts everything else).  Bad arguments: nothing. */
+void lrm_pileup_ins_add_host(const uint8_t *ops, int n_ops, const uint8_t *read, uint32_t read_len, uint64_t loc, uint64_t lo,
+                             uint64_t hi, uint32_t ins_cols, uint32_t *ins_planes);
+/* cols[k], content[k], ins_words + 4 * ins_cols * k: the record, the text byte and the position-major insertion words of
+ * position k (ins_cols == 0: ins_words is not read).  out: cap bytes (may be NULL with cap == 0).  Returns the polished
+ * length whether or not it fits, < 0 for refused options or arguments. */
+int64_t lrm_pileup_polish_host(const lrm_pileup_col *cols, const uint32_t *ins_words, uint32_t ins_cols, const char *content,
+                               uint64_t count, const lrm_pileup_call_options *opt, uint8_t *out, uint64_t cap);
+/* The allele of one position from its 4 * ins_cols insertion words.  0 ok, < 0 refused. */
+int lrm_pileup_ins_allele_host(uint32_t depth, uint32_t n_ins, const uint32_t *ins_words, uint32_t ins_cols,
+                               const lrm_pileup_call_options *opt, lrm_pileup_ins_allele *out);
+/* Test-only: the first `words` words of the insertion planes' allocation (4 * ins_cols * (hi - lo) words, then 16 guard
+ * words of 0xC5C5C5C5) into host memory; waits for `stream`. */
+int lrm_debug_pileup_ins_raw(lrm_pileup *pl, uint32_t *out, uint64_t words, void *stream);
 
 /* SPLIT READS (lrm_map_options.split; docs/GACT_SPEC.md, "Split reads"): the soft-clipped ends of a batch that went through
  * the anchored extension with end clipping, mapped as reads of their own.  For read i with n = lens[i] bases, R the read as

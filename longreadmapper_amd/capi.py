@@ -75,6 +75,15 @@ SYMBOLS = {
     "lrm_pileup_sites_host": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "lrm_pileup_sites_format": (C.c_int64, [C.POINTER(MtaEntry), C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int64]),
     "lrm_debug_pileup_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "lrm_pileup_create_ins": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32]),
+    "lrm_pileup_ins_cols": (C.c_uint32, [C.c_void_p]),
+    "lrm_pileup_ins_read_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "lrm_pileup_polish_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "lrm_pileup_site_alleles_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "lrm_pileup_ins_add_host": (None, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p]),
+    "lrm_pileup_polish_host": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "lrm_pileup_ins_allele_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "lrm_debug_pileup_ins_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "lrm_aln_summary_host": (None, [C.c_void_p, C.c_int, C.POINTER(AlnSummary)]),
     "lrm_aln_summary_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                       C.c_void_p, C.c_void_p]),

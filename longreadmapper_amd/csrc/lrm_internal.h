@@ -364,6 +364,9 @@ struct lrm_pileup {
     int device;
     uint64_t lo, hi, W, n_tiles, bytes;
     uint32_t *d_planes, *d_tiles, *d_call;
+    // the insertion planes of pileup_ins_step.h (lrm_pileup_create_ins): 4 * ins_cols * W words and the guard words, an
+    // allocation of their own; null with ins_cols == 0
+    uint32_t *d_ins, ins_cols;
 };
 // the same rows as the summary and the events, plus the read rows (d_reads + row * stride, d_lens) the extension left; a
 // row without an alignment, or with d_mapq[row].mapq < min_mapq (d_mapq null: no filter), adds nothing
@@ -376,6 +379,15 @@ int lrm_launch_pileup_read(const lrm_pileup *pl, uint64_t first, uint64_t count,
 struct PileCallRule;
 int lrm_launch_pileup_sites(const lrm_pileup *pl, const PileCallRule &rule, uint64_t first, uint64_t count, lrm_pileup_site *d_sites,
                             uint64_t cap, uint64_t *d_n_sites, uint8_t *d_cons, void *stream);
+// the insertion side (docs/GACT_SPEC.md, "Pileup insertions and the polished consensus"): the insertion words of window
+// positions [first, first + count), count > 0, position-major; the polished sequence of the same positions (0 < count,
+// count * (ins_cols + 1) < 2^32, pl->d_call allocated: tile sums and their scan, the tiles' byte counts, their scan, the
+// bytes); the inserted allele of every record of a site table
+int lrm_launch_pileup_ins_read(const lrm_pileup *pl, uint64_t first, uint64_t count, uint32_t *d_out, void *stream);
+int lrm_launch_pileup_polish(const lrm_pileup *pl, const PileCallRule &rule, uint64_t first, uint64_t count, uint8_t *d_seq, uint64_t cap,
+                             uint64_t *d_len, void *stream);
+int lrm_launch_pileup_site_alleles(const lrm_pileup *pl, const PileCallRule &rule, const lrm_pileup_site *d_sites, uint64_t n,
+                                   lrm_pileup_ins_allele *d_out, void *stream);
 int lrm_launch_seed(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint64_t stride,
                     const uint32_t *d_lens, uint64_t n, uint32_t seed_len,
                     uint32_t thres, lrm_entry *d_best, const LrmMapTune &mt, void *stream, uint8_t *d_phase_out = nullptr);

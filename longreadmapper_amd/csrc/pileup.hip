@@ -1,10 +1,13 @@
 // pileup.hip -- the pileup accumulator (lrm_pileup; docs/GACT_SPEC.md, "Pileup" and "Pileup calls"): the object's lifetime, its
-// device-buffer entry points, the host rules' entries.  Host code only: the kernels are pileup_kernels.hip, the rules pileup_step.h and pileup_call_step.h.
+// device-buffer entry points, the host rules' entries.  Host code only: the kernels are pileup_kernels.hip, the rules pileup_step.h,
+// pileup_call_step.h and pileup_ins_step.h ("Pileup insertions and the polished consensus").
 #include <hip/hip_runtime.h>
 #include <cstdlib>
+#include <cstring>
 #include "lrm_hip_util.h"
 #include "pileup_step.h"
 #include "pileup_call_step.h"
+#include "pileup_ins_step.h"
 
 // positions [first, first + count) lie inside a window of W positions (W == 0: no window at all)
 static int pile_range_check(uint64_t W, uint64_t first, uint64_t count) {
@@ -29,13 +32,15 @@ extern "C" int lrm_pileup_cols_host(const uint32_t *planes, uint64_t lo, uint64_
 
 extern "C" void lrm_pileup_free(lrm_pileup *pl) {
     if (!pl) return;
-    if (hipSetDevice(pl->device) == hipSuccess) lrm_dev_free({pl->d_planes, pl->d_tiles, pl->d_call});
+    if (hipSetDevice(pl->device) == hipSuccess) lrm_dev_free({pl->d_planes, pl->d_tiles, pl->d_call, pl->d_ins});
     free(pl);
 }
 
-extern "C" int lrm_pileup_create(lrm_pileup **out, lrm_index *idx, uint64_t lo, uint64_t hi) {
+// ins_cols == 0: the accumulator of lrm_pileup_create, nothing more allocated or booked
+extern "C" int lrm_pileup_create_ins(lrm_pileup **out, lrm_index *idx, uint64_t lo, uint64_t hi, uint32_t ins_cols) {
     if (!out || !idx) { lrm_set_error("null argument"); return -1; }
     *out = nullptr;
+    if (ins_cols > LRM_PILEUP_INS_COLS_MAX) { lrm_set_error("pileup: %u insertion columns, at most %d", ins_cols, LRM_PILEUP_INS_COLS_MAX); return -1; }
     if (idx->n_peers > 1) { lrm_set_error("pileup: a group handle holds one text per replica; create the accumulator on one replica (lrm_index_replica)"); return -1; }
     const uint64_t con_len = idx->view.con_len;
     if (lo >= hi || hi > con_len) { lrm_set_error("pileup: window [%llu, %llu) is empty or ends behind the text (%llu positions)", (unsigned long long) lo, (unsigned long long) hi, (unsigned long long) con_len); return -1; }
@@ -55,15 +60,30 @@ extern "C" int lrm_pileup_create(lrm_pileup **out, lrm_index *idx, uint64_t lo, 
         lrm_pileup_free(pl);
         return -1;
     }
+    if (ins_cols) {                                                    // the insertion planes: guarded and zeroed like the first allocation
+        const uint64_t ins_bytes = 4ull * LRM_PILEUP_INS_WORDS(pl->W, ins_cols);
+        const LrmDevAlloc ins_table[] = {{(void **) &pl->d_ins, ins_bytes + guard_bytes}};
+        if (lrm_dev_alloc_table(ins_table, "pileup insertion bytes", &pl->bytes)) { lrm_pileup_free(pl); return -1; }
+        pl->ins_cols = ins_cols;
+        if (hipMemset(pl->d_ins, 0, ins_bytes) != hipSuccess || hipMemset((char *) pl->d_ins + ins_bytes, LRM_PILEUP_GUARD & 0xFF, guard_bytes) != hipSuccess ||
+            hipDeviceSynchronize() != hipSuccess) {
+            lrm_set_error("pileup: clearing %llu bytes failed", (unsigned long long) ins_bytes);
+            lrm_pileup_free(pl);
+            return -1;
+        }
+    }
     *out = pl;
     return 0;
 }
+extern "C" int lrm_pileup_create(lrm_pileup **out, lrm_index *idx, uint64_t lo, uint64_t hi) { return lrm_pileup_create_ins(out, idx, lo, hi, 0u); }
+extern "C" uint32_t lrm_pileup_ins_cols(const lrm_pileup *pl) { return pl ? pl->ins_cols : 0u; }
 
 extern "C" uint64_t lrm_pileup_bytes(const lrm_pileup *pl) { return pl ? pl->bytes : 0; }
 extern "C" int lrm_pileup_reset(lrm_pileup *pl, void *stream) {
     if (!pl) { lrm_set_error("null argument"); return -1; }
     if (lrm_require_device(pl->device)) return -1;
     HIPCHK(hipMemsetAsync(pl->d_planes, 0, 4ull * LRM_PILEUP_WORDS(pl->W), (hipStream_t) stream));
+    if (pl->d_ins) HIPCHK(hipMemsetAsync(pl->d_ins, 0, 4ull * LRM_PILEUP_INS_WORDS(pl->W, pl->ins_cols), (hipStream_t) stream));
     return 0;
 }
 
@@ -95,6 +115,13 @@ static int lrm_pileup_call_check(const lrm_pileup_call_options *opt, PileCallRul
     return 0;
 }
 
+// the stage's scratch (two words per tile), allocated by the first call that asks -- the sites or the polish -- and booked then
+static int lrm_pileup_call_scratch(lrm_pileup *pl) {
+    if (pl->d_call) return 0;
+    const LrmDevAlloc table[] = {{(void **) &pl->d_call, 8ull * pl->n_tiles}};
+    return lrm_dev_alloc_table(table, "pileup call bytes", &pl->bytes);
+}
+
 extern "C" int64_t lrm_pileup_sites_host(const lrm_pileup_col *cols, const char *content, uint64_t pos0, uint64_t count,
                                          const lrm_pileup_call_options *opt, lrm_pileup_site *out, uint64_t cap, uint8_t *cons) {
     PileCallRule rule;
@@ -117,10 +144,7 @@ extern "C" int lrm_pileup_sites_dev(lrm_pileup *pl, const lrm_pileup_call_option
         HIPCHK(hipMemsetAsync(d_n_sites, 0, 8, (hipStream_t) stream));
         return 0;
     }
-    if (!pl->d_call) {                                                 // the stage's scratch, on the first call that asks
-        const LrmDevAlloc table[] = {{(void **) &pl->d_call, 8ull * pl->n_tiles}};
-        if (lrm_dev_alloc_table(table, "pileup call bytes", &pl->bytes)) return -1;
-    }
+    if (lrm_pileup_call_scratch(pl)) return -1;
     return lrm_launch_pileup_sites(pl, rule, first, count, d_sites, cap, d_n_sites, d_cons, stream);
 }
 
@@ -129,6 +153,90 @@ extern "C" int lrm_debug_pileup_raw(lrm_pileup *pl, uint32_t *out, uint64_t word
     if (words > LRM_PILEUP_WORDS(pl->W) + LRM_PILEUP_GUARD_WORDS) { lrm_set_error("pileup: the accumulator holds %llu words", (unsigned long long) (LRM_PILEUP_WORDS(pl->W) + LRM_PILEUP_GUARD_WORDS)); return -1; }
     if (lrm_require_device(pl->device)) return -1;
     HIPCHK(hipMemcpyAsync(out, pl->d_planes, 4ull * words, hipMemcpyDeviceToHost, (hipStream_t) stream));
+    HIPCHK(hipStreamSynchronize((hipStream_t) stream));
+    return 0;
+}
+
+// ---- the insertion side (docs/GACT_SPEC.md, "Pileup insertions and the polished consensus"; the rules: pileup_ins_step.h) ----
+static int pile_ins_check(const lrm_pileup *pl, const char *what) {
+    if (pl->ins_cols) return 0;
+    lrm_set_error("%s: the accumulator has no insertion planes (lrm_pileup_create_ins)", what);
+    return -1;
+}
+
+extern "C" void lrm_pileup_ins_add_host(const uint8_t *ops, int n_ops, const uint8_t *read, uint32_t read_len, uint64_t loc, uint64_t lo,
+                                        uint64_t hi, uint32_t ins_cols, uint32_t *ins_planes) {
+    if (!ops || n_ops <= 0 || !ins_planes || lo >= hi || ins_cols == 0 || ins_cols > LRM_PILEUP_INS_COLS_MAX) return;
+    pile_ins_host_add(ops, (uint64_t) n_ops, read, read ? read_len : 0u, loc, lo, hi, ins_cols, ins_planes);
+}
+
+extern "C" int64_t lrm_pileup_polish_host(const lrm_pileup_col *cols, const uint32_t *ins_words, uint32_t ins_cols, const char *content,
+                                          uint64_t count, const lrm_pileup_call_options *opt, uint8_t *out, uint64_t cap) {
+    PileCallRule rule;
+    if (lrm_pileup_call_check(opt, &rule)) return -1;
+    if (ins_cols > LRM_PILEUP_INS_COLS_MAX) { lrm_set_error("pileup: %u insertion columns, at most %d", ins_cols, LRM_PILEUP_INS_COLS_MAX); return -1; }
+    if ((count && (!cols || !content || (ins_cols && !ins_words))) || (cap && !out)) { lrm_set_error("null argument"); return -1; }
+    return (int64_t) pile_host_polish(cols, ins_words, ins_cols, content, count, rule, out, cap);
+}
+
+extern "C" int lrm_pileup_ins_allele_host(uint32_t depth, uint32_t n_ins, const uint32_t *ins_words, uint32_t ins_cols,
+                                          const lrm_pileup_call_options *opt, lrm_pileup_ins_allele *out) {
+    PileCallRule rule;
+    if (lrm_pileup_call_check(opt, &rule)) return -1;
+    if (ins_cols == 0 || ins_cols > LRM_PILEUP_INS_COLS_MAX) { lrm_set_error("pileup: %u insertion columns, 1 to %d", ins_cols, LRM_PILEUP_INS_COLS_MAX); return -1; }
+    if (!ins_words || !out) { lrm_set_error("null argument"); return -1; }
+    uint32_t w[4];
+    pile_ins_allele_words(pile_ins_allele(rule, depth, n_ins, ins_words, 1u, ins_cols), w);
+    memcpy(out, w, sizeof(w));
+    return 0;
+}
+
+extern "C" int lrm_pileup_ins_read_dev(lrm_pileup *pl, uint64_t first, uint64_t count, uint32_t *d_out, void *stream) {
+    if (!pl || (count && !d_out)) { lrm_set_error("null argument"); return -1; }
+    if (pile_ins_check(pl, "pileup insertion read-back")) return -1;
+    if (pile_range_check(pl->W, first, count)) return -1;
+    if ((uintptr_t) d_out & 15u) { lrm_set_error("pileup insertion words must be 16-byte aligned"); return -1; }
+    if (count == 0) return 0;
+    if (lrm_require_device(pl->device)) return -1;
+    return lrm_launch_pileup_ins_read(pl, first, count, d_out, stream);
+}
+
+extern "C" int lrm_pileup_polish_dev(lrm_pileup *pl, const lrm_pileup_call_options *opt, uint64_t first, uint64_t count, uint8_t *d_seq,
+                                     uint64_t cap, uint64_t *d_len, void *stream) {
+    if (!pl || !d_len || (cap && !d_seq)) { lrm_set_error("null argument"); return -1; }
+    PileCallRule rule;
+    if (lrm_pileup_call_check(opt, &rule)) return -1;
+    if (pile_range_check(pl->W, first, count)) return -1;
+    if (count * (uint64_t) (pl->ins_cols + 1u) > 0xFFFFFFFFull) { lrm_set_error("pileup polish: %llu positions of up to %u bytes in one call (byte ranks are 32-bit: below 2^32 bytes)", (unsigned long long) count, pl->ins_cols + 1u); return -1; }
+    if ((uintptr_t) d_len & 7u) { lrm_set_error("the polished length must be 8-byte aligned"); return -1; }
+    if (lrm_require_device(pl->device)) return -1;
+    if (count == 0) {                                                  // no tile holds a position: the length is 0
+        HIPCHK(hipMemsetAsync(d_len, 0, 8, (hipStream_t) stream));
+        return 0;
+    }
+    if (lrm_pileup_call_scratch(pl)) return -1;
+    return lrm_launch_pileup_polish(pl, rule, first, count, d_seq, cap, d_len, stream);
+}
+
+extern "C" int lrm_pileup_site_alleles_dev(lrm_pileup *pl, const lrm_pileup_call_options *opt, const lrm_pileup_site *d_sites, uint64_t n,
+                                           lrm_pileup_ins_allele *d_out, void *stream) {
+    if (!pl || (n && (!d_sites || !d_out))) { lrm_set_error("null argument"); return -1; }
+    PileCallRule rule;
+    if (lrm_pileup_call_check(opt, &rule)) return -1;
+    if (pile_ins_check(pl, "pileup site alleles")) return -1;
+    if (((uintptr_t) d_sites | (uintptr_t) d_out) & 15u) { lrm_set_error("pileup sites and alleles must be 16-byte aligned"); return -1; }
+    if (n == 0) return 0;
+    if (lrm_require_device(pl->device)) return -1;
+    return lrm_launch_pileup_site_alleles(pl, rule, d_sites, n, d_out, stream);
+}
+
+extern "C" int lrm_debug_pileup_ins_raw(lrm_pileup *pl, uint32_t *out, uint64_t words, void *stream) {
+    if (!pl || !out) { lrm_set_error("null argument"); return -1; }
+    if (pile_ins_check(pl, "pileup")) return -1;
+    const uint64_t held = LRM_PILEUP_INS_WORDS(pl->W, pl->ins_cols) + LRM_PILEUP_GUARD_WORDS;
+    if (words > held) { lrm_set_error("pileup: the insertion planes hold %llu words", (unsigned long long) held); return -1; }
+    if (lrm_require_device(pl->device)) return -1;
+    HIPCHK(hipMemcpyAsync(out, pl->d_ins, 4ull * words, hipMemcpyDeviceToHost, (hipStream_t) stream));
     HIPCHK(hipStreamSynchronize((hipStream_t) stream));
     return 0;
 }

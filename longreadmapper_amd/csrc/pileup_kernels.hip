@@ -6,9 +6,13 @@
 // planes as they are.  The call stage (docs/GACT_SPEC.md, "Pileup calls") reads the same planes and the text: the sites --
 // the positions where the reads disagree with the text -- compacted into a table by count, scan, write at the prefix sum
 // (the idiom of compact_rows.h: no atomics, the same table whatever the scheduling), and one consensus byte per position.
+// The insertion side (docs/GACT_SPEC.md, "Pileup insertions and the polished consensus"): an accumulator with insertion
+// planes launches pileup_add_ins_kernel, the same row walk compiled with the inserted bases counted too; the polish kernels
+// write the consensus letters and the inserted bases as one sequence, compacted by the same idiom over byte counts.
 #include <hip/hip_runtime.h>
 #include "pileup_step.h"
 #include "pileup_call_step.h"
+#include "pileup_ins_step.h"
 
 namespace {
 
@@ -20,30 +24,47 @@ __device__ __forceinline__ void pile_add(uint32_t *p, uint32_t v) {
 
 // what a wavefront carries from step to step of its row, all uniform: the target-consuming and the query-consuming columns
 // so far, and the last op byte of the previous step (0 before column 0)
-struct PileRow { uint32_t t = 0, q = 0, carry = 0; };
+// (run: with insertion planes, the 'I' columns that end the previous step, saturated -- pile_ins_carry)
+struct PileRow { uint32_t t = 0, q = 0, carry = 0, run = 0; };
 
 // the window as a kernel sees it: text positions [lo, hi), W = hi - lo, the event planes behind the W + 1 depth words
 struct PileWindow { uint64_t lo, hi, W; uint32_t *planes; };
+// the insertion planes of an accumulator that has them (pileup_ins_step.h): K columns, 4 * K planes of W words
+struct PileIns { uint32_t *planes; uint32_t K; };
+
+// The 'I' columns immediately in front of a lane's first column, saturated at 16: the trailing 'I' columns of the lane before
+// it (DPP wave_shr:1) -- a lane whose 16 columns are all 'I' hands on "at least 16", which no K reaches, so no scan is
+// needed -- and for lane 0 those of the previous step's lane 63 (`carry`, uniform; 0 before column 0): op_prev_byte's shape.
+__device__ __forceinline__ uint32_t pile_ins_carry(uint32_t &carry, uint32_t trail) {
+    const uint32_t in = (uint32_t) __builtin_amdgcn_update_dpp((int) carry, (int) trail, DPP_WAVE_SHR1, 0xf, 0xf, false);   // lane 0 keeps the carry
+    carry = (uint32_t) __builtin_amdgcn_readlane((int) trail, 63);
+    return in;
+}
 
 // One step: the lane's 16 columns (zeros from column n on).  The packed scan of the lane's target-consuming and its
 // query-consuming columns gives the lane's target column and its first query byte.  The lane's at most 16 query bytes are
 // contiguous: one unaligned 16-byte read (nothing at or behind read + len), every 'X' column's byte picked out of the four
-// registers.
+// registers.  INS: the variant of an accumulator with insertion planes -- the same masks and the same 16 query bytes also
+// give the inserted bases (pile_ins_word_step); a lane whose only event is a continuing 'I' column goes on.
+template <bool INS>
 __device__ __forceinline__ void pile_step(PileRow &r, const uint4 cur, const uint8_t *__restrict__ read, uint32_t len, uint64_t loc,
-                                          const PileWindow &win) {
+                                          const PileWindow &win, const PileIns &ins) {
     const uint32_t w[4] = {cur.x, cur.y, cur.z, cur.w};
     uint32_t prev = op_prev_byte(r.carry, w[3]);
     OpMasks m[4];
-    uint32_t tc = 0, qc = 0, any = 0, any_x = 0;
+    uint32_t tc = 0, qc = 0, any = 0, any_x = 0, trail = 0;
 #pragma unroll
     for (uint32_t k = 0; k < 4; ++k) {
         m[k] = op_masks(w[k], (w[k] << 8) | prev);
         prev = w[k] >> 24;
         tc += (uint32_t) __popc(m[k].eq | m[k].x | m[k].d);
         qc += (uint32_t) __popc(m[k].eq | m[k].x | m[k].i | m[k].s);
-        any |= m[k].x | m[k].d | m[k].i_open;
-        any_x |= m[k].x;
+        any |= m[k].x | m[k].d | (INS ? m[k].i : m[k].i_open);
+        any_x |= m[k].x | (INS ? m[k].i : 0u);
+        if (INS) trail = pile_ins_run_behind(m[k].i, trail);
     }
+    uint32_t run = 0;
+    if (INS) run = pile_ins_carry(r.run, trail);
     uint32_t t_lane, q_lane;
     op_scan_pair(tc, qc, r.t, r.q, t_lane, q_lane);
     if (!any) return;
@@ -51,21 +72,28 @@ __device__ __forceinline__ void pile_step(PileRow &r, const uint4 cur, const uin
     if (any_x) qb = row_load_last_step<uint32_t>(read, q_lane, len);
     uint32_t t = t_lane, q = 0;
 #pragma unroll
-    for (uint32_t k = 0; k < 4; ++k)
+    for (uint32_t k = 0; k < 4; ++k) {
+        if (INS)                                                     // (before pile_word_step moves t and q on by the word)
+            pile_ins_word_step(m[k], t, q, run, ins.K, qb.x, qb.y, qb.z, qb.w, [&](uint32_t j, uint32_t cls, uint32_t tcol) {
+                const uint64_t pos = loc + tcol;
+                if (pos >= win.lo && pos < win.hi) pile_add(ins.planes + LRM_PILEUP_INS_PLANE(win.W, j, cls) + (pos - win.lo), 1u);
+            });
         pile_word_step(m[k], t, q, qb.x, qb.y, qb.z, qb.w, [&](uint32_t plane, uint32_t tcol) {
             const uint64_t pos = loc + tcol;
             if (pos >= win.lo && pos < win.hi) pile_add(win.planes + LRM_PILEUP_EVENT_PLANE(win.W, plane) + (pos - win.lo), 1u);
         });
+    }
 }
 
 // One wavefront per read, four per workgroup; no LDS, no barrier: the walk of op_rows.h.  A read without an alignment, a
 // filtered read and a read that starts at or behind the window's end leave before their first row load.  Lane 0 makes the
 // two depth adds once the row's target span is known.
-__global__ __launch_bounds__(256) void pileup_add_kernel(const uint8_t *__restrict__ reads, uint64_t stride, const uint32_t *__restrict__ lens,
-                                                         const uint8_t *__restrict__ store, uint64_t pitch, const int32_t *__restrict__ n_ops,
-                                                         const int32_t *__restrict__ score, const int32_t *__restrict__ meta_r,
-                                                         const lrm_seq_meta *__restrict__ meta, uint64_t rows, const lrm_mapq *__restrict__ mapq,
-                                                         uint32_t min_mapq, PileWindow win) {
+template <bool INS>
+__device__ __forceinline__ void pile_add_row(const uint8_t *__restrict__ reads, uint64_t stride, const uint32_t *__restrict__ lens,
+                                             const uint8_t *__restrict__ store, uint64_t pitch, const int32_t *__restrict__ n_ops,
+                                             const int32_t *__restrict__ score, const int32_t *__restrict__ meta_r,
+                                             const lrm_seq_meta *__restrict__ meta, uint64_t rows, const lrm_mapq *__restrict__ mapq,
+                                             uint32_t min_mapq, const PileWindow &win, const PileIns &ins) {
     uint64_t row; uint32_t lane;
     if (!op_row_of_wave(rows, row, lane)) return;
     const int nn = n_ops[row];
@@ -76,7 +104,7 @@ __global__ __launch_bounds__(256) void pileup_add_kernel(const uint8_t *__restri
     const uint8_t *read = reads + row * stride;
     const uint32_t len = lens[row];
     PileRow r;
-    op_row_walk(store + row * pitch, (uint32_t) nn, lane, [&](const uint4 cur, uint32_t) { pile_step(r, cur, read, len, loc, win); });
+    op_row_walk(store + row * pitch, (uint32_t) nn, lane, [&](const uint4 cur, uint32_t) { pile_step<INS>(r, cur, read, len, loc, win, ins); });
     if (lane == 0) {
         const uint64_t a = loc > win.lo ? loc : win.lo, end = loc + r.t, b = end < win.hi ? end : win.hi;
         if (a < b) {                                                 // the covered interval clipped to the window
@@ -84,6 +112,21 @@ __global__ __launch_bounds__(256) void pileup_add_kernel(const uint8_t *__restri
             pile_add(win.planes + (b - win.lo), 0xFFFFFFFFu);        // -1; word W when the interval reaches hi
         }
     }
+}
+// the kernel of a plain accumulator, and the variant of one with insertion planes: the same row walk, compiled twice
+__global__ __launch_bounds__(256) void pileup_add_kernel(const uint8_t *__restrict__ reads, uint64_t stride, const uint32_t *__restrict__ lens,
+                                                         const uint8_t *__restrict__ store, uint64_t pitch, const int32_t *__restrict__ n_ops,
+                                                         const int32_t *__restrict__ score, const int32_t *__restrict__ meta_r,
+                                                         const lrm_seq_meta *__restrict__ meta, uint64_t rows, const lrm_mapq *__restrict__ mapq,
+                                                         uint32_t min_mapq, PileWindow win) {
+    pile_add_row<false>(reads, stride, lens, store, pitch, n_ops, score, meta_r, meta, rows, mapq, min_mapq, win, PileIns{nullptr, 0u});
+}
+__global__ __launch_bounds__(256) void pileup_add_ins_kernel(const uint8_t *__restrict__ reads, uint64_t stride, const uint32_t *__restrict__ lens,
+                                                             const uint8_t *__restrict__ store, uint64_t pitch, const int32_t *__restrict__ n_ops,
+                                                             const int32_t *__restrict__ score, const int32_t *__restrict__ meta_r,
+                                                             const lrm_seq_meta *__restrict__ meta, uint64_t rows, const lrm_mapq *__restrict__ mapq,
+                                                             uint32_t min_mapq, PileWindow win, PileIns ins) {
+    pile_add_row<true>(reads, stride, lens, store, pitch, n_ops, score, meta_r, meta, rows, mapq, min_mapq, win, ins);
 }
 
 // the sum over the 256 threads of a workgroup, returned in every thread, and the inclusive prefix of this thread: a scan
@@ -231,6 +274,83 @@ __global__ __launch_bounds__(256) void pileup_sites_kernel(const uint32_t *__res
     });
 }
 
+// ---- the insertion side (docs/GACT_SPEC.md, "Pileup insertions and the polished consensus") ----
+// the bytes of one position inside the requested range: its cons letter and, where it enters, its inserted allele.  The
+// position's 4 * K insertion words are read only where 2 * n_ins > depth (pile_polish_at): 16 * K bytes per position otherwise.
+__device__ __forceinline__ PilePolish pile_polish_pos(const uint32_t *__restrict__ planes, uint64_t W, uint64_t g, uint32_t depth,
+                                                      const uint8_t *__restrict__ text, const PileCallRule &rule, const PileIns &ins) {
+    const PilePos p = pile_call_at(planes, W, g, depth, text, rule);
+    return pile_polish_at(rule, p.call.cons, depth, p.n_ins, ins.K, [&]() { return pile_ins_allele(rule, depth, p.n_ins, ins.planes + g, W, ins.K); });
+}
+
+// polish 1: one workgroup per tile that holds a requested position; the tile's number of BYTES goes to tile_bytes[blockIdx.x]
+__global__ __launch_bounds__(256) void pileup_polish_count_kernel(const uint32_t *__restrict__ planes, uint64_t W, const uint32_t *__restrict__ tile_base,
+                                                                  uint64_t tile0, uint64_t first, uint64_t count, const uint8_t *__restrict__ text,
+                                                                  PileCallRule rule, PileIns ins, uint32_t *__restrict__ tile_bytes) {
+    __shared__ uint32_t lds[4];
+    uint32_t mine = 0;
+    pile_tile_rescan(planes, W, tile_base, tile0 + blockIdx.x, lds, [&](uint64_t g, uint32_t depth) {
+        if (g < first || g - first >= count) return;                 // (first + count <= W: g < W here)
+        mine += pile_polish_pos(planes, W, g, depth, text, rule, ins).n;
+    });
+    uint32_t all;
+    (void) block256_incl_scan(mine, lds, all);
+    if (threadIdx.x == 0) tile_bytes[blockIdx.x] = all;
+}
+
+// polish 2 is pileup_tile_scan_kernel over the tiles' byte counts.  polish 3: one workgroup per tile again; the last one
+// writes the total as 64 bits.  A tile without a byte, or whose first byte already lies at or behind cap, leaves after its
+// scalar loads.  Otherwise the tile is evaluated again; a round's byte counts (0 .. K + 1 per thread) are ranked by a block
+// scan, the running offset carried as the depth is, and every byte goes to seq[tile base + rank] when that lies below cap:
+// byte stores (the offsets are arbitrary), nothing outside seq[0 .. cap).
+__global__ __launch_bounds__(256) void pileup_polish_write_kernel(const uint32_t *__restrict__ planes, uint64_t W, const uint32_t *__restrict__ tile_base,
+                                                                  uint64_t tile0, uint64_t first, uint64_t count, const uint8_t *__restrict__ text,
+                                                                  PileCallRule rule, PileIns ins, const uint32_t *__restrict__ tile_bytes,
+                                                                  const uint32_t *__restrict__ tile_rank, uint8_t *__restrict__ seq, uint64_t cap,
+                                                                  uint64_t *__restrict__ len_out) {
+    __shared__ uint32_t lds[4];
+    const uint32_t n_here = tile_bytes[blockIdx.x];
+    uint64_t rank = tile_rank[blockIdx.x];
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *len_out = rank + n_here;
+    if (n_here == 0 || rank >= cap) return;
+    pile_tile_rescan(planes, W, tile_base, tile0 + blockIdx.x, lds, [&](uint64_t g, uint32_t depth) {
+        PilePolish p = {};
+        if (g >= first && g - first < count) p = pile_polish_pos(planes, W, g, depth, text, rule, ins);
+        uint32_t all;
+        const uint64_t at = rank + (block256_incl_scan(p.n, lds, all) - p.n);
+        rank += all;
+#pragma unroll
+        for (uint32_t j = 0; j <= LRM_PILEUP_INS_COLS_LIMIT; ++j)
+            if (j < p.n && at + j < cap) seq[at + j] = (uint8_t) pile_polish_byte(p, j);
+    });
+}
+
+// the insertion words of positions [first, first + items / K), position-major: one thread per position and insertion column
+// reads the column's four planes and writes one aligned 16-byte group
+__global__ __launch_bounds__(256) void pileup_ins_read_kernel(const uint32_t *__restrict__ ins, uint64_t W, uint32_t K, uint64_t first, uint64_t items,
+                                                              uint4 *__restrict__ out) {
+    const uint64_t i = (uint64_t) blockIdx.x * 256u + threadIdx.x;
+    if (i >= items) return;
+    const uint64_t g = first + i / K;                                // (first + items / K <= W)
+    const uint32_t *s = ins + LRM_PILEUP_INS_PLANE(W, i % K, 0u) + g;
+    out[i] = make_uint4(s[0], s[W], s[2u * W], s[3u * W]);
+}
+
+// the inserted allele of every record of a site table, one thread per site: depth and n_ins are the record's, so no scan;
+// a pos outside the window gives an all-zero record
+__global__ __launch_bounds__(256) void pileup_site_alleles_kernel(const uint32_t *__restrict__ ins, uint64_t lo, uint64_t hi, uint32_t K,
+                                                                  PileCallRule rule, const lrm_pileup_site *__restrict__ sites, uint64_t n,
+                                                                  uint4 *__restrict__ out) {
+    const uint64_t i = (uint64_t) blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint4 *s = reinterpret_cast<const uint4 *>(sites + i);
+    const uint4 h0 = s[0], h1 = s[1];                                // pos, depth, n_ref | n_alt, n_del, n_ins, the four bytes
+    const uint64_t pos = (uint64_t) h0.x | ((uint64_t) h0.y << 32);
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    if (pos >= lo && pos < hi) pile_ins_allele_words(pile_ins_allele(rule, h0.z, h1.z, ins + (pos - lo), hi - lo, K), w);
+    out[i] = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
 // What the read-back and the call stage start with: the sums of the difference plane over the tiles up to the last requested
 // position's, and their scan into `bases`.  tile0: the tile of `first`, grid: the tiles that hold a requested position.
 struct PileTiles { uint64_t tile0; uint32_t grid, *bases; };
@@ -252,8 +372,48 @@ int lrm_launch_pileup_add(const lrm_pileup *pl, const uint8_t *d_reads, uint64_t
     uint32_t grid;
     if (op_rows_grid(b.rows, "pileup", &grid)) return -1;
     const PileWindow win = {pl->lo, pl->hi, pl->W, pl->d_planes};
-    hipLaunchKernelGGL(pileup_add_kernel, dim3(grid), dim3(256), 0, (hipStream_t) stream, d_reads, stride, d_lens, b.store, b.pitch, b.n_ops,
-                       b.score, b.meta_r, b.meta, b.rows, d_mapq, min_mapq, win);
+    if (pl->ins_cols)                                                // the same launch also counts the insertion columns
+        hipLaunchKernelGGL(pileup_add_ins_kernel, dim3(grid), dim3(256), 0, (hipStream_t) stream, d_reads, stride, d_lens, b.store, b.pitch, b.n_ops,
+                           b.score, b.meta_r, b.meta, b.rows, d_mapq, min_mapq, win, PileIns{pl->d_ins, pl->ins_cols});
+    else
+        hipLaunchKernelGGL(pileup_add_kernel, dim3(grid), dim3(256), 0, (hipStream_t) stream, d_reads, stride, d_lens, b.store, b.pitch, b.n_ops,
+                           b.score, b.meta_r, b.meta, b.rows, d_mapq, min_mapq, win);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int lrm_launch_pileup_ins_read(const lrm_pileup *pl, uint64_t first, uint64_t count, uint32_t *d_out, void *stream) {
+    const uint64_t items = count * pl->ins_cols;
+    uint32_t grid;
+    if (lrm_grid_1d((items + 255u) / 256u, "pileup insertion read-back", &grid)) return -1;
+    hipLaunchKernelGGL(pileup_ins_read_kernel, dim3(grid), dim3(256), 0, (hipStream_t) stream, pl->d_ins, pl->W, pl->ins_cols, first, items,
+                       reinterpret_cast<uint4 *>(d_out));
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int lrm_launch_pileup_polish(const lrm_pileup *pl, const PileCallRule &rule, uint64_t first, uint64_t count, uint8_t *d_seq, uint64_t cap,
+                             uint64_t *d_len, void *stream) {
+    const hipStream_t st = (hipStream_t) stream;
+    PileTiles t;
+    if (pile_launch_tile_bases(pl, first, count, "pileup polish", st, &t)) return -1;
+    uint32_t *n_here = pl->d_call, *rank = pl->d_call + pl->n_tiles;
+    const uint8_t *text = (const uint8_t *) pl->idx->view.content + pl->lo;
+    const PileIns ins = {pl->d_ins, pl->ins_cols};
+    hipLaunchKernelGGL(pileup_polish_count_kernel, dim3(t.grid), dim3(256), 0, st, pl->d_planes, pl->W, t.bases, t.tile0, first, count, text, rule, ins, n_here);
+    hipLaunchKernelGGL(pileup_tile_scan_kernel, dim3(1), dim3(1024), 0, st, n_here, (uint64_t) t.grid, rank);
+    hipLaunchKernelGGL(pileup_polish_write_kernel, dim3(t.grid), dim3(256), 0, st, pl->d_planes, pl->W, t.bases, t.tile0, first, count, text, rule, ins,
+                       n_here, rank, d_seq, cap, d_len);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int lrm_launch_pileup_site_alleles(const lrm_pileup *pl, const PileCallRule &rule, const lrm_pileup_site *d_sites, uint64_t n,
+                                   lrm_pileup_ins_allele *d_out, void *stream) {
+    uint32_t grid;
+    if (lrm_grid_1d((n + 255u) / 256u, "pileup site alleles", &grid)) return -1;
+    hipLaunchKernelGGL(pileup_site_alleles_kernel, dim3(grid), dim3(256), 0, (hipStream_t) stream, pl->d_ins, pl->lo, pl->hi, pl->ins_cols, rule,
+                       d_sites, n, reinterpret_cast<uint4 *>(d_out));
     HIPCHK(hipGetLastError());
     return 0;
 }

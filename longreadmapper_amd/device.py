@@ -29,11 +29,14 @@ class DeviceMapper:
     def __init__(self, index, n_max, max_len, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT,
                  device=0, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0, split=False,
                  split_min_len=0, seg_cap=None, seg_rows=None, mapq=False, summary=False, md=False, secondary=False, sec_cap=None,
-                 sec_min_hits=0, sec_ratio_pct=0, pileup=None, pileup_min_mapq=0):
+                 sec_min_hits=0, sec_ratio_pct=0, pileup=None, pileup_min_mapq=0, pileup_ins_cols=0):
         """pileup=(lo, hi): an accumulator over the text positions [lo, hi) (lrm_pileup_create; docs/GACT_SPEC.md, "Pileup";
         index.text_window gives a sequence's).  extend() adds every batch behind the summary and the event stages
         (lrm_pileup_add_dev) -- with mapq=True only the reads whose lrm_mapq record says mapq >= pileup_min_mapq -- and it
         stays in device memory across batches: pileup_columns() returns the PILEUP_COL_DT records, pileup_reset() clears it.
+        pileup_ins_cols=K (1..8): the accumulator also counts the bases of the first K columns of every insertion
+        (lrm_pileup_create_ins; docs/GACT_SPEC.md, "Pileup insertions and the polished consensus"): pileup_ins_columns(),
+        pileup_polish() with the inserted bases, pileup_site_alleles().
         secondary (needs mapq): secondary() after seed() and extend() finds the rival locus of every candidate read and
         extends the read there, in this mapper's extension mode (lrm_secondary_batch_dev; docs/GACT_SPEC.md, "Secondary
         alignments"); secondary_results() returns the table and the per-candidate outputs.  sec_cap: room for that many
@@ -79,9 +82,10 @@ class DeviceMapper:
         self.diff_off = self._alloc(n_max + 1, torch.int64) if md else None
         self.diff_events = self._alloc(1, torch.int32) if md else None
         self.pileup, self.pileup_window, self.pileup_min_mapq = None, None, pileup_min_mapq
+        self.pileup_ins_cols = int(pileup_ins_cols) if pileup is not None else 0
         if pileup is not None:
             pl = C.c_void_p()
-            check(lib.lrm_pileup_create(C.byref(pl), index.handle, int(pileup[0]), int(pileup[1])), "lrm_pileup_create")
+            check(lib.lrm_pileup_create_ins(C.byref(pl), index.handle, int(pileup[0]), int(pileup[1]), self.pileup_ins_cols), "lrm_pileup_create_ins")
             self.pileup, self.pileup_window = pl, (int(pileup[0]), int(pileup[1]))
         self.sec, self.n_sec = None, 0
         if secondary:
@@ -236,6 +240,57 @@ class DeviceMapper:
             cap = total
         sites = _records(d_sites[:total], capi.PILEUP_SITE_DT)
         return sites, total, (d_cons[:count].cpu().numpy() if consensus else None)
+
+    def _pileup_range(self, first, count):
+        first = 0 if first is None else first
+        return first, (self.pileup_window[1] - self.pileup_window[0] - first if count is None else count)
+
+    def pileup_ins_columns(self, first=None, count=None):
+        """The insertion words of window positions first .. first + count - 1 (default: the whole window) -> uint32 array of
+        shape (count, K, 4): [position, insertion column, base class A C G T] (lrm_pileup_ins_read_dev) --
+        DeviceMapper(..., pileup=(lo, hi), pileup_ins_cols=K)."""
+        assert self.pileup is not None
+        first, count = self._pileup_range(first, count)
+        k = self.pileup_ins_cols
+        out = self._alloc((max(count, 1), max(k, 1), 4), self.torch.int32)
+        check(lib.lrm_pileup_ins_read_dev(self.pileup, first, count, out.data_ptr(), self._stream()), "lrm_pileup_ins_read_dev")
+        return out[:count].cpu().numpy().view(np.uint32)
+
+    def pileup_polish(self, first=None, count=None, cap=None, min_depth=0, min_count=0, min_pct=0):
+        """The polished sequence of window positions first .. first + count - 1 (default: the whole window) as uint8 bytes
+        (lrm_pileup_polish_dev): the consensus letters, deleted positions dropped, the inserted bases put in where the
+        accumulator counts them (pileup_ins_cols) -- what textio.write_consensus takes for a window that is one sequence.
+        cap: the room of the first buffer (default: count + count // 64 + 64); when the bytes did not fit, the stage runs
+        once more with cap = the length -- the counters do not move, so the second call is the same question."""
+        assert self.pileup is not None
+        first, count = self._pileup_range(first, count)
+        cap = count + count // 64 + 64 if cap is None else cap
+        opt = capi.PileupCallOptions(min_depth, min_count, min_pct, 0)
+        d_len = self._alloc(1, self.torch.int64)
+        while True:
+            d_seq = self._alloc(max(cap, 1), self.torch.uint8)
+            check(lib.lrm_pileup_polish_dev(self.pileup, C.byref(opt), first, count, d_seq.data_ptr() if cap else None, cap, d_len.data_ptr(),
+                                            self._stream()), "lrm_pileup_polish_dev")
+            total = int(d_len.cpu()[0])
+            if total <= cap:
+                break
+            cap = total
+        return d_seq[:total].cpu().numpy()
+
+    def pileup_site_alleles(self, sites, min_depth=0, min_count=0, min_pct=0):
+        """The inserted allele of every record of a site table of this accumulator (pileup_sites()) -> PILEUP_INS_ALLELE_DT
+        records (lrm_pileup_site_alleles_dev): n_col0, len, flags (INS_ENTERS, INS_FULL) and the len bases."""
+        assert self.pileup is not None
+        sites = np.ascontiguousarray(sites, dtype=capi.PILEUP_SITE_DT)
+        n = len(sites)
+        opt = capi.PileupCallOptions(min_depth, min_count, min_pct, 0)
+        d_sites = self._record_tensor(max(n, 1), capi.PILEUP_SITE_DT, self.torch.int32)
+        if n:
+            d_sites[:n].copy_(self.torch.from_numpy(sites.view(np.int32).reshape(n, -1)))
+        d_out = self._record_tensor(max(n, 1), capi.PILEUP_INS_ALLELE_DT, self.torch.int32)
+        check(lib.lrm_pileup_site_alleles_dev(self.pileup, C.byref(opt), d_sites.data_ptr(), n, d_out.data_ptr(), self._stream()),
+              "lrm_pileup_site_alleles_dev")
+        return _records(d_out[:n], capi.PILEUP_INS_ALLELE_DT)
 
     def pileup_reset(self):
         assert self.pileup is not None

@@ -252,6 +252,8 @@ MAPQ_DT, SUMMARY_DT = dtype_of(Mapq), dtype_of(AlnSummary)
 SECONDARY_DT = dtype_of(Secondary)
 PILEUP_COL_DT = dtype_of(PileupCol)
 PILEUP_SITE_DT = dtype_of(PileupSite)
+# lrm_pileup_ins_allele (16 bytes): a record that crosses only as an array, so it has a dtype and no ctypes structure
+PILEUP_INS_ALLELE_DT = np.dtype([("n_col0", "<u4"), ("len", "u1"), ("flags", "u1"), ("pad", "u1", (2,)), ("bases", "u1", (8,))])
 
 N_KERNELS = 9
 MAPQ_SLOTS, MAPQ_OVERFLOW = 4096, 1    # lrm_mapq.flags
@@ -263,6 +265,8 @@ DIFF_NO_ROOM = 2**64 - 1               # lrm_batch_diff.off_out of a read whose 
 PILEUP_TILE = 2048                     # positions per workgroup of the pileup read-back
 PILEUP_PLANES = ("x_a", "x_c", "x_g", "x_t", "x_other", "n_del", "n_ins")     # the event planes behind the depth's difference plane
 CALL_SNV, CALL_DEL, CALL_INS = 1, 2, 4   # lrm_pileup_site.kinds
+PILEUP_INS_COLS_MAX = 8                # insertion columns of an accumulator (lrm_pileup_create_ins)
+INS_ENTERS, INS_FULL = 1, 2            # lrm_pileup_ins_allele.flags
 ANCHOR_ANCHORED, ANCHOR_FALLBACK, ANCHOR_NO_LEFT, ANCHOR_LEFT_CLIPPED, ANCHOR_RIGHT_CLIPPED = 1, 2, 4, 8, 16
 ANCHOR_SOFT_LEFT, ANCHOR_SOFT_RIGHT = 32, 64      # end clipping (lrm_map_options.clip)
 ANCHOR_DIAGS = 64
@@ -272,7 +276,7 @@ DEFAULT_GACT = (320, 120, 128)
 CONSTANTS = dict(LRM_N_KERNELS=N_KERNELS, LRM_MAPQ_SLOTS=MAPQ_SLOTS, LRM_MAPQ_OVERFLOW=MAPQ_OVERFLOW, LRM_SEG_RIGHT=SEG_RIGHT,
                  LRM_SEG_ALIGNED=SEG_ALIGNED, LRM_SEC_ALIGNED=SEC_ALIGNED, LRM_SEC_DUPLICATE=SEC_DUPLICATE, LRM_SPLIT_MIN_DEFAULT=SPLIT_MIN_DEFAULT, LRM_DIFF_X=DIFF_X, LRM_DIFF_D_OPEN=DIFF_D_OPEN,
                  LRM_DIFF_D_MORE=DIFF_D_MORE, LRM_PILEUP_TILE=PILEUP_TILE, LRM_CALL_SNV=CALL_SNV, LRM_CALL_DEL=CALL_DEL, LRM_CALL_INS=CALL_INS,
-                 LRM_ANCHOR_ANCHORED=ANCHOR_ANCHORED,
+                 LRM_PILEUP_INS_COLS_MAX=PILEUP_INS_COLS_MAX, LRM_INS_ENTERS=INS_ENTERS, LRM_INS_FULL=INS_FULL, LRM_ANCHOR_ANCHORED=ANCHOR_ANCHORED,
                  LRM_ANCHOR_FALLBACK=ANCHOR_FALLBACK, LRM_ANCHOR_NO_LEFT=ANCHOR_NO_LEFT, LRM_ANCHOR_LEFT_CLIPPED=ANCHOR_LEFT_CLIPPED,
                  LRM_ANCHOR_RIGHT_CLIPPED=ANCHOR_RIGHT_CLIPPED, LRM_ANCHOR_SOFT_LEFT=ANCHOR_SOFT_LEFT,
                  LRM_ANCHOR_SOFT_RIGHT=ANCHOR_SOFT_RIGHT, LRM_ANCHOR_DIAGS=ANCHOR_DIAGS, LRM_GACT_T_DEFAULT=DEFAULT_GACT[0],
@@ -302,7 +306,7 @@ def units16(nbytes):
 
 # what capi re-exports: the pointer types, the structs, the record dtypes and the header's constants -- not the helpers
 __all__ = ["u8p", "u32p", "u64p", "i32p", "STRUCTS", "LATER_STRUCTS", "BatchDiff", "Secondary", "SecondaryOptions", "SecondaryDev", "SecondaryOut",
-           "SECONDARY_DT", "PileupCol", "PILEUP_COL_DT", "PileupCallOptions", "PileupSite", "PILEUP_SITE_DT", "CALL_SNV", "CALL_DEL", "CALL_INS", "PILEUP_TILE", "PILEUP_PLANES", "SEC_ALIGNED", "SEC_DUPLICATE", "MAP_OPTION_FIELDS", "CONSTANTS", "BS_COUNTERS", *(s.__name__ for s in STRUCTS),
+           "SECONDARY_DT", "PileupCol", "PILEUP_COL_DT", "PileupCallOptions", "PileupSite", "PILEUP_SITE_DT", "PILEUP_INS_ALLELE_DT", "PILEUP_INS_COLS_MAX", "INS_ENTERS", "INS_FULL", "CALL_SNV", "CALL_DEL", "CALL_INS", "PILEUP_TILE", "PILEUP_PLANES", "SEC_ALIGNED", "SEC_DUPLICATE", "MAP_OPTION_FIELDS", "CONSTANTS", "BS_COUNTERS", *(s.__name__ for s in STRUCTS),
            "ENTRY_DT", "META_DT", "CIGAR_DT", "ANCHOR_DT", "CLIP_DT", "SEGMENT_DT", "MAPQ_DT", "SUMMARY_DT", "N_KERNELS", "MAPQ_SLOTS",
            "MAPQ_OVERFLOW", "SEG_RIGHT", "SEG_ALIGNED", "SPLIT_MIN_DEFAULT", "DIFF_X", "DIFF_D_OPEN", "DIFF_D_MORE", "DIFF_NO_ROOM", "ANCHOR_ANCHORED", "ANCHOR_FALLBACK", "ANCHOR_NO_LEFT",
            "ANCHOR_LEFT_CLIPPED", "ANCHOR_RIGHT_CLIPPED", "ANCHOR_SOFT_LEFT", "ANCHOR_SOFT_RIGHT", "ANCHOR_DIAGS"]

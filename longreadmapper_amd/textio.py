@@ -199,11 +199,17 @@ def sites_text(host, sites):
     return buf.raw[:k]
 
 
-def write_sites(path, host, sites, chunk=1 << 16):
-    """The site table as text, no header -> the number of lines."""
+def write_sites(path, host, sites, chunk=1 << 16, alleles=None):
+    """The site table as text, no header -> the number of lines.  alleles: the PILEUP_INS_ALLELE_DT records of the same sites
+    (DeviceMapper.pileup_site_alleles()); every line then ends on one more column, the inserted bases ('.' when there are none)."""
+    assert alleles is None or len(alleles) == len(sites)
     with open(path, "wb") as f:
         for p in range(0, len(sites), chunk):
-            f.write(sites_text(host, sites[p:p + chunk]))
+            text = sites_text(host, sites[p:p + chunk])
+            if alleles is not None:
+                lines = text.split(b"\n")[:-1]
+                text = b"".join(line + b"\t" + (bytes(a["bases"][:int(a["len"])]) or b".") + b"\n" for line, a in zip(lines, alleles[p:p + chunk]))
+            f.write(text)
     return len(sites)
 
 

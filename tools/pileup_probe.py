@@ -5,8 +5,13 @@ pileup_add_kernel, of the read-back of the whole window (tile sums, their scan, 
 stream shape -- of aln_diff_kernel and aln_summary_kernel; next to the read-back, in the same process, the call stage
 (docs/GACT_SPEC.md, "Pileup calls": lrm_pileup_sites_dev over the whole window, with and without the cons bytes) and the bytes
 each path would bring down the link.  Printed: ms per Gbp of reads (mean, min, max), the number of
-atomic adds of one pileup_add launch (from the accumulator itself) and the adds per second at the fastest launch.
-    python tools/pileup_probe.py       PROBE_READS / PROBE_LEN / PROBE_REF scale it down, PROBE_REPEATS (default 10)"""
+atomic adds of one pileup_add launch (from the accumulator itself) and the adds per second at the fastest launch.  Then the
+insertion side (docs/GACT_SPEC.md, "Pileup insertions and the polished consensus"): the add on two plain accumulators
+launched in turn (this build's spread against itself; with PROBE_PARENT_LIB also the parent commit's library on accumulators
+of its own, in the same process), the add with K = 4 and K = 8 insertion columns, the polish next to the sites + cons bytes,
+the site alleles and the insertion read-back.
+    python tools/pileup_probe.py       PROBE_READS / PROBE_LEN / PROBE_REF scale it down, PROBE_REPEATS (default 10),
+                                       PROBE_PARENT_LIB=<path of the parent commit's liblrm_accel.so>"""
 import ctypes as C
 import os
 import sys
@@ -109,5 +114,87 @@ raw2 = np.zeros(8 * W + 1, dtype=np.uint32)
 check(lib.lrm_debug_pileup_raw(dm.pileup, raw2.ctypes.data, len(raw2), stream), "lrm_debug_pileup_raw")
 print("  after %d launches every counter word is %d times the first launch's: %s; deepest position %d" %
       (k, k, bool(np.array_equal(raw2, raw * np.uint32(k))), int(cols_now["depth"].max())), flush=True)
+# ---- the insertion side (docs/GACT_SPEC.md, "Pileup insertions and the polished consensus") ----
+def add_to(library, handle):
+    return lambda: check(library.lrm_pileup_add_dev(
+        handle, d_reads.data_ptr(), d_reads.stride(0), d_lens.data_ptr(), dm.store.data_ptr(), dm.store_stride, dm.n_ops.data_ptr(),
+        dm.score.data_ptr(), dm.meta_r.data_ptr(), dm.meta.data_ptr(), n, None, 0, stream), "lrm_pileup_add_dev")
+
+
+def alternated(legs):
+    """legs: [(name, call)], launched in turn REPEATS times after one warm-up each -> {name: [ms]}"""
+    for _, call in legs:
+        call()
+    torch.cuda.synchronize()
+    ms = {name: [] for name, _ in legs}
+    for rep in range(REPEATS):
+        for name, call in legs:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            call()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[name].append(e0.elapsed_time(e1))
+    for name, _ in legs:
+        print("  %s: %.3f ms per Gbp (min %.3f, max %.3f; alternated)" % (name, np.mean(ms[name]) / gbp, min(ms[name]) / gbp, max(ms[name]) / gbp), flush=True)
+    return ms
+
+
+def accumulator(library, ins_cols=None):
+    h = C.c_void_p()
+    if ins_cols is None:
+        check(library.lrm_pileup_create(C.byref(h), di.handle, window[0], window[1]), "lrm_pileup_create")
+    else:
+        check(library.lrm_pileup_create_ins(C.byref(h), di.handle, window[0], window[1], ins_cols), "lrm_pileup_create_ins")
+    return h
+
+
+# the add on a plain accumulator: this build against itself (the spread) and, with PROBE_PARENT_LIB=<liblrm_accel.so of the
+# parent commit>, against the parent's kernel on an accumulator of the parent's own -- all in this process, launched in turn
+plain_a, plain_b = accumulator(lib), accumulator(lib)
+legs = [("pileup_add_kernel, plain accumulator, this build (a)", add_to(lib, plain_a)), ("pileup_add_kernel, plain accumulator, this build (b)", add_to(lib, plain_b))]
+parent_path = os.environ.get("PROBE_PARENT_LIB")
+if parent_path:
+    parent = C.CDLL(parent_path)
+    for name in ("lrm_pileup_create", "lrm_pileup_add_dev", "lrm_pileup_free"):
+        getattr(parent, name).restype, getattr(parent, name).argtypes = capi.SYMBOLS[name]
+    parent_a, parent_b = C.c_void_p(), C.c_void_p()
+    for h in (parent_a, parent_b):
+        check(parent.lrm_pileup_create(C.byref(h), di.handle, window[0], window[1]), "lrm_pileup_create (parent)")
+    legs += [("pileup_add_kernel, the parent's library (a)", add_to(parent, parent_a)), ("pileup_add_kernel, the parent's library (b)", add_to(parent, parent_b))]
+alternated(legs)
+for h in (plain_a, plain_b):
+    lib.lrm_pileup_free(h)
+if parent_path:
+    for h in (parent_a, parent_b):
+        parent.lrm_pileup_free(h)
+# the add with insertion planes, the polish next to the sites + cons bytes, the site alleles
+for ins_cols in (4, 8):
+    acc = accumulator(lib, ins_cols)
+    timed("pileup_add_ins_kernel, K = %d (%.1f MB of insertion planes)" % (ins_cols, 16 * ins_cols * W / 1e6), add_to(lib, acc))
+    if ins_cols == 8:
+        ins_raw = np.zeros(4 * ins_cols * W, dtype=np.uint32)
+        check(lib.lrm_debug_pileup_ins_raw(acc, ins_raw.ctypes.data, len(ins_raw), stream), "lrm_debug_pileup_ins_raw")
+        per_col = ins_raw.reshape(ins_cols, 4 * W).astype(np.int64).sum(axis=1) // (1 + REPEATS)
+        print("  insertion adds of one launch per column: %s (%.4f G in all, next to %.4f G event adds)" %
+              (" ".join(str(int(v)) for v in per_col), per_col.sum() / 1e9, event_adds / 1e9), flush=True)
+        d_seq = torch.zeros(W + W // 8, dtype=torch.uint8, device="cuda")
+        d_len = torch.zeros(1, dtype=torch.int64, device="cuda")
+        alternated([("pileup calls, whole window, sites + cons bytes (K = 8 accumulator)", lambda: check(lib.lrm_pileup_sites_dev(
+                        acc, None, 0, W, d_sites.data_ptr(), SITE_CAP, d_n_sites.data_ptr(), d_cons.data_ptr(), stream), "lrm_pileup_sites_dev")),
+                    ("pileup polish, whole window (K = 8 accumulator)", lambda: check(lib.lrm_pileup_polish_dev(
+                        acc, None, 0, W, d_seq.data_ptr(), d_seq.numel(), d_len.data_ptr(), stream), "lrm_pileup_polish_dev")),
+                    ("pileup polish, whole window (plain accumulator)", lambda: check(lib.lrm_pileup_polish_dev(
+                        dm.pileup, None, 0, W, d_seq.data_ptr(), d_seq.numel(), d_len.data_ptr(), stream), "lrm_pileup_polish_dev"))])
+        check(lib.lrm_pileup_polish_dev(acc, None, 0, W, d_seq.data_ptr(), d_seq.numel(), d_len.data_ptr(), stream), "lrm_pileup_polish_dev")
+        n_sites8 = int(d_n_sites.cpu()[0])
+        print("  polished length %d of %d positions; %d sites" % (int(d_len.cpu()[0]), W, n_sites8), flush=True)
+        d_alleles = torch.zeros((max(min(n_sites8, SITE_CAP), 1), 4), dtype=torch.int32, device="cuda")
+        timed("pileup site alleles, %d sites" % min(n_sites8, SITE_CAP), lambda: check(lib.lrm_pileup_site_alleles_dev(
+            acc, None, d_sites.data_ptr(), min(n_sites8, SITE_CAP), d_alleles.data_ptr(), stream), "lrm_pileup_site_alleles_dev"))
+        d_words = torch.zeros((1 << 20, ins_cols, 4), dtype=torch.int32, device="cuda")
+        timed("pileup insertion read-back, 2^20 positions", lambda: check(lib.lrm_pileup_ins_read_dev(acc, 0, 1 << 20, d_words.data_ptr(), stream),
+                                                                         "lrm_pileup_ins_read_dev"))
+    lib.lrm_pileup_free(acc)
 dm.close()
 di.close()
