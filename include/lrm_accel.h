@@ -23,7 +23,9 @@
  *   PART 3 result flags, alnmain.c:458-477                      lrm_result_flags (lrm_result_flags_mapq: a real MAPQ)
  *   (no counterpart: the reference prints neither NM nor MD)     lrm_aln_summary_dev, lrm_aln_diff_dev (lrm_md_format: MD:Z)
  *   (no counterpart: the reference has no per-position output)   lrm_pileup_create, lrm_pileup_add_dev, lrm_pileup_read_dev,
- *                                                                  lrm_pileup_sites_dev, lrm_pileup_create_ins, lrm_pileup_polish_dev
+ *                                                                  lrm_pileup_sites_dev, lrm_pileup_create_ins, lrm_pileup_polish_dev;
+ *                                                                  on host buffers lrm_map_batch_submit_ex3 (lrm_batch_pileup), one
+ *                                                                  accumulator per replica, lrm_pileup_merge_dev
  *   context_destroy(), accaln.c:7-43                            lrm_index_free
  *   host batch loop over devices, alnmain.c:302-330             lrm_index_upload_multi (+ the same batch calls)
  *   pair_end(), alnmain.c:554-557 (unimplemented, returns -1)   lrm_pair_end
@@ -691,6 +693,55 @@ int lrm_pileup_ins_allele_host(uint32_t depth, uint32_t n_ins, const uint32_t *i
 /* Test-only: the first `words` words of the insertion planes' allocation (4 * ins_cols * (hi - lo) words, then 16 guard
  * words of 0xC5C5C5C5) into host memory; waits for `stream`. */
 int lrm_debug_pileup_ins_raw(lrm_pileup *pl, uint32_t *out, uint64_t words, void *stream);
+/* PILEUP ON THE HOST-BUFFER PATH AND ACROSS REPLICAS (docs/GACT_SPEC.md, section of that name).  A host-buffer batch may name
+ * one accumulator per replica of its handle; every extension group of the batch is then added to its replica's accumulator
+ * behind the group's extension, on the group's stream, from the device mirrors of the batch (the one launch of
+ * lrm_pileup_add_dev; nothing is downloaded, no device memory is allocated for it).  The accumulators of the replicas are
+ * combined afterwards with lrm_pileup_merge_dev: all counters are integer sums.
+ * lrm_pileup_create_replica: lrm_pileup_create_ins on replica r of a handle (0 <= r < lrm_index_replicas(idx), checked) -- the
+ * way to an accumulator on replica 0 of a group handle, which is the group handle itself and which lrm_pileup_create refuses. */
+int lrm_pileup_create_replica(lrm_pileup **out, lrm_index *idx, int r, uint64_t lo, uint64_t hi, uint32_t ins_cols);
+/* The request of a batch.  pileups[r]: the accumulator of replica r, created on that replica (lrm_pileup_create_replica, or
+ * lrm_pileup_create[_ins] on a handle of one device); n_pileups == lrm_index_replicas(idx).  min_mapq: a read whose lrm_mapq
+ * record says less adds nothing; it needs lrm_batch_extras.mapq_out (the filter reads the records of that stage on the device).
+ * Refused with nothing queued: another n_pileups, an entry that is NULL or of another replica, reserved != 0, min_mapq != 0
+ * without mapq_out, store_stride above 2^31.  Contract:
+ *   - when lrm_map_batch_wait returns 0, all counts of the batch are in the accumulators: any later read-side call, on any
+ *     stream, sees them;
+ *   - several batches in flight may add to one accumulator (the adds are atomic, the sums integer); the slices of a replica's
+ *     share of one batch do;
+ *   - the accumulators must outlive the ticket; lrm_pileup_reset with a batch in flight is the caller's error;
+ *   - a batch that fails may have added part of its reads;
+ *   - lrm_split_batch and lrm_secondary_batch add nothing. */
+typedef struct lrm_batch_pileup {
+    uint32_t struct_size, min_mapq;
+    lrm_pileup **pileups;
+    uint32_t n_pileups, reserved;
+} lrm_batch_pileup;
+/* lrm_map_batch_submit_ex2 plus the request (pile == NULL: exactly lrm_map_batch_submit_ex2).  Every other output is the same
+ * bytes with it or without. */
+int lrm_map_batch_submit_ex3(lrm_index *idx, char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
+                             lrm_params p, lrm_gact_params gp, lrm_entry *best_out, lrm_cigar *cig_out,
+                             uint8_t *store_mem, uint64_t store_stride, int *score_out, lrm_seq_meta *meta_out,
+                             int *meta_r_out, const lrm_map_options *opt, const lrm_batch_extras *ex,
+                             const lrm_batch_diff *diff, const lrm_batch_pileup *pile, lrm_ticket **ticket_out);
+/* dst += src.  Both must have the same lo, hi and ins_cols and be different objects (refused otherwise).  Every one of the
+ * 8 * (hi - lo) + 1 counter words of dst -- the difference plane of the depth included -- gets src's word added, in 32 bits
+ * and wrapping like the counters; with insertion planes every one of their 16 * ins_cols * (hi - lo) / 4 words likewise.  The
+ * guard words are not touched and src is not modified (a caller who wants it empty resets it).  Asynchronous on `stream`, a
+ * stream of dst's device; the batches that add to src must have been waited for, and the caller orders other writers of dst
+ * (the kernel uses no atomics).  src on dst's device: one streaming kernel per allocation reads src's planes directly.  src
+ * on another device: a staging buffer on dst's device (allocated by the first such merge, counted by lrm_pileup_bytes(dst)
+ * from then on, freed with dst) receives src's words chunk by chunk through hipMemcpyPeerAsync on `stream`, and the kernel
+ * adds each chunk; the next copy follows the add by stream order. */
+int lrm_pileup_merge_dev(lrm_pileup *dst, const lrm_pileup *src, void *stream);
+/* Test-only: the staged route with chunks of chunk_words words (a multiple of 4, at least 4: checked) on any pair of devices. */
+int lrm_debug_pileup_merge_staged(lrm_pileup *dst, const lrm_pileup *src, uint64_t chunk_words, void *stream);
+/* lrm_pileup_sites_format with one more column at the end of every line: the inserted bases of the site, alleles[k].bases[0 ..
+ * alleles[k].len), '.' when len == 0 (alleles: what lrm_pileup_site_alleles_dev wrote for the same table).  alleles == NULL:
+ * exactly lrm_pileup_sites_format. */
+int64_t lrm_pileup_sites_format_ins(const lrm_mta_entry *mta, int mta_len, const lrm_pileup_site *sites,
+                                    const lrm_pileup_ins_allele *alleles, uint64_t count, char *buf, int64_t buflen);
 
 /* SPLIT READS (lrm_map_options.split; docs/GACT_SPEC.md, "Split reads"): the soft-clipped ends of a batch that went through
  * the anchored extension with end clipping, mapped as reads of their own.  For read i with n = lens[i] bases, R the read as

@@ -8,7 +8,7 @@
  *   SAM record printing               alnmain.c:485-527                  -> lrm_sam_format (_split, _mapq, _md)
  *   parse_cigar (gact submodule, source absent; PARITY UNPINNED)         -> lrm_parse_cigar
  *   single_end                        alnmain.c:277-551                  -> lrm_accaln
- *   (no counterpart: the reference prints SAM only)                      -> lrm_paf_format, lrm_accaln_paf
+ *   (no counterpart: the reference prints SAM only)                      -> lrm_paf_format, lrm_accaln_paf, lrm_accaln_pileup
  */
 #ifndef LRM_IO_HOST_H
 #define LRM_IO_HOST_H
@@ -151,6 +151,27 @@ int lrm_accaln_secondary(const char *genome, const char *reads_path, const char 
  * fixed-size lrm_split_out cannot carry. */
 int lrm_accaln_paf(const char *genome, const char *reads_path, const char *paf_path, lrm_params p, lrm_gact_params gp,
                    int device, uint64_t *total, uint64_t *valid, const lrm_map_options *opt, int mapq);
+
+/* The flow of lrm_accaln_mapq with a PILEUP (docs/GACT_SPEC.md, "Pileup on the host-buffer path and across replicas"; po ==
+ * NULL: lrm_accaln_mapq): every batch goes through lrm_map_batch_submit_ex3 onto one accumulator, created behind the index
+ * upload with lrm_pileup_create_ins over the window of `seq` -- one sequence of the index, or with -1 everything from the first
+ * sequence's first base to the last one's last (32 + 16 * ins_cols bytes of device memory per position: the creation error is
+ * the flow's error).  Behind the last wait the flow writes, for each selected sequence in index order from its slice of the window:
+ *   sites_path  the lines of lrm_pileup_sites_format for the sites of lrm_pileup_sites_dev with `call`; with ins_cols > 0 every
+ *               line ends on the inserted-bases column (lrm_pileup_sites_format_ins)
+ *   fasta_path  >name, then the bytes of lrm_pileup_polish_dev, 60 columns a line (ins_cols == 0: the consensus without '-')
+ * Either path may be NULL.  sam_path may be NULL here: the reads are mapped and downloaded, nothing is formatted or written;
+ * total / valid count as before.  Refused (-1) before any output file is created: min_mapq != 0 with mapq == 0, seq outside
+ * [-1, the number of sequences), a nonzero reserved field, ins_cols > 8, call.min_pct > 100. */
+typedef struct lrm_accaln_pileup_options {
+    uint32_t struct_size, ins_cols, min_mapq, reserved;
+    lrm_pileup_call_options call;
+    int32_t seq; uint32_t reserved2;
+    const char *sites_path, *fasta_path;
+} lrm_accaln_pileup_options;
+int lrm_accaln_pileup(const char *genome, const char *reads_path, const char *sam_path, lrm_params p, lrm_gact_params gp, int device,
+                      long rg_id, uint64_t *total, uint64_t *valid, const lrm_map_options *opt, int mapq,
+                      const lrm_accaln_pileup_options *po);
 
 #ifdef __cplusplus
 }

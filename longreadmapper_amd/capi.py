@@ -53,6 +53,10 @@ SYMBOLS = {
     "lrm_map_batch_submit_ex2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, Params, GactParams,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.POINTER(MapOptions), C.POINTER(BatchExtras), C.POINTER(BatchDiff), C.POINTER(C.c_void_p)]),
+    "lrm_map_batch_submit_ex3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, Params, GactParams,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(MapOptions), C.POINTER(BatchExtras), C.POINTER(BatchDiff), C.POINTER(BatchPileup),
+                                           C.POINTER(C.c_void_p)]),
     "lrm_map_batch_wait": (C.c_int, [C.c_void_p]),
     "lrm_aln_diff_offsets_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "lrm_aln_diff_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
@@ -84,6 +88,10 @@ SYMBOLS = {
     "lrm_pileup_polish_host": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]),
     "lrm_pileup_ins_allele_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "lrm_debug_pileup_ins_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "lrm_pileup_create_replica": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32]),
+    "lrm_pileup_merge_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lrm_debug_pileup_merge_staged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "lrm_pileup_sites_format_ins": (C.c_int64, [C.POINTER(MtaEntry), C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int64]),
     "lrm_aln_summary_host": (None, [C.c_void_p, C.c_int, C.POINTER(AlnSummary)]),
     "lrm_aln_summary_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                       C.c_void_p, C.c_void_p]),
@@ -214,6 +222,8 @@ SYMBOLS = {
                                  C.POINTER(MapOptions)]),
     "lrm_accaln_mapq": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, Params, GactParams, C.c_int, C.c_long, u64p, u64p,
                                   C.POINTER(MapOptions), C.c_int]),
+    "lrm_accaln_pileup": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, Params, GactParams, C.c_int, C.c_long, u64p, u64p,
+                                    C.POINTER(MapOptions), C.c_int, C.POINTER(AccalnPileupOptions)]),
 }
 
 

@@ -155,6 +155,12 @@ struct AccalnRun {
     bool split = false;                                  // after a batch's wait its clipped ends go through lrm_split_batch
     bool sec = false;                                    // ... and its candidates through lrm_secondary_batch (needs mapq)
     lrm_secondary_options so;
+    // lrm_accaln_pileup: every batch adds to one accumulator over [pile_lo, pile_hi), created behind the upload; sam_path may
+    // then be null -- the reads are mapped and downloaded, nothing is formatted or written
+    bool pile_on = false;
+    lrm_accaln_pileup_options po;
+    lrm_pileup *acc = nullptr;
+    uint64_t pile_lo = 0, pile_hi = 0;
     bool want_pinned = false;
     lrm_host_index hi;
     lrm_index *gpu = nullptr;
@@ -234,6 +240,8 @@ struct AccalnRun {
         int rc = lrm_index_upload_opt(&gpu, &hi.fmi, &hi.lch, &hi.sa, hi.content, hi.con_len, hi.mta, hi.mta_len, &device, 1, &iopt);
         t_upload = now();
         if (rc) return rc;
+        if (pile_on && lrm_pileup_create_ins(&acc, gpu, pile_lo, pile_hi, po.ins_cols)) return -1;
+        if (!sam_path) return lrm_reader_open(&rd, reads_path);       // (lrm_accaln_pileup alone)
         out_fd = open(sam_path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
         if (out_fd < 0) { lrm_set_error("cannot create: %s", sam_path); return -1; }
         if (!paf) {                                                   // (PAF has no header)
@@ -297,7 +305,11 @@ struct AccalnRun {
         BatchSet *s = nullptr;
         while (mapped.pop(s)) {
             std::unique_ptr<TextBatch> tb;
-            if (!err.get() && free_texts.pop(tb)) {
+            if (!sam_path) {                                          // no text asked for: the counters alone
+                const uint64_t n = s->b.n;
+                total += n;
+                for (uint64_t i = 0; i < n; ++i) valid += (s->score[i] >= 0 && s->meta_r[i] != 0) ? 1 : 0;
+            } else if (!err.get() && free_texts.pop(tb)) {
                 const uint64_t n = s->b.n;
                 const double t0 = now();
                 if (paf) {
@@ -429,9 +441,10 @@ struct AccalnRun {
             const double t0 = now();
             const lrm_batch_extras ex = {(uint32_t) sizeof(lrm_batch_extras), 0, mapq ? s->mq.data() : nullptr, paf || md ? s->sum.data() : nullptr};
             const lrm_batch_diff df = {(uint32_t) sizeof(lrm_batch_diff), 0, s->diff_off.data(), s->diff_cnt.data(), s->events, s->events_cap, &s->events_needed};
-            const int src = lrm_map_batch_submit_ex2(gpu, s->b.seqs, s->b.stride, s->b.lens, s->b.n, p, gp, s->best.data(), s->cig.data(),
+            const lrm_batch_pileup bp = {(uint32_t) sizeof(lrm_batch_pileup), po.min_mapq, &acc, 1u, 0u};
+            const int src = lrm_map_batch_submit_ex3(gpu, s->b.seqs, s->b.stride, s->b.lens, s->b.n, p, gp, s->best.data(), s->cig.data(),
                                                     s->store, s->sstride, s->score.data(), s->meta.data(), s->meta_r.data(), &mopt,
-                                                    &ex, md ? &df : nullptr, &s->ticket);
+                                                    &ex, md ? &df : nullptr, acc ? &bp : nullptr, &s->ticket);
             t_map += now() - t0;
             if (verbose) fprintf(stderr, "[lrm accaln] %.3f submitted %llu reads (%s store) in %.3f s\n", now() - t_upload, (unsigned long long) s->b.n, s->store == s->store_pin ? "pinned" : "pageable", now() - t0);
             if (!first_submitted) { { std::lock_guard<std::mutex> lk(dims_m); first_submitted = true; } dims_cv.notify_all(); }
@@ -440,6 +453,108 @@ struct AccalnRun {
             if (inflight.size() >= 3) finish_oldest();
         }
         while (!inflight.empty()) finish_oldest();
+    }
+
+    // ---- lrm_accaln_pileup: the sites table and the polished sequences of the selected sequences, behind the last wait ----
+    struct DevMem {                                                           // device memory of the read side, freed on every way out
+        void *p = nullptr;
+        ~DevMem() { if (p) (void) hipFree(p); }
+        int room(uint64_t bytes) {
+            if (p) (void) hipFree(p);
+            p = nullptr;
+            if (hipMalloc(&p, bytes ? bytes : 1) == hipSuccess) return 0;
+            (void) hipGetLastError();
+            p = nullptr;
+            lrm_set_error("pileup output: device allocation of %llu bytes failed", (unsigned long long) bytes);
+            return -1;
+        }
+    };
+    static int down(void *dst, const void *src, uint64_t bytes) {
+        if (bytes && hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) { (void) hipGetLastError(); lrm_set_error("pileup output: download failed"); return -1; }
+        return 0;
+    }
+    // the sites of window positions [first, first + count) as text lines; a table that did not fit is asked for again with
+    // the reported total (the counters do not move)
+    int write_sites_of(FILE *f, uint64_t first, uint64_t count) {
+        DevMem d_sites, d_n, d_al;
+        uint64_t cap = std::min<uint64_t>(count, 4096 + count / 256), n_sites = 0;
+        if (d_n.room(8)) return -1;
+        for (;;) {
+            if (d_sites.room(cap * sizeof(lrm_pileup_site))) return -1;
+            if (lrm_pileup_sites_dev(acc, &po.call, first, count, (lrm_pileup_site *) d_sites.p, cap, (uint64_t *) d_n.p, nullptr, nullptr)) return -1;
+            if (down(&n_sites, d_n.p, 8)) return -1;
+            if (n_sites <= cap) break;
+            cap = n_sites;
+        }
+        std::vector<lrm_pileup_site> sites((size_t) n_sites);
+        std::vector<lrm_pileup_ins_allele> al;
+        if (down(sites.data(), d_sites.p, n_sites * sizeof(lrm_pileup_site))) return -1;
+        if (po.ins_cols && n_sites) {
+            al.resize((size_t) n_sites);
+            if (d_al.room(n_sites * sizeof(lrm_pileup_ins_allele))) return -1;
+            if (lrm_pileup_site_alleles_dev(acc, &po.call, (const lrm_pileup_site *) d_sites.p, n_sites, (lrm_pileup_ins_allele *) d_al.p, nullptr)) return -1;
+            if (down(al.data(), d_al.p, n_sites * sizeof(lrm_pileup_ins_allele))) return -1;
+        }
+        uint64_t longest = 0;
+        for (int k = 0; k < hi.mta_len; ++k) longest = std::max<uint64_t>(longest, hi.mta[k].name ? hi.mta[k].name_len : 0);
+        const uint64_t chunk = 1u << 16;
+        std::vector<char> text((size_t) ((longest + 128) * std::min(chunk, n_sites) + 1));
+        for (uint64_t at = 0; at < n_sites; at += chunk) {
+            const uint64_t k = std::min(chunk, n_sites - at);
+            const int64_t len = lrm_pileup_sites_format_ins(hi.mta, hi.mta_len, sites.data() + at, po.ins_cols ? al.data() + at : nullptr, k, text.data(), (int64_t) text.size());
+            if (len < 0) return -1;
+            if (fwrite(text.data(), 1, (size_t) len, f) != (size_t) len) { lrm_set_error("cannot write: %s", po.sites_path); return -1; }
+        }
+        return 0;
+    }
+    // the polished bytes of window positions [first, first + count), 60 columns a line; col: the column the line stands at
+    int write_polish_of(FILE *f, uint64_t first, uint64_t count, uint32_t *col) {
+        DevMem d_seq, d_len;
+        uint64_t cap = count + count / 64 + 64, len = 0;
+        if (d_len.room(8)) return -1;
+        for (;;) {
+            if (d_seq.room(cap)) return -1;
+            if (lrm_pileup_polish_dev(acc, &po.call, first, count, (uint8_t *) d_seq.p, cap, (uint64_t *) d_len.p, nullptr)) return -1;
+            if (down(&len, d_len.p, 8)) return -1;
+            if (len <= cap) break;
+            cap = len;
+        }
+        std::vector<char> seq((size_t) len);
+        if (down(seq.data(), d_seq.p, len)) return -1;
+        std::string lines;
+        lines.reserve((size_t) (len + len / 60 + 2));
+        for (uint64_t at = 0; at < len;) {
+            const uint64_t k = std::min<uint64_t>(60u - *col, len - at);
+            lines.append(seq.data() + at, (size_t) k);
+            at += k;
+            *col += (uint32_t) k;
+            if (*col == 60u) { lines.push_back('\n'); *col = 0; }
+        }
+        if (fwrite(lines.data(), 1, lines.size(), f) != lines.size()) { lrm_set_error("cannot write: %s", po.fasta_path); return -1; }
+        return 0;
+    }
+    int write_pileup() {
+        if (hipSetDevice(device) != hipSuccess) { (void) hipGetLastError(); lrm_set_error("no HIP device %d", device); return -1; }
+        FILE *fs = nullptr, *ff = nullptr;
+        if (po.sites_path && !(fs = fopen(po.sites_path, "wb"))) { lrm_set_error("cannot create: %s", po.sites_path); return -1; }
+        if (po.fasta_path && !(ff = fopen(po.fasta_path, "wb"))) { lrm_set_error("cannot create: %s", po.fasta_path); if (fs) fclose(fs); return -1; }
+        // (site ranks and byte ranks of one call are 32-bit: a sequence goes through in pieces below both bounds)
+        const uint64_t piece = 0xFFFFFFFFull / (po.ins_cols + 1u);
+        int rc = 0;
+        for (int s = po.seq < 0 ? 0 : po.seq; !rc && s < (po.seq < 0 ? hi.mta_len : po.seq + 1); ++s) {
+            const lrm_mta_entry &m = hi.mta[s];
+            uint32_t col = 0;
+            if (ff && (fputc('>', ff) == EOF || (m.name && fwrite(m.name, 1, m.name_len, ff) != m.name_len) || fputc('\n', ff) == EOF)) { lrm_set_error("cannot write: %s", po.fasta_path); rc = -1; }
+            for (uint64_t at = 0; !rc && at < m.seq_len; at += piece) {
+                const uint64_t first = m.offset - pile_lo + at, count = std::min<uint64_t>(piece, m.seq_len - at);
+                if (fs) rc = write_sites_of(fs, first, count);
+                if (!rc && ff) rc = write_polish_of(ff, first, count, &col);
+            }
+            if (!rc && ff && col && fputc('\n', ff) == EOF) { lrm_set_error("cannot write: %s", po.fasta_path); rc = -1; }
+        }
+        if (fs && fclose(fs) != 0 && !rc) { lrm_set_error("cannot write: %s", po.sites_path); rc = -1; }
+        if (ff && fclose(ff) != 0 && !rc) { lrm_set_error("cannot write: %s", po.fasta_path); rc = -1; }
+        return rc;
     }
 
     // all batches: starts the stages, submits on this thread, and takes everything down again in the order that matters
@@ -456,9 +571,11 @@ struct AccalnRun {
         { std::lock_guard<std::mutex> lk(dims_m); dims_stop = true; }
         dims_cv.notify_all();
         pin.join();
-        const int rc = err.get();
+        int rc = err.get();
         if (rc) lrm_set_error("%s", err.msg.c_str());
+        else if (acc) rc = write_pileup();                                    // every batch has been waited for: all counts are in
         const double t_done = now();
+        if (acc) { lrm_pileup_free(acc); acc = nullptr; }
         if (gpu) { lrm_index_free(gpu); gpu = nullptr; }                      // before the pinned buffers of the sets go
         sets.clear();
         if (verbose) fprintf(stderr, "[lrm accaln] last batch written %.2f s after the upload; freeing the device image and the pinned sets %.2f s\n",
@@ -473,6 +590,7 @@ struct AccalnRun {
             fprintf(stderr, "[lrm accaln] index files %.2f s, upload %.2f s, batches %.2f s wall (busy: loader %.2f, device waits %.2f, "
                             "formatter %.2f, write %.2f)\n", t_read_idx - t_begin, t_upload - t_read_idx, now() - t_upload, t_load, t_map,
                     t_fmt, t_write);
+        if (acc) lrm_pileup_free(acc);
         if (gpu) lrm_index_free(gpu);
         lrm_host_index_free(&hi);
     }
@@ -483,13 +601,25 @@ struct AccalnRun {
 // one run of the flow: SAM (lrm_accaln*) or PAF (lrm_accaln_paf) into out_path
 static int accaln_run(const char *genome, const char *reads_path, const char *out_path, lrm_params p, lrm_gact_params gp, int device,
                       long rg_id, uint64_t *total_out, uint64_t *valid_out, const lrm_map_options *user, bool mapq, bool paf, bool md = false,
-                      const lrm_secondary_options *so = nullptr) {
+                      const lrm_secondary_options *so = nullptr, const lrm_accaln_pileup_options *po = nullptr) {
     AccalnRun r(p, gp, device, mapq, paf, md);
     memset(&r.so, 0, sizeof(r.so));
+    memset(&r.po, 0, sizeof(r.po));
     if (so) { r.sec = true; lrm_options_over_defaults(&r.so, so); }
     if (r.take_options(user)) return -1;
     if (lrm_host_index_read(genome, &r.hi)) return -1;
-    int rc = r.begin(reads_path, out_path, rg_id);
+    int rc = 0;
+    if (po) {                                                                 // the window of the accumulator: one sequence, or all of them
+        r.pile_on = true;
+        r.po = *po;
+        if (po->seq < -1 || po->seq >= r.hi.mta_len) { lrm_set_error("lrm_accaln_pileup_options.seq %d: -1 or a sequence of the index (%d)", po->seq, r.hi.mta_len); rc = -1; }
+        else if (r.hi.mta_len < 1) { lrm_set_error("the index holds no sequence"); rc = -1; }
+        else {
+            const lrm_mta_entry &a = r.hi.mta[po->seq < 0 ? 0 : po->seq], &b = r.hi.mta[po->seq < 0 ? r.hi.mta_len - 1 : po->seq];
+            r.pile_lo = a.offset; r.pile_hi = b.offset + b.seq_len;
+        }
+    }
+    if (rc == 0) rc = r.begin(reads_path, out_path, rg_id);
     if (rc == 0) rc = r.run();
     r.end();
     if (total_out) *total_out = r.total;
@@ -528,4 +658,18 @@ extern "C" int lrm_accaln_opt(const char *genome, const char *reads_path, const 
 extern "C" int lrm_accaln(const char *genome, const char *reads_path, const char *sam_path, lrm_params p,
                           lrm_gact_params gp, int device, long rg_id, uint64_t *total_out, uint64_t *valid_out) {
     return lrm_accaln_mapq(genome, reads_path, sam_path, p, gp, device, rg_id, total_out, valid_out, nullptr, 0);
+}
+// po: every batch adds to one accumulator (lrm_map_batch_submit_ex3), and behind the last wait the flow writes the sites table
+// and the polished sequences; po == NULL: lrm_accaln_mapq
+extern "C" int lrm_accaln_pileup(const char *genome, const char *reads_path, const char *sam_path, lrm_params p, lrm_gact_params gp,
+                                 int device, long rg_id, uint64_t *total_out, uint64_t *valid_out, const lrm_map_options *user, int mapq,
+                                 const lrm_accaln_pileup_options *po) {
+    if (!po) return lrm_accaln_mapq(genome, reads_path, sam_path, p, gp, device, rg_id, total_out, valid_out, user, mapq);
+    if (!genome || !reads_path) { lrm_set_error("null argument"); return -1; }
+    if (po->struct_size < sizeof(lrm_accaln_pileup_options)) { lrm_set_error("lrm_accaln_pileup_options.struct_size %u: the struct has %zu bytes", po->struct_size, sizeof(lrm_accaln_pileup_options)); return -1; }
+    if (po->reserved != 0u || po->reserved2 != 0u || po->call.reserved != 0u) { lrm_set_error("lrm_accaln_pileup_options: a reserved field is not 0"); return -1; }
+    if (po->min_mapq != 0u && mapq == 0) { lrm_set_error("lrm_accaln_pileup_options.min_mapq needs mapq (the filter reads the records of the mapping-quality stage)"); return -1; }
+    if (po->ins_cols > LRM_PILEUP_INS_COLS_MAX) { lrm_set_error("pileup: %u insertion columns, at most %d", po->ins_cols, LRM_PILEUP_INS_COLS_MAX); return -1; }
+    if (po->call.min_pct > 100u) { lrm_set_error("pileup calls: min_pct %u above 100", po->call.min_pct); return -1; }
+    return accaln_run(genome, reads_path, sam_path, p, gp, device, rg_id, total_out, valid_out, user, mapq != 0, false, false, nullptr, po);
 }

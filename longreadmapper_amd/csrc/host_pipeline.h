@@ -93,6 +93,9 @@ struct MapJob {
     // difference events (lrm_batch_diff): per read where its events are and how many (null: no stage); the event buffer and
     // its room are the batch's, shared by every slice
     uint64_t *diff_off; uint32_t *diff_cnt; uint32_t *diff_events; uint64_t diff_cap;
+    // pileup (lrm_batch_pileup): the accumulator of the replica this job runs on -- every slice of the replica's share adds to
+    // it behind its groups' extension -- and the MAPQ a read needs to be counted (null: no stage)
+    lrm_pileup *pile; uint32_t pile_min_mapq;
     MapJob slice(uint64_t o, uint64_t m) const {        // reads [o, o + m): every array of the caller moves on by o elements
         MapJob j = *this;
         j.n = m;

@@ -362,6 +362,12 @@ int plan_and_issue(LrmHostCtx &c, SliceJob &sj) {
             } else if (lrm_launch_extend(idx, S.ws_ext[xs].get(), b, j.gp, mt, c.ext[xs])) return -1;
             if (sj.want_summary &&                                             // what the alignments consist of, while the op bytes are in HBM
                 lrm_launch_aln_summary(LrmOpRows{b.store, dstride, b.n_ops, b.score, b.meta_r, b.meta, u.m}, (lrm_aln_summary *) d[A_SUMMARY].p + u.off, c.ext[xs])) return -1;
+            // the pileup of the group, from the mirrors as the extension left them (reverse-strand reads reverse-complemented in
+            // place, with keep_reads too: that option only keeps them from coming down); the MAPQ records of the group's
+            // sub-batches were complete before their ev_seed
+            if (j.pile &&
+                lrm_launch_pileup_add(j.pile, (const uint8_t *) b.reads, j.stride, b.lens, LrmOpRows{b.store, dstride, b.n_ops, b.score, b.meta_r, b.meta, u.m},
+                                      j.pile_min_mapq ? (const lrm_mapq *) d[A_MAPQ].p + u.off : nullptr, j.pile_min_mapq, c.ext[xs])) return -1;
             if (mt.cigar_text &&                                               // length of every read's run-length CIGAR text
                 lrm_launch_cigar_text(b.store, dstride, b.n_ops, b.score, b.meta_r, (uint32_t *) d[A_TLEN].p + u.off, nullptr, nullptr, u.m, c.ext[xs])) return -1;
             HIPCHK(hipEventRecord(S.ev_ext[g], c.ext[xs]));

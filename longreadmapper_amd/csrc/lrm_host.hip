@@ -11,6 +11,7 @@
 #include <cstring>
 #include <exception>
 #include "host_pipeline.h"
+#include "pileup_step.h"                       // LRM_PILEUP_MAX_STRIDE
 #include "../../include/lrm_io_host.h"     // lrm_parse_cigar: the CIGAR text of the secondary pass
 
 namespace {
@@ -70,7 +71,9 @@ int submit_replica(lrm_index *ix, const MapJob &j, const LrmMapTune &mt, lrm_tic
     return 0;
 }
 
-int submit_impl(lrm_index *idx, const MapJob &j, const lrm_map_options *opt, lrm_ticket **out, uint64_t *diff_needed_out = nullptr) {
+// piles: one accumulator per replica (lrm_batch_pileup, checked by the entry point), or null
+int submit_impl(lrm_index *idx, const MapJob &j, const lrm_map_options *opt, lrm_ticket **out, uint64_t *diff_needed_out = nullptr,
+                lrm_pileup *const *piles = nullptr) {
     LrmMapTune mt = idx->mtune;
     if (opt) lrm_call_map_tune(idx, opt, &mt);
     const uint32_t max_len = max_of(j.lens, j.n);
@@ -99,7 +102,9 @@ int submit_impl(lrm_index *idx, const MapJob &j, const lrm_map_options *opt, lrm
             for (int r = 0; r < np; ++r) {
                 const uint64_t lo = cuts[r], hi = cuts[r + 1];
                 if (hi <= lo) continue;
-                if (submit_replica(idx->peers[r], j.slice(lo, hi - lo), mt, t.get(), np)) {
+                MapJob jr = j.slice(lo, hi - lo);
+                jr.pile = piles ? piles[r] : nullptr;
+                if (submit_replica(idx->peers[r], jr, mt, t.get(), np)) {
                     // the replicas queued so far run to completion before the caller gets its buffers back
                     const std::string msg = lrm_last_error();
                     { std::unique_lock<std::mutex> lk(t->m); t->cv.wait(lk, [&] { return t->pending == 0; }); }
@@ -127,10 +132,11 @@ int wait_impl(lrm_ticket *t) {
 }
 
 // C ABI: no C++ exception may leave the library (allocation failures of the host-side bookkeeping, thread creation)
-int run_job(lrm_index *idx, const MapJob &j, const lrm_map_options *opt, lrm_ticket **ticket_out, uint64_t *diff_needed_out = nullptr) {
+int run_job(lrm_index *idx, const MapJob &j, const lrm_map_options *opt, lrm_ticket **ticket_out, uint64_t *diff_needed_out = nullptr,
+            lrm_pileup *const *piles = nullptr) {
     try {
         lrm_ticket *t = nullptr;
-        if (submit_impl(idx, j, opt, &t, diff_needed_out)) return -1;
+        if (submit_impl(idx, j, opt, &t, diff_needed_out, piles)) return -1;
         if (ticket_out) { *ticket_out = t; return 0; }
         return wait_impl(t);
     } catch (const std::exception &e) {
@@ -192,11 +198,13 @@ extern "C" int lrm_map_batch(lrm_index *idx, char *reads_buf, uint64_t stride, c
 // "Mapping quality"); summary_out: the alignment summary stage behind every group's extension ("Alignment summary and PAF").
 // diff: the difference events on top (lrm_batch_diff; docs/GACT_SPEC.md, "Difference events and MD:Z"): the stage runs when every
 // extension group is collected, into the one buffer the whole batch shares.
-extern "C" int lrm_map_batch_submit_ex2(lrm_index *idx, char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
+// pile: one accumulator per replica (lrm_batch_pileup; docs/GACT_SPEC.md, "Pileup on the host-buffer path and across replicas"):
+// every extension group is added to its replica's accumulator behind its extension.
+extern "C" int lrm_map_batch_submit_ex3(lrm_index *idx, char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
                                         lrm_params p, lrm_gact_params gp, lrm_entry *best_out, lrm_cigar *cig_out,
                                         uint8_t *store_mem, uint64_t store_stride, int *score_out, lrm_seq_meta *meta_out,
                                         int *meta_r_out, const lrm_map_options *opt, const lrm_batch_extras *ex,
-                                        const lrm_batch_diff *diff, lrm_ticket **ticket_out) {
+                                        const lrm_batch_diff *diff, const lrm_batch_pileup *pile, lrm_ticket **ticket_out) {
     if (!ticket_out) { lrm_set_error("null argument"); return -1; }
     MapJob j;
     if (map_job_of(j, idx, reads_buf, stride, lens, n, p, gp, best_out, cig_out, store_mem, store_stride, score_out, meta_out, meta_r_out)) return -1;
@@ -204,6 +212,23 @@ extern "C" int lrm_map_batch_submit_ex2(lrm_index *idx, char *reads_buf, uint64_
         const size_t have = ex->struct_size ? ex->struct_size : sizeof(*ex);
         if (have >= offsetof(lrm_batch_extras, mapq_out) + sizeof(ex->mapq_out)) j.mapq_out = ex->mapq_out;
         if (have >= offsetof(lrm_batch_extras, summary_out) + sizeof(ex->summary_out)) j.summary_out = ex->summary_out;
+    }
+    lrm_pileup *const *piles = nullptr;
+    if (pile) {                                                      // checked before anything of the request is written or queued
+        if (pile->struct_size < sizeof(lrm_batch_pileup)) { lrm_set_error("lrm_batch_pileup.struct_size %u: the struct has %zu bytes", pile->struct_size, sizeof(lrm_batch_pileup)); return -1; }
+        if (pile->reserved != 0u) { lrm_set_error("lrm_batch_pileup.reserved is %u, not 0", pile->reserved); return -1; }
+        const int np = lrm_index_replicas(idx);
+        if (!pile->pileups || pile->n_pileups != (uint32_t) np) { lrm_set_error("lrm_batch_pileup: %u accumulators for a handle of %d replicas (one per replica)", pile->pileups ? pile->n_pileups : 0u, np); return -1; }
+        for (int r = 0; r < np; ++r) {
+            const lrm_pileup *pl = pile->pileups[r];
+            if (!pl) { lrm_set_error("lrm_batch_pileup: pileups[%d] is NULL", r); return -1; }
+            if (pl->idx != lrm_index_replica(idx, r)) { lrm_set_error("lrm_batch_pileup: pileups[%d] was not created on replica %d of this handle", r, r); return -1; }
+        }
+        if (pile->min_mapq != 0u && !j.mapq_out) { lrm_set_error("lrm_batch_pileup.min_mapq needs lrm_batch_extras.mapq_out (the filter reads the records of the mapping-quality stage)"); return -1; }
+        if (store_stride > LRM_PILEUP_MAX_STRIDE) { lrm_set_error("pileup: store_stride %llu above 2^31 (the column counts of a row are 32-bit)", (unsigned long long) store_stride); return -1; }
+        piles = pile->pileups;
+        j.pile = piles[0];
+        j.pile_min_mapq = pile->min_mapq;
     }
     uint64_t *needed_out = nullptr;
     if (diff) {
@@ -213,7 +238,15 @@ extern "C" int lrm_map_batch_submit_ex2(lrm_index *idx, char *reads_buf, uint64_
         j.diff_off = diff->off_out; j.diff_cnt = diff->cnt_out; j.diff_events = diff->events_out; j.diff_cap = diff->cap;
         needed_out = diff->needed_out;
     }
-    return run_job(idx, j, opt, ticket_out, needed_out);
+    return run_job(idx, j, opt, ticket_out, needed_out, piles);
+}
+extern "C" int lrm_map_batch_submit_ex2(lrm_index *idx, char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
+                                        lrm_params p, lrm_gact_params gp, lrm_entry *best_out, lrm_cigar *cig_out,
+                                        uint8_t *store_mem, uint64_t store_stride, int *score_out, lrm_seq_meta *meta_out,
+                                        int *meta_r_out, const lrm_map_options *opt, const lrm_batch_extras *ex,
+                                        const lrm_batch_diff *diff, lrm_ticket **ticket_out) {
+    return lrm_map_batch_submit_ex3(idx, reads_buf, stride, lens, n, p, gp, best_out, cig_out, store_mem, store_stride, score_out,
+                                    meta_out, meta_r_out, opt, ex, diff, nullptr, ticket_out);
 }
 extern "C" int lrm_map_batch_submit_ex(lrm_index *idx, char *reads_buf, uint64_t stride, const uint32_t *lens, uint64_t n,
                                        lrm_params p, lrm_gact_params gp, lrm_entry *best_out, lrm_cigar *cig_out,

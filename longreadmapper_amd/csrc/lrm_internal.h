@@ -367,11 +367,17 @@ struct lrm_pileup {
     // the insertion planes of pileup_ins_step.h (lrm_pileup_create_ins): 4 * ins_cols * W words and the guard words, an
     // allocation of their own; null with ins_cols == 0
     uint32_t *d_ins, ins_cols;
+    // the staging buffer of a merge from another device (lrm_pileup_merge_dev): LRM_PILEUP_MERGE_CHUNK words, allocated by the
+    // first staged merge and booked into `bytes` then
+    uint32_t *d_stage;
 };
+#define LRM_PILEUP_MERGE_CHUNK (4ull << 20)              // words of the staging buffer (16 MiB): a multiple of 4
 // the same rows as the summary and the events, plus the read rows (d_reads + row * stride, d_lens) the extension left; a
 // row without an alignment, or with d_mapq[row].mapq < min_mapq (d_mapq null: no filter), adds nothing
 int lrm_launch_pileup_add(const lrm_pileup *pl, const uint8_t *d_reads, uint64_t stride, const uint32_t *d_lens, const LrmOpRows &b,
                           const lrm_mapq *d_mapq, uint32_t min_mapq, void *stream);
+// dst[0 .. words) += src[0 .. words), 32-bit and wrapping (pileup_merge_kernel): one launch; words == 0: nothing
+int lrm_launch_pileup_merge(uint32_t *d_dst, const uint32_t *d_src, uint64_t words, void *stream);
 // the records of window positions [first, first + count), count > 0: tile sums, their scan, the records
 int lrm_launch_pileup_read(const lrm_pileup *pl, uint64_t first, uint64_t count, lrm_pileup_col *d_out, void *stream);
 // the call stage over the same positions (docs/GACT_SPEC.md, "Pileup calls"), 0 < count < 2^32, pl->d_call allocated: tile

@@ -32,16 +32,17 @@ extern "C" int lrm_pileup_cols_host(const uint32_t *planes, uint64_t lo, uint64_
 
 extern "C" void lrm_pileup_free(lrm_pileup *pl) {
     if (!pl) return;
-    if (hipSetDevice(pl->device) == hipSuccess) lrm_dev_free({pl->d_planes, pl->d_tiles, pl->d_call, pl->d_ins});
+    if (hipSetDevice(pl->device) == hipSuccess) lrm_dev_free({pl->d_planes, pl->d_tiles, pl->d_call, pl->d_ins, pl->d_stage});
     free(pl);
 }
 
-// ins_cols == 0: the accumulator of lrm_pileup_create, nothing more allocated or booked
-extern "C" int lrm_pileup_create_ins(lrm_pileup **out, lrm_index *idx, uint64_t lo, uint64_t hi, uint32_t ins_cols) {
+// ins_cols == 0: the accumulator of lrm_pileup_create, nothing more allocated or booked.  as_replica: idx was named as one
+// replica of its handle (lrm_pileup_create_replica) -- replica 0 of a group handle is the group handle itself
+static int pile_create(lrm_pileup **out, lrm_index *idx, uint64_t lo, uint64_t hi, uint32_t ins_cols, bool as_replica) {
     if (!out || !idx) { lrm_set_error("null argument"); return -1; }
     *out = nullptr;
     if (ins_cols > LRM_PILEUP_INS_COLS_MAX) { lrm_set_error("pileup: %u insertion columns, at most %d", ins_cols, LRM_PILEUP_INS_COLS_MAX); return -1; }
-    if (idx->n_peers > 1) { lrm_set_error("pileup: a group handle holds one text per replica; create the accumulator on one replica (lrm_index_replica)"); return -1; }
+    if (!as_replica && idx->n_peers > 1) { lrm_set_error("pileup: a group handle holds one text per replica; create the accumulator on one replica (lrm_index_replica)"); return -1; }
     const uint64_t con_len = idx->view.con_len;
     if (lo >= hi || hi > con_len) { lrm_set_error("pileup: window [%llu, %llu) is empty or ends behind the text (%llu positions)", (unsigned long long) lo, (unsigned long long) hi, (unsigned long long) con_len); return -1; }
     if (lrm_require_device(idx->device)) return -1;
@@ -75,7 +76,15 @@ extern "C" int lrm_pileup_create_ins(lrm_pileup **out, lrm_index *idx, uint64_t 
     *out = pl;
     return 0;
 }
-extern "C" int lrm_pileup_create(lrm_pileup **out, lrm_index *idx, uint64_t lo, uint64_t hi) { return lrm_pileup_create_ins(out, idx, lo, hi, 0u); }
+extern "C" int lrm_pileup_create_ins(lrm_pileup **out, lrm_index *idx, uint64_t lo, uint64_t hi, uint32_t ins_cols) { return pile_create(out, idx, lo, hi, ins_cols, false); }
+extern "C" int lrm_pileup_create(lrm_pileup **out, lrm_index *idx, uint64_t lo, uint64_t hi) { return pile_create(out, idx, lo, hi, 0u, false); }
+extern "C" int lrm_pileup_create_replica(lrm_pileup **out, lrm_index *idx, int r, uint64_t lo, uint64_t hi, uint32_t ins_cols) {
+    if (!out || !idx) { lrm_set_error("null argument"); return -1; }
+    *out = nullptr;
+    lrm_index *rep = lrm_index_replica(idx, r);
+    if (!rep) { lrm_set_error("pileup: replica %d of a handle of %d", r, lrm_index_replicas(idx)); return -1; }
+    return pile_create(out, rep, lo, hi, ins_cols, true);
+}
 extern "C" uint32_t lrm_pileup_ins_cols(const lrm_pileup *pl) { return pl ? pl->ins_cols : 0u; }
 
 extern "C" uint64_t lrm_pileup_bytes(const lrm_pileup *pl) { return pl ? pl->bytes : 0; }
@@ -155,6 +164,46 @@ extern "C" int lrm_debug_pileup_raw(lrm_pileup *pl, uint32_t *out, uint64_t word
     HIPCHK(hipMemcpyAsync(out, pl->d_planes, 4ull * words, hipMemcpyDeviceToHost, (hipStream_t) stream));
     HIPCHK(hipStreamSynchronize((hipStream_t) stream));
     return 0;
+}
+
+// ---- the merge (docs/GACT_SPEC.md, "Pileup on the host-buffer path and across replicas") ----
+// dst += src over both allocations.  chunk == 0: the kernel reads src's planes directly (one device).  Otherwise src's words
+// cross chunk by chunk into dst's staging buffer and the kernel adds each chunk; copy and add alternate by stream order.
+static int pile_merge(lrm_pileup *dst, const lrm_pileup *src, uint64_t chunk, void *stream) {
+    if (!dst || !src) { lrm_set_error("null argument"); return -1; }
+    if (dst == src) { lrm_set_error("pileup merge: dst and src are the same accumulator"); return -1; }
+    if (dst->lo != src->lo || dst->hi != src->hi) {
+        lrm_set_error("pileup merge: windows [%llu, %llu) and [%llu, %llu) differ", (unsigned long long) dst->lo, (unsigned long long) dst->hi,
+                      (unsigned long long) src->lo, (unsigned long long) src->hi);
+        return -1;
+    }
+    if (dst->ins_cols != src->ins_cols) { lrm_set_error("pileup merge: %u and %u insertion columns", dst->ins_cols, src->ins_cols); return -1; }
+    if (chunk > LRM_PILEUP_MERGE_CHUNK) { lrm_set_error("pileup merge: a chunk of %llu words, the staging buffer holds %llu", (unsigned long long) chunk, (unsigned long long) LRM_PILEUP_MERGE_CHUNK); return -1; }
+    if (lrm_require_device(dst->device)) return -1;
+    if (chunk && !dst->d_stage) {
+        const LrmDevAlloc table[] = {{(void **) &dst->d_stage, 4ull * LRM_PILEUP_MERGE_CHUNK}};
+        if (lrm_dev_alloc_table(table, "pileup merge staging bytes", &dst->bytes)) return -1;
+    }
+    const hipStream_t st = (hipStream_t) stream;
+    const struct { uint32_t *d; const uint32_t *s; uint64_t words; } parts[2] = {
+        {dst->d_planes, src->d_planes, LRM_PILEUP_WORDS(dst->W)}, {dst->d_ins, src->d_ins, dst->ins_cols ? LRM_PILEUP_INS_WORDS(dst->W, dst->ins_cols) : 0u}};
+    for (const auto &p : parts) {
+        if (!chunk) { if (lrm_launch_pileup_merge(p.d, p.s, p.words, stream)) return -1; continue; }
+        for (uint64_t off = 0; off < p.words; off += chunk) {
+            const uint64_t n = p.words - off < chunk ? p.words - off : chunk;
+            if (src->device == dst->device) HIPCHK(hipMemcpyAsync(dst->d_stage, p.s + off, 4ull * n, hipMemcpyDeviceToDevice, st));
+            else HIPCHK(hipMemcpyPeerAsync(dst->d_stage, dst->device, p.s + off, src->device, 4ull * n, st));
+            if (lrm_launch_pileup_merge(p.d + off, dst->d_stage, n, stream)) return -1;
+        }
+    }
+    return 0;
+}
+extern "C" int lrm_pileup_merge_dev(lrm_pileup *dst, const lrm_pileup *src, void *stream) {
+    return pile_merge(dst, src, dst && src && dst->device != src->device ? LRM_PILEUP_MERGE_CHUNK : 0u, stream);
+}
+extern "C" int lrm_debug_pileup_merge_staged(lrm_pileup *dst, const lrm_pileup *src, uint64_t chunk_words, void *stream) {
+    if (chunk_words < 4u || (chunk_words & 3u)) { lrm_set_error("pileup merge: a chunk of %llu words, not a multiple of 4 of at least 4", (unsigned long long) chunk_words); return -1; }
+    return pile_merge(dst, src, chunk_words, stream);
 }
 
 // ---- the insertion side (docs/GACT_SPEC.md, "Pileup insertions and the polished consensus"; the rules: pileup_ins_step.h) ----

@@ -351,6 +351,22 @@ __global__ __launch_bounds__(256) void pileup_site_alleles_kernel(const uint32_t
     out[i] = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
+// the merge of two accumulators (docs/GACT_SPEC.md, "Pileup on the host-buffer path and across replicas"): dst[w] += src[w] for
+// w < words, 32-bit and wrapping like the counters.  A plain stream, no LDS, no atomics (the caller orders the writers of dst):
+// the first `quads` groups of four words go through 16-byte loads and one 16-byte store each -- quads is words / 4 when both
+// pointers are 16-byte aligned, 0 otherwise --, the words behind them one by one.  An allocation holds 8 W + 1 words, so
+// there is always such a tail.  Nothing at or behind word `words` of either side is touched.
+__global__ __launch_bounds__(256) void pileup_merge_kernel(uint32_t *__restrict__ dst, const uint32_t *__restrict__ src, uint64_t words, uint64_t quads) {
+    const uint64_t tid = (uint64_t) blockIdx.x * 256u + threadIdx.x, step = (uint64_t) gridDim.x * 256u;
+    uint4 *d4 = reinterpret_cast<uint4 *>(dst);
+    const uint4 *s4 = reinterpret_cast<const uint4 *>(src);
+    for (uint64_t q = tid; q < quads; q += step) {
+        const uint4 a = d4[q], b = s4[q];
+        d4[q] = make_uint4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+    }
+    for (uint64_t w = 4u * quads + tid; w < words; w += step) dst[w] += src[w];
+}
+
 // What the read-back and the call stage start with: the sums of the difference plane over the tiles up to the last requested
 // position's, and their scan into `bases`.  tile0: the tile of `first`, grid: the tiles that hold a requested position.
 struct PileTiles { uint64_t tile0; uint32_t grid, *bases; };
@@ -378,6 +394,17 @@ int lrm_launch_pileup_add(const lrm_pileup *pl, const uint8_t *d_reads, uint64_t
     else
         hipLaunchKernelGGL(pileup_add_kernel, dim3(grid), dim3(256), 0, (hipStream_t) stream, d_reads, stride, d_lens, b.store, b.pitch, b.n_ops,
                            b.score, b.meta_r, b.meta, b.rows, d_mapq, min_mapq, win);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// four 16-byte groups per thread until the grid covers the chip a few times over, a grid-stride loop from there on
+int lrm_launch_pileup_merge(uint32_t *d_dst, const uint32_t *d_src, uint64_t words, void *stream) {
+    if (words == 0) return 0;
+    const uint64_t quads = (((uintptr_t) d_dst | (uintptr_t) d_src) & 15u) ? 0u : words / 4u;
+    const uint64_t items = quads ? quads : words, blocks = (items + 1023u) / 1024u;
+    const uint32_t grid = (uint32_t) (blocks < 1u ? 1u : (blocks > 8192u ? 8192u : blocks));
+    hipLaunchKernelGGL(pileup_merge_kernel, dim3(grid), dim3(256), 0, (hipStream_t) stream, d_dst, d_src, words, quads);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -1,4 +1,4 @@
-// pileup_text.cpp -- pileup records as text (lrm_pileup_format, lrm_pileup_sites_format, include/lrm_accel.h; docs/GACT_SPEC.md, "Pileup", "Pileup calls").  Host-side
+// pileup_text.cpp -- pileup records as text (lrm_pileup_format, lrm_pileup_sites_format[_ins], include/lrm_accel.h; docs/GACT_SPEC.md, "Pileup", "Pileup calls").  Host-side
 // C++; the numbers go through put_uint of sam_text.h.
 #include <cstdint>
 #include <cstring>
@@ -65,8 +65,9 @@ int pileup_put_site_line(char *dst, const char *name, uint64_t name_len, uint64_
     return (int) (p - dst);
 }
 
-extern "C" int64_t lrm_pileup_sites_format(const lrm_mta_entry *mta, int mta_len, const lrm_pileup_site *sites, uint64_t count, char *buf,
-                                           int64_t buflen) {
+// alleles (may be null): one more column per line, the inserted bases of the site or '.' (lrm_pileup_sites_format_ins)
+extern "C" int64_t lrm_pileup_sites_format_ins(const lrm_mta_entry *mta, int mta_len, const lrm_pileup_site *sites,
+                                               const lrm_pileup_ins_allele *alleles, uint64_t count, char *buf, int64_t buflen) {
     if (!mta || mta_len <= 0 || !buf || buflen <= 0 || (count && !sites)) { lrm_set_error("null argument"); return -1; }
     int64_t at = 0;
     int seq = 0;                                                       // sites come in ascending position: start at the last sequence found
@@ -80,9 +81,21 @@ extern "C" int64_t lrm_pileup_sites_format(const lrm_mta_entry *mta, int mta_len
         if (tried == mta_len) { lrm_set_error("pileup sites text: position %llu lies in no sequence", (unsigned long long) pos); return -1; }
         const lrm_mta_entry &m = mta[seq];
         const uint64_t name_len = m.name ? m.name_len : 0;
-        if ((uint64_t) (buflen - at) < pileup_site_line_room(name_len) + 1) { lrm_set_error("pileup sites text: buffer of %lld bytes too small", (long long) buflen); return -2; }   // (+1: the NUL)
+        if ((uint64_t) (buflen - at) < pileup_site_line_room(name_len) + 1 + (alleles ? 1u + LRM_PILEUP_INS_COLS_MAX : 0u)) { lrm_set_error("pileup sites text: buffer of %lld bytes too small", (long long) buflen); return -2; }   // (+1: the NUL)
         at += pileup_put_site_line(buf + at, m.name ? m.name : "", name_len, pos - m.offset + 1, sites[k]);
+        if (alleles) {                                                 // the line's '\n' moves behind the new column
+            const uint32_t len = alleles[k].len < LRM_PILEUP_INS_COLS_MAX ? alleles[k].len : LRM_PILEUP_INS_COLS_MAX;
+            buf[at - 1] = '\t';
+            if (len == 0) buf[at++] = '.';
+            memcpy(buf + at, alleles[k].bases, len);
+            at += len;
+            buf[at++] = '\n';
+        }
     }
     buf[at] = '\0';
     return at;
+}
+extern "C" int64_t lrm_pileup_sites_format(const lrm_mta_entry *mta, int mta_len, const lrm_pileup_site *sites, uint64_t count, char *buf,
+                                           int64_t buflen) {
+    return lrm_pileup_sites_format_ins(mta, mta_len, sites, nullptr, count, buf, buflen);
 }

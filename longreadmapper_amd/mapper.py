@@ -256,8 +256,12 @@ def ops_of(res, i):
 
 def map_batch_submit(index, reads, lens, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT, store=None,
                      options=None, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0, mapq=False,
-                     summary=False, md=False, md_cap=None, md_events=None):
-    """md_events: a caller-provided uint32 array for the events (needs md_cap; e.g. pinned_empty).  md=True (lrm_map_batch_submit_ex2): the result gains the difference events of the batch -- md_off, md_cnt (per read),
+                     summary=False, md=False, md_cap=None, md_events=None, pileup=None, pileup_min_mapq=0):
+    """pileup: a pileup.Pileup, or a list with one per replica of the handle (lrm_map_batch_submit_ex3; docs/GACT_SPEC.md, "Pileup on
+    the host-buffer path and across replicas"): every extension group of the batch is added to its replica's accumulator; with
+    mapq=True only the reads whose record says mapq >= pileup_min_mapq.  All counts are in when wait() returns; every other
+    output is the same bytes.
+    md_events: a caller-provided uint32 array for the events (needs md_cap; e.g. pinned_empty).  md=True (lrm_map_batch_submit_ex2): the result gains the difference events of the batch -- md_off, md_cnt (per read),
     md_events (uint32 words; read i's are md_events[md_off[i]:md_off[i] + md_cnt[i]], md_off[i] == DIFF_NO_ROOM: no room) and
     md_needed, the batch's total; md_cap: room for that many events (None: the bound n * store_stride).
     lrm_map_batch_submit_ex (mapq=True: the result gains "mapq", the MAPQ_DT records of the batch; summary=True: it gains
@@ -274,6 +278,17 @@ def map_batch_submit(index, reads, lens, seed_len=DEFAULT_SEED_LEN, thres=DEFAUL
     ticket = C.c_void_p()
     ex = capi.BatchExtras(C.sizeof(capi.BatchExtras), 0, buf.extras["mapq"].ctypes.data if mapq else None,
                           buf.extras["summary"].ctypes.data if summary else None)
+    if pileup is not None:
+        piles = list(pileup) if isinstance(pileup, (list, tuple)) else [pileup]
+        arr = (C.c_void_p * max(len(piles), 1))(*[None if a is None else a.handle for a in piles])
+        bp = capi.BatchPileup(C.sizeof(capi.BatchPileup), pileup_min_mapq, arr, len(piles), 0)
+        check(lib.lrm_map_batch_submit_ex3(index.handle, *batch, capi.Params(n, seed_len, thres), capi.GactParams(*gact),
+                                           buf.best.ctypes.data, *buf.out_args, C.byref(opt) if opt is not None else None,
+                                           C.byref(ex) if buf.extras else None, C.byref(buf.diff) if md else None, C.byref(bp),
+                                           C.byref(ticket)), "lrm_map_batch_submit_ex3")
+        text = bool(opt.cigar_text) if opt is not None else False
+        dense = (bool(opt.dense_results) or text) if opt is not None else False
+        return PendingBatch(ticket, buf, (reads, lens, *piles), dense, text)          # (the accumulators outlive the ticket)
     if md:
         check(lib.lrm_map_batch_submit_ex2(index.handle, *batch, capi.Params(n, seed_len, thres), capi.GactParams(*gact),
                                            buf.best.ctypes.data, *buf.out_args, C.byref(opt) if opt is not None else None,
@@ -290,17 +305,18 @@ def map_batch_submit(index, reads, lens, seed_len=DEFAULT_SEED_LEN, thres=DEFAUL
 
 def map_batch(index, reads, lens, seed_len=DEFAULT_SEED_LEN, thres=DEFAULT_THRES, gact=DEFAULT_GACT, store=None,
               options=None, anchored=False, anchor_min_len=0, clip=False, clip_penalty=0, clip_end_bonus=0, mapq=False, summary=False,
-              md=False, md_cap=None, md_events=None):
-    """PART 1 + PART 2 in one device pass; `reads` is modified in place like extend_batch.
+              md=False, md_cap=None, md_events=None, pileup=None, pileup_min_mapq=0):
+    """pileup, pileup_min_mapq: see map_batch_submit (submit + wait).
+    PART 1 + PART 2 in one device pass; `reads` is modified in place like extend_batch.
     Without `options` this is lrm_map_batch (the handle's default options), with them (or with anchored=True or
     clip=True, which are among them) submit + wait.  mapq=True: the mapping-quality records (MAPQ_DT) come back as
     res["mapq"] next to the other results, which do not change; summary=True: the alignment summary records (SUMMARY_DT) as
     res["summary"], likewise (submit + wait through lrm_map_batch_submit_ex); md=True: the difference events as md_off, md_cnt,
     md_events and md_needed (map_batch_submit)."""
     options = _anchor_options(options, anchored, anchor_min_len, clip, clip_penalty, clip_end_bonus)
-    if options is not None or mapq or summary or md:
+    if options is not None or mapq or summary or md or pileup is not None:
         return map_batch_submit(index, reads, lens, seed_len, thres, gact, store, options, mapq=mapq, summary=summary, md=md,
-                                md_cap=md_cap, md_events=md_events).wait()
+                                md_cap=md_cap, md_events=md_events, pileup=pileup, pileup_min_mapq=pileup_min_mapq).wait()
     lens, n, max_len, batch = _batch(reads, lens)
     buf = ResultBuffers(n, max(store_need(max_len, False), 1), store)
     check(lib.lrm_map_batch(index.handle, *batch, capi.Params(n, seed_len, thres), capi.GactParams(*gact), buf.best.ctypes.data,

@@ -199,7 +199,19 @@ class _PileupSite(C.Structure):
         (name, C.c_uint8) for name in ("ref", "alt", "cons", "kinds")]
 
 
+class _BatchPileup(C.Structure):       # host pointers; docs/GACT_SPEC.md, "Pileup on the host-buffer path and across replicas"
+    _fields_ = [("struct_size", C.c_uint32), ("min_mapq", C.c_uint32), ("pileups", C.POINTER(C.c_void_p)), ("n_pileups", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class _AccalnPileupOptions(C.Structure):       # include/lrm_io_host.h
+    _fields_ = [("struct_size", C.c_uint32), ("ins_cols", C.c_uint32), ("min_mapq", C.c_uint32), ("reserved", C.c_uint32),
+                ("call", _PileupCallOptions), ("seq", C.c_int32), ("reserved2", C.c_uint32), ("sites_path", C.c_char_p),
+                ("fasta_path", C.c_char_p)]
+
+
 PileupCol, PileupCallOptions, PileupSite = _PileupCol, _PileupCallOptions, _PileupSite
+BatchPileup, AccalnPileupOptions = _BatchPileup, _AccalnPileupOptions
 
 
 class GactTable(C.Structure):          # host pointers
@@ -243,7 +255,8 @@ MAP_OPTION_FIELDS = _MAP_OPTION_WORDS + ("split", "split_min_len")
 # are listed here and compared in the same way by the tests of their feature (tests/test_aln_diff_cpu.py)
 LATER_STRUCTS = {BatchDiff: "lrm_batch_diff", Secondary: "lrm_secondary", SecondaryOptions: "lrm_secondary_options",
                  SecondaryDev: "lrm_secondary_dev", SecondaryOut: "lrm_secondary_out", PileupCol: "lrm_pileup_col",
-                 PileupCallOptions: "lrm_pileup_call_options", PileupSite: "lrm_pileup_site"}
+                 PileupCallOptions: "lrm_pileup_call_options", PileupSite: "lrm_pileup_site", BatchPileup: "lrm_batch_pileup",
+                 AccalnPileupOptions: "lrm_accaln_pileup_options"}
 
 # the records that cross the boundary as arrays
 ENTRY_DT, META_DT, CIGAR_DT = dtype_of(Entry), dtype_of(SeqMeta), dtype_of(Cigar)
@@ -306,7 +319,7 @@ def units16(nbytes):
 
 # what capi re-exports: the pointer types, the structs, the record dtypes and the header's constants -- not the helpers
 __all__ = ["u8p", "u32p", "u64p", "i32p", "STRUCTS", "LATER_STRUCTS", "BatchDiff", "Secondary", "SecondaryOptions", "SecondaryDev", "SecondaryOut",
-           "SECONDARY_DT", "PileupCol", "PILEUP_COL_DT", "PileupCallOptions", "PileupSite", "PILEUP_SITE_DT", "PILEUP_INS_ALLELE_DT", "PILEUP_INS_COLS_MAX", "INS_ENTERS", "INS_FULL", "CALL_SNV", "CALL_DEL", "CALL_INS", "PILEUP_TILE", "PILEUP_PLANES", "SEC_ALIGNED", "SEC_DUPLICATE", "MAP_OPTION_FIELDS", "CONSTANTS", "BS_COUNTERS", *(s.__name__ for s in STRUCTS),
+           "SECONDARY_DT", "PileupCol", "PILEUP_COL_DT", "PileupCallOptions", "PileupSite", "BatchPileup", "AccalnPileupOptions", "PILEUP_SITE_DT", "PILEUP_INS_ALLELE_DT", "PILEUP_INS_COLS_MAX", "INS_ENTERS", "INS_FULL", "CALL_SNV", "CALL_DEL", "CALL_INS", "PILEUP_TILE", "PILEUP_PLANES", "SEC_ALIGNED", "SEC_DUPLICATE", "MAP_OPTION_FIELDS", "CONSTANTS", "BS_COUNTERS", *(s.__name__ for s in STRUCTS),
            "ENTRY_DT", "META_DT", "CIGAR_DT", "ANCHOR_DT", "CLIP_DT", "SEGMENT_DT", "MAPQ_DT", "SUMMARY_DT", "N_KERNELS", "MAPQ_SLOTS",
            "MAPQ_OVERFLOW", "SEG_RIGHT", "SEG_ALIGNED", "SPLIT_MIN_DEFAULT", "DIFF_X", "DIFF_D_OPEN", "DIFF_D_MORE", "DIFF_NO_ROOM", "ANCHOR_ANCHORED", "ANCHOR_FALLBACK", "ANCHOR_NO_LEFT",
            "ANCHOR_LEFT_CLIPPED", "ANCHOR_RIGHT_CLIPPED", "ANCHOR_SOFT_LEFT", "ANCHOR_SOFT_RIGHT", "ANCHOR_DIAGS"]

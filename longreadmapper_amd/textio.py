@@ -229,17 +229,33 @@ def write_consensus(path, host, s, cons, lo):
 
 
 def accaln(genome, reads, out, batch_size, seed_len=20, thres=300, gact=(0, 0, 0), device=0, rg_id=1, options=None, mapq=0, paf=False, md=False,
-           secondary=None):
-    """secondary: an lrm_secondary_options (capi.SecondaryOptions) -- lrm_accaln_secondary: the flow of lrm_accaln_mapq plus a FLAG
+           secondary=None, pileup=None):
+    """pileup: dict(seq=-1, ins_cols=0, min_mapq=0, sites=None, fasta=None, min_depth=0, min_count=0, min_pct=0) -- lrm_accaln_pileup:
+    the flow of lrm_accaln_mapq with every batch added to one accumulator over sequence seq (-1: all); behind the last batch the
+    sites table goes to `sites` and the polished sequences to `fasta` (either may be None).  out=None is allowed with it: no SAM.
+    secondary: an lrm_secondary_options (capi.SecondaryOptions) -- lrm_accaln_secondary: the flow of lrm_accaln_mapq plus a FLAG
     256 line for every reported secondary alignment.
     md: NM:i and MD:Z on every mapped primary line (lrm_accaln_md).
     A whole reads file to SAM (paf: PAF) -> (total, valid): lrm_accaln_paf, or the first of lrm_accaln_mapq / lrm_accaln_opt
     / lrm_accaln that takes what was given (options: an lrm_map_options).  A failure raises LrmError with the code in .rc."""
     total, valid = C.c_uint64(), C.c_uint64()
-    head = (os.fsencode(genome), os.fsencode(reads), os.fsencode(out), capi.Params(batch_size, seed_len, thres), capi.GactParams(*gact), device)
+    head = (os.fsencode(genome), os.fsencode(reads), None if out is None else os.fsencode(out), capi.Params(batch_size, seed_len, thres), capi.GactParams(*gact), device)
     counts, opt = (C.byref(total), C.byref(valid)), _at(options)
     assert not (md and paf), "PAF lines carry no MD:Z"
     assert secondary is None or not (md or paf), "the secondary flow prints SAM without MD:Z"
+    assert out is not None or pileup is not None, "only the pileup flow runs without an output file"
+    if pileup is not None:
+        assert not (md or paf) and secondary is None, "the pileup flow prints the SAM of lrm_accaln_mapq"
+        unknown = set(pileup) - {"seq", "ins_cols", "min_mapq", "sites", "fasta", "min_depth", "min_count", "min_pct"}
+        assert not unknown, "pileup has no field %s" % sorted(unknown)
+        path = {k: None if pileup.get(k) is None else os.fsencode(pileup[k]) for k in ("sites", "fasta")}
+        po = capi.AccalnPileupOptions(C.sizeof(capi.AccalnPileupOptions), pileup.get("ins_cols", 0), pileup.get("min_mapq", 0), 0,
+                                      capi.PileupCallOptions(pileup.get("min_depth", 0), pileup.get("min_count", 0), pileup.get("min_pct", 0), 0),
+                                      pileup.get("seq", -1), 0, path["sites"], path["fasta"])
+        rc = lib.lrm_accaln_pileup(*head, rg_id, *counts, opt, mapq, C.byref(po))
+        if rc < 0:
+            raise capi.failure("lrm_accaln_pileup", rc=rc)
+        return int(total.value), int(valid.value)
     entry, tail = (("lrm_accaln_secondary", (rg_id, *counts, opt, C.byref(secondary))) if secondary is not None else ("lrm_accaln_paf", (*counts, opt, mapq)) if paf else ("lrm_accaln_md", (rg_id, *counts, opt, mapq, 1)) if md else ("lrm_accaln_mapq", (rg_id, *counts, opt, mapq)) if mapq else
                    ("lrm_accaln_opt", (rg_id, *counts, opt)) if options is not None else ("lrm_accaln", (rg_id, *counts)))
     rc = getattr(lib, entry)(*head, *tail)

@@ -9,7 +9,9 @@ atomic adds of one pileup_add launch (from the accumulator itself) and the adds 
 insertion side (docs/GACT_SPEC.md, "Pileup insertions and the polished consensus"): the add on two plain accumulators
 launched in turn (this build's spread against itself; with PROBE_PARENT_LIB also the parent commit's library on accumulators
 of its own, in the same process), the add with K = 4 and K = 8 insertion columns, the polish next to the sites + cons bytes,
-the site alleles and the insertion read-back.
+the site alleles and the insertion read-back.  Last, the host-buffer path (ms per batch with two batches in flight on pinned
+buffers with dense results: without an accumulator, with a plain one and with K = 8; PROBE_HOST_BATCHES timed batches a leg) and
+the merge of two accumulators over the window on both routes.
     python tools/pileup_probe.py       PROBE_READS / PROBE_LEN / PROBE_REF scale it down, PROBE_REPEATS (default 10),
                                        PROBE_PARENT_LIB=<path of the parent commit's liblrm_accel.so>"""
 import ctypes as C
@@ -197,4 +199,52 @@ for ins_cols in (4, 8):
                                                                          "lrm_pileup_ins_read_dev"))
     lib.lrm_pileup_free(acc)
 dm.close()
+# ---- the host-buffer path and the merge (docs/GACT_SPEC.md, "Pileup on the host-buffer path and across replicas") ----
+# The same batch through map_batch_submit on pinned buffers with dense results, two batches in flight, HOST_BATCHES timed
+# batches a leg after two warm-up ones: without an accumulator, with a plain one, with K = 8.  Wall time per batch.
+import time
+
+from longreadmapper_amd.pileup import Pileup
+
+HOST_BATCHES = int(os.environ.get("PROBE_HOST_BATCHES", "8"))
+stride_s = max(mapper.units16(mapper.store_need(length, False)), 16)
+pin = [(mapper.pinned_empty(r["reads"].shape), mapper.pinned_empty((n, stride_s))) for _ in range(2)]
+for reads_p, _ in pin:
+    reads_p[:] = r["reads"]
+
+
+def host_leg(what, acc):
+    pending, t0, done = [], None, 0
+    for k in range(HOST_BATCHES + 2):
+        reads_p, store_p = pin[k & 1]
+        if len(pending) == 2:
+            pending.pop(0).wait()
+            done += 1
+            if done == 2:                                    # two warm-up batches are through: the clock starts
+                t0 = time.perf_counter()
+        pending.append(mapper.map_batch_submit(di, reads_p, r["lens"], store=store_p, options=dict(dense_results=1), pileup=acc))
+    for pb in pending:
+        pb.wait()
+    ms = (time.perf_counter() - t0) * 1e3 / HOST_BATCHES
+    print("  host path, pinned + dense, two batches in flight, %s: %.2f ms per batch of %.3f Gbp (%d batches)" % (what, ms, gbp, HOST_BATCHES), flush=True)
+    return ms
+
+
+for rep in range(2):                                         # the legs in turn, twice: the second round is the spread
+    host_leg("no accumulator", None)
+    for ins_cols in (0, 8):
+        acc = Pileup(di, window[0], window[1], ins_cols)
+        host_leg("accumulator, K = %d" % ins_cols, acc)
+        acc.close()
+for reads_p, store_p in pin:
+    mapper.pinned_free(reads_p)
+    mapper.pinned_free(store_p)
+# the merge of two accumulators over the window, both routes (the staged one forced on this device: its copies are device to device)
+for ins_cols in (0, 8):
+    dst, src = Pileup(di, window[0], window[1], ins_cols), Pileup(di, window[0], window[1], ins_cols)
+    words = 8 * W + 1 + 4 * ins_cols * W
+    timed("pileup merge, direct, K = %d (%.1f MB a side)" % (ins_cols, 4 * words / 1e6), lambda: dst.merge(src), per=(12 * words, "bytes (8 read, 4 written per word)"))
+    timed("pileup merge, staged in chunks of 4 Mi words, K = %d" % ins_cols, lambda: dst.merge(src, staged_chunk=4 << 20))
+    dst.close()
+    src.close()
 di.close()
