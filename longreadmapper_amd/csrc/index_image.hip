@@ -461,6 +461,7 @@ extern "C" void lrm_index_free(lrm_index *idx) {
     if (idx->d_core) (void) hipFree(idx->d_core);
     if (idx->d_sd) (void) hipFree(idx->d_sd);
     if (idx->d_sdx) (void) hipFree(idx->d_sdx);
+    if (idx->d_sd_filt) (void) hipFree(idx->d_sd_filt);
     if (idx->owns_blob && idx->d_blob) (void) hipFree(idx->d_blob);
     delete idx;
 }

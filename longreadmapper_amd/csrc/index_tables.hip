@@ -207,6 +207,7 @@ static bool sd_plan(const lrm_index *idx, uint64_t free_b, SdPlan *pl) {
     }
     return false;
 }
+static void sd_filter_build(lrm_index *idx);
 static int sd_build(lrm_index *idx, const SdPlan &pl) {
     uint64_t *d = nullptr, *ovf = nullptr, *tab = nullptr;
     uint32_t *claimed = nullptr;
@@ -260,7 +261,79 @@ static int sd_build(lrm_index *idx, const SdPlan &pl) {
     idx->view.sd_cbits = pl.cbits;
     idx->sd_side_entries = n;
     if (idx->mtune.verbose) fprintf(stderr, "[lrm] seed table: %d positions per line, 2^%d lines, %d-byte slots, %d count bits, %llu side entries\n", pl.f, pl.bits, pl.slot, pl.cbits, n);
+    sd_filter_build(idx);
     return 0;
+}
+
+// Presence bitmap of the seed table's lines, derived from the FINISHED table (after sd_build_kernel and the side-table
+// build): bit (line >> g) is set iff any of the 8 words of any of the 2^g lines it covers is non-zero.  seed_search looks
+// the bit up before it fetches a line and takes a clear bit for a line of zeros.  Why that is exact: on an all-zero line
+// sd_search returns 0, "absent", before the side table is consulted -- no slot matches with e != 0, and the overflow bit of
+// slot 0 is clear.  Whatever makes a seed present leaves a non-zero word in ITS line: an entry that found room is a
+// non-zero slot (k >= 1 or a tag), an entry that found no room sets the overflow bit of slot 0 of a line that is full, and
+// a count of cmax sits in its line beside its side-table entry.  So a clear bit means exactly what the fetched line
+// would have said.  One lane per line; a lane reads the word before the atomic, so a bit costs one atomic per wavefront
+// that finds it clear, not one per line.
+__global__ __launch_bounds__(256) void sd_filter_kernel(const ulonglong2 *__restrict__ sd, uint64_t lines, uint32_t g,
+                                                        uint32_t *__restrict__ filt) {
+    const uint64_t line = (uint64_t) blockIdx.x * 256 + threadIdx.x;
+    if (line >= lines) return;
+    const ulonglong2 x0 = sd[line * 4], x1 = sd[line * 4 + 1], x2 = sd[line * 4 + 2], x3 = sd[line * 4 + 3];
+    if (((x0.x | x0.y) | (x1.x | x1.y) | (x2.x | x2.y) | (x3.x | x3.y)) == 0) return;
+    const uint64_t bit = line >> g;
+    const uint32_t m = 1u << (bit & 31u);
+    if (!(filt[bit >> 5] & m)) atomicOr(&filt[bit >> 5], m);
+}
+__global__ __launch_bounds__(256) void sd_filter_count_kernel(const uint32_t *__restrict__ filt, uint64_t words,
+                                                              unsigned long long *__restrict__ n_set) {
+    uint32_t c = 0;
+    for (uint64_t i = (uint64_t) blockIdx.x * 256 + threadIdx.x; i < words; i += (uint64_t) gridDim.x * 256) c += __popc(filt[i]);
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+    if ((threadIdx.x & 63u) == 0 && c) atomicAdd(n_set, (unsigned long long) c);
+}
+// Built for the table form that seed_search's SD48 instantiation reads (four positions per line, 8-byte slots, tags of at
+// most 32 bits) and kept only when at most HALF of its bits are set: a bitmap fuller than that cannot halve the fetches.
+// g is the smallest for which the bitmap is at most itune.sd_filter_kb KiB.  Bench text (9.28 M rows, 2^25 lines): 0.277
+// cores per line, 24 % of the lines non-zero; at 2 MiB g = 1 and 1 - exp(-0.553) = 43 % of the bits are set.  A chr1-sized
+// text (2^30 lines, g = 6, 15 cores per bit) fills every bit: there the pass over the 64 GiB table is not even made -- a
+// text whose every S-mer occurred four times would still set more than half of the bits when cores per bit > 4 ln 2.
+// Nothing depends on the bitmap: any failure here leaves the handle without one.
+static void sd_filter_build(lrm_index *idx) {
+    const LrmIndexView &v = idx->view;
+    const int kb = idx->itune.sd_filter_kb;
+    if (kb <= 0 || !lrm_sd48_form(v)) return;
+    const uint64_t lines = 1ull << v.sd_bits, max_bits = (uint64_t) kb * 8192;
+    uint32_t g = 0;
+    while ((lines >> g) > max_bits) ++g;
+    const uint64_t bits = lines >> g;
+    if (bits < 512) return;                                       // (the zeros behind the bitmap start on a 64-byte boundary)
+    if ((double) v.length / (double) bits > 4.0 * 0.6931471805599453) {
+        if (idx->mtune.verbose) fprintf(stderr, "[lrm] seed filter: not built, %.1f rows per bit at %d KiB\n", (double) v.length / (double) bits, kb);
+        return;
+    }
+    uint32_t *filt = nullptr;
+    unsigned long long *d_n = nullptr, n_set = 0;
+    // (64 bytes of zeros stand behind the bitmap: the line that seed_search fetches where a bit is clear, sd_issue_filtered)
+    bool ok = hipMalloc(&filt, bits / 8 + 64) == hipSuccess && hipMalloc(&d_n, 8) == hipSuccess
+              && hipMemset(filt, 0, bits / 8 + 64) == hipSuccess && hipMemset(d_n, 0, 8) == hipSuccess;
+    if (ok) {
+        const uint64_t chunk = 1ull << 30;                                        // lines per launch
+        for (uint64_t l0 = 0; l0 < lines; l0 += chunk) {
+            const uint64_t nl = lines - l0 < chunk ? lines - l0 : chunk;
+            hipLaunchKernelGGL(sd_filter_kernel, dim3((uint32_t) ((nl + 255) / 256)), dim3(256), 0, 0,
+                               reinterpret_cast<const ulonglong2 *>(v.sd) + l0 * 4, nl, g, filt + ((l0 >> g) >> 5));
+        }
+        hipLaunchKernelGGL(sd_filter_count_kernel, dim3(256), dim3(256), 0, 0, filt, bits / 32, d_n);
+        ok = hipDeviceSynchronize() == hipSuccess && hipMemcpy(&n_set, d_n, 8, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    if (d_n) (void) hipFree(d_n);
+    const bool keep = ok && 2 * n_set <= bits;
+    if (idx->mtune.verbose && ok)
+        fprintf(stderr, "[lrm] seed filter: %llu bytes, one bit per %u lines, %.1f %% of the bits set%s\n", (unsigned long long) (bits / 8), 1u << g,
+                100.0 * (double) n_set / (double) bits, keep ? "" : ": more than half, not kept");
+    if (!keep) { if (filt) (void) hipFree(filt); (void) hipGetLastError(); return; }
+    idx->d_sd_filt = filt;
+    idx->view.sd_filt = filt; idx->view.sd_filt_shift = (int32_t) g;
 }
 
 // The long seed table.  seed_search's time is its L2 misses divided by ~50 G random 64-byte lines per second

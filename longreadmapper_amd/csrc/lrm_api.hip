@@ -65,7 +65,7 @@ extern "C" int lrm_device_count(void) {
 // options: the caller's structs, then the LRM_* environment overrides as they stood when the handle was created
 // ------------------------------------------------------------------------------------------
 static const char *const k_env_names[] = {
-    "LRM_SA_SAMPLED", "LRM_LC_LONG", "LRM_LC_PAIR", "LRM_LC_BYTES", "LRM_LC_CORE", "LRM_LCX_THRESHOLD", "LRM_SD", "LRM_SD_SHARE", "LRM_SD_BITS",   // index
+    "LRM_SA_SAMPLED", "LRM_LC_LONG", "LRM_LC_PAIR", "LRM_LC_BYTES", "LRM_LC_CORE", "LRM_LCX_THRESHOLD", "LRM_SD", "LRM_SD_SHARE", "LRM_SD_BITS", "LRM_SD_FILTER_KB",   // index
     "LRM_GACT_IMPL", "LRM_SEED_ROUNDS", "LRM_HOST_DENSE", "LRM_HOST_SLICE", "LRM_HOST_SUBS",
     "LRM_HOST_GROUP", "LRM_BS_WAVES", "LRM_SS_ITEMS", "LRM_VOTE_VG", "LRM_VOTE_T1", "LRM_VOTE_U", "LRM_VOTE_LOAD",
     "LRM_HOST_EXT_STREAMS", "LRM_HOST_SEED_STREAMS", "LRM_HOST_VERBOSE", "LRM_VOTE_FAST", "LRM_HOST_SLOTS", "LRM_SS_PAD"};
@@ -129,6 +129,8 @@ void lrm_resolve_index_tune(const lrm_index_options *opt, const LrmEnv &env, Lrm
     if (env.get("LRM_SD", &v)) t->sd = v != 0;
     if (env.get("LRM_SD_SHARE", &v) && (v == 2 || v == 4)) t->sd_f = (int) v;
     if (env.get("LRM_SD_BITS", &v) && v >= 4 && v <= 32) t->sd_bits = (int) v;
+    t->sd_filter_kb = LRM_SD_FILTER_KB_DEFAULT;
+    if (env.get("LRM_SD_FILTER_KB", &v) && v >= 0 && v <= 65536) t->sd_filter_kb = (int) v;
     if (env.get("LRM_LCX_THRESHOLD", &v) && v >= 1 && v <= 0xFFFFFFll) t->lcx_threshold = (uint64_t) v;
 }
 

@@ -95,7 +95,17 @@ struct LrmIndexView {
     int32_t sd_kbits;         // bits of k in a slot
     int32_t sd_slot;          // slot bytes: 8 (eight per line, overflow flag in slot 0) or 6 (ten per line, entry count in the last 4 bytes)
     int32_t sd_cbits;         // count bits of a slot (all ones: the side table has the count)
+    // optional presence bitmap of the seed table's lines (index_tables.hip, sd_filter_build): bit (line >> sd_filt_shift) is set iff
+    // any of the 2^sd_filt_shift lines it covers holds a non-zero word; null = unused (seed_search then fetches every line)
+    const uint32_t *sd_filt;
+    int32_t sd_filt_shift;
 };
+// The seed table's usual form (E. coli- to chr1-sized texts): four positions per line, 8-byte slots, tags of at most 32 bits
+// (the tag's bits as sd_key_of counts them: role 2, outside bases 6, residue = core bits - line bits).  seed_search has an
+// instantiation of its own for it (SD48), and only this form gets a presence bitmap.
+static inline bool lrm_sd48_form(const LrmIndexView &v) {
+    return v.sd && v.sd_f == 4 && v.sd_slot == 8 && 8 + 2 * (v.sd_len - 3) - v.sd_bits <= 32;
+}
 
 // ---- resolved choices of a handle ------------------------------------------------------------------------------
 // Options come from the caller (lrm_index_options / lrm_map_options); LRM_* environment variables are tuning
@@ -108,10 +118,16 @@ struct LrmEnv {                     // the LRM_* variables as they stood when th
     bool get(const char *key, long long *out) const;
 };
 void lrm_env_snapshot(LrmEnv *e);
+// Largest presence bitmap of the seed table's lines, KiB (LRM_SD_FILTER_KB overrides; 0: none).  Measured on the bench text
+// (2^25 lines), seed_search alone: 4 MiB (one bit per line, 23.5 % set) 5.40 ms, 2 MiB (one per two lines, 41.4 %) 5.57,
+// 1 MiB (65.7 %: not kept), none 6.24 - 6.44; the bench 66.6 - 66.9 / 65.7 - 66.0 / - / 62.8 - 63.7 Gbp/s (profiles/r19).
+// The default goes by those times: the L2 miss counter falls by 15 % at 4 MiB and by 25 % at 2 MiB (section 1 there).
+#define LRM_SD_FILTER_KB_DEFAULT 4096
 struct LrmIndexTune {
     int sa_ratio;                   // 1: full SA; 2..64: sampled
     int lc_long, lc_long_max, lc_pair, lc_entry_bytes, lc_count_bits, lc_core;
     int sd, sd_len, sd_f, sd_bits, sd_cbits;      // seed table: -1 / 0 / 1, seed length, positions per line (0 automatic), tests: lines, count bits
+    int sd_filter_kb;               // largest presence bitmap of the seed table's lines, KiB (LRM_SD_FILTER_KB; 0: none)
     uint64_t lcx_threshold;
 };
 struct LrmMapTune {
@@ -155,6 +171,7 @@ struct lrm_index {
     uint64_t *d_core;         // core table (owned; may be null)
     uint64_t *d_sd, *d_sdx;   // seed table and its side hash table (owned; may be null)
     uint64_t sd_side_entries; // entries of the side table (stats)
+    uint32_t *d_sd_filt;      // presence bitmap of the seed table's lines (owned; may be null)
     uint64_t *d_cpl;          // planar 2-bit copy of the text for the bit-sliced GACT kernel (owned; may be null)
     int cpl_ok;               // text is pure ACGT (otherwise the byte kernels are used)
     uint64_t *d_sas;          // sampled-SA locate mode (csa_access, fmidx.c:315-331): SA rows i*sa_ratio (owned; may be null)

@@ -75,6 +75,31 @@ __device__ __forceinline__ void sd_issue_shared(const LrmIndexView &ix, const Sd
         b = *reinterpret_cast<const ulonglong2 *>(src + 2);
     }
 }
+// The same fetch behind the presence bitmap of the table's lines (index_tables.hip, sd_filter_build; four positions per line
+// only), in two steps.  sd_filter_issue: the quad starts the load of the bitmap word of its line (the four lanes share the
+// core, so the word).  sd_issue_filtered, with the word in hand: a quad whose bit is set fetches its line, the others fetch
+// the 64 bytes of zeros that stand behind the bitmap -- a line of zeros is what the table holds where the bit is clear, so
+// sd_finish_shared answers "absent" with no branch of its own, and the fetch INSTRUCTION is issued on every path, whatever
+// the bits say: the count of loads in flight stays the same everywhere, which the counted waits of the loop need.  A
+// position past the end (real false) loads word 0 and fetches the zeros.  What a clear bit saves is a random line of a
+// table of GiB; what it costs is a word of a bitmap of a few MiB, which does NOT all stay in the L2 beside the streaming
+// table lines (bench text, 4 MiB: about four in ten bitmap loads miss it, 2 MiB: two in ten) but is cheap all the same --
+// the larger bitmap has more L2 misses and is the faster one (profiles/r19, section 1).
+__device__ __forceinline__ uint32_t sd_filter_issue(const LrmIndexView &ix, const SdKey &key, bool real, uint32_t &bit) {
+    const uint64_t line = quad_perm64<0x00>(key.line);                                        // quad_perm [0,0,0,0]
+    bit = real ? (uint32_t) (line >> (uint32_t) ix.sd_filt_shift) : 0u;
+    return ix.sd_filt[bit >> 5];
+}
+__device__ __forceinline__ void sd_issue_filtered(const LrmIndexView &ix, const SdKey &key, bool real, uint32_t word, uint32_t bit,
+                                                  ulonglong2 &a, ulonglong2 &b) {
+    const uint32_t lane = __lane_id();
+    const uint64_t line = quad_perm64<0x00>(key.line);
+    const uint64_t *zeros = reinterpret_cast<const uint64_t *>(ix.sd_filt + ((1ull << ix.sd_bits) >> (uint32_t) ix.sd_filt_shift >> 5));
+    const bool pass = real && ((word >> (bit & 31u)) & 1u);
+    const uint64_t *src = pass ? ix.sd + line * 8 : zeros;
+    a = *reinterpret_cast<const ulonglong2 *>(src + (lane & 3u) * 2);
+    b = a;
+}
 __device__ __forceinline__ int sd_finish_shared(const LrmIndexView &ix, const SdKey &key, uint64_t code, const ulonglong2 &a, const ulonglong2 &b,
                                                 uint64_t &k, uint64_t &c, uint32_t *cnt) {
     uint64_t W[8];
@@ -145,7 +170,13 @@ __device__ __forceinline__ void ss_append(uint64_t *s_tot, uint64_t *s_rec, uint
 // SD48: the instantiation for the seed table's usual form (E. coli- to chr1-sized texts: four positions per line, 8-byte
 // slots, tags of at most 32 bits; the launcher checks idx->view): the shared-lines loop is compiled for that form alone,
 // with no branch on the other table forms in it.  Every other handle, and the counting build, take the generic one.
-template <int SS_ITEMS, bool COUNT, bool SD48>
+// FILT (only together with SD48; the launcher takes it when the handle has a presence bitmap of the table's lines,
+// idx->view.sd_filt): the kernel sits at the memory system's rate of random lines, and three in four lines of a sparse
+// table (a bacterial-sized text) hold nothing, so a position first reads the bit of its line -- from a bitmap of a few
+// MiB, of whose loads six in ten hit the L2 at the default size -- and fetches the line only when the bit is set: fewer
+// random lines is the one thing that moves this kernel (profiles/r19: 6.24 - 6.44 -> 5.39 - 5.47 ms alone).  The counting build takes the one-fetch loop WITHOUT the bitmap, so seed_table_lookups keeps meaning
+// "lookups that seeds need".  With FILT false nothing of this is compiled in.
+template <int SS_ITEMS, bool COUNT, bool SD48, bool FILT = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COUNT ? 1 : 6, 8)))
 void seed_search_kernel(LrmIndexView ix, const uint64_t *__restrict__ reads2,
                                                           uint64_t words_per_read,
@@ -185,6 +216,10 @@ void seed_search_kernel(LrmIndexView ix, const uint64_t *__restrict__ reads2,
     // scalar window loads: -2.5 %) move it much.  Also measured [r2]: a
     // 2 MiB presence bitmap of the 12-mers in front of the table lookup (57 % of the seeds die on an L2 hit instead of
     // fetching a table line): 27.3 vs 27.5 ms, not kept; non-temporal loads for the one-touch table lines: 31.7 ms.
+    // (That bitmap stood in front of ANOTHER kernel: a seed that passed its first lookup went on to about 4.4 dependent
+    // rank requests, a wavefront lasted as long as its longest chain, and killing lanes one step earlier shortened
+    // nothing.  Since the seed table every seed costs exactly one line and a wavefront iteration is one fetch, so the r2
+    // figure does not answer the question for this kernel: see FILT above, which is measured on it.)
     const uint32_t len = lens[read];
     const uint32_t jl = len > (uint32_t) seed_len ? len - (uint32_t) seed_len : 0;   // alnmain.c:353 (fenced for len<s)
     const uint64_t *words = reads2 + read * words_per_read;
@@ -218,7 +253,7 @@ void seed_search_kernel(LrmIndexView ix, const uint64_t *__restrict__ reads2,
         // position, a multiple of 64, and positions only grow), and the loop leaves at its end only: every lane of the
         // wavefront takes part in every fetch, and the count of fetches in flight is the same on every path, which is what
         // lets the compiler wait for the older of two (a fetch past the last iteration reads line 0 and is never looked at).
-        struct Look { uint64_t code; SdKey key; ulonglong2 a, b; bool have; };
+        struct Look { uint64_t code; SdKey key; ulonglong2 a, b; bool have, real; uint32_t word, bit; };
         auto look = [&](bool real, uint32_t j, uint32_t j0) {
             Look f;
             f.have = real && j < lim;
@@ -233,7 +268,9 @@ void seed_search_kernel(LrmIndexView ix, const uint64_t *__restrict__ reads2,
                 f.key = sd_key_of(ixs, f.code, j & (uint32_t) (ixs.sd_f - 1));
             }
             if (SD48) __builtin_assume(f.key.tb <= 32u);
-            sd_issue_shared(ixs, f.key, f.a, f.b);
+            f.real = real;
+            if (FILT) f.word = sd_filter_issue(ixs, f.key, real, f.bit);
+            else sd_issue_shared(ixs, f.key, f.a, f.b);
             if (SD48) __builtin_amdgcn_sched_barrier(0);          // the fetch leaves BEFORE the search that follows waits for the one before it
             return f;
         };
@@ -258,7 +295,34 @@ void seed_search_kernel(LrmIndexView ix, const uint64_t *__restrict__ reads2,
         if (j0 < lim) {
             const uint32_t left = (lim - j0 + 255u) >> 8;                                          // iterations with a position below lim
             const uint32_t n_it = left < (uint32_t) (SS_ITEMS / 256) ? left : (uint32_t) (SS_ITEMS / 256);
-            if (SD48) {
+            if (FILT) {
+                // Behind the bitmap a position goes through THREE steps: look (as above, but what it starts is the load of the
+                // bitmap word), fetch (with the word in hand, the line fetch: sd_issue_filtered) and take.  Per iteration for
+                // position j: the word load of j + 512 leaves, the word of j + 256 is waited for and its line fetch leaves, the
+                // line of j is waited for and searched.  Loads retire in the order they were issued, and at either wait two
+                // younger ones are out, so both waits are for "all but two".  The words land in two registers and the lines in two
+                // sets that change roles, as above; keys and codes are carried from step to step by moves, which wait for nothing.
+                auto fetch = [&](Look f) {
+                    sd_issue_filtered(ixs, f.key, f.real, f.word, f.bit, f.a, f.b);
+                    __builtin_amdgcn_sched_barrier(0);
+                    return f;
+                };
+                Look pa = look(true, j, j0), pb = look(1 < n_it, j + 256u, j0 + 256u);
+                Look ga = fetch(pa), gb;
+                uint32_t it = 0;
+#pragma unroll 1
+                do {
+                    pa = look(it + 2 < n_it, j + 512u, j0 + 512u);
+                    gb = fetch(pb);
+                    take(ga);
+                    step();
+                    pb = look(it + 3 < n_it, j + 512u, j0 + 512u);
+                    ga = fetch(pa);
+                    if (it + 1 < n_it) take(gb);
+                    step();
+                    it += 2;
+                } while (it < n_it);
+            } else if (SD48) {
                 Look fa = look(true, j, j0), fb;
                 uint32_t it = 0;
 #pragma unroll 1
@@ -507,10 +571,11 @@ int lrm_launch_seed(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint
         uint32_t grid;
         if (lrm_grid_1d(n * bpr, "seed_search", &grid)) return -1;
         lrm_time_begin(ws, LRM_K_SEED_SEARCH, stream);
-        // (the tag's bits as sd_key_of counts them: role 2, outside bases 6, residue = core bits - line bits)
         const LrmIndexView &v = idx->view;
-        const bool sd48 = v.sd && v.sd_f == 4 && v.sd_slot == 8 && 8 + 2 * (v.sd_len - 3) - v.sd_bits <= 32;
+        const bool sd48 = lrm_sd48_form(v);
+        const bool filt = sd48 && v.sd_filt;
         auto sk = ws->counting ? seed_search_kernel<2048, true, false>
+                  : filt ? (ss_items == 1024u ? seed_search_kernel<1024, false, true, true> : ss_items == 4096u ? seed_search_kernel<4096, false, true, true> : seed_search_kernel<2048, false, true, true>)
                   : sd48 ? (ss_items == 1024u ? seed_search_kernel<1024, false, true> : ss_items == 4096u ? seed_search_kernel<4096, false, true> : seed_search_kernel<2048, false, true>)
                          : (ss_items == 1024u ? seed_search_kernel<1024, false, false> : ss_items == 4096u ? seed_search_kernel<4096, false, false> : seed_search_kernel<2048, false, false>);
         if (ws->counting) bpr = (uint32_t) (((uint64_t) np * cap_q + 2047) / 2048);
