@@ -742,6 +742,53 @@ int lrm_debug_pileup_merge_staged(lrm_pileup *dst, const lrm_pileup *src, uint64
  * exactly lrm_pileup_sites_format. */
 int64_t lrm_pileup_sites_format_ins(const lrm_mta_entry *mta, int mta_len, const lrm_pileup_site *sites,
                                     const lrm_pileup_ins_allele *alleles, uint64_t count, char *buf, int64_t buflen);
+/* PILEUP VARIANTS AND VCF (docs/GACT_SPEC.md, section of that name): the sites of a range as variant records -- adjacent
+ * deleted positions merged into one run, the inserted allele inside the record, a genotype on every record.  Over the window
+ * positions [first, first + count), with kinds, alt, n_alt of the call rule, position g in ascending order gives up to three
+ * records, in this order:
+ *   DEL  when kinds has LRM_CALL_DEL and g == first or position g - 1 has no LRM_CALL_DEL.  len: the consecutive positions
+ *        from g on, inside the range, that have LRM_CALL_DEL -- runs are cut at both ends of the range and nowhere else.
+ *        n_alt = n_del, n_ref = n_eq and depth are those of g, the run's FIRST position; alt = 0.
+ *   SNV  when kinds has LRM_CALL_SNV.  len = 1; alt, n_alt as in the call rule; n_ref = n_eq.
+ *   INS  when kinds has LRM_CALL_INS.  n_alt = n_ins, n_ref = n_eq; on an accumulator with insertion planes len, bases, n_col0
+ *        and ins_flags are the inserted allele of the position (lrm_pileup_ins_allele_host), otherwise 0.
+ *   gt   2 when 100 * n_alt >= hom_pct * depth (64-bit products), else 1.
+ * Options: hom_pct == 0 means 70; hom_pct > 100, a nonzero reserved word or refused call options are refused. */
+typedef struct lrm_pileup_variant_options { lrm_pileup_call_options call; uint32_t hom_pct, reserved[3]; } lrm_pileup_variant_options;
+typedef struct lrm_pileup_variant {    /* 48 bytes, 16-byte aligned */
+    uint64_t pos;                      /* the text position (DEL: of the run's first deleted base) */
+    uint32_t len, depth;
+    uint32_t n_ref, n_alt, n_col0;
+    uint8_t kind, ref, alt, gt;        /* kind: exactly one of LRM_CALL_SNV / _DEL / _INS; ref: the text byte at pos as stored */
+    uint8_t bases[8];
+    uint8_t ins_flags, pad[7];         /* LRM_INS_ENTERS, LRM_INS_FULL; the padding is zero */
+} lrm_pileup_variant;
+/* The records of window positions [first, first + count), first + count <= hi - lo and 3 * count < 2^32 (checked: ranks are
+ * 32-bit), into d_vars (cap records in device memory, 16-byte aligned; may be NULL with cap == 0).  *d_n_vars (device
+ * memory, 8-byte aligned) gets the total whether or not the table fits; records from index cap on are not written and
+ * nothing outside d_vars[0 .. cap) is touched.  opt NULL: the defaults.  Works on plain accumulators and on accumulators with
+ * insertion planes.  Everything is asynchronous on `stream`: no host wait; the counters are not modified.  The scratch is
+ * that of lrm_pileup_sites_dev (allocated by the first call of any of the three) plus 8 more bytes per tile, which the
+ * first call allocates and lrm_pileup_bytes counts from then on. */
+int lrm_pileup_variants_dev(lrm_pileup *pl, const lrm_pileup_variant_options *opt, uint64_t first, uint64_t count,
+                            lrm_pileup_variant *d_vars, uint64_t cap, uint64_t *d_n_vars, void *stream);
+/* The same rule on records the caller holds, usable without a GPU; cols, ins_words, ins_cols and content as for
+ * lrm_pileup_polish_host, position k of the range is text position pos0 + k.  out: cap records (may be NULL with cap == 0).
+ * Returns the total whether or not it fits, < 0 for refused options or arguments. */
+int64_t lrm_pileup_variants_host(const lrm_pileup_col *cols, const uint32_t *ins_words, uint32_t ins_cols, const char *content,
+                                 uint64_t pos0, uint64_t count, const lrm_pileup_variant_options *opt, lrm_pileup_variant *out, uint64_t cap);
+/* VCF 4.2 text.  lrm_vcf_header: ##fileformat, one ##contig=<ID=,length=> per sequence, the INFO and FORMAT lines used below,
+ * the column line with `sample` (NULL: SAMPLE).  lrm_pileup_variants_format_vcf: one line per record,
+ *   name  POS  .  REF  ALT  .  .  DP=<depth>  GT:AD  <0/1|1/1>:<n_ref>,<n_alt>
+ * SNV: POS is pos (1-based), REF the text byte, ALT alt.  DEL: POS is that of the base before the run, REF that base plus the
+ * len deleted text bytes, ALT that base; a run on a sequence's first base: POS 1, REF the deleted bytes plus the base behind
+ * them, ALT that base.  INS: POS is pos, REF the text byte, ALT the text byte plus bases[0 .. len), <INS> when len == 0;
+ * ;INSFULL behind DP when LRM_INS_FULL is set.  Text bytes print in upper case.  The sequence of a record is the entry of mta
+ * that holds pos; content: the text (host memory).  Both return the text length (NUL-terminated, the NUL not counted), < 0
+ * when buf (buflen bytes) is too small or an argument is bad (a pos in no sequence, a run that leaves its sequence). */
+int64_t lrm_pileup_variants_format_vcf(const lrm_mta_entry *mta, int mta_len, const char *content, const lrm_pileup_variant *vars,
+                                       uint64_t count, char *buf, int64_t buflen);
+int64_t lrm_vcf_header(const lrm_mta_entry *mta, int mta_len, const char *sample, char *buf, int64_t buflen);
 
 /* SPLIT READS (lrm_map_options.split; docs/GACT_SPEC.md, "Split reads"): the soft-clipped ends of a batch that went through
  * the anchored extension with end clipping, mapped as reads of their own.  For read i with n = lens[i] bases, R the read as

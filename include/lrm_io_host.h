@@ -8,7 +8,7 @@
  *   SAM record printing               alnmain.c:485-527                  -> lrm_sam_format (_split, _mapq, _md)
  *   parse_cigar (gact submodule, source absent; PARITY UNPINNED)         -> lrm_parse_cigar
  *   single_end                        alnmain.c:277-551                  -> lrm_accaln
- *   (no counterpart: the reference prints SAM only)                      -> lrm_paf_format, lrm_accaln_paf, lrm_accaln_pileup
+ *   (no counterpart: the reference prints SAM only)                      -> lrm_paf_format, lrm_accaln_paf, lrm_accaln_pileup[_vcf]
  */
 #ifndef LRM_IO_HOST_H
 #define LRM_IO_HOST_H
@@ -172,6 +172,20 @@ typedef struct lrm_accaln_pileup_options {
 int lrm_accaln_pileup(const char *genome, const char *reads_path, const char *sam_path, lrm_params p, lrm_gact_params gp, int device,
                       long rg_id, uint64_t *total, uint64_t *valid, const lrm_map_options *opt, int mapq,
                       const lrm_accaln_pileup_options *po);
+/* lrm_accaln_pileup plus a VCF file (docs/GACT_SPEC.md, "Pileup variants and VCF"; vo == NULL: exactly lrm_accaln_pileup).
+ * Behind the last wait the flow also writes vcf_path: lrm_vcf_header with `sample` (NULL: SAMPLE), then for each selected
+ * sequence in index order the lines of lrm_pileup_variants_format_vcf for the records of lrm_pileup_variants_dev with po->call
+ * and hom_pct over that sequence's slice of the window -- a deleted run therefore never crosses a sequence end.  Refused (-1)
+ * before any output file is created: what lrm_accaln_pileup refuses, po == NULL, a struct_size below the struct's, hom_pct >
+ * 100, vcf_path == NULL, reserved != 0. */
+typedef struct lrm_accaln_vcf_options {
+    uint32_t struct_size, hom_pct;
+    const char *vcf_path, *sample;
+    uint64_t reserved;
+} lrm_accaln_vcf_options;
+int lrm_accaln_pileup_vcf(const char *genome, const char *reads_path, const char *sam_path, lrm_params p, lrm_gact_params gp, int device,
+                          long rg_id, uint64_t *total, uint64_t *valid, const lrm_map_options *opt, int mapq,
+                          const lrm_accaln_pileup_options *po, const lrm_accaln_vcf_options *vo);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 
 ACCEL_SRCS = ["lrm_api.hip", "index_image.hip", "index_group.hip", "workspace.hip", "lrm_host.hip", "host_pipeline.hip", "result_pack_kernels.hip", "seed_kernels.hip", "index_tables.hip", "vote_kernels.hip", "locus_kernels.hip", "gact_kernels.hip", "planar_pack_kernels.hip", "gact_bs_kernels.hip", "extend_launch.hip", "anchor_kernels.hip", "compact_rows.hip", "split_kernels.hip", "extend_taps.hip", "mapq_kernels.hip", "secondary_kernels.hip", "aln_summary_kernels.hip", "aln_diff_kernels.hip", "pileup_kernels.hip", "pileup.hip", "suffix_sort.cpp", "index_build.cpp", "index_files.cpp", "fastq_reader.cpp", "sam_text.cpp", "paf_text.cpp", "pileup_text.cpp", "accaln_flow.cpp"]
-ACCEL_DEPS = ACCEL_SRCS + ["lrm_internal.h", "extend_stage.h", "lrm_hip_util.h", "vote_hits.h", "vote_hash.h", "host_pipeline.h", "seed_index_dev.h", "gact_bs_circuit.h", "anchor_clip.h", "anchor_plan.h", "mapq_rule.h", "mapq_table.h", "rival_rule.h", "compact_rows.h", "op_rows.h", "aln_diff_step.h", "pileup_step.h", "pileup_call_step.h", "pileup_ins_step.h", "seq_bytes.h", "base_words.h", "packed_text.h", "sam_text.h", "paf_text.h", "pileup_text.h", "../../include/lrm_accel.h", "../../include/lrm_index_host.h",
+ACCEL_DEPS = ACCEL_SRCS + ["lrm_internal.h", "extend_stage.h", "lrm_hip_util.h", "vote_hits.h", "vote_hash.h", "host_pipeline.h", "seed_index_dev.h", "gact_bs_circuit.h", "anchor_clip.h", "anchor_plan.h", "mapq_rule.h", "mapq_table.h", "rival_rule.h", "compact_rows.h", "op_rows.h", "aln_diff_step.h", "pileup_step.h", "pileup_call_step.h", "pileup_ins_step.h", "pileup_var_step.h", "seq_bytes.h", "base_words.h", "packed_text.h", "sam_text.h", "paf_text.h", "pileup_text.h", "../../include/lrm_accel.h", "../../include/lrm_index_host.h",
                            "../../include/lrm_io_host.h"]
 ACCEL_LIB = os.environ.get("LRM_ACCEL_LIB") or os.path.join(HERE, "liblrm_accel.so")     # LRM_ACCEL_LIB: a tuning build (tools/)
 SYNTH_LIB = os.path.join(HERE, "liblrm_synth.so")

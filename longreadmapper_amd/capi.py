@@ -92,6 +92,10 @@ SYMBOLS = {
     "lrm_pileup_merge_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "lrm_debug_pileup_merge_staged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "lrm_pileup_sites_format_ins": (C.c_int64, [C.POINTER(MtaEntry), C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int64]),
+    "lrm_pileup_variants_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "lrm_pileup_variants_host": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "lrm_pileup_variants_format_vcf": (C.c_int64, [C.POINTER(MtaEntry), C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int64]),
+    "lrm_vcf_header": (C.c_int64, [C.POINTER(MtaEntry), C.c_int, C.c_char_p, C.c_void_p, C.c_int64]),
     "lrm_aln_summary_host": (None, [C.c_void_p, C.c_int, C.POINTER(AlnSummary)]),
     "lrm_aln_summary_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                       C.c_void_p, C.c_void_p]),
@@ -224,6 +228,8 @@ SYMBOLS = {
                                   C.POINTER(MapOptions), C.c_int]),
     "lrm_accaln_pileup": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, Params, GactParams, C.c_int, C.c_long, u64p, u64p,
                                     C.POINTER(MapOptions), C.c_int, C.POINTER(AccalnPileupOptions)]),
+    "lrm_accaln_pileup_vcf": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, Params, GactParams, C.c_int, C.c_long, u64p, u64p,
+                                        C.POINTER(MapOptions), C.c_int, C.POINTER(AccalnPileupOptions), C.POINTER(AccalnVcfOptions)]),
 }
 
 

@@ -161,6 +161,8 @@ struct AccalnRun {
     lrm_accaln_pileup_options po;
     lrm_pileup *acc = nullptr;
     uint64_t pile_lo = 0, pile_hi = 0;
+    bool vcf_on = false;                                 // lrm_accaln_pileup_vcf: the variant records of the same accumulator as VCF
+    lrm_accaln_vcf_options vo;
     bool want_pinned = false;
     lrm_host_index hi;
     lrm_index *gpu = nullptr;
@@ -507,6 +509,37 @@ struct AccalnRun {
         }
         return 0;
     }
+    // the variant records of window positions [first, first + count) as VCF lines; a table that did not fit is asked for again
+    // with the reported total
+    int write_variants_of(FILE *f, uint64_t first, uint64_t count) {
+        DevMem d_vars, d_n;
+        const lrm_pileup_variant_options opt = {po.call, vo.hom_pct, {0u, 0u, 0u}};
+        uint64_t cap = std::min<uint64_t>(3 * count, 4096 + count / 256), n_vars = 0;
+        if (d_n.room(8)) return -1;
+        for (;;) {
+            if (d_vars.room(cap * sizeof(lrm_pileup_variant))) return -1;
+            if (lrm_pileup_variants_dev(acc, &opt, first, count, (lrm_pileup_variant *) d_vars.p, cap, (uint64_t *) d_n.p, nullptr)) return -1;
+            if (down(&n_vars, d_n.p, 8)) return -1;
+            if (n_vars <= cap) break;
+            cap = n_vars;
+        }
+        std::vector<lrm_pileup_variant> vars((size_t) n_vars);
+        if (down(vars.data(), d_vars.p, n_vars * sizeof(lrm_pileup_variant))) return -1;
+        uint64_t longest = 0;
+        for (int k = 0; k < hi.mta_len; ++k) longest = std::max<uint64_t>(longest, hi.mta[k].name ? hi.mta[k].name_len : 0);
+        const uint64_t chunk = 1u << 14;
+        std::vector<char> text;
+        for (uint64_t at = 0; at < n_vars; at += chunk) {
+            const uint64_t k = std::min(chunk, n_vars - at);
+            uint64_t room = 1;                                                // (a deletion's REF holds its deleted bases)
+            for (uint64_t j = 0; j < k; ++j) room += longest + 128u + (vars[at + j].kind == LRM_CALL_DEL ? vars[at + j].len : 0u);
+            if (text.size() < room) text.resize((size_t) room);
+            const int64_t len = lrm_pileup_variants_format_vcf(hi.mta, hi.mta_len, (const char *) hi.content, vars.data() + at, k, text.data(), (int64_t) text.size());
+            if (len < 0) return -1;
+            if (fwrite(text.data(), 1, (size_t) len, f) != (size_t) len) { lrm_set_error("cannot write: %s", vo.vcf_path); return -1; }
+        }
+        return 0;
+    }
     // the polished bytes of window positions [first, first + count), 60 columns a line; col: the column the line stands at
     int write_polish_of(FILE *f, uint64_t first, uint64_t count, uint32_t *col) {
         DevMem d_seq, d_len;
@@ -538,9 +571,22 @@ struct AccalnRun {
         FILE *fs = nullptr, *ff = nullptr;
         if (po.sites_path && !(fs = fopen(po.sites_path, "wb"))) { lrm_set_error("cannot create: %s", po.sites_path); return -1; }
         if (po.fasta_path && !(ff = fopen(po.fasta_path, "wb"))) { lrm_set_error("cannot create: %s", po.fasta_path); if (fs) fclose(fs); return -1; }
+        FILE *fv = nullptr;
+        if (vcf_on && !(fv = fopen(vo.vcf_path, "wb"))) { lrm_set_error("cannot create: %s", vo.vcf_path); if (fs) fclose(fs); if (ff) fclose(ff); return -1; }
         // (site ranks and byte ranks of one call are 32-bit: a sequence goes through in pieces below both bounds)
         const uint64_t piece = 0xFFFFFFFFull / (po.ins_cols + 1u);
         int rc = 0;
+        if (fv) {                                                             // the header names every sequence of the index
+            uint64_t room = 2048 + (vo.sample ? strlen(vo.sample) : 0);
+            for (int k = 0; k < hi.mta_len; ++k) room += 64u + (hi.mta[k].name ? hi.mta[k].name_len : 0);
+            std::vector<char> head((size_t) room);
+            const int64_t len = lrm_vcf_header(hi.mta, hi.mta_len, vo.sample, head.data(), (int64_t) head.size());
+            if (len < 0) rc = -1;
+            else if (fwrite(head.data(), 1, (size_t) len, fv) != (size_t) len) { lrm_set_error("cannot write: %s", vo.vcf_path); rc = -1; }
+        }
+        // (record ranks of one call are 32-bit too, three records a position: a run is cut only where a sequence ends or a
+        // piece of 2^32 / 3 positions does)
+        const uint64_t var_piece = 0xFFFFFFFFull / 3u;
         for (int s = po.seq < 0 ? 0 : po.seq; !rc && s < (po.seq < 0 ? hi.mta_len : po.seq + 1); ++s) {
             const lrm_mta_entry &m = hi.mta[s];
             uint32_t col = 0;
@@ -551,7 +597,10 @@ struct AccalnRun {
                 if (!rc && ff) rc = write_polish_of(ff, first, count, &col);
             }
             if (!rc && ff && col && fputc('\n', ff) == EOF) { lrm_set_error("cannot write: %s", po.fasta_path); rc = -1; }
+            for (uint64_t at = 0; fv && !rc && at < m.seq_len; at += var_piece)
+                rc = write_variants_of(fv, m.offset - pile_lo + at, std::min<uint64_t>(var_piece, m.seq_len - at));
         }
+        if (fv && fclose(fv) != 0 && !rc) { lrm_set_error("cannot write: %s", vo.vcf_path); rc = -1; }
         if (fs && fclose(fs) != 0 && !rc) { lrm_set_error("cannot write: %s", po.sites_path); rc = -1; }
         if (ff && fclose(ff) != 0 && !rc) { lrm_set_error("cannot write: %s", po.fasta_path); rc = -1; }
         return rc;
@@ -601,10 +650,13 @@ struct AccalnRun {
 // one run of the flow: SAM (lrm_accaln*) or PAF (lrm_accaln_paf) into out_path
 static int accaln_run(const char *genome, const char *reads_path, const char *out_path, lrm_params p, lrm_gact_params gp, int device,
                       long rg_id, uint64_t *total_out, uint64_t *valid_out, const lrm_map_options *user, bool mapq, bool paf, bool md = false,
-                      const lrm_secondary_options *so = nullptr, const lrm_accaln_pileup_options *po = nullptr) {
+                      const lrm_secondary_options *so = nullptr, const lrm_accaln_pileup_options *po = nullptr,
+                      const lrm_accaln_vcf_options *vo = nullptr) {
     AccalnRun r(p, gp, device, mapq, paf, md);
     memset(&r.so, 0, sizeof(r.so));
     memset(&r.po, 0, sizeof(r.po));
+    memset(&r.vo, 0, sizeof(r.vo));
+    if (vo) { r.vcf_on = true; r.vo = *vo; }
     if (so) { r.sec = true; lrm_options_over_defaults(&r.so, so); }
     if (r.take_options(user)) return -1;
     if (lrm_host_index_read(genome, &r.hi)) return -1;
@@ -660,16 +712,35 @@ extern "C" int lrm_accaln(const char *genome, const char *reads_path, const char
     return lrm_accaln_mapq(genome, reads_path, sam_path, p, gp, device, rg_id, total_out, valid_out, nullptr, 0);
 }
 // po: every batch adds to one accumulator (lrm_map_batch_submit_ex3), and behind the last wait the flow writes the sites table
-// and the polished sequences; po == NULL: lrm_accaln_mapq
-extern "C" int lrm_accaln_pileup(const char *genome, const char *reads_path, const char *sam_path, lrm_params p, lrm_gact_params gp,
-                                 int device, long rg_id, uint64_t *total_out, uint64_t *valid_out, const lrm_map_options *user, int mapq,
-                                 const lrm_accaln_pileup_options *po) {
-    if (!po) return lrm_accaln_mapq(genome, reads_path, sam_path, p, gp, device, rg_id, total_out, valid_out, user, mapq);
+// and the polished sequences; po == NULL: lrm_accaln_mapq.  vo: the variant records of the same slices as a VCF file too
+static int accaln_pileup(const char *genome, const char *reads_path, const char *sam_path, lrm_params p, lrm_gact_params gp, int device,
+                         long rg_id, uint64_t *total_out, uint64_t *valid_out, const lrm_map_options *user, int mapq,
+                         const lrm_accaln_pileup_options *po, const lrm_accaln_vcf_options *vo) {
     if (!genome || !reads_path) { lrm_set_error("null argument"); return -1; }
     if (po->struct_size < sizeof(lrm_accaln_pileup_options)) { lrm_set_error("lrm_accaln_pileup_options.struct_size %u: the struct has %zu bytes", po->struct_size, sizeof(lrm_accaln_pileup_options)); return -1; }
     if (po->reserved != 0u || po->reserved2 != 0u || po->call.reserved != 0u) { lrm_set_error("lrm_accaln_pileup_options: a reserved field is not 0"); return -1; }
     if (po->min_mapq != 0u && mapq == 0) { lrm_set_error("lrm_accaln_pileup_options.min_mapq needs mapq (the filter reads the records of the mapping-quality stage)"); return -1; }
     if (po->ins_cols > LRM_PILEUP_INS_COLS_MAX) { lrm_set_error("pileup: %u insertion columns, at most %d", po->ins_cols, LRM_PILEUP_INS_COLS_MAX); return -1; }
     if (po->call.min_pct > 100u) { lrm_set_error("pileup calls: min_pct %u above 100", po->call.min_pct); return -1; }
-    return accaln_run(genome, reads_path, sam_path, p, gp, device, rg_id, total_out, valid_out, user, mapq != 0, false, false, nullptr, po);
+    if (vo) {
+        if (vo->struct_size < sizeof(lrm_accaln_vcf_options)) { lrm_set_error("lrm_accaln_vcf_options.struct_size %u: the struct has %zu bytes", vo->struct_size, sizeof(lrm_accaln_vcf_options)); return -1; }
+        if (vo->reserved != 0u) { lrm_set_error("lrm_accaln_vcf_options: the reserved field is not 0"); return -1; }
+        if (vo->hom_pct > 100u) { lrm_set_error("pileup variants: hom_pct %u above 100", vo->hom_pct); return -1; }
+        if (!vo->vcf_path) { lrm_set_error("lrm_accaln_vcf_options.vcf_path is NULL"); return -1; }
+    }
+    return accaln_run(genome, reads_path, sam_path, p, gp, device, rg_id, total_out, valid_out, user, mapq != 0, false, false, nullptr, po, vo);
+}
+extern "C" int lrm_accaln_pileup(const char *genome, const char *reads_path, const char *sam_path, lrm_params p, lrm_gact_params gp,
+                                 int device, long rg_id, uint64_t *total_out, uint64_t *valid_out, const lrm_map_options *user, int mapq,
+                                 const lrm_accaln_pileup_options *po) {
+    if (!po) return lrm_accaln_mapq(genome, reads_path, sam_path, p, gp, device, rg_id, total_out, valid_out, user, mapq);
+    return accaln_pileup(genome, reads_path, sam_path, p, gp, device, rg_id, total_out, valid_out, user, mapq, po, nullptr);
+}
+// vo == NULL: exactly lrm_accaln_pileup; the VCF file needs the accumulator, so vo without po is refused
+extern "C" int lrm_accaln_pileup_vcf(const char *genome, const char *reads_path, const char *sam_path, lrm_params p, lrm_gact_params gp,
+                                     int device, long rg_id, uint64_t *total_out, uint64_t *valid_out, const lrm_map_options *user, int mapq,
+                                     const lrm_accaln_pileup_options *po, const lrm_accaln_vcf_options *vo) {
+    if (!vo) return lrm_accaln_pileup(genome, reads_path, sam_path, p, gp, device, rg_id, total_out, valid_out, user, mapq, po);
+    if (!po) { lrm_set_error("lrm_accaln_pileup_vcf: the VCF file needs lrm_accaln_pileup_options (the accumulator)"); return -1; }
+    return accaln_pileup(genome, reads_path, sam_path, p, gp, device, rg_id, total_out, valid_out, user, mapq, po, vo);
 }

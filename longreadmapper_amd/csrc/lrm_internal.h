@@ -387,6 +387,9 @@ struct lrm_pileup {
     // the staging buffer of a merge from another device (lrm_pileup_merge_dev): LRM_PILEUP_MERGE_CHUNK words, allocated by the
     // first staged merge and booked into `bytes` then
     uint32_t *d_stage;
+    // two more words per tile for the variant stage (the tiles' deleted-run summaries, then the run lengths that continue
+    // behind each tile), allocated by the first lrm_pileup_variants_dev and booked into `bytes` then
+    uint32_t *d_var;
 };
 #define LRM_PILEUP_MERGE_CHUNK (4ull << 20)              // words of the staging buffer (16 MiB): a multiple of 4
 // the same rows as the summary and the events, plus the read rows (d_reads + row * stride, d_lens) the extension left; a
@@ -411,6 +414,11 @@ int lrm_launch_pileup_polish(const lrm_pileup *pl, const PileCallRule &rule, uin
                              uint64_t *d_len, void *stream);
 int lrm_launch_pileup_site_alleles(const lrm_pileup *pl, const PileCallRule &rule, const lrm_pileup_site *d_sites, uint64_t n,
                                    lrm_pileup_ins_allele *d_out, void *stream);
+// the variant stage (docs/GACT_SPEC.md, "Pileup variants and VCF"), 0 < count, 3 * count < 2^32, pl->d_call and pl->d_var
+// allocated: tile sums and their scan, the tiles' record counts and run summaries, the two scans, the table
+struct PileVarRule;
+int lrm_launch_pileup_variants(const lrm_pileup *pl, const PileVarRule &rule, uint64_t first, uint64_t count, lrm_pileup_variant *d_vars,
+                               uint64_t cap, uint64_t *d_n_vars, void *stream);
 int lrm_launch_seed(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint64_t stride,
                     const uint32_t *d_lens, uint64_t n, uint32_t seed_len,
                     uint32_t thres, lrm_entry *d_best, const LrmMapTune &mt, void *stream, uint8_t *d_phase_out = nullptr);

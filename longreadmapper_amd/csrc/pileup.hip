@@ -1,6 +1,6 @@
 // pileup.hip -- the pileup accumulator (lrm_pileup; docs/GACT_SPEC.md, "Pileup" and "Pileup calls"): the object's lifetime, its
 // device-buffer entry points, the host rules' entries.  Host code only: the kernels are pileup_kernels.hip, the rules pileup_step.h,
-// pileup_call_step.h and pileup_ins_step.h ("Pileup insertions and the polished consensus").
+// pileup_call_step.h, pileup_ins_step.h ("Pileup insertions and the polished consensus") and pileup_var_step.h ("Pileup variants and VCF").
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <cstring>
@@ -8,6 +8,7 @@
 #include "pileup_step.h"
 #include "pileup_call_step.h"
 #include "pileup_ins_step.h"
+#include "pileup_var_step.h"
 
 // positions [first, first + count) lie inside a window of W positions (W == 0: no window at all)
 static int pile_range_check(uint64_t W, uint64_t first, uint64_t count) {
@@ -32,7 +33,7 @@ extern "C" int lrm_pileup_cols_host(const uint32_t *planes, uint64_t lo, uint64_
 
 extern "C" void lrm_pileup_free(lrm_pileup *pl) {
     if (!pl) return;
-    if (hipSetDevice(pl->device) == hipSuccess) lrm_dev_free({pl->d_planes, pl->d_tiles, pl->d_call, pl->d_ins, pl->d_stage});
+    if (hipSetDevice(pl->device) == hipSuccess) lrm_dev_free({pl->d_planes, pl->d_tiles, pl->d_call, pl->d_ins, pl->d_stage, pl->d_var});
     free(pl);
 }
 
@@ -288,4 +289,48 @@ extern "C" int lrm_debug_pileup_ins_raw(lrm_pileup *pl, uint32_t *out, uint64_t 
     HIPCHK(hipMemcpyAsync(out, pl->d_ins, 4ull * words, hipMemcpyDeviceToHost, (hipStream_t) stream));
     HIPCHK(hipStreamSynchronize((hipStream_t) stream));
     return 0;
+}
+
+// ---- the variant stage (docs/GACT_SPEC.md, "Pileup variants and VCF"; the rule: pileup_var_step.h) ----
+static_assert(sizeof(lrm_pileup_variant) == 48, "lrm_pileup_variant is three 16-byte parts");
+static int lrm_pileup_variant_check(const lrm_pileup_variant_options *opt, PileVarRule *rule) {
+    const lrm_pileup_variant_options o = opt ? *opt : lrm_pileup_variant_options{{0, 0, 0, 0}, 0, {0, 0, 0}};
+    PileCallRule call;
+    if (lrm_pileup_call_check(&o.call, &call)) return -1;
+    if (o.hom_pct > 100u) { lrm_set_error("pileup variants: hom_pct %u above 100", o.hom_pct); return -1; }
+    if (o.reserved[0] | o.reserved[1] | o.reserved[2]) { lrm_set_error("pileup variants: lrm_pileup_variant_options.reserved is not 0"); return -1; }
+    *rule = pile_var_rule(call, o.hom_pct);
+    return 0;
+}
+
+extern "C" int64_t lrm_pileup_variants_host(const lrm_pileup_col *cols, const uint32_t *ins_words, uint32_t ins_cols, const char *content,
+                                            uint64_t pos0, uint64_t count, const lrm_pileup_variant_options *opt, lrm_pileup_variant *out,
+                                            uint64_t cap) {
+    PileVarRule rule;
+    if (lrm_pileup_variant_check(opt, &rule)) return -1;
+    if (ins_cols > LRM_PILEUP_INS_COLS_MAX) { lrm_set_error("pileup: %u insertion columns, at most %d", ins_cols, LRM_PILEUP_INS_COLS_MAX); return -1; }
+    if ((count && (!cols || !content || (ins_cols && !ins_words))) || (cap && !out)) { lrm_set_error("null argument"); return -1; }
+    return (int64_t) pile_host_variants(cols, ins_words, ins_cols, content, pos0, count, rule, reinterpret_cast<uint32_t *>(out), cap);
+}
+
+extern "C" int lrm_pileup_variants_dev(lrm_pileup *pl, const lrm_pileup_variant_options *opt, uint64_t first, uint64_t count,
+                                       lrm_pileup_variant *d_vars, uint64_t cap, uint64_t *d_n_vars, void *stream) {
+    if (!pl || !d_n_vars || (cap && !d_vars)) { lrm_set_error("null argument"); return -1; }
+    PileVarRule rule;
+    if (lrm_pileup_variant_check(opt, &rule)) return -1;
+    if (count > 0xFFFFFFFFull / 3u) { lrm_set_error("pileup variants: %llu positions of up to 3 records in one call (record ranks are 32-bit: below 2^32 records)", (unsigned long long) count); return -1; }
+    if (pile_range_check(pl->W, first, count)) return -1;
+    if ((uintptr_t) d_vars & 15u) { lrm_set_error("pileup variants must be 16-byte aligned"); return -1; }
+    if ((uintptr_t) d_n_vars & 7u) { lrm_set_error("the pileup variant count must be 8-byte aligned"); return -1; }
+    if (lrm_require_device(pl->device)) return -1;
+    if (count == 0) {                                                  // no tile holds a position: the total is 0
+        HIPCHK(hipMemsetAsync(d_n_vars, 0, 8, (hipStream_t) stream));
+        return 0;
+    }
+    if (lrm_pileup_call_scratch(pl)) return -1;
+    if (!pl->d_var) {                                                  // the stage's own two words per tile, booked once
+        const LrmDevAlloc table[] = {{(void **) &pl->d_var, 8ull * pl->n_tiles}};
+        if (lrm_dev_alloc_table(table, "pileup variant bytes", &pl->bytes)) return -1;
+    }
+    return lrm_launch_pileup_variants(pl, rule, first, count, d_vars, cap, d_n_vars, stream);
 }

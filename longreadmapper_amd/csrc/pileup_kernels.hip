@@ -9,10 +9,13 @@
 // The insertion side (docs/GACT_SPEC.md, "Pileup insertions and the polished consensus"): an accumulator with insertion
 // planes launches pileup_add_ins_kernel, the same row walk compiled with the inserted bases counted too; the polish kernels
 // write the consensus letters and the inserted bases as one sequence, compacted by the same idiom over byte counts.
+// The variant stage (docs/GACT_SPEC.md, "Pileup variants and VCF"): the sites as variant records, adjacent deleted positions
+// merged into one run by a segmented scan of per-tile summaries -- count, scan, write once more, over record counts.
 #include <hip/hip_runtime.h>
 #include "pileup_step.h"
 #include "pileup_call_step.h"
 #include "pileup_ins_step.h"
+#include "pileup_var_step.h"
 
 namespace {
 
@@ -367,6 +370,172 @@ __global__ __launch_bounds__(256) void pileup_merge_kernel(uint32_t *__restrict_
     for (uint64_t w = 4u * quads + tid; w < words; w += step) dst[w] += src[w];
 }
 
+// ---- the variant stage (docs/GACT_SPEC.md, "Pileup variants and VCF"; the rule: pileup_var_step.h) ----
+// What a workgroup keeps of its tile: the words of the block scan, the LRM_CALL_DEL flags of the tile's requested positions
+// as a bit map (bit i of word i / 32: the tile's position i; positions outside the range are 0), and the flag of the position
+// in front of the tile (0 when that lies outside the range).
+struct PileVarLds { uint32_t scan[4], map[LRM_PILEUP_TILE / 32u], prev; };
+
+// The first pass over a tile: every requested position evaluated, the map and `prev` left in LDS behind a barrier.  The
+// position in front of the tile has the depth tile_base[tile] -- the exclusive prefix is its inclusive one -- so one thread
+// evaluates it directly.  A wavefront's 64 flags of a round are one ballot: two words of the map, no atomics.  Returns this
+// thread's number of SNV and INS records.
+__device__ __forceinline__ uint32_t pile_var_map(const uint32_t *__restrict__ planes, uint64_t W, const uint32_t *__restrict__ tile_base, uint64_t tile,
+                                                 uint64_t first, uint64_t count, const uint8_t *__restrict__ text, const PileCallRule &rule, PileVarLds &s) {
+    if (threadIdx.x == 0) {
+        const uint64_t g0 = tile * LRM_PILEUP_TILE;
+        uint32_t prev = 0;
+        if (g0 > first) prev = (pile_call_at(planes, W, g0 - 1u, tile_base[tile], text, rule).call.kinds & LRM_CALL_DEL) ? 1u : 0u;
+        s.prev = prev;
+    }
+    uint32_t mine = 0, round = 0;
+    pile_tile_rescan(planes, W, tile_base, tile, s.scan, [&](uint64_t g, uint32_t depth) {
+        uint32_t kinds = 0;
+        if (g >= first && g - first < count) kinds = pile_call_at(planes, W, g, depth, text, rule).call.kinds;   // (first + count <= W: g < W here)
+        mine += ((kinds & LRM_CALL_SNV) ? 1u : 0u) + ((kinds & LRM_CALL_INS) ? 1u : 0u);
+        const unsigned long long del = __ballot((kinds & LRM_CALL_DEL) != 0u);
+        if ((threadIdx.x & 63u) == 0u) {
+            const uint32_t at = round * 8u + (threadIdx.x >> 6) * 2u;
+            s.map[at] = (uint32_t) del;
+            s.map[at + 1u] = (uint32_t) (del >> 32);
+        }
+        ++round;
+    });
+    __syncthreads();
+    return mine;
+}
+
+// variants 1: one workgroup per tile that holds a requested position.  The tile's number of records -- its SNV and INS
+// positions plus the deleted positions that start a run, read off the map a word per thread -- goes to tile_n[blockIdx.x];
+// the tile's summary for the runs that cross tiles goes to tile_lead[blockIdx.x]: how many of its leading requested positions
+// are deleted without a gap, and whether these are all of them (pile_var_lead_word).
+__global__ __launch_bounds__(256) void pileup_var_count_kernel(const uint32_t *__restrict__ planes, uint64_t W, const uint32_t *__restrict__ tile_base,
+                                                               uint64_t tile0, uint64_t first, uint64_t count, const uint8_t *__restrict__ text,
+                                                               PileCallRule rule, uint32_t *__restrict__ tile_n, uint32_t *__restrict__ tile_lead) {
+    __shared__ PileVarLds s;
+    const uint64_t tile = tile0 + blockIdx.x;
+    uint32_t mine = pile_var_map(planes, W, tile_base, tile, first, count, text, rule, s);
+    if (threadIdx.x < 64u) {                                           // wavefront 0, a word of the map per lane
+        const uint32_t i = threadIdx.x, w = s.map[i];
+        const uint32_t carry = i ? s.map[i - 1u] >> 31 : s.prev;
+        mine += (uint32_t) __popc(w & ~((w << 1) | carry));            // deleted, and the position before is not
+        const uint64_t g0 = tile * LRM_PILEUP_TILE, end = first + count;
+        const uint32_t a = first > g0 ? (uint32_t) (first - g0) : 0u;  // the tile's requested positions are [a, b)
+        const uint32_t b = end - g0 < LRM_PILEUP_TILE ? (uint32_t) (end - g0) : (uint32_t) LRM_PILEUP_TILE;
+        const uint32_t from_a = i == (a >> 5) ? ~0u << (a & 31u) : (i > (a >> 5) ? ~0u : 0u);
+        const uint32_t open = ~w & from_a;                             // not deleted, at or behind a
+        const uint32_t stop = open ? 32u * i + (uint32_t) __builtin_ctz(open) : (uint32_t) LRM_PILEUP_TILE;
+        const uint32_t nearest = ~wave_max_u32(~stop);                 // the minimum over the 64 words
+        const uint32_t until = nearest < b ? nearest : b;
+        PileVarLead lead;
+        lead.len = until - a;
+        lead.full = until == b;
+        if (i == 0) tile_lead[blockIdx.x] = pile_var_lead_word(lead);
+    }
+    uint32_t all;
+    (void) block256_incl_scan(mine, s.scan, all);
+    if (threadIdx.x == 0) tile_n[blockIdx.x] = all;
+}
+
+// variants 2 is pileup_tile_scan_kernel over the tiles' record counts.  variants 3: tile_ext[t] = the length of the deleted run
+// that starts at the first position of tile t + 1, 0 for the last tile: tile_ext[t] = lead[t + 1] + (tile t + 1 wholly
+// deleted ? tile_ext[t + 1] : 0).  A backward segmented scan with pile_var_lead_join by one workgroup of 1024 that loops over
+// its n tiles from the last one like block1024_excl_scan: a scan over the wavefront on shuffles, the 16 wavefront summaries
+// through LDS, the summary of everything done so far carried from round to round.  The work is the same whatever the runs.
+__global__ __launch_bounds__(1024) void pileup_var_ext_kernel(const uint32_t *__restrict__ tile_lead, uint64_t n, uint32_t *__restrict__ tile_ext) {
+    __shared__ uint32_t wave_total[16];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const PileVarLead none = {0u, true};
+    PileVarLead running = none;                                        // of the tiles behind every tile done so far
+    for (uint64_t base = 0; base < n; base += 1024u) {
+        const uint64_t r = base + tid;                                 // item r is tile n - 1 - r: the scan runs from the last tile
+        PileVarLead v = r < n ? pile_var_lead_of(tile_lead[n - 1u - r]) : none;
+#pragma unroll
+        for (uint32_t d = 1; d < 64u; d <<= 1) {                       // v: this tile, then the d - 1 tiles behind it
+            const PileVarLead far = pile_var_lead_of((uint32_t) __shfl_up(pile_var_lead_word(v), d, 64));
+            if (lane >= d) v = pile_var_lead_join(v, far);
+        }
+        if (lane == 63u) wave_total[wave] = pile_var_lead_word(v);
+        const PileVarLead behind = pile_var_lead_of((uint32_t) __shfl_up(pile_var_lead_word(v), 1u, 64));
+        PileVarLead acc = lane ? behind : none;                        // the tiles of this wavefront behind this one
+        __syncthreads();
+        PileVarLead chunk = none;
+#pragma unroll
+        for (int k = 15; k >= 0; --k) {                                // nearest first: wavefront 15 holds the tiles in front
+            const PileVarLead wt = pile_var_lead_of(wave_total[k]);
+            if ((uint32_t) k < wave) acc = pile_var_lead_join(acc, wt);
+            chunk = pile_var_lead_join(chunk, wt);
+        }
+        if (r < n) tile_ext[n - 1u - r] = pile_var_lead_join(acc, running).len;
+        running = pile_var_lead_join(chunk, running);
+        __syncthreads();                                               // wave_total is rewritten by the next round
+    }
+}
+
+// variants 4: one workgroup per tile again.  The last one writes the total as 64 bits.  A tile without a record, or whose
+// first record already lies at or behind cap, leaves after its scalar loads.  Otherwise the first pass leaves the map again
+// and a second one evaluates the tile once more: a round's per-thread record counts (0 .. 3) are ranked by a block scan, the
+// running rank carried as the depth is, and every record goes to vars[rank] with three aligned 16-byte stores when rank <
+// cap.  The thread of a run's first position finds its end in the map -- the first clear bit behind it, at most 64 words --
+// and adds tile_ext when the run reaches the tile's end.  The position's 4 * K insertion words are read only where it has
+// LRM_CALL_INS; the allele travels as one 64-bit word (no private segment).
+__global__ __launch_bounds__(256) void pileup_var_write_kernel(const uint32_t *__restrict__ planes, uint64_t W, const uint32_t *__restrict__ tile_base,
+                                                               uint64_t tile0, uint64_t first, uint64_t count, uint64_t lo,
+                                                               const uint8_t *__restrict__ text, PileVarRule rule, PileIns ins,
+                                                               const uint32_t *__restrict__ tile_n, const uint32_t *__restrict__ tile_rank,
+                                                               const uint32_t *__restrict__ tile_ext, lrm_pileup_variant *__restrict__ vars,
+                                                               uint64_t cap, uint64_t *__restrict__ n_vars) {
+    __shared__ PileVarLds s;
+    const uint32_t n_here = tile_n[blockIdx.x];
+    uint64_t rank = tile_rank[blockIdx.x];
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *n_vars = rank + n_here;
+    if (n_here == 0 || rank >= cap) return;
+    const uint64_t tile = tile0 + blockIdx.x;
+    (void) pile_var_map(planes, W, tile_base, tile, first, count, text, rule.call, s);
+    const uint32_t ext = tile_ext[blockIdx.x];
+    uint32_t round = 0;
+    pile_tile_rescan(planes, W, tile_base, tile, s.scan, [&](uint64_t g, uint32_t depth) {
+        PilePos p = {};
+        if (g >= first && g - first < count) p = pile_call_at(planes, W, g, depth, text, rule.call);
+        const uint32_t i = round * 256u + threadIdx.x;                 // the position's place in the tile
+        ++round;
+        const uint32_t before = i ? (s.map[(i - 1u) >> 5] >> ((i - 1u) & 31u)) & 1u : s.prev;
+        const uint32_t emits = pile_var_emits(p.call.kinds, before != 0u);
+        const uint32_t c = pile_var_count(emits);
+        uint32_t all;
+        uint64_t at = rank + (block256_incl_scan(c, s.scan, all) - c);
+        rank += all;
+        if (c == 0u || at >= cap) return;
+        uint32_t run = 0;
+        if (emits & LRM_CALL_DEL) {
+            uint32_t k = i >> 5;
+            uint32_t open = ~s.map[k] & (~0u << (i & 31u));            // (bit i itself is set)
+            while (!open && ++k < LRM_PILEUP_TILE / 32u) open = ~s.map[k];
+            run = open ? 32u * k + (uint32_t) __builtin_ctz(open) - i : (uint32_t) LRM_PILEUP_TILE - i + ext;
+        }
+        PileInsAllele a = {0u, 0u, 0u, 0ull};
+        if ((emits & LRM_CALL_INS) && ins.K != 0u) a = pile_ins_allele(rule.call, depth, p.n_ins, ins.planes + g, W, ins.K);
+        auto put = [&](uint32_t kind) {
+            if (!(emits & kind)) return;
+            if (at < cap) {
+                uint32_t w[12];
+                pile_var_record(rule, kind, lo + g, depth, p.n_eq, p.n_del, p.n_ins, p.byte, p.call, run, a, w);
+                // (each part pinned in four consecutive registers, as in pileup_sites_kernel)
+                pile_u32x4 h0 = {w[0], w[1], w[2], w[3]}, h1 = {w[4], w[5], w[6], w[7]}, h2 = {w[8], w[9], w[10], w[11]};
+                asm volatile("" : "+v"(h0), "+v"(h1), "+v"(h2));
+                pile_u32x4 *o = reinterpret_cast<pile_u32x4 *>(vars + at);
+                o[0] = h0;
+                o[1] = h1;
+                o[2] = h2;
+            }
+            ++at;
+        };
+        put(LRM_CALL_DEL);
+        put(LRM_CALL_SNV);
+        put(LRM_CALL_INS);
+    });
+}
+
 // What the read-back and the call stage start with: the sums of the difference plane over the tiles up to the last requested
 // position's, and their scan into `bases`.  tile0: the tile of `first`, grid: the tiles that hold a requested position.
 struct PileTiles { uint64_t tile0; uint32_t grid, *bases; };
@@ -465,6 +634,22 @@ int lrm_launch_pileup_sites(const lrm_pileup *pl, const PileCallRule &rule, uint
     hipLaunchKernelGGL(pileup_tile_scan_kernel, dim3(1), dim3(1024), 0, st, n_here, (uint64_t) t.grid, rank);
     hipLaunchKernelGGL(pileup_sites_kernel, dim3(t.grid), dim3(256), 0, st, pl->d_planes, pl->W, t.bases, t.tile0, first, count, pl->lo, text, rule,
                        n_here, rank, d_sites, cap, d_n_sites);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int lrm_launch_pileup_variants(const lrm_pileup *pl, const PileVarRule &rule, uint64_t first, uint64_t count, lrm_pileup_variant *d_vars,
+                               uint64_t cap, uint64_t *d_n_vars, void *stream) {
+    const hipStream_t st = (hipStream_t) stream;
+    PileTiles t;
+    if (pile_launch_tile_bases(pl, first, count, "pileup variants", st, &t)) return -1;
+    uint32_t *n_here = pl->d_call, *rank = pl->d_call + pl->n_tiles, *lead = pl->d_var, *ext = pl->d_var + pl->n_tiles;
+    const uint8_t *text = (const uint8_t *) pl->idx->view.content + pl->lo;
+    hipLaunchKernelGGL(pileup_var_count_kernel, dim3(t.grid), dim3(256), 0, st, pl->d_planes, pl->W, t.bases, t.tile0, first, count, text, rule.call, n_here, lead);
+    hipLaunchKernelGGL(pileup_tile_scan_kernel, dim3(1), dim3(1024), 0, st, n_here, (uint64_t) t.grid, rank);
+    hipLaunchKernelGGL(pileup_var_ext_kernel, dim3(1), dim3(1024), 0, st, lead, (uint64_t) t.grid, ext);
+    hipLaunchKernelGGL(pileup_var_write_kernel, dim3(t.grid), dim3(256), 0, st, pl->d_planes, pl->W, t.bases, t.tile0, first, count, pl->lo, text, rule,
+                       PileIns{pl->d_ins, pl->ins_cols}, n_here, rank, ext, d_vars, cap, d_n_vars);
     HIPCHK(hipGetLastError());
     return 0;
 }

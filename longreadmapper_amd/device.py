@@ -292,6 +292,27 @@ class DeviceMapper:
               "lrm_pileup_site_alleles_dev")
         return _records(d_out[:n], capi.PILEUP_INS_ALLELE_DT)
 
+    def pileup_variants(self, first=None, count=None, cap=None, min_depth=0, min_count=0, min_pct=0, hom_pct=0):
+        """The variant stage over the accumulator (lrm_pileup_variants_dev; docs/GACT_SPEC.md, "Pileup variants and VCF") on
+        window positions first .. first + count - 1 (default: the whole window) -> (variants, total): PILEUP_VARIANT_DT
+        records in ascending position, DEL before SNV before INS -- adjacent deleted positions merged into one record, the
+        inserted allele inside the INS record (pileup_ins_cols), gt 2 where the alternative reaches hom_pct (0: 70) percent of
+        the depth.  What textio.write_vcf takes.  cap as for pileup_sites(): a table that did not fit is asked for once more."""
+        assert self.pileup is not None
+        first, count = self._pileup_range(first, count)
+        cap = min(3 * count, 4096 + count // 256) if cap is None else cap
+        opt = capi.PileupVariantOptions(capi.PileupCallOptions(min_depth, min_count, min_pct, 0), hom_pct, (0, 0, 0))
+        d_total = self._alloc(1, self.torch.int64)
+        while True:
+            d_vars = self._record_tensor(max(cap, 1), capi.PILEUP_VARIANT_DT, self.torch.int32)
+            check(lib.lrm_pileup_variants_dev(self.pileup, C.byref(opt), first, count, d_vars.data_ptr() if cap else None, cap, d_total.data_ptr(),
+                                              self._stream()), "lrm_pileup_variants_dev")
+            total = int(d_total.cpu()[0])
+            if total <= cap:
+                break
+            cap = total
+        return _records(d_vars[:total], capi.PILEUP_VARIANT_DT), total
+
     def pileup_reset(self):
         assert self.pileup is not None
         check(lib.lrm_pileup_reset(self.pileup, self._stream()), "lrm_pileup_reset")

@@ -8,7 +8,7 @@ import numpy as np
 
 from . import capi
 from .capi import check, lib
-from .records import PILEUP_COL_DT, PILEUP_INS_ALLELE_DT, PILEUP_SITE_DT
+from .records import PILEUP_COL_DT, PILEUP_INS_ALLELE_DT, PILEUP_SITE_DT, PILEUP_VARIANT_DT
 
 GUARD_WORDS = 16           # behind the counter words of either allocation (lrm_debug_pileup_raw / _ins_raw)
 
@@ -116,6 +116,23 @@ class Pileup:
         check(lib.lrm_pileup_site_alleles_dev(self.handle, C.byref(opt), d_sites.data_ptr(), n, d_out.data_ptr(), self._stream()),
               "lrm_pileup_site_alleles_dev")
         return self._host(d_out, n, PILEUP_INS_ALLELE_DT)
+
+    def variants(self, first=None, count=None, cap=None, min_depth=0, min_count=0, min_pct=0, hom_pct=0):
+        """lrm_pileup_variants_dev -> (variants, total): PILEUP_VARIANT_DT records, deleted runs merged, the inserted allele inside;
+        a table that did not fit is asked for again with cap = total."""
+        first, count = self._range(first, count)
+        cap = min(3 * count, 4096 + count // 256) if cap is None else cap
+        opt = capi.PileupVariantOptions(capi.PileupCallOptions(min_depth, min_count, min_pct, 0), hom_pct, (0, 0, 0))
+        d_total = self._alloc(1, self.torch.int64)
+        while True:
+            d_vars = self._records(cap, PILEUP_VARIANT_DT)
+            check(lib.lrm_pileup_variants_dev(self.handle, C.byref(opt), first, count, d_vars.data_ptr() if cap else None, cap, d_total.data_ptr(),
+                                              self._stream()), "lrm_pileup_variants_dev")
+            total = int(d_total.cpu()[0])
+            if total <= cap:
+                break
+            cap = total
+        return self._host(d_vars, total, PILEUP_VARIANT_DT), total
 
     # ---- management ----
     def reset(self):

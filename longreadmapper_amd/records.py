@@ -210,8 +210,23 @@ class _AccalnPileupOptions(C.Structure):       # include/lrm_io_host.h
                 ("fasta_path", C.c_char_p)]
 
 
+class _PileupVariantOptions(C.Structure):  # docs/GACT_SPEC.md, "Pileup variants and VCF"; a zero field means its default
+    _fields_ = [("call", _PileupCallOptions), ("hom_pct", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class _PileupVariant(C.Structure):
+    _fields_ = [("pos", C.c_uint64)] + [(name, C.c_uint32) for name in ("len", "depth", "n_ref", "n_alt", "n_col0")] + [
+        (name, C.c_uint8) for name in ("kind", "ref", "alt", "gt")] + [("bases", C.c_uint8 * 8), ("ins_flags", C.c_uint8), ("pad", C.c_uint8 * 7)]
+
+
+class _AccalnVcfOptions(C.Structure):          # include/lrm_io_host.h
+    _fields_ = [("struct_size", C.c_uint32), ("hom_pct", C.c_uint32), ("vcf_path", C.c_char_p), ("sample", C.c_char_p),
+                ("reserved", C.c_uint64)]
+
+
 PileupCol, PileupCallOptions, PileupSite = _PileupCol, _PileupCallOptions, _PileupSite
 BatchPileup, AccalnPileupOptions = _BatchPileup, _AccalnPileupOptions
+PileupVariantOptions, PileupVariant, AccalnVcfOptions = _PileupVariantOptions, _PileupVariant, _AccalnVcfOptions
 
 
 class GactTable(C.Structure):          # host pointers
@@ -256,7 +271,8 @@ MAP_OPTION_FIELDS = _MAP_OPTION_WORDS + ("split", "split_min_len")
 LATER_STRUCTS = {BatchDiff: "lrm_batch_diff", Secondary: "lrm_secondary", SecondaryOptions: "lrm_secondary_options",
                  SecondaryDev: "lrm_secondary_dev", SecondaryOut: "lrm_secondary_out", PileupCol: "lrm_pileup_col",
                  PileupCallOptions: "lrm_pileup_call_options", PileupSite: "lrm_pileup_site", BatchPileup: "lrm_batch_pileup",
-                 AccalnPileupOptions: "lrm_accaln_pileup_options"}
+                 AccalnPileupOptions: "lrm_accaln_pileup_options", PileupVariantOptions: "lrm_pileup_variant_options",
+                 PileupVariant: "lrm_pileup_variant", AccalnVcfOptions: "lrm_accaln_vcf_options"}
 
 # the records that cross the boundary as arrays
 ENTRY_DT, META_DT, CIGAR_DT = dtype_of(Entry), dtype_of(SeqMeta), dtype_of(Cigar)
@@ -267,6 +283,9 @@ PILEUP_COL_DT = dtype_of(PileupCol)
 PILEUP_SITE_DT = dtype_of(PileupSite)
 # lrm_pileup_ins_allele (16 bytes): a record that crosses only as an array, so it has a dtype and no ctypes structure
 PILEUP_INS_ALLELE_DT = np.dtype([("n_col0", "<u4"), ("len", "u1"), ("flags", "u1"), ("pad", "u1", (2,)), ("bases", "u1", (8,))])
+# lrm_pileup_variant (48 bytes): the members of PileupVariant with the eight bases as one field
+PILEUP_VARIANT_DT = np.dtype([("pos", "<u8"), ("len", "<u4"), ("depth", "<u4"), ("n_ref", "<u4"), ("n_alt", "<u4"), ("n_col0", "<u4"), ("kind", "u1"),
+                              ("ref", "u1"), ("alt", "u1"), ("gt", "u1"), ("bases", "u1", (8,)), ("ins_flags", "u1"), ("pad", "u1", (7,))])
 
 N_KERNELS = 9
 MAPQ_SLOTS, MAPQ_OVERFLOW = 4096, 1    # lrm_mapq.flags
@@ -319,7 +338,7 @@ def units16(nbytes):
 
 # what capi re-exports: the pointer types, the structs, the record dtypes and the header's constants -- not the helpers
 __all__ = ["u8p", "u32p", "u64p", "i32p", "STRUCTS", "LATER_STRUCTS", "BatchDiff", "Secondary", "SecondaryOptions", "SecondaryDev", "SecondaryOut",
-           "SECONDARY_DT", "PileupCol", "PILEUP_COL_DT", "PileupCallOptions", "PileupSite", "BatchPileup", "AccalnPileupOptions", "PILEUP_SITE_DT", "PILEUP_INS_ALLELE_DT", "PILEUP_INS_COLS_MAX", "INS_ENTERS", "INS_FULL", "CALL_SNV", "CALL_DEL", "CALL_INS", "PILEUP_TILE", "PILEUP_PLANES", "SEC_ALIGNED", "SEC_DUPLICATE", "MAP_OPTION_FIELDS", "CONSTANTS", "BS_COUNTERS", *(s.__name__ for s in STRUCTS),
+           "SECONDARY_DT", "PileupCol", "PILEUP_COL_DT", "PileupCallOptions", "PileupSite", "BatchPileup", "AccalnPileupOptions", "PileupVariantOptions", "PileupVariant", "AccalnVcfOptions", "PILEUP_VARIANT_DT", "PILEUP_SITE_DT", "PILEUP_INS_ALLELE_DT", "PILEUP_INS_COLS_MAX", "INS_ENTERS", "INS_FULL", "CALL_SNV", "CALL_DEL", "CALL_INS", "PILEUP_TILE", "PILEUP_PLANES", "SEC_ALIGNED", "SEC_DUPLICATE", "MAP_OPTION_FIELDS", "CONSTANTS", "BS_COUNTERS", *(s.__name__ for s in STRUCTS),
            "ENTRY_DT", "META_DT", "CIGAR_DT", "ANCHOR_DT", "CLIP_DT", "SEGMENT_DT", "MAPQ_DT", "SUMMARY_DT", "N_KERNELS", "MAPQ_SLOTS",
            "MAPQ_OVERFLOW", "SEG_RIGHT", "SEG_ALIGNED", "SPLIT_MIN_DEFAULT", "DIFF_X", "DIFF_D_OPEN", "DIFF_D_MORE", "DIFF_NO_ROOM", "ANCHOR_ANCHORED", "ANCHOR_FALLBACK", "ANCHOR_NO_LEFT",
            "ANCHOR_LEFT_CLIPPED", "ANCHOR_RIGHT_CLIPPED", "ANCHOR_SOFT_LEFT", "ANCHOR_SOFT_RIGHT", "ANCHOR_DIAGS"]

@@ -213,6 +213,38 @@ def write_sites(path, host, sites, chunk=1 << 16, alleles=None):
     return len(sites)
 
 
+def vcf_header(host, sample="SAMPLE"):
+    """lrm_vcf_header: the VCF 4.2 header lines of a HostIndex, one ##contig per sequence."""
+    room = 2048 + len(os.fsencode(sample)) + sum(64 + int(host.h.mta[s].name_len) for s in range(host.mta_len))
+    buf = C.create_string_buffer(room)
+    k = lib.lrm_vcf_header(host.h.mta, host.mta_len, os.fsencode(sample), buf, room)
+    if k < 0:
+        raise capi.failure("lrm_vcf_header", rc=k)
+    return buf.raw[:k]
+
+
+def vcf_text(host, variants):
+    """lrm_pileup_variants_format_vcf: one VCF line per PILEUP_VARIANT_DT record (DeviceMapper.pileup_variants())."""
+    variants = np.ascontiguousarray(variants, dtype=capi.PILEUP_VARIANT_DT)
+    longest = max((int(host.h.mta[s].name_len) for s in range(host.mta_len)), default=0)
+    deleted = int(variants["len"][variants["kind"] == capi.CALL_DEL].sum())        # a deletion's REF holds its deleted bases
+    room = (longest + 128) * len(variants) + deleted + 1
+    buf = C.create_string_buffer(room)
+    k = lib.lrm_pileup_variants_format_vcf(host.h.mta, host.mta_len, host.h.content, variants.ctypes.data if len(variants) else None, len(variants), buf, room)
+    if k < 0:
+        raise capi.failure("lrm_pileup_variants_format_vcf", rc=k)
+    return buf.raw[:k]
+
+
+def write_vcf(path, host, variants, sample="SAMPLE", chunk=1 << 14):
+    """The variant table as a VCF file: the header, then one line per record -> the number of records."""
+    with open(path, "wb") as f:
+        f.write(vcf_header(host, sample))
+        for p in range(0, len(variants), chunk):
+            f.write(vcf_text(host, variants[p:p + chunk]))
+    return len(variants)
+
+
 def write_consensus(path, host, s, cons, lo):
     """The consensus of sequence s of a HostIndex as FASTA: cons[k] is the letter of text position lo + k
     (DeviceMapper.pileup_sites(consensus=True) of a window that starts at lo) and has to cover the sequence
@@ -233,6 +265,7 @@ def accaln(genome, reads, out, batch_size, seed_len=20, thres=300, gact=(0, 0, 0
     """pileup: dict(seq=-1, ins_cols=0, min_mapq=0, sites=None, fasta=None, min_depth=0, min_count=0, min_pct=0) -- lrm_accaln_pileup:
     the flow of lrm_accaln_mapq with every batch added to one accumulator over sequence seq (-1: all); behind the last batch the
     sites table goes to `sites` and the polished sequences to `fasta` (either may be None).  out=None is allowed with it: no SAM.
+    With vcf= in the dict (and hom_pct=0, sample=None) the variant records go to that VCF file too (lrm_accaln_pileup_vcf).
     secondary: an lrm_secondary_options (capi.SecondaryOptions) -- lrm_accaln_secondary: the flow of lrm_accaln_mapq plus a FLAG
     256 line for every reported secondary alignment.
     md: NM:i and MD:Z on every mapped primary line (lrm_accaln_md).
@@ -246,13 +279,20 @@ def accaln(genome, reads, out, batch_size, seed_len=20, thres=300, gact=(0, 0, 0
     assert out is not None or pileup is not None, "only the pileup flow runs without an output file"
     if pileup is not None:
         assert not (md or paf) and secondary is None, "the pileup flow prints the SAM of lrm_accaln_mapq"
-        unknown = set(pileup) - {"seq", "ins_cols", "min_mapq", "sites", "fasta", "min_depth", "min_count", "min_pct"}
+        unknown = set(pileup) - {"seq", "ins_cols", "min_mapq", "sites", "fasta", "min_depth", "min_count", "min_pct", "vcf", "hom_pct", "sample"}
         assert not unknown, "pileup has no field %s" % sorted(unknown)
         path = {k: None if pileup.get(k) is None else os.fsencode(pileup[k]) for k in ("sites", "fasta")}
         po = capi.AccalnPileupOptions(C.sizeof(capi.AccalnPileupOptions), pileup.get("ins_cols", 0), pileup.get("min_mapq", 0), 0,
                                       capi.PileupCallOptions(pileup.get("min_depth", 0), pileup.get("min_count", 0), pileup.get("min_pct", 0), 0),
                                       pileup.get("seq", -1), 0, path["sites"], path["fasta"])
-        rc = lib.lrm_accaln_pileup(*head, rg_id, *counts, opt, mapq, C.byref(po))
+        if pileup.get("vcf") is not None:
+            sample = pileup.get("sample")
+            vo = capi.AccalnVcfOptions(C.sizeof(capi.AccalnVcfOptions), pileup.get("hom_pct", 0), os.fsencode(pileup["vcf"]),
+                                       None if sample is None else os.fsencode(sample), 0)
+            rc = lib.lrm_accaln_pileup_vcf(*head, rg_id, *counts, opt, mapq, C.byref(po), C.byref(vo))
+        else:
+            assert "hom_pct" not in pileup and "sample" not in pileup, "hom_pct and sample belong to vcf="
+            rc = lib.lrm_accaln_pileup(*head, rg_id, *counts, opt, mapq, C.byref(po))
         if rc < 0:
             raise capi.failure("lrm_accaln_pileup", rc=rc)
         return int(total.value), int(valid.value)

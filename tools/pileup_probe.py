@@ -4,7 +4,8 @@ HBM; the window is the whole text.  Then, with events on the stream, a warm-up a
 pileup_add_kernel, of the read-back of the whole window (tile sums, their scan, the records), and -- as yardsticks of the same
 stream shape -- of aln_diff_kernel and aln_summary_kernel; next to the read-back, in the same process, the call stage
 (docs/GACT_SPEC.md, "Pileup calls": lrm_pileup_sites_dev over the whole window, with and without the cons bytes) and the bytes
-each path would bring down the link.  Printed: ms per Gbp of reads (mean, min, max), the number of
+each path would bring down the link, and the variant stage (docs/GACT_SPEC.md, "Pileup variants and VCF": lrm_pileup_variants_dev)
+launched in turn with the sites call on the same window.  Printed: ms per Gbp of reads (mean, min, max), the number of
 atomic adds of one pileup_add launch (from the accumulator itself) and the adds per second at the fastest launch.  Then the
 insertion side (docs/GACT_SPEC.md, "Pileup insertions and the polished consensus"): the add on two plain accumulators
 launched in turn (this build's spread against itself; with PROBE_PARENT_LIB also the parent commit's library on accumulators
@@ -13,7 +14,8 @@ the site alleles and the insertion read-back.  Last, the host-buffer path (ms pe
 buffers with dense results: without an accumulator, with a plain one and with K = 8; PROBE_HOST_BATCHES timed batches a leg) and
 the merge of two accumulators over the window on both routes.
     python tools/pileup_probe.py       PROBE_READS / PROBE_LEN / PROBE_REF scale it down, PROBE_REPEATS (default 10),
-                                       PROBE_PARENT_LIB=<path of the parent commit's liblrm_accel.so>"""
+                                       PROBE_PARENT_LIB=<path of the parent commit's liblrm_accel.so>,
+                                       PROBE_UNTIL=variants ends the probe behind the call and variant stages"""
 import ctypes as C
 import os
 import sys
@@ -82,6 +84,25 @@ def timed(what, call, per=None):
     return ms
 
 
+def alternated(legs):
+    """legs: [(name, call)], launched in turn REPEATS times after one warm-up each -> {name: [ms]}"""
+    for _, call in legs:
+        call()
+    torch.cuda.synchronize()
+    ms = {name: [] for name, _ in legs}
+    for rep in range(REPEATS):
+        for name, call in legs:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            call()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[name].append(e0.elapsed_time(e1))
+    for name, _ in legs:
+        print("  %s: %.3f ms per Gbp (min %.3f, max %.3f; alternated)" % (name, np.mean(ms[name]) / gbp, min(ms[name]) / gbp, max(ms[name]) / gbp), flush=True)
+    return ms
+
+
 timed("pileup_add_kernel", lambda: check(lib.lrm_pileup_add_dev(
     dm.pileup, d_reads.data_ptr(), d_reads.stride(0), d_lens.data_ptr(), dm.store.data_ptr(), dm.store_stride, dm.n_ops.data_ptr(),
     dm.score.data_ptr(), dm.meta_r.data_ptr(), dm.meta.data_ptr(), n, None, 0, stream), "lrm_pileup_add_dev"), per=(adds, "adds"))
@@ -103,6 +124,35 @@ print("  %d sites under the default options (SNV %d, DEL %d, INS %d; table of %d
        ", ".join("%s %d" % (ch, letters[ord(ch)]) for ch in "ACGTN-")), flush=True)
 print("  down the link: the records %.1f MB; the site table %.3f MB + 8 bytes; the cons bytes %.1f MB" %
       (32 * W / 1e6, 32 * min(n_sites, SITE_CAP) / 1e6, W / 1e6), flush=True)
+# the variant stage (docs/GACT_SPEC.md, "Pileup variants and VCF") next to the sites call of the same build, in turn, on the same window
+VAR_CAP = 1 << 20
+d_vars = torch.zeros((VAR_CAP, 12), dtype=torch.int32, device="cuda")
+d_n_vars = torch.zeros(1, dtype=torch.int64, device="cuda")
+
+
+def variant_legs(handle, what):
+    ms = alternated([("pileup calls, whole window, sites only (%s)" % what, lambda: check(lib.lrm_pileup_sites_dev(
+                         handle, None, 0, W, d_sites.data_ptr(), SITE_CAP, d_n_sites.data_ptr(), None, stream), "lrm_pileup_sites_dev")),
+                     ("pileup variants, whole window (%s)" % what, lambda: check(lib.lrm_pileup_variants_dev(
+                         handle, None, 0, W, d_vars.data_ptr(), VAR_CAP, d_n_vars.data_ptr(), stream), "lrm_pileup_variants_dev"))])
+    a, b = (float(np.mean(v)) for v in ms.values())
+    n_vars = int(d_n_vars.cpu()[0])
+    vk = d_vars[:min(n_vars, VAR_CAP), 7].cpu().numpy().view(np.uint32) & 0xFF
+    print("  variants / sites: %.3f ms / %.3f ms per launch = %.3f; %d records (DEL %d, SNV %d, INS %d) from %d sites; the table %.3f MB" %
+          (b, a, b / a, n_vars, int((vk == 2).sum()), int((vk == 1).sum()), int((vk == 4).sum()), int(d_n_sites.cpu()[0]), 48 * min(n_vars, VAR_CAP) / 1e6), flush=True)
+
+
+variant_legs(dm.pileup, "plain accumulator")
+if os.environ.get("PROBE_UNTIL") == "variants":                # the call and variant stages only: one more K = 8 accumulator, then the end
+    acc8 = C.c_void_p()
+    check(lib.lrm_pileup_create_ins(C.byref(acc8), di.handle, window[0], window[1], 8), "lrm_pileup_create_ins")
+    check(lib.lrm_pileup_add_dev(acc8, d_reads.data_ptr(), d_reads.stride(0), d_lens.data_ptr(), dm.store.data_ptr(), dm.store_stride, dm.n_ops.data_ptr(),
+                                 dm.score.data_ptr(), dm.meta_r.data_ptr(), dm.meta.data_ptr(), n, None, 0, stream), "lrm_pileup_add_dev")
+    variant_legs(acc8, "K = 8 accumulator")
+    lib.lrm_pileup_free(acc8)
+    dm.close()
+    di.close()
+    sys.exit(0)
 timed("aln_diff_kernel", lambda: check(lib.lrm_aln_diff_dev(
     di.handle, dm.store.data_ptr(), dm.store_stride, dm.n_ops.data_ptr(), dm.score.data_ptr(), dm.meta_r.data_ptr(), dm.meta.data_ptr(), n,
     dm.diff_off.data_ptr(), total, dm.diff_events.data_ptr(), stream), "lrm_aln_diff_dev"))
@@ -121,25 +171,6 @@ def add_to(library, handle):
     return lambda: check(library.lrm_pileup_add_dev(
         handle, d_reads.data_ptr(), d_reads.stride(0), d_lens.data_ptr(), dm.store.data_ptr(), dm.store_stride, dm.n_ops.data_ptr(),
         dm.score.data_ptr(), dm.meta_r.data_ptr(), dm.meta.data_ptr(), n, None, 0, stream), "lrm_pileup_add_dev")
-
-
-def alternated(legs):
-    """legs: [(name, call)], launched in turn REPEATS times after one warm-up each -> {name: [ms]}"""
-    for _, call in legs:
-        call()
-    torch.cuda.synchronize()
-    ms = {name: [] for name, _ in legs}
-    for rep in range(REPEATS):
-        for name, call in legs:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            call()
-            e1.record()
-            torch.cuda.synchronize()
-            ms[name].append(e0.elapsed_time(e1))
-    for name, _ in legs:
-        print("  %s: %.3f ms per Gbp (min %.3f, max %.3f; alternated)" % (name, np.mean(ms[name]) / gbp, min(ms[name]) / gbp, max(ms[name]) / gbp), flush=True)
-    return ms
 
 
 def accumulator(library, ins_cols=None):
@@ -188,6 +219,7 @@ for ins_cols in (4, 8):
                         acc, None, 0, W, d_seq.data_ptr(), d_seq.numel(), d_len.data_ptr(), stream), "lrm_pileup_polish_dev")),
                     ("pileup polish, whole window (plain accumulator)", lambda: check(lib.lrm_pileup_polish_dev(
                         dm.pileup, None, 0, W, d_seq.data_ptr(), d_seq.numel(), d_len.data_ptr(), stream), "lrm_pileup_polish_dev"))])
+        variant_legs(acc, "K = 8 accumulator")
         check(lib.lrm_pileup_polish_dev(acc, None, 0, W, d_seq.data_ptr(), d_seq.numel(), d_len.data_ptr(), stream), "lrm_pileup_polish_dev")
         n_sites8 = int(d_n_sites.cpu()[0])
         print("  polished length %d of %d positions; %d sites" % (int(d_len.cpu()[0]), W, n_sites8), flush=True)
