@@ -226,7 +226,7 @@ static int sd_build(lrm_index *idx, const SdPlan &pl) {
     if (ovf_cap > (1ull << 30)) ovf_cap = 1ull << 30;
     if (idx->itune.sd_bits) ovf_cap = (uint64_t) pl.f * L + 4096;                 // (tests force crowded lines)
     why = "no room for the table";
-    if (hipMalloc(&d, pl.bytes) != hipSuccess) { d = nullptr; return give_up(); }
+    if (hipMalloc(&d, pl.bytes + LRM_SD_TAIL) != hipSuccess) { d = nullptr; return give_up(); }     // (+ the line of zeros, lrm_internal.h)
     why = "no room for the overflow list";
     if (hipMalloc(&ovf, ovf_cap * 16) != hipSuccess) { ovf = nullptr; return give_up(); }
     if (hipMalloc(&n_ovf, 8) != hipSuccess) { n_ovf = nullptr; return give_up(); }
@@ -234,7 +234,7 @@ static int sd_build(lrm_index *idx, const SdPlan &pl) {
     if (hipMalloc(&claimed, cl_bytes) != hipSuccess) { claimed = nullptr; return give_up(); }
     why = "memset failed";
     if (hipMemset(claimed, 0, cl_bytes) != hipSuccess) return give_up();
-    hipLaunchKernelGGL(sd_clear_kernel, dim3(256 * 64), dim3(256), 0, 0, reinterpret_cast<ulonglong2 *>(d), pl.bytes / 16);     // (128 GiB: not a hipMemset)
+    hipLaunchKernelGGL(sd_clear_kernel, dim3(256 * 64), dim3(256), 0, 0, reinterpret_cast<ulonglong2 *>(d), (pl.bytes + LRM_SD_TAIL) / 16);     // (128 GiB: not a hipMemset)
     if (hipGetLastError() != hipSuccess || hipMemset(n_ovf, 0, 8) != hipSuccess) return give_up();
     LrmIndexView sdv = idx->view;
     sdv.sd_len = idx->itune.sd_len; sdv.sd_f = pl.f; sdv.sd_bits = pl.bits; sdv.sd_kbits = pl.kbits; sdv.sd_slot = pl.slot; sdv.sd_cbits = pl.cbits;

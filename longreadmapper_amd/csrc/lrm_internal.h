@@ -106,6 +106,12 @@ struct LrmIndexView {
 static inline bool lrm_sd48_form(const LrmIndexView &v) {
     return v.sd && v.sd_f == 4 && v.sd_slot == 8 && 8 + 2 * (v.sd_len - 3) - v.sd_bits <= 32;
 }
+// The table ends in one more line, LRM_SD_TAIL bytes of zeros (sd_build): the line that seed_search fetches for a quad whose
+// bitmap bit is clear.  While the table AND that line lie below 2^32 bytes -- (2^sd_bits + 1) * 64 <= 2^32, so at most 2^25
+// lines, a table of 2 GiB -- a line is addressed as the table's base plus a 32-bit byte offset (seed_search's OFF32 form);
+// a longer table keeps 64-bit line addresses.
+#define LRM_SD_TAIL 64
+static inline bool lrm_sd_off32(const LrmIndexView &v) { return v.sd_bits <= 25; }
 
 // ---- resolved choices of a handle ------------------------------------------------------------------------------
 // Options come from the caller (lrm_index_options / lrm_map_options); LRM_* environment variables are tuning

@@ -88,6 +88,9 @@ __device__ __forceinline__ bool sd_side_lookup(const LrmIndexView &ix, uint64_t 
 // `e = match ? slot : e`: an empty slot can only "match" a tag of zero, a real entry before it overrides it, and e == 0 in
 // the end means "not there".  The tag sits in the top bits of a slot: 32-bit compares on the high dword (8-byte slots, tags
 // of <= 32 bits) or on the third halfword (6-byte slots, tags of <= 16 bits: the 2^31-line table of a GRCh38-sized text).
+// sd_answer: what the slot found (e, 0 for none) and the line's overflow mark say -- 0: absent (rr = 0); 1: k, c set; 2: take
+// the other tables.  The second half of sd_search; seed_search's loop behind the bitmap finds e in its own way.
+__device__ __forceinline__ int sd_answer(const LrmIndexView &ix, uint64_t code, uint64_t e, bool ovf, uint64_t &k, uint64_t &c, uint32_t *cnt);
 __device__ __forceinline__ int sd_search(const LrmIndexView &ix, const SdKey &key, uint64_t code, const uint64_t (&W)[8],
                                          uint64_t &k, uint64_t &c, uint32_t *cnt) {
     uint64_t e = 0;
@@ -141,6 +144,9 @@ __device__ __forceinline__ int sd_search(const LrmIndexView &ix, const SdKey &ke
         // the text does not hold (most seeds of a noisy read) goes on to the side table only when its filter bit is set
         ovf = (D[15] & 0xFFu) > 10u && ((D[15] >> (8u + sd_filter_bit((uint32_t) key.tag))) & 1u);
     }
+    return sd_answer(ix, code, e, ovf, k, c, cnt);
+}
+__device__ __forceinline__ int sd_answer(const LrmIndexView &ix, uint64_t code, uint64_t e, bool ovf, uint64_t &k, uint64_t &c, uint32_t *cnt) {
     const uint64_t cmax = (1ull << ix.sd_cbits) - 1ull;
     if (e != 0) {
         k = e & ((1ull << ix.sd_kbits) - 1ull);

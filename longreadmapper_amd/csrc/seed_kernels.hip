@@ -100,6 +100,53 @@ __device__ __forceinline__ void sd_issue_filtered(const LrmIndexView &ix, const 
     a = *reinterpret_cast<const ulonglong2 *>(src + (lane & 3u) * 2);
     b = a;
 }
+// The same two steps for a table that ends below 2^32 bytes (lrm_sd_off32), where a line index is ONE register: one DPP
+// move, 32-bit shifts, and the fetch addressed as the table's base (scalar) plus a 32-bit byte offset.  A quad whose bit is
+// clear fetches the line of zeros at the table's own end (LRM_SD_TAIL): one select between two offsets in registers, no
+// second base address.  line is the quad's line, kept from the first step for the second; piece and zpiece are the byte
+// offsets of the lane's 16 bytes inside a line and inside the line of zeros, both the same in every step.  A position past
+// the end comes with key.line == 0, so its bit index is 0 with no select.  (Per position 9 vector instructions where the
+// 64-bit form above has 22, profiles/r20, section 1.)
+__device__ __forceinline__ uint32_t sd_filter_issue32(const LrmIndexView &ix, const SdKey &key, uint32_t &bit, uint32_t &line) {
+    line = (uint32_t) __builtin_amdgcn_update_dpp(0, (int) (uint32_t) key.line, 0x00, 0xf, 0xf, true);      // quad_perm [0,0,0,0]
+    bit = line >> (uint32_t) ix.sd_filt_shift;
+    return ix.sd_filt[bit >> 5];
+}
+__device__ __forceinline__ void sd_issue_filtered32(const LrmIndexView &ix, bool real, uint32_t word, uint32_t bit, uint32_t line,
+                                                    uint32_t piece, uint32_t zpiece, ulonglong2 &a, ulonglong2 &b) {
+    const bool pass = real && ((word >> (bit & 31u)) & 1u);
+    const uint32_t off = pass ? (line << 6) + piece : zpiece;
+    a = *reinterpret_cast<const ulonglong2 *>(reinterpret_cast<const char *>(ix.sd) + off);
+    b = a;
+}
+// The gather and the search of sd_finish_shared / sd_search in one, for the loop behind the bitmap (four positions per line,
+// 8-byte slots, tags of at most 32 bits), slot by slot from the last to the first as there.  The tag compare is
+// `x = hi ^ (tag << sh)`, `x < 2^sh`: x is zero above the slot's count exactly where the tags agree and IS the slot's high
+// dword below the tag, so the one value serves the compare and the select, and the DPP move of a high dword -- one use, and
+// that use next to it -- folds into the xor: five vector instructions per slot where gather-then-search has six.  The chain
+// of high dwords starts at `tag << sh`, which the last xor turns into 0, "no slot".  (2^sh sits in a scalar register behind
+// an empty asm: where the compiler can see the power of two it turns the compare back into a shift and a compare.)
+template <int CTRL>
+__device__ __forceinline__ void sd_slot32(uint64_t w, uint32_t tsh, uint32_t lim, uint32_t &elo, uint32_t &ex, uint32_t &x, uint32_t &lo) {
+    x = (uint32_t) __builtin_amdgcn_update_dpp(0, (int) (uint32_t) (w >> 32), CTRL, 0xf, 0xf, true) ^ tsh;
+    lo = (uint32_t) __builtin_amdgcn_update_dpp(0, (int) (uint32_t) w, CTRL, 0xf, 0xf, true);
+    const bool m = x < lim;
+    elo = m ? lo : elo;
+    ex = m ? x : ex;
+}
+__device__ __forceinline__ int sd_finish_quad32(const LrmIndexView &ix, const SdKey &key, uint64_t code, const ulonglong2 &a,
+                                                uint64_t &k, uint64_t &c) {
+    const uint32_t sh = 32u - key.tb, tsh = (uint32_t) key.tag << sh;
+    uint32_t lim = 1u << sh, elo = 0, ex = tsh, x, lo;
+    asm("" : "+s"(lim));
+    sd_slot32<0xFF>(a.y, tsh, lim, elo, ex, x, lo); sd_slot32<0xFF>(a.x, tsh, lim, elo, ex, x, lo);       // slots 7, 6: [3,3,3,3]
+    sd_slot32<0xAA>(a.y, tsh, lim, elo, ex, x, lo); sd_slot32<0xAA>(a.x, tsh, lim, elo, ex, x, lo);       // 5, 4: [2,2,2,2]
+    sd_slot32<0x55>(a.y, tsh, lim, elo, ex, x, lo); sd_slot32<0x55>(a.x, tsh, lim, elo, ex, x, lo);       // 3, 2: [1,1,1,1]
+    sd_slot32<0x00>(a.y, tsh, lim, elo, ex, x, lo); sd_slot32<0x00>(a.x, tsh, lim, elo, ex, x, lo);       // 1, 0: [0,0,0,0]
+    // bit 63 - tb of slot 0, the line's overflow mark: below the tag in the high dword, where x is the slot's own bits
+    const bool ovf = key.tb == 32u ? lo >> 31 : (x >> (sh - 1u)) & 1u;
+    return sd_answer(ix, code, (uint64_t) elo | ((uint64_t) (ex ^ tsh) << 32), ovf, k, c, nullptr);
+}
 __device__ __forceinline__ int sd_finish_shared(const LrmIndexView &ix, const SdKey &key, uint64_t code, const ulonglong2 &a, const ulonglong2 &b,
                                                 uint64_t &k, uint64_t &c, uint32_t *cnt) {
     uint64_t W[8];
@@ -174,9 +221,17 @@ __device__ __forceinline__ void ss_append(uint64_t *s_tot, uint64_t *s_rec, uint
 // idx->view.sd_filt): the kernel sits at the memory system's rate of random lines, and three in four lines of a sparse
 // table (a bacterial-sized text) hold nothing, so a position first reads the bit of its line -- from a bitmap of a few
 // MiB, of whose loads six in ten hit the L2 at the default size -- and fetches the line only when the bit is set: fewer
-// random lines is the one thing that moves this kernel (profiles/r19: 6.24 - 6.44 -> 5.39 - 5.47 ms alone).  The counting build takes the one-fetch loop WITHOUT the bitmap, so seed_table_lookups keeps meaning
-// "lookups that seeds need".  With FILT false nothing of this is compiled in.
-template <int SS_ITEMS, bool COUNT, bool SD48, bool FILT = false>
+// random lines moved this kernel from 6.24 - 6.44 to 5.39 - 5.47 ms alone (profiles/r19), at the price of 0.28 G more vector
+// wave-instructions per launch -- and with fewer lines to wait for, those instructions are now the other limit (see the
+// note on what binds the kernel, below).  The counting build takes the one-fetch loop WITHOUT the bitmap, so
+// seed_table_lookups keeps meaning "lookups that seeds need".  With FILT false nothing of this is compiled in.
+// OFF32 (only together with FILT; the launcher takes it while the table and the line of zeros at its end lie below 2^32
+// bytes, lrm_sd_off32: the bench text's 2^25 lines are the largest such table): the same three-step loop with fewer vector
+// instructions per position -- a line index is one register and a line's address the table's base plus a 32-bit offset
+// (sd_filter_issue32, sd_issue_filtered32), the window is cut from the scalar words with shifts whose counts are the same
+// in every step, and gather and search are one pass over the slots (sd_finish_quad32).  Results are the same bit for bit;
+// the longer tables (up to chr1-sized) keep the FILT loop as it was.  Counts and times: profiles/r20.
+template <int SS_ITEMS, bool COUNT, bool SD48, bool FILT = false, bool OFF32 = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COUNT ? 1 : 6, 8)))
 void seed_search_kernel(LrmIndexView ix, const uint64_t *__restrict__ reads2,
                                                           uint64_t words_per_read,
@@ -210,10 +265,14 @@ void seed_search_kernel(LrmIndexView ix, const uint64_t *__restrict__ reads2,
     // survivors of the table lookup into fewer wavefronts (+8 %), and searching 2 / 4 of the lane's seeds TOGETHER
     // (independent chains per lane, all rank gathers of a step in flight at once: 43.4 / 56.7 ms per step against
     // 29.0 [r2]): a wavefront of one-seed lanes stops as soon as its 64 neighbouring seeds are dead, a wavefront of
-    // interleaved chains runs until its longest chain ends.  What binds the kernel is the memory system's rate of
+    // interleaved chains runs until its longest chain ends.  What bound THAT kernel [r2] was the memory system's rate of
     // random requests (56 G 64-byte L2 misses per second on the small text): neither more resident wavefronts (see
     // SS_ITEMS) nor fewer vector instructions (7.1 -> 5.0 G per Gbp with C[] folded into the occ prefixes and the
-    // scalar window loads: -2.5 %) move it much.  Also measured [r2]: a
+    // scalar window loads: -2.5 %) moved it much.  That no longer holds for vector instructions: behind the seed table
+    // and the bitmap of its lines the kernel alone runs at 92 % of the random-line rate AND at 93 % of the integer issue
+    // rate bench.py assumes (3.09 G wave-instructions in 5.4 ms), and in the three-stream step, where the extension's and
+    // the vote's instructions share the SIMDs with it, a vector instruction here has a measured price: 0.45 ms of the
+    // step per G wave-instructions (profiles/r20, section 0).  Hence the OFF32 form below.  Also measured [r2]: a
     // 2 MiB presence bitmap of the 12-mers in front of the table lookup (57 % of the seeds die on an L2 hit instead of
     // fetching a table line): 27.3 vs 27.5 ms, not kept; non-temporal loads for the one-touch table lines: 31.7 ms.
     // (That bitmap stood in front of ANOTHER kernel: a seed that passed its first lookup went on to about 4.4 dependent
@@ -253,7 +312,8 @@ void seed_search_kernel(LrmIndexView ix, const uint64_t *__restrict__ reads2,
         // position, a multiple of 64, and positions only grow), and the loop leaves at its end only: every lane of the
         // wavefront takes part in every fetch, and the count of fetches in flight is the same on every path, which is what
         // lets the compiler wait for the older of two (a fetch past the last iteration reads line 0 and is never looked at).
-        struct Look { uint64_t code; SdKey key; ulonglong2 a, b; bool have, real; uint32_t word, bit; };
+        const uint32_t lane_rel = tid & 63u;
+        struct Look { uint64_t code; SdKey key; ulonglong2 a, b; bool have, real; uint32_t word, bit, line; };
         auto look = [&](bool real, uint32_t j, uint32_t j0) {
             Look f;
             f.have = real && j < lim;
@@ -262,14 +322,25 @@ void seed_search_kernel(LrmIndexView ix, const uint64_t *__restrict__ reads2,
             if (real) {
                 const uint64_t *wp = words + (j0 >> 5);                                            // wave-uniform address: scalar loads
                 const uint64_t W0 = wp[0], W1 = wp[1], W2 = wp[2];
+                if (OFF32) {
+                    // rel is the lane id (j0 is lane 0's position and a multiple of 64), so the two shift counts are the
+                    // same in every step; and the words are scalars, which a shift takes as they are and a select does
+                    // not: both halves of the wavefront's window are cut and ONE select follows, where selects of the
+                    // words in front of the shifts cost a register copy per scalar (profiles/r20)
+                    const uint32_t sh = (lane_rel & 31u) * 2u;
+                    const uint64_t c0 = (W0 >> sh) | ((W1 << 1) << (63 - sh)), c1 = (W1 >> sh) | ((W2 << 1) << (63 - sh));
+                    f.code = f.have ? (lane_rel < 32u ? c0 : c1) & smask : 0ull;
+                } else {
                 const uint32_t rel = j - j0, sh = (rel & 31u) * 2u;
                 const uint64_t lo = rel < 32u ? W0 : W1, hi = rel < 32u ? W1 : W2;
                 f.code = f.have ? ((lo >> sh) | ((hi << 1) << (63 - sh))) & smask : 0ull;
+                }
                 f.key = sd_key_of(ixs, f.code, j & (uint32_t) (ixs.sd_f - 1));
             }
             if (SD48) __builtin_assume(f.key.tb <= 32u);
             f.real = real;
-            if (FILT) f.word = sd_filter_issue(ixs, f.key, real, f.bit);
+            if (FILT && OFF32) f.word = sd_filter_issue32(ixs, f.key, f.bit, f.line);
+            else if (FILT) f.word = sd_filter_issue(ixs, f.key, real, f.bit);
             else sd_issue_shared(ixs, f.key, f.a, f.b);
             if (SD48) __builtin_amdgcn_sched_barrier(0);          // the fetch leaves BEFORE the search that follows waits for the one before it
             return f;
@@ -278,7 +349,8 @@ void seed_search_kernel(LrmIndexView ix, const uint64_t *__restrict__ reads2,
         uint32_t j0 = (uint32_t) __builtin_amdgcn_readfirstlane((int) (j & ~63u));                  // lane 0's position
         auto take = [&](const Look &f) {
             uint64_t k = 0, l = 0, c = 0, rr;
-            const int st = sd_finish_shared(ixs, f.key, f.code, f.a, f.b, k, c, COUNT ? my_cnt : nullptr);
+            const int st = OFF32 ? sd_finish_quad32(ixs, f.key, f.code, f.a, k, c)
+                                 : sd_finish_shared(ixs, f.key, f.code, f.a, f.b, k, c, COUNT ? my_cnt : nullptr);
             if (f.have) {
                 if (st == 1) rr = c;
                 else if (st == 0) rr = 0;
@@ -302,8 +374,13 @@ void seed_search_kernel(LrmIndexView ix, const uint64_t *__restrict__ reads2,
                 // line of j is waited for and searched.  Loads retire in the order they were issued, and at either wait two
                 // younger ones are out, so both waits are for "all but two".  The words land in two registers and the lines in two
                 // sets that change roles, as above; keys and codes are carried from step to step by moves, which wait for nothing.
+                // (the two offsets of the 32-bit form, pinned in registers before the loop: left to itself the compiler copies
+                //  a scalar into a register in front of every select)
+                uint32_t piece = (tid & 3u) * 16u, zpiece = (64u << ixs.sd_bits) + piece;
+                if (OFF32) asm volatile("" : "+v"(piece), "+v"(zpiece));
                 auto fetch = [&](Look f) {
-                    sd_issue_filtered(ixs, f.key, f.real, f.word, f.bit, f.a, f.b);
+                    if (OFF32) sd_issue_filtered32(ixs, f.real, f.word, f.bit, f.line, piece, zpiece, f.a, f.b);
+                    else sd_issue_filtered(ixs, f.key, f.real, f.word, f.bit, f.a, f.b);
                     __builtin_amdgcn_sched_barrier(0);
                     return f;
                 };
@@ -574,7 +651,9 @@ int lrm_launch_seed(lrm_index *idx, lrm_workspace *ws, const char *d_reads, uint
         const LrmIndexView &v = idx->view;
         const bool sd48 = lrm_sd48_form(v);
         const bool filt = sd48 && v.sd_filt;
+        const bool off32 = filt && lrm_sd_off32(v);               // (the bench text: 2^25 lines)
         auto sk = ws->counting ? seed_search_kernel<2048, true, false>
+                  : off32 ? (ss_items == 1024u ? seed_search_kernel<1024, false, true, true, true> : ss_items == 4096u ? seed_search_kernel<4096, false, true, true, true> : seed_search_kernel<2048, false, true, true, true>)
                   : filt ? (ss_items == 1024u ? seed_search_kernel<1024, false, true, true> : ss_items == 4096u ? seed_search_kernel<4096, false, true, true> : seed_search_kernel<2048, false, true, true>)
                   : sd48 ? (ss_items == 1024u ? seed_search_kernel<1024, false, true> : ss_items == 4096u ? seed_search_kernel<4096, false, true> : seed_search_kernel<2048, false, true>)
                          : (ss_items == 1024u ? seed_search_kernel<1024, false, false> : ss_items == 4096u ? seed_search_kernel<4096, false, false> : seed_search_kernel<2048, false, false>);
